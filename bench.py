@@ -240,6 +240,82 @@ def measure_copy_bandwidth(dev, nbytes=1 << 30, reps=10):
     return 2.0 * nbytes / 1e9 / sec
 
 
+# ------------------------------------------------------------------ inputs and outputs of the timed path
+def synthetic_batch(frames, distinct, first, width, height, world=1):
+    """Left and right uint8 batches [frames, height, width], the ones TrackingPipeline.set_synthetic(distinct, first) makes:
+    `distinct` seeded pairs (synth.frame) tiled over the batch. A pair is a Python loop over ~2300 rectangles (0.2 s on one
+    core at 1280x720), so the pairs are made by worker processes, started fresh (not forked from this one): at most 16 of
+    them (a one-GPU box's CPU share), split between the ranks of the host. Called before this process touches the GPU."""
+    n = min(distinct, frames)
+    jobs = [(first + i, width, height, True) for i in range(n)]
+    try:
+        ncores = len(os.sched_getaffinity(0))
+    except AttributeError:
+        ncores = os.cpu_count() or 1
+    workers = min(max(1, min(ncores, 16) // max(world, 1)), n)
+    if workers > 1:
+        import multiprocessing as mp
+        with mp.get_context("spawn").Pool(workers) as pool:
+            pairs = pool.starmap(synth.frame, jobs)
+    else:
+        pairs = [synth.frame(*j) for j in jobs]
+    L = np.stack([pairs[i % n][0] for i in range(frames)])
+    R = np.stack([pairs[i % n][1] for i in range(frames)])
+    return L, R
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(pipe, out_dir, max_sample=32, seed=0):
+    """--dump-outputs: what the last step computed -- the records TrackingPipeline.step() hands on and the local-BA results --
+    as out_dir/<name>.npy (float32, or float64 for counts and statistics). Per-frame arrays are written whole; the per-keypoint
+    records and the BA points are written for a fixed sample of frames (`sample_frames.npy`, drawn with `seed`, no larger than
+    `max_sample` and than what fits in DUMP_BYTES). Rows past a frame's count are zeroed: they hold no result."""
+    from trackingbench_slam_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    pipe.drain()
+    if pipe.Tout.is_cuda:
+        torch.cuda.synchronize(pipe.Tout.device)
+    F, cap = pipe.F, pipe.kp_cap
+    host = lambda t: t.cpu().numpy()                                       # noqa: E731
+    bas = [b for b, _, _ in pipe.bas]
+    out = {"pose_Tcw": host(pipe.Tout).reshape(F, 4, 4).astype(np.float32),
+           "pose_inliers": host(pipe.n_inliers).astype(np.float64),
+           "pose_stats": host(pipe.pose_stats).astype(np.float64),
+           "keypoint_counts": host(pipe.trk_counts).astype(np.float64),
+           "match_counts": host(pipe.match_counts).astype(np.float64),
+           "obs_counts": host(pipe.obs_counts).astype(np.float64)}
+    if bas:
+        out["ba_poses"] = np.concatenate([host(b.poses) for b in bas]).reshape(F, bas[0].nkf, 4, 4).astype(np.float32)
+        out["ba_stats"] = np.concatenate([host(b.stats) for b in bas]).astype(np.float64)
+    npt = bas[0].npt if bas else 0
+    per_frame = 4 * (cap * (7 + 32 + 4 + 1) + 3 * npt)                  # float32 bytes of one sampled frame
+    fixed = sum(a.nbytes for a in out.values()) + 8 * max_sample
+    S = int(min(max_sample, F, max((DUMP_BYTES - fixed) // per_frame, 1)))
+    sample = np.sort(np.random.default_rng(seed).choice(F, size=S, replace=False))
+    sel = torch.from_numpy(sample).to(pipe.Tout.device)
+    out["sample_frames"] = sample.astype(np.float64)
+
+    def rows(t, counts):                                                  # [S, cap, ...] with rows >= count zeroed
+        a = host(t.index_select(0, sel))
+        live = np.arange(a.shape[1])[None, :] < host(counts.index_select(0, sel))[:, None]
+        return np.where(live.reshape(live.shape + (1,) * (a.ndim - 2)), a, np.zeros((), a.dtype))   # a select: bits kept
+
+    kp = rows(pipe.trk_kps, pipe.trk_counts).view(capi.KEYPOINT).reshape(S, cap)
+    out["keypoints"] = np.stack([kp[f].astype(np.float32) for f in capi.KEYPOINT.names], -1)
+    out["descriptors"] = rows(pipe.trk_desc, pipe.trk_counts).astype(np.float32)
+    m = np.ascontiguousarray(rows(pipe.matches, pipe.match_counts)).view(capi.MATCH).reshape(S, cap)
+    out["matches"] = np.stack([m[f].astype(np.float32) for f in capi.MATCH.names], -1)
+    out["pose_outliers"] = rows(pipe.outlier, pipe.obs_counts).astype(np.float32)
+    if bas:
+        pts = torch.cat([b.pts for b in bas])
+        out["ba_points"] = host(pts.index_select(0, sel.to(pts.device))).astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------ launcher (python bench.py --gpus N, WORLD_SIZE unset)
 def _free_port():
     s = socket.socket()
@@ -330,14 +406,14 @@ def parse_args(argv=None):
     ap.add_argument("--ba-pts", type=int, default=5000)
     ap.add_argument("--ba-iters", type=int, default=10)
     ap.add_argument("--no-ba", action="store_true", help="diagnostic only: drop the local-BA stage")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--region-events", choices=("auto", "dominant", "on", "off"), default="auto",
-                    help="HIP events inside the timed region: 'dominant' times the roofline's kernel only (k_ba_schur, 30 launches "
+                    help="--full only (a plain run records no events): HIP events inside the timed region: 'dominant' times the roofline's kernel only (k_ba_schur, 30 launches "
                          "per step), 'on' every kernel (~400 launches per step: two event records each cost ~2 %% of the step), "
                          "'off' none. auto: dominant above 64 frames per GPU; below, off (the event records are a third of a "
                          "~5 us kernel and keep the local-BA call from replaying its HIP graph). The per-kernel tables "
                          "come from the isolated passes right after the region either way")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: length of the CPU baseline")
     ap.add_argument("--ba-split", type=int, default=0,
                     help="partitions of the BA windows, one stream + host thread each (0 = by batch size: 1 up to 64 frames, else 3)")
     ap.add_argument("--ba-lag", action="store_true",
@@ -349,6 +425,15 @@ def parse_args(argv=None):
     ap.add_argument("--exchange", choices=("packed", "padded"), default="packed",
                     help="the track gather at the end of a batch (N > 1): packed = live rows only, sized by the largest rank of "
                          "the batch (counts first, then one gather per record); padded = whole capacity-sized record tensors")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP events inside the timed region (--region-events), the "
+                         "measured copy bandwidth, isolated per-kernel passes, the roofline and the CPU baseline. A plain run "
+                         "only sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's batch) as DIR/<name>.npy, float32 / "
+                         "float64, 64 MB at most: per-frame poses and counts, the keypoint / descriptor / match records of a "
+                         "fixed seeded sample of frames, the local-BA poses and statistics of every window and the points of "
+                         "the sampled windows")
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)   # gloo: CPU test of the launcher / exchange
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # StubPipeline, no GPU: not a measurement
     return ap.parse_args(argv)
@@ -358,6 +443,9 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         print("error: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1:
+        print("error: --steps must be >= 1", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start the ranks ourselves, as a child, before any GPU call in this process
@@ -374,12 +462,15 @@ def main(argv=None):
 
     if gpu:
         from trackingbench_slam_amd.pipeline import TrackingPipeline
+        # the frames TrackingPipeline.set_synthetic() would make, generated before this process touches the GPU
+        L, R = synthetic_batch(args.frames, args.distinct, rank * args.frames, args.width, args.height, world)
         torch.cuda.set_device(dev)
         pipe = TrackingPipeline(args.width, args.height, args.levels, args.scale, args.target, args.init_th, args.min_th,
                                 frames=args.frames, device=dev, with_ba=not args.no_ba, ba_kf=args.ba_kf, ba_pts=args.ba_pts,
                                 ba_iters=args.ba_iters, seed=rank, ba_split=args.ba_split or (1 if args.frames <= 64 else 3),
                                 ba_distinct=args.ba_distinct, ba_lag=args.ba_lag)
-        pipe.set_synthetic(distinct=args.distinct, first=rank * args.frames)
+        pipe.set_stereo_frames(L, R)
+        del L, R
     else:
         pipe = StubPipeline(args.frames, rank)
 
@@ -431,6 +522,8 @@ def main(argv=None):
         one_step()
     fence()
     mode = args.region_events if args.region_events != "auto" else ("dominant" if args.frames > 64 else "off")
+    if not args.full:
+        mode = "off"         # the headline figure needs no events: a plain run times the steps alone
     if mode == "dominant" and args.no_ba:
         mode = "on"          # without the BA stage the roofline's kernel is an extractor kernel: time them all
     region_events = gpu and mode != "off"
@@ -478,7 +571,9 @@ def main(argv=None):
 
     out = None
     if rank == 0:
-        out = report(args, pipe, prof, el, world, n_joined, dev)
+        if args.dump_outputs:    # before report(): its isolated passes run the chains again
+            dump_outputs(pipe, args.dump_outputs)
+        out = report(args, pipe, prof, el, world, n_joined, dev) if args.full else headline(args, pipe, el, world, n_joined)
         if world > 1:
             per_rank = state["xbytes"] // max(state["xsteps"], 1)
             out["config"]["exchange"] = {"mode": args.exchange if not state["sync_only"] else "in line (padded)",
@@ -660,8 +755,18 @@ def report(args, pipe, prof, el, world, n_joined, dev):
                                     "achieved": round(per_launch / 1e9 / (iso[name] / 1e3), 2),
                                     "frac": round(per_launch / 1e9 / (iso[name] / 1e3) / HBM_PEAK_GBS, 5)}
 
+    out = headline(args, pipe, el, world, n_joined)
+    out["roofline"] = roofline
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
+    return out
+
+
+def headline(args, pipe, el, world, n_joined):
+    """The result line of a plain run: the figure over the timed steps and the configuration it was taken at."""
     frames_total = args.frames * world * args.steps
-    out = {
+    ms_per_step = 1e3 * el / args.steps
+    return {
         "metric": "frames/sec end-to-end (extract+match+local-BA)", "value": round(frames_total / el, 2),
         "unit": "frames/s", "n_gpus": n_joined, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
@@ -682,11 +787,7 @@ def report(args, pipe, prof, el, world, n_joined, dev):
                                    "batch behind tracking); every batch's windows are complete inside the timed region"
                                    if getattr(pipe, "ba_lag", False) else "joined at the end of every step"),
                    "parallelism": "frames sharded x%d, RCCL gather of tracks" % world},
-        "roofline": roofline,
     }
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
-    return out
 
 
 if __name__ == "__main__":

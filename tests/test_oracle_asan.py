@@ -17,7 +17,8 @@ def test_oracle_under_asan_ubsan():
         pytest.skip("libasan.so not found")
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "liboracle_asan.so"], stdout=subprocess.DEVNULL)
     env = dict(os.environ)
-    env.update(ORACLE_LIB="liboracle_asan.so", LD_PRELOAD=asan,
+    # libasan first (it must come first in the initial library list); whatever the environment preloads already stays
+    env.update(ORACLE_LIB="liboracle_asan.so", LD_PRELOAD=" ".join(p for p in (asan, env.get("LD_PRELOAD", "")) if p),
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
                         os.path.join(ROOT, "tests", "test_oracle_stages.py"), os.path.join(ROOT, "tests", "test_oracle_golden.py"),
