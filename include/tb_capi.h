@@ -375,6 +375,54 @@ int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf,
                           float* pts, const tb_ba_obs* obs, const int32_t* obs_counts, int obs_pitch, int iters,
                           double* stats);
 
+/* ---------------------------------------------------------------- device-resident stereo VO loop
+ * The tracking loop of the reference's main program, test/test_vo.cpp test_kitti (:674-850), for nseq independent stereo
+ * sequences in lock-step: one tb_vo_step_dev = frame t of every sequence, chained on the context's stream from the batched
+ * operators above. Frame t of a sequence:
+ *   pose      t = 0: the pose given to tb_vo_reset_dev (:694-697); t > 0: the last frame's Tcw (:688)
+ *   tracking  t > 0: searchByOPFlow(cur, last, pts, equalized = 1, reject = 1) (:716): LK from the last frame's raw left image
+ *             into the current one's CLAHE image; the new key list = all n tracked points, lost ones included (:717-724); key i
+ *             carries the last frame's map point i when its status is set (:731-737); PoseOptimization (:761) on one row per
+ *             key with a map point (px = tracked point, invSigma2 = 1, Xw = map point), outlier flags cleared; fewer than 3 rows
+ *             leave the pose as it is and n_inliers = 0 (LocalBA.cpp:401)
+ *   keyframe  t % keyframe_every == 0, after the pose optimisation (:772-832): ORB operator()(5-level pyramid, target, init_th,
+ *             min_th) on the left image; SetKeys(orb keys), whose mvpMapPoints.resize(m, nullptr) (Frame.cpp:114) KEEPS the
+ *             map points of entries [0, min(n, m)) and nulls [n, m); AddMapPointsByStereo(cur, right, bf, fx) (:800); every key
+ *             j with depth > 0 gets a new map point R * norm * depth + t (R, t of Twc at the optimised pose; norm from
+ *             u = (int)x, v = (int)y in double). Deviation: a depth that is not finite (zero disparity) creates no point.
+ * Dropped: SetBow (its output is unused), the viewer, imshow and the printing. Local BA is not part of the loop (the
+ * reference's map_ptr->AddKeyFrame is commented out, :839).
+ * State lives in the object (ping-pong key / map-point buffers, a copy of the last left image); after the first step a step
+ * makes no host synchronisation and no host <-> device copy. Key capacity = the extractor's kp_capacity. The object uses its
+ * context's stream and must be destroyed before its context. */
+typedef struct tb_vo tb_vo;
+typedef struct tb_vo_params {
+    int width, height;
+    int nlevels;            /* ORB pyramid levels (reference: 5) */
+    float scale;            /* pyramid scale step (0.8) */
+    int target;             /* ORB keys per keyframe (2000) */
+    float init_th, min_th;  /* FAST thresholds (80, 30) */
+    double K[4];            /* fx, fy, cx, cy */
+    float bf;               /* AddMapPointsByStereo's bf = baseline * fx (0.573 * 718.856) */
+    int keyframe_every;     /* keyframe period (10) */
+} tb_vo_params;
+int tb_vo_create(tb_ctx* ctx, const tb_vo_params* params, int nseq, tb_vo** out);
+void tb_vo_destroy(tb_vo* vo);
+/* Tcw0: device, [nseq][16] row-major; the next step is frame 0. Asynchronous. */
+int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0);
+/* left / right: nseq device images each, row stride `stride` bytes, `pitch` bytes apart (read during the call's kernels; they
+ * may be reused once the stream has passed them). right may be NULL on a step that is not a keyframe (TB_EINVAL on one that
+ * is). TB_ESTATE before the first reset. Asynchronous on the context's stream. */
+int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch);
+/* Device views of the state after the last step (valid until the next step; every output nullable):
+ * Tcw [nseq][16]; keys_xy [nseq][key_pitch][2] float; map_points [nseq][key_pitch][3] float and mp_valid [nseq][key_pitch]
+ * bytes (entry j belongs to key j); key_counts [nseq]; obs [nseq][key_pitch] tb_obs rows and obs_counts [nseq] of the step's
+ * pose optimisation (0 at frame 0); n_inliers [nseq]; outlier [nseq][key_pitch] flags of those rows. *frame = index of the
+ * last frame stepped (-1 before any). */
+int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const float** map_points, const uint8_t** mp_valid,
+                    const int32_t** key_counts, const tb_obs** obs, const int32_t** obs_counts, const int32_t** n_inliers,
+                    const uint8_t** outlier, int* key_pitch, int* frame);
+
 /* ---- multi-GPU batch entry (SURVEY.md section 8(b) `tb_batch_run`, 8(e): frames are independent units through
  * extract -> left/right match, sharded as contiguous blocks of frames, one exchange step at the end).
  * The in-process counterpart of trackingbench_slam_amd/dist.py for a C++ host that holds one context per GPU:

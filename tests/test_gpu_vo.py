@@ -1,0 +1,194 @@
+"""GPU tests of the device-resident stereo VO loop (trackingbench_slam_amd.vo.StereoVO, tb_vo_* of the C ABI) against the CPU
+composition in tests/vo_reference.py, on synthetic KITTI-geometry sequences (1241 x 376) with exact ground truth."""
+import numpy as np
+import pytest
+import torch
+
+from trackingbench_slam_amd import capi, synth_seq
+from trackingbench_slam_amd.vo import StereoVO
+
+import vo_reference as vr
+
+pytestmark = pytest.mark.gpu
+
+W, H = 1241, 376
+T = 21
+SEEDS = (0, 1, 2, 3)
+GT_BOUND = 0.25   # metres at frame 20; tests/test_vo_reference.py measures the composition against it
+
+
+@pytest.fixture(scope="module")
+def seqs():
+    out = [synth_seq.sequence(s, T) for s in SEEDS]
+    L = np.stack([o[0] for o in out], 1)   # [T, S, H, W]
+    R = np.stack([o[1] for o in out], 1)
+    G = np.stack([o[2] for o in out], 1)   # [T, S, 4, 4]
+    return L, R, G
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _gpu_state(vo):
+    """The GPU's state after the last step as one vo_reference state per sequence (keys / map points cut at the key count)."""
+    xy, kc = vo.keys()
+    mp, mv = vo.map_points()
+    Tcw = vo.Tcw().cpu().numpy()
+    xy, kc, mp, mv = xy.cpu().numpy(), kc.cpu().numpy(), mp.cpu().numpy(), mv.cpu().numpy()
+    return [dict(t=vo.frame + 1, Tcw=Tcw[s], keys=xy[s, :kc[s]].copy(), mp=mp[s, :kc[s]].copy(), valid=mv[s, :kc[s]].astype(bool),
+                 last_img=None) for s in range(vo.S)]
+
+
+def _same_bits(a, b):
+    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def _step_parity(seqs, nframes, keyframe_every):
+    L, R, G = seqs
+    S = L.shape[1]
+    P = vr.Params(keyframe_every=keyframe_every)
+    vo = StereoVO(S, keyframe_every=keyframe_every)
+    try:
+        vo.reset(G[0])
+        prev = [vr.initial_state(G[0, s]) for s in range(S)]
+        for t in range(nframes):
+            kf = t % keyframe_every == 0
+            vo.step(_dev(L[t]), _dev(R[t]) if kf else None)
+            got = _gpu_state(vo)
+            obs, oc = vo.obs()
+            obs, oc = obs.cpu().numpy(), oc.cpu().numpy()
+            ninl, outl = vo.n_inliers().cpu().numpy(), vo.outlier().cpu().numpy()
+            for s in range(S):
+                cpu_in = dict(prev[s], last_img=L[t - 1, s] if t else None)
+                exp, info = vr.step(cpu_in, L[t, s], R[t, s], P, spawn_Tcw=got[s]["Tcw"])
+                g = got[s]
+                where = "frame %d seq %d" % (t, s)
+                assert _same_bits(g["keys"], exp["keys"]), where
+                assert np.array_equal(g["valid"], exp["valid"]), where
+                assert _same_bits(g["mp"][exp["valid"]], exp["mp"][exp["valid"]]), where
+                n = len(info["obs"])
+                assert oc[s] == n, where
+                rows = np.stack([info["obs"][k] for k in ("u", "v", "X", "Y", "Z", "inv_sigma2")], -1) if n else np.zeros((0, 6), np.float32)
+                assert _same_bits(obs[s, :n], rows), where
+                assert ninl[s] == info["n_inliers"], where
+                assert np.array_equal(outl[s, :n], info["outlier"][:n]), where
+                assert np.allclose(g["Tcw"], exp["Tcw"], rtol=1e-6, atol=1e-6), where
+                if t:
+                    assert n >= 3, where   # the synthetic sequences always track
+            prev = got
+    finally:
+        vo.close()
+
+
+def test_step_parity_21_frames(seqs):
+    _step_parity(seqs, T, 10)
+
+
+def test_step_parity_keyframe_every_3(seqs):
+    _step_parity(seqs, 7, 3)
+
+
+def test_free_run_matches_cpu_and_ground_truth(seqs):
+    L, R, G = seqs
+    S = L.shape[1]
+    P = vr.Params()
+    vo = StereoVO(S)
+    try:
+        vo.reset(G[0])
+        traj = []
+        for t in range(T):
+            vo.step(_dev(L[t]), _dev(R[t]) if t % 10 == 0 else None)
+            traj.append(vo.Tcw().cpu().numpy())
+    finally:
+        vo.close()
+    for s in range(S):
+        states, _ = vr.run(L[:, s], R[:, s], G[0, s], P)
+        for t in range(T):
+            assert np.allclose(traj[t][s], states[t]["Tcw"], rtol=1e-4, atol=1e-4), (s, t)
+        assert vr.translation_error(traj[T - 1][s], G[T - 1, s]) < GT_BOUND, s
+        assert vr.translation_error(states[T - 1]["Tcw"], G[T - 1, s]) < GT_BOUND, s
+
+
+def _run_all(vo, L, R, G, nframes, every):
+    vo.reset(G[0])
+    out = []
+    for t in range(nframes):
+        vo.step(_dev(L[t]), _dev(R[t]) if t % every == 0 else None)
+        xy, kc = vo.keys()
+        mp, mv = vo.map_points()
+        o, oc = vo.obs()
+        out.append([x.cpu().numpy() for x in (vo.Tcw(), xy, kc, mp, mv, o, oc, vo.n_inliers(), vo.outlier())])
+    return out
+
+
+def test_batch_independence(seqs):
+    L, R, G = seqs
+    S = L.shape[1]
+    n = 12
+    vo = StereoVO(S)
+    try:
+        together = _run_all(vo, L, R, G, n, 10)
+    finally:
+        vo.close()
+    for s in range(S):
+        one = StereoVO(1)
+        try:
+            alone = _run_all(one, L[:, s:s + 1], R[:, s:s + 1], G[:, s:s + 1], n, 10)
+        finally:
+            one.close()
+        for t in range(n):
+            tg, xy, kc, mp, mv, o, oc, ni, ol = together[t]
+            a_tg, a_xy, a_kc, a_mp, a_mv, a_o, a_oc, a_ni, a_ol = alone[t]
+            k = kc[s]
+            assert k == a_kc[0] and oc[s] == a_oc[0] and ni[s] == a_ni[0], (s, t)
+            assert _same_bits(tg[s], a_tg[0]) and _same_bits(xy[s, :k], a_xy[0, :k]), (s, t)
+            assert np.array_equal(mv[s, :k], a_mv[0, :k]) and _same_bits(mp[s, :k][mv[s, :k] > 0], a_mp[0, :k][a_mv[0, :k] > 0]), (s, t)
+            assert _same_bits(o[s, :oc[s]], a_o[0, :oc[s]]) and np.array_equal(ol[s, :oc[s]], a_ol[0, :oc[s]]), (s, t)
+
+
+def test_loss_and_recovery(seqs):
+    """Sequence 0 sees uniform frames at steps 4-6: the keyframe at 5 finds no keys, so steps 6-9 have no observation -- the
+    pose is held, n_inliers is 0 and nothing fails; the keyframe at 10 makes new map points and tracking resumes at 11."""
+    L, R, G = seqs
+    L = L[:, :2].copy(); R = R[:, :2].copy(); G = G[:, :2]
+    L[4:7, 0] = 128; R[4:7, 0] = 128
+    vo = StereoVO(2, keyframe_every=5)
+    try:
+        vo.reset(G[0])
+        poses, ninl, oc = [], [], []
+        for t in range(14):
+            vo.step(_dev(L[t]), _dev(R[t]) if t % 5 == 0 else None)
+            poses.append(vo.Tcw().cpu().numpy()); ninl.append(vo.n_inliers().cpu().numpy()); oc.append(vo.obs()[1].cpu().numpy())
+            assert np.isfinite(poses[-1]).all(), t
+    finally:
+        vo.close()
+    for t in range(6, 10):
+        assert oc[t][0] == 0 and ninl[t][0] == 0, t
+        assert _same_bits(poses[t][0], poses[t - 1][0]), t
+    for t in range(11, 14):
+        assert oc[t][0] >= 100 and ninl[t][0] >= 50, t
+    assert not _same_bits(poses[11][0], poses[10][0])
+    for t in range(1, 14):   # the other sequence is unaffected
+        assert ninl[t][1] >= 50, t
+
+
+def test_argument_checks(seqs):
+    L, R, G = seqs
+    vo = StereoVO(2)
+    try:
+        assert vo.step_rc(_dev(L[0, :2])) == capi.TB_ESTATE          # before reset
+        vo.reset(G[0, :2])
+        assert vo.step_rc(_dev(L[0, :2]), None) == capi.TB_EINVAL    # frame 0 is a keyframe: right images required
+        assert vo.step_rc(_dev(L[0, :2]), _dev(R[0, :2])) == 0
+        assert vo.step_rc(_dev(L[1, :2]), None) == 0                 # not a keyframe: right may be omitted
+    finally:
+        vo.close()
+    for bad in (dict(keyframe_every=0), dict(nlevels=1), dict(target=0), dict(scale=1.5), dict(bf=0.0)):
+        with pytest.raises(capi.TBError) as e:
+            StereoVO(2, **bad)
+        assert e.value.code == capi.TB_EINVAL, bad
+    with pytest.raises(capi.TBError) as e:
+        StereoVO(0)
+    assert e.value.code == capi.TB_EINVAL

@@ -1,0 +1,104 @@
+"""Throughput of the device-resident stereo VO loop (trackingbench_slam_amd.vo.StereoVO) on synthetic stereo sequences.
+
+For every batch size S: S sequences x T frames, rendered once on the host (synth_seq; `--distinct` different sequences,
+repeated to fill the batch) and uploaded before anything is timed, so the steps read device-resident frames. Three passes:
+
+    stats   one untimed run that reads the state after every step: pose observations and inliers per tracking frame,
+            translation drift against the ground truth
+    timed   reset + T steps, HIP events on the loop's stream around every step, one synchronisation at the end
+    prof    the same steps with the library's per-kernel event timing on (tb_profile_*): the per-kernel split
+
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from trackingbench_slam_amd import synth_seq   # noqa: E402
+from trackingbench_slam_amd.vo import StereoVO  # noqa: E402
+
+
+def centre(T):
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return -T[:3, :3].T @ T[:3, 3]
+
+
+def run_size(S, L, R, G, T, every, timed_only=False):
+    D = L.shape[1]
+    rep = lambda a: a[:, np.arange(S) % D]   # noqa: E731
+    dL = torch.from_numpy(np.ascontiguousarray(rep(L))).cuda()
+    dR = torch.from_numpy(np.ascontiguousarray(rep(R))).cuda()
+    Gs = rep(G)
+    vo = StereoVO(S, keyframe_every=every)
+    try:
+        # stats (and the first step, which sizes every buffer)
+        vo.reset(Gs[0])
+        obs, inl, drift = [], [], []
+        for t in range(T):
+            vo.step(dL[t], dR[t] if t % every == 0 else None)
+            if timed_only:
+                continue
+            if t % every:
+                obs.append(vo.obs()[1].cpu().numpy()); inl.append(vo.n_inliers().cpu().numpy())
+            Tcw = vo.Tcw().cpu().numpy()
+            drift.append([float(np.linalg.norm(centre(Tcw[s]) - centre(Gs[t, s]))) for s in range(S)])
+        obs, inl, drift = np.array(obs), np.array(inl), np.array(drift)
+        torch.cuda.synchronize()
+        # timed
+        vo.reset(Gs[0])
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(T)]
+        torch.cuda.synchronize()
+        for t in range(T):
+            ev[t][0].record(vo.stream)
+            vo.step(dL[t], dR[t] if t % every == 0 else None)
+            ev[t][1].record(vo.stream)
+        torch.cuda.synchronize()
+        ms = np.array([a.elapsed_time(b) for a, b in ev])
+        total_ms = ev[0][0].elapsed_time(ev[-1][1])
+        kf = np.array([t % every == 0 for t in range(T)])
+        if timed_only:
+            return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3))
+        # per-kernel split
+        vo.reset(Gs[0])
+        torch.cuda.synchronize()
+        vo.profile_enable(True)
+        for t in range(T):
+            vo.step(dL[t], dR[t] if t % every == 0 else None)
+        rep_ = vo.profile_report()
+        vo.profile_enable(False)
+    finally:
+        vo.close()
+    kern = {k: dict(calls=c, ms=round(m, 4)) for k, (c, m) in sorted(rep_.items(), key=lambda kv: -kv[1][1])}
+    return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3),
+                ms_per_track_step=round(float(ms[~kf].mean()), 4), ms_per_keyframe_step=round(float(ms[kf].mean()), 4),
+                ms_first_keyframe_step=round(float(ms[0]), 4), kernels_ms_over_T_steps=kern,
+                obs_per_frame=dict(mean=round(float(obs.mean()), 1), min=int(obs.min())),
+                inliers_per_frame=dict(mean=round(float(inl.mean()), 1), min=int(inl.min())),
+                drift_m=dict(final_mean=round(float(drift[-1].mean()), 4), final_max=round(float(drift[-1].max()), 4),
+                             all_max=round(float(drift.max()), 4)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="16,64,256")
+    ap.add_argument("--steps", type=int, default=21)
+    ap.add_argument("--distinct", type=int, default=4, help="different synthetic sequences, repeated to fill a batch")
+    ap.add_argument("--keyframe-every", type=int, default=10)
+    ap.add_argument("--timed-only", action="store_true", help="first pass without state reads, then the timed pass only "
+                    "(for a trace of the steps: no host <-> device copy between them)")
+    args = ap.parse_args()
+    T = args.steps
+    seqs = [synth_seq.sequence(s, T) for s in range(args.distinct)]
+    L = np.stack([q[0] for q in seqs], 1); R = np.stack([q[1] for q in seqs], 1); G = np.stack([q[2] for q in seqs], 1)
+    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only) for S in args.sizes.split(",")]
+    print(json.dumps(dict(tool="bench_vo", device=torch.cuda.get_device_name(0), width=1241, height=376,
+                          keyframe_every=args.keyframe_every, distinct_sequences=args.distinct, results=res)))
+
+
+if __name__ == "__main__":
+    main()

@@ -42,7 +42,7 @@ EXPORTS = [
     "tb_bow_transform_batch_dev", "tb_search_by_bow_batch_dev", "tb_pose_opt", "tb_pose_opt_batch_dev", "tb_local_ba", "tb_local_ba_batch_dev",
     "tb_clahe", "tb_clahe_dev", "tb_optical_flow_pyr_lk", "tb_optical_flow_pyr_lk_dev", "tb_optical_flow_pyr_lk_batch_dev", "tb_search_by_opflow", "tb_search_by_opflow_batch_dev",
     "tb_find_fundamental_ransac", "tb_reject_with_f", "tb_reject_with_f_batch_dev", "tb_add_map_points_by_stereo", "tb_add_map_points_by_stereo_batch_dev",
-    "tb_batch_run",
+    "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
 ]
 
 
@@ -83,6 +83,8 @@ def lib():
         L.tb_last_error.argtypes = [C.c_void_p]
         L.tb_destroy.argtypes = [C.c_void_p]
         L.tb_extractor_destroy.argtypes = [C.c_void_p]
+        L.tb_vo_destroy.restype = None
+        L.tb_vo_destroy.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -162,6 +164,52 @@ def batch_run(contexts, left, right, nlevels=8, scale=0.8, target=2000, init_th=
         raise TBError(rc, "; ".join(m for m in msgs if m) or lib().tb_strerror(rc).decode())
     return [(kps[0, f, :cnt[0, f]].copy(), desc[0, f, :cnt[0, f]].copy(), kps[1, f, :cnt[1, f]].copy(), desc[1, f, :cnt[1, f]].copy(),
              mt[f, :mc[f]].copy()) for f in range(F)]
+
+
+class VOParams(C.Structure):
+    """tb_vo_params of include/tb_capi.h"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("nlevels", C.c_int), ("scale", C.c_float), ("target", C.c_int),
+                ("init_th", C.c_float), ("min_th", C.c_float), ("K", C.c_double * 4), ("bf", C.c_float), ("keyframe_every", C.c_int)]
+
+
+class VO:
+    """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out."""
+
+    def __init__(self, ctx, params, nseq):
+        self.ctx = ctx
+        self.nseq = int(nseq)
+        self._h = C.c_void_p()
+        ctx.check(lib().tb_vo_create(ctx._h, C.byref(params), self.nseq, C.byref(self._h)))
+
+    def close(self):
+        # the loop owns an extractor plan of its context: destroy it while the context is alive
+        if self._h and self.ctx._h:
+            lib().tb_vo_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset_dev(self, Tcw0_ptr):
+        self.ctx.check(lib().tb_vo_reset_dev(self._h, C.c_void_p(Tcw0_ptr)))
+
+    def step_dev(self, left_ptr, right_ptr, stride, pitch):
+        """Returns the status code (0 or a negative TB_E* code) instead of raising, so argument checks can be tested."""
+        return lib().tb_vo_step_dev(self._h, C.c_void_p(left_ptr), C.c_void_p(right_ptr or None), int(stride), C.c_size_t(pitch))
+
+    def state_dev(self):
+        """dict of device pointers (Tcw, keys_xy, map_points, mp_valid, key_counts, obs, obs_counts, n_inliers, outlier) + key_pitch,
+        frame."""
+        ptrs = [C.c_void_p() for _ in range(9)]
+        pitch, frame = C.c_int(0), C.c_int(0)
+        self.ctx.check(lib().tb_vo_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(pitch), C.byref(frame)))
+        names = ("Tcw", "keys_xy", "map_points", "mp_valid", "key_counts", "obs", "obs_counts", "n_inliers", "outlier")
+        out = {k: q.value for k, q in zip(names, ptrs)}
+        out["key_pitch"], out["frame"] = pitch.value, frame.value
+        return out
 
 
 class Context:

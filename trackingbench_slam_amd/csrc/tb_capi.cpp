@@ -1830,6 +1830,192 @@ int tb_add_map_points_by_stereo(tb_ctx* ctx, const uint8_t* img_stereo, const ui
     return TB_OK;
 }
 
+/* ---- device-resident stereo VO loop (test/test_vo.cpp test_kitti): see include/tb_capi.h */
+struct tb_vo {
+    tb_ctx* ctx = nullptr;
+    tb_vo_params p;
+    int nseq = 0, P = 0;        /* sequences, key capacity (= the extractor's kp_capacity) */
+    tb_extractor* ex = nullptr;
+    tb_camera cam;              /* width / height: CameraModel::IsInFrame of both frames */
+    int next = -1;              /* frame index of the next step (-1: not reset) */
+    int cur = 0;                /* which half of the ping-pong buffers holds the last frame */
+    /* ping-pong state: the last frame's and the current frame's */
+    uint8_t* img[2] = {nullptr, nullptr};    /* [nseq][h][w] left images */
+    float* keys[2] = {nullptr, nullptr};     /* [nseq][P][2] */
+    int32_t* kcnt[2] = {nullptr, nullptr};   /* [nseq] */
+    float* mp[2] = {nullptr, nullptr};       /* [nseq][P][3] */
+    uint8_t* valid[2] = {nullptr, nullptr};  /* [nseq][P] */
+    float* Tcw[2] = {nullptr, nullptr};      /* [nseq][16] */
+    /* per-step buffers */
+    uint8_t* right = nullptr;                /* [nseq][h][w] */
+    uint8_t* status = nullptr;               /* [nseq][P] LK status of the tracking step */
+    tb_match* matches = nullptr;             /* [nseq][P] */
+    int32_t* mcounts = nullptr;              /* [nseq] */
+    tb_obs* obs = nullptr;                   /* [nseq][P] */
+    int32_t* obs_counts = nullptr;           /* [nseq] */
+    uint8_t* outlier = nullptr;              /* [nseq][P] */
+    int32_t* n_inliers = nullptr;            /* [nseq] */
+    float* st_pts = nullptr;                 /* [nseq][P][2] stereo tracks */
+    uint8_t* st_status = nullptr;            /* [nseq][P] */
+    float* depth = nullptr;                  /* [nseq][P] */
+};
+
+void tb_vo_destroy(tb_vo* vo) {
+    if (!vo) return;
+    hipSetDevice(vo->ctx->device);
+    hipStreamSynchronize(vo->ctx->stream);
+    if (vo->ex) tb_extractor_destroy(vo->ex);
+    for (int k = 0; k < 2; k++) {
+        hipFree(vo->img[k]); hipFree(vo->keys[k]); hipFree(vo->kcnt[k]); hipFree(vo->mp[k]); hipFree(vo->valid[k]); hipFree(vo->Tcw[k]);
+    }
+    hipFree(vo->right); hipFree(vo->status); hipFree(vo->matches); hipFree(vo->mcounts); hipFree(vo->obs); hipFree(vo->obs_counts);
+    hipFree(vo->outlier); hipFree(vo->n_inliers); hipFree(vo->st_pts); hipFree(vo->st_status); hipFree(vo->depth);
+    delete vo;
+}
+
+int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
+    TB_ENTER(ctx);
+    if (!ctx || !p || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (nseq < 1 || p->width < 1 || p->height < 1 || p->nlevels < 2 || p->nlevels > TB_MAX_LEVELS || !(p->scale > 0.f && p->scale < 1.f) ||
+        p->target < 1 || p->keyframe_every < 1 || !(p->K[0] > 0.0) || !(p->K[1] > 0.0) || !std::isfinite(p->K[2]) ||
+        !std::isfinite(p->K[3]) || !(p->bf > 0.f) || !std::isfinite(p->bf))
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_create: bad parameters (nseq %d, %dx%d, %d levels, scale %g, target %d, keyframe_every %d)",
+                       nseq, p->width, p->height, p->nlevels, (double)p->scale, p->target, p->keyframe_every);
+    std::vector<float> sf(p->nlevels), tmp(p->nlevels);
+    tb_scale_factors(p->nlevels, p->scale, sf.data(), tmp.data(), tmp.data(), tmp.data());
+    std::unique_ptr<tb_vo, void (*)(tb_vo*)> vu(new tb_vo(), tb_vo_destroy);
+    tb_vo* vo = vu.get();
+    vo->ctx = ctx;
+    vo->p = *p;
+    vo->nseq = nseq;
+    int rc = tb_extractor_create(ctx, p->width, p->height, p->nlevels, sf.data(), nullptr, nullptr, nseq, p->target, &vo->ex);
+    if (rc) return rc;
+    vo->P = vo->ex->g.selCap;
+    memset(&vo->cam, 0, sizeof vo->cam);
+    vo->cam.fx = (float)p->K[0]; vo->cam.fy = (float)p->K[1]; vo->cam.cx = (float)p->K[2]; vo->cam.cy = (float)p->K[3];
+    vo->cam.width = p->width; vo->cam.height = p->height;
+    const size_t S = (size_t)nseq, P = (size_t)vo->P, img = (size_t)p->width * p->height;
+    for (int k = 0; k < 2; k++) {
+        TB_HIP(ctx, hipMalloc(&vo->img[k], S * img));
+        TB_HIP(ctx, hipMalloc(&vo->keys[k], S * P * 2 * sizeof(float)));
+        TB_HIP(ctx, hipMalloc(&vo->kcnt[k], S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->mp[k], S * P * 3 * sizeof(float)));
+        TB_HIP(ctx, hipMalloc(&vo->valid[k], S * P));
+        TB_HIP(ctx, hipMalloc(&vo->Tcw[k], S * 16 * sizeof(float)));
+    }
+    TB_HIP(ctx, hipMalloc(&vo->right, S * img));
+    TB_HIP(ctx, hipMalloc(&vo->status, S * P));
+    TB_HIP(ctx, hipMalloc(&vo->matches, S * P * sizeof(tb_match)));
+    TB_HIP(ctx, hipMalloc(&vo->mcounts, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->obs, S * P * sizeof(tb_obs)));
+    TB_HIP(ctx, hipMalloc(&vo->obs_counts, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->outlier, S * P));
+    TB_HIP(ctx, hipMalloc(&vo->n_inliers, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->st_pts, S * P * 2 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&vo->st_status, S * P));
+    TB_HIP(ctx, hipMalloc(&vo->depth, S * P * sizeof(float)));
+    for (int k = 0; k < 2; k++) {
+        TB_HIP(ctx, hipMemsetAsync(vo->kcnt[k], 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->valid[k], 0, S * P, ctx->stream));
+    }
+    TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, S * sizeof(int32_t), ctx->stream));
+    /* every scratch slot the step's operators use, at its largest size now: a step never grows one (growth synchronises) */
+    const size_t pitch = img;
+    void* d;
+    if ((rc = tb_scratch(ctx, 5, S * pitch, &d)) || (rc = tb_scratch(ctx, 6, S * 8 * 8 * 256, &d)) ||
+        (rc = tb_scratch(ctx, 7, std::max(tbk_lk_work_bytes(p->width, p->height, 3, nseq), S * P * 3 * sizeof(double)), &d)) ||
+        (rc = tb_scratch(ctx, 8, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, 9, S * sizeof(int32_t), &d)) ||
+        (rc = tb_scratch(ctx, 10, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, 11, S * sizeof(int32_t), &d)))
+        return rc;
+    *out = vu.release();
+    return TB_OK;
+}
+
+int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo || !Tcw0) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    /* frame 0 reads the "last frame": no keys, pose Tcw0 */
+    TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[vo->cur], Tcw0, (size_t)vo->nseq * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->kcnt[vo->cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+    vo->next = 0;
+    return TB_OK;
+}
+
+int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    if (vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev before tb_vo_reset_dev");
+    const int t = vo->next;
+    const bool keyframe = t % p.keyframe_every == 0;
+    if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
+    if (keyframe && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
+    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
+    const size_t ip = (size_t)W * H;
+    const int a = vo->cur, b = a ^ 1;   /* a: last frame, b: this frame */
+    int rc;
+    if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
+    if (t == 0) {
+        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->kcnt[b], 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+    } else {
+        /* test_vo.cpp:716: searchByOPFlow(cur, last, pts, true, true) -- the tracked points land in this frame's key list */
+        if ((rc = tb_search_by_opflow_batch_dev(ctx, S, vo->img[b], vo->img[a], W, H, W, ip, &vo->cam, vo->keys[a], vo->kcnt[a], P, 1, 1,
+                                                vo->keys[b], vo->status, vo->matches, P, vo->mcounts)))
+            return rc;
+        if ((rc = tbk_vo_track(ctx, S, vo->kcnt[a], vo->status, vo->keys[b], vo->mp[a], vo->valid[a], P, vo->kcnt[b], vo->mp[b], vo->valid[b],
+                               vo->obs, vo->obs_counts, vo->outlier)))
+            return rc;
+        /* :761 LocalBA::PoseOptimization, started from the last frame's pose (:688) */
+        if ((rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
+            return rc;
+    }
+    if (keyframe) {
+        /* :774-785 ORB operator()(pyramid, sf, target, init_th, min_th) + SetKeys */
+        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
+        if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
+        if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
+        if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
+        const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
+        tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
+        if ((rc = tbk_vo_kf_pack(ctx, S, kps, cnt, selCap, P, vo->keys[b], vo->kcnt[b], vo->valid[b]))) return rc;
+        /* :800 AddMapPointsByStereo(cur, right, d * fx, fx), then the new map points (:802-832) */
+        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
+                                                        vo->st_pts, vo->st_status, vo->depth)))
+            return rc;
+        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
+    }
+    vo->cur = b;
+    vo->next = t + 1;
+    return TB_OK;
+}
+
+int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const float** map_points, const uint8_t** mp_valid,
+                    const int32_t** key_counts, const tb_obs** obs, const int32_t** obs_counts, const int32_t** n_inliers,
+                    const uint8_t** outlier, int* key_pitch, int* frame) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    const int c = vo->cur;
+    if (Tcw) *Tcw = vo->Tcw[c];
+    if (keys_xy) *keys_xy = vo->keys[c];
+    if (map_points) *map_points = vo->mp[c];
+    if (mp_valid) *mp_valid = vo->valid[c];
+    if (key_counts) *key_counts = vo->kcnt[c];
+    if (obs) *obs = vo->obs;
+    if (obs_counts) *obs_counts = vo->obs_counts;
+    if (n_inliers) *n_inliers = vo->n_inliers;
+    if (outlier) *outlier = vo->outlier;
+    if (key_pitch) *key_pitch = vo->P;
+    if (frame) *frame = vo->next - 1 < -1 ? -1 : vo->next - 1;
+    return TB_OK;
+}
+
 /* ---- multi-GPU batch entry: see include/tb_capi.h */
 int tb_batch_run(tb_ctx** ctxs, int ngpu, const tb_batch_params* p, int nframes, const uint8_t* left, const uint8_t* right,
                  int stride, size_t pitch, int cap, tb_keypoint* kps, uint8_t* desc, int32_t* counts, tb_match* matches,

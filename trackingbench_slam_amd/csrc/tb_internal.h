@@ -232,4 +232,14 @@ int tbk_lk_track(tb_ctx* ctx, int npairs, const uint8_t* d_prev, const uint8_t* 
                  const float* d_prev_pts, const int32_t* d_counts, int n, int pts_pitch, int win, int max_level, float* d_next_pts,
                  uint8_t* d_status, float* d_err, void* d_work, int* top_level);
 
+/* device-resident stereo VO loop (k_vo.hip) */
+int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst);
+int tbk_vo_track(tb_ctx* ctx, int nseq, const int32_t* d_prev_counts, const uint8_t* d_status, const float* d_keys, const float* d_prev_mp,
+                 const uint8_t* d_prev_valid, int pitch, int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, tb_obs* d_obs,
+                 int32_t* d_obs_counts, uint8_t* d_outlier);
+int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, float* d_keys,
+                   int32_t* d_key_counts, uint8_t* d_valid);
+int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
+                    const double K[4], int pitch, float* d_mp, uint8_t* d_valid);
+
 #endif
