@@ -140,7 +140,8 @@ int tb_search_by_bf(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, i
 int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, const int32_t* counts1,
                               const uint8_t* desc2, const int32_t* counts2, size_t set_pitch,
                               float ratio, float min_th, tb_match* out, int cap, int32_t* out_counts);
-/* Matcher::searchByViolence, matcher.cpp:299-395 (+ Frame grid, Frame.cpp:187-265). */
+/* Matcher::searchByViolence, matcher.cpp:299-395 (+ Frame grid, Frame.cpp:187-265). Host pointers: stages F2's lookup grid
+ * and one pair for tb_search_by_violence_batch_dev, so histo_len <= 1024 (the reference uses 30). */
 int tb_search_by_violence(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int n1,
                           const tb_keypoint* k2, const uint8_t* d2, int n2, int img2_width, int img2_height,
                           int min_level, int max_level, float radius, int th_low, float nratio,
@@ -152,7 +153,9 @@ int tb_search_by_violence(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1,
  * lists as CSR, in insertion order. DBoW2 and its vocabulary stay outside this library (the reference tree ships no
  * vocabulary file). has_mp2 (nullable, n2 bytes): F2->GetMapPoint(i) != nullptr, read when map_point_only is set.
  * th_low / nratio / histo_len / check_orientation = the Matcher's TH_LOW / nRatio / HISTO_LENGTH / checkOrientation.
- * Matches: queryIdx = F1 key, trainIdx = F2 key, imgIdx = -1, distance = Hamming, in the reference's order. */
+ * Matches: queryIdx = F1 key, trainIdx = F2 key, imgIdx = -1, distance = Hamming, in the reference's order. Runs
+ * tb_search_by_bow_batch_dev on one pair, so histo_len <= 1024 (the reference uses 30), and a feature vector whose node ids
+ * are not strictly ascending or whose offsets are out of order is TB_EINVAL. */
 int tb_search_by_bow(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int n1, const uint32_t* nodes1, const int32_t* start1,
                      const uint32_t* items1, int nn1, const tb_keypoint* k2, const uint8_t* d2, int n2, const uint8_t* has_mp2,
                      const uint32_t* nodes2, const int32_t* start2, const uint32_t* items2, int nn2, int map_point_only, int th_low,
@@ -164,7 +167,8 @@ int tb_search_by_bow(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int 
  * descriptors d1 (n1 x 32), taken1[i] != 0 iff F1->GetMapPoint(i) has Observations() > 0 (nullable = none).
  * F2 = reference frame: keys k2 (octave, angle) and, aligned with them, its map points mp2 (bad != 0 also for "no
  * map point") with descriptors mp2_desc (n2 x 32). scale_factors = F1->GetScaleFactors() (nlevels entries).
- * Matches: queryIdx = F1 key, trainIdx = i2, imgIdx = -1, distance = Hamming; order as the reference emits them. */
+ * Matches: queryIdx = F1 key, trainIdx = i2, imgIdx = -1, distance = Hamming; order as the reference emits them.
+ * Runs tb_search_by_projection_batch_dev on one pair: histo_len <= 1024 and nlevels <= 32 (the reference uses 30 and 8). */
 int tb_search_by_projection(tb_ctx* ctx, const float Tcw1[16], const tb_camera* cam1, int img1_width, int img1_height,
                             const tb_keypoint* k1, const uint8_t* d1, const uint8_t* taken1, int n1,
                             const tb_keypoint* k2, const tb_mappoint* mp2, const uint8_t* mp2_desc, int n2,
@@ -172,7 +176,8 @@ int tb_search_by_projection(tb_ctx* ctx, const float Tcw1[16], const tb_camera* 
                             int check_orientation, tb_match* out, int cap, int* count);
 /* Matcher::searchByProjection(map, F1, radio), matcher.cpp:539-617 (+ Frame::IsInFrustum, Frame.cpp:370-412, entered
  * with viewingCosLimit 0.5; the predicted level is the reference's constant 0). mps = map->GetAllMapPoints() in
- * order; trainIdx = index into mps. */
+ * order; trainIdx = index into mps. Runs tb_search_by_projection_map_batch_dev on one frame: nlevels <= 32 (the reference
+ * uses 8). */
 int tb_search_by_projection_map(tb_ctx* ctx, const float Tcw1[16], const tb_camera* cam1, int img1_width, int img1_height,
                                 const tb_keypoint* k1, const uint8_t* d1, const uint8_t* taken1, int n1,
                                 const tb_mappoint* mps, const uint8_t* mp_desc, int nmp,
@@ -245,9 +250,10 @@ int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, co
                                int desc_pitch, int levelsup, int32_t* word_ids, int32_t* node_ids, double* weights,
                                uint64_t* fv_keys, int32_t* fv_counts);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
- * sorted-list form above: pair p matches frame p of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX],
- * fv keys [npairs][pitchX] with fv_countsX[p] entries; has_mp2 nullable [npairs][pitch2]). Matches [npairs][cap] in the
- * reference's order, out_counts[p]; flags[p] != 0: a rotation bin outside the histogram (the reference asserts). */
+ * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
+ * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
+ * entries; has_mp2 nullable [npairs][pitch2]). Matches [npairs][cap] in the reference's order, out_counts[p]; flags[p] != 0:
+ * a rotation bin outside the histogram (the reference asserts). */
 int tb_search_by_bow_batch_dev(tb_ctx* ctx, int npairs, const tb_keypoint* k1, const uint8_t* d1, int pitch1,
                                const uint64_t* fv1, const int32_t* fv_counts1, const tb_keypoint* k2, const uint8_t* d2, int pitch2,
                                const uint64_t* fv2, const int32_t* fv_counts2, const uint8_t* has_mp2, int map_point_only,

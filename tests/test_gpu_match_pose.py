@@ -71,6 +71,34 @@ def test_violence_golden_and_params(ctx, golden):
     assert len(ctx.search_by_violence(k1, d1, k2[:0], d2[:0], 1241, 376)) == 0
 
 
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _raw_violence(ctx, k1, d1, k2, d2, cap, histo_len=30):
+    """tb_search_by_violence through the raw C ABI: (return code, *count, out[:cap])."""
+    k1 = np.ascontiguousarray(k1, capi.KEYPOINT); k2 = np.ascontiguousarray(k2, capi.KEYPOINT)
+    d1, d2 = np.ascontiguousarray(d1, np.uint8), np.ascontiguousarray(d2, np.uint8)
+    out = np.zeros(max(cap, 1), capi.MATCH); n = C.c_int(-7)
+    rc = capi.lib().tb_search_by_violence(ctx._h, _ptr(k1), _ptr(d1), len(k1), _ptr(k2), _ptr(d2), len(k2), 1241, 376, 0, 8,
+                                          C.c_float(50.0), 100, C.c_float(1.0), histo_len, 1, _ptr(out), cap, C.byref(n))
+    return rc, n.value, out[:cap]
+
+
+def test_violence_capacity_and_bounds(ctx, golden):
+    """The host form's capacity contract: cap = count - 1 -> TB_ECAPACITY with the full count, cap = count -> the oracle's
+    list; histo_len above the batched kernels' 1024 bins is rejected."""
+    k1, d1, k2, d2 = (golden[f"c8_{x}"] for x in ("kps_left", "desc_left", "kps_right", "desc_right"))
+    exp = oracle.search_by_violence(k1, d1, k2, d2, 1241, 376, 0, 8, 50.0, th_low=100, nratio=1.0, histo_len=30)
+    assert len(exp) > 1
+    rc, n, _ = _raw_violence(ctx, k1, d1, k2, d2, len(exp) - 1)
+    assert rc == capi.TB_ECAPACITY and n == len(exp)
+    rc, n, out = _raw_violence(ctx, k1, d1, k2, d2, len(exp))
+    assert rc == capi.TB_OK and n == len(exp)
+    _eq_struct(out, exp)
+    assert _raw_violence(ctx, k1, d1, k2, d2, len(exp), histo_len=1025)[0] == capi.TB_EINVAL
+
 def _pose_close(a, b):
     assert np.allclose(a, b, rtol=1e-6, atol=1e-6 * max(1.0, float(np.abs(b).max())))
 
@@ -163,6 +191,38 @@ def test_search_by_bow_edges(ctx):
         bad = dict(fv1); bad[next(iter(bad))] = [10 ** 6]
         ctx.search_by_bow(k1, d1, bad, k2, d2, fv2, **kw)
 
+
+
+def _raw_bow(ctx, k1, d1, csr1, k2, d2, csr2, cap, has_mp2=None, map_point_only=False, th_low=80, nratio=0.95, histo_len=30):
+    """tb_search_by_bow through the raw C ABI on CSR feature vectors (nodes, start, items): (return code, *count, out[:cap])."""
+    k1 = np.ascontiguousarray(k1, capi.KEYPOINT); k2 = np.ascontiguousarray(k2, capi.KEYPOINT)
+    d1, d2 = np.ascontiguousarray(d1, np.uint8), np.ascontiguousarray(d2, np.uint8)
+    (n1, s1, i1), (n2, s2, i2) = csr1, csr2
+    out = np.zeros(max(cap, 1), capi.MATCH); n = C.c_int(-7)
+    rc = capi.lib().tb_search_by_bow(ctx._h, _ptr(k1), _ptr(d1), len(k1), _ptr(n1), _ptr(s1), _ptr(i1), len(n1), _ptr(k2), _ptr(d2),
+                                     len(k2), _ptr(has_mp2), _ptr(n2), _ptr(s2), _ptr(i2), len(n2), int(map_point_only), th_low,
+                                     C.c_float(nratio), histo_len, 1, _ptr(out), cap, C.byref(n))
+    return rc, n.value, out[:cap]
+
+
+def test_search_by_bow_capacity_and_bounds(ctx):
+    """cap = count - 1 -> TB_ECAPACITY with the full count, cap = count -> the oracle's list; node ids out of order and
+    histo_len above 1024 are rejected."""
+    k1, d1, fv1, k2, d2, fv2, has_mp2 = _bow_case(6)
+    csr1, csr2 = capi.Context._fv(fv1), capi.Context._fv(fv2)
+    exp = oracle.search_by_bow(k1, d1, fv1, k2, d2, fv2, has_mp2=has_mp2, map_point_only=True, th_low=80, nratio=0.95, histo_len=30)
+    assert len(exp) > 1
+    rc, n, _ = _raw_bow(ctx, k1, d1, csr1, k2, d2, csr2, len(exp) - 1, has_mp2, True)
+    assert rc == capi.TB_ECAPACITY and n == len(exp)
+    rc, n, out = _raw_bow(ctx, k1, d1, csr1, k2, d2, csr2, len(exp), has_mp2, True)
+    assert rc == capi.TB_OK and n == len(exp)
+    _eq_struct(out, exp)
+    for side in (0, 1):
+        nodes = [csr1[0].copy(), csr2[0].copy()]
+        nodes[side][[0, 1]] = nodes[side][[1, 0]]                                   # two node ids swapped
+        bad = [(nodes[0],) + csr1[1:], (nodes[1],) + csr2[1:]]
+        assert _raw_bow(ctx, k1, d1, bad[0], k2, d2, bad[1], len(exp))[0] == capi.TB_EINVAL
+    assert _raw_bow(ctx, k1, d1, csr1, k2, d2, csr2, len(exp), histo_len=1025)[0] == capi.TB_EINVAL
 
 def test_pose_from_stereo_tracks_finds_the_baseline(ctx):
     """tb_stereo_tracks_to_obs_batch_dev + PoseOptimization from the identity, the composition bench.py times: keys of a left

@@ -70,6 +70,65 @@ def test_projection_edges(ctx):
     _same(mg, mo)
 
 
+
+def _raw_projection(ctx, c, taken1, cap, map_mode=False, nratio=8.0, histo_len=30):
+    """tb_search_by_projection[_map] through the raw C ABI (taken1 may be None): (return code, *count, out[:cap])."""
+    import ctypes as C
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    T = np.ascontiguousarray(c["Tcw"], np.float32).reshape(16)
+    cam = np.ascontiguousarray(c["cam"], capi.CAMERA)
+    k1, k2 = np.ascontiguousarray(c["k1"], capi.KEYPOINT), np.ascontiguousarray(c["k2"], capi.KEYPOINT)
+    d1, md = np.ascontiguousarray(c["d1"], np.uint8), np.ascontiguousarray(c["mp_desc"], np.uint8)
+    mp, sf = np.ascontiguousarray(c["mp"], capi.MAPPOINT), np.ascontiguousarray(c["sf"], np.float32)
+    tk = None if taken1 is None else np.ascontiguousarray(taken1, np.uint8)
+    out = np.zeros(max(cap, 1), capi.MATCH); n = C.c_int(-7)
+    L = capi.lib()
+    head = (ctx._h, ptr(T), ptr(cam), int(c["width"]), int(c["height"]), ptr(k1), ptr(d1), ptr(tk), len(k1))
+    if map_mode:
+        rc = L.tb_search_by_projection_map(*head, ptr(mp), ptr(md), len(mp), ptr(sf), len(sf), C.c_float(nratio), C.c_float(0.8), 100,
+                                           ptr(out), cap, C.byref(n))
+    else:
+        rc = L.tb_search_by_projection(*head, ptr(k2), ptr(mp), ptr(md), len(mp), ptr(sf), len(sf), C.c_float(nratio), 100, histo_len, 1,
+                                       ptr(out), cap, C.byref(n))
+    return rc, n.value, out[:cap]
+
+
+@pytest.mark.parametrize("map_mode", [False, True])
+def test_projection_capacity_and_null_taken(ctx, map_mode):
+    """cap = count - 1 -> TB_ECAPACITY with the full count, cap = count -> the oracle's list; taken1 = NULL is all zeros."""
+    c = synth.projection_case(11, n1=1500, nmp=1200)
+    c["k1"]["octave"][::2] = 0
+    a = (c["Tcw"], c["cam"], c["width"], c["height"], c["k1"], c["d1"], c["taken1"])
+    m = (c["mp"], c["mp_desc"], c["sf"], 3.0 if map_mode else 8.0)
+    exp = oracle.search_by_projection_map(*a, *m, 0.8) if map_mode else oracle.search_by_projection(*a, c["k2"], *m)
+    nr = m[-1]
+    assert len(exp) > 1
+    rc, n, _ = _raw_projection(ctx, c, c["taken1"], len(exp) - 1, map_mode, nr)
+    assert rc == capi.TB_ECAPACITY and n == len(exp)
+    rc, n, out = _raw_projection(ctx, c, c["taken1"], len(exp), map_mode, nr)
+    assert rc == capi.TB_OK and n == len(exp)
+    _same(out, exp)
+    zeros = np.zeros(len(c["k1"]), np.uint8)
+    a0 = a[:-1] + (zeros,)
+    exp0 = oracle.search_by_projection_map(*a0, *m, 0.8) if map_mode else oracle.search_by_projection(*a0, c["k2"], *m)
+    rc, n, out_null = _raw_projection(ctx, c, None, len(c["mp"]), map_mode, nr)
+    rc0, n0, out_zero = _raw_projection(ctx, c, zeros, len(c["mp"]), map_mode, nr)
+    assert rc == rc0 == capi.TB_OK and n == n0 == len(exp0) > 0
+    _same(out_null[:n], exp0)
+    _same(out_zero[:n0], exp0)
+
+
+def test_projection_bounds_and_error_order(ctx):
+    """histo_len above the batched kernels' 1024 bins is rejected; with both a rotation bin outside the histogram and a key
+    octave outside the scale factors, the octave is reported (TB_EINVAL), as the host form always has."""
+    c = synth.projection_case(12, n1=1500, nmp=1200)
+    cap = len(c["mp"])
+    assert _raw_projection(ctx, c, c["taken1"], cap, histo_len=1025)[0] == capi.TB_EINVAL
+    c["k2"]["angle"] = np.random.default_rng(3).uniform(0, 360, len(c["k2"])).astype(np.float32)
+    assert _raw_projection(ctx, c, c["taken1"], cap, histo_len=12)[0] == capi.TB_EUNSUPPORTED
+    c["k2"]["octave"][::3] = 9
+    assert _raw_projection(ctx, c, c["taken1"], cap, histo_len=12)[0] == capi.TB_EINVAL
+
 def _grid_ref(k, w, h):
     """Frame::AssignFeaturesToGrid as CSR (numpy restatement; round half away from zero as std::round)."""
     hinv, winv = np.float32(120) / np.float32(w), np.float32(36) / np.float32(h)

@@ -144,72 +144,13 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
     return TB_OK;
 }
 
-/* a14: window search. One thread per F1 key; F2's 120x36 grid arrives as CSR (cellStart, cellItems). */
-__global__ void __launch_bounds__(256)
-k_window(const tb_keypoint* __restrict__ k1, const uint8_t* __restrict__ d1, int n1, const tb_keypoint* __restrict__ k2,
-         const uint8_t* __restrict__ d2, const int32_t* __restrict__ cellStart, const int32_t* __restrict__ cellItems,
-         float widthInv, float heightInv, int min_level, int max_level, float r, int32_t* __restrict__ best) {
-    const int GRID_ROWS = 36, GRID_COLS = 120;
-    const int i1 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i1 >= n1) return;
-    int bestDist = 0x7fffffff, bestDist2 = 0x7fffffff, bestIdx = -1, ncand = 0;
-    const float x = k1[i1].x, y = k1[i1].y;
-    /* Frame::GetFeaturesInArea, Frame.cpp:202-255 */
-    const int nMinCellX = max(0, (int)floorf(TB_FMUL(TB_FSUB(x, r), widthInv)));
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(TB_FMUL(TB_FADD(x, r), widthInv)));
-    const int nMinCellY = max(0, (int)floorf(TB_FMUL(TB_FSUB(y, r), heightInv)));
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(TB_FMUL(TB_FADD(y, r), heightInv)));
-    if (nMinCellX < GRID_COLS && nMaxCellX >= 0 && nMinCellY < GRID_ROWS && nMaxCellY >= 0) {
-        const bool bCheckLevels = (min_level > 0) || (max_level >= 0);
-        const unsigned long long* a = reinterpret_cast<const unsigned long long*>(d1) + (size_t)i1 * 4;
-        Desc256 da;
-        da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
-            for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
-                const int c = ix * GRID_ROWS + iy;
-                for (int s = cellStart[c]; s < cellStart[c + 1]; s++) {
-                    const int j = cellItems[s];
-                    const tb_keypoint kp = k2[j];
-                    if (bCheckLevels) {
-                        if (kp.octave < min_level) continue;
-                        if (max_level >= 0 && kp.octave > max_level) continue;
-                    }
-                    if (!(fabsf(TB_FSUB(kp.x, x)) < r && fabsf(TB_FSUB(kp.y, y)) < r)) continue;
-                    ncand++;
-                    const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d2) + (size_t)j * 4);
-                    if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx = j; }
-                    else if (dist < bestDist2) bestDist2 = dist;
-                }
-            }
-    }
-    best[4 * i1] = bestDist;
-    best[4 * i1 + 1] = bestDist2;
-    best[4 * i1 + 2] = bestIdx;
-    best[4 * i1 + 3] = ncand;
-}
-
-int tbk_window_match(tb_ctx* ctx, const tb_keypoint* d_k1, const uint8_t* d_d1, int n1, const tb_keypoint* d_k2,
-                     const uint8_t* d_d2, int n2, const int32_t* d_cellStart, const int32_t* d_cellItems, float widthInv,
-                     float heightInv, int min_level, int max_level, float r, int32_t* d_best) {
-    if (n1 <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_window");
-    hipLaunchKernelGGL(k_window, dim3((n1 + 255) / 256), dim3(256), 0, ctx->stream, d_k1, d_d1, n1, d_k2, d_d2, d_cellStart,
-                       d_cellItems, widthInv, heightInv, min_level, max_level, r, d_best);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
-}
-
 /* ------------------------------------------------------------------------------------------------
- * SURVEY 8(f) row 1 -- Matcher::searchByProjection, both overloads (matcher.cpp:406-617).
- * Two steps on the device: (1) one thread per map point projects it into F1 and derives its search window
- * (k_project_frame: matcher.cpp:431-458; k_project_map: Frame::IsInFrustum, Frame.cpp:370-412, and
- * matcher.cpp:558-567), (2) one thread per query walks F1's 120x36 lookup grid in the reference's order
- * (ix, iy, insertion) and keeps best / second best with their levels (k_window_q). Float arithmetic: one rounding
+ * SURVEY 8(f) row 1 -- Matcher::searchByProjection, both overloads (matcher.cpp:406-617): device helpers of
+ * k_proj_search_batch, which projects one map point into F1 and derives its search window (matcher.cpp:431-458; the map
+ * overload: Frame::IsInFrustum, Frame.cpp:370-412, and matcher.cpp:558-567). Float arithmetic: one rounding
  * per reference operation, fixed-size Eigen 3.3 reduction order c0 + (c1 + c2), no FMA contraction. */
 #pragma clang fp contract(off)
 struct ProjPose { float T[16]; };
-struct ProjQuery { float u, v, r; int32_t minL, maxL; };  /* r < 0: no search for this map point */
 
 __device__ __forceinline__ void pj_se3_map(const ProjPose& P, const float* X, float* Pc) {
 #pragma unroll
@@ -237,137 +178,6 @@ __device__ __forceinline__ bool pj_in_frame(const tb_camera& cam, const float* p
     if (!(fabsf(px[0]) < 2147483648.f) || !(fabsf(px[1]) < 2147483648.f)) return false; /* x86 cast -> INT_MIN */
     const int u = (int)px[0], v = (int)px[1];
     return u >= 0 && u < (int)((float)cam.width * 1.f) && v >= 0 && v < (int)((float)cam.height * 1.f);
-}
-
-__global__ void __launch_bounds__(256)
-k_project_frame(ProjPose P, tb_camera cam, const tb_keypoint* __restrict__ k2, const tb_mappoint* __restrict__ mp2, int n2,
-                const float* __restrict__ sf, int nlevels, float nratio, ProjQuery* __restrict__ q, int* __restrict__ bad_octave) {
-    const int i2 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i2 >= n2) return;
-    ProjQuery o = {0.f, 0.f, -1.f, 0, 0};
-    const tb_mappoint mp = mp2[i2];
-    if (!mp.bad) {
-        float Pc[3], uv[2];
-        pj_se3_map(P, mp.pos, Pc);
-        const float invzc = 1.0f / Pc[2];
-        if (!(invzc < 0)) {
-            pj_world2cam(cam, Pc, uv);
-            if (pj_in_frame(cam, uv)) {
-                const int oct = k2[i2].octave;
-                if (oct < 0 || oct >= nlevels) *bad_octave = 1; /* benign race: every writer stores 1 */
-                else { o.u = uv[0]; o.v = uv[1]; o.r = nratio * sf[oct]; o.minL = oct - 1; o.maxL = oct + 1; }
-            }
-        }
-    }
-    q[i2] = o;
-}
-
-__global__ void __launch_bounds__(256)
-k_project_map(ProjPose P, tb_camera cam, const tb_mappoint* __restrict__ mps, int nmp, float sf0, float nratio,
-              ProjQuery* __restrict__ q) {
-    const int im = blockIdx.x * blockDim.x + threadIdx.x;
-    if (im >= nmp) return;
-    ProjQuery o = {0.f, 0.f, -1.f, 0, 0};
-    const tb_mappoint mp = mps[im];
-    if (!mp.bad) {
-        float Pc[3], uv[2], Ow[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) { /* Frame::SetPose: mOw = -Rcw^T tcw */
-            const float c0 = -P.T[i] * P.T[3], c1 = -P.T[4 + i] * P.T[7], c2 = -P.T[8 + i] * P.T[11];
-            Ow[i] = c0 + (c1 + c2);
-        }
-        pj_se3_map(P, mp.pos, Pc);
-        if (!(Pc[2] < 0.0f)) {
-            pj_world2cam(cam, Pc, uv);
-            if (pj_in_frame(cam, uv)) {
-                const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
-                const float dist3 = sqrtf(PO[0] * PO[0] + (PO[1] * PO[1] + PO[2] * PO[2]));
-                if (!(dist3 < mp.min_dist || dist3 > mp.max_dist)) {
-                    const float viewCos = (PO[0] * mp.normal[0] + (PO[1] * mp.normal[1] + PO[2] * mp.normal[2])) / dist3;
-                    if (!(viewCos < 0.5f)) {
-                        float r = 4.f;
-                        if ((double)viewCos > 0.998) r = 2.5f;
-                        if ((double)nratio != 1.0) r *= nratio;
-                        o.u = uv[0]; o.v = uv[1]; o.r = r * sf0; o.minL = -1; o.maxL = 0;
-                    }
-                }
-            }
-        }
-    }
-    q[im] = o;
-}
-
-/* best[6 q]: bestDist, bestDist2, bestIdx, bestLevel, bestLevel2, candidates in the window */
-__global__ void __launch_bounds__(256)
-k_window_q(const ProjQuery* __restrict__ q, const uint8_t* __restrict__ qd, int nq, const tb_keypoint* __restrict__ k1,
-           const uint8_t* __restrict__ d1, const uint8_t* __restrict__ taken1, const int32_t* __restrict__ cellStart,
-           const int32_t* __restrict__ cellItems, float widthInv, float heightInv, int32_t* __restrict__ best) {
-    const int GRID_ROWS = 36, GRID_COLS = 120;
-    const int iq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (iq >= nq) return;
-    int bestDist = 256, bestDist2 = 256, bestIdx = -1, bestLevel = -1, bestLevel2 = -1, ncand = 0;
-    const ProjQuery w = q[iq];
-    if (w.r >= 0.f) {
-        const float x = w.u, y = w.v, r = w.r;
-        const int nMinCellX = max(0, (int)floorf((x - r) * widthInv));
-        const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf((x + r) * widthInv));
-        const int nMinCellY = max(0, (int)floorf((y - r) * heightInv));
-        const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf((y + r) * heightInv));
-        if (nMinCellX < GRID_COLS && nMaxCellX >= 0 && nMinCellY < GRID_ROWS && nMaxCellY >= 0) {
-            const bool bCheckLevels = (w.minL > 0) || (w.maxL >= 0);
-            const unsigned long long* a = reinterpret_cast<const unsigned long long*>(qd) + (size_t)iq * 4;
-            Desc256 da;
-            da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
-            for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
-                for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
-                    const int c = ix * GRID_ROWS + iy;
-                    for (int s = cellStart[c]; s < cellStart[c + 1]; s++) {
-                        const int j = cellItems[s];
-                        const tb_keypoint kp = k1[j];
-                        if (bCheckLevels) {
-                            if (kp.octave < w.minL) continue;
-                            if (w.maxL >= 0 && kp.octave > w.maxL) continue;
-                        }
-                        if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;
-                        ncand++;
-                        if (taken1[j]) continue;
-                        const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d1) + (size_t)j * 4);
-                        if (dist < bestDist) {
-                            bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp.octave; bestIdx = j;
-                        } else if (dist < bestDist2) {
-                            bestLevel2 = kp.octave; bestDist2 = dist;
-                        }
-                    }
-                }
-        }
-    }
-    int32_t* o = best + (size_t)iq * 6;
-    o[0] = bestDist; o[1] = bestDist2; o[2] = bestIdx; o[3] = bestLevel; o[4] = bestLevel2; o[5] = ncand;
-}
-
-int tbk_projection_search(tb_ctx* ctx, int map_overload, const float Tcw[16], const tb_camera* cam, const tb_keypoint* d_k2,
-                          const tb_mappoint* d_mp, const uint8_t* d_mpdesc, int nq, const float* d_sf, int nlevels, float sf0,
-                          float nratio, const tb_keypoint* d_k1, const uint8_t* d_d1, const uint8_t* d_taken1,
-                          const int32_t* d_cellStart, const int32_t* d_cellItems, float widthInv, float heightInv,
-                          void* d_queries, int32_t* d_best, int* d_flag) {
-    if (nq <= 0) return TB_OK;
-    ProjPose P;
-    for (int i = 0; i < 16; i++) P.T[i] = Tcw[i];
-    ProjQuery* q = (ProjQuery*)d_queries;
-    tb_prof_begin(ctx, "k_project");
-    if (map_overload)
-        hipLaunchKernelGGL(k_project_map, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, P, *cam, d_mp, nq, sf0, nratio, q);
-    else
-        hipLaunchKernelGGL(k_project_frame, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, P, *cam, d_k2, d_mp, nq, d_sf,
-                           nlevels, nratio, q, d_flag);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    tb_prof_begin(ctx, "k_window_q");
-    hipLaunchKernelGGL(k_window_q, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, q, d_mpdesc, nq, d_k1, d_d1, d_taken1,
-                       d_cellStart, d_cellItems, widthInv, heightInv, d_best);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -432,7 +242,7 @@ struct ProjBatch {
     tb_match* out; int cap; int32_t* out_counts; int32_t* flags; /* flags[p]: 1 = octave outside the table, 2 = bin outside the histogram */
 };
 
-/* projection + window search of one map point of pair blockIdx.y (k_project_frame + k_window_q fused) */
+/* projection + window search of one map point of pair blockIdx.y */
 __global__ void __launch_bounds__(256)
 k_proj_search_batch(ProjBatch B) {
     const int p = blockIdx.y, i2 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -458,7 +268,7 @@ k_proj_search_batch(ProjBatch B) {
                 else { x = uv[0]; y = uv[1]; r = B.nratio * B.sf[oct]; minL = oct - 1; maxL = oct + 1; search = true; }
             }
         }
-    } else if (!mp.bad) { /* Frame::IsInFrustum (Frame.cpp:370-412) + the window of matcher.cpp:558-567, as k_project_map */
+    } else if (!mp.bad) { /* Frame::IsInFrustum (Frame.cpp:370-412) + the window of matcher.cpp:558-567 */
         float Pc[3], uv[2], Ow[3];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -651,7 +461,7 @@ int tbk_projection_batch(tb_ctx* ctx, int npairs, const float* d_Tcw, const tb_c
 
 /* ------------------------------------------------------------------------------------------------
  * Batched, device-resident Matcher::searchByViolence (matcher.cpp:299-395) on the device-built lookup grids: pair =
- * blockIdx.y; window search per F1 key (k_window's body), then acceptance (th_low, nratio), rotation histogram,
+ * blockIdx.y; window search per F1 key, then acceptance (th_low, nratio), rotation histogram,
  * ComputeThreeMaxima and the reference's output order, one workgroup per pair. */
 struct VioBatch {
     const tb_keypoint* k1; const uint8_t* d1; const int32_t* n1; int pitch1;
@@ -805,43 +615,6 @@ int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const u
     TB_HIP(ctx, hipGetLastError());
     tb_prof_begin(ctx, "k_violence_accept");
     hipLaunchKernelGGL(k_violence_accept_batch, dim3(npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
-}
-
-/* ---- Matcher::searchByBow (matcher.cpp:619-721), the search over shared vocabulary nodes.
- * One thread per QUERY = one feature of F1 that lies in a node both frames have (the host's walk of the two sorted node
- * lists, matcher.cpp:637-698, yields the queries in the reference's emission order): best / second-best Hamming
- * distance over F2's features of that node in list order (:645-669). best[q] = {bestDist1, bestDist2, bestIdx2, 0}.
- * Bound: gather latency (a node holds a handful of features); no SURVEY 8(d) row. */
-__global__ void __launch_bounds__(256)
-k_bow_search(int nq, const int4* __restrict__ queries /* idx1, start2, end2, 0 */, const uint8_t* __restrict__ d1,
-             const uint8_t* __restrict__ d2, const uint32_t* __restrict__ items2, const uint8_t* __restrict__ has_mp2,
-             int map_point_only, int4* __restrict__ best) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    const int4 qu = queries[q];
-    Desc256 a;
-    const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(d1 + 32 * (size_t)qu.x);
-    a.w[0] = pa[0]; a.w[1] = pa[1]; a.w[2] = pa[2]; a.w[3] = pa[3];
-    int bestDist1 = 256, bestIdx2 = -1, bestDist2 = 256;
-    for (int p2 = qu.y; p2 < qu.z; p2++) {
-        const int idx2 = (int)items2[p2];
-        if (map_point_only && !(has_mp2 && has_mp2[idx2])) continue;
-        const int dist = bf_dist(a, reinterpret_cast<const unsigned long long*>(d2 + 32 * (size_t)idx2));
-        if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx2 = idx2; }
-        else if (dist < bestDist2) bestDist2 = dist;
-    }
-    best[q] = make_int4(bestDist1, bestDist2, bestIdx2, 0);
-}
-
-int tbk_bow_search(tb_ctx* ctx, int nq, const void* d_queries, const uint8_t* d_d1, const uint8_t* d_d2, const uint32_t* d_items2,
-                   const uint8_t* d_has_mp2, int map_point_only, void* d_best) {
-    if (nq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_bow_search");
-    hipLaunchKernelGGL(k_bow_search, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, nq, (const int4*)d_queries, d_d1, d_d2, d_items2,
-                       d_has_mp2, map_point_only, (int4*)d_best);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -1,8 +1,8 @@
 /* Host side of libtb_hip.so: the C ABI of include/tb_capi.h on top of the HIP kernels (k_*.hip).
  * No CPU compute fallback lives here: every operator either runs its kernels or returns an error.
  * Host work is limited to set-up arithmetic the reference also does on the host (scale vectors, level
- * sizes, quotas, resize coefficient tables, cell tables), data movement, and the final ordering /
- * histogram bookkeeping of the window matcher.
+ * sizes, quotas, resize coefficient tables, cell tables) and data movement: a single-frame (host) form stages its inputs
+ * and runs the batched kernels on one pair.
  */
 #include "tb_internal.h"
 #include "tb_math.h"
@@ -199,7 +199,7 @@ void tb_destroy(tb_ctx* ctx) {
     hipStreamSynchronize(ctx->stream);
     ctx->plans.clear();
     while (!ctx->live.empty()) tb_extractor_destroy(*ctx->live.begin()); /* plans never outlive their context */
-    for (int i = 0; i < 12; i++)
+    for (int i = 0; i < TB_NSLOTS; i++)
         if (ctx->scratch[i]) hipFree(ctx->scratch[i]);
     for (auto& g : ctx->ba_graphs) hipGraphExecDestroy(g.second);
     prof_drain(ctx);
@@ -771,9 +771,9 @@ int tb_fast_detect(tb_ctx* ctx, const uint8_t* image, int width, int height, int
     void *d_img, *d_out, *d_cnt;
     const int rcap = (nms ? ((width + 1) / 2) * ((height + 1) / 2) : width * height) + 64;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)width * height, &d_img))) return rc;
-    if ((rc = tb_scratch(ctx, 1, (size_t)rcap * 4, &d_out))) return rc;
-    if ((rc = tb_scratch(ctx, 2, 256, &d_cnt))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)width * height, &d_img))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)rcap * 4, &d_out))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, 256, &d_cnt))) return rc;
     TB_HIP(ctx, hipMemcpy2DAsync(d_img, width, image, stride, width, height, hipMemcpyHostToDevice, ctx->stream));
     rc = tbk_fast_image(ctx, (const uint8_t*)d_img, width, height, width, threshold, nms, 9, (uint32_t*)d_out, rcap, (int32_t*)d_cnt);
     if (rc) return rc;
@@ -870,6 +870,31 @@ void tb_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3) {
     else if ((float)max3 < 0.1f * (float)max1) { *ind3 = -1; }
 }
 
+/* ---- the single-frame matchers: host staging around the batched forms, one pair, and one tail */
+/* the next 16-byte aligned piece of a staging slot: returns its offset and moves `end` past it */
+static size_t stage_piece(size_t& end, size_t bytes) {
+    const size_t o = end;
+    end += (bytes + 15) & ~(size_t)15;
+    return o;
+}
+
+/* the end of every single-frame matcher: one synchronisation for the device list's count and flag (cf = count, flag), the
+ * flag reported as the error the host form returns, then *count, the capacity check and the copy-out */
+static int match_tail(tb_ctx* ctx, const tb_match* dout, const int32_t* dcf, int cap, tb_match* out, int* count) {
+    int32_t cf[2] = {0, 0};
+    TB_HIP(ctx, hipMemcpyAsync(cf, dcf, sizeof cf, hipMemcpyDeviceToHost, ctx->stream));
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (cf[1] == 1) return tb_fail(ctx, TB_EINVAL, "searchByProjection: a key octave is outside the scale factors");
+    if (cf[1] == 2) return tb_fail(ctx, TB_EUNSUPPORTED, "rotation bin outside histogram (reference asserts)");
+    *count = cf[0];
+    if (cf[0] > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", cf[0], cap);
+    if (cf[0] > 0 && out) TB_HIP(ctx, hipMemcpy(out, dout, (size_t)cf[0] * sizeof(tb_match), hipMemcpyDeviceToHost));
+    return TB_OK;
+}
+
+#define TB_UPLOAD(ctx, dst, src, bytes) \
+    do { if (bytes) TB_HIP(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, (ctx)->stream)); } while (0)
+
 static int bf_host(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int crosscheck, int filter, float ratio,
                    float min_th, tb_match* out, int cap, int* count) {
     if (!ctx || !count || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2)) return TB_EINVAL;
@@ -879,13 +904,13 @@ static int bf_host(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, in
     const size_t pitch = (size_t)max_n * 32;
     void *dd1, *dd2, *tb, *qb, *dout, *dcnt;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, pitch, &dd1))) return rc;
-    if ((rc = tb_scratch(ctx, 1, pitch, &dd2))) return rc;
-    if ((rc = tb_scratch(ctx, 2, (size_t)max_n * 8, &tb))) return rc;
-    if ((rc = tb_scratch(ctx, 3, (size_t)max_n * 8, &qb))) return rc;
-    if ((rc = tb_scratch(ctx, 4, (size_t)n1 * sizeof(tb_match), &dout))) return rc;
-    if ((rc = tb_scratch(ctx, 5, 256, &dcnt))) return rc;
-    int32_t cnts[3] = {n1, n2, 0};
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, pitch, &dd1))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, pitch, &dd2))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)max_n * 8, &tb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)max_n * 8, &qb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)n1 * sizeof(tb_match), &dout))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, 256, &dcnt))) return rc;
+    int32_t cnts[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and a flag that stays 0 */
     TB_HIP(ctx, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, ctx->stream));
     TB_HIP(ctx, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, ctx->stream));
     TB_HIP(ctx, hipMemcpyAsync(dcnt, cnts, sizeof cnts, hipMemcpyHostToDevice, ctx->stream));
@@ -894,13 +919,7 @@ static int bf_host(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, in
                       max_n, crosscheck, filter, ratio, min_th, (tb_match*)dout, n1, (int32_t*)dcnt + 2,
                       (unsigned long long*)tb, (unsigned long long*)qb);
     if (rc) return rc;
-    int32_t c = 0;
-    TB_HIP(ctx, hipMemcpyAsync(&c, (int32_t*)dcnt + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *count = c;
-    if (c > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", c, cap);
-    if (c > 0 && out) TB_HIP(ctx, hipMemcpy(out, dout, (size_t)c * sizeof(tb_match), hipMemcpyDeviceToHost));
-    return TB_OK;
+    return match_tail(ctx, (const tb_match*)dout, (const int32_t*)dcnt + 2, cap, out, count);
 }
 
 int tb_match_bf(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int crosscheck, tb_match* out, int cap,
@@ -925,8 +944,8 @@ int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, con
     const int max_n = (int)(set_pitch / 32);
     void *tb, *qb;
     int rc;
-    if ((rc = tb_scratch(ctx, 2, (size_t)npairs * max_n * 8, &tb))) return rc;
-    if ((rc = tb_scratch(ctx, 3, (size_t)npairs * max_n * 8, &qb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)npairs * max_n * 8, &tb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)npairs * max_n * 8, &qb))) return rc;
     return tbk_bf_batch(ctx, npairs, desc1, counts1, desc2, counts2, set_pitch, max_n, 1, 1, ratio, min_th, out, cap, out_counts,
                         (unsigned long long*)tb, (unsigned long long*)qb);
 }
@@ -987,8 +1006,8 @@ int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, co
     if (!desc || (fv_keys && (!fv_counts || desc_pitch > 8192))) return TB_EINVAL;
     void *dn = node_ids, *dwt = weights;
     int rc;
-    if (fv_keys && !node_ids && (rc = tb_scratch(ctx, 4, (size_t)nframes * desc_pitch * 4, &dn))) return rc;
-    if (fv_keys && !weights && (rc = tb_scratch(ctx, 5, (size_t)nframes * desc_pitch * 8, &dwt))) return rc;
+    if (fv_keys && !node_ids && (rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)nframes * desc_pitch * 4, &dn))) return rc;
+    if (fv_keys && !weights && (rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)nframes * desc_pitch * 8, &dwt))) return rc;
     return tbk_bow_transform(ctx, voc->nnodes, voc->L, voc->d_child_start, voc->d_child_items, voc->d_desc, voc->d_word_id, voc->d_weight,
                              nframes, desc, counts, desc_pitch, levelsup, word_ids, (int32_t*)dn, (double*)dwt,
                              (unsigned long long*)fv_keys, fv_counts);
@@ -1001,8 +1020,8 @@ int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int 
     if (n == 0) return TB_OK;
     void *dd, *dw, *dn, *dwt;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)n * 32, &dd)) || (rc = tb_scratch(ctx, 1, (size_t)n * 4, &dw)) ||
-        (rc = tb_scratch(ctx, 2, (size_t)n * 4, &dn)) || (rc = tb_scratch(ctx, 3, (size_t)n * 8, &dwt)))
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)n * 32, &dd)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)n * 4, &dw)) ||
+        (rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)n * 4, &dn)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)n * 8, &dwt)))
         return rc;
     hipStream_t s = ctx->stream;
     TB_HIP(ctx, hipMemcpyAsync(dd, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
@@ -1026,7 +1045,7 @@ int tb_search_by_bow_batch_dev(tb_ctx* ctx, int npairs, const tb_keypoint* k1, c
     if (!k1 || !d1 || !fv1 || !fv_counts1 || !k2 || !d2 || !fv2 || !fv_counts2 || !out_counts || !flags || (cap && !out)) return TB_EINVAL;
     void* best;
     int rc;
-    if ((rc = tb_scratch(ctx, 6, (size_t)npairs * pitch1 * 16, &best))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * pitch1 * 16, &best))) return rc;
     return tbk_bow_search_batch(ctx, npairs, k1, d1, pitch1, (const unsigned long long*)fv1, fv_counts1, k2, d2, pitch2,
                                 (const unsigned long long*)fv2, fv_counts2, has_mp2, map_point_only, th_low, nratio, histo_len,
                                 check_orientation, out, cap, out_counts, flags, (int32_t*)best);
@@ -1043,7 +1062,7 @@ int tb_stereo_tracks_to_obs_batch_dev(tb_ctx* ctx, int nframes, const tb_keypoin
     if (!keys_left || !keys_right || !matches || !match_counts || !obs || !obs_counts) return TB_EINVAL;
     void* dsig;
     int rc;
-    if ((rc = tb_scratch(ctx, 4, TB_MAX_LEVELS * sizeof(float), &dsig))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, TB_MAX_LEVELS * sizeof(float), &dsig))) return rc;
     /* the table is a few floats of host memory: staged through a pinned-free async copy (the stream orders it before the kernel) */
     TB_HIP(ctx, hipMemcpyAsync(dsig, inv_sigma2, (size_t)nlevels * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return tbk_stereo_obs(ctx, nframes, keys_left, keys_right, key_pitch, matches, match_counts, match_pitch, K, bf, (const float*)dsig, nlevels,
@@ -1055,87 +1074,49 @@ int tb_search_by_violence(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1,
                           float radius, int th_low, float nratio, int histo_len, int check_orientation, tb_match* out,
                           int cap, int* count) {
     TB_ENTER(ctx);
-    if (!ctx || !count || n1 < 0 || n2 < 0 || histo_len < 1 || img2_width < 1 || img2_height < 1) return TB_EINVAL;
+    if (!ctx || !count || n1 < 0 || n2 < 0 || histo_len < 1 || histo_len > 1024 || img2_width < 1 || img2_height < 1) return TB_EINVAL;
     *count = 0;
     if (n1 == 0) return TB_OK;
     if ((n1 && (!k1 || !d1)) || (n2 && (!k2 || !d2))) return TB_EINVAL;
-    const int GRID_ROWS = 36, GRID_COLS = 120;
-    /* Frame.cpp:30-31: the two inverse factors are swapped in the reference; kept */
-    const float heightInv = (float)GRID_COLS / (float)img2_width;
-    const float widthInv = (float)GRID_ROWS / (float)img2_height;
-    /* Frame::AssignFeaturesToGrid as CSR (insertion order inside a cell = key index order) */
-    std::vector<int32_t> cellOf((size_t)n2), start((size_t)GRID_COLS * GRID_ROWS + 1, 0), items((size_t)std::max(n2, 1));
-    for (int i = 0; i < n2; i++) {
-        const int posX = (int)roundf(k2[i].x * widthInv), posY = (int)roundf(k2[i].y * heightInv);
-        cellOf[i] = (posX < 0 || posX >= GRID_COLS || posY < 0 || posY >= GRID_ROWS) ? -1 : posX * GRID_ROWS + posY;
-        if (cellOf[i] >= 0) start[cellOf[i] + 1]++;
-    }
-    for (size_t c = 0; c < (size_t)GRID_COLS * GRID_ROWS; c++) start[c + 1] += start[c];
-    {
-        std::vector<int32_t> fill(start.begin(), start.end() - 1);
-        for (int i = 0; i < n2; i++)
-            if (cellOf[i] >= 0) items[fill[cellOf[i]]++] = i;
-    }
-    void *dk1, *dd1, *dk2, *dd2, *dst, *dit, *dbest;
+    const size_t p2 = (size_t)std::max(n2, 1), kb = sizeof(tb_keypoint);
+    size_t end = 0;
+    const size_t oK1 = stage_piece(end, n1 * kb), oD1 = stage_piece(end, (size_t)n1 * 32), oK2 = stage_piece(end, p2 * kb),
+                 oD2 = stage_piece(end, p2 * 32), oCs = stage_piece(end, (TB_GRID_CELLS + 1) * 4), oCi = stage_piece(end, p2 * 4),
+                 oOut = stage_piece(end, (size_t)n1 * sizeof(tb_match)), oCnt = stage_piece(end, 16);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)n1 * 32, &dd1))) return rc;
-    if ((rc = tb_scratch(ctx, 1, (size_t)std::max(n2, 1) * 32, &dd2))) return rc;
-    if ((rc = tb_scratch(ctx, 2, (size_t)n1 * sizeof(tb_keypoint), &dk1))) return rc;
-    if ((rc = tb_scratch(ctx, 3, (size_t)std::max(n2, 1) * sizeof(tb_keypoint), &dk2))) return rc;
-    if ((rc = tb_scratch(ctx, 4, start.size() * 4, &dst))) return rc;
-    if ((rc = tb_scratch(ctx, 5, items.size() * 4, &dit))) return rc;
-    if ((rc = tb_scratch(ctx, 6, (size_t)n1 * 16, &dbest))) return rc;
-    TB_HIP(ctx, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dk1, k1, (size_t)n1 * sizeof(tb_keypoint), hipMemcpyHostToDevice, ctx->stream));
-    if (n2 > 0) {
-        TB_HIP(ctx, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(dk2, k2, (size_t)n2 * sizeof(tb_keypoint), hipMemcpyHostToDevice, ctx->stream));
-    }
-    TB_HIP(ctx, hipMemcpyAsync(dst, start.data(), start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dit, items.data(), items.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = tbk_window_match(ctx, (const tb_keypoint*)dk1, (const uint8_t*)dd1, n1, (const tb_keypoint*)dk2, (const uint8_t*)dd2, n2,
-                          (const int32_t*)dst, (const int32_t*)dit, widthInv, heightInv, min_level, max_level, radius,
-                          (int32_t*)dbest);
-    if (rc) return rc;
-    std::vector<int32_t> best((size_t)n1 * 4);
-    TB_HIP(ctx, hipMemcpyAsync(best.data(), dbest, best.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    /* acceptance + rotation histogram, matcher.cpp:352-392 (bookkeeping over <= n1 survivors) */
-    std::vector<tb_match> matches;
-    std::vector<std::vector<int>> rotHist((size_t)histo_len);
-    const float factor = 1.f / (float)histo_len;
-    for (int i1 = 0; i1 < n1; i1++) {
-        const int bestDist = best[4 * i1], bestDist2 = best[4 * i1 + 1], bestIdx = best[4 * i1 + 2];
-        if (best[4 * i1 + 3] == 0) continue;
-        if (bestDist <= th_low && (float)bestDist < (float)bestDist2 * nratio) {
-            tb_match m = {i1, bestIdx, -1, (float)bestDist};
-            matches.push_back(m);
-            if (check_orientation) {
-                float rot = k1[i1].angle - k2[bestIdx].angle;
-                if (rot < 0) rot += 360.f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == histo_len) bin = 0;
-                if (bin < 0 || bin >= histo_len) return tb_fail(ctx, TB_EUNSUPPORTED, "rotation bin %d outside histogram (reference asserts)", bin);
-                rotHist[bin].push_back((int)matches.size() - 1);
-            }
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    const int32_t cnt[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and flag */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oK1, k1, n1 * kb);
+    TB_UPLOAD(ctx, b + oD1, d1, (size_t)n1 * 32);
+    TB_UPLOAD(ctx, b + oK2, k2, n2 * kb);
+    TB_UPLOAD(ctx, b + oD2, d2, (size_t)n2 * 32);
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    const tb_keypoint *dk1 = (const tb_keypoint*)(b + oK1), *dk2 = (const tb_keypoint*)(b + oK2);
+    if ((rc = tbk_grid_build_batch(ctx, 1, dk2, dcnt + 1, (int)p2, img2_width, img2_height, (int32_t*)(b + oCs), (int32_t*)(b + oCi))))
+        return rc;
+    if ((rc = tb_search_by_violence_batch_dev(ctx, 1, dk1, (const uint8_t*)(b + oD1), dcnt, n1, dk2, (const uint8_t*)(b + oD2), dcnt + 1,
+                                              (int)p2, (const int32_t*)(b + oCs), (const int32_t*)(b + oCi), img2_width, img2_height,
+                                              min_level, max_level, radius, th_low, nratio, histo_len, check_orientation,
+                                              (tb_match*)(b + oOut), n1, dcnt + 2, dcnt + 3)))
+        return rc;
+    return match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 2, cap, out, count);
+}
+
+/* one DBoW2 feature vector (CSR: nodes, start, items) as the batched form's key list (node << 32) | feature, nodes ascending and a
+ * node's features in CSR order. With `other` (F2's nodes), F1's nodes that F2 lacks are left out: they can match nothing. */
+static int bow_keys(tb_ctx* ctx, const char* frame, const uint32_t* nodes, const int32_t* start, const uint32_t* items, int nn, int n,
+                    const uint32_t* other, int nother, std::vector<uint64_t>& keys) {
+    for (int a = 0; a < nn; a++) {
+        if (a && nodes[a] <= nodes[a - 1]) return tb_fail(ctx, TB_EINVAL, "searchByBow: node ids of %s not strictly ascending", frame);
+        if (start[a] < 0 || start[a + 1] < start[a]) return tb_fail(ctx, TB_EINVAL, "searchByBow: feature vector offsets");
+        if (other && !std::binary_search(other, other + nother, nodes[a])) continue;
+        for (int p = start[a]; p < start[a + 1]; p++) {
+            if (items[p] >= (uint32_t)n) return tb_fail(ctx, TB_EINVAL, "searchByBow: feature index %u of %s out of range", items[p], frame);
+            keys.push_back((uint64_t)nodes[a] << 32 | items[p]);
         }
     }
-    std::vector<tb_match> good;
-    if (check_orientation) {
-        std::vector<int> sizes((size_t)histo_len);
-        for (int i = 0; i < histo_len; i++) sizes[i] = (int)rotHist[i].size();
-        int ind[3] = {-1, -1, -1};
-        tb_three_maxima(sizes.data(), histo_len, &ind[0], &ind[1], &ind[2]);
-        for (int i = 0; i < histo_len; i++)
-            if (i == ind[0] || i == ind[1] || i == ind[2])
-                for (int item : rotHist[i]) good.push_back(matches[item]);
-    } else {
-        good.swap(matches);
-    }
-    *count = (int)good.size();
-    if ((int)good.size() > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", (int)good.size(), cap);
-    if (out) std::copy(good.begin(), good.end(), out);
     return TB_OK;
 }
 
@@ -1145,214 +1126,109 @@ int tb_search_by_bow(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int 
                      const uint32_t* nodes2, const int32_t* start2, const uint32_t* items2, int nn2, int map_point_only, int th_low,
                      float nratio, int histo_len, int check_orientation, tb_match* out, int cap, int* count) {
     TB_ENTER(ctx);
-    if (!ctx || !count || n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || histo_len < 1 || cap < 0) return TB_EINVAL;
+    if (!ctx || !count || n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || histo_len < 1 || histo_len > 1024 || cap < 0) return TB_EINVAL;
     *count = 0;
     if ((nn1 && (!nodes1 || !start1)) || (nn2 && (!nodes2 || !start2)) || (n1 && (!k1 || !d1)) || (n2 && (!k2 || !d2))) return TB_EINVAL;
-    /* the walk of the two sorted node lists (matcher.cpp:637-698): one query per feature of F1 in a shared node, in the
-     * reference's emission order */
-    struct Q { int32_t idx1, s2, e2, pad; };
-    std::vector<Q> queries;
-    int a = 0, b = 0;
-    const int tot2 = nn2 ? start2[nn2] : 0;
-    while (a < nn1 && b < nn2) {
-        if (nodes1[a] == nodes2[b]) {
-            if (start2[b] < 0 || start2[b + 1] < start2[b] || start2[b + 1] > tot2 || start1[a + 1] < start1[a]) return tb_fail(ctx, TB_EINVAL, "searchByBow: feature vector offsets");
-            for (int p1 = start1[a]; p1 < start1[a + 1]; p1++) {
-                const int idx1 = (int)items1[p1];
-                if (idx1 < 0 || idx1 >= n1) return tb_fail(ctx, TB_EINVAL, "searchByBow: feature index %d of F1 out of range", idx1);
-                queries.push_back(Q{idx1, start2[b], start2[b + 1], 0});
-            }
-            a++; b++;
-        } else if (nodes1[a] < nodes2[b]) {
-            while (a < nn1 && nodes1[a] < nodes2[b]) a++;
-        } else {
-            while (b < nn2 && nodes2[b] < nodes1[a]) b++;
-        }
-    }
-    for (int i = 0; i < tot2; i++)
-        if ((int)items2[i] < 0 || (int)items2[i] >= n2) return tb_fail(ctx, TB_EINVAL, "searchByBow: feature index %u of F2 out of range", items2[i]);
-    const int nq = (int)queries.size();
-    if (nq == 0) return TB_OK;
-    void *dd1, *dd2, *dit, *dq, *dbest, *dmp;
+    std::vector<uint64_t> fv1, fv2;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)n1 * 32, &dd1)) || (rc = tb_scratch(ctx, 1, (size_t)n2 * 32, &dd2)) ||
-        (rc = tb_scratch(ctx, 4, (size_t)std::max(tot2, 1) * 4, &dit)) || (rc = tb_scratch(ctx, 5, (size_t)nq * 16, &dq)) ||
-        (rc = tb_scratch(ctx, 6, (size_t)nq * 16, &dbest)) || (rc = tb_scratch(ctx, 3, (size_t)std::max(n2, 1), &dmp)))
+    if ((rc = bow_keys(ctx, "F2", nodes2, start2, items2, nn2, n2, nullptr, 0, fv2))) return rc;
+    if ((rc = bow_keys(ctx, "F1", nodes1, start1, items1, nn1, n1, nodes2, nn2, fv1))) return rc;
+    if (fv1.empty()) return TB_OK;
+    /* a feature listed under two nodes is queried twice: the pitches cover both the keys and the lists */
+    const int nq = (int)fv1.size(), nf2 = (int)fv2.size();
+    const size_t p1 = (size_t)std::max(n1, nq), p2 = (size_t)std::max({n2, nf2, 1}), kb = sizeof(tb_keypoint);
+    size_t end = 0;
+    const size_t oK1 = stage_piece(end, p1 * kb), oD1 = stage_piece(end, p1 * 32), oF1 = stage_piece(end, p1 * 8),
+                 oK2 = stage_piece(end, p2 * kb), oD2 = stage_piece(end, p2 * 32), oF2 = stage_piece(end, p2 * 8),
+                 oMp = stage_piece(end, p2), oOut = stage_piece(end, (size_t)nq * sizeof(tb_match)), oCnt = stage_piece(end, 16);
+    char* b;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    const int32_t cnt[4] = {nq, nf2, 0, 0}; /* list lengths, then the match count and flag */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oK1, k1, n1 * kb);
+    TB_UPLOAD(ctx, b + oD1, d1, (size_t)n1 * 32);
+    TB_UPLOAD(ctx, b + oF1, fv1.data(), (size_t)nq * 8);
+    TB_UPLOAD(ctx, b + oK2, k2, n2 * kb);
+    TB_UPLOAD(ctx, b + oD2, d2, (size_t)n2 * 32);
+    TB_UPLOAD(ctx, b + oF2, fv2.data(), (size_t)nf2 * 8);
+    if (has_mp2) TB_UPLOAD(ctx, b + oMp, has_mp2, (size_t)n2);
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    if ((rc = tb_search_by_bow_batch_dev(ctx, 1, (const tb_keypoint*)(b + oK1), (const uint8_t*)(b + oD1), (int)p1, (const uint64_t*)(b + oF1),
+                                         dcnt, (const tb_keypoint*)(b + oK2), (const uint8_t*)(b + oD2), (int)p2, (const uint64_t*)(b + oF2),
+                                         dcnt + 1, has_mp2 ? (const uint8_t*)(b + oMp) : nullptr, map_point_only, th_low, nratio, histo_len,
+                                         check_orientation, (tb_match*)(b + oOut), nq, dcnt + 2, dcnt + 3)))
         return rc;
-    hipStream_t s = ctx->stream;
-    TB_HIP(ctx, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dit, items2, (size_t)tot2 * 4, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dq, queries.data(), (size_t)nq * 16, hipMemcpyHostToDevice, s));
-    if (has_mp2) TB_HIP(ctx, hipMemcpyAsync(dmp, has_mp2, (size_t)n2, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipStreamSynchronize(s)); /* queries is a function-lifetime staging buffer */
-    if ((rc = tbk_bow_search(ctx, nq, dq, (const uint8_t*)dd1, (const uint8_t*)dd2, (const uint32_t*)dit, has_mp2 ? (const uint8_t*)dmp : nullptr,
-                             map_point_only, dbest)))
-        return rc;
-    std::vector<int32_t> best((size_t)nq * 4);
-    TB_HIP(ctx, hipMemcpyAsync(best.data(), dbest, best.size() * 4, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipStreamSynchronize(s));
-    /* acceptance + rotation histogram, matcher.cpp:671-717 (bookkeeping over <= nq survivors) */
-    std::vector<tb_match> matches;
-    std::vector<std::vector<int>> rotHist((size_t)histo_len);
-    const float factor = 1.f / (float)histo_len;
-    for (int q = 0; q < nq; q++) {
-        const int bestDist1 = best[4 * q], bestDist2 = best[4 * q + 1], bestIdx2 = best[4 * q + 2];
-        if (bestDist1 < th_low && bestIdx2 >= 0 && (float)bestDist1 < nratio * (float)bestDist2) {
-            const int idx1 = queries[q].idx1;
-            tb_match m = {idx1, bestIdx2, -1, (float)bestDist1};
-            matches.push_back(m);
-            if (check_orientation) {
-                float rot = k1[idx1].angle - k2[bestIdx2].angle;
-                if (rot < 0) rot += 360.f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == histo_len) bin = 0;
-                if (bin < 0 || bin >= histo_len) return tb_fail(ctx, TB_EUNSUPPORTED, "rotation bin %d outside histogram (reference asserts)", bin);
-                rotHist[bin].push_back((int)matches.size() - 1);
-            }
-        }
-    }
-    std::vector<tb_match> good;
-    if (check_orientation) {
-        std::vector<int> sizes((size_t)histo_len);
-        for (int i = 0; i < histo_len; i++) sizes[i] = (int)rotHist[i].size();
-        int ind[3] = {-1, -1, -1};
-        tb_three_maxima(sizes.data(), histo_len, &ind[0], &ind[1], &ind[2]);
-        for (int i = 0; i < histo_len; i++)
-            if (i == ind[0] || i == ind[1] || i == ind[2])
-                for (int item : rotHist[i]) good.push_back(matches[item]);
-    } else {
-        good.swap(matches);
-    }
-    *count = (int)good.size();
-    if ((int)good.size() > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", (int)good.size(), cap);
-    if (out) std::copy(good.begin(), good.end(), out);
-    return TB_OK;
+    return match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 2, cap, out, count);
 }
 
-/* ---- Matcher::searchByProjection, both overloads (matcher.cpp:406-617) */
-namespace {
-struct ProjHost {
-    std::vector<int32_t> best;
-    int bad_octave = 0;
-};
-/* upload F1 (keys, descriptors, taken flags, lookup grid) and the map points, run projection + window search */
-int projection_run(tb_ctx* ctx, int map_overload, const float Tcw1[16], const tb_camera* cam1, int img1_w, int img1_h,
-                   const tb_keypoint* k1, const uint8_t* d1, const uint8_t* taken1, int n1, const tb_keypoint* k2,
-                   const tb_mappoint* mps, const uint8_t* mp_desc, int nq, const float* sf, int nlevels, float nratio,
-                   ProjHost& H) {
-    const int GRID_ROWS = 36, GRID_COLS = 120;
-    const float heightInv = (float)GRID_COLS / (float)img1_w; /* swapped in the reference (Frame.cpp:30-31); kept */
-    const float widthInv = (float)GRID_ROWS / (float)img1_h;
-    std::vector<int32_t> cellOf((size_t)std::max(n1, 1)), start((size_t)GRID_COLS * GRID_ROWS + 1, 0), items((size_t)std::max(n1, 1));
-    for (int i = 0; i < n1; i++) {
-        const int posX = (int)roundf(k1[i].x * widthInv), posY = (int)roundf(k1[i].y * heightInv);
-        cellOf[i] = (posX < 0 || posX >= GRID_COLS || posY < 0 || posY >= GRID_ROWS) ? -1 : posX * GRID_ROWS + posY;
-        if (cellOf[i] >= 0) start[cellOf[i] + 1]++;
-    }
-    for (size_t c = 0; c < (size_t)GRID_COLS * GRID_ROWS; c++) start[c + 1] += start[c];
-    {
-        std::vector<int32_t> fill(start.begin(), start.end() - 1);
-        for (int i = 0; i < n1; i++)
-            if (cellOf[i] >= 0) items[fill[cellOf[i]]++] = i;
-    }
-    const size_t m1 = (size_t)std::max(n1, 1), mq = (size_t)nq;
-    /* slot 7 holds the small arrays back to back (16-byte aligned pieces) */
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t oMp = 0, oTaken = al(oMp + mq * sizeof(tb_mappoint)), oSf = al(oTaken + m1), oQ = al(oSf + (size_t)nlevels * 4),
-                 oFlag = al(oQ + mq * 20), misc = oFlag + 16;
-    void *dd1, *dmd, *dk1, *dk2, *dst, *dit, *dbest, *dmisc;
+/* ---- Matcher::searchByProjection, both overloads (matcher.cpp:406-617). F1 staged with its lookup grid,
+ * the nq map points (k2: their keys, frame overload only) after it. */
+static int projection_host(tb_ctx* ctx, int map_mode, const float Tcw1[16], const tb_camera* cam1, int img1_w, int img1_h,
+                           const tb_keypoint* k1, const uint8_t* d1, const uint8_t* taken1, int n1, const tb_keypoint* k2,
+                           const tb_mappoint* mps, const uint8_t* mp_desc, int nq, const float* sf, int nlevels, float nratio,
+                           float radio, int th_high, int histo_len, int check_orientation, tb_match* out, int cap, int* count) {
+    const size_t p1 = (size_t)std::max(n1, 1), kb = sizeof(tb_keypoint);
+    size_t end = 0;
+    const size_t oT = stage_piece(end, 64), oK1 = stage_piece(end, p1 * kb), oD1 = stage_piece(end, p1 * 32), oTk = stage_piece(end, p1),
+                 oCs = stage_piece(end, (TB_GRID_CELLS + 1) * 4), oCi = stage_piece(end, p1 * 4), oK2 = stage_piece(end, k2 ? nq * kb : 0),
+                 oMp = stage_piece(end, nq * sizeof(tb_mappoint)), oMd = stage_piece(end, (size_t)nq * 32),
+                 oOut = stage_piece(end, (size_t)nq * sizeof(tb_match)), oCnt = stage_piece(end, 16);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, m1 * 32, &dd1))) return rc;
-    if ((rc = tb_scratch(ctx, 1, mq * 32, &dmd))) return rc;
-    if ((rc = tb_scratch(ctx, 2, m1 * sizeof(tb_keypoint), &dk1))) return rc;
-    if ((rc = tb_scratch(ctx, 3, mq * sizeof(tb_keypoint), &dk2))) return rc;
-    if ((rc = tb_scratch(ctx, 4, start.size() * 4, &dst))) return rc;
-    if ((rc = tb_scratch(ctx, 5, items.size() * 4, &dit))) return rc;
-    if ((rc = tb_scratch(ctx, 6, mq * 24, &dbest))) return rc;
-    if ((rc = tb_scratch(ctx, 7, misc, &dmisc))) return rc;
-    char* mb = (char*)dmisc;
-    hipStream_t s = ctx->stream;
-    std::vector<uint8_t> taken(m1, 0);
-    if (taken1) std::copy(taken1, taken1 + n1, taken.begin());
-    if (n1 > 0) {
-        TB_HIP(ctx, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-        TB_HIP(ctx, hipMemcpyAsync(dk1, k1, (size_t)n1 * sizeof(tb_keypoint), hipMemcpyHostToDevice, s));
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    const int32_t cnt[4] = {n1, nq, 0, 0}; /* n1, map points, then the match count and flag */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oT, Tcw1, 64);
+    TB_UPLOAD(ctx, b + oK1, k1, n1 * kb);
+    TB_UPLOAD(ctx, b + oD1, d1, (size_t)n1 * 32);
+    if (taken1) TB_UPLOAD(ctx, b + oTk, taken1, (size_t)n1);
+    else TB_HIP(ctx, hipMemsetAsync(b + oTk, 0, p1, ctx->stream));
+    if (k2) TB_UPLOAD(ctx, b + oK2, k2, nq * kb);
+    TB_UPLOAD(ctx, b + oMp, mps, nq * sizeof(tb_mappoint));
+    TB_UPLOAD(ctx, b + oMd, mp_desc, (size_t)nq * 32);
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    const tb_keypoint* dk1 = (const tb_keypoint*)(b + oK1);
+    const int32_t *cs = (const int32_t*)(b + oCs), *ci = (const int32_t*)(b + oCi);
+    if ((rc = tbk_grid_build_batch(ctx, 1, dk1, dcnt, (int)p1, img1_w, img1_h, (int32_t*)(b + oCs), (int32_t*)(b + oCi)))) return rc;
+    auto run = [&](int check) {
+        const float* dT = (const float*)(b + oT);
+        const uint8_t *dd1 = (const uint8_t*)(b + oD1), *dtk = (const uint8_t*)(b + oTk), *dmd = (const uint8_t*)(b + oMd);
+        const tb_mappoint* dmp = (const tb_mappoint*)(b + oMp);
+        tb_match* dout = (tb_match*)(b + oOut);
+        if (map_mode)
+            return tb_search_by_projection_map_batch_dev(ctx, 1, dT, cam1, img1_w, img1_h, dk1, dd1, dtk, dcnt, (int)p1, cs, ci, dmp, dmd,
+                                                         dcnt + 1, nq, nq, sf, nlevels, nratio, radio, th_high, dout, nq, dcnt + 2, dcnt + 3);
+        return tb_search_by_projection_batch_dev(ctx, 1, dT, cam1, img1_w, img1_h, dk1, dd1, dtk, dcnt, (int)p1, cs, ci,
+                                                 (const tb_keypoint*)(b + oK2), dmp, dmd, dcnt + 1, nq, sf, nlevels, nratio, th_high,
+                                                 histo_len, check, dout, nq, dcnt + 2, dcnt + 3);
+    };
+    if ((rc = run(check_orientation))) return rc;
+    rc = match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 2, cap, out, count);
+    if (rc == TB_EUNSUPPORTED && check_orientation) {
+        /* the histogram's flag (2) overwrites the search's (1), but an octave outside the table is the error the host form
+         * reports first: look again without the histogram */
+        int32_t flag = 0;
+        if (const int e = run(0)) return e;
+        TB_HIP(ctx, hipMemcpyAsync(&flag, dcnt + 3, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+        TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (flag == 1) return tb_fail(ctx, TB_EINVAL, "searchByProjection: a key octave is outside the scale factors");
     }
-    TB_HIP(ctx, hipMemcpyAsync(mb + oTaken, taken.data(), m1, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dmd, mp_desc, mq * 32, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(mb + oMp, mps, mq * sizeof(tb_mappoint), hipMemcpyHostToDevice, s));
-    if (k2) TB_HIP(ctx, hipMemcpyAsync(dk2, k2, mq * sizeof(tb_keypoint), hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(mb + oSf, sf, (size_t)nlevels * 4, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemsetAsync(mb + oFlag, 0, 16, s));
-    TB_HIP(ctx, hipMemcpyAsync(dst, start.data(), start.size() * 4, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dit, items.data(), items.size() * 4, hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipStreamSynchronize(s)); /* the host vectors above go out of use */
-    rc = tbk_projection_search(ctx, map_overload, Tcw1, cam1, (const tb_keypoint*)dk2, (const tb_mappoint*)(mb + oMp),
-                               (const uint8_t*)dmd, nq, (const float*)(mb + oSf), nlevels, sf[0], nratio, (const tb_keypoint*)dk1,
-                               (const uint8_t*)dd1, (const uint8_t*)(mb + oTaken), (const int32_t*)dst, (const int32_t*)dit, widthInv,
-                               heightInv, mb + oQ, (int32_t*)dbest, (int*)(mb + oFlag));
-    if (rc) return rc;
-    H.best.resize(mq * 6);
-    TB_HIP(ctx, hipMemcpyAsync(H.best.data(), dbest, mq * 24, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipMemcpyAsync(&H.bad_octave, mb + oFlag, sizeof(int), hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipStreamSynchronize(s));
-    return TB_OK;
+    return rc;
 }
-}  // namespace
 
 int tb_search_by_projection(tb_ctx* ctx, const float Tcw1[16], const tb_camera* cam1, int img1_width, int img1_height,
                             const tb_keypoint* k1, const uint8_t* d1, const uint8_t* taken1, int n1, const tb_keypoint* k2,
                             const tb_mappoint* mp2, const uint8_t* mp2_desc, int n2, const float* scale_factors, int nlevels,
                             float nratio, int th_high, int histo_len, int check_orientation, tb_match* out, int cap, int* count) {
     TB_ENTER(ctx);
-    if (!ctx || !count || !Tcw1 || !cam1 || n1 < 0 || n2 < 0 || histo_len < 1 || nlevels < 1 || !scale_factors || img1_width < 1 ||
-        img1_height < 1)
+    if (!ctx || !count || !Tcw1 || !cam1 || n1 < 0 || n2 < 0 || histo_len < 1 || histo_len > 1024 || nlevels < 1 ||
+        nlevels > TB_MAX_LEVELS * 2 || !scale_factors || img1_width < 1 || img1_height < 1)
         return TB_EINVAL;
     *count = 0;
     if (n2 == 0) return TB_OK;
     if ((n1 && (!k1 || !d1)) || !k2 || !mp2 || !mp2_desc) return TB_EINVAL;
-    ProjHost H;
-    int rc = projection_run(ctx, 0, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, k2, mp2, mp2_desc, n2, scale_factors,
-                            nlevels, nratio, H);
-    if (rc) return rc;
-    if (H.bad_octave) return tb_fail(ctx, TB_EINVAL, "searchByProjection: a key octave is outside the %d scale factors", nlevels);
-    /* acceptance + rotation histogram, matcher.cpp:483-530 (bookkeeping over <= n2 survivors) */
-    std::vector<tb_match> matches;
-    std::vector<std::vector<int>> rotHist((size_t)histo_len);
-    const float factor = 1.0f / (float)histo_len;
-    for (int i2 = 0; i2 < n2; i2++) {
-        const int bestDist = H.best[6 * (size_t)i2], bestIdx1 = H.best[6 * (size_t)i2 + 2];
-        if (H.best[6 * (size_t)i2 + 5] == 0 || bestIdx1 < 0) continue;
-        if (bestDist <= th_high) {
-            tb_match m = {bestIdx1, i2, -1, (float)bestDist};
-            matches.push_back(m);
-            if (check_orientation) {
-                float rot = k2[i2].angle - k1[bestIdx1].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == histo_len) bin = 0;
-                if (bin < 0 || bin >= histo_len) return tb_fail(ctx, TB_EUNSUPPORTED, "rotation bin %d outside histogram (reference asserts)", bin);
-                rotHist[bin].push_back((int)matches.size() - 1);
-            }
-        }
-    }
-    std::vector<tb_match> good;
-    if (check_orientation) {
-        std::vector<int> sizes((size_t)histo_len);
-        for (int i = 0; i < histo_len; i++) sizes[i] = (int)rotHist[i].size();
-        int ind[3] = {-1, -1, -1};
-        tb_three_maxima(sizes.data(), histo_len, &ind[0], &ind[1], &ind[2]);
-        for (int i = 0; i < histo_len; i++)
-            if (i == ind[0] || i == ind[1] || i == ind[2])
-                for (int item : rotHist[i]) good.push_back(matches[item]);
-    } else {
-        good.swap(matches);
-    }
-    *count = (int)good.size();
-    if ((int)good.size() > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", (int)good.size(), cap);
-    if (out) std::copy(good.begin(), good.end(), out);
-    return TB_OK;
+    return projection_host(ctx, 0, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, k2, mp2, mp2_desc, n2, scale_factors, nlevels,
+                           nratio, 0.f, th_high, histo_len, check_orientation, out, cap, count);
 }
 
 int tb_search_by_projection_map(tb_ctx* ctx, const float Tcw1[16], const tb_camera* cam1, int img1_width, int img1_height,
@@ -1360,29 +1236,14 @@ int tb_search_by_projection_map(tb_ctx* ctx, const float Tcw1[16], const tb_came
                                 const uint8_t* mp_desc, int nmp, const float* scale_factors, int nlevels, float nratio, float radio,
                                 int th_high, tb_match* out, int cap, int* count) {
     TB_ENTER(ctx);
-    if (!ctx || !count || !Tcw1 || !cam1 || n1 < 0 || nmp < 0 || nlevels < 1 || !scale_factors || img1_width < 1 || img1_height < 1)
+    if (!ctx || !count || !Tcw1 || !cam1 || n1 < 0 || nmp < 0 || nlevels < 1 || nlevels > TB_MAX_LEVELS * 2 || !scale_factors ||
+        img1_width < 1 || img1_height < 1)
         return TB_EINVAL;
     *count = 0;
     if (nmp == 0) return TB_OK;
     if ((n1 && (!k1 || !d1)) || !mps || !mp_desc) return TB_EINVAL;
-    ProjHost H;
-    int rc = projection_run(ctx, 1, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, nullptr, mps, mp_desc, nmp,
-                            scale_factors, nlevels, nratio, H);
-    if (rc) return rc;
-    std::vector<tb_match> matches;
-    for (int im = 0; im < nmp; im++) { /* ratio test, matcher.cpp:606-613 */
-        const int32_t* b = &H.best[6 * (size_t)im];
-        if (b[5] == 0 || b[2] < 0) continue;
-        if (b[0] <= th_high) {
-            if (b[3] == b[4] && (float)b[0] > radio * (float)b[1]) continue;
-            tb_match m = {b[2], im, -1, (float)b[0]};
-            matches.push_back(m);
-        }
-    }
-    *count = (int)matches.size();
-    if ((int)matches.size() > cap) return tb_fail(ctx, TB_ECAPACITY, "matches: %d, capacity %d", (int)matches.size(), cap);
-    if (out) std::copy(matches.begin(), matches.end(), out);
-    return TB_OK;
+    return projection_host(ctx, 1, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, nullptr, mps, mp_desc, nmp, scale_factors,
+                           nlevels, nratio, radio, th_high, 1, 0, out, cap, count);
 }
 
 /* ---- device-resident lookup grid + batched projection search */
@@ -1408,7 +1269,7 @@ int tb_search_by_projection_batch_dev(tb_ctx* ctx, int npairs, const float* Tcw1
     if (!Tcw1 || !k1 || !d1 || !taken1 || !n1 || !cell_start || !cell_items || !k2 || !mp2 || !mp2_desc || !n2 || !out || !out_counts || !flags)
         return TB_EINVAL;
     void* dbest;
-    int rc = tb_scratch(ctx, 6, (size_t)npairs * pitch2 * 6 * sizeof(int32_t), &dbest);
+    int rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * pitch2 * 6 * sizeof(int32_t), &dbest);
     if (rc) return rc;
     return tbk_projection_batch(ctx, npairs, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, pitch1, cell_start, cell_items, k2, mp2,
                                 mp2_desc, n2, pitch2, scale_factors, nlevels, nratio, th_high, histo_len, check_orientation,
@@ -1429,7 +1290,7 @@ int tb_search_by_projection_map_batch_dev(tb_ctx* ctx, int npairs, const float* 
     if (!Tcw1 || !k1 || !d1 || !taken1 || !n1 || !cell_start || !cell_items || !mps || !mp_desc || !nmp || !out || !out_counts || !flags)
         return TB_EINVAL;
     void* dbest;
-    int rc = tb_scratch(ctx, 6, (size_t)npairs * max_nmp * 6 * sizeof(int32_t), &dbest);
+    int rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * max_nmp * 6 * sizeof(int32_t), &dbest);
     if (rc) return rc;
     return tbk_projection_batch(ctx, npairs, Tcw1, cam1, img1_width, img1_height, k1, d1, taken1, n1, pitch1, cell_start, cell_items,
                                 nullptr, mps, mp_desc, nmp, mp_pitch, scale_factors, nlevels, nratio, th_high, 1, 0, (int32_t*)dbest, out,
@@ -1447,7 +1308,7 @@ int tb_search_by_violence_batch_dev(tb_ctx* ctx, int npairs, const tb_keypoint* 
     if (npairs == 0) return TB_OK;
     if (!k1 || !d1 || !n1 || !k2 || !d2 || !n2 || !cell_start2 || !cell_items2 || !out || !out_counts || !flags) return TB_EINVAL;
     void* dbest;
-    int rc = tb_scratch(ctx, 6, (size_t)npairs * pitch1 * 4 * sizeof(int32_t), &dbest);
+    int rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * pitch1 * 4 * sizeof(int32_t), &dbest);
     if (rc) return rc;
     return tbk_violence_batch(ctx, npairs, k1, d1, n1, pitch1, k2, d2, n2, pitch2, cell_start2, cell_items2, img2_width, img2_height,
                               min_level, max_level, radius, th_low, nratio, histo_len, check_orientation, (int32_t*)dbest, out, cap,
@@ -1462,7 +1323,7 @@ int tb_pose_opt_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const f
     if (!ctx || nproblems < 0 || !K || !Tcw_in || !obs || !counts || !outlier || !Tcw_out || !n_inliers || obs_pitch < 1)
         return TB_EINVAL;
     void* derr;
-    int rc = tb_scratch(ctx, 7, (size_t)nproblems * obs_pitch * 3 * sizeof(double), &derr);
+    int rc = tb_scratch(ctx, TB_SLOT_LK, (size_t)nproblems * obs_pitch * 3 * sizeof(double), &derr);
     if (rc) return rc;
     return tbk_pose_batch(ctx, nproblems, K, Tcw_in, obs, counts, obs_pitch, outlier, Tcw_out, n_inliers, stats, (double*)derr);
 }
@@ -1474,9 +1335,9 @@ int tb_pose_opt(tb_ctx* ctx, const double K[4], const float Tcw_in[16], const tb
     const int pitch = std::max(n, 1);
     void *dobs, *dmisc, *dout;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)pitch * sizeof(tb_obs), &dobs))) return rc;
-    if ((rc = tb_scratch(ctx, 1, (size_t)pitch, &dout))) return rc;
-    if ((rc = tb_scratch(ctx, 2, 512, &dmisc))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)pitch * sizeof(tb_obs), &dobs))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)pitch, &dout))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, 512, &dmisc))) return rc;
     /* dmisc: Tin[16] f32 | Tout[16] f32 | count i32 | ninl i32 | stats[8] f64 (at byte 192) */
     float* dTin = (float*)dmisc;
     float* dTout = dTin + 16;
@@ -1512,7 +1373,7 @@ int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf,
     if (nwindows == 0) return TB_OK;
     const size_t wb = tbk_local_ba_work_bytes(ctx, nwindows, nkf, nfixed, npt, obs_pitch);
     void* dwork;
-    int rc = tb_scratch(ctx, 6, wb, &dwork);
+    int rc = tb_scratch(ctx, TB_SLOT_WORK, wb, &dwork);
     if (rc) return rc;
     return tbk_local_ba_batch(ctx, nwindows, K, nkf, nfixed, poses, npt, pts, obs, obs_counts, obs_pitch, iters, stats, dwork, wb);
 }
@@ -1530,10 +1391,10 @@ int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* pose
     std::stable_sort(sorted.begin(), sorted.end(), [](const tb_ba_obs& a, const tb_ba_obs& b) { return a.pt < b.pt; });
     void *dposes, *dpts, *dobs, *dmisc;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)nkf * 64, &dposes))) return rc;
-    if ((rc = tb_scratch(ctx, 1, (size_t)npt * 12, &dpts))) return rc;
-    if ((rc = tb_scratch(ctx, 2, (size_t)nobs * sizeof(tb_ba_obs), &dobs))) return rc;
-    if ((rc = tb_scratch(ctx, 3, 256, &dmisc))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)nkf * 64, &dposes))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)npt * 12, &dpts))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)nobs * sizeof(tb_ba_obs), &dobs))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, 256, &dmisc))) return rc;
     double* dstats = (double*)dmisc;
     int32_t* dcnt = (int32_t*)((char*)dmisc + 64);
     int32_t cnt = nobs;
@@ -1560,7 +1421,7 @@ int tb_clahe_dev(tb_ctx* ctx, const uint8_t* src, int width, int height, int str
     if (!ctx || !src || !dst || width < 1 || height < 1 || stride < width || dst_stride < width || tiles_x < 1 || tiles_y < 1) return TB_EINVAL;
     void* lut;
     int rc;
-    if ((rc = tb_scratch(ctx, 6, (size_t)tiles_x * tiles_y * 256, &lut))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)tiles_x * tiles_y * 256, &lut))) return rc;
     return tbk_clahe(ctx, 1, src, width, height, stride, 0, clip_limit, tiles_x, tiles_y, dst, dst_stride, 0, (uint8_t*)lut);
 }
 
@@ -1570,8 +1431,8 @@ int tb_clahe(tb_ctx* ctx, const uint8_t* src, int width, int height, int stride,
     if (!ctx || !src || !dst || width < 1 || height < 1 || stride < width || dst_stride < width || tiles_x < 1 || tiles_y < 1) return TB_EINVAL;
     void *ds, *dd;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, (size_t)stride * height, &ds))) return rc;
-    if ((rc = tb_scratch(ctx, 1, (size_t)dst_stride * height, &dd))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)stride * height, &ds))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)dst_stride * height, &dd))) return rc;
     TB_HIP(ctx, hipMemcpyAsync(ds, src, (size_t)stride * height, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = tb_clahe_dev(ctx, (const uint8_t*)ds, width, height, stride, clip_limit, tiles_x, tiles_y, (uint8_t*)dd, dst_stride))) return rc;
     TB_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, dd, dst_stride, width, height, hipMemcpyDeviceToHost, ctx->stream));
@@ -1587,7 +1448,7 @@ int tb_optical_flow_pyr_lk_dev(tb_ctx* ctx, const uint8_t* prev, const uint8_t* 
     if (max_level < 0 || max_level > 5) return tb_fail(ctx, TB_EUNSUPPORTED, "optical flow: max_level %d (0..5)", max_level);
     void* work;
     int rc;
-    if ((rc = tb_scratch(ctx, 7, tbk_lk_work_bytes(width, height, max_level, 1), &work))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_LK, tbk_lk_work_bytes(width, height, max_level, 1), &work))) return rc;
     return tbk_lk_track(ctx, 1, prev, next, width, height, stride, 0, prev_pts, nullptr, n, n, win, max_level, next_pts, status, err, work,
                         nullptr);
 }
@@ -1602,7 +1463,7 @@ int tb_optical_flow_pyr_lk_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* pre
     if (max_level < 0 || max_level > 5) return tb_fail(ctx, TB_EUNSUPPORTED, "optical flow: max_level %d (0..5)", max_level);
     void* work;
     int rc;
-    if ((rc = tb_scratch(ctx, 7, tbk_lk_work_bytes(width, height, max_level, npairs), &work))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_LK, tbk_lk_work_bytes(width, height, max_level, npairs), &work))) return rc;
     return tbk_lk_track(ctx, npairs, prev, next, width, height, stride, image_pitch, prev_pts, counts, pts_pitch, pts_pitch, win, max_level,
                         next_pts, status, err, work, nullptr);
 }
@@ -1617,13 +1478,13 @@ int tb_optical_flow_pyr_lk(tb_ctx* ctx, const uint8_t* prev, const uint8_t* next
     const size_t img = (size_t)stride * height, np2 = (size_t)std::max(n, 1) * 2 * sizeof(float);
     void *dp, *dn, *dpts, *dout, *dst, *derr, *work;
     int rc;
-    if ((rc = tb_scratch(ctx, 0, img, &dp))) return rc;
-    if ((rc = tb_scratch(ctx, 1, img, &dn))) return rc;
-    if ((rc = tb_scratch(ctx, 2, np2, &dpts))) return rc;
-    if ((rc = tb_scratch(ctx, 3, np2, &dout))) return rc;
-    if ((rc = tb_scratch(ctx, 4, (size_t)std::max(n, 1), &dst))) return rc;
-    if ((rc = tb_scratch(ctx, 5, (size_t)std::max(n, 1) * sizeof(float), &derr))) return rc;
-    if ((rc = tb_scratch(ctx, 7, tbk_lk_work_bytes(width, height, max_level, 1), &work))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, img, &dp))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, img, &dn))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, np2, &dpts))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, np2, &dout))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)std::max(n, 1), &dst))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)std::max(n, 1) * sizeof(float), &derr))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_LK, tbk_lk_work_bytes(width, height, max_level, 1), &work))) return rc;
     TB_HIP(ctx, hipMemcpyAsync(dp, prev, img, hipMemcpyHostToDevice, ctx->stream));
     TB_HIP(ctx, hipMemcpyAsync(dn, next, img, hipMemcpyHostToDevice, ctx->stream));
     if (n) TB_HIP(ctx, hipMemcpyAsync(dpts, prev_pts, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -1694,14 +1555,14 @@ int tb_search_by_opflow_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* img1, 
     const uint8_t* next = img1;
     if (equalized) { /* matcher.cpp:736-739: img1 = F1->Equalize() (Frame.cpp:453-458) */
         void *eq, *lut;
-        if ((rc = tb_scratch(ctx, 5, (size_t)npairs * image_pitch, &eq))) return rc;
-        if ((rc = tb_scratch(ctx, 6, (size_t)npairs * 8 * 8 * 256, &lut))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)npairs * image_pitch, &eq))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * 8 * 8 * 256, &lut))) return rc;
         if ((rc = tbk_clahe(ctx, npairs, img1, width, height, stride, image_pitch, 3.0, 8, 8, (uint8_t*)eq, stride, image_pitch, (uint8_t*)lut))) return rc;
         next = (const uint8_t*)eq;
     }
     if (pts_pitch) {
         void* work;
-        if ((rc = tb_scratch(ctx, 7, tbk_lk_work_bytes(width, height, 3, npairs), &work))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_LK, tbk_lk_work_bytes(width, height, 3, npairs), &work))) return rc;
         /* matcher.cpp:744: calcOpticalFlowPyrLK(img2, img1, keys of F2, cur_points, ..., Size(21, 21), 3) */
         if ((rc = tbk_lk_track(ctx, npairs, img2, next, width, height, stride, image_pitch, keys2_xy, counts, pts_pitch, pts_pitch, 21, 3,
                                cur_points, status, nullptr, work, nullptr)))
@@ -1712,8 +1573,8 @@ int tb_search_by_opflow_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* img1, 
         /* matcher.cpp:751-755: rejectWithF(cur_points, F2->GetCVKeys(), status); then the matches of what is left (pairs with
          * 8..14 tracked points take cv::findFundamentalMat's LMedS branch inside the same kernel, as in tb_reject_with_f) */
         void *work, *fl;
-        if ((rc = tb_scratch(ctx, 8, tbk_ransac_work_bytes(npairs, pts_pitch), &work))) return rc;
-        if ((rc = tb_scratch(ctx, 9, (size_t)npairs * sizeof(int32_t), &fl))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(npairs, pts_pitch), &work))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, (size_t)npairs * sizeof(int32_t), &fl))) return rc;
         if ((rc = tbk_ransac_f(ctx, npairs, cur_points, keys2_xy, status, counts, pts_pitch, 0, 1.0, 0.99, work, (int32_t*)fl, nullptr, nullptr)))
             return rc;
         rc = tbk_flow_accept(ctx, npairs, cur_points, status, counts, pts_pitch, cam1->width, cam1->height, out, cap, out_counts);
@@ -1727,8 +1588,8 @@ static int ransac_host(tb_ctx* ctx, const float* p1, const float* p2, int n, uin
     void *d1, *d2, *dst, *work, *misc;
     int rc;
     const size_t nb = (size_t)std::max(n, 1) * 2 * sizeof(float);
-    if ((rc = tb_scratch(ctx, 0, nb, &d1)) || (rc = tb_scratch(ctx, 1, nb, &d2)) || (rc = tb_scratch(ctx, 2, (size_t)std::max(n, 1), &dst)) ||
-        (rc = tb_scratch(ctx, 8, tbk_ransac_work_bytes(1, n), &work)) || (rc = tb_scratch(ctx, 9, 256, &misc)))
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, nb, &d1)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE1, nb, &d2)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)std::max(n, 1), &dst)) ||
+        (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(1, n), &work)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, 256, &misc)))
         return rc;
     hipStream_t s = ctx->stream;
     TB_HIP(ctx, hipMemcpyAsync(d1, p1, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1775,8 +1636,8 @@ int tb_reject_with_f_batch_dev(tb_ctx* ctx, int npairs, const float* cur_pts, co
     if (!cur_pts || !last_pts || !status) return TB_EINVAL;
     void *work, *fl;
     int rc;
-    if ((rc = tb_scratch(ctx, 8, tbk_ransac_work_bytes(npairs, pts_pitch), &work))) return rc;
-    if ((rc = tb_scratch(ctx, 9, (size_t)npairs * sizeof(int32_t), &fl))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(npairs, pts_pitch), &work))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, (size_t)npairs * sizeof(int32_t), &fl))) return rc;
     return tbk_ransac_f(ctx, npairs, cur_pts, last_pts, status, counts, pts_pitch, 0, 1.0, 0.99, work, (int32_t*)fl, nullptr, nullptr);
 }
 
@@ -1800,8 +1661,8 @@ int tb_add_map_points_by_stereo_batch_dev(tb_ctx* ctx, int npairs, const uint8_t
     if (!depth || !cur_points || !status || !keys_xy) return TB_EINVAL;
     void *m, *mc;
     int rc;
-    if ((rc = tb_scratch(ctx, 10, (size_t)npairs * pts_pitch * sizeof(tb_match), &m))) return rc;
-    if ((rc = tb_scratch(ctx, 11, (size_t)npairs * sizeof(int32_t), &mc))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STEREO_MATCHES, (size_t)npairs * pts_pitch * sizeof(tb_match), &m))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STEREO_COUNTS, (size_t)npairs * sizeof(int32_t), &mc))) return rc;
     /* LocalBA.cpp:54: matcher->searchByOPFlow(stereo_frame, current_frame, pts, true, true) */
     if ((rc = tb_search_by_opflow_batch_dev(ctx, npairs, img_stereo, img_current, width, height, stride, image_pitch, cam_stereo, keys_xy,
                                             counts, pts_pitch, 1, 1, cur_points, status, (tb_match*)m, pts_pitch, (int32_t*)mc)))
@@ -1924,10 +1785,10 @@ int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
     /* every scratch slot the step's operators use, at its largest size now: a step never grows one (growth synchronises) */
     const size_t pitch = img;
     void* d;
-    if ((rc = tb_scratch(ctx, 5, S * pitch, &d)) || (rc = tb_scratch(ctx, 6, S * 8 * 8 * 256, &d)) ||
-        (rc = tb_scratch(ctx, 7, std::max(tbk_lk_work_bytes(p->width, p->height, 3, nseq), S * P * 3 * sizeof(double)), &d)) ||
-        (rc = tb_scratch(ctx, 8, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, 9, S * sizeof(int32_t), &d)) ||
-        (rc = tb_scratch(ctx, 10, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, 11, S * sizeof(int32_t), &d)))
+    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, S * pitch, &d)) || (rc = tb_scratch(ctx, TB_SLOT_WORK, S * 8 * 8 * 256, &d)) ||
+        (rc = tb_scratch(ctx, TB_SLOT_LK, std::max(tbk_lk_work_bytes(p->width, p->height, 3, nseq), S * P * 3 * sizeof(double)), &d)) ||
+        (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, S * sizeof(int32_t), &d)) ||
+        (rc = tb_scratch(ctx, TB_SLOT_STEREO_MATCHES, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, TB_SLOT_STEREO_COUNTS, S * sizeof(int32_t), &d)))
         return rc;
     *out = vu.release();
     return TB_OK;

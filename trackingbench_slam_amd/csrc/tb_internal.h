@@ -15,6 +15,26 @@
 #define TB_MAX_LEVELS 16
 #define TB_BORDER 16          /* EDGE_THRESHOLD - 3, ORBextractor.cpp:749 */
 #define TB_NODE_CAP_MAX 2048  /* quadtree list capacity that fits LDS (k_octree.hip) */
+#define TB_GRID_CELLS (120 * 36) /* Frame's key lookup grid, FRAME_GRID_COLS x FRAME_GRID_ROWS */
+
+/* tb_scratch slots. A slot keeps what a call put there until the next call that takes it: host forms stage in 0-5, _dev
+ * forms keep their work in 6-11, and an entry point that chains others (stereo -> opflow -> LK -> RANSAC, the VO step)
+ * must not hand them a slot it still reads. */
+enum {
+    TB_SLOT_STAGE0 = 0,         /* host forms: staged inputs and outputs (the single-frame matchers: all of them) */
+    TB_SLOT_STAGE1 = 1,         /* host forms: staged inputs and outputs */
+    TB_SLOT_STAGE2 = 2,         /* host forms; tb_search_by_bf_batch_dev: best match per train descriptor */
+    TB_SLOT_STAGE3 = 3,         /* host forms; tb_search_by_bf_batch_dev: best match per query descriptor */
+    TB_SLOT_STAGE4 = 4,         /* host forms; tb_bow_transform_batch_dev: node ids; tb_stereo_tracks_to_obs_batch_dev: sigma table */
+    TB_SLOT_STAGE5 = 5,         /* host forms; tb_bow_transform_batch_dev: weights; tb_search_by_opflow_batch_dev: equalised images */
+    TB_SLOT_WORK = 6,           /* _dev forms: one call's work (matchers' best rows, local BA, CLAHE tables) */
+    TB_SLOT_LK = 7,             /* LK pyramids (tbk_lk_work_bytes); tb_pose_opt_batch_dev: residuals */
+    TB_SLOT_RANSAC = 8,         /* tbk_ransac_f work */
+    TB_SLOT_RANSAC_FLAGS = 9,   /* tbk_ransac_f flags (host form: flags, F and iterations) */
+    TB_SLOT_STEREO_MATCHES = 10, /* tb_add_map_points_by_stereo_batch_dev: the opflow matches it does not return */
+    TB_SLOT_STEREO_COUNTS = 11, /* tb_add_map_points_by_stereo_batch_dev: their counts */
+    TB_NSLOTS = 12
+};
 
 struct tb_ctx {
     int device = 0;
@@ -36,8 +56,8 @@ struct tb_ctx {
     std::vector<hipEvent_t> prof_pool;
     std::map<std::string, std::pair<long, double>> prof_acc;
     /* grow-only device scratch for the matcher / pose entry points */
-    void* scratch[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_cap[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* scratch[TB_NSLOTS] = {};
+    size_t scratch_cap[TB_NSLOTS] = {};
 };
 
 int tb_fail(tb_ctx* ctx, int code, const char* fmt, ...);
@@ -170,18 +190,11 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
                  const int32_t* c2, size_t set_pitch, int max_n, int crosscheck, int filter, float ratio,
                  float min_th, tb_match* out, int cap, int32_t* out_counts, unsigned long long* d_tbest,
                  unsigned long long* d_qbest);
-int tbk_window_match(tb_ctx* ctx, const tb_keypoint* d_k1, const uint8_t* d_d1, int n1, const tb_keypoint* d_k2,
-                     const uint8_t* d_d2, int n2, const int32_t* d_cellStart, const int32_t* d_cellItems,
-                     float widthInv, float heightInv, int min_level, int max_level, float r,
-                     int32_t* d_best /* n1 x 4: bestDist, bestDist2, bestIdx, #candidates */);
 int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, const int32_t* d_n1, int pitch1,
                        const tb_keypoint* d_k2, const uint8_t* d_d2, const int32_t* d_n2, int pitch2, const int32_t* d_cellStart,
                        const int32_t* d_cellItems, int img2_w, int img2_h, int min_level, int max_level, float radius, int th_low,
                        float nratio, int histo_len, int check_orientation, int32_t* d_best, tb_match* d_out, int cap,
                        int32_t* d_out_counts, int32_t* d_flags);
-/* searchByBow's search over shared vocabulary nodes (queries: int4 idx1, start2, end2, 0; best: int4) */
-int tbk_bow_search(tb_ctx* ctx, int nq, const void* d_queries, const uint8_t* d_d1, const uint8_t* d_d2, const uint32_t* d_items2,
-                   const uint8_t* d_has_mp2, int map_point_only, void* d_best);
 /* device-resident lookup grids and the batched searchByProjection(F1, F2) on them */
 int tbk_grid_build_batch(tb_ctx* ctx, int nframes, const tb_keypoint* d_keys, const int32_t* d_counts, int key_pitch, int img_w,
                          int img_h, int32_t* d_cellStart, int32_t* d_cellItems);
@@ -191,12 +204,6 @@ int tbk_projection_batch(tb_ctx* ctx, int npairs, const float* d_Tcw, const tb_c
                          const uint8_t* d_mp2d, const int32_t* d_n2, int pitch2, const float* sf, int nlevels, float nratio,
                          int th_high, int histo_len, int check_orientation, int32_t* d_best, tb_match* d_out, int cap,
                          int32_t* d_out_counts, int32_t* d_flags, int map_mode, float radio, int max_n2);
-/* searchByProjection: project nq map points into F1 and search F1's lookup grid; best[6 nq] */
-int tbk_projection_search(tb_ctx* ctx, int map_overload, const float Tcw[16], const tb_camera* cam, const tb_keypoint* d_k2,
-                          const tb_mappoint* d_mp, const uint8_t* d_mpdesc, int nq, const float* d_sf, int nlevels, float sf0,
-                          float nratio, const tb_keypoint* d_k1, const uint8_t* d_d1, const uint8_t* d_taken1,
-                          const int32_t* d_cellStart, const int32_t* d_cellItems, float widthInv, float heightInv,
-                          void* d_queries, int32_t* d_best, int* d_flag);
 int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_start, const int32_t* d_child_items, const uint8_t* d_vdesc,
                       const int32_t* d_word_id, const double* d_weight, int nframes, const uint8_t* d_desc, const int32_t* d_counts,
                       int desc_pitch, int levelsup, int32_t* d_word_ids, int32_t* d_node_ids, double* d_weights,
