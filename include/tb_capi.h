@@ -429,6 +429,47 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
                     const int32_t** key_counts, const tb_obs** obs, const int32_t** obs_counts, const int32_t** n_inliers,
                     const uint8_t** outlier, int* key_pitch, int* frame);
 
+/* The tracker of the loop: test_kitti's four tracking lines (:711-716) are switched by commenting them in and out; besides
+ * optical flow (:716) the two descriptor trackers named with full arguments run here:
+ *   TB_VO_BF        searchByBF(cur, key_frame, 0, 5, 10, 30) (:712): only the whole-set branch exists (matcher.cpp:177), so
+ *                   (min_level, max_level) must be (0, nlevels) -- Frame::GetMaxLevel() returns nLevels -- else TB_EUNSUPPORTED
+ *   TB_VO_VIOLENCE  searchByViolence(cur, key_frame, 0, 5, 50) (:713) with the Matcher's TH_LOW, nRatio, HISTO_LENGTH and
+ *                   checkOrientation as setBowParam(50, 100, 30, true, 6) (:709) leaves them: 50, 6, 30, 1; histo_len in 1..1024,
+ *                   radius > 0 and min_level <= max_level (TB_EINVAL otherwise)
+ * A descriptor frame t (test_vo_1 :169-300 is the same loop written out):
+ *   extract   ORB operator()(pyramid, target, init_th, min_th) on every left image; the records / descriptors are the frame's keys
+ *   tracking  t > 0: the matcher, current frame (query) against the last keyframe (train); for every match whose keyframe entry
+ *             trainIdx has a map point, key queryIdx gets it (Frame::AddMapPoint overwrites: a later match in list order wins;
+ *             both matchers emit each queryIdx at most once); PoseOptimization from the last frame's pose on one row per key
+ *             with a map point, IN KEY ORDER (LocalBA.cpp:333-363): px = the key, Xw = its map point, invSigma2 =
+ *             invLevelSigma2[octave]; fewer than 3 rows hold the pose and n_inliers = 0
+ *   keyframe  t % keyframe_every == 0: test_kitti's second ORB call on the same pyramid (:774-785) returns the same keys, so
+ *             SetKeys resizes m to m and keeps every carried map point: it is not run again; then AddMapPointsByStereo and the new
+ *             map points exactly as the optical-flow loop makes them; the frame becomes the keyframe (its records, descriptors,
+ *             map points and, for violence, its lookup grid -- built once per keyframe)
+ * As for optical flow, after the first step a step makes no host synchronisation and no host <-> device copy; the matcher's flags
+ * stay on the device (tb_vo_tracker_state_dev; violence with factor = 1 / HISTO_LENGTH never flags). */
+enum { TB_VO_OPFLOW = 0, TB_VO_BF = 1, TB_VO_VIOLENCE = 2 };
+typedef struct tb_vo_tracker {
+    int kind;                       /* TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE */
+    float bf_ratio, bf_min_th;      /* searchByBF ratio / minTh (:712: 10, 30) */
+    int min_level, max_level;       /* both descriptor trackers (:712, :713: 0, 5) */
+    float radius;                   /* searchByViolence search radius (:713: 50) */
+    int th_low; float nratio; int histo_len; int check_orientation;   /* the Matcher's fields at :713: 50, 6, 30, 1 */
+} tb_vo_tracker;
+/* tb_vo_create with a tracker; tracker NULL or kind TB_VO_OPFLOW = tb_vo_create. */
+int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* params, const tb_vo_tracker* tracker, int nseq, tb_vo** out);
+/* Device views of a descriptor tracker's state after the last step (valid until the next step; every output nullable; TB_ESTATE
+ * for an optical-flow loop):
+ *   orb [nseq][key_pitch] tb_keypoint, orb_desc [nseq][key_pitch][32], orb_counts [nseq]: the current frame's ORB keys (= its keys)
+ *   matches [nseq][key_pitch] (queryIdx = current key, trainIdx = keyframe key), match_counts [nseq] (0 at frame 0), flags [nseq]
+ *   the keyframe: kf_orb / kf_desc / kf_counts as above, kf_map_points [nseq][key_pitch][3], kf_mp_valid [nseq][key_pitch];
+ *   *kf_frame = the index of its frame (-1 before any) */
+int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** orb_desc, const int32_t** orb_counts,
+                            const tb_match** matches, const int32_t** match_counts, const int32_t** flags, const tb_keypoint** kf_orb,
+                            const uint8_t** kf_desc, const float** kf_map_points, const uint8_t** kf_mp_valid,
+                            const int32_t** kf_counts, int* kf_frame);
+
 /* ---- multi-GPU batch entry (SURVEY.md section 8(b) `tb_batch_run`, 8(e): frames are independent units through
  * extract -> left/right match, sharded as contiguous blocks of frames, one exchange step at the end).
  * The in-process counterpart of trackingbench_slam_amd/dist.py for a C++ host that holds one context per GPU:

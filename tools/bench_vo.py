@@ -8,7 +8,8 @@ repeated to fill the batch) and uploaded before anything is timed, so the steps 
     timed   reset + T steps, HIP events on the loop's stream around every step, one synchronisation at the end
     prof    the same steps with the library's per-kernel event timing on (tb_profile_*): the per-kernel split
 
-Prints one JSON line.
+--tracker picks the loop's tracking line (test_vo.cpp:712-716): opflow (default), bf or violence with the reference's arguments;
+the descriptor trackers also report their matches per tracking frame. Prints one JSON line.
 """
 import argparse
 import json
@@ -28,23 +29,25 @@ def centre(T):
     return -T[:3, :3].T @ T[:3, 3]
 
 
-def run_size(S, L, R, G, T, every, timed_only=False):
+def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow"):
     D = L.shape[1]
     rep = lambda a: a[:, np.arange(S) % D]   # noqa: E731
     dL = torch.from_numpy(np.ascontiguousarray(rep(L))).cuda()
     dR = torch.from_numpy(np.ascontiguousarray(rep(R))).cuda()
     Gs = rep(G)
-    vo = StereoVO(S, keyframe_every=every)
+    vo = StereoVO(S, keyframe_every=every, tracker=tracker)
     try:
         # stats (and the first step, which sizes every buffer)
         vo.reset(Gs[0])
-        obs, inl, drift = [], [], []
+        obs, inl, drift, mts = [], [], [], []
         for t in range(T):
             vo.step(dL[t], dR[t] if t % every == 0 else None)
             if timed_only:
                 continue
             if t % every:
                 obs.append(vo.obs()[1].cpu().numpy()); inl.append(vo.n_inliers().cpu().numpy())
+                if tracker != "opflow":
+                    mts.append(vo.matches()[1].cpu().numpy())
             Tcw = vo.Tcw().cpu().numpy()
             drift.append([float(np.linalg.norm(centre(Tcw[s]) - centre(Gs[t, s]))) for s in range(S)])
         obs, inl, drift = np.array(obs), np.array(inl), np.array(drift)
@@ -74,13 +77,17 @@ def run_size(S, L, R, G, T, every, timed_only=False):
     finally:
         vo.close()
     kern = {k: dict(calls=c, ms=round(m, 4)) for k, (c, m) in sorted(rep_.items(), key=lambda kv: -kv[1][1])}
+    extra = {}
+    if mts:
+        mts = np.array(mts)
+        extra["matches_per_frame"] = dict(mean=round(float(mts.mean()), 1), min=int(mts.min()))
     return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3),
                 ms_per_track_step=round(float(ms[~kf].mean()), 4), ms_per_keyframe_step=round(float(ms[kf].mean()), 4),
                 ms_first_keyframe_step=round(float(ms[0]), 4), kernels_ms_over_T_steps=kern,
                 obs_per_frame=dict(mean=round(float(obs.mean()), 1), min=int(obs.min())),
                 inliers_per_frame=dict(mean=round(float(inl.mean()), 1), min=int(inl.min())),
                 drift_m=dict(final_mean=round(float(drift[-1].mean()), 4), final_max=round(float(drift[-1].max()), 4),
-                             all_max=round(float(drift.max()), 4)))
+                             all_max=round(float(drift.max()), 4)), **extra)
 
 
 def main():
@@ -89,14 +96,15 @@ def main():
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--distinct", type=int, default=4, help="different synthetic sequences, repeated to fill a batch")
     ap.add_argument("--keyframe-every", type=int, default=10)
+    ap.add_argument("--tracker", choices=("opflow", "bf", "violence"), default="opflow")
     ap.add_argument("--timed-only", action="store_true", help="first pass without state reads, then the timed pass only "
                     "(for a trace of the steps: no host <-> device copy between them)")
     args = ap.parse_args()
     T = args.steps
     seqs = [synth_seq.sequence(s, T) for s in range(args.distinct)]
     L = np.stack([q[0] for q in seqs], 1); R = np.stack([q[1] for q in seqs], 1); G = np.stack([q[2] for q in seqs], 1)
-    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only) for S in args.sizes.split(",")]
-    print(json.dumps(dict(tool="bench_vo", device=torch.cuda.get_device_name(0), width=1241, height=376,
+    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker) for S in args.sizes.split(",")]
+    print(json.dumps(dict(tool="bench_vo", tracker=args.tracker, device=torch.cuda.get_device_name(0), width=1241, height=376,
                           keyframe_every=args.keyframe_every, distinct_sequences=args.distinct, results=res)))
 
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "tb_clahe", "tb_clahe_dev", "tb_optical_flow_pyr_lk", "tb_optical_flow_pyr_lk_dev", "tb_optical_flow_pyr_lk_batch_dev", "tb_search_by_opflow", "tb_search_by_opflow_batch_dev",
     "tb_find_fundamental_ransac", "tb_reject_with_f", "tb_reject_with_f_batch_dev", "tb_add_map_points_by_stereo", "tb_add_map_points_by_stereo_batch_dev",
     "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
+    "tb_vo_create_ex", "tb_vo_tracker_state_dev",
 ]
 
 
@@ -172,14 +173,29 @@ class VOParams(C.Structure):
                 ("init_th", C.c_float), ("min_th", C.c_float), ("K", C.c_double * 4), ("bf", C.c_float), ("keyframe_every", C.c_int)]
 
 
-class VO:
-    """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out."""
+TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE = 0, 1, 2
 
-    def __init__(self, ctx, params, nseq):
+
+class VOTracker(C.Structure):
+    """tb_vo_tracker of include/tb_capi.h"""
+    _fields_ = [("kind", C.c_int), ("bf_ratio", C.c_float), ("bf_min_th", C.c_float), ("min_level", C.c_int), ("max_level", C.c_int),
+                ("radius", C.c_float), ("th_low", C.c_int), ("nratio", C.c_float), ("histo_len", C.c_int),
+                ("check_orientation", C.c_int)]
+
+
+class VO:
+    """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
+    tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL)."""
+
+    def __init__(self, ctx, params, nseq, tracker=None, use_ex=False):
         self.ctx = ctx
         self.nseq = int(nseq)
         self._h = C.c_void_p()
-        ctx.check(lib().tb_vo_create(ctx._h, C.byref(params), self.nseq, C.byref(self._h)))
+        if tracker is None and not use_ex:
+            ctx.check(lib().tb_vo_create(ctx._h, C.byref(params), self.nseq, C.byref(self._h)))
+        else:
+            trp = C.byref(tracker) if tracker is not None else None
+            ctx.check(lib().tb_vo_create_ex(ctx._h, C.byref(params), trp, self.nseq, C.byref(self._h)))
 
     def close(self):
         # the loop owns an extractor plan of its context: destroy it while the context is alive
@@ -209,6 +225,18 @@ class VO:
         names = ("Tcw", "keys_xy", "map_points", "mp_valid", "key_counts", "obs", "obs_counts", "n_inliers", "outlier")
         out = {k: q.value for k, q in zip(names, ptrs)}
         out["key_pitch"], out["frame"] = pitch.value, frame.value
+        return out
+
+    def tracker_state_dev(self):
+        """dict of device pointers of a descriptor tracker (orb, orb_desc, orb_counts, matches, match_counts, flags, kf_orb, kf_desc,
+        kf_map_points, kf_mp_valid, kf_counts) + kf_frame."""
+        ptrs = [C.c_void_p() for _ in range(11)]
+        kf_frame = C.c_int(0)
+        self.ctx.check(lib().tb_vo_tracker_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(kf_frame)))
+        names = ("orb", "orb_desc", "orb_counts", "matches", "match_counts", "flags", "kf_orb", "kf_desc", "kf_map_points",
+                 "kf_mp_valid", "kf_counts")
+        out = {k: q.value for k, q in zip(names, ptrs)}
+        out["kf_frame"] = kf_frame.value
         return out
 
 

@@ -63,6 +63,79 @@ k_vo_track(const int32_t* __restrict__ prev_counts, const uint8_t* __restrict__ 
     if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
 }
 
+/* Descriptor trackers, frame t (test_vo.cpp:712-713 and test_vo_1 :193-227): the current frame's keys are its ORB records
+ * (all m of them) and the matcher has matched them (query) against the keyframe's (train):
+ *   - a fresh frame: no map point on any key, outlier flags false;
+ *   - for every match whose keyframe entry trainIdx has a map point, key queryIdx gets that point (Frame::AddMapPoint
+ *     overwrites, so a later match in list order wins -- win[] keeps the last such match per key; both matchers emit each
+ *     queryIdx at most once, so this only decides malformed lists);
+ *   - PoseOptimization's rows: one per key that has a map point, IN KEY ORDER (LocalBA.cpp:333-363 walks i = 0..N):
+ *     px = the key, Xw = the map point, invSigma2 = invLevelSigma2[octave] (LocalBA.cpp:349);
+ *   - keys_xy / key_counts = the records' (x, y) and m (what the stereo operator and tb_vo_state_dev read).
+ * win [nseq][pitch] is work memory: it is written and read with atomics only (L2), so the three phases need no other fence. */
+struct tb_vo_sigma {
+    float v[TB_MAX_LEVELS];
+    int n;
+};
+
+__global__ void __launch_bounds__(256)
+k_vo_match_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__ orb_counts, const tb_match* __restrict__ matches,
+                 const int32_t* __restrict__ match_counts, const float* __restrict__ kf_mp, const uint8_t* __restrict__ kf_valid,
+                 const int32_t* __restrict__ kf_counts, int pitch, tb_vo_sigma sig, int32_t* __restrict__ win, float* __restrict__ keys,
+                 int32_t* __restrict__ key_counts, float* __restrict__ mp, uint8_t* __restrict__ valid, tb_obs* __restrict__ obs,
+                 int32_t* __restrict__ obs_counts, uint8_t* __restrict__ outlier) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(orb_counts[s], 0), pitch);
+    const int nm = min(max(match_counts[s], 0), pitch);
+    const int nk = min(max(kf_counts[s], 0), pitch);
+    const size_t o = (size_t)s * pitch;
+    const tb_keypoint* K = orb + o;
+    const tb_match* M = matches + o;
+    int32_t* Wn = win + o;
+    for (int i = tid; i < n; i += 256) atomicExch(&Wn[i], -1);
+    __syncthreads();
+    for (int k = tid; k < nm; k += 256) {
+        const int q = M[k].queryIdx, tr = M[k].trainIdx;
+        if (q >= 0 && q < n && tr >= 0 && tr < nk && kf_valid[o + tr]) atomicMax(&Wn[q], k);
+    }
+    __syncthreads();
+    tb_obs* O = obs + o;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        bool ok = false;
+        tb_obs r = {0, 0, 0, 0, 0, 0};
+        if (i < n) {
+            const int k = atomicAdd(&Wn[i], 0);
+            ok = k >= 0;
+            float X = 0.f, Y = 0.f, Z = 0.f;
+            if (ok) {
+                const size_t j = o + M[k].trainIdx;
+                X = kf_mp[3 * j]; Y = kf_mp[3 * j + 1]; Z = kf_mp[3 * j + 2];
+            }
+            mp[3 * (o + i)] = X; mp[3 * (o + i) + 1] = Y; mp[3 * (o + i) + 2] = Z;
+            valid[o + i] = ok ? 1 : 0;
+            outlier[o + i] = 0;
+            const tb_keypoint kp = K[i];
+            keys[2 * (o + i)] = kp.x; keys[2 * (o + i) + 1] = kp.y;
+            r.u = kp.x; r.v = kp.y;
+            r.X = X; r.Y = Y; r.Z = Z;
+            r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];   /* the extractor's octaves are in [0, nlevels) */
+        }
+        const unsigned long long bm = __ballot(ok);
+        if (lane == 0) wsum[wave] = __popcll(bm);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        if (ok) O[at] = r; /* at < n <= pitch */
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
+}
+
 /* Keyframe, first half: SetKeys(orb_keys) (test_vo.cpp:785). The ORB records become (x, y) pairs (what the stereo op reads)
  * and the map-point list is resized to m: mvpMapPoints.resize(m, nullptr) (Frame.cpp:114) KEEPS entries [0, min(n, m)) --
  * the map points step 2 attached to the previous key list at those indices -- and entries [n, m) are null. n = the key
@@ -166,6 +239,23 @@ int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d
     tb_prof_begin(ctx, "k_vo_kf_spawn");
     hipLaunchKernelGGL(k_vo_kf_spawn, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_depth, d_Tcw, K[0], K[1], K[2], K[3],
                        pitch, d_mp, d_valid);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
+                       const int32_t* d_match_counts, const float* d_kf_mp, const uint8_t* d_kf_valid, const int32_t* d_kf_counts, int pitch,
+                       const float* inv_sigma2, int nlevels, int32_t* d_win, float* d_keys, int32_t* d_key_counts, float* d_mp,
+                       uint8_t* d_valid, tb_obs* d_obs, int32_t* d_obs_counts, uint8_t* d_outlier) {
+    if (nseq <= 0) return TB_OK;
+    if (nlevels < 1 || nlevels > TB_MAX_LEVELS) return TB_EINVAL;
+    tb_vo_sigma sig = {};
+    for (int l = 0; l < nlevels; l++) sig.v[l] = inv_sigma2[l];
+    sig.n = nlevels;
+    tb_prof_begin(ctx, "k_vo_match_carry");
+    hipLaunchKernelGGL(k_vo_match_carry, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts, d_kf_mp,
+                       d_kf_valid, d_kf_counts, pitch, sig, d_win, d_keys, d_key_counts, d_mp, d_valid, d_obs, d_obs_counts, d_outlier);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -1719,6 +1719,22 @@ struct tb_vo {
     float* st_pts = nullptr;                 /* [nseq][P][2] stereo tracks */
     uint8_t* st_status = nullptr;            /* [nseq][P] */
     float* depth = nullptr;                  /* [nseq][P] */
+    /* descriptor trackers (tr.kind != TB_VO_OPFLOW): the current frame's ORB results, the keyframe's snapshot */
+    tb_vo_tracker tr;
+    float inv_sigma2[TB_MAX_LEVELS];         /* Frame::GetInverseScaleSigmaSquares */
+    tb_keypoint* orb = nullptr;              /* [nseq][P] */
+    uint8_t* orb_desc = nullptr;             /* [nseq][P][32] */
+    int32_t* orb_cnt = nullptr;              /* [nseq] */
+    int32_t* mflags = nullptr;               /* [nseq] matcher flags */
+    int32_t* win = nullptr;                  /* [nseq][P] k_vo_match_carry work */
+    tb_keypoint* kf_orb = nullptr;           /* [nseq][P] */
+    uint8_t* kf_desc = nullptr;              /* [nseq][P][32] */
+    int32_t* kf_cnt = nullptr;               /* [nseq] */
+    float* kf_mp = nullptr;                  /* [nseq][P][3] */
+    uint8_t* kf_valid = nullptr;             /* [nseq][P] */
+    int32_t* kf_cell_start = nullptr;        /* [nseq][4321] violence: the keyframe's lookup grid */
+    int32_t* kf_cell_items = nullptr;        /* [nseq][P] */
+    int kf_frame = -1;
 };
 
 void tb_vo_destroy(tb_vo* vo) {
@@ -1731,11 +1747,13 @@ void tb_vo_destroy(tb_vo* vo) {
     }
     hipFree(vo->right); hipFree(vo->status); hipFree(vo->matches); hipFree(vo->mcounts); hipFree(vo->obs); hipFree(vo->obs_counts);
     hipFree(vo->outlier); hipFree(vo->n_inliers); hipFree(vo->st_pts); hipFree(vo->st_status); hipFree(vo->depth);
+    hipFree(vo->orb); hipFree(vo->orb_desc); hipFree(vo->orb_cnt); hipFree(vo->mflags); hipFree(vo->win); hipFree(vo->kf_orb);
+    hipFree(vo->kf_desc); hipFree(vo->kf_cnt); hipFree(vo->kf_mp); hipFree(vo->kf_valid); hipFree(vo->kf_cell_start);
+    hipFree(vo->kf_cell_items);
     delete vo;
 }
 
-int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
-    TB_ENTER(ctx);
+static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out) {
     if (!ctx || !p || !out) return TB_EINVAL;
     *out = nullptr;
     if (nseq < 1 || p->width < 1 || p->height < 1 || p->nlevels < 2 || p->nlevels > TB_MAX_LEVELS || !(p->scale > 0.f && p->scale < 1.f) ||
@@ -1750,6 +1768,8 @@ int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
     vo->ctx = ctx;
     vo->p = *p;
     vo->nseq = nseq;
+    memset(&vo->tr, 0, sizeof vo->tr);
+    if (tr) vo->tr = *tr;
     int rc = tb_extractor_create(ctx, p->width, p->height, p->nlevels, sf.data(), nullptr, nullptr, nseq, p->target, &vo->ex);
     if (rc) return rc;
     vo->P = vo->ex->g.selCap;
@@ -1790,8 +1810,60 @@ int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
         (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, S * sizeof(int32_t), &d)) ||
         (rc = tb_scratch(ctx, TB_SLOT_STEREO_MATCHES, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, TB_SLOT_STEREO_COUNTS, S * sizeof(int32_t), &d)))
         return rc;
+    if (vo->tr.kind != TB_VO_OPFLOW) {
+        tb_scale_factors(p->nlevels, p->scale, tmp.data(), nullptr, nullptr, vo->inv_sigma2);
+        TB_HIP(ctx, hipMalloc(&vo->orb, S * P * sizeof(tb_keypoint)));
+        TB_HIP(ctx, hipMalloc(&vo->orb_desc, S * P * 32));
+        TB_HIP(ctx, hipMalloc(&vo->orb_cnt, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->mflags, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->win, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->kf_orb, S * P * sizeof(tb_keypoint)));
+        TB_HIP(ctx, hipMalloc(&vo->kf_desc, S * P * 32));
+        TB_HIP(ctx, hipMalloc(&vo->kf_cnt, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->kf_mp, S * P * 3 * sizeof(float)));
+        TB_HIP(ctx, hipMalloc(&vo->kf_valid, S * P));
+        TB_HIP(ctx, hipMalloc(&vo->kf_cell_start, S * 4321 * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->kf_cell_items, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMemsetAsync(vo->orb_cnt, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, S * sizeof(int32_t), ctx->stream));
+        /* the matcher's slots: searchByBF's best rows per side (STAGE2 / STAGE3), searchByViolence's (WORK, shared with CLAHE) */
+        if (vo->tr.kind == TB_VO_BF) {
+            if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE3, S * P * 8, &d))) return rc;
+        } else if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * P * 16, &d))) {
+            return rc;
+        }
+    }
     *out = vu.release();
     return TB_OK;
+}
+
+int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
+    TB_ENTER(ctx);
+    return vo_create(ctx, p, nullptr, nseq, out);
+}
+
+int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out) {
+    TB_ENTER(ctx);
+    if (!ctx || !p || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (tr && tr->kind != TB_VO_OPFLOW) {
+        if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
+        if (tr->kind == TB_VO_BF) {
+            if (!std::isfinite(tr->bf_ratio) || !std::isfinite(tr->bf_min_th))
+                return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByBF ratio / minTh must be finite");
+            /* matcher.cpp:177: only MinLevel == 0 && MaxLevel == F1->GetMaxLevel() (= nLevels) takes the whole-set branch */
+            if (tr->min_level != 0 || tr->max_level != p->nlevels)
+                return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_ex: searchByBF levels (%d, %d): only the whole-set branch (0, %d) exists",
+                               tr->min_level, tr->max_level, p->nlevels);
+        } else if (tr->histo_len < 1 || tr->histo_len > 1024 || !(tr->radius > 0.f) || !std::isfinite(tr->radius) ||
+                   tr->min_level > tr->max_level || !std::isfinite(tr->nratio)) {
+            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByViolence arguments (levels %d..%d, radius %g, histo_len %d)",
+                           tr->min_level, tr->max_level, (double)tr->radius, tr->histo_len);
+        }
+    }
+    return vo_create(ctx, p, tr && tr->kind != TB_VO_OPFLOW ? tr : nullptr, nseq, out);
 }
 
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
@@ -1801,7 +1873,73 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     /* frame 0 reads the "last frame": no keys, pose Tcw0 */
     TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[vo->cur], Tcw0, (size_t)vo->nseq * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(vo->kcnt[vo->cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+    if (vo->tr.kind != TB_VO_OPFLOW) {   /* no keyframe yet */
+        TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+        vo->kf_frame = -1;
+    }
     vo->next = 0;
+    return TB_OK;
+}
+
+/* A descriptor tracker's frame t after the left images are in img[b] (see include/tb_capi.h, tb_vo_tracker). */
+static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, int stride, size_t pitch) {
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    const tb_vo_tracker& tr = vo->tr;
+    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
+    const size_t ip = (size_t)W * H, SP = (size_t)S * P;
+    const int a = vo->cur, b = a ^ 1;
+    int rc;
+    /* ORB operator() on every frame; the extractor's results do not outlive its next call, so they are copied out */
+    if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
+    if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
+    if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
+    if ((rc = tb_extractor_copy_results_dev(vo->ex, S, vo->orb, vo->orb_desc, vo->orb_cnt, P))) return rc;
+    if (t == 0) {
+        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+    } else if (tr.kind == TB_VO_BF) {
+        /* :712 searchByBF(cur, key_frame, 0, nLevels, ratio, minTh): the whole-set branch */
+        if ((rc = tb_search_by_bf_batch_dev(ctx, S, vo->orb_desc, vo->orb_cnt, vo->kf_desc, vo->kf_cnt, (size_t)P * 32, tr.bf_ratio,
+                                            tr.bf_min_th, vo->matches, P, vo->mcounts)))
+            return rc;
+    } else {
+        /* :713 searchByViolence(cur, key_frame, min_level, max_level, radius) over the keyframe's lookup grid */
+        if ((rc = tb_search_by_violence_batch_dev(ctx, S, vo->orb, vo->orb_desc, vo->orb_cnt, P, vo->kf_orb, vo->kf_desc, vo->kf_cnt, P,
+                                                  vo->kf_cell_start, vo->kf_cell_items, W, H, tr.min_level, tr.max_level, tr.radius,
+                                                  tr.th_low, tr.nratio, tr.histo_len, tr.check_orientation, vo->matches, P, vo->mcounts,
+                                                  vo->mflags)))
+            return rc;
+    }
+    /* the keys, the map points the matches carry over and the pose rows (match count 0 at frame 0: a fresh frame) */
+    if ((rc = tbk_vo_match_carry(ctx, S, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->kf_mp, vo->kf_valid, vo->kf_cnt, P,
+                                 vo->inv_sigma2, p.nlevels, vo->win, vo->keys[b], vo->kcnt[b], vo->mp[b], vo->valid[b], vo->obs,
+                                 vo->obs_counts, vo->outlier)))
+        return rc;
+    if (t > 0 &&
+        (rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
+        return rc;
+    if (keyframe) {
+        /* :774-785 extracts again on the same pyramid: the same keys, so SetKeys resizes m to m and keeps every carried map
+         * point -- nothing to do. Then :800 AddMapPointsByStereo and the new map points (:802-832), as the optical-flow loop. */
+        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
+        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
+                                                        vo->st_pts, vo->st_status, vo->depth)))
+            return rc;
+        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
+        /* key_frame = cur_frame_ptr (:836): a snapshot of fixed-size slabs; violence's lookup grid once per keyframe */
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_orb, vo->orb, SP * sizeof(tb_keypoint), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_desc, vo->orb_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_cnt, vo->orb_cnt, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp, vo->mp[b], SP * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_valid, vo->valid[b], SP, hipMemcpyDeviceToDevice, ctx->stream));
+        if (tr.kind == TB_VO_VIOLENCE &&
+            (rc = tb_frame_grid_batch_dev(ctx, S, vo->kf_orb, vo->kf_cnt, P, W, H, vo->kf_cell_start, vo->kf_cell_items)))
+            return rc;
+        vo->kf_frame = t;
+    }
     return TB_OK;
 }
 
@@ -1820,7 +1958,9 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
     const int a = vo->cur, b = a ^ 1;   /* a: last frame, b: this frame */
     int rc;
     if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
-    if (t == 0) {
+    if (vo->tr.kind != TB_VO_OPFLOW) {
+        if ((rc = vo_step_desc(vo, t, keyframe, right, stride, pitch))) return rc;
+    } else if (t == 0) {
         TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->kcnt[b], 0, (size_t)S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
@@ -1837,7 +1977,7 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
         if ((rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
             return rc;
     }
-    if (keyframe) {
+    if (keyframe && vo->tr.kind == TB_VO_OPFLOW) {
         /* :774-785 ORB operator()(pyramid, sf, target, init_th, min_th) + SetKeys */
         if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
         if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
@@ -1874,6 +2014,28 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
     if (outlier) *outlier = vo->outlier;
     if (key_pitch) *key_pitch = vo->P;
     if (frame) *frame = vo->next - 1 < -1 ? -1 : vo->next - 1;
+    return TB_OK;
+}
+
+int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** orb_desc, const int32_t** orb_counts,
+                            const tb_match** matches, const int32_t** match_counts, const int32_t** flags, const tb_keypoint** kf_orb,
+                            const uint8_t** kf_desc, const float** kf_map_points, const uint8_t** kf_mp_valid,
+                            const int32_t** kf_counts, int* kf_frame) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (vo->tr.kind == TB_VO_OPFLOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_tracker_state_dev: the loop tracks by optical flow");
+    if (orb) *orb = vo->orb;
+    if (orb_desc) *orb_desc = vo->orb_desc;
+    if (orb_counts) *orb_counts = vo->orb_cnt;
+    if (matches) *matches = vo->matches;
+    if (match_counts) *match_counts = vo->mcounts;
+    if (flags) *flags = vo->mflags;
+    if (kf_orb) *kf_orb = vo->kf_orb;
+    if (kf_desc) *kf_desc = vo->kf_desc;
+    if (kf_map_points) *kf_map_points = vo->kf_mp;
+    if (kf_mp_valid) *kf_mp_valid = vo->kf_valid;
+    if (kf_counts) *kf_counts = vo->kf_cnt;
+    if (kf_frame) *kf_frame = vo->kf_frame;
     return TB_OK;
 }
 

@@ -244,6 +244,10 @@ int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h,
 int tbk_vo_track(tb_ctx* ctx, int nseq, const int32_t* d_prev_counts, const uint8_t* d_status, const float* d_keys, const float* d_prev_mp,
                  const uint8_t* d_prev_valid, int pitch, int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, tb_obs* d_obs,
                  int32_t* d_obs_counts, uint8_t* d_outlier);
+int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
+                       const int32_t* d_match_counts, const float* d_kf_mp, const uint8_t* d_kf_valid, const int32_t* d_kf_counts, int pitch,
+                       const float* inv_sigma2, int nlevels, int32_t* d_win, float* d_keys, int32_t* d_key_counts, float* d_mp,
+                       uint8_t* d_valid, tb_obs* d_obs, int32_t* d_obs_counts, uint8_t* d_outlier);
 int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, float* d_keys,
                    int32_t* d_key_counts, uint8_t* d_valid);
 int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
