@@ -126,7 +126,9 @@ int tb_fastgrid_extract(tb_ctx* ctx, const uint8_t* const* levels, const int* wi
                         const uint8_t* occupancy, int n_occupancy, tb_keypoint* kps, int cap, int* count);
 
 /* ---------------------------------------------------------------- matchers
- * Matcher::DescriptorDistance / ComputeThreeMaxima (matcher.cpp:793-851): host helpers. */
+ * Matcher::DescriptorDistance / ComputeThreeMaxima (matcher.cpp:793-851): host helpers.
+ * The matcher host forms (out, cap, *count) list at most cap matches: more is TB_ECAPACITY with the full count in *count
+ * and out not written. */
 int tb_descriptor_distance(const uint8_t* a, const uint8_t* b);
 void tb_three_maxima(const int* bin_sizes, int nbins, int* ind1, int* ind2, int* ind3);
 /* cv::BFMatcher(NORM_HAMMING, crossCheck).match (the call inside searchByBF, matcher.cpp:207) */
@@ -295,9 +297,11 @@ int tb_pose_opt_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const f
  * tb_search_by_opflow replaces Matcher::searchByOPFlow(F1, F2, cur_points, equalized, reject), matcher.cpp:724-768:
  * tracks F2's keys (keys2_xy) from img2 into img1, clears the points that leave F1's frame (cam1->width / height,
  * CameraModel.h:33-39) and returns DMatch(i, i) records (distance FLT_MAX, imgIdx -1, as a default-constructed
- * cv::DMatch). equalized != 0: img1 goes through tb_clahe(3.0, 8 x 8) first (F1->Equalize(), matcher.cpp:736-739).
+ * cv::DMatch). equalized != 0: img1 is equalised first, as tb_clahe(3.0, 8 x 8) does (F1->Equalize(), matcher.cpp:736-739).
  * reject != 0: Matcher::rejectWithF (matcher.cpp:853-881) = cv::findFundamentalMat(FM_RANSAC, 1.0, 0.99) clears the
- * flags of the epipolar outliers before the matches are listed (tb_reject_with_f below). cur_points: n (x, y) pairs out. */
+ * flags of the epipolar outliers before the matches are listed (as tb_reject_with_f below). cur_points: n (x, y) pairs out.
+ * Runs tb_search_by_opflow_batch_dev on one pair, so TB_ECAPACITY reports the full match count in *count, as the other
+ * matcher host forms do. */
 /* Frame::Equalize, Frame.cpp:453-458: cv::createCLAHE(clip_limit = 3.0, Size(tiles_x, tiles_y) = 8 x 8)->apply(src, dst)
  * (OpenCV 3.3 routine restated, parity unpinned). Host pointers; dst has the size of src. tb_clahe_dev: device pointers,
  * asynchronous on the context's stream. */
@@ -355,7 +359,7 @@ int tb_reject_with_f_batch_dev(tb_ctx* ctx, int npairs, const float* cur_pts, co
  * pts, equalized = true, reject = true), then depth[i] = bf / fabsf(pts[i].x - key[i].x) for the surviving keys i of the
  * current frame and -1 for the others (fx is unused by the reference; its drawing and imshow are dropped). img_stereo /
  * img_current: level-0 images; cam_stereo: the stereo frame's camera (width / height for IsInFrame); keys_xy: the current
- * frame's keys. *n_depth = number of depths set. Host pointers. */
+ * frame's keys. *n_depth = number of depths set. Host pointers; runs tb_add_map_points_by_stereo_batch_dev on one pair. */
 int tb_add_map_points_by_stereo(tb_ctx* ctx, const uint8_t* img_stereo, const uint8_t* img_current, int width, int height, int stride,
                                 const tb_camera* cam_stereo, const float* keys_xy, int n, float bf, float* depth, int* n_depth);
 /* Batched device form: pair p's images at + p * image_pitch, its keys / tracked points / status / depths at slot

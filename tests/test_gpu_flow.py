@@ -1,6 +1,8 @@
 """GPU parity tests (pytest -m gpu): the optical-flow matcher (first part) against the CPU oracle,
 bit for bit -- both sides use exact integer window sums and the same float operation sequence. The oracle itself is a
 restatement of cv::calcOpticalFlowPyrLK (OpenCV 3.3 is not in the reference tree): parity with OpenCV UNPINNED."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -70,6 +72,37 @@ def test_search_by_opflow(ctx):
     ocur, oidx = oracle.search_by_opflow(R, L, cam, pts, reject=True)
     assert np.array_equal(cur.view(np.uint32), ocur.view(np.uint32)) and np.array_equal(m["queryIdx"], oidx)
     assert len(ctx.search_by_opflow(R, L, cam, np.zeros((0, 2), np.float32))[1]) == 0
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _raw_opflow(ctx, img1, img2, cam, keys, cap):
+    """tb_search_by_opflow (equalized, reject) through the raw C ABI: (return code, *count, out[:cap])."""
+    img1, img2 = np.ascontiguousarray(img1, np.uint8), np.ascontiguousarray(img2, np.uint8)
+    h, w = img1.shape
+    cam, keys = np.ascontiguousarray(cam, capi.CAMERA), np.ascontiguousarray(keys, np.float32)
+    cur = np.zeros((len(keys), 2), np.float32)
+    out = np.zeros(max(cap, 1), capi.MATCH); n = C.c_int(-7)
+    rc = capi.lib().tb_search_by_opflow(ctx._h, _ptr(img1), _ptr(img2), w, h, w, _ptr(cam), _ptr(keys), len(keys), 1, 1, _ptr(cur),
+                                        _ptr(out), cap, C.byref(n))
+    return rc, n.value, out[:cap]
+
+
+def test_search_by_opflow_capacity(ctx):
+    """The capacity contract of the matcher host forms: cap = count - 1 -> TB_ECAPACITY with the full count, cap = count ->
+    the oracle's list."""
+    L, R = synth.frame(4, 640, 480, stereo=True)
+    pts = _keys(L, 800)
+    cam = oracle.camera(500, 500, 320, 240, 640, 480)
+    _, exp = oracle.search_by_opflow(R, L, cam, pts, equalized=True, reject=True)
+    assert len(exp) > 1
+    rc, n, _ = _raw_opflow(ctx, R, L, cam, pts, len(exp) - 1)
+    assert rc == capi.TB_ECAPACITY and n == len(exp)
+    rc, n, out = _raw_opflow(ctx, R, L, cam, pts, len(exp))
+    assert rc == capi.TB_OK and n == len(exp)
+    assert np.array_equal(out["queryIdx"], exp) and np.array_equal(out["trainIdx"], exp) and (out["imgIdx"] == -1).all()
 
 
 def test_lk_batch_device_resident(ctx):

@@ -720,7 +720,21 @@ int tb_extractor_candidates_host(tb_extractor* ex, int index, int level, tb_corn
     return TB_OK;
 }
 
-/* ------------------------------------------------------------------ single-frame operator forms */
+/* ------------------------------------------------------------------ single-frame operator forms
+ * A host form stages its inputs and outputs in TB_SLOT_HOST, runs the batched form (or its launcher) on one frame or pair,
+ * and copies the results back behind one synchronisation. */
+/* the next 16-byte aligned piece of a staging slot: returns its offset and moves `end` past it */
+static size_t stage_piece(size_t& end, size_t bytes) {
+    const size_t o = end;
+    end += (bytes + 15) & ~(size_t)15;
+    return o;
+}
+
+#define TB_UPLOAD(ctx, dst, src, bytes) \
+    do { if (bytes) TB_HIP(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, (ctx)->stream)); } while (0)
+#define TB_DOWNLOAD(ctx, dst, src, bytes) \
+    do { if (bytes) TB_HIP(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, (ctx)->stream)); } while (0)
+
 static int get_plan(tb_ctx* ctx, const char* tag, int nlevels, const float* sf, const int* ws, const int* hs, int max_target,
                     tb_extractor** out) {
     std::string key = tag;
@@ -768,23 +782,24 @@ int tb_fast_detect(tb_ctx* ctx, const uint8_t* image, int width, int height, int
     *count = 0;
     if (width < 7 || height < 7) return TB_OK;
     threshold = std::min(std::max(threshold, 0), 255);
-    void *d_img, *d_out, *d_cnt;
     const int rcap = (nms ? ((width + 1) / 2) * ((height + 1) / 2) : width * height) + 64;
+    size_t end = 0;
+    const size_t oImg = stage_piece(end, (size_t)width * height), oOut = stage_piece(end, (size_t)rcap * 4), oCnt = stage_piece(end, 4);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)width * height, &d_img))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)rcap * 4, &d_out))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, 256, &d_cnt))) return rc;
-    TB_HIP(ctx, hipMemcpy2DAsync(d_img, width, image, stride, width, height, hipMemcpyHostToDevice, ctx->stream));
-    rc = tbk_fast_image(ctx, (const uint8_t*)d_img, width, height, width, threshold, nms, 9, (uint32_t*)d_out, rcap, (int32_t*)d_cnt);
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_HIP(ctx, hipMemcpy2DAsync(b + oImg, width, image, stride, width, height, hipMemcpyHostToDevice, ctx->stream));
+    rc = tbk_fast_image(ctx, (const uint8_t*)(b + oImg), width, height, width, threshold, nms, 9, (uint32_t*)(b + oOut), rcap,
+                        (int32_t*)(b + oCnt));
     if (rc) return rc;
     int32_t c = 0;
-    TB_HIP(ctx, hipMemcpyAsync(&c, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    TB_DOWNLOAD(ctx, &c, b + oCnt, 4);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *count = c;
     if (c > cap || c > rcap) return tb_fail(ctx, TB_ECAPACITY, "fast_detect: %d corners, capacity %d", c, cap);
     std::vector<uint32_t> rec((size_t)c);
     if (c > 0) {
-        TB_HIP(ctx, hipMemcpy(rec.data(), d_out, (size_t)c * 4, hipMemcpyDeviceToHost));
+        TB_HIP(ctx, hipMemcpy(rec.data(), b + oOut, (size_t)c * 4, hipMemcpyDeviceToHost));
         /* raster order of cv::FAST: sort by (y, x) */
         std::sort(rec.begin(), rec.end(), [](uint32_t a, uint32_t b) { return (a & 0xffffff) < (b & 0xffffff); });
     }
@@ -870,14 +885,6 @@ void tb_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3) {
     else if ((float)max3 < 0.1f * (float)max1) { *ind3 = -1; }
 }
 
-/* ---- the single-frame matchers: host staging around the batched forms, one pair, and one tail */
-/* the next 16-byte aligned piece of a staging slot: returns its offset and moves `end` past it */
-static size_t stage_piece(size_t& end, size_t bytes) {
-    const size_t o = end;
-    end += (bytes + 15) & ~(size_t)15;
-    return o;
-}
-
 /* the end of every single-frame matcher: one synchronisation for the device list's count and flag (cf = count, flag), the
  * flag reported as the error the host form returns, then *count, the capacity check and the copy-out */
 static int match_tail(tb_ctx* ctx, const tb_match* dout, const int32_t* dcf, int cap, tb_match* out, int* count) {
@@ -892,9 +899,7 @@ static int match_tail(tb_ctx* ctx, const tb_match* dout, const int32_t* dcf, int
     return TB_OK;
 }
 
-#define TB_UPLOAD(ctx, dst, src, bytes) \
-    do { if (bytes) TB_HIP(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, (ctx)->stream)); } while (0)
-
+/* the launcher, best rows staged too: tb_search_by_bf_batch_dev fixes crosscheck and filter to searchByBF's */
 static int bf_host(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int crosscheck, int filter, float ratio,
                    float min_th, tb_match* out, int cap, int* count) {
     if (!ctx || !count || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2)) return TB_EINVAL;
@@ -902,24 +907,21 @@ static int bf_host(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, in
     if (n1 == 0 || n2 == 0) return TB_OK;
     const int max_n = std::max(n1, n2);
     const size_t pitch = (size_t)max_n * 32;
-    void *dd1, *dd2, *tb, *qb, *dout, *dcnt;
+    size_t end = 0;
+    const size_t oD1 = stage_piece(end, pitch), oD2 = stage_piece(end, pitch), oTb = stage_piece(end, (size_t)max_n * 8),
+                 oQb = stage_piece(end, (size_t)max_n * 8), oOut = stage_piece(end, (size_t)n1 * sizeof(tb_match)), oCnt = stage_piece(end, 16);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, pitch, &dd1))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, pitch, &dd2))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)max_n * 8, &tb))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)max_n * 8, &qb))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)n1 * sizeof(tb_match), &dout))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, 256, &dcnt))) return rc;
-    int32_t cnts[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and a flag that stays 0 */
-    TB_HIP(ctx, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dcnt, cnts, sizeof cnts, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = tbk_bf_batch(ctx, 1, (const uint8_t*)dd1, (const int32_t*)dcnt, (const uint8_t*)dd2, (const int32_t*)dcnt + 1, pitch,
-                      max_n, crosscheck, filter, ratio, min_th, (tb_match*)dout, n1, (int32_t*)dcnt + 2,
-                      (unsigned long long*)tb, (unsigned long long*)qb);
-    if (rc) return rc;
-    return match_tail(ctx, (const tb_match*)dout, (const int32_t*)dcnt + 2, cap, out, count);
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and a flag that stays 0 */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oD1, d1, (size_t)n1 * 32);
+    TB_UPLOAD(ctx, b + oD2, d2, (size_t)n2 * 32);
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    if ((rc = tbk_bf_batch(ctx, 1, (const uint8_t*)(b + oD1), dcnt, (const uint8_t*)(b + oD2), dcnt + 1, pitch, max_n, crosscheck, filter,
+                           ratio, min_th, (tb_match*)(b + oOut), n1, dcnt + 2, (unsigned long long*)(b + oTb), (unsigned long long*)(b + oQb))))
+        return rc;
+    return match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 2, cap, out, count);
 }
 
 int tb_match_bf(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int crosscheck, tb_match* out, int cap,
@@ -944,8 +946,8 @@ int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, con
     const int max_n = (int)(set_pitch / 32);
     void *tb, *qb;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)npairs * max_n * 8, &tb))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)npairs * max_n * 8, &qb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, (size_t)npairs * max_n * 8, &tb))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, (size_t)npairs * max_n * 8, &qb))) return rc;
     return tbk_bf_batch(ctx, npairs, desc1, counts1, desc2, counts2, set_pitch, max_n, 1, 1, ratio, min_th, out, cap, out_counts,
                         (unsigned long long*)tb, (unsigned long long*)qb);
 }
@@ -1006,8 +1008,8 @@ int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, co
     if (!desc || (fv_keys && (!fv_counts || desc_pitch > 8192))) return TB_EINVAL;
     void *dn = node_ids, *dwt = weights;
     int rc;
-    if (fv_keys && !node_ids && (rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)nframes * desc_pitch * 4, &dn))) return rc;
-    if (fv_keys && !weights && (rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)nframes * desc_pitch * 8, &dwt))) return rc;
+    if (fv_keys && !node_ids && (rc = tb_scratch(ctx, TB_SLOT_BOW_NODES, (size_t)nframes * desc_pitch * 4, &dn))) return rc;
+    if (fv_keys && !weights && (rc = tb_scratch(ctx, TB_SLOT_BOW_WEIGHTS, (size_t)nframes * desc_pitch * 8, &dwt))) return rc;
     return tbk_bow_transform(ctx, voc->nnodes, voc->L, voc->d_child_start, voc->d_child_items, voc->d_desc, voc->d_word_id, voc->d_weight,
                              nframes, desc, counts, desc_pitch, levelsup, word_ids, (int32_t*)dn, (double*)dwt,
                              (unsigned long long*)fv_keys, fv_counts);
@@ -1018,20 +1020,20 @@ int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int 
     TB_ENTER(ctx);
     if (!ctx || !voc || voc->ctx != ctx || n < 0 || levelsup < 0 || (n && (!desc || !word_ids || !weights || !node_ids))) return TB_EINVAL;
     if (n == 0) return TB_OK;
-    void *dd, *dw, *dn, *dwt;
+    size_t end = 0;
+    const size_t oD = stage_piece(end, (size_t)n * 32), oW = stage_piece(end, (size_t)n * 4), oN = stage_piece(end, (size_t)n * 4),
+                 oWt = stage_piece(end, (size_t)n * 8);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)n * 32, &dd)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)n * 4, &dw)) ||
-        (rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)n * 4, &dn)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE3, (size_t)n * 8, &dwt)))
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_UPLOAD(ctx, b + oD, desc, (size_t)n * 32);
+    if ((rc = tb_bow_transform_batch_dev(ctx, voc, 1, (const uint8_t*)(b + oD), nullptr, n, levelsup, (int32_t*)(b + oW), (int32_t*)(b + oN),
+                                         (double*)(b + oWt), nullptr, nullptr)))
         return rc;
-    hipStream_t s = ctx->stream;
-    TB_HIP(ctx, hipMemcpyAsync(dd, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
-    if ((rc = tbk_bow_transform(ctx, voc->nnodes, voc->L, voc->d_child_start, voc->d_child_items, voc->d_desc, voc->d_word_id, voc->d_weight,
-                                1, (const uint8_t*)dd, nullptr, n, levelsup, (int32_t*)dw, (int32_t*)dn, (double*)dwt, nullptr, nullptr)))
-        return rc;
-    TB_HIP(ctx, hipMemcpyAsync(word_ids, dw, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipMemcpyAsync(node_ids, dn, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipMemcpyAsync(weights, dwt, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipStreamSynchronize(s));
+    TB_DOWNLOAD(ctx, word_ids, b + oW, (size_t)n * 4);
+    TB_DOWNLOAD(ctx, node_ids, b + oN, (size_t)n * 4);
+    TB_DOWNLOAD(ctx, weights, b + oWt, (size_t)n * 8);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TB_OK;
 }
 
@@ -1062,7 +1064,7 @@ int tb_stereo_tracks_to_obs_batch_dev(tb_ctx* ctx, int nframes, const tb_keypoin
     if (!keys_left || !keys_right || !matches || !match_counts || !obs || !obs_counts) return TB_EINVAL;
     void* dsig;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, TB_MAX_LEVELS * sizeof(float), &dsig))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_STEREO_SIGMA, TB_MAX_LEVELS * sizeof(float), &dsig))) return rc;
     /* the table is a few floats of host memory: staged through a pinned-free async copy (the stream orders it before the kernel) */
     TB_HIP(ctx, hipMemcpyAsync(dsig, inv_sigma2, (size_t)nlevels * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return tbk_stereo_obs(ctx, nframes, keys_left, keys_right, key_pitch, matches, match_counts, match_pitch, K, bf, (const float*)dsig, nlevels,
@@ -1085,7 +1087,7 @@ int tb_search_by_violence(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1,
                  oOut = stage_piece(end, (size_t)n1 * sizeof(tb_match)), oCnt = stage_piece(end, 16);
     char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
     const int32_t cnt[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and flag */
     int32_t* dcnt = (int32_t*)(b + oCnt);
     TB_UPLOAD(ctx, b + oK1, k1, n1 * kb);
@@ -1142,7 +1144,7 @@ int tb_search_by_bow(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int 
                  oK2 = stage_piece(end, p2 * kb), oD2 = stage_piece(end, p2 * 32), oF2 = stage_piece(end, p2 * 8),
                  oMp = stage_piece(end, p2), oOut = stage_piece(end, (size_t)nq * sizeof(tb_match)), oCnt = stage_piece(end, 16);
     char* b;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
     const int32_t cnt[4] = {nq, nf2, 0, 0}; /* list lengths, then the match count and flag */
     int32_t* dcnt = (int32_t*)(b + oCnt);
     TB_UPLOAD(ctx, b + oK1, k1, n1 * kb);
@@ -1175,7 +1177,7 @@ static int projection_host(tb_ctx* ctx, int map_mode, const float Tcw1[16], cons
                  oOut = stage_piece(end, (size_t)nq * sizeof(tb_match)), oCnt = stage_piece(end, 16);
     char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, end, (void**)&b))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
     const int32_t cnt[4] = {n1, nq, 0, 0}; /* n1, map points, then the match count and flag */
     int32_t* dcnt = (int32_t*)(b + oCnt);
     TB_UPLOAD(ctx, b + oT, Tcw1, 64);
@@ -1333,32 +1335,25 @@ int tb_pose_opt(tb_ctx* ctx, const double K[4], const float Tcw_in[16], const tb
     TB_ENTER(ctx);
     if (!ctx || !K || !Tcw_in || !Tcw_out || !n_inliers || n < 0 || (n && (!obs || !outlier))) return TB_EINVAL;
     const int pitch = std::max(n, 1);
-    void *dobs, *dmisc, *dout;
+    size_t end = 0;
+    const size_t oObs = stage_piece(end, (size_t)pitch * sizeof(tb_obs)), oOut = stage_piece(end, (size_t)pitch), oTin = stage_piece(end, 64),
+                 oTout = stage_piece(end, 64), oStats = stage_piece(end, 64), oCnt = stage_piece(end, 8);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)pitch * sizeof(tb_obs), &dobs))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)pitch, &dout))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, 512, &dmisc))) return rc;
-    /* dmisc: Tin[16] f32 | Tout[16] f32 | count i32 | ninl i32 | stats[8] f64 (at byte 192) */
-    float* dTin = (float*)dmisc;
-    float* dTout = dTin + 16;
-    int32_t* dcnt = (int32_t*)(dTout + 16);
-    int32_t* dninl = dcnt + 1;
-    double* dstats = (double*)((char*)dmisc + 192);
-    int32_t cnt = n;
-    if (n > 0) {
-        TB_HIP(ctx, hipMemcpyAsync(dobs, obs, (size_t)n * sizeof(tb_obs), hipMemcpyHostToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(dout, outlier, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    TB_HIP(ctx, hipMemcpyAsync(dTin, Tcw_in, 64, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dcnt, &cnt, 4, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = tb_pose_opt_batch_dev(ctx, 1, K, dTin, (const tb_obs*)dobs, dcnt, pitch, (uint8_t*)dout, dTout, dninl, dstats);
-    if (rc) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    int32_t* dcnt = (int32_t*)(b + oCnt); /* the row count, then the inliers */
+    TB_UPLOAD(ctx, b + oObs, obs, (size_t)n * sizeof(tb_obs));
+    TB_UPLOAD(ctx, b + oOut, outlier, (size_t)n);
+    TB_UPLOAD(ctx, b + oTin, Tcw_in, 64);
+    TB_UPLOAD(ctx, dcnt, &n, 4);
+    if ((rc = tb_pose_opt_batch_dev(ctx, 1, K, (const float*)(b + oTin), (const tb_obs*)(b + oObs), dcnt, pitch, (uint8_t*)(b + oOut),
+                                    (float*)(b + oTout), dcnt + 1, (double*)(b + oStats))))
+        return rc;
     int32_t ninl = 0;
-    TB_HIP(ctx, hipMemcpyAsync(Tcw_out, dTout, 64, hipMemcpyDeviceToHost, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(&ninl, dninl, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0) TB_HIP(ctx, hipMemcpyAsync(outlier, dout, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (stats) TB_HIP(ctx, hipMemcpyAsync(stats, dstats, 64, hipMemcpyDeviceToHost, ctx->stream));
+    TB_DOWNLOAD(ctx, Tcw_out, b + oTout, 64);
+    TB_DOWNLOAD(ctx, &ninl, dcnt + 1, 4);
+    TB_DOWNLOAD(ctx, outlier, b + oOut, (size_t)n);
+    if (stats) TB_DOWNLOAD(ctx, stats, b + oStats, 64);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_inliers = ninl;
     return TB_OK;
@@ -1389,26 +1384,24 @@ int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* pose
     /* the kernels want observations grouped by point: stable sort keeps each point's edges in caller order */
     std::vector<tb_ba_obs> sorted(obs, obs + nobs);
     std::stable_sort(sorted.begin(), sorted.end(), [](const tb_ba_obs& a, const tb_ba_obs& b) { return a.pt < b.pt; });
-    void *dposes, *dpts, *dobs, *dmisc;
+    size_t end = 0;
+    const size_t oPoses = stage_piece(end, (size_t)nkf * 64), oPts = stage_piece(end, (size_t)npt * 12),
+                 oObs = stage_piece(end, (size_t)nobs * sizeof(tb_ba_obs)), oStats = stage_piece(end, 64), oCnt = stage_piece(end, 4);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)nkf * 64, &dposes))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)npt * 12, &dpts))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)nobs * sizeof(tb_ba_obs), &dobs))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, 256, &dmisc))) return rc;
-    double* dstats = (double*)dmisc;
-    int32_t* dcnt = (int32_t*)((char*)dmisc + 64);
-    int32_t cnt = nobs;
-    TB_HIP(ctx, hipMemcpyAsync(dposes, poses, (size_t)nkf * 64, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dpts, pts, (size_t)npt * 12, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dobs, sorted.data(), (size_t)nobs * sizeof(tb_ba_obs), hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dcnt, &cnt, 4, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = tb_local_ba_batch_dev(ctx, 1, K, nkf, nfixed, (float*)dposes, npt, (float*)dpts, (const tb_ba_obs*)dobs, dcnt, nobs, iters, dstats);
-    if (rc) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    float *dposes = (float*)(b + oPoses), *dpts = (float*)(b + oPts);
+    TB_UPLOAD(ctx, dposes, poses, (size_t)nkf * 64);
+    TB_UPLOAD(ctx, dpts, pts, (size_t)npt * 12);
+    TB_UPLOAD(ctx, b + oObs, sorted.data(), (size_t)nobs * sizeof(tb_ba_obs));
+    TB_UPLOAD(ctx, b + oCnt, &nobs, 4);
+    if ((rc = tb_local_ba_batch_dev(ctx, 1, K, nkf, nfixed, dposes, npt, dpts, (const tb_ba_obs*)(b + oObs), (const int32_t*)(b + oCnt), nobs,
+                                    iters, (double*)(b + oStats))))
+        return rc;
     double st[8];
-    TB_HIP(ctx, hipMemcpyAsync(poses, dposes, (size_t)nkf * 64, hipMemcpyDeviceToHost, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(pts, dpts, (size_t)npt * 12, hipMemcpyDeviceToHost, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(st, dstats, 64, hipMemcpyDeviceToHost, ctx->stream));
+    TB_DOWNLOAD(ctx, poses, dposes, (size_t)nkf * 64);
+    TB_DOWNLOAD(ctx, pts, dpts, (size_t)npt * 12);
+    TB_DOWNLOAD(ctx, st, b + oStats, 64);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) memcpy(stats, st, 64);
     if (st[7] < 0) return tb_fail(ctx, TB_EINVAL, "local_ba: observations rejected by the device-side check");
@@ -1429,13 +1422,15 @@ int tb_clahe(tb_ctx* ctx, const uint8_t* src, int width, int height, int stride,
              uint8_t* dst, int dst_stride) {
     TB_ENTER(ctx);
     if (!ctx || !src || !dst || width < 1 || height < 1 || stride < width || dst_stride < width || tiles_x < 1 || tiles_y < 1) return TB_EINVAL;
-    void *ds, *dd;
+    size_t end = 0;
+    const size_t oSrc = stage_piece(end, (size_t)stride * height), oDst = stage_piece(end, (size_t)dst_stride * height);
+    char* b;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, (size_t)stride * height, &ds))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, (size_t)dst_stride * height, &dd))) return rc;
-    TB_HIP(ctx, hipMemcpyAsync(ds, src, (size_t)stride * height, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = tb_clahe_dev(ctx, (const uint8_t*)ds, width, height, stride, clip_limit, tiles_x, tiles_y, (uint8_t*)dd, dst_stride))) return rc;
-    TB_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, dd, dst_stride, width, height, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_UPLOAD(ctx, b + oSrc, src, (size_t)stride * height);
+    if ((rc = tb_clahe_dev(ctx, (const uint8_t*)(b + oSrc), width, height, stride, clip_limit, tiles_x, tiles_y, (uint8_t*)(b + oDst), dst_stride)))
+        return rc;
+    TB_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, b + oDst, dst_stride, width, height, hipMemcpyDeviceToHost, ctx->stream));
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TB_OK;
 }
@@ -1475,28 +1470,25 @@ int tb_optical_flow_pyr_lk(tb_ctx* ctx, const uint8_t* prev, const uint8_t* next
     if (!ctx || !prev || !next || n < 0 || width < 1 || height < 1 || stride < width) return TB_EINVAL;
     if (n && (!prev_pts || !next_pts || !status)) return TB_EINVAL;
     if (max_level < 0 || max_level > 5) return tb_fail(ctx, TB_EUNSUPPORTED, "optical flow: max_level %d (0..5)", max_level);
-    const size_t img = (size_t)stride * height, np2 = (size_t)std::max(n, 1) * 2 * sizeof(float);
-    void *dp, *dn, *dpts, *dout, *dst, *derr, *work;
+    const size_t img = (size_t)stride * height, np2 = (size_t)n * 2 * sizeof(float);
+    size_t end = 0;
+    const size_t oPrev = stage_piece(end, img), oNext = stage_piece(end, img), oPts = stage_piece(end, np2), oOut = stage_piece(end, np2),
+                 oSt = stage_piece(end, (size_t)n), oErr = stage_piece(end, (size_t)n * sizeof(float));
+    char* b;
+    void* work;
     int rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, img, &dp))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE1, img, &dn))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, np2, &dpts))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE3, np2, &dout))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE4, (size_t)std::max(n, 1), &dst))) return rc;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)std::max(n, 1) * sizeof(float), &derr))) return rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
     if ((rc = tb_scratch(ctx, TB_SLOT_LK, tbk_lk_work_bytes(width, height, max_level, 1), &work))) return rc;
-    TB_HIP(ctx, hipMemcpyAsync(dp, prev, img, hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemcpyAsync(dn, next, img, hipMemcpyHostToDevice, ctx->stream));
-    if (n) TB_HIP(ctx, hipMemcpyAsync(dpts, prev_pts, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TB_UPLOAD(ctx, b + oPrev, prev, img);
+    TB_UPLOAD(ctx, b + oNext, next, img);
+    TB_UPLOAD(ctx, b + oPts, prev_pts, np2);
     int top = 0;
-    rc = tbk_lk_track(ctx, 1, (const uint8_t*)dp, (const uint8_t*)dn, width, height, stride, 0, (const float*)dpts, nullptr, n, n, win,
-                      max_level, (float*)dout, (uint8_t*)dst, (float*)derr, work, &top);
+    rc = tbk_lk_track(ctx, 1, (const uint8_t*)(b + oPrev), (const uint8_t*)(b + oNext), width, height, stride, 0, (const float*)(b + oPts),
+                      nullptr, n, n, win, max_level, (float*)(b + oOut), (uint8_t*)(b + oSt), (float*)(b + oErr), work, &top);
     if (rc) return rc;
-    if (n) {
-        TB_HIP(ctx, hipMemcpyAsync(next_pts, dout, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(status, dst, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        if (err) TB_HIP(ctx, hipMemcpyAsync(err, derr, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
+    TB_DOWNLOAD(ctx, next_pts, b + oOut, np2);
+    TB_DOWNLOAD(ctx, status, b + oSt, (size_t)n);
+    if (err) TB_DOWNLOAD(ctx, err, b + oErr, (size_t)n * sizeof(float));
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (top_level) *top_level = top;
     return TB_OK;
@@ -1508,38 +1500,28 @@ int tb_search_by_opflow(tb_ctx* ctx, const uint8_t* img1, const uint8_t* img2, i
     TB_ENTER(ctx);
     if (!ctx || !count || !cam1 || n < 0 || cap < 0 || (n && (!cur_points || !keys2_xy)) || (cap && !out)) return TB_EINVAL;
     *count = 0;
-    std::vector<uint8_t> status((size_t)std::max(n, 1)), eq;
+    if (!img1 || !img2 || width < 1 || height < 1 || stride < width) return TB_EINVAL;
+    /* one pair of n keys (pitch 1 when n = 0: the images are still checked and equalised); the list holds every match */
+    const size_t img = (size_t)stride * height, p = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oI1 = stage_piece(end, img), oI2 = stage_piece(end, img), oKeys = stage_piece(end, p * 2 * sizeof(float)),
+                 oCur = stage_piece(end, p * 2 * sizeof(float)), oSt = stage_piece(end, p), oOut = stage_piece(end, p * sizeof(tb_match)),
+                 oCnt = stage_piece(end, 16);
+    char* b;
     int rc;
-    if (equalized) { /* matcher.cpp:736-739: img1 = F1->Equalize() = CLAHE(3.0, 8 x 8) of F1's level 0 (Frame.cpp:453-458) */
-        eq.resize((size_t)stride * height);
-        if ((rc = tb_clahe(ctx, img1, width, height, stride, 3.0, 8, 8, eq.data(), stride))) return rc;
-        img1 = eq.data();
-    }
-    /* matcher.cpp:744: calcOpticalFlowPyrLK(img2, img1, keys of F2, cur_points, ..., Size(21, 21), 3) */
-    rc = tb_optical_flow_pyr_lk(ctx, img2, img1, width, height, stride, keys2_xy, n, 21, 3, cur_points, status.data(), nullptr, nullptr);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++) {
-        if (!status[i]) continue;
-        /* :746-748, IsInFrame(Vector2i(cur.x, cur.y)): the conversion truncates; out-of-int-range converts to INT_MIN on
-         * x86 and fails the test */
-        const float x = cur_points[2 * i], y = cur_points[2 * i + 1];
-        bool in = fabsf(x) < 2147483648.f && fabsf(y) < 2147483648.f;
-        if (in) {
-            const int u = (int)x, v = (int)y;
-            in = u >= 0 && u < (int)((float)cam1->width * 1.f) && v >= 0 && v < (int)((float)cam1->height * 1.f);
-        }
-        if (!in) status[i] = 0;
-    }
-    if (reject && (rc = tb_reject_with_f(ctx, cur_points, keys2_xy, n, status.data()))) return rc; /* matcher.cpp:751-755 */
-    int m = 0;
-    for (int i = 0; i < n; i++) {
-        if (!status[i]) continue;
-        if (m >= cap) return tb_fail(ctx, TB_ECAPACITY, "searchByOPFlow: more than %d matches", cap);
-        out[m].queryIdx = i; out[m].trainIdx = i; out[m].imgIdx = -1; out[m].distance = 3.402823466e+38f; /* cv::DMatch() */
-        m++;
-    }
-    *count = m;
-    return TB_OK;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt[3] = {n, 0, 0}; /* n, then the match count and a flag that stays 0 */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oI1, img1, img);
+    TB_UPLOAD(ctx, b + oI2, img2, img);
+    TB_UPLOAD(ctx, b + oKeys, keys2_xy, (size_t)n * 2 * sizeof(float));
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    if ((rc = tb_search_by_opflow_batch_dev(ctx, 1, (const uint8_t*)(b + oI1), (const uint8_t*)(b + oI2), width, height, stride, img, cam1,
+                                            (const float*)(b + oKeys), dcnt, (int)p, equalized, reject, (float*)(b + oCur),
+                                            (uint8_t*)(b + oSt), (tb_match*)(b + oOut), (int)p, dcnt + 1)))
+        return rc;
+    TB_DOWNLOAD(ctx, cur_points, b + oCur, (size_t)n * 2 * sizeof(float));
+    return match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 1, cap, out, count);
 }
 
 int tb_search_by_opflow_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* img1, const uint8_t* img2, int width, int height, int stride,
@@ -1555,7 +1537,7 @@ int tb_search_by_opflow_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* img1, 
     const uint8_t* next = img1;
     if (equalized) { /* matcher.cpp:736-739: img1 = F1->Equalize() (Frame.cpp:453-458) */
         void *eq, *lut;
-        if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, (size_t)npairs * image_pitch, &eq))) return rc;
+        if ((rc = tb_scratch(ctx, TB_SLOT_OPFLOW_EQ, (size_t)npairs * image_pitch, &eq))) return rc;
         if ((rc = tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * 8 * 8 * 256, &lut))) return rc;
         if ((rc = tbk_clahe(ctx, npairs, img1, width, height, stride, image_pitch, 3.0, 8, 8, (uint8_t*)eq, stride, image_pitch, (uint8_t*)lut))) return rc;
         next = (const uint8_t*)eq;
@@ -1582,31 +1564,32 @@ int tb_search_by_opflow_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* img1, 
     return rc;
 }
 
-/* Matcher::rejectWithF / cv::findFundamentalMat, host forms: upload, one workgroup, download */
+/* Matcher::rejectWithF / cv::findFundamentalMat, host forms: the launcher, which returns F and the iteration count */
 static int ransac_host(tb_ctx* ctx, const float* p1, const float* p2, int n, uint8_t* status, int mode, double thresh, double conf,
                        double* F, int* iters, int* flag) {
-    void *d1, *d2, *dst, *work, *misc;
+    const size_t nb = (size_t)n * 2 * sizeof(float);
+    size_t end = 0;
+    const size_t o1 = stage_piece(end, nb), o2 = stage_piece(end, nb), oSt = stage_piece(end, (size_t)n), oFl = stage_piece(end, 8),
+                 oF = stage_piece(end, 9 * sizeof(double));
+    char* b;
+    void* work;
     int rc;
-    const size_t nb = (size_t)std::max(n, 1) * 2 * sizeof(float);
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE0, nb, &d1)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE1, nb, &d2)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE2, (size_t)std::max(n, 1), &dst)) ||
-        (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(1, n), &work)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, 256, &misc)))
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(1, n), &work)))
         return rc;
-    hipStream_t s = ctx->stream;
-    TB_HIP(ctx, hipMemcpyAsync(d1, p1, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(d2, p2, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    TB_HIP(ctx, hipMemcpyAsync(dst, status, (size_t)n, hipMemcpyHostToDevice, s));
-    int32_t* d_flag = (int32_t*)misc;
-    int32_t* d_iters = d_flag + 1;
-    double* d_F = (double*)((char*)misc + 16);
-    TB_HIP(ctx, hipMemsetAsync(misc, 0, 128, s));
-    if ((rc = tbk_ransac_f(ctx, 1, (const float*)d1, (const float*)d2, (uint8_t*)dst, nullptr, n, mode, thresh, conf, work, d_flag, d_F, d_iters)))
+    int32_t* dfl = (int32_t*)(b + oFl); /* flag, then the iterations */
+    TB_UPLOAD(ctx, b + o1, p1, nb);
+    TB_UPLOAD(ctx, b + o2, p2, nb);
+    TB_UPLOAD(ctx, b + oSt, status, (size_t)n);
+    TB_HIP(ctx, hipMemsetAsync(b + oF, 0, 9 * sizeof(double), ctx->stream)); /* F stays 0 where no model comes back */
+    if ((rc = tbk_ransac_f(ctx, 1, (const float*)(b + o1), (const float*)(b + o2), (uint8_t*)(b + oSt), nullptr, n, mode, thresh, conf, work,
+                           dfl, (double*)(b + oF), dfl + 1)))
         return rc;
     int32_t h[2] = {0, 0};
     double hF[9];
-    TB_HIP(ctx, hipMemcpyAsync(status, dst, (size_t)n, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipMemcpyAsync(h, misc, sizeof h, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipMemcpyAsync(hF, d_F, sizeof hF, hipMemcpyDeviceToHost, s));
-    TB_HIP(ctx, hipStreamSynchronize(s));
+    TB_DOWNLOAD(ctx, status, b + oSt, (size_t)n);
+    TB_DOWNLOAD(ctx, h, dfl, sizeof h);
+    TB_DOWNLOAD(ctx, hF, b + oF, sizeof hF);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (flag) *flag = h[0];
     if (iters) *iters = h[1];
     if (F) memcpy(F, hF, sizeof hF);
@@ -1677,17 +1660,27 @@ int tb_add_map_points_by_stereo(tb_ctx* ctx, const uint8_t* img_stereo, const ui
     *n_depth = 0;
     for (int i = 0; i < n; i++) depth[i] = -1.0f;
     if (n == 0) return TB_OK;
-    std::vector<float> cur((size_t)2 * n);
-    std::vector<tb_match> mt((size_t)n);
-    int cnt = 0;
-    const int rc = tb_search_by_opflow(ctx, img_stereo, img_current, width, height, stride, cam_stereo, keys_xy, n, 1, 1, cur.data(),
-                                       mt.data(), n, &cnt);
-    if (rc) return rc;
-    for (int k = 0; k < cnt; k++) {  /* LocalBA.cpp:58-65: left_id = trainIdx, right_id = queryIdx (equal) */
-        const int i = mt[k].trainIdx;
-        depth[i] = bf / fabsf(cur[2 * mt[k].queryIdx] - keys_xy[2 * i]);
-    }
-    *n_depth = cnt;
+    if (width < 1 || height < 1 || stride < width) return TB_EINVAL;
+    const size_t img = (size_t)stride * height;
+    size_t end = 0;
+    const size_t oI1 = stage_piece(end, img), oI2 = stage_piece(end, img), oKeys = stage_piece(end, (size_t)n * 2 * sizeof(float)),
+                 oCur = stage_piece(end, (size_t)n * 2 * sizeof(float)), oSt = stage_piece(end, (size_t)n),
+                 oDepth = stage_piece(end, (size_t)n * sizeof(float));
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_UPLOAD(ctx, b + oI1, img_stereo, img);
+    TB_UPLOAD(ctx, b + oI2, img_current, img);
+    TB_UPLOAD(ctx, b + oKeys, keys_xy, (size_t)n * 2 * sizeof(float));
+    if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, 1, (const uint8_t*)(b + oI1), (const uint8_t*)(b + oI2), width, height, stride, img,
+                                                    cam_stereo, (const float*)(b + oKeys), nullptr, n, bf, (float*)(b + oCur),
+                                                    (uint8_t*)(b + oSt), (float*)(b + oDepth))))
+        return rc;
+    std::vector<uint8_t> status((size_t)n);
+    TB_DOWNLOAD(ctx, depth, b + oDepth, (size_t)n * sizeof(float));
+    TB_DOWNLOAD(ctx, status.data(), b + oSt, (size_t)n);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_depth = (int)std::count(status.begin(), status.end(), 1); /* the keys that kept a match */
     return TB_OK;
 }
 
@@ -1805,7 +1798,7 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     /* every scratch slot the step's operators use, at its largest size now: a step never grows one (growth synchronises) */
     const size_t pitch = img;
     void* d;
-    if ((rc = tb_scratch(ctx, TB_SLOT_STAGE5, S * pitch, &d)) || (rc = tb_scratch(ctx, TB_SLOT_WORK, S * 8 * 8 * 256, &d)) ||
+    if ((rc = tb_scratch(ctx, TB_SLOT_OPFLOW_EQ, S * pitch, &d)) || (rc = tb_scratch(ctx, TB_SLOT_WORK, S * 8 * 8 * 256, &d)) ||
         (rc = tb_scratch(ctx, TB_SLOT_LK, std::max(tbk_lk_work_bytes(p->width, p->height, 3, nseq), S * P * 3 * sizeof(double)), &d)) ||
         (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, S * sizeof(int32_t), &d)) ||
         (rc = tb_scratch(ctx, TB_SLOT_STEREO_MATCHES, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, TB_SLOT_STEREO_COUNTS, S * sizeof(int32_t), &d)))
@@ -1828,9 +1821,9 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
         TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, S * sizeof(int32_t), ctx->stream));
-        /* the matcher's slots: searchByBF's best rows per side (STAGE2 / STAGE3), searchByViolence's (WORK, shared with CLAHE) */
+        /* the matcher's slots: searchByBF's best rows per side, searchByViolence's (WORK, shared with CLAHE) */
         if (vo->tr.kind == TB_VO_BF) {
-            if ((rc = tb_scratch(ctx, TB_SLOT_STAGE2, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_STAGE3, S * P * 8, &d))) return rc;
+            if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, S * P * 8, &d))) return rc;
         } else if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * P * 16, &d))) {
             return rc;
         }

@@ -17,23 +17,24 @@
 #define TB_NODE_CAP_MAX 2048  /* quadtree list capacity that fits LDS (k_octree.hip) */
 #define TB_GRID_CELLS (120 * 36) /* Frame's key lookup grid, FRAME_GRID_COLS x FRAME_GRID_ROWS */
 
-/* tb_scratch slots. A slot keeps what a call put there until the next call that takes it: host forms stage in 0-5, _dev
- * forms keep their work in 6-11, and an entry point that chains others (stereo -> opflow -> LK -> RANSAC, the VO step)
- * must not hand them a slot it still reads. */
+/* tb_scratch slots. A slot keeps what a call put there until the next call that takes it, and an entry point that chains
+ * others (stereo -> opflow -> LK -> RANSAC, the VO step) must not hand them a slot it still reads. Host forms stage in
+ * TB_SLOT_HOST and nothing else does. */
 enum {
-    TB_SLOT_STAGE0 = 0,         /* host forms: staged inputs and outputs (the single-frame matchers: all of them) */
-    TB_SLOT_STAGE1 = 1,         /* host forms: staged inputs and outputs */
-    TB_SLOT_STAGE2 = 2,         /* host forms; tb_search_by_bf_batch_dev: best match per train descriptor */
-    TB_SLOT_STAGE3 = 3,         /* host forms; tb_search_by_bf_batch_dev: best match per query descriptor */
-    TB_SLOT_STAGE4 = 4,         /* host forms; tb_bow_transform_batch_dev: node ids; tb_stereo_tracks_to_obs_batch_dev: sigma table */
-    TB_SLOT_STAGE5 = 5,         /* host forms; tb_bow_transform_batch_dev: weights; tb_search_by_opflow_batch_dev: equalised images */
-    TB_SLOT_WORK = 6,           /* _dev forms: one call's work (matchers' best rows, local BA, CLAHE tables) */
-    TB_SLOT_LK = 7,             /* LK pyramids (tbk_lk_work_bytes); tb_pose_opt_batch_dev: residuals */
-    TB_SLOT_RANSAC = 8,         /* tbk_ransac_f work */
-    TB_SLOT_RANSAC_FLAGS = 9,   /* tbk_ransac_f flags (host form: flags, F and iterations) */
-    TB_SLOT_STEREO_MATCHES = 10, /* tb_add_map_points_by_stereo_batch_dev: the opflow matches it does not return */
-    TB_SLOT_STEREO_COUNTS = 11, /* tb_add_map_points_by_stereo_batch_dev: their counts */
-    TB_NSLOTS = 12
+    TB_SLOT_HOST = 0,           /* host forms: staged inputs and outputs */
+    TB_SLOT_BF_TRAIN = 1,       /* tb_search_by_bf_batch_dev: best match per train descriptor */
+    TB_SLOT_BF_QUERY = 2,       /* tb_search_by_bf_batch_dev: best match per query descriptor */
+    TB_SLOT_BOW_NODES = 3,      /* tb_bow_transform_batch_dev: node ids */
+    TB_SLOT_STEREO_SIGMA = 3,   /*   shared: tb_stereo_tracks_to_obs_batch_dev's sigma table */
+    TB_SLOT_BOW_WEIGHTS = 4,    /* tb_bow_transform_batch_dev: weights */
+    TB_SLOT_OPFLOW_EQ = 4,      /*   shared: tb_search_by_opflow_batch_dev's equalised images */
+    TB_SLOT_WORK = 5,           /* _dev forms: one call's work (matchers' best rows, local BA, CLAHE tables) */
+    TB_SLOT_LK = 6,             /* LK pyramids (tbk_lk_work_bytes); tb_pose_opt_batch_dev: residuals */
+    TB_SLOT_RANSAC = 7,         /* tbk_ransac_f work */
+    TB_SLOT_RANSAC_FLAGS = 8,   /* tbk_ransac_f flags */
+    TB_SLOT_STEREO_MATCHES = 9, /* tb_add_map_points_by_stereo_batch_dev: the opflow matches it does not return */
+    TB_SLOT_STEREO_COUNTS = 10, /* tb_add_map_points_by_stereo_batch_dev: their counts */
+    TB_NSLOTS = 11
 };
 
 struct tb_ctx {
