@@ -452,27 +452,72 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
  *             map points exactly as the optical-flow loop makes them; the frame becomes the keyframe (its records, descriptors,
  *             map points and, for violence, its lookup grid -- built once per keyframe)
  * As for optical flow, after the first step a step makes no host synchronisation and no host <-> device copy; the matcher's flags
- * stay on the device (tb_vo_tracker_state_dev; violence with factor = 1 / HISTO_LENGTH never flags). */
-enum { TB_VO_OPFLOW = 0, TB_VO_BF = 1, TB_VO_VIOLENCE = 2 };
+ * stay on the device (tb_vo_tracker_state_dev; violence with factor = 1 / HISTO_LENGTH never flags).
+ *
+ * The projection trackers: test/test_projection.cpp test_projection (:449-646) is test_kitti's loop with the tracking line
+ * replaced by one of two commented lines, both named with full arguments:
+ *   TB_VO_PROJECTION      setProjectionParam(30, 50, 30, true, 30); searchByProjection(cur, key_frame) (:512-513): nratio 30,
+ *                         th_high 50, histo_len 30, check_orientation 1. F1 = the current frame, F2 = the keyframe: its keys
+ *                         (octave, angle), its key-aligned map points and those points' descriptors
+ *   TB_VO_PROJECTION_MAP  setProjectionParam(30, 50, 30, true, 20); searchByProjection(map_ptr, cur, 0.6) (:516-517): nratio 20,
+ *                         radio 0.6, th_high 50, against the sequence's own map; trainIdx indexes the live map
+ *                         (map_ptr->GetAllMapPoints().at(trainIdx), :527). The predicted level is the reference's constant 0, so
+ *                         only keys of octave 0 can match (Frame.cpp:403, matcher.cpp:568)
+ * th_high >= 0, histo_len in 1..1024 and, for the map, map_keyframes >= 1 (TB_EINVAL otherwise). A projection frame t follows
+ * the descriptor frame above, with these differences:
+ *   every frame  after ORB, AssignFeaturesToGrid on the current frame's keys (:504): the matchers look up the CURRENT frame's
+ *                grid. The pose the matcher projects with is the last frame's Tcw (:510)
+ *   tracking     t > 0: taken1 is all zero -- Frame::AddMapPoint (Frame.cpp:322-326) never calls AddObservation, so
+ *                Observations() is 0 throughout the loop. The matchers emit one match per map point, so several matches may
+ *                name one key: the later match in list order wins it. Rows in key order, invSigma2 by octave, fewer than 3 rows
+ *                hold the pose, as above
+ *   descriptor   a map point's descriptor is the row of the frame that created it (MapPoint.cpp:35-36, :631), not the keyframe's
+ *                row at the entry it was carried to: 32 bytes travel with xyz, in the frame state and in the keyframe snapshot
+ *   keyframe     as above; with the map, every new point is also appended to it in key order (:631-634) as a tb_mappoint:
+ *                pos, normal = (pos - Ow) / |pos - Ow| (MapPoint.cpp:22-24; float32, left to right), min_dist 1 and max_dist
+ *                1000 (the constants GetMin/MaxDistanceInvariance return, MapPoint.cpp:207-217: a point nearer than 1 m or farther
+ *                than 1000 m never matches -- reproduced, not fixed), bad 0, and the key's descriptor. map_ptr->AddKeyFrame (:635)
+ *                has no effect on matching and is dropped
+ * The map (the one deviation): the reference's map only grows; device memory is fixed, so the map holds the points of the last
+ * map_keyframes keyframes (capacity map_keyframes * key_pitch), in insertion order. When keyframe number map_keyframes + 1 arrives
+ * the oldest keyframe's points leave as a block and the rest move down (a keyframe that spawned no point still counts as a
+ * block). A run with at most map_keyframes keyframes is the reference's loop exactly. The match list of the map tracker holds one
+ * match per map point at most: its capacity is the map's, not key_pitch (tb_vo_map_state_dev). */
+enum { TB_VO_OPFLOW = 0, TB_VO_BF = 1, TB_VO_VIOLENCE = 2, TB_VO_PROJECTION = 3, TB_VO_PROJECTION_MAP = 4 };
 typedef struct tb_vo_tracker {
-    int kind;                       /* TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE */
+    int kind;                       /* TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, TB_VO_PROJECTION_MAP */
     float bf_ratio, bf_min_th;      /* searchByBF ratio / minTh (:712: 10, 30) */
     int min_level, max_level;       /* both descriptor trackers (:712, :713: 0, 5) */
     float radius;                   /* searchByViolence search radius (:713: 50) */
-    int th_low; float nratio; int histo_len; int check_orientation;   /* the Matcher's fields at :713: 50, 6, 30, 1 */
+    int th_low; float nratio; int histo_len; int check_orientation;   /* the Matcher's fields at :713: 50, 6, 30, 1;
+                                       projection: nratio 30 (map: 20), histo_len 30, check_orientation 1 */
+    int th_high;                    /* projection trackers: the Matcher's TH_HIGH (50) */
+    float radio;                    /* TB_VO_PROJECTION_MAP: searchByProjection's radio (0.6) */
+    int map_keyframes;              /* TB_VO_PROJECTION_MAP: keyframes the map holds (4) */
 } tb_vo_tracker;
 /* tb_vo_create with a tracker; tracker NULL or kind TB_VO_OPFLOW = tb_vo_create. */
 int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* params, const tb_vo_tracker* tracker, int nseq, tb_vo** out);
 /* Device views of a descriptor tracker's state after the last step (valid until the next step; every output nullable; TB_ESTATE
  * for an optical-flow loop):
  *   orb [nseq][key_pitch] tb_keypoint, orb_desc [nseq][key_pitch][32], orb_counts [nseq]: the current frame's ORB keys (= its keys)
- *   matches [nseq][key_pitch] (queryIdx = current key, trainIdx = keyframe key), match_counts [nseq] (0 at frame 0), flags [nseq]
+ *   matches [nseq][key_pitch] (queryIdx = current key, trainIdx = keyframe key), match_counts [nseq] (0 at frame 0), flags [nseq];
+ *   TB_VO_PROJECTION_MAP: matches [nseq][map capacity], trainIdx = live map index
  *   the keyframe: kf_orb / kf_desc / kf_counts as above, kf_map_points [nseq][key_pitch][3], kf_mp_valid [nseq][key_pitch];
  *   *kf_frame = the index of its frame (-1 before any) */
 int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** orb_desc, const int32_t** orb_counts,
                             const tb_match** matches, const int32_t** match_counts, const int32_t** flags, const tb_keypoint** kf_orb,
                             const uint8_t** kf_desc, const float** kf_map_points, const uint8_t** kf_mp_valid,
                             const int32_t** kf_counts, int* kf_frame);
+/* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
+ * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
+ * where its map point is valid. */
+int tb_vo_mp_desc_dev(tb_vo* vo, const uint8_t** mp_desc, const uint8_t** kf_mp_desc);
+/* Device views of the map of a TB_VO_PROJECTION_MAP loop after the last step (valid until the next step; every output nullable;
+ * TB_ESTATE for a loop without a map): points [nseq][capacity] records in insertion order and desc [nseq][capacity][32], of which
+ * counts[s] are live; block_counts [nseq][map_keyframes]: the points each held keyframe added, oldest first (*blocks of them are
+ * in use). *capacity = map_keyframes * key_pitch = the match capacity. */
+int tb_vo_map_state_dev(tb_vo* vo, const tb_mappoint** points, const uint8_t** desc, const int32_t** counts,
+                        const int32_t** block_counts, int* capacity, int* map_keyframes, int* blocks);
 
 /* ---- multi-GPU batch entry (SURVEY.md section 8(b) `tb_batch_run`, 8(e): frames are independent units through
  * extract -> left/right match, sharded as contiguous blocks of frames, one exchange step at the end).

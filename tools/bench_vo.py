@@ -9,7 +9,10 @@ repeated to fill the batch) and uploaded before anything is timed, so the steps 
     prof    the same steps with the library's per-kernel event timing on (tb_profile_*): the per-kernel split
 
 --tracker picks the loop's tracking line (test_vo.cpp:712-716): opflow (default), bf or violence with the reference's arguments;
-the descriptor trackers also report their matches per tracking frame. Prints one JSON line.
+the descriptor trackers also report their matches per tracking frame. projection and projection_map are the two lines of
+test_projection.cpp:512-517; the map tracker's step grows with its map, so its tracking step is also reported by the number of
+keyframes the map holds (--map-keyframes, default 4; --steps 41 fills four at the default keyframe period). Prints one JSON
+line.
 """
 import argparse
 import json
@@ -29,13 +32,13 @@ def centre(T):
     return -T[:3, :3].T @ T[:3, 3]
 
 
-def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow"):
+def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow", params=None):
     D = L.shape[1]
     rep = lambda a: a[:, np.arange(S) % D]   # noqa: E731
     dL = torch.from_numpy(np.ascontiguousarray(rep(L))).cuda()
     dR = torch.from_numpy(np.ascontiguousarray(rep(R))).cuda()
     Gs = rep(G)
-    vo = StereoVO(S, keyframe_every=every, tracker=tracker)
+    vo = StereoVO(S, keyframe_every=every, tracker=tracker, **(params or {}))
     try:
         # stats (and the first step, which sizes every buffer)
         vo.reset(Gs[0])
@@ -81,6 +84,11 @@ def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow"):
     if mts:
         mts = np.array(mts)
         extra["matches_per_frame"] = dict(mean=round(float(mts.mean()), 1), min=int(mts.min()))
+    if tracker == "projection_map":
+        # tracking frame t matches against the points of min(t // every + 1, map_keyframes) keyframes
+        held = np.array([min(t // every + 1, params["map_keyframes"]) for t in range(T)])
+        extra["ms_per_track_step_by_map_keyframes"] = {str(k): round(float(ms[~kf & (held == k)].mean()), 4)
+                                                       for k in sorted(set(held[~kf].tolist()))}
     return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3),
                 ms_per_track_step=round(float(ms[~kf].mean()), 4), ms_per_keyframe_step=round(float(ms[kf].mean()), 4),
                 ms_first_keyframe_step=round(float(ms[0]), 4), kernels_ms_over_T_steps=kern,
@@ -96,16 +104,20 @@ def main():
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--distinct", type=int, default=4, help="different synthetic sequences, repeated to fill a batch")
     ap.add_argument("--keyframe-every", type=int, default=10)
-    ap.add_argument("--tracker", choices=("opflow", "bf", "violence"), default="opflow")
+    ap.add_argument("--tracker", choices=("opflow", "bf", "violence", "projection", "projection_map"), default="opflow")
+    ap.add_argument("--map-keyframes", type=int, default=4, help="projection_map: keyframes the map holds")
+    ap.add_argument("--speed", type=float, default=0.5, help="metres per frame of the synthetic sequences")
     ap.add_argument("--timed-only", action="store_true", help="first pass without state reads, then the timed pass only "
                     "(for a trace of the steps: no host <-> device copy between them)")
     args = ap.parse_args()
     T = args.steps
-    seqs = [synth_seq.sequence(s, T) for s in range(args.distinct)]
+    seqs = [synth_seq.sequence(s, T, speed=args.speed) for s in range(args.distinct)]
+    params = dict(map_keyframes=args.map_keyframes) if args.tracker == "projection_map" else None
     L = np.stack([q[0] for q in seqs], 1); R = np.stack([q[1] for q in seqs], 1); G = np.stack([q[2] for q in seqs], 1)
-    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker) for S in args.sizes.split(",")]
+    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker, params) for S in args.sizes.split(",")]
     print(json.dumps(dict(tool="bench_vo", tracker=args.tracker, device=torch.cuda.get_device_name(0), width=1241, height=376,
-                          keyframe_every=args.keyframe_every, distinct_sequences=args.distinct, results=res)))
+                          keyframe_every=args.keyframe_every, distinct_sequences=args.distinct, speed_m_per_frame=args.speed,
+                          **(params or {}), results=res)))
 
 
 if __name__ == "__main__":

@@ -43,7 +43,7 @@ EXPORTS = [
     "tb_clahe", "tb_clahe_dev", "tb_optical_flow_pyr_lk", "tb_optical_flow_pyr_lk_dev", "tb_optical_flow_pyr_lk_batch_dev", "tb_search_by_opflow", "tb_search_by_opflow_batch_dev",
     "tb_find_fundamental_ransac", "tb_reject_with_f", "tb_reject_with_f_batch_dev", "tb_add_map_points_by_stereo", "tb_add_map_points_by_stereo_batch_dev",
     "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
-    "tb_vo_create_ex", "tb_vo_tracker_state_dev",
+    "tb_vo_create_ex", "tb_vo_tracker_state_dev", "tb_vo_mp_desc_dev", "tb_vo_map_state_dev",
 ]
 
 
@@ -173,14 +173,14 @@ class VOParams(C.Structure):
                 ("init_th", C.c_float), ("min_th", C.c_float), ("K", C.c_double * 4), ("bf", C.c_float), ("keyframe_every", C.c_int)]
 
 
-TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE = 0, 1, 2
+TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, TB_VO_PROJECTION_MAP = 0, 1, 2, 3, 4
 
 
 class VOTracker(C.Structure):
     """tb_vo_tracker of include/tb_capi.h"""
     _fields_ = [("kind", C.c_int), ("bf_ratio", C.c_float), ("bf_min_th", C.c_float), ("min_level", C.c_int), ("max_level", C.c_int),
                 ("radius", C.c_float), ("th_low", C.c_int), ("nratio", C.c_float), ("histo_len", C.c_int),
-                ("check_orientation", C.c_int)]
+                ("check_orientation", C.c_int), ("th_high", C.c_int), ("radio", C.c_float), ("map_keyframes", C.c_int)]
 
 
 class VO:
@@ -237,6 +237,21 @@ class VO:
                  "kf_mp_valid", "kf_counts")
         out = {k: q.value for k, q in zip(names, ptrs)}
         out["kf_frame"] = kf_frame.value
+        return out
+
+    def mp_desc_dev(self):
+        """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self.ctx.check(lib().tb_vo_mp_desc_dev(self._h, C.byref(a), C.byref(b)))
+        return dict(mp_desc=a.value, kf_mp_desc=b.value)
+
+    def map_state_dev(self):
+        """dict of device pointers of the map tracker's map (points, desc, counts, block_counts) + capacity, map_keyframes, blocks."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        cap, mk, nb = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.ctx.check(lib().tb_vo_map_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(cap), C.byref(mk), C.byref(nb)))
+        out = {k: q.value for k, q in zip(("points", "desc", "counts", "block_counts"), ptrs)}
+        out["capacity"], out["map_keyframes"], out["blocks"] = cap.value, mk.value, nb.value
         return out
 
 

@@ -200,6 +200,189 @@ k_vo_kf_spawn(const float* __restrict__ keys, const int32_t* __restrict__ key_co
     }
 }
 
+/* Projection trackers (test/test_projection.cpp test_projection, :512-517 with the commented lines enabled): the carry after
+ * searchByProjection. As k_vo_match_carry -- a fresh frame, the last match in list order wins a key (the projection matchers
+ * emit one match per map point, so several may name the same key: win[] decides by atomicMax over match indices), rows in key
+ * order, invSigma2 by octave -- with two differences:
+ *   - a map point's descriptor is the row of the frame that created it (MapPoint.cpp:35-36), so the 32 bytes travel with xyz;
+ *   - MAP = false: trainIdx names a keyframe entry (src_mp / src_valid / src_desc at stride `pitch`, key aligned);
+ *     MAP = true: trainIdx names a live map record (map_ptr->GetAllMapPoints().at(trainIdx), :527; records at stride
+ *     src_pitch) and the match list is src_pitch long, one match per map point at most.
+ * Keys without a map point get a zero descriptor. */
+template <bool MAP>
+__global__ void __launch_bounds__(256)
+k_vo_proj_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__ orb_counts, const tb_match* __restrict__ matches,
+                const int32_t* __restrict__ match_counts, int match_pitch, const float* __restrict__ src_mp,
+                const uint8_t* __restrict__ src_valid, const tb_mappoint* __restrict__ src_rec, const uint8_t* __restrict__ src_desc,
+                const int32_t* __restrict__ src_counts, int src_pitch, int pitch, tb_vo_sigma sig, int32_t* __restrict__ win,
+                float* __restrict__ keys, int32_t* __restrict__ key_counts, float* __restrict__ mp, uint8_t* __restrict__ valid,
+                uint8_t* __restrict__ mp_desc, tb_obs* __restrict__ obs, int32_t* __restrict__ obs_counts, uint8_t* __restrict__ outlier) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(orb_counts[s], 0), pitch);
+    const int nm = min(max(match_counts[s], 0), match_pitch);   /* the matcher's count is not truncated, its list is */
+    const int ns = min(max(src_counts[s], 0), src_pitch);
+    const size_t o = (size_t)s * pitch, os = (size_t)s * src_pitch;
+    const tb_keypoint* K = orb + o;
+    const tb_match* M = matches + (size_t)s * match_pitch;
+    int32_t* Wn = win + o;
+    for (int i = tid; i < n; i += 256) atomicExch(&Wn[i], -1);
+    __syncthreads();
+    for (int k = tid; k < nm; k += 256) {
+        const int q = M[k].queryIdx, tr = M[k].trainIdx;
+        if (q >= 0 && q < n && tr >= 0 && tr < ns && (MAP || src_valid[os + tr])) atomicMax(&Wn[q], k);
+    }
+    __syncthreads();
+    tb_obs* O = obs + o;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        bool ok = false;
+        tb_obs r = {0, 0, 0, 0, 0, 0};
+        if (i < n) {
+            const int k = atomicAdd(&Wn[i], 0);
+            ok = k >= 0;
+            float X = 0.f, Y = 0.f, Z = 0.f;
+            unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+            if (ok) {
+                const size_t j = os + M[k].trainIdx;
+                if (MAP) { X = src_rec[j].pos[0]; Y = src_rec[j].pos[1]; Z = src_rec[j].pos[2]; }
+                else { X = src_mp[3 * j]; Y = src_mp[3 * j + 1]; Z = src_mp[3 * j + 2]; }
+                const unsigned long long* D = reinterpret_cast<const unsigned long long*>(src_desc) + 4 * j;
+                d0 = D[0]; d1 = D[1]; d2 = D[2]; d3 = D[3];
+            }
+            mp[3 * (o + i)] = X; mp[3 * (o + i) + 1] = Y; mp[3 * (o + i) + 2] = Z;
+            unsigned long long* E = reinterpret_cast<unsigned long long*>(mp_desc) + 4 * (o + i);
+            E[0] = d0; E[1] = d1; E[2] = d2; E[3] = d3;
+            valid[o + i] = ok ? 1 : 0;
+            outlier[o + i] = 0;
+            const tb_keypoint kp = K[i];
+            keys[2 * (o + i)] = kp.x; keys[2 * (o + i) + 1] = kp.y;
+            r.u = kp.x; r.v = kp.y;
+            r.X = X; r.Y = Y; r.Z = Z;
+            r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];
+        }
+        const unsigned long long bm = __ballot(ok);
+        if (lane == 0) wsum[wave] = __popcll(bm);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        if (ok) O[at] = r; /* at < n <= pitch */
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
+}
+
+/* Keyframe of a projection tracker, after k_vo_kf_spawn (test_projection.cpp:631-634): every key j that spawned a point
+ * (the spawn's own test on depth[j]) gives the point its descriptor row; rec[j] (nullable) becomes the key-aligned tb_mappoint
+ * searchByProjection(F1, F2) reads of the keyframe -- pos and bad = "no map point"; it reads nothing else of it. With a map
+ * (map_rec != NULL) the spawned points are appended to the sequence's map tail in key order (ballot / prefix compaction as
+ * k_vo_track): pos, normal = (pos - Ow) / |pos - Ow| (MapPoint.cpp:22-24; Ow = twc as the spawn computes it; float32, one
+ * operation per statement, left to right), min_dist 1 and max_dist 1000 (the constants GetMin/MaxDistanceInvariance return,
+ * MapPoint.cpp:207-217), bad 0, and the descriptor. map_n[s] grows by the block's size, which goes to map_blocks[s][slot].
+ * A keyframe adds at most `pitch` points and the map holds nblk * pitch, so the tail never overflows; the store is guarded
+ * all the same. */
+__global__ void __launch_bounds__(256)
+k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__ depth, const float* __restrict__ mp,
+               const uint8_t* __restrict__ valid, const uint8_t* __restrict__ orb_desc, const float* __restrict__ Tcw, int pitch,
+               uint8_t* __restrict__ mp_desc, tb_mappoint* __restrict__ rec, tb_mappoint* __restrict__ map_rec,
+               uint8_t* __restrict__ map_desc, int32_t* __restrict__ map_n, int32_t* __restrict__ map_blocks, int nblk, int slot,
+               int map_pitch) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = min(max(key_counts[s], 0), pitch);
+    const size_t o = (size_t)s * pitch, om = (size_t)s * map_pitch;
+    const float* T = Tcw + 16 * s;
+    float t[3];
+    for (int i = 0; i < 3; i++) {
+        float a = T[i] * T[3];
+        const float b = T[4 + i] * T[7];
+        a = a + b;
+        const float c = T[8 + i] * T[11];
+        a = a + c;
+        t[i] = -a;
+    }
+    const int n0 = map_rec ? min(max(map_n[s], 0), map_pitch) : 0;
+    int base = 0;
+    for (int j0 = 0; j0 < m; j0 += 256) {
+        const int j = j0 + tid;
+        bool ok = false;
+        tb_mappoint r = {{0, 0, 0}, {0, 0, 0}, 0, 0, 1};
+        unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+        if (j < m) {
+            const float d = depth[o + j];
+            ok = d > 0.f && isfinite(d);
+            if (ok) {
+                const unsigned long long* D = reinterpret_cast<const unsigned long long*>(orb_desc) + 4 * (o + j);
+                d0 = D[0]; d1 = D[1]; d2 = D[2]; d3 = D[3];
+                unsigned long long* E = reinterpret_cast<unsigned long long*>(mp_desc) + 4 * (o + j);
+                E[0] = d0; E[1] = d1; E[2] = d2; E[3] = d3;
+            }
+            if (valid[o + j]) {
+                r.pos[0] = mp[3 * (o + j)]; r.pos[1] = mp[3 * (o + j) + 1]; r.pos[2] = mp[3 * (o + j) + 2];
+                r.bad = 0;
+            }
+            if (rec) rec[o + j] = r;
+        }
+        if (!map_rec) continue;   /* uniform over the workgroup */
+        const unsigned long long bm = __ballot(ok);
+        if (lane == 0) wsum[wave] = __popcll(bm);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        const int at = n0 + off + __popcll(bm & ((1ull << lane) - 1));
+        if (ok && at < map_pitch) {
+            const float e0 = r.pos[0] - t[0], e1 = r.pos[1] - t[1], e2 = r.pos[2] - t[2];
+            float q = e0 * e0;
+            const float q1 = e1 * e1;
+            q = q + q1;
+            const float q2 = e2 * e2;
+            q = q + q2;
+            const float len = sqrtf(q);
+            r.normal[0] = e0 / len; r.normal[1] = e1 / len; r.normal[2] = e2 / len;
+            r.min_dist = 1.0f; r.max_dist = 1000.0f;
+            map_rec[om + at] = r;
+            unsigned long long* E = reinterpret_cast<unsigned long long*>(map_desc) + 4 * (om + at);
+            E[0] = d0; E[1] = d1; E[2] = d2; E[3] = d3;
+        }
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (map_rec && tid == 0) {
+        map_n[s] = min(n0 + base, map_pitch);
+        map_blocks[(size_t)s * nblk + slot] = min(n0 + base, map_pitch) - n0;
+    }
+}
+
+/* The map holds the points of the last nblk keyframes. When one more arrives the oldest keyframe's points leave as a block and
+ * the rest move down: records [blocks[0], n) of the source buffers become [0, n - blocks[0]) of the destination buffers (a
+ * second set -- nothing is moved in place), the block counts move down one slot and the last slot is emptied for the append.
+ * Records (9 words) and descriptors (8 words) are copied as 32-bit words; grid (tiles, nseq). */
+__global__ void __launch_bounds__(256)
+k_vo_map_evict(const tb_mappoint* __restrict__ src_rec, const uint8_t* __restrict__ src_desc, const int32_t* __restrict__ src_n,
+               const int32_t* __restrict__ src_blocks, int nblk, int map_pitch, tb_mappoint* __restrict__ dst_rec,
+               uint8_t* __restrict__ dst_desc, int32_t* __restrict__ dst_n, int32_t* __restrict__ dst_blocks) {
+    const int s = blockIdx.y;
+    const int n = min(max(src_n[s], 0), map_pitch);
+    const int b0 = min(max(src_blocks[(size_t)s * nblk], 0), n);
+    const int keep = n - b0;
+    const size_t om = (size_t)s * map_pitch;
+    const uint32_t* R = reinterpret_cast<const uint32_t*>(src_rec + om + b0);
+    uint32_t* Rd = reinterpret_cast<uint32_t*>(dst_rec + om);
+    const uint32_t* D = reinterpret_cast<const uint32_t*>(src_desc) + 8 * (om + b0);
+    uint32_t* Dd = reinterpret_cast<uint32_t*>(dst_desc) + 8 * om;
+    const size_t step = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t nr = (size_t)keep * (sizeof(tb_mappoint) / 4), nd = (size_t)keep * 8;
+    for (size_t i = first; i < nr; i += step) Rd[i] = R[i];
+    for (size_t i = first; i < nd; i += step) Dd[i] = D[i];
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < nblk; i += 256) dst_blocks[(size_t)s * nblk + i] = i + 1 < nblk ? src_blocks[(size_t)s * nblk + i + 1] : 0;
+        if (threadIdx.x == 0) dst_n[s] = keep;
+    }
+}
+
 int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst) {
     if (nimg <= 0) return TB_OK;
     const int bx = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 512);
@@ -256,6 +439,59 @@ int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const in
     tb_prof_begin(ctx, "k_vo_match_carry");
     hipLaunchKernelGGL(k_vo_match_carry, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts, d_kf_mp,
                        d_kf_valid, d_kf_counts, pitch, sig, d_win, d_keys, d_key_counts, d_mp, d_valid, d_obs, d_obs_counts, d_outlier);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
+                      const int32_t* d_match_counts, int match_pitch, const float* d_src_mp, const uint8_t* d_src_valid,
+                      const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_counts, int src_pitch, int pitch,
+                      const float* inv_sigma2, int nlevels, int32_t* d_win, float* d_keys, int32_t* d_key_counts, float* d_mp,
+                      uint8_t* d_valid, uint8_t* d_mp_desc, tb_obs* d_obs, int32_t* d_obs_counts, uint8_t* d_outlier) {
+    if (nseq <= 0) return TB_OK;
+    if (nlevels < 1 || nlevels > TB_MAX_LEVELS || match_pitch < 1 || src_pitch < 1) return TB_EINVAL;
+    tb_vo_sigma sig = {};
+    for (int l = 0; l < nlevels; l++) sig.v[l] = inv_sigma2[l];
+    sig.n = nlevels;
+    if (map_mode) {
+        tb_prof_begin(ctx, "k_vo_proj_carry_map");
+        hipLaunchKernelGGL(k_vo_proj_carry<true>, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts,
+                           match_pitch, d_src_mp, d_src_valid, d_src_rec, d_src_desc, d_src_counts, src_pitch, pitch, sig, d_win, d_keys,
+                           d_key_counts, d_mp, d_valid, d_mp_desc, d_obs, d_obs_counts, d_outlier);
+    } else {
+        tb_prof_begin(ctx, "k_vo_proj_carry_kf");
+        hipLaunchKernelGGL(k_vo_proj_carry<false>, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts,
+                           match_pitch, d_src_mp, d_src_valid, d_src_rec, d_src_desc, d_src_counts, src_pitch, pitch, sig, d_win, d_keys,
+                           d_key_counts, d_mp, d_valid, d_mp_desc, d_obs, d_obs_counts, d_outlier);
+    }
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const float* d_depth, const float* d_mp, const uint8_t* d_valid,
+                     const uint8_t* d_orb_desc, const float* d_Tcw, int pitch, uint8_t* d_mp_desc, tb_mappoint* d_rec,
+                     tb_mappoint* d_map_rec, uint8_t* d_map_desc, int32_t* d_map_n, int32_t* d_map_blocks, int nblk, int slot,
+                     int map_pitch) {
+    if (nseq <= 0) return TB_OK;
+    if (d_map_rec && (nblk < 1 || slot < 0 || slot >= nblk || map_pitch < 1)) return TB_EINVAL;
+    tb_prof_begin(ctx, "k_vo_kf_append");
+    hipLaunchKernelGGL(k_vo_kf_append, dim3(nseq), dim3(256), 0, ctx->stream, d_key_counts, d_depth, d_mp, d_valid, d_orb_desc, d_Tcw, pitch,
+                       d_mp_desc, d_rec, d_map_rec, d_map_desc, d_map_n, d_map_blocks, nblk, slot, map_pitch);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_n,
+                     const int32_t* d_src_blocks, int nblk, int map_pitch, tb_mappoint* d_dst_rec, uint8_t* d_dst_desc, int32_t* d_dst_n,
+                     int32_t* d_dst_blocks) {
+    if (nseq <= 0) return TB_OK;
+    if (nblk < 1 || map_pitch < 1) return TB_EINVAL;
+    tb_prof_begin(ctx, "k_vo_map_evict");
+    hipLaunchKernelGGL(k_vo_map_evict, dim3(8, nseq), dim3(256), 0, ctx->stream, d_src_rec, d_src_desc, d_src_n, d_src_blocks, nblk, map_pitch,
+                       d_dst_rec, d_dst_desc, d_dst_n, d_dst_blocks);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -1728,7 +1728,24 @@ struct tb_vo {
     int32_t* kf_cell_start = nullptr;        /* [nseq][4321] violence: the keyframe's lookup grid */
     int32_t* kf_cell_items = nullptr;        /* [nseq][P] */
     int kf_frame = -1;
+    /* projection trackers (TB_VO_PROJECTION, TB_VO_PROJECTION_MAP) */
+    int Mcap = 0;                            /* match capacity: P, or the map's capacity */
+    float sf[TB_MAX_LEVELS];                 /* Frame::GetScaleFactors */
+    int32_t* cell_start = nullptr;           /* [nseq][4321] the current frame's lookup grid */
+    int32_t* cell_items = nullptr;           /* [nseq][P] */
+    uint8_t* taken = nullptr;                /* [nseq][P] zero: Observations() is 0 throughout the loop */
+    uint8_t* mp_desc = nullptr;              /* [nseq][P][32] the descriptors of the current frame's map points */
+    uint8_t* kf_mp_desc = nullptr;           /* [nseq][P][32] */
+    tb_mappoint* kf_rec = nullptr;           /* [nseq][P] TB_VO_PROJECTION: the keyframe's map points as the matcher reads them */
+    /* the map (TB_VO_PROJECTION_MAP): two sets, eviction moves the survivors from one into the other */
+    int mapK = 0, map_cap = 0, map_cur = 0, map_nblk = 0;   /* keyframes held, capacity, live set, blocks in use */
+    tb_mappoint* map_rec[2] = {nullptr, nullptr};   /* [nseq][map_cap] */
+    uint8_t* map_desc[2] = {nullptr, nullptr};      /* [nseq][map_cap][32] */
+    int32_t* map_n[2] = {nullptr, nullptr};         /* [nseq] live counts */
+    int32_t* map_blocks[2] = {nullptr, nullptr};    /* [nseq][mapK] points per held keyframe, oldest first */
 };
+
+static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
 
 void tb_vo_destroy(tb_vo* vo) {
     if (!vo) return;
@@ -1743,6 +1760,10 @@ void tb_vo_destroy(tb_vo* vo) {
     hipFree(vo->orb); hipFree(vo->orb_desc); hipFree(vo->orb_cnt); hipFree(vo->mflags); hipFree(vo->win); hipFree(vo->kf_orb);
     hipFree(vo->kf_desc); hipFree(vo->kf_cnt); hipFree(vo->kf_mp); hipFree(vo->kf_valid); hipFree(vo->kf_cell_start);
     hipFree(vo->kf_cell_items);
+    hipFree(vo->cell_start); hipFree(vo->cell_items); hipFree(vo->taken); hipFree(vo->mp_desc); hipFree(vo->kf_mp_desc); hipFree(vo->kf_rec);
+    for (int k = 0; k < 2; k++) {
+        hipFree(vo->map_rec[k]); hipFree(vo->map_desc[k]); hipFree(vo->map_n[k]); hipFree(vo->map_blocks[k]);
+    }
     delete vo;
 }
 
@@ -1766,6 +1787,13 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     int rc = tb_extractor_create(ctx, p->width, p->height, p->nlevels, sf.data(), nullptr, nullptr, nseq, p->target, &vo->ex);
     if (rc) return rc;
     vo->P = vo->ex->g.selCap;
+    vo->Mcap = vo->P;
+    if (vo->tr.kind == TB_VO_PROJECTION_MAP) {
+        if ((size_t)vo->tr.map_keyframes * (size_t)vo->P > (size_t)INT32_MAX / 64)
+            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: map_keyframes %d x %d keys is too large", vo->tr.map_keyframes, vo->P);
+        vo->mapK = vo->tr.map_keyframes;
+        vo->map_cap = vo->Mcap = vo->mapK * vo->P;
+    }
     memset(&vo->cam, 0, sizeof vo->cam);
     vo->cam.fx = (float)p->K[0]; vo->cam.fy = (float)p->K[1]; vo->cam.cx = (float)p->K[2]; vo->cam.cy = (float)p->K[3];
     vo->cam.width = p->width; vo->cam.height = p->height;
@@ -1780,7 +1808,7 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     }
     TB_HIP(ctx, hipMalloc(&vo->right, S * img));
     TB_HIP(ctx, hipMalloc(&vo->status, S * P));
-    TB_HIP(ctx, hipMalloc(&vo->matches, S * P * sizeof(tb_match)));
+    TB_HIP(ctx, hipMalloc(&vo->matches, S * (size_t)vo->Mcap * sizeof(tb_match)));
     TB_HIP(ctx, hipMalloc(&vo->mcounts, S * sizeof(int32_t)));
     TB_HIP(ctx, hipMalloc(&vo->obs, S * P * sizeof(tb_obs)));
     TB_HIP(ctx, hipMalloc(&vo->obs_counts, S * sizeof(int32_t)));
@@ -1824,8 +1852,35 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
         /* the matcher's slots: searchByBF's best rows per side, searchByViolence's (WORK, shared with CLAHE) */
         if (vo->tr.kind == TB_VO_BF) {
             if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, S * P * 8, &d))) return rc;
+        } else if (vo_is_proj(vo)) {
+            /* the projection matchers' best rows: 6 words per map point */
+            if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * (size_t)vo->Mcap * 6 * sizeof(int32_t), &d))) return rc;
         } else if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * P * 16, &d))) {
             return rc;
+        }
+    }
+    if (vo_is_proj(vo)) {
+        for (int l = 0; l < p->nlevels; l++) vo->sf[l] = sf[l];
+        TB_HIP(ctx, hipMalloc(&vo->cell_start, S * 4321 * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->cell_items, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&vo->taken, S * P));
+        TB_HIP(ctx, hipMalloc(&vo->mp_desc, S * P * 32));
+        TB_HIP(ctx, hipMalloc(&vo->kf_mp_desc, S * P * 32));
+        TB_HIP(ctx, hipMemsetAsync(vo->taken, 0, S * P, ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mp_desc, 0, S * P * 32, ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->kf_mp_desc, 0, S * P * 32, ctx->stream));
+        if (vo->tr.kind == TB_VO_PROJECTION) {
+            TB_HIP(ctx, hipMalloc(&vo->kf_rec, S * P * sizeof(tb_mappoint)));
+        } else {
+            const size_t C = (size_t)vo->map_cap;
+            for (int k = 0; k < 2; k++) {
+                TB_HIP(ctx, hipMalloc(&vo->map_rec[k], S * C * sizeof(tb_mappoint)));
+                TB_HIP(ctx, hipMalloc(&vo->map_desc[k], S * C * 32));
+                TB_HIP(ctx, hipMalloc(&vo->map_n[k], S * sizeof(int32_t)));
+                TB_HIP(ctx, hipMalloc(&vo->map_blocks[k], S * vo->mapK * sizeof(int32_t)));
+                TB_HIP(ctx, hipMemsetAsync(vo->map_n[k], 0, S * sizeof(int32_t), ctx->stream));
+                TB_HIP(ctx, hipMemsetAsync(vo->map_blocks[k], 0, S * vo->mapK * sizeof(int32_t), ctx->stream));
+            }
         }
     }
     *out = vu.release();
@@ -1842,8 +1897,15 @@ int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr,
     if (!ctx || !p || !out) return TB_EINVAL;
     *out = nullptr;
     if (tr && tr->kind != TB_VO_OPFLOW) {
-        if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
-        if (tr->kind == TB_VO_BF) {
+        if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE && tr->kind != TB_VO_PROJECTION && tr->kind != TB_VO_PROJECTION_MAP)
+            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
+        if (tr->kind == TB_VO_PROJECTION || tr->kind == TB_VO_PROJECTION_MAP) {
+            const bool map = tr->kind == TB_VO_PROJECTION_MAP;
+            if (tr->th_high < 0 || tr->histo_len < 1 || tr->histo_len > 1024 || !std::isfinite(tr->nratio) ||
+                (map && (tr->map_keyframes < 1 || !std::isfinite(tr->radio))))
+                return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByProjection arguments (nratio %g, th_high %d, histo_len %d, radio %g, map_keyframes %d)",
+                               (double)tr->nratio, tr->th_high, tr->histo_len, (double)tr->radio, tr->map_keyframes);
+        } else if (tr->kind == TB_VO_BF) {
             if (!std::isfinite(tr->bf_ratio) || !std::isfinite(tr->bf_min_th))
                 return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByBF ratio / minTh must be finite");
             /* matcher.cpp:177: only MinLevel == 0 && MaxLevel == F1->GetMaxLevel() (= nLevels) takes the whole-set branch */
@@ -1869,6 +1931,11 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     if (vo->tr.kind != TB_VO_OPFLOW) {   /* no keyframe yet */
         TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
         vo->kf_frame = -1;
+    }
+    if (vo->mapK) {   /* an empty map */
+        TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->map_blocks[vo->map_cur], 0, (size_t)vo->nseq * vo->mapK * sizeof(int32_t), ctx->stream));
+        vo->map_nblk = 0;
     }
     vo->next = 0;
     return TB_OK;
@@ -1936,6 +2003,92 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
     return TB_OK;
 }
 
+/* A projection tracker's frame t after the left images are in img[b] (see include/tb_capi.h, tb_vo_tracker). */
+static int vo_step_proj(tb_vo* vo, int t, bool keyframe, const uint8_t* right, int stride, size_t pitch) {
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    const tb_vo_tracker& tr = vo->tr;
+    const bool map = tr.kind == TB_VO_PROJECTION_MAP;
+    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
+    const size_t ip = (size_t)W * H, SP = (size_t)S * P;
+    const int a = vo->cur, b = a ^ 1;
+    int rc;
+    /* test_projection.cpp:495-504: ORB operator(), SetKeys, AssignFeaturesToGrid on every frame */
+    if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
+    if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
+    if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
+    if ((rc = tb_extractor_copy_results_dev(vo->ex, S, vo->orb, vo->orb_desc, vo->orb_cnt, P))) return rc;
+    if ((rc = tb_frame_grid_batch_dev(ctx, S, vo->orb, vo->orb_cnt, P, W, H, vo->cell_start, vo->cell_items))) return rc;
+    if (t == 0) {
+        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+    } else if (map) {
+        /* :516-517 searchByProjection(map_ptr, cur, radio) at the last frame's pose (:510) */
+        if ((rc = tb_search_by_projection_map_batch_dev(ctx, S, vo->Tcw[a], &vo->cam, W, H, vo->orb, vo->orb_desc, vo->taken, vo->orb_cnt, P,
+                                                        vo->cell_start, vo->cell_items, vo->map_rec[vo->map_cur], vo->map_desc[vo->map_cur],
+                                                        vo->map_n[vo->map_cur], vo->map_cap, vo->map_cap, vo->sf, p.nlevels, tr.nratio,
+                                                        tr.radio, tr.th_high, vo->matches, vo->Mcap, vo->mcounts, vo->mflags)))
+            return rc;
+    } else {
+        /* :512-513 searchByProjection(cur, key_frame) at the last frame's pose (:510) */
+        if ((rc = tb_search_by_projection_batch_dev(ctx, S, vo->Tcw[a], &vo->cam, W, H, vo->orb, vo->orb_desc, vo->taken, vo->orb_cnt, P,
+                                                    vo->cell_start, vo->cell_items, vo->kf_orb, vo->kf_rec, vo->kf_mp_desc, vo->kf_cnt, P,
+                                                    vo->sf, p.nlevels, tr.nratio, tr.th_high, tr.histo_len, tr.check_orientation,
+                                                    vo->matches, vo->Mcap, vo->mcounts, vo->mflags)))
+            return rc;
+    }
+    /* :520-530: the keys, the map points (and their descriptors) the matches carry over, the pose rows (no match at frame 0) */
+    if (map) {
+        rc = tbk_vo_proj_carry(ctx, S, 1, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->Mcap, nullptr, nullptr, vo->map_rec[vo->map_cur],
+                               vo->map_desc[vo->map_cur], vo->map_n[vo->map_cur], vo->map_cap, P, vo->inv_sigma2, p.nlevels, vo->win,
+                               vo->keys[b], vo->kcnt[b], vo->mp[b], vo->valid[b], vo->mp_desc, vo->obs, vo->obs_counts, vo->outlier);
+    } else {
+        rc = tbk_vo_proj_carry(ctx, S, 0, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->Mcap, vo->kf_mp, vo->kf_valid, nullptr,
+                               vo->kf_mp_desc, vo->kf_cnt, P, P, vo->inv_sigma2, p.nlevels, vo->win, vo->keys[b], vo->kcnt[b], vo->mp[b],
+                               vo->valid[b], vo->mp_desc, vo->obs, vo->obs_counts, vo->outlier);
+    }
+    if (rc) return rc;
+    if (t > 0 &&
+        (rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
+        return rc;
+    if (keyframe) {
+        /* :577-634: the second ORB call returns the same keys (see vo_step_desc); stereo depths, the new map points */
+        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
+        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
+                                                        vo->st_pts, vo->st_status, vo->depth)))
+            return rc;
+        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
+        int slot = 0;
+        if (map) {
+            if (vo->map_nblk == vo->mapK) {   /* the oldest keyframe's points leave; the survivors move into the other set */
+                const int c = vo->map_cur, d = c ^ 1;
+                if ((rc = tbk_vo_map_evict(ctx, S, vo->map_rec[c], vo->map_desc[c], vo->map_n[c], vo->map_blocks[c], vo->mapK, vo->map_cap,
+                                           vo->map_rec[d], vo->map_desc[d], vo->map_n[d], vo->map_blocks[d])))
+                    return rc;
+                vo->map_cur = d;
+                vo->map_nblk = vo->mapK - 1;
+            }
+            slot = vo->map_nblk++;
+        }
+        const int c = vo->map_cur;
+        if ((rc = tbk_vo_kf_append(ctx, S, vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->orb_desc, vo->Tcw[b], P, vo->mp_desc,
+                                   map ? nullptr : vo->kf_rec, map ? vo->map_rec[c] : nullptr, map ? vo->map_desc[c] : nullptr,
+                                   map ? vo->map_n[c] : nullptr, map ? vo->map_blocks[c] : nullptr, map ? vo->mapK : 0, slot, vo->map_cap)))
+            return rc;
+        /* key_frame = cur_frame_ptr (:641) */
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_orb, vo->orb, SP * sizeof(tb_keypoint), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_desc, vo->orb_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_cnt, vo->orb_cnt, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp, vo->mp[b], SP * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_valid, vo->valid[b], SP, hipMemcpyDeviceToDevice, ctx->stream));
+        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp_desc, vo->mp_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
+        vo->kf_frame = t;
+    }
+    return TB_OK;
+}
+
 int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
     TB_ENTER((vo ? vo->ctx : nullptr));
     if (!vo) return TB_EINVAL;
@@ -1952,7 +2105,8 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
     int rc;
     if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
     if (vo->tr.kind != TB_VO_OPFLOW) {
-        if ((rc = vo_step_desc(vo, t, keyframe, right, stride, pitch))) return rc;
+        if ((rc = vo_is_proj(vo) ? vo_step_proj(vo, t, keyframe, right, stride, pitch) : vo_step_desc(vo, t, keyframe, right, stride, pitch)))
+            return rc;
     } else if (t == 0) {
         TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->kcnt[b], 0, (size_t)S * sizeof(int32_t), ctx->stream));
@@ -2029,6 +2183,31 @@ int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** 
     if (kf_mp_valid) *kf_mp_valid = vo->kf_valid;
     if (kf_counts) *kf_counts = vo->kf_cnt;
     if (kf_frame) *kf_frame = vo->kf_frame;
+    return TB_OK;
+}
+
+int tb_vo_mp_desc_dev(tb_vo* vo, const uint8_t** mp_desc, const uint8_t** kf_mp_desc) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo_is_proj(vo)) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_mp_desc_dev: the loop's tracker carries no map-point descriptors");
+    if (mp_desc) *mp_desc = vo->mp_desc;
+    if (kf_mp_desc) *kf_mp_desc = vo->kf_mp_desc;
+    return TB_OK;
+}
+
+int tb_vo_map_state_dev(tb_vo* vo, const tb_mappoint** points, const uint8_t** desc, const int32_t** counts, const int32_t** block_counts,
+                        int* capacity, int* map_keyframes, int* blocks) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->mapK) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_map_state_dev: the loop has no map");
+    const int c = vo->map_cur;
+    if (points) *points = vo->map_rec[c];
+    if (desc) *desc = vo->map_desc[c];
+    if (counts) *counts = vo->map_n[c];
+    if (block_counts) *block_counts = vo->map_blocks[c];
+    if (capacity) *capacity = vo->map_cap;
+    if (map_keyframes) *map_keyframes = vo->mapK;
+    if (blocks) *blocks = vo->map_nblk;
     return TB_OK;
 }
 

@@ -254,4 +254,17 @@ int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_
 int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
                     const double K[4], int pitch, float* d_mp, uint8_t* d_valid);
 
+int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
+                      const int32_t* d_match_counts, int match_pitch, const float* d_src_mp, const uint8_t* d_src_valid,
+                      const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_counts, int src_pitch, int pitch,
+                      const float* inv_sigma2, int nlevels, int32_t* d_win, float* d_keys, int32_t* d_key_counts, float* d_mp,
+                      uint8_t* d_valid, uint8_t* d_mp_desc, tb_obs* d_obs, int32_t* d_obs_counts, uint8_t* d_outlier);
+int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const float* d_depth, const float* d_mp, const uint8_t* d_valid,
+                     const uint8_t* d_orb_desc, const float* d_Tcw, int pitch, uint8_t* d_mp_desc, tb_mappoint* d_rec,
+                     tb_mappoint* d_map_rec, uint8_t* d_map_desc, int32_t* d_map_n, int32_t* d_map_blocks, int nblk, int slot,
+                     int map_pitch);
+int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_n,
+                     const int32_t* d_src_blocks, int nblk, int map_pitch, tb_mappoint* d_dst_rec, uint8_t* d_dst_desc, int32_t* d_dst_n,
+                     int32_t* d_dst_blocks);
+
 #endif

@@ -9,6 +9,10 @@
 `tracker="bf"` or `"violence"` swaps the tracking line for the reference's descriptor trackers (test_vo.cpp:712-713): ORB on
 every frame, searchByBF / searchByViolence against the last keyframe, the keyframe's map points carried through the matches.
 
+`tracker="projection"` or `"projection_map"` runs the reference's projection loop (test/test_projection.cpp:512-517):
+searchByProjection of the keyframe's map points, or of a device-resident map the keyframes add their points to, into the
+current frame's lookup grid. The map holds the points of the last `map_keyframes` keyframes.
+
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
 """
@@ -33,17 +37,28 @@ class _DevArray:
 TRACKER_DEFAULTS = {
     "bf": dict(ratio=10.0, min_th=30.0, min_level=0, max_level=None),
     "violence": dict(min_level=0, max_level=5, radius=50.0, th_low=50, nratio=6.0, histo_len=30, check_orientation=True),
+    # test_projection.cpp:512-513 setProjectionParam(30, 50, 30, true, 30); searchByProjection(cur, key_frame)
+    "projection": dict(nratio=30.0, th_high=50, histo_len=30, check_orientation=True),
+    # :516-517 setProjectionParam(30, 50, 30, true, 20); searchByProjection(map, cur, 0.6); map_keyframes: include/tb_capi.h
+    "projection_map": dict(nratio=20.0, radio=0.6, th_high=50, histo_len=30, check_orientation=True, map_keyframes=4),
 }
 
 
 def _tracker(kind, nlevels, params):
     if kind not in TRACKER_DEFAULTS:
-        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence'" % (kind,))
+        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence', 'projection', 'projection_map'" % (kind,))
     unknown = set(params) - set(TRACKER_DEFAULTS[kind])
     if unknown:
         raise TypeError("tracker %r takes no parameter %s" % (kind, ", ".join(sorted(unknown))))
     q = dict(TRACKER_DEFAULTS[kind], **params)
     t = capi.VOTracker()
+    if kind in ("projection", "projection_map"):
+        t.kind = capi.TB_VO_PROJECTION if kind == "projection" else capi.TB_VO_PROJECTION_MAP
+        t.nratio, t.th_high, t.histo_len = float(q["nratio"]), int(q["th_high"]), int(q["histo_len"])
+        t.check_orientation = int(bool(q["check_orientation"]))
+        if kind == "projection_map":
+            t.radio, t.map_keyframes = float(q["radio"]), int(q["map_keyframes"])
+        return t
     t.min_level = int(q["min_level"])
     if kind == "bf":
         t.kind = capi.TB_VO_BF
@@ -176,9 +191,16 @@ class StereoVO:
         return (self._tget("orb", (self.S, P, 7), "<i4", torch.int32), self._tget("orb_desc", (self.S, P, 32), "|u1", torch.uint8),
                 self._tget("orb_counts", (self.S,), "<i4", torch.int32))
 
+    @property
+    def match_capacity(self):
+        """Rows of a sequence's match list: key_pitch, or the map's capacity for tracker "projection_map" (one match per map
+        point at most)."""
+        return self.vo.map_state_dev()["capacity"] if self.tracker == "projection_map" else self.key_pitch
+
     def matches(self):
-        """The step's matches: (rows [S, P, 4] int32 = queryIdx, trainIdx, imgIdx, distance bits; counts [S]; matcher flags [S])"""
-        P = self.key_pitch
+        """The step's matches: (rows [S, M, 4] int32 = queryIdx, trainIdx, imgIdx, distance bits, M = match_capacity; counts [S];
+        matcher flags [S])"""
+        P = self.match_capacity
         return (self._tget("matches", (self.S, P, 4), "<i4", torch.int32), self._tget("match_counts", (self.S,), "<i4", torch.int32),
                 self._tget("flags", (self.S,), "<i4", torch.int32))
 
@@ -192,6 +214,33 @@ class StereoVO:
                     map_points=self._tget("kf_map_points", (self.S, P, 3), "<f4", torch.float32),
                     mp_valid=self._tget("kf_mp_valid", (self.S, P), "|u1", torch.uint8),
                     frame=self.vo.tracker_state_dev()["kf_frame"])
+
+    # ---- projection trackers (tracker "projection" / "projection_map")
+    def _pget(self, ptr, shape, typestr, dtype):
+        with torch.cuda.stream(self.stream):
+            out = torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.dev).view(dtype).clone()
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        return out
+
+    def mp_desc(self):
+        """The descriptors that travel with the map points: (current frame's [S, P, 32] uint8, keyframe's [S, P, 32]); entry j
+        means something where its map point is valid."""
+        d = self.vo.mp_desc_dev()
+        P = self.key_pitch
+        return (self._pget(d["mp_desc"], (self.S, P, 32), "|u1", torch.uint8),
+                self._pget(d["kf_mp_desc"], (self.S, P, 32), "|u1", torch.uint8))
+
+    def map(self):
+        """The map of tracker "projection_map": dict(points [S, C, 9] int32 -- tb_mappoint records (pos[3], normal[3], min_dist,
+        max_dist as float32, bad as int32), viewed as int32 -- desc [S, C, 32] uint8, counts [S] live points, block_counts
+        [S, map_keyframes] points per held keyframe (oldest first), capacity C, map_keyframes, blocks = keyframes held)"""
+        m = self.vo.map_state_dev()
+        Cp, K = m["capacity"], m["map_keyframes"]
+        return dict(points=self._pget(m["points"], (self.S, Cp, 9), "<i4", torch.int32),
+                    desc=self._pget(m["desc"], (self.S, Cp, 32), "|u1", torch.uint8),
+                    counts=self._pget(m["counts"], (self.S,), "<i4", torch.int32),
+                    block_counts=self._pget(m["block_counts"], (self.S, K), "<i4", torch.int32),
+                    capacity=Cp, map_keyframes=K, blocks=m["blocks"])
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
