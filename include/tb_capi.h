@@ -262,6 +262,47 @@ int tb_search_by_bow_batch_dev(tb_ctx* ctx, int npairs, const tb_keypoint* k1, c
                                int th_low, float nratio, int histo_len, int check_orientation, tb_match* out, int cap,
                                int32_t* out_counts, int32_t* flags);
 
+/* Vocabulary training -- TemplatedVocabulary<FORB::TDescriptor, FORB>::create(training_features, k, L, weighting, scoring)
+ * (third_part/DBoW2/DBoW2/TemplatedVocabulary.h:558-616; HKmeansStep :642-819, initiateClustersKMpp :833-913, createWords
+ * :918-938, setNodeWeights :943-996; FORB::meanValue / distance, FORB.cpp:28-101) on the device, bit for bit:
+ *  - root = node 0; a node with n <= k descriptors gets one child per descriptor; a larger one runs Hamming k-means: kmeans++
+ *    seeding with D(x) weights (a point at distance 0 is never updated, the next centre is the first index whose running sum
+ *    is >= cut_d, seeding stops when the distances sum to 0, so a node of identical descriptors gets one child), then
+ *    bit-majority centres (bit set iff count >= n/2 + n%2; a group of one keeps its descriptor) and first-minimum association
+ *    until the association repeats;
+ *  - children are made for every cluster, then each child with more than one descriptor is expanded while level < L; node ids
+ *    follow create's recursion: a node's children get consecutive ids, then the first child's subtree, then the second's;
+ *  - words = childless nodes other than the root in id order; weight 1 for TF / BINARY, log(ndocs / Ni) for TF_IDF / IDF with
+ *    Ni = documents with a descriptor whose transform() walk ends in the word (C library log of the double quotient, on the
+ *    host); a word no training descriptor walks to keeps weight 0.
+ * Deviations from the reference:
+ *  1. random numbers: the reference seeds rand() from the clock (DUtils/Random.cpp:18-22). Here every k-means node draws from the
+ *     counter-based splitmix64 stream (synth.Stream) of seed + (level << 40) + j: level = the level of the children being made
+ *     (1 for the root's), j = the rank of the parent among all nodes of the previous level in (parent rank, child index) order.
+ *     Draw 0 gives the first centre int(u n), u = (u64 >> 11) 2^-53; every further centre takes the next draw, cut_d = u *
+ *     dist_sum (one double multiply), redrawn while cut_d == 0.0;
+ *  2. empty cluster: meanValue of an empty group releases the Mat and the reference then reads an empty Mat; here the cluster
+ *     keeps its last centre. stats.empty_clusters counts the children that end with no descriptor;
+ *  3. iteration cap: the reference loops without bound; here a node stops after its max_iters-th association with the centres
+ *     used for it. stats.capped_nodes counts the nodes stopped that way (the association differed from the one before, or
+ *     max_iters is 1). stats.iters_per_level[l - 1]: associations run for the children of level l (0: no k-means node).
+ * Limits: 2 <= k <= 32, 1 <= L <= TB_VOC_MAX_L, at most 2^26 descriptors in all (TB_EUNSUPPORTED beyond); max_iters >= 1,
+ * ndocs >= 0, 0 <= counts[d] <= desc_pitch (TB_EINVAL). No descriptors at all give the root alone (:645).
+ * tb_vocab_train_dev: document d has counts[d] descriptors at desc + d * desc_pitch * 32 (device pointers; what lies beyond
+ * counts[d] is not read). tb_vocab_train: host pointers, the documents concatenated; staged onto the _dev form. Both
+ * synchronise the context's stream. The handle is an ordinary tb_vocab (tb_bow_transform*, tb_vocab_destroy).
+ * tb_vocab_info / tb_vocab_export read any tb_vocab back (host arrays of tb_vocabulary's shapes: child_start [nnodes + 1],
+ * child_items [nnodes - 1], desc [nnodes][32], word_id / weight [nnodes]; each nullable). */
+#define TB_VOC_MAX_L 8
+typedef struct tb_vocab_train_params { int k, L, weighting, scoring; uint64_t seed; int max_iters; } tb_vocab_train_params;
+typedef struct tb_vocab_train_stats { int nnodes, nwords, capped_nodes, empty_clusters; int iters_per_level[TB_VOC_MAX_L]; } tb_vocab_train_stats;
+int tb_vocab_train_dev(tb_ctx* ctx, const tb_vocab_train_params* params, int ndocs, const uint8_t* desc, const int32_t* counts,
+                       int desc_pitch, tb_vocab** out, tb_vocab_train_stats* stats);
+int tb_vocab_train(tb_ctx* ctx, const tb_vocab_train_params* params, int ndocs, const uint8_t* desc, const int32_t* counts,
+                   tb_vocab** out, tb_vocab_train_stats* stats);
+int tb_vocab_info(const tb_vocab* voc, int* nnodes, int* nwords, int* k, int* L, int* weighting, int* scoring);
+int tb_vocab_export(const tb_vocab* voc, int32_t* child_start, int32_t* child_items, uint8_t* desc, int32_t* word_id, double* weight);
+
 /* Stereo tracks -> PoseOptimization's inputs, batched and device-resident (round 3). For frame f and each of its
  * match_counts[f] left <-> right matches (queryIdx = left key, trainIdx = right key; the output of
  * tb_search_by_bf_batch_dev): Depth = bf / |x_right - x_left| (LocalBA::AddMapPointsByStereo, LocalBA.cpp:60-64), the map

@@ -43,6 +43,9 @@ namespace DBoW2 {
 typedef unsigned int WordId;
 typedef double WordValue;
 class BowVector : public std::map<WordId, WordValue> {};
+/* the values TemplatedVocabulary::create takes (BowVector.h); the integers are what the ORBvoc text file stores */
+enum WeightingType { TF_IDF, TF, IDF, BINARY };
+enum ScoringType { L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT };
 }
 struct tb_vocab;
 namespace TRACKING_BENCH {
@@ -53,6 +56,15 @@ public:
     FlatVocabulary(const FlatVocabulary&) = delete;
     FlatVocabulary& operator=(const FlatVocabulary&) = delete;
     bool loadFromTextFile(const std::string& filename);     /* TemplatedVocabulary.h:1338-1420 */
+    /* TemplatedVocabulary::create (TemplatedVocabulary.h:114, :558-616) trained on the device (tb_vocab_train: the reference's
+     * algorithm with counter-based random numbers of seed 0, at most 200 k-means iterations per node, an empty cluster keeps
+     * its centre). One 1 x 32 CV_8U descriptor per cv::Mat, one inner vector per training image. The trained tree stays on the
+     * device for Frame::SetBow. Throws std::runtime_error outside 2 <= k <= 32, 1 <= L <= 8. */
+    void create(const std::vector<std::vector<cv::Mat>>& training_features, int k, int L, DBoW2::WeightingType weighting = DBoW2::TF_IDF,
+                DBoW2::ScoringType scoring = DBoW2::L1_NORM);
+    /* the line format loadFromTextFile reads (TemplatedVocabulary.h:1429-1449); weights with 17 significant digits, so the
+     * file gives back the same doubles (the reference prints 6) */
+    void saveToTextFile(const std::string& filename) const;
     bool empty() const { return word_id.size() <= 1; }
     unsigned int size() const { return nwords; }            /* number of words */
     int getBranchingFactor() const { return k; }

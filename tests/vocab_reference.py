@@ -1,0 +1,177 @@
+"""numpy restatement of DBoW2's vocabulary training (TemplatedVocabulary<FORB::TDescriptor, FORB>::create), the yardstick of
+tests/test_gpu_vocab_train.py. Written from the description of the algorithm, in create's own recursion order:
+
+* root = node 0; a node with n <= k descriptors gets one child per descriptor; a node with more runs Hamming k-means:
+  kmeans++ seeding with D(x) (not D^2), a point whose distance is 0 is never updated, the next centre is the first index whose
+  running sum reaches cut_d, seeding stops when the distances sum to 0; every iteration replaces the centres by the bit
+  majority (bit set iff count >= n/2 + n%2, a group of one keeps its descriptor) and assigns every descriptor to the FIRST
+  centre of smallest distance; the loop ends when the assignment repeats.
+* children are created for all clusters first, then each child with more than one descriptor is expanded while level < L.
+* words = childless nodes other than the root in id order; IDF / TF_IDF weights log(NDocs / Ni) with Ni counted from the tree
+  walk of every training descriptor (first-min rule), a word nobody walks to keeps weight 0.
+
+The three deviations from the reference, shared with the device implementation (include/tb_capi.h, tb_vocab_train):
+1. random numbers: every k-means node draws from synth.Stream(seed + (level << 40) + j), level = the level of the children
+   being made, j = the rank of the parent among all nodes of the previous level; draw 0 picks the first centre int(u n), every
+   further centre takes the next draw, cut_d = u * dist_sum, redrawn while cut_d == 0.0;
+2. an empty cluster keeps its last centre;
+3. max_iters: after the max_iters-th association a node stops with the centres used for that association; it counts as capped
+   unless that association repeated the one before.
+stats: nnodes, nwords, capped_nodes, empty_clusters (children that end with no descriptor), iters_per_level[level - 1] = the
+largest number of associations any k-means node of that level ran (0: no k-means node)."""
+import math
+
+import numpy as np
+
+from trackingbench_slam_amd import synth
+
+TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
+MAX_L = 8
+_POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.int64)
+
+
+def distance(D, c):
+    """Hamming distances of the rows of D [n, 32] to one descriptor c [32]"""
+    return _POP8[D ^ c[None, :]].sum(1)
+
+
+def distances(D, C):
+    """[n, m] Hamming distances of the rows of D to the rows of C"""
+    return _POP8[D[:, None, :] ^ C[None, :, :]].sum(2)
+
+
+def mean_value(D):
+    """FORB::meanValue of a non-empty group"""
+    n = len(D)
+    if n == 1:
+        return D[0].copy()
+    cnt = np.unpackbits(D, axis=1).sum(0)
+    return np.packbits(cnt >= n // 2 + n % 2)
+
+
+def associate(D, C):
+    """index of the first centre of smallest distance, per descriptor"""
+    return np.argmin(distances(D, C), axis=1)
+
+
+def seed_centres(D, k, st):
+    """kmeans++ as the reference writes it; returns the indices of the chosen descriptors"""
+    n = len(D)
+    first = min(int(st.uniform(1)[0] * float(n)), n - 1)
+    picks = [first]
+    mind = distance(D, D[first])
+    while len(picks) < k:
+        d = distance(D, D[picks[-1]])
+        upd = (mind > 0) & (d < mind)
+        mind[upd] = d[upd]
+        s = int(mind.sum())
+        if s == 0:
+            break
+        while True:
+            cut = st.uniform(1)[0] * float(s)
+            if cut != 0.0:
+                break
+        hit = np.flatnonzero(np.cumsum(mind).astype(np.float64) >= cut)
+        picks.append(int(hit[0]) if len(hit) else n - 1)
+    return picks
+
+
+def kmeans(D, k, st, max_iters):
+    """-> centres [m, 32], assignment [n], associations run, capped"""
+    C = D[seed_centres(D, k, st)].copy()
+    last, it = None, 0
+    while True:
+        it += 1
+        if it > 1:
+            for c in range(len(C)):
+                g = D[last == c]
+                if len(g):
+                    C[c] = mean_value(g)
+        a = associate(D, C)
+        if it > 1 and np.array_equal(a, last):
+            return C, a, it, False
+        if it == max_iters:
+            return C, a, it, True
+        last = a
+
+
+def walk(child_lists, desc, D):
+    """TemplatedVocabulary::transform's walk for every row of D: the node id each ends in"""
+    cur = np.zeros(len(D), np.int64)
+    live = np.arange(len(D))
+    while len(live):
+        order = live[np.argsort(cur[live], kind="stable")]
+        nodes, starts = np.unique(cur[order], return_index=True)
+        ends = list(starts[1:]) + [len(order)]
+        nxt = []
+        for nd, s, e in zip(nodes, starts, ends):
+            ch = child_lists[nd]
+            if not ch:
+                continue
+            idx = order[s:e]
+            cur[idx] = np.asarray(ch)[associate(D[idx], desc[ch])]
+            nxt.append(idx)
+        live = np.concatenate(nxt) if nxt else np.zeros(0, np.int64)
+    return cur
+
+
+def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200):
+    """docs: sequence of uint8 [n_i, 32] arrays -> (synth.Vocabulary, stats dict)"""
+    assert k >= 2 and 1 <= L <= MAX_L and max_iters >= 1
+    docs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
+    allD = np.concatenate(docs) if docs else np.zeros((0, 32), np.uint8)
+    desc = [np.zeros(32, np.uint8)]
+    children = [[]]
+    rank = [0] * (L + 2)          # nodes created so far per level
+    rank_of = [0]
+    stats = dict(nnodes=0, nwords=0, capped_nodes=0, empty_clusters=0, iters_per_level=[0] * MAX_L)
+
+    def step(parent, D, level):
+        n = len(D)
+        if n == 0:
+            return
+        if n <= k:
+            C, a = D.copy(), np.arange(n)
+        else:
+            st = synth.Stream(seed + (level << 40) + rank_of[parent])
+            C, a, it, capped = kmeans(D, k, st, max_iters)
+            stats["capped_nodes"] += int(capped)
+            stats["iters_per_level"][level - 1] = max(stats["iters_per_level"][level - 1], it)
+        ids = []
+        for c in range(len(C)):
+            ids.append(len(desc))
+            desc.append(C[c])
+            children.append([])
+            rank_of.append(rank[level])
+            rank[level] += 1
+        children[parent] = ids
+        groups = [D[a == c] for c in range(len(C))]
+        stats["empty_clusters"] += sum(1 for g in groups if len(g) == 0)
+        if level < L:
+            for c, g in enumerate(groups):
+                if len(g) > 1:
+                    step(ids[c], g, level + 1)
+
+    step(0, allD, 1)
+    nn = len(desc)
+    desc = np.stack(desc)
+    cs, ci = [0], []
+    for n in range(nn):
+        ci.extend(children[n])
+        cs.append(len(ci))
+    word_id = np.zeros(nn, np.int32)
+    weight = np.zeros(nn, np.float64)
+    words = [n for n in range(1, nn) if not children[n]]
+    word_id[words] = np.arange(len(words))
+    if weighting in (TF, BINARY):
+        weight[words] = 1.0
+    else:
+        Ni = np.zeros(nn, np.int64)
+        for d in docs:
+            if len(d):
+                Ni[np.unique(walk(children, desc, d))] += 1
+        for n in words:
+            if Ni[n] > 0:
+                weight[n] = math.log(float(len(docs)) / float(Ni[n]))
+    stats["nnodes"], stats["nwords"] = nn, len(words)
+    return synth.Vocabulary(k, L, cs, ci, desc, word_id, weight, weighting, scoring), stats

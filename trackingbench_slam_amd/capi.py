@@ -44,7 +44,25 @@ EXPORTS = [
     "tb_find_fundamental_ransac", "tb_reject_with_f", "tb_reject_with_f_batch_dev", "tb_add_map_points_by_stereo", "tb_add_map_points_by_stereo_batch_dev",
     "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
     "tb_vo_create_ex", "tb_vo_tracker_state_dev", "tb_vo_mp_desc_dev", "tb_vo_map_state_dev",
+    "tb_vocab_train", "tb_vocab_train_dev", "tb_vocab_info", "tb_vocab_export",
 ]
+
+TB_VOC_MAX_L = 8
+
+
+class VocabTrainParams(C.Structure):
+    """tb_vocab_train_params of include/tb_capi.h"""
+    _fields_ = [("k", C.c_int), ("L", C.c_int), ("weighting", C.c_int), ("scoring", C.c_int), ("seed", C.c_uint64), ("max_iters", C.c_int)]
+
+
+class VocabTrainStats(C.Structure):
+    """tb_vocab_train_stats of include/tb_capi.h"""
+    _fields_ = [("nnodes", C.c_int), ("nwords", C.c_int), ("capped_nodes", C.c_int), ("empty_clusters", C.c_int),
+                ("iters_per_level", C.c_int * TB_VOC_MAX_L)]
+
+    def as_dict(self):
+        return dict(nnodes=self.nnodes, nwords=self.nwords, capped_nodes=self.capped_nodes, empty_clusters=self.empty_clusters,
+                    iters_per_level=list(self.iters_per_level))
 
 
 class TBError(RuntimeError):
@@ -541,6 +559,42 @@ class Context:
 
     def vocab_destroy(self, h):
         lib().tb_vocab_destroy(h)
+
+    def vocab_export(self, h):
+        """tb_vocab_info + tb_vocab_export: the handle's tree as a synth.Vocabulary (host arrays)."""
+        from . import synth
+        v = [C.c_int() for _ in range(6)]
+        self.check(lib().tb_vocab_info(h, *[C.byref(x) for x in v]))
+        nn, _, k, L, weighting, scoring = [x.value for x in v]
+        cs = np.zeros(nn + 1, np.int32); ci = np.zeros(max(nn - 1, 1), np.int32); desc = np.zeros((nn, 32), np.uint8)
+        wid = np.zeros(nn, np.int32); wt = np.zeros(nn, np.float64)
+        self.check(lib().tb_vocab_export(h, _p(cs), _p(ci), _p(desc), _p(wid), _p(wt)))
+        return synth.Vocabulary(k, L, cs, ci[:cs[nn]], desc, wid, wt, weighting, scoring)
+
+    def vocab_train(self, docs, k=10, L=5, weighting=0, scoring=0, seed=0, max_iters=200):
+        """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the device (tb_vocab_train). docs: one
+        uint8 [n_i, 32] array per training document. Returns (handle, synth.Vocabulary, stats dict); the handle feeds
+        bow_transform / tb_search_by_bow_batch_dev and is freed by vocab_destroy; Vocabulary.to_text writes an ORBvoc-style file."""
+        docs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
+        counts = np.array([len(d) for d in docs] + [0], np.int32)
+        flat = np.concatenate(docs) if docs else np.zeros((0, 32), np.uint8)
+        P = VocabTrainParams(int(k), int(L), int(weighting), int(scoring), int(seed) & (2 ** 64 - 1), int(max_iters))
+        st = VocabTrainStats()
+        h = C.c_void_p()
+        self.check(lib().tb_vocab_train(self._h, C.byref(P), len(docs), _p(flat) if len(flat) else None, _p(counts), C.byref(h), C.byref(st)))
+        return h, self.vocab_export(h), st.as_dict()
+
+    def vocab_train_dev(self, desc, counts, k=10, L=5, weighting=0, scoring=0, seed=0, max_iters=200):
+        """tb_vocab_train_dev on torch tensors of this context's device: desc uint8 [ndocs, pitch, 32] (extractor output as it
+        is), counts int32 [ndocs]. Returns (handle, synth.Vocabulary, stats dict)."""
+        ndocs, pitch = desc.shape[0], desc.shape[1]
+        assert desc.is_contiguous() and desc.shape[2] == 32 and counts.is_contiguous() and counts.numel() == ndocs
+        P = VocabTrainParams(int(k), int(L), int(weighting), int(scoring), int(seed) & (2 ** 64 - 1), int(max_iters))
+        st = VocabTrainStats()
+        h = C.c_void_p()
+        self.check(lib().tb_vocab_train_dev(self._h, C.byref(P), ndocs, C.c_void_p(desc.data_ptr()), C.c_void_p(counts.data_ptr()), pitch,
+                                            C.byref(h), C.byref(st)))
+        return h, self.vocab_export(h), st.as_dict()
 
     def bow_transform(self, vocab_handle, desc, levelsup=4):
         """Frame::SetBow's voc->transform per feature (reference Frame.cpp:267-270): (word_ids, weights, node_ids)."""

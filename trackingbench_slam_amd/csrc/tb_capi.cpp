@@ -999,6 +999,123 @@ int tb_vocab_create(tb_ctx* ctx, const tb_vocabulary* h, tb_vocab** out) {
     return TB_OK;
 }
 
+/* ---- vocabulary training (see include/tb_capi.h; k_vocab.hip) */
+static int vocab_train_args(tb_ctx* ctx, const tb_vocab_train_params* P, int ndocs, const uint8_t* desc, const int32_t* counts,
+                            tb_vocab** out, tb_vocab_train_stats* stats) {
+    if (!ctx || !P || !out || !stats || ndocs < 0 || (ndocs && !counts)) return TB_EINVAL;
+    *out = nullptr;
+    if (P->max_iters < 1 || P->k < 0 || P->L < 0 || P->weighting < 0 || P->weighting > 3 || P->scoring < 0 || P->scoring > 5)
+        return tb_fail(ctx, TB_EINVAL, "vocabulary training: max_iters %d, k %d, L %d, weighting %d, scoring %d", P->max_iters, P->k, P->L,
+                       P->weighting, P->scoring);
+    if (P->k < 2 || P->k > 32 || P->L < 1 || P->L > TB_VOC_MAX_L)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "vocabulary training: k %d outside 2..32 or L %d outside 1..%d", P->k, P->L, TB_VOC_MAX_L);
+    return TB_OK;
+}
+
+static int vocab_train_run(tb_ctx* ctx, const tb_vocab_train_params* P, int ndocs, const uint8_t* d_desc, const int32_t* h_counts,
+                           int desc_pitch, tb_vocab** out, tb_vocab_train_stats* stats) {
+    long long total = 0;
+    for (int d = 0; d < ndocs; d++) {
+        if (h_counts[d] < 0 || h_counts[d] > desc_pitch) return tb_fail(ctx, TB_EINVAL, "vocabulary training: %d descriptors in document %d", h_counts[d], d);
+        total += h_counts[d];
+    }
+    if (total > (1ll << 26)) return tb_fail(ctx, TB_EUNSUPPORTED, "vocabulary training: %lld descriptors (at most 2^26)", total);
+    if (total && !d_desc) return TB_EINVAL;
+    tb_vocab* v = new (std::nothrow) tb_vocab();
+    if (!v) return TB_ENOMEM;
+    v->ctx = ctx; v->k = P->k; v->L = P->L; v->weighting = P->weighting; v->scoring = P->scoring;
+    tb_vocab_arrays a;
+    const int rc = tbk_vocab_train(ctx, P, ndocs, d_desc, h_counts, desc_pitch, &a, stats);
+    if (rc) { delete v; return rc; }
+    v->nnodes = a.nnodes; v->d_child_start = a.d_child_start; v->d_child_items = a.d_child_items; v->d_word_id = a.d_word_id;
+    v->d_desc = a.d_desc; v->d_weight = a.d_weight;
+    *out = v;
+    return TB_OK;
+}
+
+int tb_vocab_train_dev(tb_ctx* ctx, const tb_vocab_train_params* P, int ndocs, const uint8_t* desc, const int32_t* counts,
+                       int desc_pitch, tb_vocab** out, tb_vocab_train_stats* stats) {
+    TB_ENTER(ctx);
+    int rc;
+    if ((rc = vocab_train_args(ctx, P, ndocs, desc, counts, out, stats))) return rc;
+    if (desc_pitch < 0) return TB_EINVAL;
+    std::vector<int32_t> hc(ndocs);
+    if (ndocs) {
+        TB_HIP(ctx, hipMemcpyAsync(hc.data(), counts, (size_t)ndocs * 4, hipMemcpyDeviceToHost, ctx->stream));
+        TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return vocab_train_run(ctx, P, ndocs, desc, hc.data(), desc_pitch, out, stats);
+}
+
+int tb_vocab_train(tb_ctx* ctx, const tb_vocab_train_params* P, int ndocs, const uint8_t* desc, const int32_t* counts, tb_vocab** out,
+                   tb_vocab_train_stats* stats) {
+    TB_ENTER(ctx);
+    int rc;
+    if ((rc = vocab_train_args(ctx, P, ndocs, desc, counts, out, stats))) return rc;
+    int pitch = 0;
+    long long total = 0;
+    for (int d = 0; d < ndocs; d++) {
+        if (counts[d] < 0) return tb_fail(ctx, TB_EINVAL, "vocabulary training: %d descriptors in document %d", counts[d], d);
+        pitch = std::max(pitch, counts[d]);
+        total += counts[d];
+    }
+    if (total > (1ll << 26)) return tb_fail(ctx, TB_EUNSUPPORTED, "vocabulary training: %lld descriptors (at most 2^26)", total);
+    if (total && !desc) return TB_EINVAL;
+    /* the documents, one per row of the _dev form's [ndocs][pitch][32]; the padding is never read */
+    uint8_t* d_rows = nullptr;
+    if (total) {
+        TB_HIP(ctx, hipMalloc(&d_rows, (size_t)ndocs * pitch * 32));
+        size_t at = 0;
+        for (int d = 0; d < ndocs; d++) {
+            if (counts[d]) {
+                const hipError_t e = hipMemcpyAsync(d_rows + (size_t)d * pitch * 32, desc + at, (size_t)counts[d] * 32, hipMemcpyHostToDevice, ctx->stream);
+                if (e != hipSuccess) { hipFree(d_rows); return tb_fail(ctx, TB_EDEVICE, "vocabulary training upload: %s", hipGetErrorString(e)); }
+            }
+            at += (size_t)counts[d] * 32;
+        }
+    }
+    rc = vocab_train_run(ctx, P, ndocs, d_rows, counts, pitch, out, stats);
+    hipStreamSynchronize(ctx->stream);
+    hipFree(d_rows);
+    return rc;
+}
+
+int tb_vocab_info(const tb_vocab* v, int* nnodes, int* nwords, int* k, int* L, int* weighting, int* scoring) {
+    if (!v || !v->ctx) return TB_EINVAL;
+    TB_ENTER(v->ctx);
+    if (nnodes) *nnodes = v->nnodes;
+    if (k) *k = v->k;
+    if (L) *L = v->L;
+    if (weighting) *weighting = v->weighting;
+    if (scoring) *scoring = v->scoring;
+    if (nwords) {   /* the childless nodes other than the root */
+        std::vector<int32_t> cs((size_t)v->nnodes + 1);
+        TB_HIP(v->ctx, hipMemcpy(cs.data(), v->d_child_start, cs.size() * 4, hipMemcpyDeviceToHost));
+        int n = 0;
+        for (int i = 1; i < v->nnodes; i++) n += cs[i + 1] == cs[i];
+        *nwords = n;
+    }
+    return TB_OK;
+}
+
+int tb_vocab_export(const tb_vocab* v, int32_t* child_start, int32_t* child_items, uint8_t* desc, int32_t* word_id, double* weight) {
+    if (!v || !v->ctx) return TB_EINVAL;
+    tb_ctx* ctx = v->ctx;
+    TB_ENTER(ctx);
+    const size_t nn = (size_t)v->nnodes;
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (child_start) TB_HIP(ctx, hipMemcpy(child_start, v->d_child_start, (nn + 1) * 4, hipMemcpyDeviceToHost));
+    if (child_items) {
+        int32_t nc = 0;
+        TB_HIP(ctx, hipMemcpy(&nc, v->d_child_start + nn, 4, hipMemcpyDeviceToHost));
+        if (nc) TB_HIP(ctx, hipMemcpy(child_items, v->d_child_items, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    }
+    if (desc) TB_HIP(ctx, hipMemcpy(desc, v->d_desc, nn * 32, hipMemcpyDeviceToHost));
+    if (word_id) TB_HIP(ctx, hipMemcpy(word_id, v->d_word_id, nn * 4, hipMemcpyDeviceToHost));
+    if (weight) TB_HIP(ctx, hipMemcpy(weight, v->d_weight, nn * 8, hipMemcpyDeviceToHost));
+    return TB_OK;
+}
+
 int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const uint8_t* desc, const int32_t* counts,
                                int desc_pitch, int levelsup, int32_t* word_ids, int32_t* node_ids, double* weights,
                                uint64_t* fv_keys, int32_t* fv_counts) {

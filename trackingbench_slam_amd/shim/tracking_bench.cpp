@@ -4,6 +4,7 @@
  * (the reference has no error convention: empty inputs return silently).
  */
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -172,6 +173,52 @@ namespace TRACKING_BENCH
         for (int n = 1; n < nn; n++) if (leaf[n]) word_id[n] = (int32_t)nwords++;
         if (device) { tb_vocab_destroy(device); device = nullptr; }
         return true;
+    }
+
+    void FlatVocabulary::create(const std::vector<std::vector<cv::Mat>>& training_features, int k_, int L_, DBoW2::WeightingType weighting_,
+                                DBoW2::ScoringType scoring_)
+    {
+        std::vector<int32_t> counts;
+        std::vector<uint8_t> d;
+        for (const auto& doc : training_features)
+        {
+            counts.push_back((int32_t)doc.size());
+            for (const cv::Mat& m : doc)
+            {
+                if (m.rows != 1 || m.cols != 32) throw std::runtime_error("FlatVocabulary::create: a descriptor is not 1 x 32");
+                d.insert(d.end(), m.ptr(0), m.ptr(0) + 32);
+            }
+        }
+        tb_vocab_train_params P;
+        P.k = k_; P.L = L_; P.weighting = (int)weighting_; P.scoring = (int)scoring_; P.seed = 0; P.max_iters = 200;
+        tb_vocab_train_stats st;
+        tb_vocab* v = nullptr;
+        check(tb_vocab_train(shim_ctx(), &P, (int)counts.size(), d.data(), counts.data(), &v, &st), "FlatVocabulary::create");
+        if (device) tb_vocab_destroy(device);
+        device = v;
+        k = k_; L = L_; weighting = P.weighting; scoring = P.scoring;
+        const size_t nn = (size_t)st.nnodes;
+        child_start.assign(nn + 1, 0); child_items.assign(nn - 1, 0); word_id.assign(nn, 0); desc.assign(nn * 32, 0); weight.assign(nn, 0.0);
+        check(tb_vocab_export(device, child_start.data(), child_items.data(), desc.data(), word_id.data(), weight.data()), "FlatVocabulary::create (export)");
+        nwords = (unsigned)st.nwords;
+    }
+
+    void FlatVocabulary::saveToTextFile(const std::string& filename) const
+    {
+        const int nn = (int)word_id.size();
+        std::vector<int> parent(nn, 0);
+        for (int n = 0; n < nn; n++)
+            for (int c = child_start[n]; c < child_start[n + 1]; c++) parent[child_items[c]] = n;
+        std::ofstream f(filename.c_str());
+        f << k << " " << L << " " << " " << scoring << " " << weighting << "\n";
+        char buf[40];
+        for (int n = 1; n < nn; n++)
+        {
+            f << parent[n] << " " << (child_start[n + 1] == child_start[n] ? 1 : 0) << " ";
+            for (int i = 0; i < 32; i++) f << (int)desc[(size_t)n * 32 + i] << " ";
+            std::snprintf(buf, sizeof buf, "%.17g", weight[n]);
+            f << buf << "\n";
+        }
     }
 
     void Frame::SetBow(const std::shared_ptr<ORBVocabulary>& voc)
