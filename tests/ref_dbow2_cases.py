@@ -1,0 +1,301 @@
+"""The cases that tests/test_ref_dbow2.py (CPU) and tests/test_gpu_ref_dbow2.py (GPU) put beside the reference's own DBoW2
+(oracle/ref_dbow2.py runs it), and tools/gen_ref_dbow2_golden.py records into tests/golden/ref_dbow2_v1.npz. Every input is
+seeded, so the fixture stores outputs only. A case is (mode, name); inputs(mode, name) builds what the driver is fed,
+live(mode, name) runs the driver, recorded(mode, name) reads the fixture, genuine(mode, name) takes the live driver where it
+exists and the fixture otherwise.
+
+Create cases: the reference is defined only where no k-means cluster ever runs empty (FORB::meanValue releases the mean of an
+empty group and the next FORB::distance dereferences it) and our iteration cap is a deviation, so create_inputs asserts from
+the restatement -- before the driver is called -- that no node had an empty cluster at ANY association and that none was capped.
+Tightly planted inputs such as planted(1, [300, 250, 400, 0, 120], 40), k=4, L=3 fail this and cannot be pinned."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import vocab_reference as vr
+from oracle import ref_dbow2
+from test_gpu_vocab_train import planted
+from trackingbench_slam_amd import synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_dbow2_v1.npz")
+RAND_MAX = 2147483647        # the C library's; the driver reports its own and the seed tests assert they agree
+
+
+# ------------------------------------------------------------------ FORB
+def _bits(*set_bits):
+    b = np.zeros(256, np.uint8)
+    b[list(set_bits)] = 1
+    return np.packbits(b)
+
+
+def forb_groups():
+    rng = np.random.default_rng(41)
+    r = lambda n: rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    g = [r(1), r(2), r(3), r(4), r(5), r(8), r(37), r(100), r(257)]
+    g.append(np.tile(r(1), (6, 1)))                                      # all equal, even
+    g.append(np.tile(r(1), (7, 1)))                                      # all equal, odd
+    # exact half-ties per bit: bit j is set in exactly n/2 of n (even n) for every j, and in (n-1)/2 and (n+1)/2 for odd n
+    half = np.array([[1] * 256, [0] * 256, [1, 0] * 128, [0, 1] * 128], np.uint8)
+    g.append(np.packbits(half, axis=1))                                  # n = 4: every bit set in exactly 2
+    g.append(np.packbits(half[[0, 1]], axis=1))                          # n = 2: threshold 1, the union
+    odd = np.array([[1, 1, 0, 0] * 64, [1, 0, 1, 0] * 64, [0, 1, 0, 0] * 64, [0, 0, 1, 0] * 64, [1, 0, 0, 0] * 64], np.uint8)
+    g.append(np.packbits(odd, axis=1))                                   # n = 5, threshold 3: counts 3, 2, 2, 0 per bit group
+    g.append(np.stack([_bits(0, 1), _bits(0, 1), _bits(0), _bits(0)]))
+    g.append(np.stack([_bits(7), _bits(255)]))
+    g.append(np.stack([_bits(), _bits(*range(256))]))                    # distance 256
+    return g
+
+
+# ------------------------------------------------------------------ transform
+GRID = [(1, 10, 3, 2, 0.0), (2, 4, 5, 4, 0.0), (3, 10, 4, 4, 0.0), (4, 6, 4, 1, 0.5), (5, 10, 3, 0, 0.0), (6, 3, 6, 9, 0.3),
+        (7, 5, 5, 2, 0.4), (8, 4, 4, 1, 0.6)]        # the grid of test_oracle_bow_transform.py + two more ragged trees
+TREES = ["s%d" % g[0] for g in GRID] + ["trained"]
+# trees on which the reference leaves nid unset for some features (a leaf above level L - levelsup > 0)
+RAGGED_UNSET = ["s4", "s7", "s8", "trained"]
+WS_ALL = [(w, s) for w in range(4) for s in range(6)]
+WS_RECORDED = [(0, 0), (1, 5), (2, 1), (3, 3)]
+
+
+def transform_name(tree, w, s, part="a"):
+    return "%s-w%d-s%d-%s" % (tree, w, s, part)
+
+
+TRAINED = (5, 5, vr.TF_IDF, 0, 9)      # k, L, weighting, scoring, seed of the "trained" tree
+
+
+def trained_docs():
+    rng = np.random.default_rng(77)
+    return [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in (150, 90, 0, 160)]
+
+
+@functools.lru_cache(maxsize=None)
+def _base_tree(tree):
+    if tree == "trained":      # leaves at levels 3 to 5: with levelsup 1 the level-3 leaves are the features without a nid
+        k, L, weighting, scoring, seed = TRAINED
+        voc, st = vr.train(trained_docs(), k, L, weighting, scoring, seed)
+        assert st["capped_nodes"] == 0
+        return voc, 1, np.concatenate(trained_docs())
+    seed, k, L, levelsup, ragged = [g for g in GRID if "s%d" % g[0] == tree][0]
+    return synth.vocabulary(seed, k, L, ragged=ragged), levelsup, None
+
+
+def transform_inputs(name):
+    """-> (vocabulary with the case's weighting and scoring, descriptors, levelsup)"""
+    tree, w, s, part = name.split("-")
+    w, s = int(w[1:]), int(s[1:])
+    base, levelsup, train_desc = _base_tree(tree)
+    voc = synth.Vocabulary(base.k, base.L, base.child_start, base.child_items, base.desc, base.word_id, base.weight, w, s)
+    n, sd = (300, 0) if part == "a" else (177, 50)
+    if tree == "trained":
+        rng = np.random.default_rng(78 + sd)
+        pick = train_desc[rng.integers(0, len(train_desc), n)]
+        flip = (rng.uniform(size=(n, 256)) < 6 / 256.0).astype(np.uint8)
+        desc = np.packbits(np.unpackbits(pick, axis=1) ^ flip, axis=1)
+    else:
+        desc = synth.descriptors_near_words(int(tree[1:]) + sd, voc, n)
+    return voc, desc, levelsup
+
+
+# ------------------------------------------------------------------ create
+def _uniform(seed, sizes):
+    rng = np.random.default_rng(seed)
+    return [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in sizes]
+
+
+def _dups(seed, nbase, times, ndocs):
+    """nbase random descriptors, each `times` times, shuffled over ndocs documents"""
+    rng = np.random.default_rng(seed)
+    d = np.tile(rng.integers(0, 256, (nbase, 32), dtype=np.uint8), (times, 1))[rng.permutation(nbase * times)]
+    return [np.ascontiguousarray(x) for x in np.array_split(d, ndocs)]
+
+
+ORB_FRAMES = [(s, f) for s in (0, 1) for f in range(4)]      # (sequence, frame) of the ORB-descriptor case
+ORB_NFEAT = 2000
+
+
+def orb_image(seq, frame):
+    from trackingbench_slam_amd import synth_seq
+    return synth_seq.render(synth_seq.scene(seq), synth_seq.trajectory(seq, 10, 0.5)[frame], 1241, 376)
+
+
+def _orb_docs():
+    """ORB descriptors of the project's own rendered frames, extracted by the CPU oracle (the device extractor gives the same
+    bytes: tests/test_gpu_ref_dbow2.py asserts it before it trains on its own)"""
+    import oracle
+    docs = []
+    for seq, frame in ORB_FRAMES:
+        lv, sf = oracle.pyramid(orb_image(seq, frame), 5, 0.8)
+        docs.append(oracle.orb_extract(lv, sf, ORB_NFEAT, 40, 10)[1])
+    return docs
+
+
+_IDENT = np.tile(np.arange(32, dtype=np.uint8), (50, 1))
+CREATE = {   # name: (docs builder, k, L, weighting, scoring, training seed)
+    "uniform-k9-L3": (lambda: _uniform(4, [400] * 6), 9, 3, vr.TF_IDF, 0, 4),
+    "planted-k3-L6-tf": (lambda: planted(5, [37, 5, 1, 90], 7), 3, 6, vr.TF, 0, 0),
+    "empty-docs-tfidf": (lambda: _uniform(3, [120, 0, 77, 200]), 4, 3, vr.TF_IDF, 1, 0),
+    "empty-docs-tf": (lambda: _uniform(3, [120, 0, 77, 200]), 4, 3, vr.TF, 0, 0),
+    "empty-docs-idf": (lambda: _uniform(3, [120, 0, 77, 200]), 4, 3, vr.IDF, 2, 0),
+    "empty-docs-binary": (lambda: _uniform(3, [120, 0, 77, 200]), 4, 3, vr.BINARY, 5, 0),
+    "uniform-k2-L6-idf": (lambda: _uniform(6, [90, 0, 110]), 2, 6, vr.IDF, 0, 1),
+    "no-docs": (lambda: [], 4, 3, vr.TF_IDF, 0, 0),
+    "three-empty-docs": (lambda: [np.zeros((0, 32), np.uint8)] * 3, 4, 3, vr.TF_IDF, 0, 0),
+    "one-descriptor": (lambda: planted(5, [1], 1), 4, 3, vr.TF_IDF, 0, 0),
+    "three-of-k4": (lambda: planted(4, [3], 3), 4, 3, vr.IDF, 0, 0),
+    "exactly-k": (lambda: planted(6, [2, 0, 2], 4), 4, 2, vr.TF_IDF, 0, 0),
+    "duplicates-k3-L5": (lambda: _dups(7, 150, 3, 3), 3, 5, vr.TF_IDF, 0, 2),
+    "duplicate-pairs-trivial": (lambda: [np.stack([_bits(1), _bits(1)]), np.stack([_bits(9)])], 3, 2, vr.IDF, 0, 0),
+    "identical": (lambda: [_IDENT[:20], _IDENT[20:]], 4, 3, vr.TF_IDF, 0, 0),
+    "uniform-3500-k6-L3": (lambda: _uniform(8, [1200, 1000, 1300]), 6, 3, vr.TF_IDF, 0, 3),
+    "orb-k10-L5": (_orb_docs, 10, 5, vr.TF_IDF, 0, 0),
+}
+CREATE_LIVE_ONLY = ["uniform-3500-k6-L3", "orb-k10-L5"]      # kept out of the fixture for their size
+
+
+@functools.lru_cache(maxsize=None)
+def create_inputs(name):
+    """-> (docs, k, L, weighting, scoring, seed, restatement vocabulary, restatement stats, [(members, picks)]); asserts the
+    condition under which the reference is defined"""
+    mk, k, L, weighting, scoring, seed = CREATE[name]
+    docs = mk()
+    seeds, bad = [], []
+    voc, st = vr.train(docs, k, L, weighting, scoring, seed, hook=lambda m, p, e, c: (seeds.append((m, p)), bad.append(e or c)))
+    assert not any(bad), "create case %s: %d k-means nodes ran a cluster empty or hit the cap" % (name, sum(bad))
+    assert st["capped_nodes"] == 0 and st["empty_clusters"] == 0, (name, st)
+    return docs, k, L, weighting, scoring, seed, voc, st, seeds
+
+
+# ------------------------------------------------------------------ seeding
+def _seed_sets():
+    rng = np.random.default_rng(90)
+    R = lambda n: rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    draws = lambda n: [int(x) for x in rng.integers(1, RAND_MAX, n)]
+    A, B, Cc = R(1)[0], R(1)[0], R(1)[0]
+    out = {}
+    out["random-40-k5"] = (R(40), 5, draws(5))
+    out["random-200-k10"] = (R(200), 10, draws(10))
+    out["n-equals-k"] = (R(6), 6, draws(6))
+    out["two-values-stop-early"] = (np.stack([A, A, B, B, A, B]), 4, draws(4))           # the sum reaches 0 after two centres
+    out["three-values-duplicated"] = (np.stack([A, B, A, Cc, B, Cc, A, Cc]), 5, draws(5))
+    out["all-equal"] = (np.tile(A, (9, 1)), 3, draws(3))                                  # one centre, one draw
+    d = draws(8)
+    d[1], d[2], d[4] = 0, 0, 0                                                            # cut 0.0 is redrawn
+    out["zero-draws-are-redrawn"] = (R(30), 4, d)
+    out["first-pick-zero"] = (R(30), 3, [0] + draws(2))
+    out["first-pick-randmax"] = (R(30), 3, [RAND_MAX] + draws(2))                         # int(n RAND_MAX / (RAND_MAX + 1)) = n - 1
+    out["cut-lands-on-the-last-index"] = (R(25), 4, [1, RAND_MAX, RAND_MAX, RAND_MAX])    # cut == the whole sum
+    dd = np.concatenate([R(12), np.tile(A, (3, 1))])
+    dd[0] = A
+    out["cut-at-sum-with-zero-tail"] = (dd, 3, [1, RAND_MAX, 5])   # first centre A: the tail's distances are 0, the sum is reached before it
+    out["tiny-cuts"] = (R(50), 6, [7, 1, 1, 1, 1, 1])                                     # cut just above 0: the first index with D > 0
+    return out
+
+
+SEED = _seed_sets()
+
+
+class DrawStream:
+    """vocab_reference.seed_centres' random stream fed from the same integers as the genuine rand(): the first pick is
+    RandomInt's r / (RAND_MAX + 1.0), every cut RandomValue's r / RAND_MAX (DUtils/Random.cpp:47-50, Random.h:55-69)"""
+
+    def __init__(self, draws):
+        self.draws, self.pos = list(draws), 0
+
+    def uniform(self, n):
+        assert n == 1 and self.pos < len(self.draws), "the restatement asked for more draws than supplied"
+        r = float(self.draws[self.pos])
+        u = r / (float(RAND_MAX) + 1.0) if self.pos == 0 else r / float(RAND_MAX)
+        self.pos += 1
+        return np.array([u])
+
+
+# ------------------------------------------------------------------ live / recorded outputs
+def all_cases():
+    """every (mode, name) -> recorded in the fixture?"""
+    c = {("forb", "groups"): True}
+    for t in TREES:
+        for w, s in WS_ALL:
+            c[("transform", transform_name(t, w, s))] = (w, s) in WS_RECORDED
+        c[("transform", transform_name(t, 0, 0, "b"))] = True
+    for n in CREATE:
+        c[("create", n)] = n not in CREATE_LIVE_ONLY
+    for n in SEED:
+        c[("seed", n)] = True
+    return c
+
+
+def live(mode, name):
+    case = "%s/%s" % (mode, name)
+    if mode == "forb":
+        return ref_dbow2.forb(forb_groups(), case)
+    if mode == "transform":
+        voc, desc, levelsup = transform_inputs(name)
+        return ref_dbow2.transform(voc, desc, levelsup, case)
+    if mode == "create":
+        docs, k, L, weighting, scoring, _, _, _, seeds = create_inputs(name)
+        return ref_dbow2.create(docs, k, L, weighting, scoring, seeds, case)
+    D, k, draws = SEED[name]
+    return ref_dbow2.seed(D, k, draws, case)
+
+
+def to_record(mode, out):
+    """the part of a driver output that the fixture keeps"""
+    # transform cases: the tree is an input, only its counts are recorded
+    drop = ("parent", "word_id", "weight_bits", "child_start", "child_items", "desc", "desc_len", "word_nodes") if mode == "transform" else ()
+    rec = {}
+    for k, v in out.items():
+        if k not in drop:
+            if v.dtype == np.int64:
+                assert (np.abs(v) < 2 ** 31).all()
+                v = v.astype(np.int32)
+            rec[k] = v
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
+def _fixture():
+    return np.load(GOLDEN, allow_pickle=False)
+
+
+def recorded(mode, name):
+    z = _fixture()
+    pre = "%s/%s/" % (mode, name)
+    out = {k[len(pre):]: z[k] for k in z.files if k.startswith(pre)}
+    assert out, "tests/golden/ref_dbow2_v1.npz holds no case %s%s" % (mode, name)
+    return out
+
+
+def genuine(mode, name):
+    """the live driver's output where the driver exists, the recorded one otherwise; skips only if neither exists"""
+    if ref_dbow2.available():
+        return live(mode, name)
+    if all_cases()[(mode, name)]:
+        return recorded(mode, name)
+    pytest.skip(ref_dbow2.SKIP_REASON + "; case %s/%s is not in the fixture" % (mode, name))
+
+
+# ------------------------------------------------------------------ comparisons shared by the CPU and the GPU tests
+def assert_same_tree(out, voc, what):
+    """a driver tree (straight from m_nodes) == a synth.Vocabulary, bit for bit"""
+    nn = voc.nnodes
+    leaves = np.flatnonzero(np.diff(voc.child_start) == 0)
+    leaves = leaves[leaves > 0]
+    assert out["tree"].tolist() == [nn, len(leaves), voc.k, voc.L, voc.c.scoring, voc.c.weighting], what
+    if "child_start" not in out:
+        return
+    assert np.array_equal(out["word_nodes"], leaves), what
+    assert np.array_equal(out["child_start"], voc.child_start) and np.array_equal(out["child_items"], voc.child_items), what
+    parent = np.zeros(nn, np.int64)
+    for n in range(nn):
+        parent[voc.child_items[voc.child_start[n]:voc.child_start[n + 1]]] = n
+    assert np.array_equal(out["parent"], parent), what
+    assert (out["desc_len"][1:] == 32).all() and np.array_equal(out["desc"][1:], voc.desc[1:]), what
+    assert np.array_equal(out["word_id"], voc.word_id), what
+    assert np.array_equal(out["weight_bits"], voc.weight.view(np.uint64)), what
+
+
+def fv_of(out):
+    """the genuine FeatureVector as {node: [feature indices]}"""
+    return {int(n): out["fv_items"][out["fv_start"][i]:out["fv_start"][i + 1]].tolist() for i, n in enumerate(out["fv_nodes"])}

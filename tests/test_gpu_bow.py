@@ -1,7 +1,8 @@
 """GPU parity tests (pytest -m gpu), SURVEY 8(f) row 4 second half: the DBoW2 transform behind Frame::SetBow
 (src/types/Frame.cpp:267-270; TemplatedVocabulary.h:1124-1260) on the device, the frames' FeatureVectors as sorted key lists,
 and the batched device-resident Matcher::searchByBow (matcher.cpp:619-721) fed by them -- all bit-exact against the oracle.
-PARITY UNPINNED against DBoW2 itself: the reference tree ships no vocabulary file, the trees are seeded synthetic ones."""
+The reference tree ships no vocabulary file, the trees are seeded synthetic ones; parity with DBoW2's own code on such trees is
+pinned in tests/test_ref_dbow2.py (the oracle) and tests/test_gpu_ref_dbow2.py (the device)."""
 import ctypes as C
 
 import numpy as np

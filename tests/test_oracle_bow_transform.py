@@ -1,7 +1,12 @@
 """CPU test: the oracle's DBoW2 transform (Frame::SetBow = voc->transform(descriptors, BowVector, FeatureVector, 4),
 reference src/types/Frame.cpp:267-270; third_part/DBoW2/DBoW2/TemplatedVocabulary.h:1124-1260, FORB.cpp:81-101) against an
-independent numpy walk of the same tree, and the properties the containers must have. PARITY UNPINNED: the reference tree
-ships no vocabulary file, so the trees are seeded synthetic ones (synth.vocabulary)."""
+independent numpy walk of the same tree, and the properties the containers must have. The reference tree ships no vocabulary
+file, so the trees are seeded synthetic ones (synth.vocabulary). Parity with DBoW2 itself is pinned next door:
+tests/test_ref_dbow2.py runs the reference's own loadFromTextFile and transform on this file's grid of trees (and more) and
+compares words, weights, node ids, BowVector bits and FeatureVectors with oracle.bow_transform / oracle.bow_containers exactly.
+The reference is undefined in four places (an empty k-means cluster, no iteration cap, an unset nid, the loader's phantom node
+after a final newline); two touch this file: a walk that ends above level L - levelsup leaves nid unset there -- here it is the
+leaf, which _walk restates as a definition -- and to_text therefore ends its file without a newline."""
 import numpy as np
 import pytest
 

@@ -1,5 +1,8 @@
 """numpy restatement of DBoW2's vocabulary training (TemplatedVocabulary<FORB::TDescriptor, FORB>::create), the yardstick of
-tests/test_gpu_vocab_train.py. Written from the description of the algorithm, in create's own recursion order:
+tests/test_gpu_vocab_train.py. Written from the description of the algorithm, in create's own recursion order, and since
+pinned to the reference's own code: tests/test_ref_dbow2.py runs the genuine FORB::distance / meanValue, initiateClustersKMpp
+(fed the same integer draws) and create (seeded per k-means node with this file's seeds, through train's hook) and gets the
+same centres, draw counts and whole trees, bit for bit.
 
 * root = node 0; a node with n <= k descriptors gets one child per descriptor; a node with more runs Hamming k-means:
   kmeans++ seeding with D(x) (not D^2), a point whose distance is 0 is never updated, the next centre is the first index whose
@@ -17,6 +20,10 @@ The three deviations from the reference, shared with the device implementation (
 2. an empty cluster keeps its last centre;
 3. max_iters: after the max_iters-th association a node stops with the centres used for that association; it counts as capped
    unless that association repeated the one before.
+Deviation 1 is pinned (the rule, not the generator). Deviations 2 and 3 are definitions where the reference has no behaviour:
+it dereferences the released mean of an empty cluster and loops without bound; the pinned cases assert neither happens. The
+other two places where DBoW2 is undefined belong to the transform and the text file (an unset nid, the loader's phantom node:
+tests/test_oracle_bow_transform.py, synth.Vocabulary.to_text).
 stats: nnodes, nwords, capped_nodes, empty_clusters (children that end with no descriptor), iters_per_level[level - 1] = the
 largest number of associations any k-means node of that level ran (0: no k-means node)."""
 import math
@@ -76,9 +83,13 @@ def seed_centres(D, k, st):
     return picks
 
 
-def kmeans(D, k, st, max_iters):
-    """-> centres [m, 32], assignment [n], associations run, capped"""
-    C = D[seed_centres(D, k, st)].copy()
+def kmeans(D, k, st, max_iters, info=None):
+    """-> centres [m, 32], assignment [n], associations run, capped. info (a dict, test-side): receives the seed picks and
+    whether any association, not only the last, left a cluster without a descriptor."""
+    picks = seed_centres(D, k, st)
+    C = D[picks].copy()
+    if info is not None:
+        info.update(picks=picks, empty_any=False)
     last, it = None, 0
     while True:
         it += 1
@@ -88,6 +99,8 @@ def kmeans(D, k, st, max_iters):
                 if len(g):
                     C[c] = mean_value(g)
         a = associate(D, C)
+        if info is not None and len(np.unique(a)) < len(C):
+            info["empty_any"] = True
         if it > 1 and np.array_equal(a, last):
             return C, a, it, False
         if it == max_iters:
@@ -115,8 +128,11 @@ def walk(child_lists, desc, D):
     return cur
 
 
-def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200):
-    """docs: sequence of uint8 [n_i, 32] arrays -> (synth.Vocabulary, stats dict)"""
+def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200, hook=None):
+    """docs: sequence of uint8 [n_i, 32] arrays -> (synth.Vocabulary, stats dict). hook (test-side, changes nothing that is
+    returned): called once per k-means node, in creation order, as hook(members, picks, empty_any, capped) -- the node's
+    descriptors and its seeds as indices into the concatenated documents, whether any association of the node left a cluster
+    empty, and whether the node hit max_iters. tests/test_ref_dbow2.py feeds these seeds to the genuine create."""
     assert k >= 2 and 1 <= L <= MAX_L and max_iters >= 1
     docs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
     allD = np.concatenate(docs) if docs else np.zeros((0, 32), np.uint8)
@@ -126,7 +142,8 @@ def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200):
     rank_of = [0]
     stats = dict(nnodes=0, nwords=0, capped_nodes=0, empty_clusters=0, iters_per_level=[0] * MAX_L)
 
-    def step(parent, D, level):
+    def step(parent, idx, level):
+        D = allD[idx]
         n = len(D)
         if n == 0:
             return
@@ -134,7 +151,10 @@ def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200):
             C, a = D.copy(), np.arange(n)
         else:
             st = synth.Stream(seed + (level << 40) + rank_of[parent])
-            C, a, it, capped = kmeans(D, k, st, max_iters)
+            info = {} if hook is not None else None
+            C, a, it, capped = kmeans(D, k, st, max_iters, info)
+            if hook is not None:
+                hook(idx.tolist(), idx[info["picks"]].tolist(), info["empty_any"], capped)
             stats["capped_nodes"] += int(capped)
             stats["iters_per_level"][level - 1] = max(stats["iters_per_level"][level - 1], it)
         ids = []
@@ -145,14 +165,14 @@ def train(docs, k, L, weighting=TF_IDF, scoring=0, seed=0, max_iters=200):
             rank_of.append(rank[level])
             rank[level] += 1
         children[parent] = ids
-        groups = [D[a == c] for c in range(len(C))]
+        groups = [idx[a == c] for c in range(len(C))]
         stats["empty_clusters"] += sum(1 for g in groups if len(g) == 0)
         if level < L:
             for c, g in enumerate(groups):
                 if len(g) > 1:
                     step(ids[c], g, level + 1)
 
-    step(0, allD, 1)
+    step(0, np.arange(len(allD)), 1)
     nn = len(desc)
     desc = np.stack(desc)
     cs, ci = [0], []

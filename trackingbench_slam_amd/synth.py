@@ -288,15 +288,24 @@ class Vocabulary:
 
     def to_text(self, path):
         """The ORBvoc-style text file TemplatedVocabulary::loadFromTextFile reads (TemplatedVocabulary.h:1338-1420): first line
-        k L scoring weighting, then one line per node in id order: parent, is-leaf, the 32 descriptor bytes, the weight."""
+        k L scoring weighting, then one line per node in id order: parent, is-leaf, the 32 descriptor bytes, the weight (repr:
+        the shortest decimal that reads back to the same double). The LAST line carries no terminator: the genuine loader
+        loops `while(!f.eof())`, so after a final newline it reads one more, empty, line and appends a phantom node under the
+        root with an unset descriptor and leaf flag (the reference's own saveToTextFile writes such a file; a k=4, L=3 round
+        trip through it reported 65 words of at most 64). What the loader builds from a file that ends in a newline is
+        undefined; from this file it builds exactly nnodes nodes and nwords words, with every parent, descriptor and weight bit as
+        written: tests/test_ref_dbow2.py runs the reference's own loader on it, the file's only consumer besides the shim's
+        FlatVocabulary. (The phantom node is one of four places where DBoW2 is undefined and the project's rule is a definition;
+        the others: an empty k-means cluster, no iteration cap, an unset nid -- DESIGN.md section 2.)"""
         parent = np.zeros(self.nnodes, np.int64)
         for n in range(self.nnodes):
             parent[self.child_items[self.child_start[n]:self.child_start[n + 1]]] = n
+        lines = ["%d %d %d %d" % (self.k, self.L, self.c.scoring, self.c.weighting)]
+        for n in range(1, self.nnodes):
+            leaf = self.child_start[n + 1] == self.child_start[n]
+            lines.append("%d %d %s %r" % (parent[n], 1 if leaf else 0, " ".join(str(int(b)) for b in self.desc[n]), float(self.weight[n])))
         with open(path, "w") as f:
-            f.write("%d %d %d %d\n" % (self.k, self.L, self.c.scoring, self.c.weighting))
-            for n in range(1, self.nnodes):
-                leaf = self.child_start[n + 1] == self.child_start[n]
-                f.write("%d %d %s %r\n" % (parent[n], 1 if leaf else 0, " ".join(str(int(b)) for b in self.desc[n]), float(self.weight[n])))
+            f.write("\n".join(lines))
 
 
 def vocabulary(seed, k=10, L=4, stop_frac=0.05, ragged=0.0):
