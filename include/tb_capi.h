@@ -237,7 +237,8 @@ int tb_search_by_violence_batch_dev(tb_ctx* ctx, int npairs, const tb_keypoint* 
  * tb_bow_transform: per descriptor the word it falls into (word_ids), that word's weight (weights; 0 = a stopped word, which
  * enters neither vector) and its ancestor at level L - levelsup (node_ids: the key of the frame's FeatureVector; the root when
  * L - levelsup <= 0; where a branch ends above that level the reference leaves the id unset -- here it is the leaf).
- * Host pointers. The BowVector / FeatureVector containers are built from these arrays (shim: Frame::SetBow). */
+ * Host pointers. The BowVector / FeatureVector containers are built from these arrays (shim: Frame::SetBow; on the device:
+ * the fv_keys of tb_bow_transform_batch_dev and tb_bow_vector_batch_dev). */
 typedef struct tb_vocab tb_vocab;
 int tb_vocab_create(tb_ctx* ctx, const tb_vocabulary* host, tb_vocab** out);
 void tb_vocab_destroy(tb_vocab* v);
@@ -251,6 +252,20 @@ int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int 
 int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const uint8_t* desc, const int32_t* counts,
                                int desc_pitch, int levelsup, int32_t* word_ids, int32_t* node_ids, double* weights,
                                uint64_t* fv_keys, int32_t* fv_counts);
+/* The other container of that transform, the BowVector (Frame::mBowVec), batched and device-resident: TemplatedVocabulary::
+ * transform(features, v, fv, levelsup) (TemplatedVocabulary.h:1124-1188) and BowVector::normalize (BowVector.cpp:57-80) on the
+ * arrays tb_bow_transform_batch_dev wrote (word_ids, weights: [nframes][desc_pitch], counts[f] of them valid). Per frame one sorted
+ * list, [nframes][desc_pitch]: bv_words ascending (the std::map's order), bv_values beside them, bv_counts[f] entries.
+ *  - a stopped word (weight 0) does not enter the vector;
+ *  - TF and TF_IDF add a word's weights in ascending feature index, IDF and BINARY keep the first;
+ *  - TF and TF_IDF under a scoring object that does not normalise (DOT_PRODUCT) divide by the number of words in the vector;
+ *  - otherwise the vector is divided by its L1 norm, or its L2 norm (L2_NORM: sqrt of the squares' sum), summed in ascending word
+ *    order by one thread and applied only when it is greater than 0.
+ * Weighting and scoring are the tb_vocab's. The values are doubles and come out bit for bit as DBoW2's: one operation per
+ * statement, no FMA, no tree reduction. Device pointers, asynchronous on the context's stream; desc_pitch <= 8192; null or
+ * inconsistent arguments are TB_EINVAL. Scoring two vectors (ScoringObject::score) stays outside this library. */
+int tb_bow_vector_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const int32_t* word_ids, const double* weights,
+                            const int32_t* counts, int desc_pitch, int32_t* bv_words, double* bv_values, int32_t* bv_counts);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -441,7 +456,7 @@ int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf,
  *             map points of entries [0, min(n, m)) and nulls [n, m); AddMapPointsByStereo(cur, right, bf, fx) (:800); every key
  *             j with depth > 0 gets a new map point R * norm * depth + t (R, t of Twc at the optimised pose; norm from
  *             u = (int)x, v = (int)y in double). Deviation: a depth that is not finite (zero disparity) creates no point.
- * Dropped: SetBow (its output is unused), the viewer, imshow and the printing. Local BA is not part of the loop (the
+ * Dropped: the viewer, imshow and the printing; SetBow (:705) runs only in a TB_VO_BOW loop, the one that reads its output. Local BA is not part of the loop (the
  * reference's map_ptr->AddKeyFrame is commented out, :839).
  * State lives in the object (ping-pong key / map-point buffers, a copy of the last left image); after the first step a step
  * makes no host synchronisation and no host <-> device copy. Key capacity = the extractor's kp_capacity. The object uses its
@@ -524,7 +539,7 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
  * the oldest keyframe's points leave as a block and the rest move down (a keyframe that spawned no point still counts as a
  * block). A run with at most map_keyframes keyframes is the reference's loop exactly. The match list of the map tracker holds one
  * match per map point at most: its capacity is the map's, not key_pitch (tb_vo_map_state_dev). */
-enum { TB_VO_OPFLOW = 0, TB_VO_BF = 1, TB_VO_VIOLENCE = 2, TB_VO_PROJECTION = 3, TB_VO_PROJECTION_MAP = 4 };
+enum { TB_VO_OPFLOW = 0, TB_VO_BF = 1, TB_VO_VIOLENCE = 2, TB_VO_PROJECTION = 3, TB_VO_PROJECTION_MAP = 4, TB_VO_BOW = 5 };
 typedef struct tb_vo_tracker {
     int kind;                       /* TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, TB_VO_PROJECTION_MAP */
     float bf_ratio, bf_min_th;      /* searchByBF ratio / minTh (:712: 10, 30) */
@@ -549,6 +564,40 @@ int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** 
                             const tb_match** matches, const int32_t** match_counts, const int32_t** flags, const tb_keypoint** kf_orb,
                             const uint8_t** kf_desc, const float** kf_map_points, const uint8_t** kf_mp_valid,
                             const int32_t** kf_counts, int* kf_frame);
+/* The fourth tracking line of test_kitti, searchByBow (:711), with Frame::SetBow (:705) on the device:
+ *   TB_VO_BOW  setBowParam(50, 100, 30, true, 6) (:706); searchByBow(cur, key_frame, true): th_low 50, nratio 6 (which makes the
+ *              ratio test vacuous -- reproduced, not fixed), histo_len 30, check_orientation 1, map_point_only 1, levelsup 4
+ *              (Frame.cpp:269). test_vo_1's set (:207, :212) is th_low 30, nratio 5, map_point_only 0.
+ * :711 as written reads searchByBow(cur_frame_ptr, cur_frame_ptr, true), a frame against itself, which tracks nothing; test_vo_1
+ * :212 and the neighbouring lines :712-713 match against key_frame, so the train frame here is the keyframe.
+ * A BoW frame t is the descriptor frame above with these differences:
+ *   every frame  after ORB, SetBow: tb_bow_transform_batch_dev with levelsup (word, weight and node per key, the FeatureVector
+ *                keys), then tb_bow_vector_batch_dev (the BowVector)
+ *   tracking     t > 0: tb_search_by_bow_batch_dev, F1 = the current frame, F2 = the keyframe, has_mp2 = the keyframe snapshot's
+ *                kf_mp_valid. Each queryIdx occurs at most once; the carry, the rows in key order, invSigma2 by octave and the
+ *                rule for fewer than 3 rows are the descriptor frame's
+ *   keyframe     the snapshot also keeps the keyframe's word and node ids, FeatureVector keys and BowVector as SetBow computed
+ *                them on that frame: they are not computed again
+ * The loop has its own creation entry because it needs a vocabulary; tb_vo_tracker keeps its layout and tb_vo_create_ex refuses
+ * TB_VO_BOW. voc (tb_vocab_create, tb_vocab_train*, on the same context) is BORROWED: it must outlive the tb_vo; NULL or a
+ * vocabulary of another context is TB_EINVAL. histo_len outside 1..1024, levelsup < 0 or th_low < 0 is TB_EINVAL (so is a
+ * zero-initialised tb_vo_bow); a key capacity above 8192 is TB_EUNSUPPORTED. The transform's and the matcher's buffers are sized
+ * in the create call: after the first step a step makes no host synchronisation and no host <-> device copy.
+ * tb_vo_state_dev and tb_vo_tracker_state_dev serve this loop as they serve the other descriptor trackers. */
+typedef struct tb_vo_bow {
+    int levelsup;           /* Frame::SetBow's levelsup (4) */
+    int map_point_only;     /* searchByBow's MapPointOnly (:711: 1): skip keyframe keys without a map point */
+    int th_low; float nratio; int histo_len; int check_orientation;   /* the Matcher's fields after :706: 50, 6, 30, 1 */
+} tb_vo_bow;
+int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* params, const tb_vo_bow* bow, const tb_vocab* voc, int nseq, tb_vo** out);
+/* Device views of SetBow's outputs after the last step (valid until the next step; every output nullable; TB_ESTATE for any other
+ * tracker), for the current frame and, kf_*, for the keyframe as computed on its frame: fv_keys [nseq][key_pitch] uint64
+ * (node << 32 | key) with fv_counts [nseq]; bv_words / bv_values [nseq][key_pitch] with bv_counts [nseq]; word_ids and node_ids
+ * [nseq][key_pitch], entry j of key j. */
+int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_counts, const int32_t** bv_words, const double** bv_values,
+                        const int32_t** bv_counts, const int32_t** word_ids, const int32_t** node_ids, const uint64_t** kf_fv_keys,
+                        const int32_t** kf_fv_counts, const int32_t** kf_bv_words, const double** kf_bv_values, const int32_t** kf_bv_counts,
+                        const int32_t** kf_word_ids, const int32_t** kf_node_ids);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

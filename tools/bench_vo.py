@@ -11,8 +11,10 @@ repeated to fill the batch) and uploaded before anything is timed, so the steps 
 --tracker picks the loop's tracking line (test_vo.cpp:712-716): opflow (default), bf or violence with the reference's arguments;
 the descriptor trackers also report their matches per tracking frame. projection and projection_map are the two lines of
 test_projection.cpp:512-517; the map tracker's step grows with its map, so its tracking step is also reported by the number of
-keyframes the map holds (--map-keyframes, default 4; --steps 41 fills four at the default keyframe period). Prints one JSON
-line.
+keyframes the map holds (--map-keyframes, default 4; --steps 41 fills four at the default keyframe period). bow is the fourth
+line of test_vo.cpp (:711, searchByBow against the keyframe, SetBow on every frame) with a vocabulary trained by
+tb_vocab_train_dev on the ORB descriptors of the sequences' first frames (k = 10, one result set per --voc-levels entry;
+--bow-set picks test_kitti's or test_vo_1's arguments). Prints one JSON line.
 """
 import argparse
 import json
@@ -23,8 +25,35 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from trackingbench_slam_amd import synth_seq   # noqa: E402
-from trackingbench_slam_amd.vo import StereoVO  # noqa: E402
+from trackingbench_slam_amd import capi, synth_seq   # noqa: E402
+from trackingbench_slam_amd.vo import BOW_TEST_VO_1, StereoVO  # noqa: E402
+
+
+def train_on_first_frames(first, L, info):
+    """vocab= for StereoVO(tracker="bow"): ORB (the loop's arguments) on the sequences' first left images, then
+    tb_vocab_train_dev on the extractor's output, all on the loop's context. info receives the tree's size."""
+    def make(ctx):
+        D, H, W = first.shape
+        exr = capi.Extractor(ctx, W, H, 5, 0.8, D, 2000)
+        try:
+            cap = exr.results_dev()[3]
+            kps = torch.zeros((D, cap, 7), dtype=torch.float32, device="cuda")
+            desc = torch.zeros((D, cap, 32), dtype=torch.uint8, device="cuda")
+            counts = torch.zeros(D, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()   # the context has its own stream
+            n = exr.set_images_host(first)
+            exr.build_pyramid(n)
+            exr.orb(n, 2000, 80.0, 30.0)
+            exr.copy_results_dev(n, kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), cap)
+            ctx.synchronize()
+            h, voc, st = ctx.vocab_train_dev(desc, counts, 10, L)
+        finally:
+            exr.close()
+        leaves = np.flatnonzero(np.diff(voc.child_start) == 0)
+        info.update(k=10, L=L, descriptors=int(counts.sum().item()), nodes=st["nnodes"], words=st["nwords"],
+                    stopped_words=int((voc.weight[leaves[leaves > 0]] == 0).sum()))
+        return h
+    return make
 
 
 def centre(T):
@@ -32,13 +61,15 @@ def centre(T):
     return -T[:3, :3].T @ T[:3, 3]
 
 
-def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow", params=None):
+def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow", params=None, voc_L=None):
     D = L.shape[1]
     rep = lambda a: a[:, np.arange(S) % D]   # noqa: E731
     dL = torch.from_numpy(np.ascontiguousarray(rep(L))).cuda()
     dR = torch.from_numpy(np.ascontiguousarray(rep(R))).cuda()
     Gs = rep(G)
-    vo = StereoVO(S, keyframe_every=every, tracker=tracker, **(params or {}))
+    voc_info = {}
+    kw = dict(vocab=train_on_first_frames(np.ascontiguousarray(L[0]), voc_L, voc_info)) if tracker == "bow" else {}
+    vo = StereoVO(S, keyframe_every=every, tracker=tracker, **kw, **(params or {}))
     try:
         # stats (and the first step, which sizes every buffer)
         vo.reset(Gs[0])
@@ -68,7 +99,8 @@ def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow", params=No
         total_ms = ev[0][0].elapsed_time(ev[-1][1])
         kf = np.array([t % every == 0 for t in range(T)])
         if timed_only:
-            return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3))
+            return dict(S=S, T=T, frames_per_s=round(S * T / (total_ms / 1e3), 1), total_ms=round(total_ms, 3),
+                        **(dict(vocabulary=voc_info) if voc_info else {}))
         # per-kernel split
         vo.reset(Gs[0])
         torch.cuda.synchronize()
@@ -80,7 +112,7 @@ def run_size(S, L, R, G, T, every, timed_only=False, tracker="opflow", params=No
     finally:
         vo.close()
     kern = {k: dict(calls=c, ms=round(m, 4)) for k, (c, m) in sorted(rep_.items(), key=lambda kv: -kv[1][1])}
-    extra = {}
+    extra = dict(vocabulary=voc_info) if voc_info else {}
     if mts:
         mts = np.array(mts)
         extra["matches_per_frame"] = dict(mean=round(float(mts.mean()), 1), min=int(mts.min()))
@@ -104,7 +136,9 @@ def main():
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--distinct", type=int, default=4, help="different synthetic sequences, repeated to fill a batch")
     ap.add_argument("--keyframe-every", type=int, default=10)
-    ap.add_argument("--tracker", choices=("opflow", "bf", "violence", "projection", "projection_map"), default="opflow")
+    ap.add_argument("--tracker", choices=("opflow", "bf", "violence", "projection", "projection_map", "bow"), default="opflow")
+    ap.add_argument("--voc-levels", default="5,6", help="bow: depths L of the trained vocabularies (k = 10)")
+    ap.add_argument("--bow-set", choices=("test_kitti", "test_vo_1"), default="test_kitti", help="bow: searchByBow's arguments")
     ap.add_argument("--map-keyframes", type=int, default=4, help="projection_map: keyframes the map holds")
     ap.add_argument("--speed", type=float, default=0.5, help="metres per frame of the synthetic sequences")
     ap.add_argument("--timed-only", action="store_true", help="first pass without state reads, then the timed pass only "
@@ -114,7 +148,12 @@ def main():
     seqs = [synth_seq.sequence(s, T, speed=args.speed) for s in range(args.distinct)]
     params = dict(map_keyframes=args.map_keyframes) if args.tracker == "projection_map" else None
     L = np.stack([q[0] for q in seqs], 1); R = np.stack([q[1] for q in seqs], 1); G = np.stack([q[2] for q in seqs], 1)
-    res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker, params) for S in args.sizes.split(",")]
+    if args.tracker == "bow":
+        params = dict(BOW_TEST_VO_1) if args.bow_set == "test_vo_1" else None
+        res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker, params, int(vl))
+               for vl in args.voc_levels.split(",") for S in args.sizes.split(",")]
+    else:
+        res = [run_size(int(S), L, R, G, T, args.keyframe_every, args.timed_only, args.tracker, params) for S in args.sizes.split(",")]
     print(json.dumps(dict(tool="bench_vo", tracker=args.tracker, device=torch.cuda.get_device_name(0), width=1241, height=376,
                           keyframe_every=args.keyframe_every, distinct_sequences=args.distinct, speed_m_per_frame=args.speed,
                           **(params or {}), results=res)))

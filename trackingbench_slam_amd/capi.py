@@ -45,6 +45,7 @@ EXPORTS = [
     "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
     "tb_vo_create_ex", "tb_vo_tracker_state_dev", "tb_vo_mp_desc_dev", "tb_vo_map_state_dev",
     "tb_vocab_train", "tb_vocab_train_dev", "tb_vocab_info", "tb_vocab_export",
+    "tb_bow_vector_batch_dev", "tb_vo_create_bow", "tb_vo_bow_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -192,6 +193,7 @@ class VOParams(C.Structure):
 
 
 TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, TB_VO_PROJECTION_MAP = 0, 1, 2, 3, 4
+TB_VO_BOW = 5
 
 
 class VOTracker(C.Structure):
@@ -201,15 +203,24 @@ class VOTracker(C.Structure):
                 ("check_orientation", C.c_int), ("th_high", C.c_int), ("radio", C.c_float), ("map_keyframes", C.c_int)]
 
 
+class VOBow(C.Structure):
+    """tb_vo_bow of include/tb_capi.h"""
+    _fields_ = [("levelsup", C.c_int), ("map_point_only", C.c_int), ("th_low", C.c_int), ("nratio", C.c_float), ("histo_len", C.c_int),
+                ("check_orientation", C.c_int)]
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
-    tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL)."""
+    tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
+    bow (a VOBow) = tb_vo_create_bow with the vocabulary handle `vocab` of the same context, which the loop borrows."""
 
-    def __init__(self, ctx, params, nseq, tracker=None, use_ex=False):
+    def __init__(self, ctx, params, nseq, tracker=None, use_ex=False, bow=None, vocab=None):
         self.ctx = ctx
         self.nseq = int(nseq)
         self._h = C.c_void_p()
-        if tracker is None and not use_ex:
+        if bow is not None:
+            ctx.check(lib().tb_vo_create_bow(ctx._h, C.byref(params), C.byref(bow), vocab, self.nseq, C.byref(self._h)))
+        elif tracker is None and not use_ex:
             ctx.check(lib().tb_vo_create(ctx._h, C.byref(params), self.nseq, C.byref(self._h)))
         else:
             trp = C.byref(tracker) if tracker is not None else None
@@ -256,6 +267,15 @@ class VO:
         out = {k: q.value for k, q in zip(names, ptrs)}
         out["kf_frame"] = kf_frame.value
         return out
+
+    def bow_state_dev(self):
+        """dict of device pointers of a searchByBow loop's SetBow outputs: fv_keys, fv_counts, bv_words, bv_values, bv_counts,
+        word_ids, node_ids of the current frame and kf_* of the keyframe."""
+        names = ("fv_keys", "fv_counts", "bv_words", "bv_values", "bv_counts", "word_ids", "node_ids")
+        names = names + tuple("kf_" + n for n in names)
+        ptrs = [C.c_void_p() for _ in names]
+        self.ctx.check(lib().tb_vo_bow_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        return {k: q.value for k, q in zip(names, ptrs)}
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""
@@ -603,6 +623,20 @@ class Context:
         wid = np.zeros(max(n, 1), np.int32); wt = np.zeros(max(n, 1), np.float64); nid = np.zeros(max(n, 1), np.int32)
         self.check(lib().tb_bow_transform(self._h, vocab_handle, _p(d), n, int(levelsup), _p(wid), _p(wt), _p(nid)))
         return wid[:n], wt[:n], nid[:n]
+
+    def bow_vector_batch_dev(self, vocab_handle, word_ids, weights, counts):
+        """tb_bow_vector_batch_dev on torch tensors of this context's device: word_ids int32 / weights float64 [F, pitch] as
+        tb_bow_transform_batch_dev wrote them, counts int32 [F]. Returns (bv_words int32 [F, pitch], bv_values float64 [F, pitch],
+        bv_counts int32 [F]): per frame the BowVector as a list sorted by word id. Asynchronous on the context's stream."""
+        import torch
+        F, pitch = word_ids.shape
+        assert word_ids.dtype == torch.int32 and weights.dtype == torch.float64 and counts.dtype == torch.int32
+        assert weights.shape == (F, pitch) and counts.numel() == F and word_ids.is_contiguous() and weights.is_contiguous() and counts.is_contiguous()
+        bw = torch.zeros_like(word_ids); bv = torch.zeros_like(weights); bc = torch.zeros_like(counts)
+        self.check(lib().tb_bow_vector_batch_dev(self._h, vocab_handle, F, C.c_void_p(word_ids.data_ptr()), C.c_void_p(weights.data_ptr()),
+                                                 C.c_void_p(counts.data_ptr()), pitch, C.c_void_p(bw.data_ptr()), C.c_void_p(bv.data_ptr()),
+                                                 C.c_void_p(bc.data_ptr())))
+        return bw, bv, bc
 
     def reject_with_f_batch(self, cur, last, status, counts=None):
         """tb_reject_with_f_batch_dev on torch tensors of this context's device: cur / last float32 [P, N, 2], status uint8

@@ -767,6 +767,103 @@ k_bow_fv_sort(const int32_t* __restrict__ node_ids, const double* __restrict__ w
     if (tid == 0) fv_counts[f] = total;
 }
 
+/* The frame's BowVector (the other half of Frame::SetBow): TemplatedVocabulary::transform(features, v, fv, levelsup),
+ * TemplatedVocabulary.h:1124-1188, and BowVector::normalize, BowVector.cpp:57-80, as a sorted list -- word ids ascending (the
+ * std::map's order) and their values. One workgroup per frame:
+ *   1. (word << 32 | feature) keys of the features whose word is not stopped into LDS, bitonic sort (as k_bow_fv_sort);
+ *   2. a word = a run of equal upper halves; the thread that owns the run's first entry adds the run's weights in list order =
+ *      ascending feature index (TF, TF_IDF: addWeight) or keeps the first (IDF, BINARY: addIfNotExist); its slot in the output
+ *      is the number of run heads before it;
+ *   3. TF / TF_IDF with a scoring object that does not normalise: every value / (double)words. Otherwise the L1 or L2 norm, summed
+ *      by ONE thread in ascending word order (the values are doubles and must come out bit for bit: a tree would reorder the
+ *      sum), sqrt for L2, and every value / norm when norm > 0.
+ * Every statement is one rounding (the library is built with -ffp-contract=off). The chain of step 3 is at most 8192 dependent
+ * adds per frame; frames run in parallel. */
+__global__ void __launch_bounds__(1024)
+k_bow_vector(const int32_t* __restrict__ word_ids, const double* __restrict__ weights, const int32_t* __restrict__ counts, int desc_pitch,
+             int weighting, int scoring, int32_t* __restrict__ bv_words, double* __restrict__ bv_values, int32_t* __restrict__ bv_counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];
+    __shared__ int wsum[16];
+    __shared__ double s_norm;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int n = counts ? min(max(counts[f], 0), desc_pitch) : desc_pitch;
+    const size_t base = (size_t)f * desc_pitch;
+    int m = 1;
+    while (m < n) m <<= 1;
+    int mine = 0;
+    for (int i = tid; i < m; i += 1024) {
+        unsigned long long k = ~0ull;
+        if (i < n && weights[base + i] > 0) { k = ((unsigned long long)(unsigned)word_ids[base + i] << 32) | (unsigned)i; mine++; }
+        sk[i] = k;
+    }
+    mine = tb_wave_sum(mine);
+    if ((tid & 63) == 0) wsum[tid >> 6] = mine;
+    __syncthreads();
+    for (int k2 = 2; k2 <= m; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < m; i += 1024) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long x = sk[i], y = sk[l];
+                    const bool up = (i & k2) == 0;
+                    if ((x > y) == up) { sk[i] = y; sk[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    int total = 0;
+    for (int w = 0; w < 16; w++) total += wsum[w];
+    __syncthreads();   /* wsum is reused below */
+    /* run heads of this thread's contiguous chunk, their rank among all heads */
+    const int per = (total + 1023) / 1024;
+    const int beg = min(tid * per, total), end = min(beg + per, total);
+    int heads = 0;
+    for (int j = beg; j < end; j++) heads += (j == 0 || (unsigned)(sk[j] >> 32) != (unsigned)(sk[j - 1] >> 32)) ? 1 : 0;
+    const int incl = tb_wave_incl_scan(heads);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    int slot = incl - heads, nwords = 0;
+    for (int w = 0; w < 16; w++) {
+        if (w < (tid >> 6)) slot += wsum[w];
+        nwords += wsum[w];
+    }
+    const bool add = weighting == 0 || weighting == 1;   /* TF_IDF, TF */
+    for (int j = beg; j < end; j++) {
+        const unsigned word = (unsigned)(sk[j] >> 32);
+        if (j != 0 && word == (unsigned)(sk[j - 1] >> 32)) continue;
+        double v = weights[base + (unsigned)sk[j]];
+        if (add)
+            for (int q = j + 1; q < total && (unsigned)(sk[q] >> 32) == word; q++) v = v + weights[base + (unsigned)sk[q]];
+        bv_words[base + slot] = (int32_t)word;
+        bv_values[base + slot] = v;
+        slot++;
+    }
+    __syncthreads();   /* the keys are dead; this block's bv_values are visible to it */
+    double* vals = reinterpret_cast<double*>(sk);
+    for (int i = tid; i < nwords; i += 1024) vals[i] = bv_values[base + i];
+    __syncthreads();
+    const bool must = scoring != 5, l2 = scoring == 1;   /* DOT_PRODUCT does not normalise; L2_NORM */
+    double div = 0.0;
+    if (!must) {
+        if (add) div = (double)nwords;
+    } else {
+        if (tid == 0) {
+            double norm = 0.0;
+            if (l2)
+                for (int i = 0; i < nwords; i++) { const double sq = vals[i] * vals[i]; norm = norm + sq; }
+            else
+                for (int i = 0; i < nwords; i++) norm = norm + fabs(vals[i]);
+            if (l2) norm = sqrt(norm);
+            s_norm = norm;
+        }
+        __syncthreads();
+        div = s_norm;
+    }
+    if (div > 0.0)
+        for (int i = tid; i < nwords; i += 1024) bv_values[base + i] = vals[i] / div;
+    if (tid == 0) bv_counts[f] = nwords;
+}
+
 /* Batched searchByBow, search stage: one thread per entry of F1's feature vector (= the reference's emission order once the
  * entries of nodes F2 does not have are dropped): the node's entries of F2 by binary search, then best / second best Hamming
  * distance in list order (matcher.cpp:645-669). best[pos] = {bestDist1, bestDist2, bestIdx2, 1 if F2 has the node}. */
@@ -911,6 +1008,21 @@ int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_sta
         tb_prof_end(ctx);
         TB_HIP(ctx, hipGetLastError());
     }
+    return TB_OK;
+}
+
+int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const double* d_weights, const int32_t* d_counts, int desc_pitch,
+                   int weighting, int scoring, int32_t* d_bv_words, double* d_bv_values, int32_t* d_bv_counts) {
+    if (nframes <= 0 || desc_pitch <= 0) return TB_OK;
+    int m = 1;
+    while (m < desc_pitch) m <<= 1;
+    const size_t lds = (size_t)m * sizeof(unsigned long long);
+    TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    tb_prof_begin(ctx, "k_bow_vector");
+    hipLaunchKernelGGL(k_bow_vector, dim3(nframes), dim3(1024), lds, ctx->stream, d_word_ids, d_weights, d_counts, desc_pitch, weighting,
+                       scoring, d_bv_words, d_bv_values, d_bv_counts);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
     return TB_OK;
 }
 

@@ -1132,6 +1132,17 @@ int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, co
                              (unsigned long long*)fv_keys, fv_counts);
 }
 
+int tb_bow_vector_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const int32_t* word_ids, const double* weights,
+                            const int32_t* counts, int desc_pitch, int32_t* bv_words, double* bv_values, int32_t* bv_counts) {
+    TB_ENTER(ctx);
+    if (!ctx || !voc || voc->ctx != ctx || nframes < 0 || desc_pitch < 0 || desc_pitch > 8192) return TB_EINVAL;
+    if (voc->weighting < 0 || voc->weighting > 3 || voc->scoring < 0 || voc->scoring > 5)
+        return tb_fail(ctx, TB_EINVAL, "tb_bow_vector_batch_dev: the vocabulary's weighting %d / scoring %d", voc->weighting, voc->scoring);
+    if (nframes == 0 || desc_pitch == 0) return TB_OK;
+    if (!word_ids || !weights || !counts || !bv_words || !bv_values || !bv_counts) return TB_EINVAL;
+    return tbk_bow_vector(ctx, nframes, word_ids, weights, counts, desc_pitch, voc->weighting, voc->scoring, bv_words, bv_values, bv_counts);
+}
+
 int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int n, int levelsup, int32_t* word_ids, double* weights,
                      int32_t* node_ids) {
     TB_ENTER(ctx);
@@ -1860,6 +1871,17 @@ struct tb_vo {
     uint8_t* map_desc[2] = {nullptr, nullptr};      /* [nseq][map_cap][32] */
     int32_t* map_n[2] = {nullptr, nullptr};         /* [nseq] live counts */
     int32_t* map_blocks[2] = {nullptr, nullptr};    /* [nseq][mapK] points per held keyframe, oldest first */
+    /* searchByBow (TB_VO_BOW): the borrowed vocabulary, Frame::SetBow's outputs of the current frame ([0]) and the keyframe ([1]) */
+    tb_vo_bow bw;
+    const tb_vocab* voc = nullptr;
+    double* bow_wt = nullptr;                       /* [nseq][P] word weights of the current frame */
+    int32_t* bow_word[2] = {nullptr, nullptr};      /* [nseq][P] word ids */
+    int32_t* bow_node[2] = {nullptr, nullptr};      /* [nseq][P] node ids */
+    uint64_t* fv_keys[2] = {nullptr, nullptr};      /* [nseq][P] FeatureVector keys */
+    int32_t* fv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
+    int32_t* bv_word[2] = {nullptr, nullptr};       /* [nseq][P] BowVector words */
+    double* bv_val[2] = {nullptr, nullptr};         /* [nseq][P] BowVector values */
+    int32_t* bv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -1881,10 +1903,16 @@ void tb_vo_destroy(tb_vo* vo) {
     for (int k = 0; k < 2; k++) {
         hipFree(vo->map_rec[k]); hipFree(vo->map_desc[k]); hipFree(vo->map_n[k]); hipFree(vo->map_blocks[k]);
     }
+    hipFree(vo->bow_wt);
+    for (int k = 0; k < 2; k++) {
+        hipFree(vo->bow_word[k]); hipFree(vo->bow_node[k]); hipFree(vo->fv_keys[k]); hipFree(vo->fv_cnt[k]); hipFree(vo->bv_word[k]);
+        hipFree(vo->bv_val[k]); hipFree(vo->bv_cnt[k]);
+    }
     delete vo;
 }
 
-static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out) {
+static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out, const tb_vo_bow* bow = nullptr,
+                     const tb_vocab* voc = nullptr) {
     if (!ctx || !p || !out) return TB_EINVAL;
     *out = nullptr;
     if (nseq < 1 || p->width < 1 || p->height < 1 || p->nlevels < 2 || p->nlevels > TB_MAX_LEVELS || !(p->scale > 0.f && p->scale < 1.f) ||
@@ -1901,10 +1929,14 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     vo->nseq = nseq;
     memset(&vo->tr, 0, sizeof vo->tr);
     if (tr) vo->tr = *tr;
+    memset(&vo->bw, 0, sizeof vo->bw);
+    if (bow) { vo->bw = *bow; vo->voc = voc; }
     int rc = tb_extractor_create(ctx, p->width, p->height, p->nlevels, sf.data(), nullptr, nullptr, nseq, p->target, &vo->ex);
     if (rc) return rc;
     vo->P = vo->ex->g.selCap;
     vo->Mcap = vo->P;
+    if (bow && vo->P > 8192)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_bow: %d keys per frame (the transform sorts at most 8192)", vo->P);
     if (vo->tr.kind == TB_VO_PROJECTION_MAP) {
         if ((size_t)vo->tr.map_keyframes * (size_t)vo->P > (size_t)INT32_MAX / 64)
             return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: map_keyframes %d x %d keys is too large", vo->tr.map_keyframes, vo->P);
@@ -1976,6 +2008,22 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
             return rc;
         }
     }
+    if (bow) {
+        /* every output of the transform is a buffer of the loop, so tb_bow_transform_batch_dev takes no scratch; the matcher's
+         * best rows (WORK) were sized above */
+        TB_HIP(ctx, hipMalloc(&vo->bow_wt, S * P * sizeof(double)));
+        for (int k = 0; k < 2; k++) {
+            TB_HIP(ctx, hipMalloc(&vo->bow_word[k], S * P * sizeof(int32_t)));
+            TB_HIP(ctx, hipMalloc(&vo->bow_node[k], S * P * sizeof(int32_t)));
+            TB_HIP(ctx, hipMalloc(&vo->fv_keys[k], S * P * sizeof(uint64_t)));
+            TB_HIP(ctx, hipMalloc(&vo->fv_cnt[k], S * sizeof(int32_t)));
+            TB_HIP(ctx, hipMalloc(&vo->bv_word[k], S * P * sizeof(int32_t)));
+            TB_HIP(ctx, hipMalloc(&vo->bv_val[k], S * P * sizeof(double)));
+            TB_HIP(ctx, hipMalloc(&vo->bv_cnt[k], S * sizeof(int32_t)));
+            TB_HIP(ctx, hipMemsetAsync(vo->fv_cnt[k], 0, S * sizeof(int32_t), ctx->stream));
+            TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[k], 0, S * sizeof(int32_t), ctx->stream));
+        }
+    }
     if (vo_is_proj(vo)) {
         for (int l = 0; l < p->nlevels; l++) vo->sf[l] = sf[l];
         TB_HIP(ctx, hipMalloc(&vo->cell_start, S * 4321 * sizeof(int32_t)));
@@ -2014,6 +2062,7 @@ int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr,
     if (!ctx || !p || !out) return TB_EINVAL;
     *out = nullptr;
     if (tr && tr->kind != TB_VO_OPFLOW) {
+        if (tr->kind == TB_VO_BOW) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: TB_VO_BOW needs a vocabulary, use tb_vo_create_bow");
         if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE && tr->kind != TB_VO_PROJECTION && tr->kind != TB_VO_PROJECTION_MAP)
             return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
         if (tr->kind == TB_VO_PROJECTION || tr->kind == TB_VO_PROJECTION_MAP) {
@@ -2038,6 +2087,26 @@ int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr,
     return vo_create(ctx, p, tr && tr->kind != TB_VO_OPFLOW ? tr : nullptr, nseq, out);
 }
 
+int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_bow* bow, const tb_vocab* voc, int nseq, tb_vo** out) {
+    TB_ENTER(ctx);
+    if (out) *out = nullptr;
+    if (!p || !out || !bow) return TB_EINVAL;
+    if (bow->histo_len < 1 || bow->histo_len > 1024 || bow->levelsup < 0 || bow->th_low < 0 || !std::isfinite(bow->nratio)) {
+        if (!ctx) return TB_EINVAL;
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: searchByBow arguments (levelsup %d, th_low %d, nratio %g, histo_len %d)",
+                       bow->levelsup, bow->th_low, (double)bow->nratio, bow->histo_len);
+    }
+    if (!ctx) return TB_EINVAL;
+    if (!voc || voc->ctx != ctx) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: a vocabulary of this context is required");
+    if (voc->weighting < 0 || voc->weighting > 3 || voc->scoring < 0 || voc->scoring > 5)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: the vocabulary's weighting %d / scoring %d", voc->weighting, voc->scoring);
+    tb_vo_tracker tr;
+    memset(&tr, 0, sizeof tr);
+    tr.kind = TB_VO_BOW;
+    tr.th_low = bow->th_low; tr.nratio = bow->nratio; tr.histo_len = bow->histo_len; tr.check_orientation = bow->check_orientation;
+    return vo_create(ctx, p, &tr, nseq, out, bow, voc);
+}
+
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     TB_ENTER((vo ? vo->ctx : nullptr));
     if (!vo || !Tcw0) return TB_EINVAL;
@@ -2048,6 +2117,10 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     if (vo->tr.kind != TB_VO_OPFLOW) {   /* no keyframe yet */
         TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
         vo->kf_frame = -1;
+    }
+    if (vo->tr.kind == TB_VO_BOW) {
+        TB_HIP(ctx, hipMemsetAsync(vo->fv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
     }
     if (vo->mapK) {   /* an empty map */
         TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
@@ -2072,11 +2145,26 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
     if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
     if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
     if ((rc = tb_extractor_copy_results_dev(vo->ex, S, vo->orb, vo->orb_desc, vo->orb_cnt, P))) return rc;
+    if (tr.kind == TB_VO_BOW) {
+        /* :705 cur_frame_ptr->SetBow(vocabulary) on every frame: voc->transform(descriptors, mBowVec, mFeatVec, levelsup) */
+        if ((rc = tb_bow_transform_batch_dev(ctx, vo->voc, S, vo->orb_desc, vo->orb_cnt, P, vo->bw.levelsup, vo->bow_word[0], vo->bow_node[0],
+                                             vo->bow_wt, vo->fv_keys[0], vo->fv_cnt[0])))
+            return rc;
+        if ((rc = tb_bow_vector_batch_dev(ctx, vo->voc, S, vo->bow_word[0], vo->bow_wt, vo->orb_cnt, P, vo->bv_word[0], vo->bv_val[0],
+                                          vo->bv_cnt[0])))
+            return rc;
+    }
     if (t == 0) {
         TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, (size_t)S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+    } else if (tr.kind == TB_VO_BOW) {
+        /* searchByBow(cur, key_frame, MapPointOnly): F1 = the current frame, F2 = the keyframe, whose map points are has_mp2 */
+        if ((rc = tb_search_by_bow_batch_dev(ctx, S, vo->orb, vo->orb_desc, P, vo->fv_keys[0], vo->fv_cnt[0], vo->kf_orb, vo->kf_desc, P,
+                                             vo->fv_keys[1], vo->fv_cnt[1], vo->kf_valid, vo->bw.map_point_only, tr.th_low, tr.nratio,
+                                             tr.histo_len, tr.check_orientation, vo->matches, P, vo->mcounts, vo->mflags)))
+            return rc;
     } else if (tr.kind == TB_VO_BF) {
         /* :712 searchByBF(cur, key_frame, 0, nLevels, ratio, minTh): the whole-set branch */
         if ((rc = tb_search_by_bf_batch_dev(ctx, S, vo->orb_desc, vo->orb_cnt, vo->kf_desc, vo->kf_cnt, (size_t)P * 32, tr.bf_ratio,
@@ -2115,6 +2203,15 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
         if (tr.kind == TB_VO_VIOLENCE &&
             (rc = tb_frame_grid_batch_dev(ctx, S, vo->kf_orb, vo->kf_cnt, P, W, H, vo->kf_cell_start, vo->kf_cell_items)))
             return rc;
+        if (tr.kind == TB_VO_BOW) {   /* the keyframe keeps the vectors SetBow gave it: they are not computed again */
+            TB_HIP(ctx, hipMemcpyAsync(vo->bow_word[1], vo->bow_word[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->bow_node[1], vo->bow_node[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->fv_keys[1], vo->fv_keys[0], SP * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->fv_cnt[1], vo->fv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->bv_word[1], vo->bv_word[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->bv_val[1], vo->bv_val[0], SP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            TB_HIP(ctx, hipMemcpyAsync(vo->bv_cnt[1], vo->bv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        }
         vo->kf_frame = t;
     }
     return TB_OK;
@@ -2300,6 +2397,30 @@ int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** 
     if (kf_mp_valid) *kf_mp_valid = vo->kf_valid;
     if (kf_counts) *kf_counts = vo->kf_cnt;
     if (kf_frame) *kf_frame = vo->kf_frame;
+    return TB_OK;
+}
+
+int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_counts, const int32_t** bv_words, const double** bv_values,
+                        const int32_t** bv_counts, const int32_t** word_ids, const int32_t** node_ids, const uint64_t** kf_fv_keys,
+                        const int32_t** kf_fv_counts, const int32_t** kf_bv_words, const double** kf_bv_values, const int32_t** kf_bv_counts,
+                        const int32_t** kf_word_ids, const int32_t** kf_node_ids) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (vo->tr.kind != TB_VO_BOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_state_dev: the loop does not track by searchByBow");
+    if (fv_keys) *fv_keys = vo->fv_keys[0];
+    if (fv_counts) *fv_counts = vo->fv_cnt[0];
+    if (bv_words) *bv_words = vo->bv_word[0];
+    if (bv_values) *bv_values = vo->bv_val[0];
+    if (bv_counts) *bv_counts = vo->bv_cnt[0];
+    if (word_ids) *word_ids = vo->bow_word[0];
+    if (node_ids) *node_ids = vo->bow_node[0];
+    if (kf_fv_keys) *kf_fv_keys = vo->fv_keys[1];
+    if (kf_fv_counts) *kf_fv_counts = vo->fv_cnt[1];
+    if (kf_bv_words) *kf_bv_words = vo->bv_word[1];
+    if (kf_bv_values) *kf_bv_values = vo->bv_val[1];
+    if (kf_bv_counts) *kf_bv_counts = vo->bv_cnt[1];
+    if (kf_word_ids) *kf_word_ids = vo->bow_word[1];
+    if (kf_node_ids) *kf_node_ids = vo->bow_node[1];
     return TB_OK;
 }
 

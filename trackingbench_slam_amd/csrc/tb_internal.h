@@ -209,6 +209,8 @@ int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_sta
                       const int32_t* d_word_id, const double* d_weight, int nframes, const uint8_t* d_desc, const int32_t* d_counts,
                       int desc_pitch, int levelsup, int32_t* d_word_ids, int32_t* d_node_ids, double* d_weights,
                       unsigned long long* d_fv_keys, int32_t* d_fv_counts);
+int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const double* d_weights, const int32_t* d_counts, int desc_pitch,
+                   int weighting, int scoring, int32_t* d_bv_words, double* d_bv_values, int32_t* d_bv_counts);
 int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, int pitch1, const unsigned long long* d_fv1,
                          const int32_t* d_n1, const tb_keypoint* d_k2, const uint8_t* d_d2, int pitch2, const unsigned long long* d_fv2,
                          const int32_t* d_n2, const uint8_t* d_has_mp2, int map_point_only, int th_low, float nratio, int histo_len,

@@ -13,6 +13,11 @@ every frame, searchByBF / searchByViolence against the last keyframe, the keyfra
 searchByProjection of the keyframe's map points, or of a device-resident map the keyframes add their points to, into the
 current frame's lookup grid. The map holds the points of the last `map_keyframes` keyframes.
 
+`tracker="bow", vocab=...` runs the fourth tracking line, searchByBow (test_vo.cpp:711) against the keyframe, with Frame::SetBow
+(:705) on the device for every frame: the DBoW2 transform, the FeatureVector keys and the BowVector. `vocab` is a
+synth.Vocabulary (uploaded and owned by the loop), a callable `f(context) -> handle` (e.g. one that trains with
+`context.vocab_train_dev`; the loop owns the handle), or a handle made on the `context=` the loop was given (borrowed).
+
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
 """
@@ -41,16 +46,23 @@ TRACKER_DEFAULTS = {
     "projection": dict(nratio=30.0, th_high=50, histo_len=30, check_orientation=True),
     # :516-517 setProjectionParam(30, 50, 30, true, 20); searchByProjection(map, cur, 0.6); map_keyframes: include/tb_capi.h
     "projection_map": dict(nratio=20.0, radio=0.6, th_high=50, histo_len=30, check_orientation=True, map_keyframes=4),
+    # :706 setBowParam(50, 100, 30, true, 6); :711 searchByBow(cur, key_frame, true); Frame.cpp:269 levelsup 4
+    "bow": dict(levelsup=4, map_point_only=True, th_low=50, nratio=6.0, histo_len=30, check_orientation=True),
 }
+# test_vo_1's searchByBow arguments (:207 setBowParam(30, ..., 5), :212 MapPointOnly false)
+BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
 
 def _tracker(kind, nlevels, params):
     if kind not in TRACKER_DEFAULTS:
-        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence', 'projection', 'projection_map'" % (kind,))
+        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence', 'projection', 'projection_map', 'bow'" % (kind,))
     unknown = set(params) - set(TRACKER_DEFAULTS[kind])
     if unknown:
         raise TypeError("tracker %r takes no parameter %s" % (kind, ", ".join(sorted(unknown))))
     q = dict(TRACKER_DEFAULTS[kind], **params)
+    if kind == "bow":
+        return capi.VOBow(int(q["levelsup"]), int(bool(q["map_point_only"])), int(q["th_low"]), float(q["nratio"]), int(q["histo_len"]),
+                          int(bool(q["check_orientation"])))
     t = capi.VOTracker()
     if kind in ("projection", "projection_map"):
         t.kind = capi.TB_VO_PROJECTION if kind == "projection" else capi.TB_VO_PROJECTION_MAP
@@ -73,16 +85,26 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
+        if tracker == "bow" and vocab is None:
+            raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
+        if tracker != "bow" and vocab is not None:
+            raise TypeError("tracker %r takes no vocabulary" % (tracker,))
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
         self.S, self.width, self.height = int(nseq), int(width), int(height)
         self.keyframe_every = int(keyframe_every)
         # the context runs on a torch stream of its own (pipeline.py: handle 0 would mean "the context's own stream")
         self.stream = torch.cuda.Stream(device=self.dev)
-        self.ctx = capi.Context(device, stream=self.stream.cuda_stream)
+        # context=: the caller's capi.Context (e.g. the one a vocabulary was trained on); it is moved onto the loop's stream and
+        # stays the caller's to close
+        self._own_ctx = context is None
+        self.ctx = capi.Context(device, stream=self.stream.cuda_stream) if context is None else context
+        if context is not None:
+            context.set_stream(self.stream.cuda_stream)
+        self.vocab, self._own_vocab = None, False
         prm = capi.VOParams(self.width, self.height, int(nlevels), float(scale), int(target), float(init_th), float(min_th),
                             (C.c_double * 4)(*[float(k) for k in K]), float(bf), self.keyframe_every)
         self.params, self.tracker = prm, tracker
@@ -90,10 +112,22 @@ class StereoVO:
             self.vo = capi.VO(self.ctx, prm, self.S)
         else:
             try:
-                self.vo = capi.VO(self.ctx, prm, self.S, _tracker(tracker, nlevels, tracker_params))
+                trk = _tracker(tracker, nlevels, tracker_params)
+                if tracker == "bow":
+                    if hasattr(vocab, "c"):           # a synth.Vocabulary: upload it
+                        self.vocab, self._own_vocab = self.ctx.vocab_create(vocab), True
+                    elif callable(vocab):
+                        self.vocab, self._own_vocab = vocab(self.ctx), True
+                    elif context is None:
+                        raise ValueError("a vocabulary handle belongs to a context: pass that context as context=")
+                    else:
+                        self.vocab = vocab
+                    self.vo = capi.VO(self.ctx, prm, self.S, bow=trk, vocab=self.vocab)
+                else:
+                    self.vo = capi.VO(self.ctx, prm, self.S, trk)
             except Exception:
-                self.ctx.close()
-                self.ctx = None
+                self.vo = None
+                self.close()
                 raise
         self._Tcw0 = None
         self.frame = -1
@@ -103,7 +137,11 @@ class StereoVO:
             self.vo.close()
             self.vo = None
         if getattr(self, "ctx", None) is not None:
-            self.ctx.close()
+            if getattr(self, "vocab", None) is not None and self._own_vocab:   # after the loop that borrowed it
+                self.ctx.vocab_destroy(self.vocab)
+            self.vocab = None
+            if self._own_ctx:
+                self.ctx.close()
             self.ctx = None
 
     def _enter(self, *tensors):
@@ -241,6 +279,28 @@ class StereoVO:
                     counts=self._pget(m["counts"], (self.S,), "<i4", torch.int32),
                     block_counts=self._pget(m["block_counts"], (self.S, K), "<i4", torch.int32),
                     capacity=Cp, map_keyframes=K, blocks=m["blocks"])
+
+    # ---- searchByBow (tracker "bow"): Frame::SetBow's outputs
+    def _bow(self, names):
+        d = self.vo.bow_state_dev()
+        P = self.key_pitch
+        spec = dict(fv_keys=((self.S, P), "<i8", torch.int64), bv_words=((self.S, P), "<i4", torch.int32),
+                    bv_values=((self.S, P), "<f8", torch.float64), word_ids=((self.S, P), "<i4", torch.int32),
+                    node_ids=((self.S, P), "<i4", torch.int32), fv_counts=((self.S,), "<i4", torch.int32),
+                    bv_counts=((self.S,), "<i4", torch.int32))
+        out = {}
+        for pre in ("", "kf_"):
+            out[pre or "cur"] = {n: self._pget(d[pre + n], *spec[n]) for n in names}
+        return out["cur"], out["kf_"]
+
+    def feature_vector(self):
+        """(current frame, keyframe): each dict(fv_keys [S, P] int64 = node id << 32 | key index, ascending -- the FeatureVector's
+        nodes in map order with every node's keys in insertion order --, fv_counts [S], word_ids [S, P], node_ids [S, P] per key)"""
+        return self._bow(("fv_keys", "fv_counts", "word_ids", "node_ids"))
+
+    def bow_vector(self):
+        """(current frame, keyframe): each dict(bv_words [S, P] int32 ascending, bv_values [S, P] float64, bv_counts [S])"""
+        return self._bow(("bv_words", "bv_values", "bv_counts"))
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
