@@ -263,9 +263,62 @@ int tb_bow_transform_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, co
  *    order by one thread and applied only when it is greater than 0.
  * Weighting and scoring are the tb_vocab's. The values are doubles and come out bit for bit as DBoW2's: one operation per
  * statement, no FMA, no tree reduction. Device pointers, asynchronous on the context's stream; desc_pitch <= 8192; null or
- * inconsistent arguments are TB_EINVAL. Scoring two vectors (ScoringObject::score) stays outside this library. */
+ * inconsistent arguments are TB_EINVAL. Two such vectors are scored by tb_bow_score* below. */
 int tb_bow_vector_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const int32_t* word_ids, const double* weights,
                             const int32_t* counts, int desc_pitch, int32_t* bv_words, double* bv_values, int32_t* bv_counts);
+/* Scoring two BowVectors -- TemplatedVocabulary::score(v1, v2) (third_part/DBoW2/DBoW2/TemplatedVocabulary.h:156-162, :1199-1203),
+ * which forwards to the vocabulary's scoring object (ScoringObject.cpp:23-311). A vector is the sorted list tb_bow_vector_batch_dev
+ * writes: words ascending, values beside them. `scoring` is the code of tb_vocabulary (tb_types.h). One term per common word,
+ * added in ascending word order into one accumulator that starts at 0, then the closing formula:
+ *   0 L1_NORM        fabs(vi - wi) - fabs(vi) - fabs(wi)            -score / 2.0                                  (:23-68)
+ *   1 L2_NORM        vi * wi                                        score >= 1 ? 1.0 : 1.0 - sqrt(1.0 - score)    (:73-120)
+ *   2 CHI_SQUARE     vi * wi / (vi + wi) where vi + wi != 0.0       2. * score                                    (:125-170)
+ *   3 KL             vi * log(vi / wi) where both are non-zero; a word of v1 alone that lies before a word of v2 adds
+ *                    vi * (log(vi) - LOG_EPS), and so does one past v2's last word when vi != 0; LOG_EPS = log(DBL_EPSILON)
+ *                    (:18, :175-221). Not symmetric: v1 (a) is the query. Lower is more similar; for the other five, higher
+ *   4 BHATTACHARYYA  sqrt(vi * wi)                                                                                (:226-266)
+ *   5 DOT_PRODUCT    vi * wi                                                                                      (:271-311)
+ * Codes 0, 1, 2, 4, 5 come out bit for bit on the host and on the device: one rounding per statement, IEEE division and sqrt, the
+ * terms of a pair computed in parallel and added serially in word order (no tree, no per-lane partial sums). KL keeps the order;
+ * its log is the C library's on the host and the device library's on the device.
+ * tb_bow_score: host pointers, no context, plain C++ built with contraction off: one pair. na / nb >= 0 (a null list needs
+ * a count of 0).
+ * tb_bow_score_batch_dev: device pointers, lists [n][pitch] with counts [n] (clamped to 0 .. pitch), asynchronous on the
+ * context's stream. mode TB_SCORE_PAIRWISE: na == nb, out[i] = score(a_i, b_i); TB_SCORE_ALL_PAIRS: out[i * nb + j] =
+ * score(a_i, b_j). Pitches in 1..8192 (a query is staged in LDS). TB_EINVAL: null or inconsistent arguments, scoring outside
+ * 0..5, another mode, a pitch out of range. */
+enum { TB_SCORE_PAIRWISE = 0, TB_SCORE_ALL_PAIRS = 1 };
+int tb_bow_score(int scoring, const int32_t* a_words, const double* a_values, int na, const int32_t* b_words, const double* b_values,
+                 int nb, double* out);
+int tb_bow_score_batch_dev(tb_ctx* ctx, int scoring, int mode, int na, const int32_t* a_words, const double* a_values,
+                           const int32_t* a_counts, int a_pitch, int nb, const int32_t* b_words, const double* b_values,
+                           const int32_t* b_counts, int b_pitch, double* out);
+/* A device-resident keyframe database: per sequence a ring of the last `capacity` keyframes' BowVectors, scored by
+ * TemplatedVocabulary::score as above. (DBoW2's TemplatedDatabase and its inverted index are not part of the reference's tree:
+ * a query scores every held entry.) All nseq sequences step together.
+ *   add    add number a (0, 1, ...) puts sequence s's vector (bv_* [nseq][src_pitch], bv_counts [nseq]) into slot a % capacity
+ *          of every sequence, overwriting the oldest, with kf_id (>= 0). The host counts the adds, so nothing is read back
+ *   query  q_* [nseq][q_pitch]: sequence s's query is v1, scored against the slots of its own ring into scores [nseq][capacity].
+ *          A slot that is empty, or among the exclude_newest most recent adds, is not ranked and its score is a quiet NaN.
+ *          top_slot / top_kf / top_score [nseq][topk] list the best min(topk, ranked) slots, best first: descending score
+ *          (ascending for KL), ties to the lower kf_id, then to the lower slot; the unused tail holds -1 (top_score: a quiet
+ *          NaN, as in scores); top_count [nseq] (nullable) = the entries listed. With topk 0 the top_* arrays may be NULL
+ *   state  device views: words / values [nseq][capacity][pitch], counts and kf_ids [nseq][capacity] (-1 = empty), *nadded
+ * Add, query and clear are asynchronous on the context's stream and make no host <-> device copy. The database must be
+ * destroyed before its context. TB_EINVAL: null or inconsistent arguments, scoring outside 0..5, nseq < 1, capacity outside
+ * 1..1024, pitch outside 1..8192, kf_id < 0, topk < 0 or > capacity, exclude_newest < 0, a source or query pitch < 1 or larger
+ * than the database's. */
+typedef struct tb_bow_db tb_bow_db;
+int tb_bow_db_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int scoring, tb_bow_db** out);
+void tb_bow_db_destroy(tb_bow_db* db);
+int tb_bow_db_clear(tb_bow_db* db);
+int tb_bow_db_add_dev(tb_bow_db* db, const int32_t* bv_words, const double* bv_values, const int32_t* bv_counts, int src_pitch,
+                      int32_t kf_id);
+int tb_bow_db_query_dev(tb_bow_db* db, const int32_t* q_words, const double* q_values, const int32_t* q_counts, int q_pitch,
+                        int exclude_newest, int topk, double* scores, int32_t* top_slot, int32_t* top_kf, double* top_score,
+                        int32_t* top_count);
+int tb_bow_db_state_dev(tb_bow_db* db, const int32_t** words, const double** values, const int32_t** counts, const int32_t** kf_ids,
+                        int* nadded);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -598,6 +651,15 @@ int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_
                         const int32_t** bv_counts, const int32_t** word_ids, const int32_t** node_ids, const uint64_t** kf_fv_keys,
                         const int32_t** kf_fv_counts, const int32_t** kf_bv_words, const double** kf_bv_values, const int32_t** kf_bv_counts,
                         const int32_t** kf_word_ids, const int32_t** kf_node_ids);
+/* The keyframe database of a TB_VO_BOW loop (off unless enabled): tb_vo_bow_db_enable creates a tb_bow_db of nseq rings of
+ * `capacity` slots, pitch = the loop's key pitch, scoring = the vocabulary's. From then on every keyframe step adds the keyframe's
+ * BowVector -- the one its snapshot holds -- with kf_id = the frame's index, after the snapshot, and tb_vo_reset_dev clears the
+ * database; a step still makes no host synchronisation and no host <-> device copy. TB_ESTATE: another tracker, after the first
+ * step, or enabled already; capacity outside 1..1024 is TB_EINVAL. tb_vo_bow_db_get lends the database (tb_bow_db_query_dev with
+ * tb_vo_bow_state_dev's bv_* as the query, tb_bow_db_state_dev); it belongs to the loop and goes with it. TB_ESTATE when the
+ * database is not enabled. */
+int tb_vo_bow_db_enable(tb_vo* vo, int capacity);
+int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

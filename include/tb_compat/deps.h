@@ -65,6 +65,10 @@ public:
     /* the line format loadFromTextFile reads (TemplatedVocabulary.h:1429-1449); weights with 17 significant digits, so the
      * file gives back the same doubles (the reference prints 6) */
     void saveToTextFile(const std::string& filename) const;
+    /* TemplatedVocabulary::score (TemplatedVocabulary.h:156-162, :1199-1203): the vocabulary's scoring object on two vectors
+     * (ScoringObject.cpp:23-311), v1 first -- KL is not symmetric. Host arithmetic (tb_bow_score); throws std::runtime_error
+     * when the vocabulary's scoring code is none of the six. */
+    double score(const DBoW2::BowVector& v1, const DBoW2::BowVector& v2) const;
     bool empty() const { return word_id.size() <= 1; }
     unsigned int size() const { return nwords; }            /* number of words */
     int getBranchingFactor() const { return k; }

@@ -46,9 +46,12 @@ EXPORTS = [
     "tb_vo_create_ex", "tb_vo_tracker_state_dev", "tb_vo_mp_desc_dev", "tb_vo_map_state_dev",
     "tb_vocab_train", "tb_vocab_train_dev", "tb_vocab_info", "tb_vocab_export",
     "tb_bow_vector_batch_dev", "tb_vo_create_bow", "tb_vo_bow_state_dev",
+    "tb_bow_score", "tb_bow_score_batch_dev", "tb_bow_db_create", "tb_bow_db_destroy", "tb_bow_db_clear", "tb_bow_db_add_dev",
+    "tb_bow_db_query_dev", "tb_bow_db_state_dev", "tb_vo_bow_db_enable", "tb_vo_bow_db_get",
 ]
 
 TB_VOC_MAX_L = 8
+TB_SCORE_PAIRWISE, TB_SCORE_ALL_PAIRS = 0, 1
 
 
 class VocabTrainParams(C.Structure):
@@ -105,6 +108,8 @@ def lib():
         L.tb_extractor_destroy.argtypes = [C.c_void_p]
         L.tb_vo_destroy.restype = None
         L.tb_vo_destroy.argtypes = [C.c_void_p]
+        L.tb_bow_db_destroy.restype = None
+        L.tb_bow_db_destroy.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -276,6 +281,20 @@ class VO:
         ptrs = [C.c_void_p() for _ in names]
         self.ctx.check(lib().tb_vo_bow_state_dev(self._h, *[C.byref(q) for q in ptrs]))
         return {k: q.value for k, q in zip(names, ptrs)}
+
+    def bow_db_enable(self, capacity):
+        """tb_vo_bow_db_enable: returns the status code (0 or a negative TB_E* code), so the state checks can be tested."""
+        rc = lib().tb_vo_bow_db_enable(self._h, int(capacity))
+        if rc == 0:
+            self._db_capacity = int(capacity)
+        return rc
+
+    def bow_db(self):
+        """tb_vo_bow_db_get: the loop's keyframe database as a borrowed BowDatabase (TB_ESTATE when it is not enabled); its pitch
+        is the loop's key pitch."""
+        h = C.c_void_p()
+        self.ctx.check(lib().tb_vo_bow_db_get(self._h, C.byref(h)))
+        return BowDatabase(self.ctx, self.nseq, self._db_capacity, self.state_dev()["key_pitch"], None, handle=h)
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""
@@ -638,6 +657,26 @@ class Context:
                                                  C.c_void_p(bc.data_ptr())))
         return bw, bv, bc
 
+    def bow_score(self, scoring, a_words, a_values, b_words, b_values):
+        """tb_bow_score: TemplatedVocabulary::score(v1 = a, v2 = b) of one pair on the host (ScoringObject.cpp:23-311); the
+        vectors are sorted lists (words ascending, values beside them). No device is involved."""
+        return bow_score(scoring, a_words, a_values, b_words, b_values)
+
+    def bow_score_batch_dev(self, scoring, a_words, a_values, a_counts, b_words, b_values, b_counts, mode=TB_SCORE_ALL_PAIRS):
+        """tb_bow_score_batch_dev on torch tensors of this context's device: words int32 / values float64 [n, pitch] as
+        tb_bow_vector_batch_dev writes them, counts int32 [n]; a is v1. Returns float64 [na] (TB_SCORE_PAIRWISE) or [na, nb]
+        (TB_SCORE_ALL_PAIRS). Asynchronous on the context's stream."""
+        import torch
+        na, nb = a_words.shape[0], b_words.shape[0]
+        for w, v, c in ((a_words, a_values, a_counts), (b_words, b_values, b_counts)):
+            assert w.dtype == torch.int32 and v.dtype == torch.float64 and c.dtype == torch.int32 and v.shape == w.shape
+            assert c.numel() == w.shape[0] and w.is_contiguous() and v.is_contiguous() and c.is_contiguous()
+        out = torch.empty((na,) if mode == TB_SCORE_PAIRWISE else (na, nb), dtype=torch.float64, device=a_words.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.check(lib().tb_bow_score_batch_dev(self._h, int(scoring), int(mode), na, p(a_words), p(a_values), p(a_counts), a_words.shape[1],
+                                                nb, p(b_words), p(b_values), p(b_counts), b_words.shape[1], p(out)))
+        return out
+
     def reject_with_f_batch(self, cur, last, status, counts=None):
         """tb_reject_with_f_batch_dev on torch tensors of this context's device: cur / last float32 [P, N, 2], status uint8
         [P, N] (updated in place and returned), counts int32 [P] or None. Asynchronous on the context's stream."""
@@ -719,6 +758,109 @@ class Context:
         self.check(lib().tb_local_ba(self._h, _p(K), len(poses), int(nfixed), _p(poses), len(pts), _p(pts), _p(obs), len(obs),
                                      int(iters), _p(stats)))
         return int(stats[0]), poses.reshape(-1, 4, 4), pts, stats
+
+
+def bow_score(scoring, a_words, a_values, b_words, b_values):
+    """tb_bow_score (host, no context): the score of v1 = a against v2 = b under the scoring code of tb_vocabulary."""
+    aw = np.ascontiguousarray(a_words, np.int32); av = np.ascontiguousarray(a_values, np.float64)
+    bw = np.ascontiguousarray(b_words, np.int32); bv = np.ascontiguousarray(b_values, np.float64)
+    assert aw.ndim == 1 and av.shape == aw.shape and bw.ndim == 1 and bv.shape == bw.shape
+    out = C.c_double(0.0)
+    rc = lib().tb_bow_score(int(scoring), _p(aw) if len(aw) else None, _p(av) if len(aw) else None, len(aw),
+                            _p(bw) if len(bw) else None, _p(bv) if len(bw) else None, len(bw), C.byref(out))
+    if rc:
+        raise TBError(rc, "tb_bow_score: %s" % lib().tb_strerror(rc).decode())
+    return out.value
+
+
+class BowDatabase:
+    """tb_bow_db: per sequence a device-resident ring of the last `capacity` keyframes' BowVectors (include/tb_capi.h). Tensors
+    are torch tensors of the context's device; add, query and clear are asynchronous on the context's stream. handle=: wrap a
+    database that belongs to someone else (tb_vo_bow_db_get); it is not destroyed here."""
+
+    def __init__(self, ctx, nseq=None, capacity=None, pitch=None, scoring=None, handle=None):
+        self.ctx = ctx
+        self._own = handle is None
+        self.nseq, self.capacity, self.pitch, self.scoring = int(nseq), int(capacity), int(pitch), scoring
+        if handle is None:
+            self._h = C.c_void_p()
+            ctx.check(lib().tb_bow_db_create(ctx._h, self.nseq, self.capacity, self.pitch, self.scoring, C.byref(self._h)))
+        else:
+            self._h = handle
+
+    def close(self):
+        if self._h and self._own and self.ctx._h:
+            lib().tb_bow_db_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        self.ctx.check(lib().tb_bow_db_clear(self._h))
+
+    def add_ptr(self, words_ptr, values_ptr, counts_ptr, src_pitch, kf_id):
+        """tb_bow_db_add_dev on device pointers; returns the status code."""
+        return lib().tb_bow_db_add_dev(self._h, C.c_void_p(words_ptr), C.c_void_p(values_ptr), C.c_void_p(counts_ptr), int(src_pitch),
+                                       int(kf_id))
+
+    def add(self, bv_words, bv_values, bv_counts, kf_id):
+        """One add for every sequence: bv_words int32 / bv_values float64 [S, src_pitch], bv_counts int32 [S]."""
+        assert bv_words.shape[0] == self.nseq and bv_values.shape == bv_words.shape and bv_counts.numel() == self.nseq
+        assert bv_words.is_contiguous() and bv_values.is_contiguous() and bv_counts.is_contiguous()
+        self.ctx.check(self.add_ptr(bv_words.data_ptr(), bv_values.data_ptr(), bv_counts.data_ptr(), bv_words.shape[1], kf_id))
+
+    def query_ptr(self, words_ptr, values_ptr, counts_ptr, q_pitch, topk, exclude_newest, device):
+        """tb_bow_db_query_dev on device pointers: dict(scores [S, capacity], top_slot / top_kf / top_score [S, topk], top_count [S])."""
+        import torch
+        S, k = self.nseq, int(topk)
+        # every element is written by the query's kernels: no fill that could race with them on another stream
+        scores = torch.empty((S, self.capacity), dtype=torch.float64, device=device)
+        top_slot = torch.empty((S, max(k, 0)), dtype=torch.int32, device=device); top_kf = torch.empty_like(top_slot)
+        top_score = torch.empty((S, max(k, 0)), dtype=torch.float64, device=device)
+        top_count = torch.empty(S, dtype=torch.int32, device=device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        self.ctx.check(lib().tb_bow_db_query_dev(self._h, C.c_void_p(words_ptr), C.c_void_p(values_ptr), C.c_void_p(counts_ptr), int(q_pitch),
+                                                 int(exclude_newest), k, p(scores), p(top_slot), p(top_kf), p(top_score), p(top_count)))
+        return dict(scores=scores, top_slot=top_slot, top_kf=top_kf, top_score=top_score, top_count=top_count)
+
+    def query(self, q_words, q_values, q_counts, topk=4, exclude_newest=0):
+        """Sequence s's query vector (v1) against its own ring: q_words int32 / q_values float64 [S, q_pitch], q_counts int32 [S]."""
+        assert q_words.shape[0] == self.nseq and q_values.shape == q_words.shape and q_counts.numel() == self.nseq
+        assert q_words.is_contiguous() and q_values.is_contiguous() and q_counts.is_contiguous()
+        return self.query_ptr(q_words.data_ptr(), q_values.data_ptr(), q_counts.data_ptr(), q_words.shape[1], topk, exclude_newest,
+                              q_words.device)
+
+    def state_dev(self):
+        """dict of device pointers (words, values, counts, kf_ids) + nadded."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        n = C.c_int(0)
+        self.ctx.check(lib().tb_bow_db_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(n)))
+        out = {k: q.value for k, q in zip(("words", "values", "counts", "kf_ids"), ptrs)}
+        out["nadded"] = n.value
+        return out
+
+    def state(self, device):
+        """Copies of the rings as torch tensors (made on the current stream, so synchronise the context first): dict(words int32 /
+        values float64 [S, capacity, pitch], counts / kf_ids int32 [S, capacity] with -1 = empty, nadded)."""
+        import torch
+        d = self.state_dev()
+        S, N, P = self.nseq, self.capacity, self.pitch
+        spec = dict(words=((S, N, P), "<i4", torch.int32), values=((S, N, P), "<f8", torch.float64), counts=((S, N), "<i4", torch.int32),
+                    kf_ids=((S, N), "<i4", torch.int32))
+        out = {k: torch.as_tensor(_DevView(d[k], sh, ts), device=device).view(dt).clone() for k, (sh, ts, dt) in spec.items()}
+        out["nadded"] = d["nadded"]
+        return out
+
+
+class _DevView:
+    """__cuda_array_interface__ view of a device pointer the library owns (read only: copied out at once)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
 
 
 class Extractor:

@@ -10,6 +10,8 @@
 #include <stdarg.h>
 #include <string.h>
 #include <algorithm>
+#include <cfloat>
+#include <climits>
 #include <cmath>
 #include <memory>
 
@@ -1143,6 +1145,157 @@ int tb_bow_vector_batch_dev(tb_ctx* ctx, const tb_vocab* voc, int nframes, const
     return tbk_bow_vector(ctx, nframes, word_ids, weights, counts, desc_pitch, voc->weighting, voc->scoring, bv_words, bv_values, bv_counts);
 }
 
+/* ---- TemplatedVocabulary::score (TemplatedVocabulary.h:156-162, :1199-1203 -> ScoringObject.cpp:23-311), see include/tb_capi.h.
+ * The host form is the walk itself, two cursors on the sorted lists with std::map::lower_bound as std::lower_bound; this file is
+ * built with -ffp-contract=off, so every statement is one rounding, as in the reference's build. */
+static const double TB_LOG_EPS = log(DBL_EPSILON);   /* GeneralScoring::LOG_EPS, ScoringObject.cpp:18 */
+
+int tb_bow_score(int scoring, const int32_t* aw, const double* av, int na, const int32_t* bw, const double* bv, int nb, double* out) {
+    if (scoring < 0 || scoring > 5 || na < 0 || nb < 0 || !out || (na && (!aw || !av)) || (nb && (!bw || !bv))) return TB_EINVAL;
+    double score = 0;
+    int i = 0, j = 0;
+    while (i < na && j < nb) {
+        const double vi = av[i], wi = bv[j];
+        if (aw[i] == bw[j]) {
+            switch (scoring) {
+            case 0: score += fabs(vi - wi) - fabs(vi) - fabs(wi); break;          /* :41 */
+            case 2: if (vi + wi != 0.0) score += vi * wi / (vi + wi); break;      /* :148 */
+            case 3: if (vi != 0 && wi != 0) score += vi * log(vi / wi); break;    /* :195 */
+            case 4: score += sqrt(vi * wi); break;                                /* :245 */
+            default: score += vi * wi; break;                                     /* :91, :290 */
+            }
+            ++i; ++j;
+        } else if (aw[i] < bw[j]) {
+            if (scoring == 3) { score += vi * (log(vi) - TB_LOG_EPS); ++i; }      /* :204: KL moves v1 one step */
+            else i = (int)(std::lower_bound(aw + i, aw + na, bw[j]) - aw);
+        } else {
+            j = (int)(std::lower_bound(bw + j, bw + nb, aw[i]) - bw);
+        }
+    }
+    switch (scoring) {
+    case 0: score = -score / 2.0; break;                                          /* :65 */
+    case 1: if (score >= 1) score = 1.0; else score = 1.0 - sqrt(1.0 - score); break;   /* :114-117 */
+    case 2: score = 2. * score; break;                                            /* :167 */
+    case 3:
+        for (; i < na; ++i)                                                       /* :216-218 */
+            if (av[i] != 0) score += av[i] * (log(av[i]) - TB_LOG_EPS);
+        break;
+    default: break;
+    }
+    *out = score;
+    return TB_OK;
+}
+
+int tb_bow_score_batch_dev(tb_ctx* ctx, int scoring, int mode, int na, const int32_t* a_words, const double* a_values,
+                           const int32_t* a_counts, int a_pitch, int nb, const int32_t* b_words, const double* b_values,
+                           const int32_t* b_counts, int b_pitch, double* out) {
+    TB_ENTER(ctx);
+    if (!ctx) return TB_EINVAL;
+    if (scoring < 0 || scoring > 5 || (mode != TB_SCORE_PAIRWISE && mode != TB_SCORE_ALL_PAIRS) || na < 0 || nb < 0 || a_pitch < 1 ||
+        a_pitch > 8192 || b_pitch < 1 || b_pitch > 8192 || (mode == TB_SCORE_PAIRWISE && na != nb))
+        return tb_fail(ctx, TB_EINVAL, "tb_bow_score_batch_dev: scoring %d, mode %d, %d x %d vectors, pitches %d / %d", scoring, mode, na, nb,
+                       a_pitch, b_pitch);
+    if (na == 0 || nb == 0) return TB_OK;
+    if (!a_words || !a_values || !a_counts || !b_words || !b_values || !b_counts || !out) return TB_EINVAL;
+    const bool pw = mode == TB_SCORE_PAIRWISE;
+    return tbk_bow_score(ctx, scoring, TB_LOG_EPS, na, a_words, a_values, a_counts, a_pitch, b_words, b_values, b_counts, b_pitch,
+                         pw ? 1 : nb, pw ? 1 : 0, 0, 0, 0, 0, out);
+}
+
+/* ---- the keyframe database: per sequence a ring of BowVectors (see include/tb_capi.h) */
+struct tb_bow_db {
+    tb_ctx* ctx = nullptr;
+    int nseq = 0, cap = 0, pitch = 0, scoring = 0;
+    long long nadded = 0;             /* adds since the last clear: the next one goes to slot nadded % cap */
+    int32_t* words = nullptr;         /* [nseq][cap][pitch] */
+    double* values = nullptr;         /* [nseq][cap][pitch] */
+    int32_t* counts = nullptr;        /* [nseq][cap] */
+    int32_t* kf_ids = nullptr;        /* [nseq][cap], -1 = empty */
+};
+
+void tb_bow_db_destroy(tb_bow_db* db) {
+    if (!db) return;
+    if (db->ctx) { hipSetDevice(db->ctx->device); hipStreamSynchronize(db->ctx->stream); }
+    hipFree(db->words); hipFree(db->values); hipFree(db->counts); hipFree(db->kf_ids);
+    delete db;
+}
+
+int tb_bow_db_clear(tb_bow_db* db) {
+    TB_ENTER((db ? db->ctx : nullptr));
+    if (!db) return TB_EINVAL;
+    tb_ctx* ctx = db->ctx;
+    const size_t n = (size_t)db->nseq * db->cap;
+    TB_HIP(ctx, hipMemsetAsync(db->counts, 0, n * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(db->kf_ids, 0xff, n * sizeof(int32_t), ctx->stream));
+    db->nadded = 0;
+    return TB_OK;
+}
+
+int tb_bow_db_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int scoring, tb_bow_db** out) {
+    TB_ENTER(ctx);
+    if (!ctx || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (nseq < 1 || capacity < 1 || capacity > 1024 || pitch < 1 || pitch > 8192 || scoring < 0 || scoring > 5)
+        return tb_fail(ctx, TB_EINVAL, "tb_bow_db_create: %d sequences, capacity %d (1..1024), pitch %d (1..8192), scoring %d", nseq,
+                       capacity, pitch, scoring);
+    std::unique_ptr<tb_bow_db, void (*)(tb_bow_db*)> du(new tb_bow_db(), tb_bow_db_destroy);
+    tb_bow_db* db = du.get();
+    db->ctx = ctx; db->nseq = nseq; db->cap = capacity; db->pitch = pitch; db->scoring = scoring;
+    const size_t n = (size_t)nseq * capacity;
+    TB_HIP(ctx, hipMalloc(&db->words, n * pitch * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&db->values, n * pitch * sizeof(double)));
+    TB_HIP(ctx, hipMalloc(&db->counts, n * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&db->kf_ids, n * sizeof(int32_t)));
+    int rc = tb_bow_db_clear(db);
+    if (rc) return rc;
+    *out = du.release();
+    return TB_OK;
+}
+
+int tb_bow_db_add_dev(tb_bow_db* db, const int32_t* bv_words, const double* bv_values, const int32_t* bv_counts, int src_pitch,
+                      int32_t kf_id) {
+    TB_ENTER((db ? db->ctx : nullptr));
+    if (!db) return TB_EINVAL;
+    if (!bv_words || !bv_values || !bv_counts || src_pitch < 1 || src_pitch > db->pitch || kf_id < 0)
+        return tb_fail(db->ctx, TB_EINVAL, "tb_bow_db_add_dev: source pitch %d (database: %d), kf_id %d", src_pitch, db->pitch, (int)kf_id);
+    int rc = tbk_bow_db_add(db->ctx, db->nseq, bv_words, bv_values, bv_counts, src_pitch, db->cap, db->pitch, (int)(db->nadded % db->cap),
+                            kf_id, db->words, db->values, db->counts, db->kf_ids);
+    if (rc) return rc;
+    db->nadded++;
+    return TB_OK;
+}
+
+int tb_bow_db_query_dev(tb_bow_db* db, const int32_t* q_words, const double* q_values, const int32_t* q_counts, int q_pitch,
+                        int exclude_newest, int topk, double* scores, int32_t* top_slot, int32_t* top_kf, double* top_score,
+                        int32_t* top_count) {
+    TB_ENTER((db ? db->ctx : nullptr));
+    if (!db) return TB_EINVAL;
+    tb_ctx* ctx = db->ctx;
+    if (!q_words || !q_values || !q_counts || !scores || q_pitch < 1 || q_pitch > db->pitch || exclude_newest < 0 || topk < 0 ||
+        topk > db->cap || (topk && (!top_slot || !top_kf || !top_score)))
+        return tb_fail(ctx, TB_EINVAL, "tb_bow_db_query_dev: query pitch %d (database: %d), exclude_newest %d, topk %d (capacity %d)", q_pitch,
+                       db->pitch, exclude_newest, topk, db->cap);
+    const int nfilled = (int)std::min<long long>(db->nadded, db->cap);
+    const int newest = db->nadded ? (int)((db->nadded - 1) % db->cap) : 0;
+    int rc = tbk_bow_score(ctx, db->scoring, TB_LOG_EPS, db->nseq, q_words, q_values, q_counts, q_pitch, db->words, db->values, db->counts,
+                           db->pitch, db->cap, db->cap, 1, nfilled, newest, exclude_newest, scores);
+    if (rc) return rc;
+    if (topk == 0 && !top_count) return TB_OK;
+    return tbk_bow_db_rank(ctx, db->nseq, scores, db->kf_ids, db->cap, nfilled, newest, exclude_newest, db->scoring == 3, topk, top_slot,
+                           top_kf, top_score, top_count);
+}
+
+int tb_bow_db_state_dev(tb_bow_db* db, const int32_t** words, const double** values, const int32_t** counts, const int32_t** kf_ids,
+                        int* nadded) {
+    if (!db) return TB_EINVAL;
+    if (words) *words = db->words;
+    if (values) *values = db->values;
+    if (counts) *counts = db->counts;
+    if (kf_ids) *kf_ids = db->kf_ids;
+    if (nadded) *nadded = (int)std::min<long long>(db->nadded, INT_MAX);
+    return TB_OK;
+}
+
 int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int n, int levelsup, int32_t* word_ids, double* weights,
                      int32_t* node_ids) {
     TB_ENTER(ctx);
@@ -1882,6 +2035,7 @@ struct tb_vo {
     int32_t* bv_word[2] = {nullptr, nullptr};       /* [nseq][P] BowVector words */
     double* bv_val[2] = {nullptr, nullptr};         /* [nseq][P] BowVector values */
     int32_t* bv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
+    tb_bow_db* db = nullptr;                        /* the keyframe database (tb_vo_bow_db_enable), owned */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -1891,6 +2045,7 @@ void tb_vo_destroy(tb_vo* vo) {
     hipSetDevice(vo->ctx->device);
     hipStreamSynchronize(vo->ctx->stream);
     if (vo->ex) tb_extractor_destroy(vo->ex);
+    tb_bow_db_destroy(vo->db);
     for (int k = 0; k < 2; k++) {
         hipFree(vo->img[k]); hipFree(vo->keys[k]); hipFree(vo->kcnt[k]); hipFree(vo->mp[k]); hipFree(vo->valid[k]); hipFree(vo->Tcw[k]);
     }
@@ -2121,6 +2276,8 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     if (vo->tr.kind == TB_VO_BOW) {
         TB_HIP(ctx, hipMemsetAsync(vo->fv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
+        int rc;
+        if (vo->db && (rc = tb_bow_db_clear(vo->db))) return rc;   /* a new run: no keyframes yet */
     }
     if (vo->mapK) {   /* an empty map */
         TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
@@ -2211,6 +2368,8 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
             TB_HIP(ctx, hipMemcpyAsync(vo->bv_word[1], vo->bv_word[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
             TB_HIP(ctx, hipMemcpyAsync(vo->bv_val[1], vo->bv_val[0], SP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
             TB_HIP(ctx, hipMemcpyAsync(vo->bv_cnt[1], vo->bv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            /* the keyframe database, when enabled: the snapshot's BowVector into the ring slot of this keyframe */
+            if (vo->db && (rc = tb_bow_db_add_dev(vo->db, vo->bv_word[1], vo->bv_val[1], vo->bv_cnt[1], P, t))) return rc;
         }
         vo->kf_frame = t;
     }
@@ -2421,6 +2580,23 @@ int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_
     if (kf_bv_counts) *kf_bv_counts = vo->bv_cnt[1];
     if (kf_word_ids) *kf_word_ids = vo->bow_word[1];
     if (kf_node_ids) *kf_node_ids = vo->bow_node[1];
+    return TB_OK;
+}
+
+int tb_vo_bow_db_enable(tb_vo* vo, int capacity) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (vo->tr.kind != TB_VO_BOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable: the loop does not track by searchByBow");
+    if (vo->next > 0) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable after a step (frame %d)", vo->next - 1);
+    if (vo->db) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable: the database is enabled already");
+    return tb_bow_db_create(vo->ctx, vo->nseq, capacity, vo->P, vo->voc->scoring, &vo->db);
+}
+
+int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out) {
+    if (!vo || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (!vo->db) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_get: the keyframe database is not enabled");
+    *out = vo->db;
     return TB_OK;
 }
 

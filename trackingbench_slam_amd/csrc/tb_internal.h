@@ -215,6 +215,16 @@ int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const
                          const int32_t* d_n1, const tb_keypoint* d_k2, const uint8_t* d_d2, int pitch2, const unsigned long long* d_fv2,
                          const int32_t* d_n2, const uint8_t* d_has_mp2, int map_point_only, int th_low, float nratio, int histo_len,
                          int check_orientation, tb_match* d_out, int cap, int32_t* d_out_counts, int32_t* d_flags, int32_t* d_best);
+/* BowVector scoring and the keyframe database's kernels (k_bow_score.hip): query i of na meets entries i * bq + j, j in [0, nj),
+ * out [na][nj]; ring != 0: the entries are ring slots, of which nfilled are in use, the last add went to `newest`, and the
+ * `exclude` newest adds are left out (their out is a quiet NaN) */
+int tbk_bow_score(tb_ctx* ctx, int scoring, double log_eps, int na, const int32_t* d_aw, const double* d_av, const int32_t* d_ac, int a_pitch,
+                  const int32_t* d_bw, const double* d_bv, const int32_t* d_bc, int b_pitch, int nj, int bq, int ring, int nfilled,
+                  int newest, int exclude, double* d_out);
+int tbk_bow_db_add(tb_ctx* ctx, int nseq, const int32_t* d_src_w, const double* d_src_v, const int32_t* d_src_c, int src_pitch, int cap,
+                   int pitch, int slot, int32_t kf_id, int32_t* d_words, double* d_values, int32_t* d_counts, int32_t* d_kf_ids);
+int tbk_bow_db_rank(tb_ctx* ctx, int nseq, const double* d_scores, const int32_t* d_kf_ids, int cap, int nfilled, int newest, int exclude,
+                    int ascending, int topk, int32_t* d_top_slot, int32_t* d_top_kf, double* d_top_score, int32_t* d_top_count);
 /* vocabulary training (k_vocab.hip): the device arrays of a tb_vocab, owned by the caller on success */
 struct tb_vocab_arrays {
     int nnodes = 0;

@@ -221,6 +221,19 @@ namespace TRACKING_BENCH
         }
     }
 
+    double FlatVocabulary::score(const DBoW2::BowVector& v1, const DBoW2::BowVector& v2) const
+    {
+        /* the maps are in word order already: the sorted lists tb_bow_score walks */
+        std::vector<int32_t> w1, w2;
+        std::vector<double> x1, x2;
+        for (const auto& e : v1) { w1.push_back((int32_t)e.first); x1.push_back(e.second); }
+        for (const auto& e : v2) { w2.push_back((int32_t)e.first); x2.push_back(e.second); }
+        double out = 0.0;
+        if (tb_bow_score(scoring, w1.data(), x1.data(), (int)w1.size(), w2.data(), x2.data(), (int)w2.size(), &out))   /* no context involved */
+            throw std::runtime_error("FlatVocabulary::score: scoring code " + std::to_string(scoring));
+        return out;
+    }
+
     void Frame::SetBow(const std::shared_ptr<ORBVocabulary>& voc)
     {
         /* Frame.cpp:267-270 / TemplatedVocabulary.h:1124-1188 */

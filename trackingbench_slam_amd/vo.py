@@ -17,6 +17,8 @@ current frame's lookup grid. The map holds the points of the last `map_keyframes
 (:705) on the device for every frame: the DBoW2 transform, the FeatureVector keys and the BowVector. `vocab` is a
 synth.Vocabulary (uploaded and owned by the loop), a callable `f(context) -> handle` (e.g. one that trains with
 `context.vocab_train_dev`; the loop owns the handle), or a handle made on the `context=` the loop was given (borrowed).
+`keyframe_db=N` keeps the BowVectors of the last N keyframes of every sequence in a device-resident database that
+`query_keyframes` scores the current frame against (TemplatedVocabulary::score), for loop and relocalisation candidates.
 
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
@@ -85,9 +87,11 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
+        if keyframe_db and tracker != "bow":
+            raise TypeError("keyframe_db= needs tracker 'bow': the database holds the keyframes' BowVectors")
         if tracker == "bow" and vocab is None:
             raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
         if tracker != "bow" and vocab is not None:
@@ -105,6 +109,7 @@ class StereoVO:
         if context is not None:
             context.set_stream(self.stream.cuda_stream)
         self.vocab, self._own_vocab = None, False
+        self.db = None          # the keyframe database (keyframe_db=N), borrowed from the loop
         prm = capi.VOParams(self.width, self.height, int(nlevels), float(scale), int(target), float(init_th), float(min_th),
                             (C.c_double * 4)(*[float(k) for k in K]), float(bf), self.keyframe_every)
         self.params, self.tracker = prm, tracker
@@ -123,6 +128,9 @@ class StereoVO:
                     else:
                         self.vocab = vocab
                     self.vo = capi.VO(self.ctx, prm, self.S, bow=trk, vocab=self.vocab)
+                    if keyframe_db:               # 0 = off: no call is made
+                        self.ctx.check(self.vo.bow_db_enable(keyframe_db))
+                        self.db = self.vo.bow_db()
                 else:
                     self.vo = capi.VO(self.ctx, prm, self.S, trk)
             except Exception:
@@ -133,6 +141,7 @@ class StereoVO:
         self.frame = -1
 
     def close(self):
+        self.db = None                       # borrowed: it goes with the loop
         if getattr(self, "vo", None) is not None:
             self.vo.close()
             self.vo = None
@@ -301,6 +310,35 @@ class StereoVO:
     def bow_vector(self):
         """(current frame, keyframe): each dict(bv_words [S, P] int32 ascending, bv_values [S, P] float64, bv_counts [S])"""
         return self._bow(("bv_words", "bv_values", "bv_counts"))
+
+    # ---- the keyframe database (tracker "bow", keyframe_db=N): the last N keyframes' BowVectors per sequence
+    def _need_db(self):
+        if self.db is None:
+            raise capi.TBError(capi.TB_ESTATE, "the keyframe database is off: StereoVO(..., tracker='bow', keyframe_db=N)")
+        return self.db
+
+    def keyframe_database(self):
+        """dict(words [S, N, P] int32, values [S, N, P] float64, counts [S, N], kf_ids [S, N] int32 with -1 = an empty slot,
+        nadded = keyframes added since the last reset): keyframe number a sits in slot a % N; kf_id = its frame index"""
+        db = self._need_db()
+        with torch.cuda.stream(self.stream):
+            out = db.state(self.dev)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        return out
+
+    def query_keyframes(self, topk=4, exclude_newest=1):
+        """TemplatedVocabulary::score of the current frame's BowVector (v1) against every keyframe its own sequence's database
+        holds, the exclude_newest most recent ones left out (1: the keyframe being tracked against). Device tensors:
+        dict(scores [S, N] float64, NaN where a slot is empty or excluded; top_slot / top_kf [S, topk] int32 and top_score
+        [S, topk] float64, best first, -1 / NaN past top_count [S]). No host synchronisation."""
+        db = self._need_db()
+        d = self.vo.bow_state_dev()
+        with torch.cuda.stream(self.stream):
+            out = db.query_ptr(d["bv_words"], d["bv_values"], d["bv_counts"], self.key_pitch, topk, exclude_newest, self.dev)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        return out
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
