@@ -319,6 +319,72 @@ int tb_bow_db_query_dev(tb_bow_db* db, const int32_t* q_words, const double* q_v
                         int32_t* top_count);
 int tb_bow_db_state_dev(tb_bow_db* db, const int32_t** words, const double** values, const int32_t** counts, const int32_t** kf_ids,
                         int* nadded);
+/* A device-resident keyframe store and the verification of keyframe-database candidates: a relocalisation pose.
+ * tb_bow_db ranks keyframes by their BowVectors; a candidate is verified as ORB-SLAM verifies one, with the reference's own
+ * operators: Matcher::searchByBow (matcher.cpp:619-721) of the query frame against the stored keyframe, PoseOptimization's rows
+ * through the matches (LocalBA.cpp:333-363) and LocalBA::PoseOptimization (LocalBA.cpp:291-490) seeded with the keyframe's pose.
+ * The reference has no such step; the composition is this library's (tests/reloc_reference.py restates it on the CPU oracle).
+ *
+ * tb_kf_store: per sequence a ring of `capacity` keyframes, ring-aligned with tb_bow_db (add number a goes to slot a % capacity of
+ * every sequence, the host counts the adds, kf_id -1 = empty). A slot holds the key count, tb_keypoint[pitch], descriptors
+ * [pitch][32], FeatureVector keys uint64[pitch] with their count, map points float[pitch][3] with uint8 validity, Tcw[16], kf_id.
+ *   add    the snapshot's arrays [nseq][src_pitch] (counts / fv_counts [nseq], clamped to both pitches) and Tcw [nseq][16] into
+ *          the next slot with kf_id (>= 0): only the live entries are copied
+ *   state  device views [nseq][capacity][pitch] (counts, fv_counts, kf_ids [nseq][capacity]; Tcw [nseq][capacity][16]), *nadded
+ * Add, clear and state are asynchronous on the context's stream and copy nothing to the host. The store owns the verification's
+ * work buffers, sized at create for nseq * max_candidates pairs, so a verification allocates nothing. TB_EINVAL: null or
+ * inconsistent arguments, nseq < 1, capacity outside 1..1024, pitch outside 1..8192, max_candidates outside 1..capacity,
+ * nseq * max_candidates > 65535, kf_id < 0, a source pitch < 1 or larger than the store's. Destroy it before its context.
+ *
+ * tb_relocalize_batch_dev: the query frames [nseq][q_pitch] (keys, descriptors, FeatureVector keys with fv_counts; counts = the
+ * key counts) against the candidates cand_slot [nseq][ncand] (device, int32 ring slots, exactly tb_bow_db_query_dev's top_slot;
+ * -1, a slot outside the ring or an empty slot = no candidate). Pair c = s * ncand + r is sequence s, rank r:
+ *   match   searchByBow(query s, stored keyframe, map_point_only) with has_mp2 = the stored validity and the Matcher's fields of
+ *           tb_reloc_params; the stored keyframe is read in place and the query is not replicated
+ *   rows    the descriptor trackers' rule (tb_vo_tracker): a match counts where the stored entry trainIdx has a map point, the last
+ *           match in list order wins a key, rows in key order: px = the query key, Xw = the stored map point, invSigma2 =
+ *           invLevelSigma2[octave] as tb_scale_factors(nlevels, scale) gives it; outlier flags cleared
+ *   pose    tb_pose_opt_batch_dev's kernel on nseq * ncand problems, seeded with the stored keyframe's Tcw: fewer than 3 rows keep
+ *           the seed and give 0 inliers. Without a candidate: counts 0, cand_kf -1, the identity
+ *   select  per sequence the candidate with the most inliers, ties to the lower rank (candidates that are absent never win);
+ *           best_rank[s] = its rank if its inliers >= min_inliers, else -1; best_kf[s] its kf_id or -1; best_Tcw[s] its pose, or
+ *           the identity when -1
+ * tb_reloc_out (every pointer nullable, device): cand_kf / cand_matches / cand_rows / cand_inliers / cand_flags [nseq][ncand]
+ * (flags: searchByBow's), cand_Tcw [nseq][ncand][16], best_rank / best_kf [nseq], best_Tcw [nseq][16]. The call makes no host
+ * synchronisation and no host <-> device copy. min_inliers is the caller's: ORB-SLAM's relocalisation asks for 50, the reference
+ * has no figure. TB_EINVAL: ncand outside 1..max_candidates, q_pitch < 1 or larger than the store's, nlevels outside
+ * 1..16, histo_len outside 1..1024, null inputs.
+ * tb_reloc_rows_dev runs the rows stage alone on match lists the caller wrote into the work buffer (tb_kf_store_work_dev's
+ * matches, match_counts [nseq * ncand]); cand_rows nullable. tb_kf_store_work_dev lends the last call's work: matches
+ * [pairs][pitch], rows tb_obs [pairs][pitch] with row_counts [pairs], outlier flags [pairs][pitch] (of the rows, after the pose
+ * stage), *pitch = the store's. */
+typedef struct tb_kf_store tb_kf_store;
+typedef struct tb_reloc_params {
+    int map_point_only, th_low; float nratio; int histo_len, check_orientation;   /* searchByBow's, as in tb_vo_bow */
+    int min_inliers;
+} tb_reloc_params;
+typedef struct tb_reloc_out {
+    int32_t *cand_kf, *cand_matches, *cand_rows, *cand_inliers, *cand_flags;
+    float* cand_Tcw;
+    int32_t *best_rank, *best_kf;
+    float* best_Tcw;
+} tb_reloc_out;
+int tb_kf_store_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int max_candidates, tb_kf_store** out);
+void tb_kf_store_destroy(tb_kf_store* st);
+int tb_kf_store_clear(tb_kf_store* st);
+int tb_kf_store_add_dev(tb_kf_store* st, const tb_keypoint* keys, const uint8_t* desc, const int32_t* counts, const uint64_t* fv_keys,
+                        const int32_t* fv_counts, const float* map_points, const uint8_t* mp_valid, int src_pitch, const float* Tcw,
+                        int32_t kf_id);
+int tb_kf_store_state_dev(tb_kf_store* st, const tb_keypoint** keys, const uint8_t** desc, const int32_t** counts,
+                          const uint64_t** fv_keys, const int32_t** fv_counts, const float** map_points, const uint8_t** mp_valid,
+                          const float** Tcw, const int32_t** kf_ids, int* nadded);
+int tb_kf_store_work_dev(tb_kf_store* st, tb_match** matches, int32_t** match_counts, const tb_obs** rows, const int32_t** row_counts,
+                         const uint8_t** outlier, int* pitch);
+int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys,
+                            const uint8_t* q_desc, const int32_t* q_counts, const uint64_t* q_fv_keys, const int32_t* q_fv_counts,
+                            int q_pitch, const int32_t* cand_slot, int ncand, const tb_reloc_params* params, const tb_reloc_out* out);
+int tb_reloc_rows_dev(tb_kf_store* st, int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts, int q_pitch,
+                      const int32_t* cand_slot, int ncand, const int32_t* match_counts, int32_t* cand_rows);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -660,6 +726,22 @@ int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_
  * database is not enabled. */
 int tb_vo_bow_db_enable(tb_vo* vo, int capacity);
 int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out);
+/* Relocalisation in a TB_VO_BOW loop (off unless enabled; a loop that does not enable it launches what it launched before).
+ * tb_vo_reloc_enable creates a tb_kf_store with the database's capacity and the loop's key pitch; from then on a keyframe step
+ * adds the snapshot right after the database add -- key records, descriptors, FeatureVector keys, kf_map_points, kf_mp_valid, the
+ * frame's optimised Tcw, kf_id = the frame's index -- and tb_vo_reset_dev clears the store. TB_ESTATE: another tracker, the
+ * database not enabled, after the first step, or enabled already; max_candidates outside 1..capacity is TB_EINVAL.
+ * tb_vo_relocalize_dev is a query: tb_bow_db_query_dev(topk, exclude_newest) with the current frame's BowVector, then
+ * tb_relocalize_batch_dev of the current frame's ORB records, descriptors and FeatureVector against top_slot with the loop's
+ * tb_vo_bow fields. It changes neither the loop's pose nor its carried points nor its keyframe, and makes no host synchronisation
+ * and no host <-> device copy. scores [nseq][capacity], top_slot / top_kf / top_score [nseq][topk] and top_count [nseq] are the
+ * query's outputs (each nullable: the loop has buffers of its own); topk in 1..max_candidates. TB_ESTATE: not enabled, or before
+ * the first step. Adopting the pose after a loss, loop correction, and ORB-SLAM's second stage (searchByProjection with the
+ * recovered pose) are not part of it. tb_vo_kf_store_get lends the store (TB_ESTATE when not enabled). */
+int tb_vo_reloc_enable(tb_vo* vo, int max_candidates);
+int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
+                         double* top_score, int32_t* top_count, const tb_reloc_out* out);
+int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

@@ -48,6 +48,9 @@ EXPORTS = [
     "tb_bow_vector_batch_dev", "tb_vo_create_bow", "tb_vo_bow_state_dev",
     "tb_bow_score", "tb_bow_score_batch_dev", "tb_bow_db_create", "tb_bow_db_destroy", "tb_bow_db_clear", "tb_bow_db_add_dev",
     "tb_bow_db_query_dev", "tb_bow_db_state_dev", "tb_vo_bow_db_enable", "tb_vo_bow_db_get",
+    "tb_kf_store_create", "tb_kf_store_destroy", "tb_kf_store_clear", "tb_kf_store_add_dev", "tb_kf_store_state_dev",
+    "tb_kf_store_work_dev", "tb_relocalize_batch_dev", "tb_reloc_rows_dev", "tb_vo_reloc_enable", "tb_vo_relocalize_dev",
+    "tb_vo_kf_store_get",
 ]
 
 TB_VOC_MAX_L = 8
@@ -110,6 +113,8 @@ def lib():
         L.tb_vo_destroy.argtypes = [C.c_void_p]
         L.tb_bow_db_destroy.restype = None
         L.tb_bow_db_destroy.argtypes = [C.c_void_p]
+        L.tb_kf_store_destroy.restype = None
+        L.tb_kf_store_destroy.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -295,6 +300,34 @@ class VO:
         h = C.c_void_p()
         self.ctx.check(lib().tb_vo_bow_db_get(self._h, C.byref(h)))
         return BowDatabase(self.ctx, self.nseq, self._db_capacity, self.state_dev()["key_pitch"], None, handle=h)
+
+    def reloc_enable(self, max_candidates):
+        """tb_vo_reloc_enable: returns the status code (0 or a negative TB_E* code), so the state checks can be tested."""
+        rc = lib().tb_vo_reloc_enable(self._h, int(max_candidates))
+        if rc == 0:
+            self._max_candidates = int(max_candidates)
+        return rc
+
+    def kf_store(self):
+        """tb_vo_kf_store_get: the loop's keyframe store as a borrowed KeyframeStore (TB_ESTATE when it is not enabled)."""
+        h = C.c_void_p()
+        self.ctx.check(lib().tb_vo_kf_store_get(self._h, C.byref(h)))
+        return KeyframeStore(self.ctx, self.nseq, self._db_capacity, self.state_dev()["key_pitch"], self._max_candidates, handle=h)
+
+    def relocalize_dev(self, topk, exclude_newest, min_inliers, capacity, device):
+        """tb_vo_relocalize_dev: dict of device tensors -- the query's scores / top_* and tb_reloc_out's fields. Returns
+        (status code, dict)."""
+        import torch
+        S, k = self.nseq, max(int(topk), 0)
+        q = dict(scores=torch.empty((S, capacity), dtype=torch.float64, device=device),
+                 top_slot=torch.empty((S, k), dtype=torch.int32, device=device), top_kf=torch.empty((S, k), dtype=torch.int32, device=device),
+                 top_score=torch.empty((S, k), dtype=torch.float64, device=device), top_count=torch.empty(S, dtype=torch.int32, device=device))
+        ro, out = reloc_out(S, k, device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        rc = lib().tb_vo_relocalize_dev(self._h, int(topk), int(exclude_newest), int(min_inliers), p(q["scores"]), p(q["top_slot"]),
+                                        p(q["top_kf"]), p(q["top_score"]), p(q["top_count"]), C.byref(ro))
+        q.update(out)
+        return rc, q
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""
@@ -861,6 +894,142 @@ class _DevView:
 
     def __init__(self, ptr, shape, typestr):
         self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+
+
+class RelocParams(C.Structure):
+    """tb_reloc_params of include/tb_capi.h"""
+    _fields_ = [("map_point_only", C.c_int), ("th_low", C.c_int), ("nratio", C.c_float), ("histo_len", C.c_int),
+                ("check_orientation", C.c_int), ("min_inliers", C.c_int)]
+
+
+class RelocOut(C.Structure):
+    """tb_reloc_out of include/tb_capi.h: device pointers, each nullable"""
+    _fields_ = [(n, C.c_void_p) for n in ("cand_kf", "cand_matches", "cand_rows", "cand_inliers", "cand_flags", "cand_Tcw", "best_rank",
+                                          "best_kf", "best_Tcw")]
+
+
+def reloc_out(S, ncand, device):
+    """(RelocOut, dict of the torch tensors it points to): every output of a verification of S sequences x ncand candidates"""
+    import torch
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=device)
+    f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)
+    t = dict(cand_kf=i32(S, ncand), cand_matches=i32(S, ncand), cand_rows=i32(S, ncand), cand_inliers=i32(S, ncand), cand_flags=i32(S, ncand),
+             cand_Tcw=f32(S, ncand, 4, 4), best_rank=i32(S), best_kf=i32(S), best_Tcw=f32(S, 4, 4))
+    ro = RelocOut(**{k: (v.data_ptr() if v.numel() else None) for k, v in t.items()})
+    return ro, t
+
+
+class KeyframeStore:
+    """tb_kf_store: per sequence a device-resident ring of the last `capacity` keyframes -- key records, descriptors, FeatureVector
+    keys, map points, pose -- ring-aligned with BowDatabase, and the verification of candidates against it (include/tb_capi.h).
+    Tensors are torch tensors of the context's device; every call is asynchronous on the context's stream. handle=: wrap a store
+    that belongs to someone else (tb_vo_kf_store_get); it is not destroyed here."""
+
+    def __init__(self, ctx, nseq, capacity, pitch, max_candidates, handle=None):
+        self.ctx = ctx
+        self._own = handle is None
+        self.nseq, self.capacity, self.pitch, self.max_candidates = int(nseq), int(capacity), int(pitch), int(max_candidates)
+        if handle is None:
+            self._h = C.c_void_p()
+            ctx.check(lib().tb_kf_store_create(ctx._h, self.nseq, self.capacity, self.pitch, self.max_candidates, C.byref(self._h)))
+        else:
+            self._h = handle
+
+    def close(self):
+        if self._h and self._own and self.ctx._h:
+            lib().tb_kf_store_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        self.ctx.check(lib().tb_kf_store_clear(self._h))
+
+    def add_rc(self, keys, desc, counts, fv_keys, fv_counts, map_points, mp_valid, Tcw, kf_id, src_pitch=None):
+        """tb_kf_store_add_dev; returns the status code. keys [S, P, 7] int32 records, desc [S, P, 32] uint8, counts [S] int32,
+        fv_keys [S, P] int64, fv_counts [S], map_points [S, P, 3] float32, mp_valid [S, P] uint8, Tcw [S, 4, 4] float32."""
+        ts = (keys, desc, counts, fv_keys, fv_counts, map_points, mp_valid, Tcw)
+        assert all(t.is_contiguous() for t in ts) and keys.shape[0] == self.nseq
+        return lib().tb_kf_store_add_dev(self._h, *[C.c_void_p(t.data_ptr()) for t in ts[:7]], int(keys.shape[1] if src_pitch is None else src_pitch),
+                                         C.c_void_p(Tcw.data_ptr()), int(kf_id))
+
+    def add(self, *a, **kw):
+        self.ctx.check(self.add_rc(*a, **kw))
+
+    def state_dev(self):
+        """dict of device pointers (keys, desc, counts, fv_keys, fv_counts, map_points, mp_valid, Tcw, kf_ids) + nadded."""
+        names = ("keys", "desc", "counts", "fv_keys", "fv_counts", "map_points", "mp_valid", "Tcw", "kf_ids")
+        ptrs = [C.c_void_p() for _ in names]
+        n = C.c_int(0)
+        self.ctx.check(lib().tb_kf_store_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(n)))
+        out = {k: q.value for k, q in zip(names, ptrs)}
+        out["nadded"] = n.value
+        return out
+
+    def state(self, device):
+        """Copies of the rings as torch tensors (made on the current stream, so synchronise the context first): dict(keys
+        [S, N, P, 7] int32 records, desc [S, N, P, 32] uint8, fv_keys [S, N, P] int64, map_points [S, N, P, 3] float32, mp_valid
+        [S, N, P] uint8, counts / fv_counts / kf_ids [S, N] int32 with kf_id -1 = empty, Tcw [S, N, 4, 4] float32, nadded)."""
+        import torch
+        d = self.state_dev()
+        S, N, P = self.nseq, self.capacity, self.pitch
+        spec = dict(keys=((S, N, P, 7), "<i4", torch.int32), desc=((S, N, P, 32), "|u1", torch.uint8), fv_keys=((S, N, P), "<i8", torch.int64),
+                    map_points=((S, N, P, 3), "<f4", torch.float32), mp_valid=((S, N, P), "|u1", torch.uint8),
+                    counts=((S, N), "<i4", torch.int32), fv_counts=((S, N), "<i4", torch.int32), kf_ids=((S, N), "<i4", torch.int32),
+                    Tcw=((S, N, 4, 4), "<f4", torch.float32))
+        out = {k: torch.as_tensor(_DevView(d[k], sh, ts), device=device).view(dt).clone() for k, (sh, ts, dt) in spec.items()}
+        out["nadded"] = d["nadded"]
+        return out
+
+    def work(self, device, ncand):
+        """tb_kf_store_work_dev: torch VIEWS (not copies) of the last call's work for S x ncand pairs: matches [pairs, P, 4] int32
+        (writable: tb_reloc_rows_dev reads them), match_counts [pairs], rows [pairs, P, 6] float32, row_counts [pairs], outlier
+        [pairs, P] uint8."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(5)]
+        pitch = C.c_int(0)
+        self.ctx.check(lib().tb_kf_store_work_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(pitch)))
+        n, P = self.nseq * int(ncand), pitch.value
+        spec = (("matches", (n, P, 4), "<i4", torch.int32), ("match_counts", (n,), "<i4", torch.int32), ("rows", (n, P, 6), "<f4", torch.float32),
+                ("row_counts", (n,), "<i4", torch.int32), ("outlier", (n, P), "|u1", torch.uint8))
+        return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
+
+    def relocalize_rc(self, K, nlevels, scale, q_keys, q_desc, q_counts, q_fv_keys, q_fv_counts, cand_slot, map_point_only=True, th_low=50,
+                      nratio=6.0, histo_len=30, check_orientation=True, min_inliers=50, ncand=None, q_pitch=None):
+        """tb_relocalize_batch_dev -> (status code, dict of output tensors). q_keys [S, Q, 7] int32 records, q_desc [S, Q, 32],
+        q_counts [S], q_fv_keys [S, Q] int64, q_fv_counts [S], cand_slot [S, ncand] int32 (a BowDatabase query's top_slot)."""
+        ts = (q_keys, q_desc, q_counts, q_fv_keys, q_fv_counts, cand_slot)
+        assert all(t.is_contiguous() for t in ts)
+        ncand = int(cand_slot.shape[1] if ncand is None else ncand)
+        ro, out = reloc_out(self.nseq, max(min(ncand, cand_slot.shape[1]), 0), q_keys.device)
+        prm = RelocParams(int(bool(map_point_only)), int(th_low), float(nratio), int(histo_len), int(bool(check_orientation)), int(min_inliers))
+        Kd = (C.c_double * 4)(*[float(k) for k in K])
+        p = [C.c_void_p(t.data_ptr()) for t in ts]
+        rc = lib().tb_relocalize_batch_dev(self._h, Kd, int(nlevels), C.c_float(scale), p[0], p[1], p[2], p[3], p[4],
+                                           int(q_keys.shape[1] if q_pitch is None else q_pitch), p[5], ncand, C.byref(prm), C.byref(ro))
+        return rc, out
+
+    def relocalize(self, *a, **kw):
+        rc, out = self.relocalize_rc(*a, **kw)
+        self.ctx.check(rc)
+        return out
+
+    def rows(self, nlevels, scale, q_keys, q_counts, cand_slot, match_counts):
+        """tb_reloc_rows_dev: the rows stage alone on the match lists in work()["matches"] with match_counts [S * ncand] int32
+        -> cand_rows [S, ncand]; the rows are in work()."""
+        import torch
+        ts = (q_keys, q_counts, cand_slot, match_counts)
+        assert all(t.is_contiguous() for t in ts)
+        ncand = int(cand_slot.shape[1])
+        rows = torch.empty((self.nseq, ncand), dtype=torch.int32, device=q_keys.device)
+        self.ctx.check(lib().tb_reloc_rows_dev(self._h, int(nlevels), C.c_float(scale), C.c_void_p(q_keys.data_ptr()), C.c_void_p(q_counts.data_ptr()),
+                                               int(q_keys.shape[1]), C.c_void_p(cand_slot.data_ptr()), ncand, C.c_void_p(match_counts.data_ptr()),
+                                               C.c_void_p(rows.data_ptr())))
+        return rows
 
 
 class Extractor:

@@ -866,12 +866,16 @@ k_bow_vector(const int32_t* __restrict__ word_ids, const double* __restrict__ we
 
 /* Batched searchByBow, search stage: one thread per entry of F1's feature vector (= the reference's emission order once the
  * entries of nodes F2 does not have are dropped): the node's entries of F2 by binary search, then best / second best Hamming
- * distance in list order (matcher.cpp:645-669). best[pos] = {bestDist1, bestDist2, bestIdx2, 1 if F2 has the node}. */
+ * distance in list order (matcher.cpp:645-669). best[pos] = {bestDist1, bestDist2, bestIdx2, 1 if F2 has the node}.
+ * ix1 / ix2 (NULL: pair p reads frame p of each side) give the frame of side 1 and side 2 that pair p reads, so a caller can
+ * match frames where they lie (tb_relocalize_batch_dev: a query against several stored keyframes); best, out, out_counts and
+ * flags stay per pair. A frame index < 0 is a pair without a partner: nothing is read, its count and flag are 0. */
 struct BowBatch {
     const tb_keypoint *k1, *k2;
     const uint8_t *d1, *d2, *has_mp2;
     const unsigned long long *fv1, *fv2;
     const int32_t *n1, *n2;
+    const int32_t *ix1, *ix2;
     int pitch1, pitch2, map_point_only, th_low, histo_len, check_orientation, cap;
     float nratio;
     int32_t* best;
@@ -881,25 +885,27 @@ struct BowBatch {
 __global__ void __launch_bounds__(256)
 k_bow_search_batch(BowBatch B) {
     const int p = blockIdx.y, pos = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n1 = min(B.n1[p], B.pitch1), n2 = min(B.n2[p], B.pitch2);
+    const int f1 = B.ix1 ? B.ix1[p] : p, f2 = B.ix2 ? B.ix2[p] : p;
+    if (f1 < 0 || f2 < 0) return;
+    const int n1 = min(B.n1[f1], B.pitch1), n2 = min(B.n2[f2], B.pitch2);
     if (pos >= n1) return;
-    const unsigned long long key = B.fv1[(size_t)p * B.pitch1 + pos];
+    const unsigned long long key = B.fv1[(size_t)f1 * B.pitch1 + pos];
     const unsigned node = (unsigned)(key >> 32), idx1 = (unsigned)key;
-    const unsigned long long* F2 = B.fv2 + (size_t)p * B.pitch2;
+    const unsigned long long* F2 = B.fv2 + (size_t)f2 * B.pitch2;
     int lo = 0, hi = n2;
     const unsigned long long want = (unsigned long long)node << 32;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (F2[mid] < want) lo = mid + 1; else hi = mid; }
     int bestDist1 = 256, bestIdx2 = -1, bestDist2 = 256, found = 0;
     if (idx1 < (unsigned)B.pitch1) {
         Desc256 a;
-        const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(B.d1 + 32 * ((size_t)p * B.pitch1 + idx1));
+        const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(B.d1 + 32 * ((size_t)f1 * B.pitch1 + idx1));
         a.w[0] = pa[0]; a.w[1] = pa[1]; a.w[2] = pa[2]; a.w[3] = pa[3];
         for (int q = lo; q < n2 && (unsigned)(F2[q] >> 32) == node; q++) {
             found = 1;
             const unsigned idx2 = (unsigned)F2[q];
             if (idx2 >= (unsigned)B.pitch2) continue;
-            if (B.map_point_only && !(B.has_mp2 && B.has_mp2[(size_t)p * B.pitch2 + idx2])) continue;
-            const int dist = bf_dist(a, reinterpret_cast<const unsigned long long*>(B.d2 + 32 * ((size_t)p * B.pitch2 + idx2)));
+            if (B.map_point_only && !(B.has_mp2 && B.has_mp2[(size_t)f2 * B.pitch2 + idx2])) continue;
+            const int dist = bf_dist(a, reinterpret_cast<const unsigned long long*>(B.d2 + 32 * ((size_t)f2 * B.pitch2 + idx2)));
             if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx2 = (int)idx2; }
             else if (dist < bestDist2) bestDist2 = dist;
         }
@@ -916,11 +922,16 @@ k_bow_accept_batch(BowBatch B) {
     __shared__ int keep[3];
     __shared__ int srun;
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int n1 = min(B.n1[p], B.pitch1);
+    const int f1 = B.ix1 ? B.ix1[p] : p, f2 = B.ix2 ? B.ix2[p] : p;
+    if (f1 < 0 || f2 < 0) {   /* the whole workgroup: no barrier has been reached */
+        if (tid == 0) { B.out_counts[p] = 0; B.flags[p] = 0; }
+        return;
+    }
+    const int n1 = min(B.n1[f1], B.pitch1);
     const int32_t* best = B.best + (size_t)p * B.pitch1 * 4;
-    const unsigned long long* F1 = B.fv1 + (size_t)p * B.pitch1;
-    const tb_keypoint* k1 = B.k1 + (size_t)p * B.pitch1;
-    const tb_keypoint* k2 = B.k2 + (size_t)p * B.pitch2;
+    const unsigned long long* F1 = B.fv1 + (size_t)f1 * B.pitch1;
+    const tb_keypoint* k1 = B.k1 + (size_t)f1 * B.pitch1;
+    const tb_keypoint* k2 = B.k2 + (size_t)f2 * B.pitch2;
     tb_match* out = B.out + (size_t)p * B.cap;
     const float factor = 1.f / (float)B.histo_len;
     auto accepted = [&](int pos, int& bin) -> bool {
@@ -1029,9 +1040,11 @@ int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const do
 int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, int pitch1, const unsigned long long* d_fv1,
                          const int32_t* d_n1, const tb_keypoint* d_k2, const uint8_t* d_d2, int pitch2, const unsigned long long* d_fv2,
                          const int32_t* d_n2, const uint8_t* d_has_mp2, int map_point_only, int th_low, float nratio, int histo_len,
-                         int check_orientation, tb_match* d_out, int cap, int32_t* d_out_counts, int32_t* d_flags, int32_t* d_best) {
+                         int check_orientation, tb_match* d_out, int cap, int32_t* d_out_counts, int32_t* d_flags, int32_t* d_best,
+                         const int32_t* d_ix1, const int32_t* d_ix2) {
     if (npairs <= 0) return TB_OK;
     BowBatch B;
+    B.ix1 = d_ix1; B.ix2 = d_ix2;
     B.k1 = d_k1; B.k2 = d_k2; B.d1 = d_d1; B.d2 = d_d2; B.has_mp2 = d_has_mp2; B.fv1 = d_fv1; B.fv2 = d_fv2; B.n1 = d_n1; B.n2 = d_n2;
     B.pitch1 = pitch1; B.pitch2 = pitch2; B.map_point_only = map_point_only; B.th_low = th_low; B.histo_len = histo_len;
     B.check_orientation = check_orientation; B.cap = cap; B.nratio = nratio; B.best = d_best; B.out = d_out; B.out_counts = d_out_counts;

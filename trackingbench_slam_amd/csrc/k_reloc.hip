@@ -1,0 +1,233 @@
+/* The keyframe store and the verification of keyframe-database candidates (relocalisation pose): the copy and compaction
+ * kernels around the batched searchByBow (k_match.hip, matcher.cpp:619-721) and PoseOptimization (k_pose.hip,
+ * LocalBA.cpp:291-490). See include/tb_capi.h, tb_kf_store / tb_relocalize_batch_dev.
+ *
+ * A store array is [nseq][cap][pitch]: frame index s * cap + slot, so the matcher reads a stored keyframe in place. */
+#include "tb_internal.h"
+
+/* Block copy of nbytes: 16-byte lanes where both sides are 16-byte aligned (every array of the store is, at a pitch that is a
+ * multiple of 4), 4-byte lanes where both are 4-byte aligned, single bytes for the rest and for the tail. */
+__device__ __forceinline__ void kf_copy(void* __restrict__ dst, const void* __restrict__ src, size_t nbytes, int tid) {
+    const uintptr_t both = (uintptr_t)dst | (uintptr_t)src;
+    size_t done = 0;
+    if ((both & 15) == 0) {
+        const size_t nv = nbytes >> 4;
+        const uint4* S = reinterpret_cast<const uint4*>(src);
+        uint4* D = reinterpret_cast<uint4*>(dst);
+        for (size_t i = tid; i < nv; i += 256) D[i] = S[i];
+        done = nv << 4;
+    } else if ((both & 3) == 0) {
+        const size_t nv = nbytes >> 2;
+        const uint32_t* S = reinterpret_cast<const uint32_t*>(src);
+        uint32_t* D = reinterpret_cast<uint32_t*>(dst);
+        for (size_t i = tid; i < nv; i += 256) D[i] = S[i];
+        done = nv << 2;
+    }
+    const uint8_t* S = reinterpret_cast<const uint8_t*>(src);
+    uint8_t* D = reinterpret_cast<uint8_t*>(dst);
+    for (size_t i = done + tid; i < nbytes; i += 256) D[i] = S[i];
+}
+
+struct KfStoreArrays {
+    tb_keypoint* keys;          /* [nseq][cap][pitch] */
+    uint8_t* desc;              /* [nseq][cap][pitch][32] */
+    unsigned long long* fv;     /* [nseq][cap][pitch] */
+    float* mp;                  /* [nseq][cap][pitch][3] */
+    uint8_t* valid;             /* [nseq][cap][pitch] */
+    float* Tcw;                 /* [nseq][cap][16] */
+    int32_t *counts, *fv_counts, *kf_ids;   /* [nseq][cap] */
+};
+struct KfStoreSrc {
+    const tb_keypoint* keys;
+    const uint8_t* desc;
+    const unsigned long long* fv;
+    const float* mp;
+    const uint8_t* valid;
+    const float* Tcw;
+    const int32_t *counts, *fv_counts;
+};
+
+/* One add of the store: workgroup (s, g) copies array group g of sequence s's snapshot (src [nseq][src_pitch]) into ring slot
+ * `slot`: 0 the key records, 1 the descriptors, 2 the FeatureVector keys, 3 the map points, their validity, the pose and the
+ * slot's header. Only the live entries move (the counts, clamped to both pitches); what lies beyond them keeps what it held. */
+__global__ void __launch_bounds__(256)
+k_kf_store_add(KfStoreSrc A, int src_pitch, int cap, int pitch, int slot, int32_t kf_id, KfStoreArrays D) {
+    const int s = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int lim = min(src_pitch, pitch);
+    const size_t n = (size_t)min(max(A.counts[s], 0), lim), nf = (size_t)min(max(A.fv_counts[s], 0), lim);
+    const size_t src = (size_t)s * src_pitch, f = (size_t)s * cap + slot, dst = f * pitch;
+    if (g == 0) {
+        kf_copy(D.keys + dst, A.keys + src, n * sizeof(tb_keypoint), tid);
+    } else if (g == 1) {
+        kf_copy(D.desc + 32 * dst, A.desc + 32 * src, n * 32, tid);
+    } else if (g == 2) {
+        kf_copy(D.fv + dst, A.fv + src, nf * sizeof(unsigned long long), tid);
+    } else {
+        kf_copy(D.mp + 3 * dst, A.mp + 3 * src, n * 3 * sizeof(float), tid);
+        kf_copy(D.valid + dst, A.valid + src, n, tid);
+        if (tid < 16) D.Tcw[16 * f + tid] = A.Tcw[16 * (size_t)s + tid];
+        if (tid == 0) { D.counts[f] = (int32_t)n; D.fv_counts[f] = (int32_t)nf; D.kf_ids[f] = kf_id; }
+    }
+}
+
+/* Pair c = s * ncand + r: the frame indices the matcher takes (side 1: the query frame s; side 2: the stored keyframe
+ * s * cap + slot, or -1 where there is no candidate -- a slot of -1, one outside the ring, or an empty one), the pose
+ * optimisation's seed (the keyframe's pose; the identity without a candidate) and the candidate's keyframe id. */
+__global__ void __launch_bounds__(256)
+k_reloc_pairs(int npairs, int ncand, int cap, const int32_t* __restrict__ cand_slot, const int32_t* __restrict__ kf_ids,
+              const float* __restrict__ kf_Tcw, int32_t* __restrict__ ix1, int32_t* __restrict__ ix2, float* __restrict__ seed,
+              int32_t* __restrict__ cand_kf) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= npairs) return;
+    const int s = c / ncand, slot = cand_slot[c];
+    int f = -1, kf = -1;
+    if (slot >= 0 && slot < cap) {
+        kf = kf_ids[(size_t)s * cap + slot];
+        if (kf >= 0) f = s * cap + slot; else kf = -1;
+    }
+    ix1[c] = s; ix2[c] = f; cand_kf[c] = kf;
+    for (int i = 0; i < 16; i++) seed[16 * (size_t)c + i] = f >= 0 ? kf_Tcw[16 * (size_t)f + i] : ((i & 3) == (i >> 2) ? 1.f : 0.f);
+}
+
+/* PoseOptimization's rows of pair c (one workgroup each), by k_vo_match_carry's rule without its side effects: for every match
+ * whose stored entry trainIdx has a map point, key queryIdx gets that point, the last such match in list order winning a key
+ * (win[], in LDS: one int per query key); then one row per key that has a point, IN KEY ORDER (LocalBA.cpp:333-363): px = the
+ * query key, Xw = the stored map point, invSigma2 = invLevelSigma2[octave] (:349). The outlier flags of the query's keys are
+ * cleared. Without a candidate: no rows. */
+struct tb_reloc_sigma {
+    float v[TB_MAX_LEVELS];
+    int n;
+};
+__global__ void __launch_bounds__(256)
+k_reloc_rows(const tb_keypoint* __restrict__ q_keys, const int32_t* __restrict__ q_counts, int q_pitch, const int32_t* __restrict__ ix1,
+             const int32_t* __restrict__ ix2, const tb_match* __restrict__ matches, const int32_t* __restrict__ match_counts,
+             const float* __restrict__ kf_mp, const uint8_t* __restrict__ kf_valid, const int32_t* __restrict__ kf_counts, int pitch,
+             tb_reloc_sigma sig, tb_obs* __restrict__ obs, int32_t* __restrict__ obs_counts, uint8_t* __restrict__ outlier,
+             int32_t* __restrict__ rows_out) {
+    extern __shared__ int win[];   /* [q_pitch] */
+    __shared__ int wsum[4];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = ix1[c], f = ix2[c];
+    if (f < 0 || s < 0) {
+        if (tid == 0) { obs_counts[c] = 0; if (rows_out) rows_out[c] = 0; }
+        return;
+    }
+    const int n = min(max(q_counts[s], 0), q_pitch);
+    const int nm = min(max(match_counts[c], 0), pitch);
+    const int nk = min(max(kf_counts[f], 0), pitch);
+    const tb_keypoint* K = q_keys + (size_t)s * q_pitch;
+    const tb_match* M = matches + (size_t)c * pitch;
+    const float* MP = kf_mp + 3 * (size_t)f * pitch;
+    const uint8_t* V = kf_valid + (size_t)f * pitch;
+    tb_obs* O = obs + (size_t)c * pitch;
+    uint8_t* OUT = outlier + (size_t)c * pitch;
+    for (int i = tid; i < n; i += 256) win[i] = -1;
+    __syncthreads();
+    for (int k = tid; k < nm; k += 256) {
+        const int q = M[k].queryIdx, tr = M[k].trainIdx;
+        if (q >= 0 && q < n && tr >= 0 && tr < nk && V[tr]) atomicMax(&win[q], k);
+    }
+    __syncthreads();
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        bool ok = false;
+        tb_obs r = {0, 0, 0, 0, 0, 0};
+        if (i < n) {
+            const int k = win[i];
+            ok = k >= 0;
+            OUT[i] = 0;
+            if (ok) {
+                const int j = M[k].trainIdx;
+                const tb_keypoint kp = K[i];
+                r.u = kp.x; r.v = kp.y;
+                r.X = MP[3 * j]; r.Y = MP[3 * j + 1]; r.Z = MP[3 * j + 2];
+                r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];
+            }
+        }
+        const unsigned long long bm = __ballot(ok);
+        if (lane == 0) wsum[wave] = __popcll(bm);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        if (ok) O[at] = r; /* at < n <= q_pitch <= pitch */
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid == 0) { obs_counts[c] = base; if (rows_out) rows_out[c] = base; }
+}
+
+/* Per sequence (one thread each): the candidate with the most inliers, ties to the lower rank, candidates that are absent left
+ * out; it is the answer when its inliers reach min_inliers. best_rank -1: best_kf -1 and the identity pose. */
+__global__ void __launch_bounds__(256)
+k_reloc_select(int nseq, int ncand, int min_inliers, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_inliers,
+               const float* __restrict__ cand_Tcw, int32_t* __restrict__ best_rank, int32_t* __restrict__ best_kf,
+               float* __restrict__ best_Tcw) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nseq) return;
+    int best = -1, most = -1;
+    for (int r = 0; r < ncand; r++) {
+        const size_t c = (size_t)s * ncand + r;
+        if (cand_kf[c] < 0) continue;
+        const int ni = cand_inliers[c];
+        if (ni > most) { most = ni; best = r; }
+    }
+    if (best >= 0 && most < min_inliers) best = -1;
+    if (best_rank) best_rank[s] = best;
+    if (best_kf) best_kf[s] = best >= 0 ? cand_kf[(size_t)s * ncand + best] : -1;
+    if (best_Tcw)
+        for (int i = 0; i < 16; i++)
+            best_Tcw[16 * (size_t)s + i] = best >= 0 ? cand_Tcw[16 * ((size_t)s * ncand + best) + i] : ((i & 3) == (i >> 2) ? 1.f : 0.f);
+}
+
+int tbk_kf_store_add(tb_ctx* ctx, int nseq, const tb_keypoint* d_keys, const uint8_t* d_desc, const int32_t* d_counts,
+                     const unsigned long long* d_fv, const int32_t* d_fv_counts, const float* d_mp, const uint8_t* d_valid, int src_pitch,
+                     const float* d_Tcw, int32_t kf_id, int cap, int pitch, int slot, tb_keypoint* s_keys, uint8_t* s_desc,
+                     unsigned long long* s_fv, float* s_mp, uint8_t* s_valid, float* s_Tcw, int32_t* s_counts, int32_t* s_fv_counts,
+                     int32_t* s_kf_ids) {
+    KfStoreSrc A = {d_keys, d_desc, d_fv, d_mp, d_valid, d_Tcw, d_counts, d_fv_counts};
+    KfStoreArrays D = {s_keys, s_desc, s_fv, s_mp, s_valid, s_Tcw, s_counts, s_fv_counts, s_kf_ids};
+    tb_prof_begin(ctx, "k_kf_store_add");
+    hipLaunchKernelGGL(k_kf_store_add, dim3(nseq, 4), dim3(256), 0, ctx->stream, A, src_pitch, cap, pitch, slot, kf_id, D);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_reloc_pairs(tb_ctx* ctx, int nseq, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids, const float* d_kf_Tcw,
+                    int32_t* d_ix1, int32_t* d_ix2, float* d_seed, int32_t* d_cand_kf) {
+    const int npairs = nseq * ncand;
+    tb_prof_begin(ctx, "k_reloc_pairs");
+    hipLaunchKernelGGL(k_reloc_pairs, dim3((npairs + 255) / 256), dim3(256), 0, ctx->stream, npairs, ncand, cap, d_cand_slot, d_kf_ids,
+                       d_kf_Tcw, d_ix1, d_ix2, d_seed, d_cand_kf);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_reloc_rows(tb_ctx* ctx, int npairs, const tb_keypoint* d_q_keys, const int32_t* d_q_counts, int q_pitch, const int32_t* d_ix1,
+                   const int32_t* d_ix2, const tb_match* d_matches, const int32_t* d_match_counts, const float* d_kf_mp,
+                   const uint8_t* d_kf_valid, const int32_t* d_kf_counts, int pitch, const float* inv_sigma2, int nlevels, tb_obs* d_obs,
+                   int32_t* d_obs_counts, uint8_t* d_outlier, int32_t* d_rows_out) {
+    tb_reloc_sigma sig;
+    sig.n = std::min(std::max(nlevels, 1), TB_MAX_LEVELS);
+    for (int l = 0; l < TB_MAX_LEVELS; l++) sig.v[l] = l < sig.n ? inv_sigma2[l] : 1.f;
+    tb_prof_begin(ctx, "k_reloc_rows");
+    hipLaunchKernelGGL(k_reloc_rows, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), ctx->stream, d_q_keys, d_q_counts, q_pitch,
+                       d_ix1, d_ix2, d_matches, d_match_counts, d_kf_mp, d_kf_valid, d_kf_counts, pitch, sig, d_obs, d_obs_counts, d_outlier,
+                       d_rows_out);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_reloc_select(tb_ctx* ctx, int nseq, int ncand, int min_inliers, const int32_t* d_cand_kf, const int32_t* d_cand_inliers,
+                     const float* d_cand_Tcw, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_Tcw) {
+    tb_prof_begin(ctx, "k_reloc_select");
+    hipLaunchKernelGGL(k_reloc_select, dim3((nseq + 255) / 256), dim3(256), 0, ctx->stream, nseq, ncand, min_inliers, d_cand_kf,
+                       d_cand_inliers, d_cand_Tcw, d_best_rank, d_best_kf, d_best_Tcw);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}

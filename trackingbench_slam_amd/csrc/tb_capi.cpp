@@ -1296,6 +1296,202 @@ int tb_bow_db_state_dev(tb_bow_db* db, const int32_t** words, const double** val
     return TB_OK;
 }
 
+/* ---- the keyframe store and candidate verification (see include/tb_capi.h) */
+struct tb_kf_store {
+    tb_ctx* ctx = nullptr;
+    int nseq = 0, cap = 0, pitch = 0, max_cand = 0;
+    long long nadded = 0;                 /* adds since the last clear: the next one goes to slot nadded % cap */
+    /* the rings, frame index s * cap + slot */
+    tb_keypoint* keys = nullptr;          /* [nseq][cap][pitch] */
+    uint8_t* desc = nullptr;              /* [nseq][cap][pitch][32] */
+    uint64_t* fv = nullptr;               /* [nseq][cap][pitch] */
+    float* mp = nullptr;                  /* [nseq][cap][pitch][3] */
+    uint8_t* valid = nullptr;             /* [nseq][cap][pitch] */
+    float* Tcw = nullptr;                 /* [nseq][cap][16] */
+    int32_t *counts = nullptr, *fv_counts = nullptr, *kf_ids = nullptr;   /* [nseq][cap] */
+    /* verification work, pairs = nseq * max_cand */
+    int32_t *ix1 = nullptr, *ix2 = nullptr;                  /* [pairs] the matcher's frame indices */
+    int32_t* best = nullptr;                                 /* [pairs][pitch][4] searchByBow's best rows */
+    tb_match* matches = nullptr;                             /* [pairs][pitch] */
+    tb_obs* obs = nullptr;                                   /* [pairs][pitch] */
+    uint8_t* outlier = nullptr;                              /* [pairs][pitch] */
+    double* err = nullptr;                                   /* [pairs][pitch][3] the pose kernel's residuals */
+    float *seed = nullptr, *pose = nullptr;                  /* [pairs][16] */
+    int32_t *mcounts = nullptr, *flags = nullptr, *ocounts = nullptr, *ninl = nullptr, *ckf = nullptr;   /* [pairs] */
+};
+
+void tb_kf_store_destroy(tb_kf_store* st) {
+    if (!st) return;
+    if (st->ctx) { hipSetDevice(st->ctx->device); hipStreamSynchronize(st->ctx->stream); }
+    hipFree(st->keys); hipFree(st->desc); hipFree(st->fv); hipFree(st->mp); hipFree(st->valid); hipFree(st->Tcw); hipFree(st->counts);
+    hipFree(st->fv_counts); hipFree(st->kf_ids); hipFree(st->ix1); hipFree(st->ix2); hipFree(st->best); hipFree(st->matches);
+    hipFree(st->obs); hipFree(st->outlier); hipFree(st->err); hipFree(st->seed); hipFree(st->pose); hipFree(st->mcounts);
+    hipFree(st->flags); hipFree(st->ocounts); hipFree(st->ninl); hipFree(st->ckf);
+    delete st;
+}
+
+int tb_kf_store_clear(tb_kf_store* st) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    const size_t n = (size_t)st->nseq * st->cap;
+    TB_HIP(ctx, hipMemsetAsync(st->counts, 0, n * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(st->fv_counts, 0, n * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(st->kf_ids, 0xff, n * sizeof(int32_t), ctx->stream));
+    st->nadded = 0;
+    return TB_OK;
+}
+
+int tb_kf_store_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int max_candidates, tb_kf_store** out) {
+    TB_ENTER(ctx);
+    if (!ctx || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (nseq < 1 || capacity < 1 || capacity > 1024 || pitch < 1 || pitch > 8192 || max_candidates < 1 || max_candidates > capacity ||
+        (long long)nseq * max_candidates > 65535)
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_create: %d sequences, capacity %d (1..1024), pitch %d (1..8192), max_candidates %d (1..capacity, at most 65535 pairs)",
+                       nseq, capacity, pitch, max_candidates);
+    std::unique_ptr<tb_kf_store, void (*)(tb_kf_store*)> su(new tb_kf_store(), tb_kf_store_destroy);
+    tb_kf_store* st = su.get();
+    st->ctx = ctx; st->nseq = nseq; st->cap = capacity; st->pitch = pitch; st->max_cand = max_candidates;
+    const size_t n = (size_t)nseq * capacity, np = n * pitch, pairs = (size_t)nseq * max_candidates, pp = pairs * pitch;
+    TB_HIP(ctx, hipMalloc(&st->keys, np * sizeof(tb_keypoint)));
+    TB_HIP(ctx, hipMalloc(&st->desc, np * 32));
+    TB_HIP(ctx, hipMalloc(&st->fv, np * sizeof(uint64_t)));
+    TB_HIP(ctx, hipMalloc(&st->mp, np * 3 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&st->valid, np));
+    TB_HIP(ctx, hipMalloc(&st->Tcw, n * 16 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&st->counts, n * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->fv_counts, n * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->kf_ids, n * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->ix1, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->ix2, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->best, pp * 16));
+    TB_HIP(ctx, hipMalloc(&st->matches, pp * sizeof(tb_match)));
+    TB_HIP(ctx, hipMalloc(&st->obs, pp * sizeof(tb_obs)));
+    TB_HIP(ctx, hipMalloc(&st->outlier, pp));
+    TB_HIP(ctx, hipMalloc(&st->err, pp * 3 * sizeof(double)));
+    TB_HIP(ctx, hipMalloc(&st->seed, pairs * 16 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&st->pose, pairs * 16 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&st->mcounts, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->flags, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->ocounts, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->ninl, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&st->ckf, pairs * sizeof(int32_t)));
+    TB_HIP(ctx, hipMemsetAsync(st->mcounts, 0, pairs * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(st->ocounts, 0, pairs * sizeof(int32_t), ctx->stream));
+    int rc = tb_kf_store_clear(st);
+    if (rc) return rc;
+    *out = su.release();
+    return TB_OK;
+}
+
+int tb_kf_store_add_dev(tb_kf_store* st, const tb_keypoint* keys, const uint8_t* desc, const int32_t* counts, const uint64_t* fv_keys,
+                        const int32_t* fv_counts, const float* map_points, const uint8_t* mp_valid, int src_pitch, const float* Tcw,
+                        int32_t kf_id) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    if (!keys || !desc || !counts || !fv_keys || !fv_counts || !map_points || !mp_valid || !Tcw || src_pitch < 1 || src_pitch > st->pitch ||
+        kf_id < 0)
+        return tb_fail(st->ctx, TB_EINVAL, "tb_kf_store_add_dev: source pitch %d (store: %d), kf_id %d", src_pitch, st->pitch, (int)kf_id);
+    int rc = tbk_kf_store_add(st->ctx, st->nseq, keys, desc, counts, (const unsigned long long*)fv_keys, fv_counts, map_points, mp_valid,
+                              src_pitch, Tcw, kf_id, st->cap, st->pitch, (int)(st->nadded % st->cap), st->keys, st->desc,
+                              (unsigned long long*)st->fv, st->mp, st->valid, st->Tcw, st->counts, st->fv_counts, st->kf_ids);
+    if (rc) return rc;
+    st->nadded++;
+    return TB_OK;
+}
+
+int tb_kf_store_state_dev(tb_kf_store* st, const tb_keypoint** keys, const uint8_t** desc, const int32_t** counts,
+                          const uint64_t** fv_keys, const int32_t** fv_counts, const float** map_points, const uint8_t** mp_valid,
+                          const float** Tcw, const int32_t** kf_ids, int* nadded) {
+    if (!st) return TB_EINVAL;
+    if (keys) *keys = st->keys;
+    if (desc) *desc = st->desc;
+    if (counts) *counts = st->counts;
+    if (fv_keys) *fv_keys = st->fv;
+    if (fv_counts) *fv_counts = st->fv_counts;
+    if (map_points) *map_points = st->mp;
+    if (mp_valid) *mp_valid = st->valid;
+    if (Tcw) *Tcw = st->Tcw;
+    if (kf_ids) *kf_ids = st->kf_ids;
+    if (nadded) *nadded = (int)std::min<long long>(st->nadded, INT_MAX);
+    return TB_OK;
+}
+
+int tb_kf_store_work_dev(tb_kf_store* st, tb_match** matches, int32_t** match_counts, const tb_obs** rows, const int32_t** row_counts,
+                         const uint8_t** outlier, int* pitch) {
+    if (!st) return TB_EINVAL;
+    if (matches) *matches = st->matches;
+    if (match_counts) *match_counts = st->mcounts;
+    if (rows) *rows = st->obs;
+    if (row_counts) *row_counts = st->ocounts;
+    if (outlier) *outlier = st->outlier;
+    if (pitch) *pitch = st->pitch;
+    return TB_OK;
+}
+
+/* the checks both verification entry points share, and invLevelSigma2 */
+static int reloc_check(tb_kf_store* st, const char* who, int nlevels, float scale, const void* q_keys, const void* q_counts, int q_pitch,
+                       const void* cand_slot, int ncand, float* inv_sigma2) {
+    tb_ctx* ctx = st->ctx;
+    if (!q_keys || !q_counts || !cand_slot || ncand < 1 || ncand > st->max_cand || q_pitch < 1 || q_pitch > st->pitch || nlevels < 1 ||
+        nlevels > TB_MAX_LEVELS || !std::isfinite(scale))
+        return tb_fail(ctx, TB_EINVAL, "%s: ncand %d (1..%d), query pitch %d (store: %d), %d levels", who, ncand, st->max_cand, q_pitch,
+                       st->pitch, nlevels);
+    float sf[TB_MAX_LEVELS];
+    return tb_scale_factors(nlevels, scale, sf, nullptr, nullptr, inv_sigma2);
+}
+
+int tb_reloc_rows_dev(tb_kf_store* st, int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts, int q_pitch,
+                      const int32_t* cand_slot, int ncand, const int32_t* match_counts, int32_t* cand_rows) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    if (!match_counts) return tb_fail(st->ctx, TB_EINVAL, "tb_reloc_rows_dev: match_counts is required");
+    float inv_sigma2[TB_MAX_LEVELS];
+    int rc;
+    if ((rc = reloc_check(st, "tb_reloc_rows_dev", nlevels, scale, q_keys, q_counts, q_pitch, cand_slot, ncand, inv_sigma2))) return rc;
+    tb_ctx* ctx = st->ctx;
+    if ((rc = tbk_reloc_pairs(ctx, st->nseq, ncand, st->cap, cand_slot, st->kf_ids, st->Tcw, st->ix1, st->ix2, st->seed, st->ckf))) return rc;
+    return tbk_reloc_rows(ctx, st->nseq * ncand, q_keys, q_counts, q_pitch, st->ix1, st->ix2, st->matches, match_counts, st->mp, st->valid,
+                          st->counts, st->pitch, inv_sigma2, nlevels, st->obs, st->ocounts, st->outlier, cand_rows);
+}
+
+int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys,
+                            const uint8_t* q_desc, const int32_t* q_counts, const uint64_t* q_fv_keys, const int32_t* q_fv_counts,
+                            int q_pitch, const int32_t* cand_slot, int ncand, const tb_reloc_params* prm, const tb_reloc_out* out) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    if (!K || !q_desc || !q_fv_keys || !q_fv_counts || !prm || prm->histo_len < 1 || prm->histo_len > 1024 || !std::isfinite(prm->nratio))
+        return tb_fail(ctx, TB_EINVAL, "tb_relocalize_batch_dev: null arguments or searchByBow fields (histo_len %d)", prm ? prm->histo_len : 0);
+    float inv_sigma2[TB_MAX_LEVELS];
+    int rc;
+    if ((rc = reloc_check(st, "tb_relocalize_batch_dev", nlevels, scale, q_keys, q_counts, q_pitch, cand_slot, ncand, inv_sigma2))) return rc;
+    static const tb_reloc_out none = {};
+    const tb_reloc_out& o = out ? *out : none;
+    const int pairs = st->nseq * ncand;
+    int32_t* ckf = o.cand_kf ? o.cand_kf : st->ckf;
+    int32_t* mcounts = o.cand_matches ? o.cand_matches : st->mcounts;
+    int32_t* flags = o.cand_flags ? o.cand_flags : st->flags;
+    int32_t* ninl = o.cand_inliers ? o.cand_inliers : st->ninl;
+    float* pose = o.cand_Tcw ? o.cand_Tcw : st->pose;
+    if ((rc = tbk_reloc_pairs(ctx, st->nseq, ncand, st->cap, cand_slot, st->kf_ids, st->Tcw, st->ix1, st->ix2, st->seed, ckf))) return rc;
+    /* side 1 = the query frame s, side 2 = the stored keyframe s * cap + slot, both read where they lie */
+    if ((rc = tbk_bow_search_batch(ctx, pairs, q_keys, q_desc, q_pitch, (const unsigned long long*)q_fv_keys, q_fv_counts, st->keys, st->desc,
+                                   st->pitch, (const unsigned long long*)st->fv, st->fv_counts, st->valid, prm->map_point_only, prm->th_low,
+                                   prm->nratio, prm->histo_len, prm->check_orientation, st->matches, st->pitch, mcounts, flags, st->best,
+                                   st->ix1, st->ix2)))
+        return rc;
+    if ((rc = tbk_reloc_rows(ctx, pairs, q_keys, q_counts, q_pitch, st->ix1, st->ix2, st->matches, mcounts, st->mp, st->valid, st->counts,
+                             st->pitch, inv_sigma2, nlevels, st->obs, st->ocounts, st->outlier, o.cand_rows)))
+        return rc;
+    if ((rc = tbk_pose_batch(ctx, pairs, K, st->seed, st->obs, st->ocounts, st->pitch, st->outlier, pose, ninl, nullptr, st->err))) return rc;
+    if (mcounts != st->mcounts)   /* tb_kf_store_work_dev lends the last call's counts */
+        TB_HIP(ctx, hipMemcpyAsync(st->mcounts, mcounts, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    if (!o.best_rank && !o.best_kf && !o.best_Tcw) return TB_OK;
+    return tbk_reloc_select(ctx, st->nseq, ncand, prm->min_inliers, ckf, ninl, pose, o.best_rank, o.best_kf, o.best_Tcw);
+}
+
 int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int n, int levelsup, int32_t* word_ids, double* weights,
                      int32_t* node_ids) {
     TB_ENTER(ctx);
@@ -2036,6 +2232,10 @@ struct tb_vo {
     double* bv_val[2] = {nullptr, nullptr};         /* [nseq][P] BowVector values */
     int32_t* bv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
     tb_bow_db* db = nullptr;                        /* the keyframe database (tb_vo_bow_db_enable), owned */
+    /* relocalisation (tb_vo_reloc_enable): the keyframe store, owned, and the query's outputs a caller does not take */
+    tb_kf_store* store = nullptr;
+    double *rl_scores = nullptr, *rl_top_score = nullptr;   /* [nseq][capacity], [nseq][max_candidates] */
+    int32_t *rl_top_slot = nullptr, *rl_top_kf = nullptr;   /* [nseq][max_candidates] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -2046,6 +2246,8 @@ void tb_vo_destroy(tb_vo* vo) {
     hipStreamSynchronize(vo->ctx->stream);
     if (vo->ex) tb_extractor_destroy(vo->ex);
     tb_bow_db_destroy(vo->db);
+    tb_kf_store_destroy(vo->store);
+    hipFree(vo->rl_scores); hipFree(vo->rl_top_score); hipFree(vo->rl_top_slot); hipFree(vo->rl_top_kf);
     for (int k = 0; k < 2; k++) {
         hipFree(vo->img[k]); hipFree(vo->keys[k]); hipFree(vo->kcnt[k]); hipFree(vo->mp[k]); hipFree(vo->valid[k]); hipFree(vo->Tcw[k]);
     }
@@ -2278,6 +2480,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
         int rc;
         if (vo->db && (rc = tb_bow_db_clear(vo->db))) return rc;   /* a new run: no keyframes yet */
+        if (vo->store && (rc = tb_kf_store_clear(vo->store))) return rc;
     }
     if (vo->mapK) {   /* an empty map */
         TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
@@ -2370,6 +2573,10 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
             TB_HIP(ctx, hipMemcpyAsync(vo->bv_cnt[1], vo->bv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
             /* the keyframe database, when enabled: the snapshot's BowVector into the ring slot of this keyframe */
             if (vo->db && (rc = tb_bow_db_add_dev(vo->db, vo->bv_word[1], vo->bv_val[1], vo->bv_cnt[1], P, t))) return rc;
+            /* the keyframe store, when enabled: the snapshot itself and the frame's optimised pose into the same ring slot */
+            if (vo->store && (rc = tb_kf_store_add_dev(vo->store, vo->kf_orb, vo->kf_desc, vo->kf_cnt, vo->fv_keys[1], vo->fv_cnt[1], vo->kf_mp,
+                                                       vo->kf_valid, P, vo->Tcw[b], t)))
+                return rc;
         }
         vo->kf_frame = t;
     }
@@ -2597,6 +2804,55 @@ int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out) {
     *out = nullptr;
     if (!vo->db) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_get: the keyframe database is not enabled");
     *out = vo->db;
+    return TB_OK;
+}
+
+int tb_vo_reloc_enable(tb_vo* vo, int max_candidates) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (vo->tr.kind != TB_VO_BOW) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: the loop does not track by searchByBow");
+    if (!vo->db) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: the keyframe database is not enabled (tb_vo_bow_db_enable)");
+    if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable after a step (frame %d)", vo->next - 1);
+    if (vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: relocalisation is enabled already");
+    int rc = tb_kf_store_create(ctx, vo->nseq, vo->db->cap, vo->P, max_candidates, &vo->store);
+    if (rc) return rc;
+    const size_t S = (size_t)vo->nseq;
+    TB_HIP(ctx, hipMalloc(&vo->rl_scores, S * vo->db->cap * sizeof(double)));
+    TB_HIP(ctx, hipMalloc(&vo->rl_top_score, S * max_candidates * sizeof(double)));
+    TB_HIP(ctx, hipMalloc(&vo->rl_top_slot, S * max_candidates * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rl_top_kf, S * max_candidates * sizeof(int32_t)));
+    return TB_OK;
+}
+
+int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
+                         double* top_score, int32_t* top_count, const tb_reloc_out* out) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_dev: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->next < 1) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_dev before the first step");
+    if (topk < 1 || topk > vo->store->max_cand || exclude_newest < 0)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_relocalize_dev: topk %d (1..%d), exclude_newest %d", topk, vo->store->max_cand, exclude_newest);
+    if (!scores) scores = vo->rl_scores;
+    if (!top_slot) top_slot = vo->rl_top_slot;
+    if (!top_kf) top_kf = vo->rl_top_kf;
+    if (!top_score) top_score = vo->rl_top_score;
+    int rc = tb_bow_db_query_dev(vo->db, vo->bv_word[0], vo->bv_val[0], vo->bv_cnt[0], vo->P, exclude_newest, topk, scores, top_slot, top_kf,
+                                 top_score, top_count);
+    if (rc) return rc;
+    tb_reloc_params prm;
+    prm.map_point_only = vo->bw.map_point_only; prm.th_low = vo->bw.th_low; prm.nratio = vo->bw.nratio; prm.histo_len = vo->bw.histo_len;
+    prm.check_orientation = vo->bw.check_orientation; prm.min_inliers = min_inliers;
+    return tb_relocalize_batch_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, vo->orb, vo->orb_desc, vo->orb_cnt, vo->fv_keys[0],
+                                   vo->fv_cnt[0], vo->P, top_slot, topk, &prm, out);
+}
+
+int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out) {
+    if (!vo || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (!vo->store) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_kf_store_get: relocalisation is not enabled");
+    *out = vo->store;
     return TB_OK;
 }
 

@@ -214,7 +214,22 @@ int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const do
 int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, int pitch1, const unsigned long long* d_fv1,
                          const int32_t* d_n1, const tb_keypoint* d_k2, const uint8_t* d_d2, int pitch2, const unsigned long long* d_fv2,
                          const int32_t* d_n2, const uint8_t* d_has_mp2, int map_point_only, int th_low, float nratio, int histo_len,
-                         int check_orientation, tb_match* d_out, int cap, int32_t* d_out_counts, int32_t* d_flags, int32_t* d_best);
+                         int check_orientation, tb_match* d_out, int cap, int32_t* d_out_counts, int32_t* d_flags, int32_t* d_best,
+                         const int32_t* d_ix1 = nullptr, const int32_t* d_ix2 = nullptr);
+/* the keyframe store and candidate verification (k_reloc.hip); d_ix1 / d_ix2 above: the frame pair p reads on each side */
+int tbk_kf_store_add(tb_ctx* ctx, int nseq, const tb_keypoint* d_keys, const uint8_t* d_desc, const int32_t* d_counts,
+                     const unsigned long long* d_fv, const int32_t* d_fv_counts, const float* d_mp, const uint8_t* d_valid, int src_pitch,
+                     const float* d_Tcw, int32_t kf_id, int cap, int pitch, int slot, tb_keypoint* s_keys, uint8_t* s_desc,
+                     unsigned long long* s_fv, float* s_mp, uint8_t* s_valid, float* s_Tcw, int32_t* s_counts, int32_t* s_fv_counts,
+                     int32_t* s_kf_ids);
+int tbk_reloc_pairs(tb_ctx* ctx, int nseq, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids, const float* d_kf_Tcw,
+                    int32_t* d_ix1, int32_t* d_ix2, float* d_seed, int32_t* d_cand_kf);
+int tbk_reloc_rows(tb_ctx* ctx, int npairs, const tb_keypoint* d_q_keys, const int32_t* d_q_counts, int q_pitch, const int32_t* d_ix1,
+                   const int32_t* d_ix2, const tb_match* d_matches, const int32_t* d_match_counts, const float* d_kf_mp,
+                   const uint8_t* d_kf_valid, const int32_t* d_kf_counts, int pitch, const float* inv_sigma2, int nlevels, tb_obs* d_obs,
+                   int32_t* d_obs_counts, uint8_t* d_outlier, int32_t* d_rows_out);
+int tbk_reloc_select(tb_ctx* ctx, int nseq, int ncand, int min_inliers, const int32_t* d_cand_kf, const int32_t* d_cand_inliers,
+                     const float* d_cand_Tcw, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_Tcw);
 /* BowVector scoring and the keyframe database's kernels (k_bow_score.hip): query i of na meets entries i * bq + j, j in [0, nj),
  * out [na][nj]; ring != 0: the entries are ring slots, of which nfilled are in use, the last add went to `newest`, and the
  * `exclude` newest adds are left out (their out is a quiet NaN) */

@@ -19,6 +19,9 @@ synth.Vocabulary (uploaded and owned by the loop), a callable `f(context) -> han
 `context.vocab_train_dev`; the loop owns the handle), or a handle made on the `context=` the loop was given (borrowed).
 `keyframe_db=N` keeps the BowVectors of the last N keyframes of every sequence in a device-resident database that
 `query_keyframes` scores the current frame against (TemplatedVocabulary::score), for loop and relocalisation candidates.
+`relocalize=M` (with keyframe_db=N) also keeps those keyframes themselves -- keys, descriptors, FeatureVector, map points, pose --
+in a device-resident store, and `relocalize()` verifies the best M candidates on the device: searchByBow against each stored
+keyframe, PoseOptimization seeded with its pose, the candidate with the most inliers. It is a query: the loop's state stays.
 
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
@@ -87,11 +90,13 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
         if keyframe_db and tracker != "bow":
             raise TypeError("keyframe_db= needs tracker 'bow': the database holds the keyframes' BowVectors")
+        if relocalize and not keyframe_db:
+            raise TypeError("relocalize= needs keyframe_db=N: the candidates come from the keyframe database")
         if tracker == "bow" and vocab is None:
             raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
         if tracker != "bow" and vocab is not None:
@@ -110,6 +115,7 @@ class StereoVO:
             context.set_stream(self.stream.cuda_stream)
         self.vocab, self._own_vocab = None, False
         self.db = None          # the keyframe database (keyframe_db=N), borrowed from the loop
+        self.store = None       # the keyframe store (relocalize=M), borrowed from the loop
         prm = capi.VOParams(self.width, self.height, int(nlevels), float(scale), int(target), float(init_th), float(min_th),
                             (C.c_double * 4)(*[float(k) for k in K]), float(bf), self.keyframe_every)
         self.params, self.tracker = prm, tracker
@@ -131,6 +137,9 @@ class StereoVO:
                     if keyframe_db:               # 0 = off: no call is made
                         self.ctx.check(self.vo.bow_db_enable(keyframe_db))
                         self.db = self.vo.bow_db()
+                        if relocalize:                # 0 = off: no call is made
+                            self.ctx.check(self.vo.reloc_enable(relocalize))
+                            self.store = self.vo.kf_store()
                 else:
                     self.vo = capi.VO(self.ctx, prm, self.S, trk)
             except Exception:
@@ -142,6 +151,7 @@ class StereoVO:
 
     def close(self):
         self.db = None                       # borrowed: it goes with the loop
+        self.store = None
         if getattr(self, "vo", None) is not None:
             self.vo.close()
             self.vo = None
@@ -335,6 +345,37 @@ class StereoVO:
         d = self.vo.bow_state_dev()
         with torch.cuda.stream(self.stream):
             out = db.query_ptr(d["bv_words"], d["bv_values"], d["bv_counts"], self.key_pitch, topk, exclude_newest, self.dev)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        return out
+
+    # ---- relocalisation (tracker "bow", keyframe_db=N, relocalize=M): the keyframes themselves and candidate verification
+    def _need_store(self):
+        if self.store is None:
+            raise capi.TBError(capi.TB_ESTATE, "relocalisation is off: StereoVO(..., tracker='bow', keyframe_db=N, relocalize=M)")
+        return self.store
+
+    def keyframe_store(self):
+        """dict(keys [S, N, P, 7] int32 records, desc [S, N, P, 32], fv_keys [S, N, P] int64, map_points [S, N, P, 3], mp_valid
+        [S, N, P], counts / fv_counts / kf_ids [S, N] with kf_id -1 = an empty slot, Tcw [S, N, 4, 4], nadded): slot a % N holds
+        keyframe number a as its snapshot was, with the pose its frame was given"""
+        st = self._need_store()
+        with torch.cuda.stream(self.stream):
+            out = st.state(self.dev)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        return out
+
+    def relocalize(self, topk=4, exclude_newest=1, min_inliers=50):
+        """Verify the database's best topk candidates for the current frame: searchByBow against each stored keyframe, the rows
+        through its map points, PoseOptimization seeded with its pose. Device tensors: query_keyframes' dict plus cand_kf /
+        cand_matches / cand_rows / cand_inliers / cand_flags [S, topk] int32, cand_Tcw [S, topk, 4, 4], best_rank / best_kf [S]
+        (-1: no candidate reached min_inliers -- ORB-SLAM's figure is 50; the reference has no such step) and best_Tcw [S, 4, 4]
+        (the identity when -1). A query: the loop's pose, points and keyframe stay. No host synchronisation."""
+        self._need_store()
+        with torch.cuda.stream(self.stream):
+            rc, out = self.vo.relocalize_dev(topk, exclude_newest, min_inliers, self.db.capacity, self.dev)
+        self.ctx.check(rc)
         torch.cuda.current_stream(self.dev).wait_stream(self.stream)
         for t in out.values():
             t.record_stream(self.stream)
