@@ -736,12 +736,47 @@ int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out);
  * tb_vo_bow fields. It changes neither the loop's pose nor its carried points nor its keyframe, and makes no host synchronisation
  * and no host <-> device copy. scores [nseq][capacity], top_slot / top_kf / top_score [nseq][topk] and top_count [nseq] are the
  * query's outputs (each nullable: the loop has buffers of its own); topk in 1..max_candidates. TB_ESTATE: not enabled, or before
- * the first step. Adopting the pose after a loss, loop correction, and ORB-SLAM's second stage (searchByProjection with the
- * recovered pose) are not part of it. tb_vo_kf_store_get lends the store (TB_ESTATE when not enabled). */
+ * the first step. Loop correction and ORB-SLAM's second stage (searchByProjection with the recovered pose) are not part of it;
+ * adopting the pose after a loss is tb_vo_recover_enable's. tb_vo_kf_store_get lends the store (TB_ESTATE when not enabled). */
 int tb_vo_reloc_enable(tb_vo* vo, int max_candidates);
 int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
                          double* top_score, int32_t* top_count, const tb_reloc_out* out);
 int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
+/* Recovery in a TB_VO_BOW loop with relocalisation (off unless enabled; a loop that does not enable it launches what it launched
+ * before): a sequence that loses track adopts the relocalisation pose and tracks against the keyframe that gave it. The reference
+ * has no such step; every operator is the reference's -- searchByBow (matcher.cpp:619-721), PoseOptimization and its rows
+ * (LocalBA.cpp:291-490, :333-363) -- and the composition is this library's (tests/vo_recover_reference.py restates it on the CPU
+ * oracle). At frame t > 0, after the tracking step's pose optimisation and before the keyframe block:
+ *   flag    lost[s] = n_inliers[s] < lost_inliers; track_inliers[s] = n_inliers[s]
+ *   query   tb_bow_db_query_dev(topk, exclude_newest) with the current BowVectors, as tb_vo_relocalize_dev
+ *   mask    a copy of top_slot in which a sequence that is not lost has -1 throughout: its pairs read nothing and can never win
+ *   verify  tb_relocalize_batch_dev on the masked slots with the loop's tb_vo_bow fields and min_inliers
+ *   adopt   where lost[s] and best_rank[s] >= 0: Tcw = best_Tcw; the carried map points are those of the winning pair's matches
+ *           by the rows rule above (the last match in list order wins a key; the failed step's points are dropped; outlier rows
+ *           keep theirs); obs, obs_counts, outlier, n_inliers, matches, match_counts and flags are the pair's;
+ *           recovered_kf[s] = best_kf[s]. Every other sequence: recovered_kf -1 and no other byte of its state changes
+ *   switch  an adopting sequence's rows of the keyframe snapshot (tb_vo_tracker_state_dev's kf_*, tb_vo_bow_state_dev's kf_*) take
+ *           the winning ring slot: the store's arrays, the database's BowVector and the word / node ids of two rings
+ *           [nseq][capacity][key_pitch] the loop fills at every keyframe step; kf_ids[s] = best_kf[s]. Live entries only
+ * then, on a keyframe step, the keyframe block as before: the frame spawns its stereo points at the adopted pose, becomes the
+ * keyframe of every sequence (kf_ids[s] = t) and goes into the database, the store and the rings. The stage is on the context's
+ * stream: no host synchronisation, no host <-> device copy; which sequences adopt is decided by device predicates alone.
+ * tb_vo_tracker_state_dev's *kf_frame stays the last keyframe step. tb_vo_reset_dev clears the state (flags 0, ids -1).
+ * tb_vo_recover_enable allocates every buffer. TB_ESTATE: relocalisation not enabled, after the first step, or enabled already;
+ * TB_EINVAL: null params, lost_inliers < 0, min_inliers < 0, exclude_newest < 0, topk outside 1..max_candidates.
+ * tb_vo_recover_state_dev: device views, each nullable (TB_ESTATE when not enabled): lost [nseq] and track_inliers [nseq] of the
+ * last step (the tracker's own count, before any adoption), recovered_kf [nseq] (the adopted keyframe's kf_id, or -1), kf_ids
+ * [nseq] (the frame index of the keyframe each sequence now tracks against, -1 before any), and the rings kf_word_ring /
+ * kf_node_ring [nseq][capacity][key_pitch], slot-aligned with the store. */
+typedef struct tb_vo_recover {
+    int lost_inliers;     /* a sequence is lost at frame t > 0 when the tracking step's n_inliers < lost_inliers */
+    int topk;             /* candidates per lost sequence, 1..max_candidates of tb_vo_reloc_enable */
+    int exclude_newest;   /* as tb_bow_db_query_dev */
+    int min_inliers;      /* as tb_reloc_params */
+} tb_vo_recover;
+int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm);
+int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** track_inliers, const int32_t** recovered_kf,
+                            const int32_t** kf_ids, const int32_t** kf_word_ring, const int32_t** kf_node_ring);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

@@ -50,7 +50,7 @@ EXPORTS = [
     "tb_bow_db_query_dev", "tb_bow_db_state_dev", "tb_vo_bow_db_enable", "tb_vo_bow_db_get",
     "tb_kf_store_create", "tb_kf_store_destroy", "tb_kf_store_clear", "tb_kf_store_add_dev", "tb_kf_store_state_dev",
     "tb_kf_store_work_dev", "tb_relocalize_batch_dev", "tb_reloc_rows_dev", "tb_vo_reloc_enable", "tb_vo_relocalize_dev",
-    "tb_vo_kf_store_get",
+    "tb_vo_kf_store_get", "tb_vo_recover_enable", "tb_vo_recover_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -219,6 +219,11 @@ class VOBow(C.Structure):
                 ("check_orientation", C.c_int)]
 
 
+class VORecover(C.Structure):
+    """tb_vo_recover of include/tb_capi.h"""
+    _fields_ = [("lost_inliers", C.c_int), ("topk", C.c_int), ("exclude_newest", C.c_int), ("min_inliers", C.c_int)]
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
@@ -328,6 +333,19 @@ class VO:
                                         p(q["top_kf"]), p(q["top_score"]), p(q["top_count"]), C.byref(ro))
         q.update(out)
         return rc, q
+
+    def recover_enable(self, prm):
+        """tb_vo_recover_enable with a VORecover (None: a null pointer): returns the status code (0 or a negative TB_E* code), so
+        the state and argument checks can be tested."""
+        return lib().tb_vo_recover_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def recover_state_dev(self):
+        """tb_vo_recover_state_dev: dict of device pointers (lost, track_inliers, recovered_kf, kf_ids, kf_word_ring,
+        kf_node_ring); TB_ESTATE when recovery is not enabled."""
+        names = ("lost", "track_inliers", "recovered_kf", "kf_ids", "kf_word_ring", "kf_node_ring")
+        ptrs = [C.c_void_p() for _ in names]
+        self.ctx.check(lib().tb_vo_recover_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        return {k: q.value for k, q in zip(names, ptrs)}
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""

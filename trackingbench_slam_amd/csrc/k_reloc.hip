@@ -181,6 +181,179 @@ k_reloc_select(int nseq, int ncand, int min_inliers, const int32_t* __restrict__
             best_Tcw[16 * (size_t)s + i] = best >= 0 ? cand_Tcw[16 * ((size_t)s * ncand + best) + i] : ((i & 3) == (i >> 2) ? 1.f : 0.f);
 }
 
+/* ---- recovery in the VO loop (tb_vo_recover_enable): a lost sequence adopts the verification's winner. All masking is by the
+ * device predicates below; a sequence that does not adopt keeps every byte of its state. */
+
+/* Entry i = s * topk + r: lost[s] = n_inliers[s] < lost_inliers and the tracker's own count (written once per sequence), and the
+ * masked copy of the query's top_slot: a sequence that is not lost has no candidate, so its pairs read nothing. */
+__global__ void __launch_bounds__(256)
+k_vo_recover_mask(int nseq, int topk, int lost_inliers, const int32_t* __restrict__ n_inliers, const int32_t* __restrict__ top_slot,
+                  uint8_t* __restrict__ lost, int32_t* __restrict__ track_inliers, int32_t* __restrict__ masked) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nseq * topk) return;
+    const int s = i / topk, ni = n_inliers[s];
+    const bool l = ni < lost_inliers;
+    masked[i] = l ? top_slot[i] : -1;
+    if (i == s * topk) { lost[s] = l ? 1 : 0; track_inliers[s] = ni; }
+}
+
+/* The pair sequence s adopts: c = s * topk + best_rank[s] where the sequence is lost and the selection has an answer, else -1
+ * (wave-uniform: one sequence per workgroup). *f = the winner's frame index s * cap + slot in the store. */
+struct VoRecoverPick {
+    const uint8_t* lost;            /* [nseq] */
+    const int32_t *best_rank, *ix2; /* [nseq], [nseq * topk] */
+    int topk;
+};
+__device__ __forceinline__ int recover_pair(const VoRecoverPick& W, int s, int* f) {
+    const int r = W.lost[s] ? W.best_rank[s] : -1;
+    const int c = r >= 0 && r < W.topk ? s * W.topk + r : -1;
+    *f = c >= 0 ? W.ix2[c] : -1;
+    return *f >= 0 ? c : -1;
+}
+
+struct VoRecoverWork {   /* the store's work buffers after tb_relocalize_batch_dev, pair-major at the store's pitch */
+    const tb_match* matches;
+    const tb_obs* obs;
+    const uint8_t* outlier;
+    const int32_t *mcounts, *flags, *ocounts, *ninl;
+    const float* kf_mp;         /* the store's rings: [nseq][cap][pitch][3] */
+    const uint8_t* kf_valid;
+    const int32_t* kf_counts;
+    const int32_t* best_kf;     /* [nseq] */
+    const float* best_Tcw;      /* [nseq][16] */
+};
+struct VoRecoverState {  /* the loop's state of the current frame, [nseq][pitch] */
+    float* Tcw;
+    float* mp;
+    uint8_t* valid;
+    tb_obs* obs;
+    uint8_t* outlier;
+    tb_match* matches;
+    int32_t *obs_counts, *n_inliers, *mcounts, *mflags, *recovered_kf;
+};
+
+/* Adopt (one workgroup per sequence): the winner's pose; the carried map points by k_reloc_rows' rule, which is
+ * k_vo_match_carry's -- every key loses its point, then every match whose stored entry has a map point gives its query key that
+ * point, the last such match in list order winning a key (win[], in LDS: one int per query key), so the points of the failed
+ * tracking step are dropped and outlier rows keep theirs --; the pair's rows, outlier flags, inlier count and match list.
+ * Every other sequence: recovered_kf -1 and nothing else. The loop's arrays and the store's share one pitch. */
+__global__ void __launch_bounds__(256)
+k_vo_recover_adopt(VoRecoverPick W, VoRecoverWork A, const int32_t* __restrict__ q_counts, int pitch, VoRecoverState D) {
+    extern __shared__ int win[];   /* [pitch] */
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int f;
+    const int c = recover_pair(W, s, &f);
+    if (c < 0) {
+        if (tid == 0) D.recovered_kf[s] = -1;
+        return;
+    }
+    const int n = min(max(q_counts[s], 0), pitch);
+    const int nm = min(max(A.mcounts[c], 0), pitch);
+    const int nk = min(max(A.kf_counts[f], 0), pitch);
+    const int nr = min(max(A.ocounts[c], 0), pitch);
+    const size_t o = (size_t)s * pitch, oc = (size_t)c * pitch, of = (size_t)f * pitch;
+    const tb_match* M = A.matches + oc;
+    for (int i = tid; i < n; i += 256) win[i] = -1;
+    __syncthreads();
+    for (int k = tid; k < nm; k += 256) {
+        const int q = M[k].queryIdx, tr = M[k].trainIdx;
+        if (q >= 0 && q < n && tr >= 0 && tr < nk && A.kf_valid[of + tr]) atomicMax(&win[q], k);
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int k = win[i];
+        float X = 0.f, Y = 0.f, Z = 0.f;
+        if (k >= 0) {
+            const size_t j = of + M[k].trainIdx;
+            X = A.kf_mp[3 * j]; Y = A.kf_mp[3 * j + 1]; Z = A.kf_mp[3 * j + 2];
+        }
+        D.mp[3 * (o + i)] = X; D.mp[3 * (o + i) + 1] = Y; D.mp[3 * (o + i) + 2] = Z;
+        D.valid[o + i] = k >= 0 ? 1 : 0;
+    }
+    kf_copy(D.obs + o, A.obs + oc, (size_t)nr * sizeof(tb_obs), tid);
+    kf_copy(D.outlier + o, A.outlier + oc, (size_t)n, tid);
+    kf_copy(D.matches + o, M, (size_t)nm * sizeof(tb_match), tid);
+    if (tid < 16) D.Tcw[16 * (size_t)s + tid] = A.best_Tcw[16 * (size_t)s + tid];
+    if (tid == 0) {
+        D.obs_counts[s] = nr; D.n_inliers[s] = A.ninl[c];
+        D.mcounts[s] = nm; D.mflags[s] = A.flags[c];
+        D.recovered_kf[s] = A.best_kf[s];
+    }
+}
+
+struct VoRecoverRings {  /* what a ring slot holds: the store, the ring-aligned database slot, the loop's word / node rings */
+    const tb_keypoint* keys;
+    const uint8_t* desc;
+    const unsigned long long* fv;
+    const float* mp;
+    const uint8_t* valid;
+    const int32_t *counts, *fv_counts;
+    const int32_t* bv_word;
+    const double* bv_val;
+    const int32_t* bv_counts;
+    const int32_t *word, *node;
+    const int32_t* best_kf;
+};
+struct VoRecoverSnap {   /* the loop's keyframe snapshot, [nseq][pitch] */
+    tb_keypoint* keys;
+    uint8_t* desc;
+    unsigned long long* fv;
+    float* mp;
+    uint8_t* valid;
+    int32_t *counts, *fv_counts;
+    int32_t* bv_word;
+    double* bv_val;
+    int32_t* bv_counts;
+    int32_t *word, *node;
+    int32_t* kf_ids;
+};
+
+/* Switch the tracking keyframe: workgroup (s, g) of an adopting sequence copies array group g of the winning ring slot into the
+ * sequence's rows of the snapshot -- 0 the key records, 1 the descriptors, 2 the FeatureVector keys, 3 the map points, their
+ * validity and the counts, 4 the BowVector, 5 the word and node ids -- as k_kf_store_add moved them in: live entries only, by
+ * kf_copy's 16 / 4 / 1-byte lanes. Every other sequence: nothing. */
+__global__ void __launch_bounds__(256)
+k_vo_recover_switch(VoRecoverPick W, VoRecoverRings A, int pitch, VoRecoverSnap D) {
+    const int s = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    int f;
+    if (recover_pair(W, s, &f) < 0) return;
+    const size_t n = (size_t)min(max(A.counts[f], 0), pitch);
+    const size_t src = (size_t)f * pitch, dst = (size_t)s * pitch;
+    if (g == 0) {
+        kf_copy(D.keys + dst, A.keys + src, n * sizeof(tb_keypoint), tid);
+    } else if (g == 1) {
+        kf_copy(D.desc + 32 * dst, A.desc + 32 * src, n * 32, tid);
+    } else if (g == 2) {
+        const size_t nf = (size_t)min(max(A.fv_counts[f], 0), pitch);
+        kf_copy(D.fv + dst, A.fv + src, nf * sizeof(unsigned long long), tid);
+        if (tid == 0) D.fv_counts[s] = (int32_t)nf;
+    } else if (g == 3) {
+        kf_copy(D.mp + 3 * dst, A.mp + 3 * src, n * 3 * sizeof(float), tid);
+        kf_copy(D.valid + dst, A.valid + src, n, tid);
+        if (tid == 0) { D.counts[s] = (int32_t)n; D.kf_ids[s] = A.best_kf[s]; }
+    } else if (g == 4) {
+        const size_t nb = (size_t)min(max(A.bv_counts[f], 0), pitch);
+        kf_copy(D.bv_word + dst, A.bv_word + src, nb * sizeof(int32_t), tid);
+        kf_copy(D.bv_val + dst, A.bv_val + src, nb * sizeof(double), tid);
+        if (tid == 0) D.bv_counts[s] = (int32_t)nb;
+    } else {
+        kf_copy(D.word + dst, A.word + src, n * sizeof(int32_t), tid);
+        kf_copy(D.node + dst, A.node + src, n * sizeof(int32_t), tid);
+    }
+}
+
+/* The loop's word / node rings at a keyframe step, beside the store add: workgroup (s, g) copies the snapshot's live word
+ * (g = 0) or node (g = 1) ids of sequence s into ring slot `slot`. */
+__global__ void __launch_bounds__(256)
+k_vo_recover_ring_add(const int32_t* __restrict__ word, const int32_t* __restrict__ node, const int32_t* __restrict__ counts, int cap,
+                      int pitch, int slot, int32_t* __restrict__ word_ring, int32_t* __restrict__ node_ring) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const size_t n = (size_t)min(max(counts[s], 0), pitch);
+    const size_t src = (size_t)s * pitch, dst = ((size_t)s * cap + slot) * pitch;
+    if (blockIdx.y == 0) kf_copy(word_ring + dst, word + src, n * sizeof(int32_t), tid);
+    else kf_copy(node_ring + dst, node + src, n * sizeof(int32_t), tid);
+}
+
 int tbk_kf_store_add(tb_ctx* ctx, int nseq, const tb_keypoint* d_keys, const uint8_t* d_desc, const int32_t* d_counts,
                      const unsigned long long* d_fv, const int32_t* d_fv_counts, const float* d_mp, const uint8_t* d_valid, int src_pitch,
                      const float* d_Tcw, int32_t kf_id, int cap, int pitch, int slot, tb_keypoint* s_keys, uint8_t* s_desc,
@@ -227,6 +400,53 @@ int tbk_reloc_select(tb_ctx* ctx, int nseq, int ncand, int min_inliers, const in
     tb_prof_begin(ctx, "k_reloc_select");
     hipLaunchKernelGGL(k_reloc_select, dim3((nseq + 255) / 256), dim3(256), 0, ctx->stream, nseq, ncand, min_inliers, d_cand_kf,
                        d_cand_inliers, d_cand_Tcw, d_best_rank, d_best_kf, d_best_Tcw);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_recover_mask(tb_ctx* ctx, int nseq, int topk, int lost_inliers, const int32_t* d_n_inliers, const int32_t* d_top_slot,
+                        uint8_t* d_lost, int32_t* d_track_inliers, int32_t* d_masked) {
+    tb_prof_begin(ctx, "k_vo_recover_mask");
+    hipLaunchKernelGGL(k_vo_recover_mask, dim3((nseq * topk + 255) / 256), dim3(256), 0, ctx->stream, nseq, topk, lost_inliers, d_n_inliers,
+                       d_top_slot, d_lost, d_track_inliers, d_masked);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_recover_adopt(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
+    VoRecoverPick W = {a->lost, a->best_rank, a->ix2, a->topk};
+    VoRecoverWork A = {a->w_matches, a->w_obs, a->w_outlier, a->w_mcounts, a->w_flags, a->w_ocounts, a->w_ninl, a->s_mp, a->s_valid,
+                       a->s_counts, a->best_kf, a->best_Tcw};
+    VoRecoverState D = {a->Tcw, a->mp, a->valid, a->obs, a->outlier, a->matches, a->obs_counts, a->n_inliers, a->mcounts, a->mflags,
+                        a->recovered_kf};
+    tb_prof_begin(ctx, "k_vo_recover_adopt");
+    hipLaunchKernelGGL(k_vo_recover_adopt, dim3(nseq), dim3(256), (size_t)a->pitch * sizeof(int), ctx->stream, W, A, a->orb_counts, a->pitch,
+                       D);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_recover_switch(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
+    VoRecoverPick W = {a->lost, a->best_rank, a->ix2, a->topk};
+    VoRecoverRings A = {a->s_keys, a->s_desc, a->s_fv, a->s_mp, a->s_valid, a->s_counts, a->s_fv_counts, a->db_words, a->db_values,
+                        a->db_counts, a->word_ring, a->node_ring, a->best_kf};
+    VoRecoverSnap D = {a->kf_orb, a->kf_desc, a->kf_fv, a->kf_mp, a->kf_valid, a->kf_cnt, a->kf_fv_cnt, a->kf_bv_word, a->kf_bv_val,
+                       a->kf_bv_cnt, a->kf_word, a->kf_node, a->kf_ids};
+    tb_prof_begin(ctx, "k_vo_recover_switch");
+    hipLaunchKernelGGL(k_vo_recover_switch, dim3(nseq, 6), dim3(256), 0, ctx->stream, W, A, a->pitch, D);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_recover_ring_add(tb_ctx* ctx, int nseq, const int32_t* d_word, const int32_t* d_node, const int32_t* d_counts, int cap, int pitch,
+                            int slot, int32_t* d_word_ring, int32_t* d_node_ring) {
+    tb_prof_begin(ctx, "k_vo_recover_ring_add");
+    hipLaunchKernelGGL(k_vo_recover_ring_add, dim3(nseq, 2), dim3(256), 0, ctx->stream, d_word, d_node, d_counts, cap, pitch, slot,
+                       d_word_ring, d_node_ring);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -2236,6 +2236,16 @@ struct tb_vo {
     tb_kf_store* store = nullptr;
     double *rl_scores = nullptr, *rl_top_score = nullptr;   /* [nseq][capacity], [nseq][max_candidates] */
     int32_t *rl_top_slot = nullptr, *rl_top_kf = nullptr;   /* [nseq][max_candidates] */
+    /* recovery (tb_vo_recover_enable): the flags and the selection of the last step, the per-sequence tracking keyframe, the
+     * masked candidates, and the rings of the keyframes' word / node ids, ring-aligned with the store */
+    bool rec_on = false;
+    tb_vo_recover rec;
+    uint8_t* rc_lost = nullptr;                                          /* [nseq] */
+    int32_t *rc_track = nullptr, *rc_kf = nullptr, *rc_kf_ids = nullptr; /* [nseq] */
+    int32_t *rc_best_rank = nullptr, *rc_best_kf = nullptr;              /* [nseq] */
+    float* rc_best_Tcw = nullptr;                                        /* [nseq][16] */
+    int32_t* rc_masked = nullptr;                                        /* [nseq][topk] */
+    int32_t *rc_word_ring = nullptr, *rc_node_ring = nullptr;            /* [nseq][capacity][P] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -2248,6 +2258,8 @@ void tb_vo_destroy(tb_vo* vo) {
     tb_bow_db_destroy(vo->db);
     tb_kf_store_destroy(vo->store);
     hipFree(vo->rl_scores); hipFree(vo->rl_top_score); hipFree(vo->rl_top_slot); hipFree(vo->rl_top_kf);
+    hipFree(vo->rc_lost); hipFree(vo->rc_track); hipFree(vo->rc_kf); hipFree(vo->rc_kf_ids); hipFree(vo->rc_best_rank);
+    hipFree(vo->rc_best_kf); hipFree(vo->rc_best_Tcw); hipFree(vo->rc_masked); hipFree(vo->rc_word_ring); hipFree(vo->rc_node_ring);
     for (int k = 0; k < 2; k++) {
         hipFree(vo->img[k]); hipFree(vo->keys[k]); hipFree(vo->kcnt[k]); hipFree(vo->mp[k]); hipFree(vo->valid[k]); hipFree(vo->Tcw[k]);
     }
@@ -2464,6 +2476,8 @@ int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_bow* bow, c
     return vo_create(ctx, p, &tr, nseq, out, bow, voc);
 }
 
+static int vo_recover_clear(tb_vo* vo);
+
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     TB_ENTER((vo ? vo->ctx : nullptr));
     if (!vo || !Tcw0) return TB_EINVAL;
@@ -2481,6 +2495,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         int rc;
         if (vo->db && (rc = tb_bow_db_clear(vo->db))) return rc;   /* a new run: no keyframes yet */
         if (vo->store && (rc = tb_kf_store_clear(vo->store))) return rc;
+        if (vo->rec_on && (rc = vo_recover_clear(vo))) return rc;
     }
     if (vo->mapK) {   /* an empty map */
         TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
@@ -2489,6 +2504,59 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     }
     vo->next = 0;
     return TB_OK;
+}
+
+/* the recovery state of a new run: nothing flagged, nothing adopted, no tracking keyframe */
+static int vo_recover_clear(tb_vo* vo) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq;
+    TB_HIP(ctx, hipMemsetAsync(vo->rc_lost, 0, S, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->rc_track, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->rc_kf, 0xff, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->rc_kf_ids, 0xff, S * sizeof(int32_t), ctx->stream));
+    return TB_OK;
+}
+
+/* The recovery stage of frame t > 0 (include/tb_capi.h, tb_vo_recover): flag, query, mask, verify, adopt, switch the tracking
+ * keyframe. Every launch is on the context's stream; which sequences adopt is decided on the device. */
+static int vo_recover_stage(tb_vo* vo, int b) {
+    tb_ctx* ctx = vo->ctx;
+    tb_kf_store* st = vo->store;
+    tb_bow_db* db = vo->db;
+    const tb_vo_recover& r = vo->rec;
+    const int S = vo->nseq, P = vo->P;
+    int rc;
+    if ((rc = tb_bow_db_query_dev(db, vo->bv_word[0], vo->bv_val[0], vo->bv_cnt[0], P, r.exclude_newest, r.topk, vo->rl_scores,
+                                  vo->rl_top_slot, vo->rl_top_kf, vo->rl_top_score, nullptr)))
+        return rc;
+    if ((rc = tbk_vo_recover_mask(ctx, S, r.topk, r.lost_inliers, vo->n_inliers, vo->rl_top_slot, vo->rc_lost, vo->rc_track, vo->rc_masked)))
+        return rc;
+    tb_reloc_params prm;
+    prm.map_point_only = vo->bw.map_point_only; prm.th_low = vo->bw.th_low; prm.nratio = vo->bw.nratio; prm.histo_len = vo->bw.histo_len;
+    prm.check_orientation = vo->bw.check_orientation; prm.min_inliers = r.min_inliers;
+    tb_reloc_out out = {};
+    out.best_rank = vo->rc_best_rank; out.best_kf = vo->rc_best_kf; out.best_Tcw = vo->rc_best_Tcw;
+    if ((rc = tb_relocalize_batch_dev(st, vo->p.K, vo->p.nlevels, vo->p.scale, vo->orb, vo->orb_desc, vo->orb_cnt, vo->fv_keys[0], vo->fv_cnt[0],
+                                      P, vo->rc_masked, r.topk, &prm, &out)))
+        return rc;
+    tb_vo_recover_args a;
+    a.topk = r.topk; a.pitch = P;
+    a.lost = vo->rc_lost; a.best_rank = vo->rc_best_rank; a.best_kf = vo->rc_best_kf; a.ix2 = st->ix2; a.best_Tcw = vo->rc_best_Tcw;
+    a.w_matches = st->matches; a.w_obs = st->obs; a.w_outlier = st->outlier; a.w_mcounts = st->mcounts; a.w_flags = st->flags;
+    a.w_ocounts = st->ocounts; a.w_ninl = st->ninl;
+    a.s_keys = st->keys; a.s_desc = st->desc; a.s_fv = (const unsigned long long*)st->fv; a.s_mp = st->mp; a.s_valid = st->valid;
+    a.s_counts = st->counts; a.s_fv_counts = st->fv_counts;
+    a.db_words = db->words; a.db_values = db->values; a.db_counts = db->counts;
+    a.word_ring = vo->rc_word_ring; a.node_ring = vo->rc_node_ring;
+    a.orb_counts = vo->orb_cnt;
+    a.Tcw = vo->Tcw[b]; a.mp = vo->mp[b]; a.valid = vo->valid[b]; a.obs = vo->obs; a.outlier = vo->outlier; a.matches = vo->matches;
+    a.obs_counts = vo->obs_counts; a.n_inliers = vo->n_inliers; a.mcounts = vo->mcounts; a.mflags = vo->mflags; a.recovered_kf = vo->rc_kf;
+    a.kf_orb = vo->kf_orb; a.kf_desc = vo->kf_desc; a.kf_fv = (unsigned long long*)vo->fv_keys[1]; a.kf_mp = vo->kf_mp;
+    a.kf_valid = vo->kf_valid; a.kf_cnt = vo->kf_cnt; a.kf_fv_cnt = vo->fv_cnt[1];
+    a.kf_bv_word = vo->bv_word[1]; a.kf_bv_val = vo->bv_val[1]; a.kf_bv_cnt = vo->bv_cnt[1];
+    a.kf_word = vo->bow_word[1]; a.kf_node = vo->bow_node[1]; a.kf_ids = vo->rc_kf_ids;
+    if ((rc = tbk_vo_recover_adopt(ctx, S, &a))) return rc;
+    return tbk_vo_recover_switch(ctx, S, &a);
 }
 
 /* A descriptor tracker's frame t after the left images are in img[b] (see include/tb_capi.h, tb_vo_tracker). */
@@ -2546,6 +2614,7 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
     if (t > 0 &&
         (rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
         return rc;
+    if (vo->rec_on && t > 0 && (rc = vo_recover_stage(vo, b))) return rc;
     if (keyframe) {
         /* :774-785 extracts again on the same pyramid: the same keys, so SetKeys resizes m to m and keeps every carried map
          * point -- nothing to do. Then :800 AddMapPointsByStereo and the new map points (:802-832), as the optical-flow loop. */
@@ -2577,6 +2646,14 @@ static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
             if (vo->store && (rc = tb_kf_store_add_dev(vo->store, vo->kf_orb, vo->kf_desc, vo->kf_cnt, vo->fv_keys[1], vo->fv_cnt[1], vo->kf_mp,
                                                        vo->kf_valid, P, vo->Tcw[b], t)))
                 return rc;
+            /* recovery, when enabled: the snapshot's word / node ids into the same ring slot (the store has just counted this
+             * add); this keyframe is what every sequence tracks against from now on */
+            if (vo->rec_on) {
+                if ((rc = tbk_vo_recover_ring_add(ctx, S, vo->bow_word[1], vo->bow_node[1], vo->kf_cnt, vo->store->cap, P,
+                                                  (int)((vo->store->nadded - 1) % vo->store->cap), vo->rc_word_ring, vo->rc_node_ring)))
+                    return rc;
+                TB_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)vo->rc_kf_ids, t, (size_t)S, ctx->stream));
+            }
         }
         vo->kf_frame = t;
     }
@@ -2846,6 +2923,49 @@ int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inlier
     prm.check_orientation = vo->bw.check_orientation; prm.min_inliers = min_inliers;
     return tb_relocalize_batch_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, vo->orb, vo->orb_desc, vo->orb_cnt, vo->fv_keys[0],
                                    vo->fv_cnt[0], vo->P, top_slot, topk, &prm, out);
+}
+
+int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable after a step (frame %d)", vo->next - 1);
+    if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: recovery is enabled already");
+    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: null parameters");
+    if (prm->lost_inliers < 0 || prm->min_inliers < 0 || prm->exclude_newest < 0 || prm->topk < 1 || prm->topk > vo->store->max_cand)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: lost_inliers %d, topk %d (1..%d), exclude_newest %d, min_inliers %d",
+                       prm->lost_inliers, prm->topk, vo->store->max_cand, prm->exclude_newest, prm->min_inliers);
+    const size_t S = (size_t)vo->nseq, ring = S * vo->store->cap * vo->P;
+    TB_HIP(ctx, hipMalloc(&vo->rc_lost, S));
+    TB_HIP(ctx, hipMalloc(&vo->rc_track, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_kf, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_kf_ids, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_best_rank, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_best_kf, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_best_Tcw, S * 16 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_masked, S * prm->topk * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_word_ring, ring * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rc_node_ring, ring * sizeof(int32_t)));
+    int rc = vo_recover_clear(vo);
+    if (rc) return rc;
+    vo->rec = *prm;
+    vo->rec_on = true;
+    return TB_OK;
+}
+
+int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** track_inliers, const int32_t** recovered_kf,
+                            const int32_t** kf_ids, const int32_t** kf_word_ring, const int32_t** kf_node_ring) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->rec_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_recover_state_dev: recovery is not enabled (tb_vo_recover_enable)");
+    if (lost) *lost = vo->rc_lost;
+    if (track_inliers) *track_inliers = vo->rc_track;
+    if (recovered_kf) *recovered_kf = vo->rc_kf;
+    if (kf_ids) *kf_ids = vo->rc_kf_ids;
+    if (kf_word_ring) *kf_word_ring = vo->rc_word_ring;
+    if (kf_node_ring) *kf_node_ring = vo->rc_node_ring;
+    return TB_OK;
 }
 
 int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out) {

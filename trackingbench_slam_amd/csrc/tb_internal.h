@@ -230,6 +230,28 @@ int tbk_reloc_rows(tb_ctx* ctx, int npairs, const tb_keypoint* d_q_keys, const i
                    int32_t* d_obs_counts, uint8_t* d_outlier, int32_t* d_rows_out);
 int tbk_reloc_select(tb_ctx* ctx, int nseq, int ncand, int min_inliers, const int32_t* d_cand_kf, const int32_t* d_cand_inliers,
                      const float* d_cand_Tcw, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_Tcw);
+/* recovery in the VO loop (k_reloc.hip): every array at one pitch, the loop's key pitch. The pick (which pair a sequence adopts),
+ * the store's work buffers and rings, the ring-aligned database, the loop's word / node rings, and the loop's state and snapshot. */
+struct tb_vo_recover_args {
+    int topk, pitch;
+    const uint8_t* lost; const int32_t *best_rank, *best_kf, *ix2; const float* best_Tcw;
+    const tb_match* w_matches; const tb_obs* w_obs; const uint8_t* w_outlier; const int32_t *w_mcounts, *w_flags, *w_ocounts, *w_ninl;
+    const tb_keypoint* s_keys; const uint8_t* s_desc; const unsigned long long* s_fv; const float* s_mp; const uint8_t* s_valid;
+    const int32_t *s_counts, *s_fv_counts;
+    const int32_t* db_words; const double* db_values; const int32_t* db_counts;
+    const int32_t *word_ring, *node_ring;
+    const int32_t* orb_counts;
+    float *Tcw, *mp; uint8_t* valid; tb_obs* obs; uint8_t* outlier; tb_match* matches;
+    int32_t *obs_counts, *n_inliers, *mcounts, *mflags, *recovered_kf;
+    tb_keypoint* kf_orb; uint8_t* kf_desc; unsigned long long* kf_fv; float* kf_mp; uint8_t* kf_valid; int32_t *kf_cnt, *kf_fv_cnt;
+    int32_t* kf_bv_word; double* kf_bv_val; int32_t* kf_bv_cnt; int32_t *kf_word, *kf_node, *kf_ids;
+};
+int tbk_vo_recover_mask(tb_ctx* ctx, int nseq, int topk, int lost_inliers, const int32_t* d_n_inliers, const int32_t* d_top_slot,
+                        uint8_t* d_lost, int32_t* d_track_inliers, int32_t* d_masked);
+int tbk_vo_recover_adopt(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a);
+int tbk_vo_recover_switch(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a);
+int tbk_vo_recover_ring_add(tb_ctx* ctx, int nseq, const int32_t* d_word, const int32_t* d_node, const int32_t* d_counts, int cap, int pitch,
+                            int slot, int32_t* d_word_ring, int32_t* d_node_ring);
 /* BowVector scoring and the keyframe database's kernels (k_bow_score.hip): query i of na meets entries i * bq + j, j in [0, nj),
  * out [na][nj]; ring != 0: the entries are ring slots, of which nfilled are in use, the last add went to `newest`, and the
  * `exclude` newest adds are left out (their out is a quiet NaN) */

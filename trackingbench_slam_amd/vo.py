@@ -22,6 +22,9 @@ synth.Vocabulary (uploaded and owned by the loop), a callable `f(context) -> han
 `relocalize=M` (with keyframe_db=N) also keeps those keyframes themselves -- keys, descriptors, FeatureVector, map points, pose --
 in a device-resident store, and `relocalize()` verifies the best M candidates on the device: searchByBow against each stored
 keyframe, PoseOptimization seeded with its pose, the candidate with the most inliers. It is a query: the loop's state stays.
+`recover=True` (or a dict, see RECOVER_DEFAULTS; with relocalize=M) makes the loop use it: a sequence whose tracking step keeps
+fewer than lost_inliers inliers is relocalised inside the step, adopts the winner's pose, matches and map points, and tracks
+against the winning keyframe from then on. Which sequences do is decided on the device; the others are untouched.
 
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
@@ -54,6 +57,10 @@ TRACKER_DEFAULTS = {
     # :706 setBowParam(50, 100, 30, true, 6); :711 searchByBow(cur, key_frame, true); Frame.cpp:269 levelsup 4
     "bow": dict(levelsup=4, map_point_only=True, th_low=50, nratio=6.0, histo_len=30, check_orientation=True),
 }
+# recover=True. ORB-SLAM-style figures, NOT the reference's (it has no relocalisation): tracking counts as lost below 30 inliers
+# (ORB-SLAM's local-map tracking asks for 30), a candidate is accepted from 50 inliers on (its relocalisation's figure), the best
+# 4 candidates are verified and the keyframe being tracked against is left out of them.
+RECOVER_DEFAULTS = dict(lost_inliers=30, topk=4, exclude_newest=1, min_inliers=50)
 # test_vo_1's searchByBow arguments (:207 setBowParam(30, ..., 5), :212 MapPointOnly false)
 BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
@@ -90,13 +97,21 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
         if keyframe_db and tracker != "bow":
             raise TypeError("keyframe_db= needs tracker 'bow': the database holds the keyframes' BowVectors")
         if relocalize and not keyframe_db:
             raise TypeError("relocalize= needs keyframe_db=N: the candidates come from the keyframe database")
+        if recover and not relocalize:
+            raise TypeError("recover= needs relocalize=M: a lost sequence adopts the verified candidate's pose")
+        if recover:
+            unknown = set(recover) - set(RECOVER_DEFAULTS) if isinstance(recover, dict) else ()
+            if unknown:
+                raise TypeError("recover= takes no parameter %s" % ", ".join(sorted(unknown)))
+            recover = dict(RECOVER_DEFAULTS, **(recover if isinstance(recover, dict) else {}))
+        self.recover = recover or None
         if tracker == "bow" and vocab is None:
             raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
         if tracker != "bow" and vocab is not None:
@@ -140,6 +155,9 @@ class StereoVO:
                         if relocalize:                # 0 = off: no call is made
                             self.ctx.check(self.vo.reloc_enable(relocalize))
                             self.store = self.vo.kf_store()
+                            if recover:               # None = off: no call is made
+                                self.ctx.check(self.vo.recover_enable(capi.VORecover(*[int(recover[k]) for k in (
+                                    "lost_inliers", "topk", "exclude_newest", "min_inliers")])))
                 else:
                     self.vo = capi.VO(self.ctx, prm, self.S, trk)
             except Exception:
@@ -380,6 +398,25 @@ class StereoVO:
         for t in out.values():
             t.record_stream(self.stream)
         return out
+
+    def recovery(self):
+        """The recovery state after the last step (recover=...): dict(lost [S] uint8 and track_inliers [S] int32 -- the tracker's own
+        inlier count, before any adoption --, recovered_kf [S] int32 = the frame index of the keyframe the sequence adopted in
+        this step or -1, kf_ids [S] int32 = the frame index of the keyframe each sequence tracks against). TB_ESTATE when off."""
+        if self.recover is None:
+            raise capi.TBError(capi.TB_ESTATE, "recovery is off: StereoVO(..., keyframe_db=N, relocalize=M, recover=True)")
+        d = self.vo.recover_state_dev()
+        i32 = ((self.S,), "<i4", torch.int32)
+        return dict(lost=self._pget(d["lost"], (self.S,), "|u1", torch.uint8), track_inliers=self._pget(d["track_inliers"], *i32),
+                    recovered_kf=self._pget(d["recovered_kf"], *i32), kf_ids=self._pget(d["kf_ids"], *i32))
+
+    def recovery_rings(self):
+        """(word ids, node ids) [S, N, P] int32 of the stored keyframes, slot-aligned with keyframe_store()"""
+        if self.recover is None:
+            raise capi.TBError(capi.TB_ESTATE, "recovery is off: StereoVO(..., keyframe_db=N, relocalize=M, recover=True)")
+        d = self.vo.recover_state_dev()
+        sh = ((self.S, self.db.capacity, self.key_pitch), "<i4", torch.int32)
+        return self._pget(d["kf_word_ring"], *sh), self._pget(d["kf_node_ring"], *sh)
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
