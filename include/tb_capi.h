@@ -608,6 +608,49 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
                     const int32_t** key_counts, const tb_obs** obs, const int32_t** obs_counts, const int32_t** n_inliers,
                     const uint8_t** outlier, int* key_pitch, int* frame);
 
+/* ---- ragged batches: per-sequence reset, idle and keyframes
+ * The lock-step entry points above give every sequence the same frame index. These three drive the same loop the way batches
+ * arrive: a sequence may be restarted in its slot while the others go on, sit a step out, or take a keyframe off the cadence.
+ * A sequence inside a ragged batch computes exactly what it computes alone: frame t_s of sequence s is frame t_s of a loop that
+ * runs this sequence by itself through tb_vo_step_dev, bit for bit.
+ *
+ * tb_vo_reset_seq_dev: `which` is a HOST array [nseq]; Tcw0 a device array [nseq][16], read only where which[s] is set. A
+ * selected sequence returns to the state tb_vo_reset_dev gives it (no keys, pose Tcw0[s], no keyframe, for TB_VO_BOW no keyframe
+ * FeatureVector / BowVector, frame index -1); the other sequences keep every byte. The call puts the loop into ragged mode; it is
+ * legal before any reset and at any point of a run. tb_vo_reset_dev leaves ragged mode. In ragged mode tb_vo_step_dev is
+ * TB_ESTATE. Asynchronous.
+ *
+ * tb_vo_step_ragged_dev: `active` and `force_keyframe` are HOST arrays [nseq]; NULL active = every sequence, NULL
+ * force_keyframe = none. For every active sequence s, frame t_s = (its frame index) + 1 is processed; it is a keyframe iff
+ * t_s % keyframe_every == 0 or force_keyframe[s] (frame 0 always is). `right` is needed (TB_EINVAL otherwise) iff some active
+ * sequence has a keyframe. An idle sequence keeps every state tensor of tb_vo_state_dev, tb_vo_tracker_state_dev,
+ * tb_vo_bow_state_dev, tb_vo_mp_desc_dev (their live entries: what the counts cover) and its copy of the last left image; its
+ * slabs of left / right are not interpreted. An active sequence that was never reset is TB_ESTATE; a step in which every
+ * sequence idles is TB_OK and changes nothing. The call is also legal after tb_vo_reset_dev: when every sequence is active, at
+ * the same frame, with the same keyframe decision, it launches exactly what tb_vo_step_dev launches; any other step puts the
+ * loop into ragged mode. The views' pointers may change from one ragged step to the next: take them again after every step.
+ *
+ * How a ragged step is made: the host knows the masks, so nothing is decided on the device and nothing is read back. The step
+ * uploads the mask and the compacted list of keyframe sequences from pinned memory with one hipMemcpyAsync -- the one host ->
+ * device copy a ragged step adds. The tracking half runs over all nseq sequences as at frame t > 0 (a freshly reset sequence has
+ * no keys and no keyframe, so it gets no match, no row, and keeps its pose), into a second set of the per-frame outputs; then
+ * one kernel gives the idle sequences back what they held and sets a frame-0 sequence's match count, flags and inliers to 0. The
+ * keyframe half runs only when some sequence has a keyframe, on a compacted batch of those sequences: its cost follows their
+ * number, not nseq.
+ *
+ * tb_vo_frames: HOST arrays [nseq], each nullable: the frame index of every sequence (-1 before its first step) and the frame
+ * index of its keyframe (-1: none). It works in lock-step mode too, where every entry equals tb_vo_state_dev's *frame /
+ * tb_vo_tracker_state_dev's *kf_frame. In ragged mode those two report the largest per-sequence value.
+ *
+ * Supported: TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, and TB_VO_BOW without a database. TB_EUNSUPPORTED from
+ * tb_vo_reset_seq_dev and tb_vo_step_ragged_dev: TB_VO_PROJECTION_MAP (the map's block count and eviction are counted on the host
+ * for the whole batch) and a TB_VO_BOW loop after tb_vo_bow_db_enable (database, store, recovery: the ring slot is the host's
+ * count of adds for the whole batch). Making those two per-sequence is a later change. */
+int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0);
+int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch, const uint8_t* active,
+                          const uint8_t* force_keyframe);
+int tb_vo_frames(tb_vo* vo, int32_t* frames, int32_t* kf_frames);
+
 /* The tracker of the loop: test_kitti's four tracking lines (:711-716) are switched by commenting them in and out; besides
  * optical flow (:716) the two descriptor trackers named with full arguments run here:
  *   TB_VO_BF        searchByBF(cur, key_frame, 0, 5, 10, 30) (:712): only the whole-set branch exists (matcher.cpp:177), so

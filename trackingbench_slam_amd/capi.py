@@ -51,6 +51,7 @@ EXPORTS = [
     "tb_kf_store_create", "tb_kf_store_destroy", "tb_kf_store_clear", "tb_kf_store_add_dev", "tb_kf_store_state_dev",
     "tb_kf_store_work_dev", "tb_relocalize_batch_dev", "tb_reloc_rows_dev", "tb_vo_reloc_enable", "tb_vo_relocalize_dev",
     "tb_vo_kf_store_get", "tb_vo_recover_enable", "tb_vo_recover_state_dev",
+    "tb_vo_reset_seq_dev", "tb_vo_step_ragged_dev", "tb_vo_frames",
 ]
 
 TB_VOC_MAX_L = 8
@@ -259,6 +260,25 @@ class VO:
     def step_dev(self, left_ptr, right_ptr, stride, pitch):
         """Returns the status code (0 or a negative TB_E* code) instead of raising, so argument checks can be tested."""
         return lib().tb_vo_step_dev(self._h, C.c_void_p(left_ptr), C.c_void_p(right_ptr or None), int(stride), C.c_size_t(pitch))
+
+    def reset_seq_dev(self, which, Tcw0_ptr):
+        """tb_vo_reset_seq_dev: `which` a bool sequence [nseq] (host), Tcw0_ptr a device array [nseq][16]. Returns the status code."""
+        w = np.ascontiguousarray(np.asarray(which, bool).astype(np.uint8))
+        assert w.shape == (self.nseq,)
+        return lib().tb_vo_reset_seq_dev(self._h, _p(w), C.c_void_p(Tcw0_ptr))
+
+    def step_ragged_dev(self, left_ptr, right_ptr, stride, pitch, active=None, force_keyframe=None):
+        """tb_vo_step_ragged_dev: active / force_keyframe bool sequences [nseq] (host) or None. Returns the status code."""
+        m = [None if x is None else np.ascontiguousarray(np.asarray(x, bool).astype(np.uint8)) for x in (active, force_keyframe)]
+        assert all(x is None or x.shape == (self.nseq,) for x in m)
+        return lib().tb_vo_step_ragged_dev(self._h, C.c_void_p(left_ptr), C.c_void_p(right_ptr or None), int(stride), C.c_size_t(pitch),
+                                           _p(m[0]), _p(m[1]))
+
+    def frames(self):
+        """tb_vo_frames: (frames [nseq], kf_frames [nseq]) int32 numpy arrays"""
+        f, k = np.zeros(self.nseq, np.int32), np.zeros(self.nseq, np.int32)
+        self.ctx.check(lib().tb_vo_frames(self._h, _p(f), _p(k)))
+        return f, k
 
     def state_dev(self):
         """dict of device pointers (Tcw, keys_xy, map_points, mp_valid, key_counts, obs, obs_counts, n_inliers, outlier) + key_pitch,

@@ -4,13 +4,16 @@
  * float32 arithmetic, one operation per statement (the library builds with -ffp-contract=off), left to right; the CPU
  * composition in tests/vo_reference.py does the same operations in the same order. */
 #include "tb_internal.h"
+#include "tb_kfcopy.h"
 
-/* Byte copy of nimg images into a tight [nimg][h][w] layout (the loop keeps the last left image for the next LK step). */
+/* Byte copy of nimg images into a tight [nimg][h][w] layout (the loop keeps the last left image for the next LK step). With an
+ * index list (a ragged step's keyframe block) image j of the output is image idx[j] of the source: a gather. */
 __global__ void __launch_bounds__(256)
-k_vo_copy_image(const uint8_t* __restrict__ src, int w, int h, int stride, size_t pitch, uint8_t* __restrict__ dst) {
+k_vo_copy_image(const uint8_t* __restrict__ src, int w, int h, int stride, size_t pitch, const int32_t* __restrict__ idx,
+                uint8_t* __restrict__ dst) {
     const int s = blockIdx.y;
     const size_t npx = (size_t)w * h;
-    const uint8_t* S = src + (size_t)s * pitch;
+    const uint8_t* S = src + (size_t)(idx ? idx[s] : s) * pitch;
     uint8_t* D = dst + (size_t)s * npx;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
         const int y = (int)(i / w), x = (int)(i - (size_t)y * w);
@@ -142,12 +145,12 @@ k_vo_match_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict_
  * count before the call (0 at frame 0: nothing was tracked). */
 __global__ void __launch_bounds__(256)
 k_vo_kf_pack(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__ orb_counts, int orb_pitch, int pitch,
-             float* __restrict__ keys, int32_t* __restrict__ key_counts, uint8_t* __restrict__ valid) {
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int m = min(max(orb_counts[s], 0), pitch);
+             float* __restrict__ keys, int32_t* __restrict__ key_counts, uint8_t* __restrict__ valid, const int32_t* __restrict__ idx) {
+    const int r = blockIdx.x, s = idx ? idx[r] : r, tid = threadIdx.x;   /* row r of the extractor's batch is sequence s */
+    const int m = min(max(orb_counts[r], 0), pitch);
     const int n = min(max(key_counts[s], 0), pitch);
     const size_t o = (size_t)s * pitch;
-    const tb_keypoint* K = orb + (size_t)s * orb_pitch;
+    const tb_keypoint* K = orb + (size_t)r * orb_pitch;
     for (int j = tid; j < m; j += 256) {
         keys[2 * (o + j)] = K[j].x;
         keys[2 * (o + j) + 1] = K[j].y;
@@ -165,10 +168,10 @@ k_vo_kf_pack(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__ or
 __global__ void __launch_bounds__(256)
 k_vo_kf_spawn(const float* __restrict__ keys, const int32_t* __restrict__ key_counts, const float* __restrict__ depth,
               const float* __restrict__ Tcw, double fx, double fy, double cx, double cy, int pitch, float* __restrict__ mp,
-              uint8_t* __restrict__ valid) {
-    const int s = blockIdx.x, tid = threadIdx.x;
+              uint8_t* __restrict__ valid, const int32_t* __restrict__ idx) {
+    const int r = blockIdx.x, s = idx ? idx[r] : r, tid = threadIdx.x;   /* depth row r belongs to sequence s */
     const int m = min(max(key_counts[s], 0), pitch);
-    const size_t o = (size_t)s * pitch;
+    const size_t o = (size_t)s * pitch, od = (size_t)r * pitch;
     const float* T = Tcw + 16 * s;
     float R[9], t[3];
     for (int i = 0; i < 3; i++)
@@ -182,7 +185,7 @@ k_vo_kf_spawn(const float* __restrict__ keys, const int32_t* __restrict__ key_co
         t[i] = -a;
     }
     for (int j = tid; j < m; j += 256) {
-        const float d = depth[o + j];
+        const float d = depth[od + j];
         if (!(d > 0.f) || !isfinite(d)) continue;
         const int u = (int)keys[2 * (o + j)], v = (int)keys[2 * (o + j) + 1];
         const float n0 = (float)(((double)u - cx) / fx), n1 = (float)(((double)v - cy) / fy), n2 = 1.0f;
@@ -289,11 +292,11 @@ k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__
                const uint8_t* __restrict__ valid, const uint8_t* __restrict__ orb_desc, const float* __restrict__ Tcw, int pitch,
                uint8_t* __restrict__ mp_desc, tb_mappoint* __restrict__ rec, tb_mappoint* __restrict__ map_rec,
                uint8_t* __restrict__ map_desc, int32_t* __restrict__ map_n, int32_t* __restrict__ map_blocks, int nblk, int slot,
-               int map_pitch) {
+               int map_pitch, const int32_t* __restrict__ idx) {
     __shared__ int wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rw = blockIdx.x, s = idx ? idx[rw] : rw, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   /* depth row rw */
     const int m = min(max(key_counts[s], 0), pitch);
-    const size_t o = (size_t)s * pitch, om = (size_t)s * map_pitch;
+    const size_t o = (size_t)s * pitch, om = (size_t)s * map_pitch, od = (size_t)rw * pitch;
     const float* T = Tcw + 16 * s;
     float t[3];
     for (int i = 0; i < 3; i++) {
@@ -312,7 +315,7 @@ k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__
         tb_mappoint r = {{0, 0, 0}, {0, 0, 0}, 0, 0, 1};
         unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
         if (j < m) {
-            const float d = depth[o + j];
+            const float d = depth[od + j];
             ok = d > 0.f && isfinite(d);
             if (ok) {
                 const unsigned long long* D = reinterpret_cast<const unsigned long long*>(orb_desc) + 4 * (o + j);
@@ -383,11 +386,159 @@ k_vo_map_evict(const tb_mappoint* __restrict__ src_rec, const uint8_t* __restric
     }
 }
 
-int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst) {
+/* ---- ragged batches (include/tb_capi.h, tb_vo_step_ragged_dev): per-sequence reset, hold of the idle sequences, the keyframe
+ * block on a compacted batch. Every copy moves live entries only, through kf_copy's 16 / 4 / 1-byte lanes; which sequence a
+ * workgroup serves, and whether it has anything to do, is one wave-uniform test per workgroup. */
+
+/* tb_vo_reset_seq_dev: a selected sequence returns to the state tb_vo_reset_dev gives it -- pose Tcw0[s], no keys, no keyframe
+ * (nullable arrays belong to the descriptor / BoW loops). cell_start (searchByViolence's keyframe grid, [nseq][ncell]) is
+ * emptied as well: in ragged mode the matcher runs for a sequence that has no keyframe yet, and an all-zero table is an empty
+ * grid. */
+__global__ void __launch_bounds__(256)
+k_vo_reset_seq(const int32_t* __restrict__ mask, const float* __restrict__ Tcw0, float* __restrict__ Tcw, int32_t* __restrict__ key_counts,
+               int32_t* __restrict__ kf_counts, int32_t* __restrict__ kf_fv_counts, int32_t* __restrict__ kf_bv_counts,
+               int32_t* __restrict__ cell_start, int ncell) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    if (!mask[s]) return;
+    if (tid < 16) Tcw[16 * (size_t)s + tid] = Tcw0[16 * (size_t)s + tid];
+    if (tid == 0) {
+        key_counts[s] = 0;
+        if (kf_counts) kf_counts[s] = 0;
+        if (kf_fv_counts) kf_fv_counts[s] = 0;
+        if (kf_bv_counts) kf_bv_counts[s] = 0;
+    }
+    if (cell_start)
+        for (int i = tid; i < ncell; i += 256) cell_start[(size_t)s * ncell + i] = 0;
+}
+
+/* A table of row copies, the body of the two kernels below. Entry e moves sequence s's row of e.src to the same row of e.dst:
+ * `count` entries of e.elem bytes, count = e.cnt[s] clamped to [0, e.lim] (e.cnt NULL: e.lim), rows e.stride entries apart. A
+ * workgroup (sequence, group) walks the table and takes the entries of its group; the table lives in the kernel's argument
+ * block, so the walk is scalar loads. */
+#define VO_ROWS_MAX 30
+struct VoRow { const uint8_t* src; uint8_t* dst; const int32_t* cnt; int lim, stride, elem, group; };
+struct VoRows { VoRow r[VO_ROWS_MAX]; int n; };
+
+__device__ __forceinline__ void vo_rows_copy(const VoRows& R, int s, int g, int tid) {
+    for (int i = 0; i < R.n; i++) {
+        if (R.r[i].group != g) continue;
+        const size_t n = R.r[i].cnt ? (size_t)min(max(R.r[i].cnt[s], 0), R.r[i].lim) : (size_t)R.r[i].lim;
+        const size_t o = (size_t)s * R.r[i].stride * R.r[i].elem;
+        kf_copy(R.r[i].dst + o, R.r[i].src + o, n * R.r[i].elem, tid);
+    }
+}
+
+/* The hold: after the tracking half ran over all sequences, an idle sequence (mask 0) gets back what it held -- side `a` of the
+ * ping-pong and the previous step's outputs go into side `b` and this step's outputs, live entries only (the counts are the
+ * held ones). Array groups (blockIdx.y): 0 keys, map points, validity, pose and every count; 1 the last left image; 2 rows and
+ * outlier flags; 3 ORB records and the match list; 4 descriptors (the keys' and the ones carried with the map points); 5 the BoW
+ * vectors. A sequence on its frame 0 (mask 2) matched against no keyframe: group 0 gives it what frame 0 of a lock-step loop
+ * has -- no matches, no flags, no inliers, the reset pose. Mask 1: nothing. */
+struct VoHoldFix { const float* a_Tcw; float* b_Tcw; int32_t *ninl, *mcnt, *mfl; };   /* mcnt / mfl: nullable */
+
+__global__ void __launch_bounds__(256)
+k_vo_hold(const int32_t* __restrict__ mask, VoHoldFix F, VoRows R) {
+    const int s = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int m = mask[s];
+    if (m == 1) return;
+    if (m == 2) {
+        if (g == 0) {
+            if (tid < 16) F.b_Tcw[16 * (size_t)s + tid] = F.a_Tcw[16 * (size_t)s + tid];
+            if (tid == 0) {
+                F.ninl[s] = 0;
+                if (F.mcnt) F.mcnt[s] = 0;
+                if (F.mfl) F.mfl[s] = 0;
+            }
+        }
+        return;
+    }
+    vo_rows_copy(R, s, g, tid);
+}
+
+/* The keyframe block's inputs on the compacted batch: row j gets the keys and the key count of sequence idx[j] (what the
+ * stereo operator reads). */
+__global__ void __launch_bounds__(256)
+k_vo_kf_gather(const int32_t* __restrict__ idx, const float* __restrict__ keys, const int32_t* __restrict__ key_counts, int pitch,
+               float* __restrict__ out_keys, int32_t* __restrict__ out_counts) {
+    const int r = blockIdx.x, s = idx[r], tid = threadIdx.x;
+    const size_t n = (size_t)min(max(key_counts[s], 0), pitch);
+    kf_copy(out_keys + 2 * (size_t)r * pitch, keys + 2 * (size_t)s * pitch, n * 2 * sizeof(float), tid);
+    if (tid == 0) out_counts[r] = key_counts[s];
+}
+
+/* key_frame = cur_frame_ptr for the sequences of the index list only: workgroup (j, g) copies array group g of sequence idx[j]
+ * from the current frame into the keyframe snapshot, live entries only. 0 the ORB records, 1 their descriptors, 2 the map points,
+ * their validity and the counts, 3 the descriptors carried with the map points (projection) or the FeatureVector keys (BoW), 4
+ * the BowVector, 5 the word and node ids. */
+__global__ void __launch_bounds__(256)
+k_vo_kf_snapshot(const int32_t* __restrict__ idx, VoRows R) {
+    vo_rows_copy(R, idx[blockIdx.x], blockIdx.y, threadIdx.x);
+}
+
+/* The two tables. Absent arrays (null destination) are left out; the returned value is the number of groups. */
+static void vo_row(VoRows& R, int group, const void* src, void* dst, const int32_t* cnt, int lim, int stride, int elem) {
+    if (!dst || R.n >= VO_ROWS_MAX) return;
+    R.r[R.n++] = VoRow{static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), cnt, lim, stride, elem, group};
+}
+static void vo_row1(VoRows& R, int group, const int32_t* src, int32_t* dst) { vo_row(R, group, src, dst, nullptr, 1, 1, 4); }
+
+static int vo_hold_rows(const tb_vo_hold_args* a, VoRows& R) {
+    const tb_vo_frame_out &p = a->prev, &c = a->cur;
+    const int P = a->pitch, M = a->match_pitch;
+    const int32_t *kc = a->kcnt[0], *oc = p.orb_cnt;
+    R.n = 0;
+    vo_row(R, 0, a->keys[0], a->keys[1], kc, P, P, 8);
+    vo_row(R, 0, a->mp[0], a->mp[1], kc, P, P, 12);
+    vo_row(R, 0, a->valid[0], a->valid[1], kc, P, P, 1);
+    vo_row(R, 0, a->Tcw[0], a->Tcw[1], nullptr, 16, 16, 4);
+    vo_row1(R, 0, a->kcnt[0], a->kcnt[1]);
+    vo_row1(R, 0, p.obs_counts, c.obs_counts);
+    vo_row1(R, 0, p.n_inliers, c.n_inliers);
+    vo_row1(R, 0, p.orb_cnt, c.orb_cnt);
+    vo_row1(R, 0, p.mcounts, c.mcounts);
+    vo_row1(R, 0, p.mflags, c.mflags);
+    vo_row1(R, 0, p.fv_cnt, c.fv_cnt);
+    vo_row1(R, 0, p.bv_cnt, c.bv_cnt);
+    vo_row(R, 1, a->img[0], a->img[1], nullptr, (int)a->npx, (int)a->npx, 1);
+    vo_row(R, 2, p.obs, c.obs, p.obs_counts, P, P, (int)sizeof(tb_obs));
+    vo_row(R, 2, p.outlier, c.outlier, kc, P, P, 1);
+    vo_row(R, 3, p.orb, c.orb, oc, P, P, (int)sizeof(tb_keypoint));
+    vo_row(R, 3, p.matches, c.matches, p.mcounts, M, M, (int)sizeof(tb_match));
+    vo_row(R, 4, p.orb_desc, c.orb_desc, oc, P, P, 32);
+    vo_row(R, 4, p.mp_desc, c.mp_desc, kc, P, P, 32);
+    vo_row(R, 5, p.bow_word, c.bow_word, oc, P, P, 4);
+    vo_row(R, 5, p.bow_node, c.bow_node, oc, P, P, 4);
+    vo_row(R, 5, p.fv_keys, c.fv_keys, p.fv_cnt, P, P, 8);
+    vo_row(R, 5, p.bv_word, c.bv_word, p.bv_cnt, P, P, 4);
+    vo_row(R, 5, p.bv_val, c.bv_val, p.bv_cnt, P, P, 8);
+    return c.fv_keys ? 6 : (c.orb ? 5 : 3);
+}
+
+static int vo_snap_rows(int P, const tb_vo_frame_out* c, const float* mp, const uint8_t* valid, const tb_vo_kf_out* k, VoRows& R) {
+    const int32_t* oc = c->orb_cnt;
+    R.n = 0;
+    vo_row(R, 0, c->orb, k->orb, oc, P, P, (int)sizeof(tb_keypoint));
+    vo_row(R, 1, c->orb_desc, k->desc, oc, P, P, 32);
+    vo_row(R, 2, mp, k->mp, oc, P, P, 12);
+    vo_row(R, 2, valid, k->valid, oc, P, P, 1);
+    vo_row1(R, 2, c->orb_cnt, k->cnt);
+    vo_row1(R, 2, c->fv_cnt, k->fv_cnt);
+    vo_row1(R, 2, c->bv_cnt, k->bv_cnt);
+    vo_row(R, 3, c->mp_desc, k->mp_desc, oc, P, P, 32);
+    vo_row(R, 3, c->fv_keys, k->fv_keys, c->fv_cnt, P, P, 8);
+    vo_row(R, 4, c->bv_word, k->bv_word, c->bv_cnt, P, P, 4);
+    vo_row(R, 4, c->bv_val, k->bv_val, c->bv_cnt, P, P, 8);
+    vo_row(R, 5, c->bow_word, k->bow_word, oc, P, P, 4);
+    vo_row(R, 5, c->bow_node, k->bow_node, oc, P, P, 4);
+    return k->fv_keys ? 6 : (k->mp_desc ? 4 : 3);
+}
+
+int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst,
+                      const int32_t* d_idx) {
     if (nimg <= 0) return TB_OK;
     const int bx = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 512);
     tb_prof_begin(ctx, "k_vo_copy_image");
-    hipLaunchKernelGGL(k_vo_copy_image, dim3(bx, nimg), dim3(256), 0, ctx->stream, d_src, w, h, stride, pitch, d_dst);
+    hipLaunchKernelGGL(k_vo_copy_image, dim3(bx, nimg), dim3(256), 0, ctx->stream, d_src, w, h, stride, pitch, d_idx, d_dst);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;
@@ -406,22 +557,22 @@ int tbk_vo_track(tb_ctx* ctx, int nseq, const int32_t* d_prev_counts, const uint
 }
 
 int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, float* d_keys,
-                   int32_t* d_key_counts, uint8_t* d_valid) {
+                   int32_t* d_key_counts, uint8_t* d_valid, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
     tb_prof_begin(ctx, "k_vo_kf_pack");
     hipLaunchKernelGGL(k_vo_kf_pack, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, orb_pitch, pitch, d_keys, d_key_counts,
-                       d_valid);
+                       d_valid, d_idx);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;
 }
 
 int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
-                    const double K[4], int pitch, float* d_mp, uint8_t* d_valid) {
+                    const double K[4], int pitch, float* d_mp, uint8_t* d_valid, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
     tb_prof_begin(ctx, "k_vo_kf_spawn");
     hipLaunchKernelGGL(k_vo_kf_spawn, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_depth, d_Tcw, K[0], K[1], K[2], K[3],
-                       pitch, d_mp, d_valid);
+                       pitch, d_mp, d_valid, d_idx);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;
@@ -473,12 +624,12 @@ int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_
 int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const float* d_depth, const float* d_mp, const uint8_t* d_valid,
                      const uint8_t* d_orb_desc, const float* d_Tcw, int pitch, uint8_t* d_mp_desc, tb_mappoint* d_rec,
                      tb_mappoint* d_map_rec, uint8_t* d_map_desc, int32_t* d_map_n, int32_t* d_map_blocks, int nblk, int slot,
-                     int map_pitch) {
+                     int map_pitch, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
     if (d_map_rec && (nblk < 1 || slot < 0 || slot >= nblk || map_pitch < 1)) return TB_EINVAL;
     tb_prof_begin(ctx, "k_vo_kf_append");
     hipLaunchKernelGGL(k_vo_kf_append, dim3(nseq), dim3(256), 0, ctx->stream, d_key_counts, d_depth, d_mp, d_valid, d_orb_desc, d_Tcw, pitch,
-                       d_mp_desc, d_rec, d_map_rec, d_map_desc, d_map_n, d_map_blocks, nblk, slot, map_pitch);
+                       d_mp_desc, d_rec, d_map_rec, d_map_desc, d_map_n, d_map_blocks, nblk, slot, map_pitch, d_idx);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;
@@ -492,6 +643,52 @@ int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const 
     tb_prof_begin(ctx, "k_vo_map_evict");
     hipLaunchKernelGGL(k_vo_map_evict, dim3(8, nseq), dim3(256), 0, ctx->stream, d_src_rec, d_src_desc, d_src_n, d_src_blocks, nblk, map_pitch,
                        d_dst_rec, d_dst_desc, d_dst_n, d_dst_blocks);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_reset_seq(tb_ctx* ctx, int nseq, const int32_t* d_mask, const float* d_Tcw0, float* d_Tcw, int32_t* d_key_counts,
+                     int32_t* d_kf_counts, int32_t* d_kf_fv_counts, int32_t* d_kf_bv_counts, int32_t* d_cell_start, int ncell) {
+    if (nseq <= 0) return TB_OK;
+    tb_prof_begin(ctx, "k_vo_reset_seq");
+    hipLaunchKernelGGL(k_vo_reset_seq, dim3(nseq), dim3(256), 0, ctx->stream, d_mask, d_Tcw0, d_Tcw, d_key_counts, d_kf_counts,
+                       d_kf_fv_counts, d_kf_bv_counts, d_cell_start, ncell);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_hold(tb_ctx* ctx, int nseq, const tb_vo_hold_args* a) {
+    if (nseq <= 0) return TB_OK;
+    if (a->npx > (size_t)INT32_MAX) return TB_EINVAL;
+    VoRows R;
+    const int groups = vo_hold_rows(a, R);
+    const VoHoldFix F = {a->Tcw[0], a->Tcw[1], a->cur.n_inliers, a->cur.mcounts, a->cur.mflags};
+    tb_prof_begin(ctx, "k_vo_hold");
+    hipLaunchKernelGGL(k_vo_hold, dim3(nseq, groups), dim3(256), 0, ctx->stream, a->mask, F, R);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_kf_gather(tb_ctx* ctx, int nkf, const int32_t* d_idx, const float* d_keys, const int32_t* d_key_counts, int pitch,
+                     float* d_out_keys, int32_t* d_out_counts) {
+    if (nkf <= 0) return TB_OK;
+    tb_prof_begin(ctx, "k_vo_kf_gather");
+    hipLaunchKernelGGL(k_vo_kf_gather, dim3(nkf), dim3(256), 0, ctx->stream, d_idx, d_keys, d_key_counts, pitch, d_out_keys, d_out_counts);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, const tb_vo_frame_out* cur, const float* d_mp,
+                       const uint8_t* d_valid, const tb_vo_kf_out* kf) {
+    if (nkf <= 0) return TB_OK;
+    VoRows R;
+    const int groups = vo_snap_rows(pitch, cur, d_mp, d_valid, kf, R);
+    tb_prof_begin(ctx, "k_vo_kf_snapshot");
+    hipLaunchKernelGGL(k_vo_kf_snapshot, dim3(nkf, groups), dim3(256), 0, ctx->stream, d_idx, R);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -2246,6 +2246,21 @@ struct tb_vo {
     float* rc_best_Tcw = nullptr;                                        /* [nseq][16] */
     int32_t* rc_masked = nullptr;                                        /* [nseq][topk] */
     int32_t *rc_word_ring = nullptr, *rc_node_ring = nullptr;            /* [nseq][capacity][P] */
+    /* ragged batches (tb_vo_reset_seq_dev / tb_vo_step_ragged_dev): the per-sequence frame counters live on the host in both
+     * modes; everything else is allocated by the first call that needs it (vo_ragged_init) */
+    bool ragged = false;                            /* the sequences no longer share one frame counter */
+    std::vector<int32_t> seq_frame, seq_kf_frame;   /* [nseq] last frame, frame of the keyframe (-1: none) */
+    std::vector<uint8_t> seq_reset;                 /* [nseq] the sequence has been reset at least once */
+    bool rg_ready = false;
+    tb_vo_frame_out rg_prev;                        /* the second set of per-frame outputs: a ragged step swaps the two */
+    uint8_t* rg_left = nullptr;                     /* [nseq][h][w] the keyframe block's left images, compacted */
+    float* rg_keys = nullptr;                       /* [nseq][P][2] its keys */
+    int32_t* rg_kcnt = nullptr;                     /* [nseq] */
+    int32_t* rg_dev = nullptr;                      /* [2][nseq] the step's mask and its keyframe index list */
+    enum { RG_RING = 8 };
+    int32_t* rg_pin = nullptr;                      /* [RG_RING][2][nseq] pinned staging; a slot is reused after its copy ran */
+    hipEvent_t rg_ev[RG_RING] = {};
+    unsigned rg_slot = 0;
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -2277,6 +2292,16 @@ void tb_vo_destroy(tb_vo* vo) {
         hipFree(vo->bow_word[k]); hipFree(vo->bow_node[k]); hipFree(vo->fv_keys[k]); hipFree(vo->fv_cnt[k]); hipFree(vo->bv_word[k]);
         hipFree(vo->bv_val[k]); hipFree(vo->bv_cnt[k]);
     }
+    {
+        const tb_vo_frame_out& q = vo->rg_prev;
+        hipFree(q.obs); hipFree(q.obs_counts); hipFree(q.outlier); hipFree(q.n_inliers); hipFree(q.orb); hipFree(q.orb_desc);
+        hipFree(q.orb_cnt); hipFree(q.matches); hipFree(q.mcounts); hipFree(q.mflags); hipFree(q.mp_desc); hipFree(q.bow_word);
+        hipFree(q.bow_node); hipFree(q.fv_keys); hipFree(q.fv_cnt); hipFree(q.bv_word); hipFree(q.bv_val); hipFree(q.bv_cnt);
+        hipFree(vo->rg_left); hipFree(vo->rg_keys); hipFree(vo->rg_kcnt); hipFree(vo->rg_dev);
+        if (vo->rg_pin) hipHostFree(vo->rg_pin);
+        for (hipEvent_t e : vo->rg_ev)
+            if (e) hipEventDestroy(e);
+    }
     delete vo;
 }
 
@@ -2296,6 +2321,7 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     vo->ctx = ctx;
     vo->p = *p;
     vo->nseq = nseq;
+    vo->seq_frame.assign(nseq, -1); vo->seq_kf_frame.assign(nseq, -1); vo->seq_reset.assign(nseq, 0);
     memset(&vo->tr, 0, sizeof vo->tr);
     if (tr) vo->tr = *tr;
     memset(&vo->bw, 0, sizeof vo->bw);
@@ -2367,6 +2393,8 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
         TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, S * sizeof(int32_t), ctx->stream));
+        /* an all-zero table is an empty grid: a ragged step runs the matcher for sequences that have no keyframe yet */
+        TB_HIP(ctx, hipMemsetAsync(vo->kf_cell_start, 0, S * 4321 * sizeof(int32_t), ctx->stream));
         /* the matcher's slots: searchByBF's best rows per side, searchByViolence's (WORK, shared with CLAHE) */
         if (vo->tr.kind == TB_VO_BF) {
             if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, S * P * 8, &d))) return rc;
@@ -2503,6 +2531,10 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         vo->map_nblk = 0;
     }
     vo->next = 0;
+    vo->ragged = false;
+    std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
+    std::fill(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end(), -1);
+    std::fill(vo->seq_reset.begin(), vo->seq_reset.end(), 1);
     return TB_OK;
 }
 
@@ -2746,16 +2778,29 @@ static int vo_step_proj(tb_vo* vo, int t, bool keyframe, const uint8_t* right, i
     return TB_OK;
 }
 
-int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
+/* The optical-flow tracker's frame t > 0 after the left images are in img[b]. */
+static int vo_track_opflow(tb_vo* vo) {
     tb_ctx* ctx = vo->ctx;
     const tb_vo_params& p = vo->p;
-    if (vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev before tb_vo_reset_dev");
-    const int t = vo->next;
-    const bool keyframe = t % p.keyframe_every == 0;
-    if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
-    if (keyframe && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
+    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
+    const size_t ip = (size_t)W * H;
+    const int a = vo->cur, b = a ^ 1;
+    int rc;
+    /* test_vo.cpp:716: searchByOPFlow(cur, last, pts, true, true) -- the tracked points land in this frame's key list */
+    if ((rc = tb_search_by_opflow_batch_dev(ctx, S, vo->img[b], vo->img[a], W, H, W, ip, &vo->cam, vo->keys[a], vo->kcnt[a], P, 1, 1,
+                                            vo->keys[b], vo->status, vo->matches, P, vo->mcounts)))
+        return rc;
+    if ((rc = tbk_vo_track(ctx, S, vo->kcnt[a], vo->status, vo->keys[b], vo->mp[a], vo->valid[a], P, vo->kcnt[b], vo->mp[b], vo->valid[b],
+                           vo->obs, vo->obs_counts, vo->outlier)))
+        return rc;
+    /* :761 LocalBA::PoseOptimization, started from the last frame's pose (:688) */
+    return tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr);
+}
+
+/* Frame t of every sequence (the arguments are checked): what tb_vo_step_dev launches. */
+static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
     const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
     const size_t ip = (size_t)W * H;
     const int a = vo->cur, b = a ^ 1;   /* a: last frame, b: this frame */
@@ -2769,17 +2814,8 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
         TB_HIP(ctx, hipMemsetAsync(vo->kcnt[b], 0, (size_t)S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
         TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-    } else {
-        /* test_vo.cpp:716: searchByOPFlow(cur, last, pts, true, true) -- the tracked points land in this frame's key list */
-        if ((rc = tb_search_by_opflow_batch_dev(ctx, S, vo->img[b], vo->img[a], W, H, W, ip, &vo->cam, vo->keys[a], vo->kcnt[a], P, 1, 1,
-                                                vo->keys[b], vo->status, vo->matches, P, vo->mcounts)))
-            return rc;
-        if ((rc = tbk_vo_track(ctx, S, vo->kcnt[a], vo->status, vo->keys[b], vo->mp[a], vo->valid[a], P, vo->kcnt[b], vo->mp[b], vo->valid[b],
-                               vo->obs, vo->obs_counts, vo->outlier)))
-            return rc;
-        /* :761 LocalBA::PoseOptimization, started from the last frame's pose (:688) */
-        if ((rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
-            return rc;
+    } else if ((rc = vo_track_opflow(vo))) {
+        return rc;
     }
     if (keyframe && vo->tr.kind == TB_VO_OPFLOW) {
         /* :774-785 ORB operator()(pyramid, sf, target, init_th, min_th) + SetKeys */
@@ -2798,6 +2834,283 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
     }
     vo->cur = b;
     vo->next = t + 1;
+    for (int s = 0; s < S; s++) {
+        vo->seq_frame[s] = t;
+        if (keyframe) vo->seq_kf_frame[s] = t;
+    }
+    return TB_OK;
+}
+
+int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    if (vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev: the loop is in ragged mode (tb_vo_step_ragged_dev, or tb_vo_reset_dev)");
+    if (vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev before tb_vo_reset_dev");
+    const int t = vo->next;
+    const bool keyframe = t % p.keyframe_every == 0;
+    if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
+    if (keyframe && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
+    return vo_step_lock(vo, t, keyframe, left, right, stride, pitch);
+}
+
+/* ---- ragged batches: see include/tb_capi.h, tb_vo_step_ragged_dev */
+static const char* vo_ragged_unsupported(const tb_vo* vo) {
+    if (vo->tr.kind == TB_VO_PROJECTION_MAP) return "TB_VO_PROJECTION_MAP counts the map's blocks and evicts for the whole batch";
+    if (vo->db) return "the keyframe database's ring slot is counted for the whole batch";
+    return nullptr;
+}
+
+/* the per-frame outputs the loop owns, as a set */
+static tb_vo_frame_out vo_frame_out(const tb_vo* vo) {
+    tb_vo_frame_out o;
+    o.obs = vo->obs; o.obs_counts = vo->obs_counts; o.outlier = vo->outlier; o.n_inliers = vo->n_inliers;
+    if (vo->tr.kind != TB_VO_OPFLOW) {
+        o.orb = vo->orb; o.orb_desc = vo->orb_desc; o.orb_cnt = vo->orb_cnt; o.matches = vo->matches; o.mcounts = vo->mcounts;
+        o.mflags = vo->mflags; o.mp_desc = vo->mp_desc;
+    }
+    if (vo->tr.kind == TB_VO_BOW) {
+        o.bow_word = vo->bow_word[0]; o.bow_node = vo->bow_node[0]; o.fv_keys = vo->fv_keys[0]; o.fv_cnt = vo->fv_cnt[0];
+        o.bv_word = vo->bv_word[0]; o.bv_val = vo->bv_val[0]; o.bv_cnt = vo->bv_cnt[0];
+    }
+    return o;
+}
+
+/* The step writes the other set from now on; rg_prev keeps what the last step left. */
+static void vo_swap_frame_out(tb_vo* vo) {
+    const tb_vo_frame_out cur = vo_frame_out(vo), n = vo->rg_prev;
+    vo->obs = n.obs; vo->obs_counts = n.obs_counts; vo->outlier = n.outlier; vo->n_inliers = n.n_inliers;
+    if (vo->tr.kind != TB_VO_OPFLOW) {
+        vo->orb = n.orb; vo->orb_desc = n.orb_desc; vo->orb_cnt = n.orb_cnt; vo->matches = n.matches; vo->mcounts = n.mcounts;
+        vo->mflags = n.mflags; vo->mp_desc = n.mp_desc;
+    }
+    if (vo->tr.kind == TB_VO_BOW) {
+        vo->bow_word[0] = n.bow_word; vo->bow_node[0] = n.bow_node; vo->fv_keys[0] = n.fv_keys; vo->fv_cnt[0] = n.fv_cnt;
+        vo->bv_word[0] = n.bv_word; vo->bv_val[0] = n.bv_val; vo->bv_cnt[0] = n.bv_cnt;
+    }
+    vo->rg_prev = cur;
+}
+
+/* Everything ragged mode needs beyond the lock-step loop, allocated once (allocation synchronises; a step never grows it). */
+static int vo_ragged_init(tb_vo* vo) {
+    if (vo->rg_ready) return TB_OK;
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq, P = (size_t)vo->P, img = (size_t)vo->p.width * vo->p.height;
+    tb_vo_frame_out& q = vo->rg_prev;
+    TB_HIP(ctx, hipMalloc(&q.obs, S * P * sizeof(tb_obs)));
+    TB_HIP(ctx, hipMalloc(&q.obs_counts, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&q.outlier, S * P));
+    TB_HIP(ctx, hipMalloc(&q.n_inliers, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMemsetAsync(q.obs_counts, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(q.n_inliers, 0, S * sizeof(int32_t), ctx->stream));
+    if (vo->tr.kind != TB_VO_OPFLOW) {
+        TB_HIP(ctx, hipMalloc(&q.orb, S * P * sizeof(tb_keypoint)));
+        TB_HIP(ctx, hipMalloc(&q.orb_desc, S * P * 32));
+        TB_HIP(ctx, hipMalloc(&q.orb_cnt, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.matches, S * (size_t)vo->Mcap * sizeof(tb_match)));
+        TB_HIP(ctx, hipMalloc(&q.mcounts, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.mflags, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMemsetAsync(q.orb_cnt, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(q.mcounts, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(q.mflags, 0, S * sizeof(int32_t), ctx->stream));
+        if (vo->mp_desc) {
+            TB_HIP(ctx, hipMalloc(&q.mp_desc, S * P * 32));
+            TB_HIP(ctx, hipMemsetAsync(q.mp_desc, 0, S * P * 32, ctx->stream));
+        }
+    }
+    if (vo->tr.kind == TB_VO_BOW) {
+        TB_HIP(ctx, hipMalloc(&q.bow_word, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.bow_node, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.fv_keys, S * P * sizeof(uint64_t)));
+        TB_HIP(ctx, hipMalloc(&q.fv_cnt, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.bv_word, S * P * sizeof(int32_t)));
+        TB_HIP(ctx, hipMalloc(&q.bv_val, S * P * sizeof(double)));
+        TB_HIP(ctx, hipMalloc(&q.bv_cnt, S * sizeof(int32_t)));
+        TB_HIP(ctx, hipMemsetAsync(q.fv_cnt, 0, S * sizeof(int32_t), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(q.bv_cnt, 0, S * sizeof(int32_t), ctx->stream));
+    }
+    TB_HIP(ctx, hipMalloc(&vo->rg_left, S * img));
+    TB_HIP(ctx, hipMalloc(&vo->rg_keys, S * P * 2 * sizeof(float)));
+    TB_HIP(ctx, hipMalloc(&vo->rg_kcnt, S * sizeof(int32_t)));
+    TB_HIP(ctx, hipMalloc(&vo->rg_dev, 2 * S * sizeof(int32_t)));
+    TB_HIP(ctx, hipHostMalloc((void**)&vo->rg_pin, (size_t)tb_vo::RG_RING * 2 * S * sizeof(int32_t), hipHostMallocDefault));
+    for (hipEvent_t& e : vo->rg_ev) TB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    vo->rg_ready = true;
+    return TB_OK;
+}
+
+/* The one host -> device copy of a ragged call: mask [nseq] and index list [nseq] from a pinned ring slot into rg_dev. The slot
+ * is reused RG_RING calls later, after its event says the copy has run. Returns the slot's host pointer through *pin. */
+static int vo_ragged_stage(tb_vo* vo, int32_t** pin) {
+    tb_ctx* ctx = vo->ctx;
+    const int k = (int)(vo->rg_slot % tb_vo::RG_RING);
+    TB_HIP(ctx, hipEventSynchronize(vo->rg_ev[k]));
+    *pin = vo->rg_pin + (size_t)k * 2 * vo->nseq;
+    return TB_OK;
+}
+static int vo_ragged_upload(tb_vo* vo, const int32_t* pin) {
+    tb_ctx* ctx = vo->ctx;
+    const int k = (int)(vo->rg_slot++ % tb_vo::RG_RING);
+    TB_HIP(ctx, hipMemcpyAsync(vo->rg_dev, pin, (size_t)2 * vo->nseq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    TB_HIP(ctx, hipEventRecord(vo->rg_ev[k], ctx->stream));
+    return TB_OK;
+}
+
+int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo || !which || !Tcw0) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (const char* why = vo_ragged_unsupported(vo)) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_reset_seq_dev: %s", why);
+    int rc;
+    if ((rc = vo_ragged_init(vo))) return rc;
+    const int S = vo->nseq;
+    int32_t* pin;
+    if ((rc = vo_ragged_stage(vo, &pin))) return rc;
+    for (int s = 0; s < S; s++) { pin[s] = which[s] ? 1 : 0; pin[S + s] = 0; }
+    if ((rc = vo_ragged_upload(vo, pin))) return rc;
+    const bool desc = vo->tr.kind != TB_VO_OPFLOW, bow = vo->tr.kind == TB_VO_BOW;
+    if ((rc = tbk_vo_reset_seq(ctx, S, vo->rg_dev, Tcw0, vo->Tcw[vo->cur], vo->kcnt[vo->cur], desc ? vo->kf_cnt : nullptr,
+                               bow ? vo->fv_cnt[1] : nullptr, bow ? vo->bv_cnt[1] : nullptr,
+                               vo->tr.kind == TB_VO_VIOLENCE ? vo->kf_cell_start : nullptr, 4321)))
+        return rc;
+    for (int s = 0; s < S; s++)
+        if (which[s]) { vo->seq_frame[s] = -1; vo->seq_kf_frame[s] = -1; vo->seq_reset[s] = 1; }
+    vo->ragged = true;
+    vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
+    vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
+    return TB_OK;
+}
+
+/* The keyframe block of a ragged step on the compacted batch of the nk sequences h_idx / d_idx name (ascending). */
+static int vo_keyframe_ragged(tb_vo* vo, int nk, const int32_t* h_idx, const int32_t* d_idx, const uint8_t* right, int stride, size_t pitch) {
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    const int P = vo->P, W = p.width, H = p.height, b = vo->cur;
+    const size_t ip = (size_t)W * H;
+    int rc;
+    if ((rc = tbk_vo_copy_image(ctx, nk, right, W, H, stride, pitch, vo->right, d_idx))) return rc;
+    if ((rc = tbk_vo_copy_image(ctx, nk, vo->img[b], W, H, W, ip, vo->rg_left, d_idx))) return rc;
+    if (vo->tr.kind == TB_VO_OPFLOW) {
+        if ((rc = tb_extractor_set_images_dev(vo->ex, vo->rg_left, nk, W, ip))) return rc;
+        if ((rc = tb_extractor_build_pyramid(vo->ex, nk))) return rc;
+        if ((rc = tb_extractor_orb(vo->ex, nk, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
+        const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
+        tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
+        if ((rc = tbk_vo_kf_pack(ctx, nk, kps, cnt, selCap, P, vo->keys[b], vo->kcnt[b], vo->valid[b], d_idx))) return rc;
+    }
+    if ((rc = tbk_vo_kf_gather(ctx, nk, d_idx, vo->keys[b], vo->kcnt[b], P, vo->rg_keys, vo->rg_kcnt))) return rc;
+    if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, nk, vo->right, vo->rg_left, W, H, W, ip, &vo->cam, vo->rg_keys, vo->rg_kcnt, P, p.bf,
+                                                    vo->st_pts, vo->st_status, vo->depth)))
+        return rc;
+    if ((rc = tbk_vo_kf_spawn(ctx, nk, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b], d_idx))) return rc;
+    if (vo->tr.kind == TB_VO_OPFLOW) return TB_OK;
+    if (vo->tr.kind == TB_VO_PROJECTION &&
+        (rc = tbk_vo_kf_append(ctx, nk, vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->orb_desc, vo->Tcw[b], P, vo->mp_desc, vo->kf_rec,
+                               nullptr, nullptr, nullptr, nullptr, 0, 0, vo->map_cap, d_idx)))
+        return rc;
+    /* key_frame = cur_frame_ptr for these sequences only */
+    const tb_vo_frame_out cur = vo_frame_out(vo);
+    tb_vo_kf_out kf;
+    kf.orb = vo->kf_orb; kf.desc = vo->kf_desc; kf.cnt = vo->kf_cnt; kf.mp = vo->kf_mp; kf.valid = vo->kf_valid; kf.mp_desc = vo->kf_mp_desc;
+    if (vo->tr.kind == TB_VO_BOW) {
+        kf.bow_word = vo->bow_word[1]; kf.bow_node = vo->bow_node[1]; kf.fv_keys = vo->fv_keys[1]; kf.fv_cnt = vo->fv_cnt[1];
+        kf.bv_word = vo->bv_word[1]; kf.bv_val = vo->bv_val[1]; kf.bv_cnt = vo->bv_cnt[1];
+    }
+    if ((rc = tbk_vo_kf_snapshot(ctx, nk, d_idx, P, &cur, vo->mp[b], vo->valid[b], &kf))) return rc;
+    if (vo->tr.kind == TB_VO_VIOLENCE) {
+        /* the keyframe's lookup grid, one call per run of neighbouring sequences */
+        for (int j = 0; j < nk;) {
+            int e = j + 1;
+            while (e < nk && h_idx[e] == h_idx[e - 1] + 1) e++;
+            const size_t s0 = (size_t)h_idx[j];
+            if ((rc = tb_frame_grid_batch_dev(ctx, e - j, vo->kf_orb + s0 * P, vo->kf_cnt + s0, P, W, H, vo->kf_cell_start + s0 * 4321,
+                                              vo->kf_cell_items + s0 * P)))
+                return rc;
+            j = e;
+        }
+    }
+    return TB_OK;
+}
+
+int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch, const uint8_t* active,
+                          const uint8_t* force_keyframe) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    if (const char* why = vo_ragged_unsupported(vo)) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_step_ragged_dev: %s", why);
+    if (!vo->ragged && vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_ragged_dev before tb_vo_reset_dev / tb_vo_reset_seq_dev");
+    const int S = vo->nseq;
+    int nact = 0, nkf = 0, t0 = -1;
+    bool same_t = true;
+    for (int s = 0; s < S; s++) {
+        if (active && !active[s]) continue;
+        if (!vo->seq_reset[s]) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_ragged_dev: sequence %d is active and was never reset", s);
+        const int t = vo->seq_frame[s] + 1;
+        if (nact++ == 0) t0 = t;
+        same_t = same_t && t == t0;
+        nkf += t % p.keyframe_every == 0 || (force_keyframe && force_keyframe[s]);
+    }
+    if (nact == 0) return TB_OK;   /* every sequence idles: nothing changes */
+    if (!left || stride < p.width || pitch < (size_t)stride * p.height)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_step_ragged_dev: left images / geometry");
+    if (nkf && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_ragged_dev: %d sequences have a keyframe and need the right images", nkf);
+    int rc;
+    if (nact == S && same_t && (nkf == 0 || nkf == S)) {
+        /* every sequence at the same frame with the same decision: this is tb_vo_step_dev's step, launch for launch */
+        if ((rc = vo_step_lock(vo, t0, nkf == S, left, right, stride, pitch))) return rc;
+        if (vo->ragged) vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
+        return TB_OK;
+    }
+    if ((rc = vo_ragged_init(vo))) return rc;
+    /* the masks, known to the host, go up in one copy; nothing is decided on the device and nothing is read back */
+    int32_t* pin;
+    if ((rc = vo_ragged_stage(vo, &pin))) return rc;
+    nkf = 0;
+    for (int s = 0; s < S; s++) {
+        const bool act = !active || active[s];
+        const int t = vo->seq_frame[s] + 1;
+        pin[s] = act ? (t == 0 ? 2 : 1) : 0;
+        if (act && (t % p.keyframe_every == 0 || (force_keyframe && force_keyframe[s]))) pin[S + nkf++] = s;
+    }
+    for (int j = nkf; j < S; j++) pin[S + j] = 0;
+    if ((rc = vo_ragged_upload(vo, pin))) return rc;
+    const int P = vo->P, W = p.width, H = p.height;
+    const int a = vo->cur, b = a ^ 1;
+    if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
+    /* the tracking half over all sequences, as frame t > 0 of the lock-step loop, into the other set of per-frame outputs: a
+     * sequence without keys or keyframe gets no match, no row and keeps its pose; an idle one is restored below */
+    vo_swap_frame_out(vo);
+    if (vo->tr.kind == TB_VO_OPFLOW) rc = vo_track_opflow(vo);
+    else if (vo_is_proj(vo)) rc = vo_step_proj(vo, 1, false, nullptr, 0, 0);
+    else rc = vo_step_desc(vo, 1, false, nullptr, 0, 0);
+    if (rc) { vo_swap_frame_out(vo); return rc; }
+    tb_vo_hold_args h;
+    h.mask = vo->rg_dev; h.pitch = P; h.match_pitch = vo->Mcap; h.npx = (size_t)W * H;
+    h.img[0] = vo->img[a]; h.img[1] = vo->img[b]; h.keys[0] = vo->keys[a]; h.keys[1] = vo->keys[b]; h.mp[0] = vo->mp[a]; h.mp[1] = vo->mp[b];
+    h.valid[0] = vo->valid[a]; h.valid[1] = vo->valid[b]; h.kcnt[0] = vo->kcnt[a]; h.kcnt[1] = vo->kcnt[b];
+    h.Tcw[0] = vo->Tcw[a]; h.Tcw[1] = vo->Tcw[b];
+    h.prev = vo->rg_prev; h.cur = vo_frame_out(vo);
+    if ((rc = tbk_vo_hold(ctx, S, &h))) return rc;
+    vo->cur = b;
+    if (nkf && (rc = vo_keyframe_ragged(vo, nkf, pin + S, vo->rg_dev + S, right, stride, pitch))) return rc;
+    for (int s = 0; s < S; s++)
+        if (pin[s]) vo->seq_frame[s]++;
+    for (int j = 0; j < nkf; j++) vo->seq_kf_frame[pin[S + j]] = vo->seq_frame[pin[S + j]];
+    vo->ragged = true;
+    vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
+    vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
+    return TB_OK;
+}
+
+int tb_vo_frames(tb_vo* vo, int32_t* frames, int32_t* kf_frames) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    for (int s = 0; s < vo->nseq; s++) {
+        if (frames) frames[s] = vo->seq_frame[s];
+        if (kf_frames) kf_frames[s] = vo->seq_kf_frame[s];
+    }
     return TB_OK;
 }
 

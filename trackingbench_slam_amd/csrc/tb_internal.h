@@ -299,7 +299,9 @@ int tbk_lk_track(tb_ctx* ctx, int npairs, const uint8_t* d_prev, const uint8_t* 
                  uint8_t* d_status, float* d_err, void* d_work, int* top_level);
 
 /* device-resident stereo VO loop (k_vo.hip) */
-int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst);
+/* d_idx (nullable, here and below): the index list of a ragged step's keyframe block -- row j serves sequence d_idx[j] */
+int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t pitch, uint8_t* d_dst,
+                      const int32_t* d_idx = nullptr);
 int tbk_vo_track(tb_ctx* ctx, int nseq, const int32_t* d_prev_counts, const uint8_t* d_status, const float* d_keys, const float* d_prev_mp,
                  const uint8_t* d_prev_valid, int pitch, int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, tb_obs* d_obs,
                  int32_t* d_obs_counts, uint8_t* d_outlier);
@@ -308,9 +310,9 @@ int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const in
                        const float* inv_sigma2, int nlevels, int32_t* d_win, float* d_keys, int32_t* d_key_counts, float* d_mp,
                        uint8_t* d_valid, tb_obs* d_obs, int32_t* d_obs_counts, uint8_t* d_outlier);
 int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, float* d_keys,
-                   int32_t* d_key_counts, uint8_t* d_valid);
+                   int32_t* d_key_counts, uint8_t* d_valid, const int32_t* d_idx = nullptr);
 int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
-                    const double K[4], int pitch, float* d_mp, uint8_t* d_valid);
+                    const double K[4], int pitch, float* d_mp, uint8_t* d_valid, const int32_t* d_idx = nullptr);
 
 int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
                       const int32_t* d_match_counts, int match_pitch, const float* d_src_mp, const uint8_t* d_src_valid,
@@ -320,9 +322,38 @@ int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_
 int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const float* d_depth, const float* d_mp, const uint8_t* d_valid,
                      const uint8_t* d_orb_desc, const float* d_Tcw, int pitch, uint8_t* d_mp_desc, tb_mappoint* d_rec,
                      tb_mappoint* d_map_rec, uint8_t* d_map_desc, int32_t* d_map_n, int32_t* d_map_blocks, int nblk, int slot,
-                     int map_pitch);
+                     int map_pitch, const int32_t* d_idx = nullptr);
 int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_n,
                      const int32_t* d_src_blocks, int nblk, int map_pitch, tb_mappoint* d_dst_rec, uint8_t* d_dst_desc, int32_t* d_dst_n,
                      int32_t* d_dst_blocks);
+/* Ragged batches (k_vo.hip): the outputs of one frame that are not part of the ping-pong (a ragged step writes a second set and
+ * keeps the previous one for the hold) and the keyframe snapshot; nullable members belong to the loops that have them. */
+struct tb_vo_frame_out {
+    tb_obs* obs = nullptr; int32_t* obs_counts = nullptr; uint8_t* outlier = nullptr; int32_t* n_inliers = nullptr;
+    tb_keypoint* orb = nullptr; uint8_t* orb_desc = nullptr; int32_t* orb_cnt = nullptr;
+    tb_match* matches = nullptr; int32_t *mcounts = nullptr, *mflags = nullptr;
+    uint8_t* mp_desc = nullptr;
+    int32_t *bow_word = nullptr, *bow_node = nullptr; uint64_t* fv_keys = nullptr; int32_t* fv_cnt = nullptr;
+    int32_t* bv_word = nullptr; double* bv_val = nullptr; int32_t* bv_cnt = nullptr;
+};
+struct tb_vo_kf_out {
+    tb_keypoint* orb = nullptr; uint8_t* desc = nullptr; int32_t* cnt = nullptr; float* mp = nullptr; uint8_t* valid = nullptr;
+    uint8_t* mp_desc = nullptr;
+    int32_t *bow_word = nullptr, *bow_node = nullptr; uint64_t* fv_keys = nullptr; int32_t* fv_cnt = nullptr;
+    int32_t* bv_word = nullptr; double* bv_val = nullptr; int32_t* bv_cnt = nullptr;
+};
+struct tb_vo_hold_args {
+    const int32_t* mask; int pitch, match_pitch; size_t npx;   /* mask [nseq]: 0 idle, 1 active, 2 active on its frame 0 */
+    uint8_t* img[2]; float* keys[2]; float* mp[2]; uint8_t* valid[2]; int32_t* kcnt[2]; float* Tcw[2];   /* [0] side a, [1] side b */
+    tb_vo_frame_out prev, cur;
+};
+int tbk_vo_reset_seq(tb_ctx* ctx, int nseq, const int32_t* d_mask, const float* d_Tcw0, float* d_Tcw, int32_t* d_key_counts,
+                     int32_t* d_kf_counts, int32_t* d_kf_fv_counts, int32_t* d_kf_bv_counts, int32_t* d_cell_start, int ncell);
+int tbk_vo_hold(tb_ctx* ctx, int nseq, const tb_vo_hold_args* a);
+int tbk_vo_kf_gather(tb_ctx* ctx, int nkf, const int32_t* d_idx, const float* d_keys, const int32_t* d_key_counts, int pitch,
+                     float* d_out_keys, int32_t* d_out_counts);
+int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, const tb_vo_frame_out* cur, const float* d_mp,
+                       const uint8_t* d_valid, const tb_vo_kf_out* kf);
+
 
 #endif

@@ -26,6 +26,10 @@ keyframe, PoseOptimization seeded with its pose, the candidate with the most inl
 fewer than lost_inliers inliers is relocalised inside the step, adopts the winner's pose, matches and map points, and tracks
 against the winning keyframe from then on. Which sequences do is decided on the device; the others are untouched.
 
+The batch need not move in lock-step: `reset(Tcw0, which=)` restarts some sequences in their slots, `step(..., active=, keyframe=)`
+advances only the active ones and gives the flagged ones a keyframe off the cadence, `frames()` tells where each one is. A sequence
+of such a ragged batch computes what it computes alone (every tracker but "projection_map", and "bow" without keyframe_db=).
+
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
 """
@@ -165,6 +169,7 @@ class StereoVO:
                 self.close()
                 raise
         self._Tcw0 = None
+        self._ragged = False
         self.frame = -1
 
     def close(self):
@@ -188,16 +193,55 @@ class StereoVO:
             if x is not None:
                 x.record_stream(self.stream)
 
-    def reset(self, Tcw0):
-        """Tcw0: [S, 4, 4] initial poses (array or tensor); the next step is frame 0."""
+    def _mask(self, m, what):
+        """a bool sequence [S] or an index list -> bool [S]; None stays None"""
+        if m is None:
+            return None
+        m = np.asarray(m)
+        if m.dtype != np.bool_:
+            idx = m.astype(np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= self.S):
+                raise ValueError("%s: sequence index out of range" % what)
+            m = np.zeros(self.S, bool)
+            m[idx] = True
+        if m.shape != (self.S,):
+            raise ValueError("%s: a bool sequence of length %d or an index list" % (what, self.S))
+        return m
+
+    def _ragged_ok(self):
+        if self.tracker == "projection_map" or self.db is not None:
+            raise TypeError("ragged batches: tracker 'projection_map' and keyframe_db= count keyframes for the whole batch")
+
+    def reset(self, Tcw0, which=None):
+        """Tcw0: [S, 4, 4] initial poses (array or tensor); the next step is frame 0. which= (a bool sequence [S] or an index
+        list) restarts only those sequences -- Tcw0 is then [S, 4, 4] or [len(which), 4, 4] in ascending sequence order -- and the
+        others keep their state: the loop is in ragged mode from then on (step() drives it; reset() without which= leaves it)."""
         T = torch.as_tensor(np.asarray(Tcw0, np.float32) if not torch.is_tensor(Tcw0) else Tcw0, dtype=torch.float32)
+        if which is not None:
+            self._ragged_ok()
+            w = self._mask(which, "which")
+            T = T.reshape(-1, 16).to(self.dev)
+            if T.shape[0] != self.S:
+                if T.shape[0] != int(w.sum()):
+                    raise ValueError("Tcw0: [S, 4, 4] or one pose per selected sequence")
+                full = torch.zeros(self.S, 16, dtype=torch.float32, device=self.dev)
+                full[torch.from_numpy(np.flatnonzero(w)).to(self.dev)] = T
+                T = full
+            T = T.contiguous()
+            self._enter(T)
+            self._Tcw0 = T
+            self.ctx.check(self.vo.reset_seq_dev(w, T.data_ptr()))
+            self._ragged = True
+            self.frame = int(self.vo.frames()[0].max())
+            return
         T = T.reshape(self.S, 16).to(self.dev).contiguous()
         self._enter(T)
         self._Tcw0 = T
         self.vo.reset_dev(T.data_ptr())
+        self._ragged = False
         self.frame = -1
 
-    def step_rc(self, left, right=None):
+    def step_rc(self, left, right=None, active=None, keyframe=None):
         """One frame; returns the library's status code (0 or a negative TB_E* code)."""
         assert left.dtype == torch.uint8 and left.is_cuda and tuple(left.shape) == (self.S, self.height, self.width)
         left = left.contiguous()
@@ -205,15 +249,31 @@ class StereoVO:
             assert right.dtype == torch.uint8 and right.is_cuda and tuple(right.shape) == tuple(left.shape)
             right = right.contiguous()
         self._enter(left, right)
-        rc = self.vo.step_dev(left.data_ptr(), right.data_ptr() if right is not None else None, self.width,
-                              self.width * self.height)
+        if active is None and keyframe is None and not self._ragged:
+            rc = self.vo.step_dev(left.data_ptr(), right.data_ptr() if right is not None else None, self.width,
+                                  self.width * self.height)
+            if rc == 0:
+                self.frame += 1
+            return rc
+        self._ragged_ok()
+        rc = self.vo.step_ragged_dev(left.data_ptr(), right.data_ptr() if right is not None else None, self.width,
+                                     self.width * self.height, self._mask(active, "active"), self._mask(keyframe, "keyframe"))
         if rc == 0:
-            self.frame += 1
+            self._ragged = True   # tb_vo_step_dev may refuse from now on; the ragged entry serves every step
+            self.frame = int(self.vo.frames()[0].max())
         return rc
 
-    def step(self, left, right=None):
-        """left / right: uint8 device tensors [S, H, W]; right may be None unless this frame is a keyframe."""
-        self.ctx.check(self.step_rc(left, right))
+    def step(self, left, right=None, active=None, keyframe=None):
+        """left / right: uint8 device tensors [S, H, W]; right may be None unless some sequence has a keyframe in this step.
+        active= (bool [S] or an index list): only these sequences take the frame, the others keep their state bit for bit and
+        their image slabs are ignored. keyframe=: these sequences take a keyframe now, whatever the cadence says. Either one makes
+        the step a ragged one (tb_vo_step_ragged_dev); frames() tells where every sequence is."""
+        self.ctx.check(self.step_rc(left, right, active, keyframe))
+
+    def frames(self):
+        """(frames [S], kf_frames [S]) int32 numpy arrays: every sequence's frame index (-1 before its first step) and the frame
+        index of its keyframe (-1: none)"""
+        return self.vo.frames()
 
     # ---- state accessors: copies (on the loop's stream, ordered before the caller's stream)
     def _get(self, key, shape, typestr, dtype):
