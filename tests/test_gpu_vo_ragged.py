@@ -134,7 +134,9 @@ def _schedule():
     return out
 
 
-@pytest.mark.parametrize("kind", ("opflow", "bow"))
+# searchByBF is left out: with these shapes the test's last assertion does not hold for it (seed 3's frame 1 yields no pose row
+# against its frame-0 keyframe, in the solo run as in the batch), whatever the batch does
+@pytest.mark.parametrize("kind", ("opflow", "violence", "projection", "bow"))
 def test_staggered_sequences_equal_their_solo_runs(seqs, voc, kind):
     L, R, G = seqs
     sched = _schedule()

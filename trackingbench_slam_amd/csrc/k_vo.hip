@@ -687,6 +687,11 @@ int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, co
     if (nkf <= 0) return TB_OK;
     VoRows R;
     const int groups = vo_snap_rows(pitch, cur, d_mp, d_valid, kf, R);
+    if (!d_idx) {   /* sequences [0, nkf): the same table, one copy of the whole slab per row */
+        for (int i = 0; i < R.n; i++)
+            TB_HIP(ctx, hipMemcpyAsync(R.r[i].dst, R.r[i].src, (size_t)nkf * R.r[i].stride * R.r[i].elem, hipMemcpyDeviceToDevice, ctx->stream));
+        return TB_OK;
+    }
     tb_prof_begin(ctx, "k_vo_kf_snapshot");
     hipLaunchKernelGGL(k_vo_kf_snapshot, dim3(nkf, groups), dim3(256), 0, ctx->stream, d_idx, R);
     tb_prof_end(ctx);

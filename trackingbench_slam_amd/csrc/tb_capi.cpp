@@ -2,7 +2,7 @@
  * No CPU compute fallback lives here: every operator either runs its kernels or returns an error.
  * Host work is limited to set-up arithmetic the reference also does on the host (scale vectors, level
  * sizes, quotas, resize coefficient tables, cell tables) and data movement: a single-frame (host) form stages its inputs
- * and runs the batched kernels on one pair.
+ * and runs the batched kernels on one pair. The device-resident VO loop that chains these operators (tb_vo_*) is tb_vo.cpp.
  */
 #include "tb_internal.h"
 #include "tb_math.h"
@@ -955,14 +955,6 @@ int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, con
 }
 
 /* ---- DBoW2 transform (see include/tb_capi.h) */
-struct tb_vocab {
-    tb_ctx* ctx = nullptr;
-    int nnodes = 0, k = 0, L = 0, weighting = 0, scoring = 0;
-    int32_t *d_child_start = nullptr, *d_child_items = nullptr, *d_word_id = nullptr;
-    uint8_t* d_desc = nullptr;
-    double* d_weight = nullptr;
-};
-
 void tb_vocab_destroy(tb_vocab* v) {
     if (!v) return;
     if (v->ctx) hipSetDevice(v->ctx->device);
@@ -1203,20 +1195,10 @@ int tb_bow_score_batch_dev(tb_ctx* ctx, int scoring, int mode, int na, const int
 }
 
 /* ---- the keyframe database: per sequence a ring of BowVectors (see include/tb_capi.h) */
-struct tb_bow_db {
-    tb_ctx* ctx = nullptr;
-    int nseq = 0, cap = 0, pitch = 0, scoring = 0;
-    long long nadded = 0;             /* adds since the last clear: the next one goes to slot nadded % cap */
-    int32_t* words = nullptr;         /* [nseq][cap][pitch] */
-    double* values = nullptr;         /* [nseq][cap][pitch] */
-    int32_t* counts = nullptr;        /* [nseq][cap] */
-    int32_t* kf_ids = nullptr;        /* [nseq][cap], -1 = empty */
-};
-
 void tb_bow_db_destroy(tb_bow_db* db) {
     if (!db) return;
     if (db->ctx) { hipSetDevice(db->ctx->device); hipStreamSynchronize(db->ctx->stream); }
-    hipFree(db->words); hipFree(db->values); hipFree(db->counts); hipFree(db->kf_ids);
+    db->own.release();
     delete db;
 }
 
@@ -1242,12 +1224,11 @@ int tb_bow_db_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int scoring
     tb_bow_db* db = du.get();
     db->ctx = ctx; db->nseq = nseq; db->cap = capacity; db->pitch = pitch; db->scoring = scoring;
     const size_t n = (size_t)nseq * capacity;
-    TB_HIP(ctx, hipMalloc(&db->words, n * pitch * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&db->values, n * pitch * sizeof(double)));
-    TB_HIP(ctx, hipMalloc(&db->counts, n * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&db->kf_ids, n * sizeof(int32_t)));
-    int rc = tb_bow_db_clear(db);
-    if (rc) return rc;
+    TB_TRY(tb_dev_alloc(ctx, db->own, &db->words, n * pitch));
+    TB_TRY(tb_dev_alloc(ctx, db->own, &db->values, n * pitch));
+    TB_TRY(tb_dev_alloc(ctx, db->own, &db->counts, n));
+    TB_TRY(tb_dev_alloc(ctx, db->own, &db->kf_ids, n));
+    TB_TRY(tb_bow_db_clear(db));
     *out = du.release();
     return TB_OK;
 }
@@ -1297,36 +1278,10 @@ int tb_bow_db_state_dev(tb_bow_db* db, const int32_t** words, const double** val
 }
 
 /* ---- the keyframe store and candidate verification (see include/tb_capi.h) */
-struct tb_kf_store {
-    tb_ctx* ctx = nullptr;
-    int nseq = 0, cap = 0, pitch = 0, max_cand = 0;
-    long long nadded = 0;                 /* adds since the last clear: the next one goes to slot nadded % cap */
-    /* the rings, frame index s * cap + slot */
-    tb_keypoint* keys = nullptr;          /* [nseq][cap][pitch] */
-    uint8_t* desc = nullptr;              /* [nseq][cap][pitch][32] */
-    uint64_t* fv = nullptr;               /* [nseq][cap][pitch] */
-    float* mp = nullptr;                  /* [nseq][cap][pitch][3] */
-    uint8_t* valid = nullptr;             /* [nseq][cap][pitch] */
-    float* Tcw = nullptr;                 /* [nseq][cap][16] */
-    int32_t *counts = nullptr, *fv_counts = nullptr, *kf_ids = nullptr;   /* [nseq][cap] */
-    /* verification work, pairs = nseq * max_cand */
-    int32_t *ix1 = nullptr, *ix2 = nullptr;                  /* [pairs] the matcher's frame indices */
-    int32_t* best = nullptr;                                 /* [pairs][pitch][4] searchByBow's best rows */
-    tb_match* matches = nullptr;                             /* [pairs][pitch] */
-    tb_obs* obs = nullptr;                                   /* [pairs][pitch] */
-    uint8_t* outlier = nullptr;                              /* [pairs][pitch] */
-    double* err = nullptr;                                   /* [pairs][pitch][3] the pose kernel's residuals */
-    float *seed = nullptr, *pose = nullptr;                  /* [pairs][16] */
-    int32_t *mcounts = nullptr, *flags = nullptr, *ocounts = nullptr, *ninl = nullptr, *ckf = nullptr;   /* [pairs] */
-};
-
 void tb_kf_store_destroy(tb_kf_store* st) {
     if (!st) return;
     if (st->ctx) { hipSetDevice(st->ctx->device); hipStreamSynchronize(st->ctx->stream); }
-    hipFree(st->keys); hipFree(st->desc); hipFree(st->fv); hipFree(st->mp); hipFree(st->valid); hipFree(st->Tcw); hipFree(st->counts);
-    hipFree(st->fv_counts); hipFree(st->kf_ids); hipFree(st->ix1); hipFree(st->ix2); hipFree(st->best); hipFree(st->matches);
-    hipFree(st->obs); hipFree(st->outlier); hipFree(st->err); hipFree(st->seed); hipFree(st->pose); hipFree(st->mcounts);
-    hipFree(st->flags); hipFree(st->ocounts); hipFree(st->ninl); hipFree(st->ckf);
+    st->own.release();
     delete st;
 }
 
@@ -1354,33 +1309,31 @@ int tb_kf_store_create(tb_ctx* ctx, int nseq, int capacity, int pitch, int max_c
     tb_kf_store* st = su.get();
     st->ctx = ctx; st->nseq = nseq; st->cap = capacity; st->pitch = pitch; st->max_cand = max_candidates;
     const size_t n = (size_t)nseq * capacity, np = n * pitch, pairs = (size_t)nseq * max_candidates, pp = pairs * pitch;
-    TB_HIP(ctx, hipMalloc(&st->keys, np * sizeof(tb_keypoint)));
-    TB_HIP(ctx, hipMalloc(&st->desc, np * 32));
-    TB_HIP(ctx, hipMalloc(&st->fv, np * sizeof(uint64_t)));
-    TB_HIP(ctx, hipMalloc(&st->mp, np * 3 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&st->valid, np));
-    TB_HIP(ctx, hipMalloc(&st->Tcw, n * 16 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&st->counts, n * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->fv_counts, n * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->kf_ids, n * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->ix1, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->ix2, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->best, pp * 16));
-    TB_HIP(ctx, hipMalloc(&st->matches, pp * sizeof(tb_match)));
-    TB_HIP(ctx, hipMalloc(&st->obs, pp * sizeof(tb_obs)));
-    TB_HIP(ctx, hipMalloc(&st->outlier, pp));
-    TB_HIP(ctx, hipMalloc(&st->err, pp * 3 * sizeof(double)));
-    TB_HIP(ctx, hipMalloc(&st->seed, pairs * 16 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&st->pose, pairs * 16 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&st->mcounts, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->flags, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->ocounts, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->ninl, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&st->ckf, pairs * sizeof(int32_t)));
-    TB_HIP(ctx, hipMemsetAsync(st->mcounts, 0, pairs * sizeof(int32_t), ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(st->ocounts, 0, pairs * sizeof(int32_t), ctx->stream));
-    int rc = tb_kf_store_clear(st);
-    if (rc) return rc;
+    tb_dev_owner& own = st->own;
+    TB_TRY(tb_dev_alloc(ctx, own, &st->keys, np));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->desc, np * 32));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->fv, np));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->mp, np * 3));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->valid, np));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->Tcw, n * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->counts, n));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->fv_counts, n));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->kf_ids, n));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ix1, pairs));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ix2, pairs));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->best, pp * 4));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->matches, pp));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->obs, pp));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->outlier, pp));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->err, pp * 3));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->seed, pairs * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->pose, pairs * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->mcounts, pairs, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->flags, pairs));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ocounts, pairs, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ninl, pairs));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ckf, pairs));
+    TB_TRY(tb_kf_store_clear(st));
     *out = su.release();
     return TB_OK;
 }
@@ -2158,1159 +2111,6 @@ int tb_add_map_points_by_stereo(tb_ctx* ctx, const uint8_t* img_stereo, const ui
     TB_DOWNLOAD(ctx, status.data(), b + oSt, (size_t)n);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_depth = (int)std::count(status.begin(), status.end(), 1); /* the keys that kept a match */
-    return TB_OK;
-}
-
-/* ---- device-resident stereo VO loop (test/test_vo.cpp test_kitti): see include/tb_capi.h */
-struct tb_vo {
-    tb_ctx* ctx = nullptr;
-    tb_vo_params p;
-    int nseq = 0, P = 0;        /* sequences, key capacity (= the extractor's kp_capacity) */
-    tb_extractor* ex = nullptr;
-    tb_camera cam;              /* width / height: CameraModel::IsInFrame of both frames */
-    int next = -1;              /* frame index of the next step (-1: not reset) */
-    int cur = 0;                /* which half of the ping-pong buffers holds the last frame */
-    /* ping-pong state: the last frame's and the current frame's */
-    uint8_t* img[2] = {nullptr, nullptr};    /* [nseq][h][w] left images */
-    float* keys[2] = {nullptr, nullptr};     /* [nseq][P][2] */
-    int32_t* kcnt[2] = {nullptr, nullptr};   /* [nseq] */
-    float* mp[2] = {nullptr, nullptr};       /* [nseq][P][3] */
-    uint8_t* valid[2] = {nullptr, nullptr};  /* [nseq][P] */
-    float* Tcw[2] = {nullptr, nullptr};      /* [nseq][16] */
-    /* per-step buffers */
-    uint8_t* right = nullptr;                /* [nseq][h][w] */
-    uint8_t* status = nullptr;               /* [nseq][P] LK status of the tracking step */
-    tb_match* matches = nullptr;             /* [nseq][P] */
-    int32_t* mcounts = nullptr;              /* [nseq] */
-    tb_obs* obs = nullptr;                   /* [nseq][P] */
-    int32_t* obs_counts = nullptr;           /* [nseq] */
-    uint8_t* outlier = nullptr;              /* [nseq][P] */
-    int32_t* n_inliers = nullptr;            /* [nseq] */
-    float* st_pts = nullptr;                 /* [nseq][P][2] stereo tracks */
-    uint8_t* st_status = nullptr;            /* [nseq][P] */
-    float* depth = nullptr;                  /* [nseq][P] */
-    /* descriptor trackers (tr.kind != TB_VO_OPFLOW): the current frame's ORB results, the keyframe's snapshot */
-    tb_vo_tracker tr;
-    float inv_sigma2[TB_MAX_LEVELS];         /* Frame::GetInverseScaleSigmaSquares */
-    tb_keypoint* orb = nullptr;              /* [nseq][P] */
-    uint8_t* orb_desc = nullptr;             /* [nseq][P][32] */
-    int32_t* orb_cnt = nullptr;              /* [nseq] */
-    int32_t* mflags = nullptr;               /* [nseq] matcher flags */
-    int32_t* win = nullptr;                  /* [nseq][P] k_vo_match_carry work */
-    tb_keypoint* kf_orb = nullptr;           /* [nseq][P] */
-    uint8_t* kf_desc = nullptr;              /* [nseq][P][32] */
-    int32_t* kf_cnt = nullptr;               /* [nseq] */
-    float* kf_mp = nullptr;                  /* [nseq][P][3] */
-    uint8_t* kf_valid = nullptr;             /* [nseq][P] */
-    int32_t* kf_cell_start = nullptr;        /* [nseq][4321] violence: the keyframe's lookup grid */
-    int32_t* kf_cell_items = nullptr;        /* [nseq][P] */
-    int kf_frame = -1;
-    /* projection trackers (TB_VO_PROJECTION, TB_VO_PROJECTION_MAP) */
-    int Mcap = 0;                            /* match capacity: P, or the map's capacity */
-    float sf[TB_MAX_LEVELS];                 /* Frame::GetScaleFactors */
-    int32_t* cell_start = nullptr;           /* [nseq][4321] the current frame's lookup grid */
-    int32_t* cell_items = nullptr;           /* [nseq][P] */
-    uint8_t* taken = nullptr;                /* [nseq][P] zero: Observations() is 0 throughout the loop */
-    uint8_t* mp_desc = nullptr;              /* [nseq][P][32] the descriptors of the current frame's map points */
-    uint8_t* kf_mp_desc = nullptr;           /* [nseq][P][32] */
-    tb_mappoint* kf_rec = nullptr;           /* [nseq][P] TB_VO_PROJECTION: the keyframe's map points as the matcher reads them */
-    /* the map (TB_VO_PROJECTION_MAP): two sets, eviction moves the survivors from one into the other */
-    int mapK = 0, map_cap = 0, map_cur = 0, map_nblk = 0;   /* keyframes held, capacity, live set, blocks in use */
-    tb_mappoint* map_rec[2] = {nullptr, nullptr};   /* [nseq][map_cap] */
-    uint8_t* map_desc[2] = {nullptr, nullptr};      /* [nseq][map_cap][32] */
-    int32_t* map_n[2] = {nullptr, nullptr};         /* [nseq] live counts */
-    int32_t* map_blocks[2] = {nullptr, nullptr};    /* [nseq][mapK] points per held keyframe, oldest first */
-    /* searchByBow (TB_VO_BOW): the borrowed vocabulary, Frame::SetBow's outputs of the current frame ([0]) and the keyframe ([1]) */
-    tb_vo_bow bw;
-    const tb_vocab* voc = nullptr;
-    double* bow_wt = nullptr;                       /* [nseq][P] word weights of the current frame */
-    int32_t* bow_word[2] = {nullptr, nullptr};      /* [nseq][P] word ids */
-    int32_t* bow_node[2] = {nullptr, nullptr};      /* [nseq][P] node ids */
-    uint64_t* fv_keys[2] = {nullptr, nullptr};      /* [nseq][P] FeatureVector keys */
-    int32_t* fv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
-    int32_t* bv_word[2] = {nullptr, nullptr};       /* [nseq][P] BowVector words */
-    double* bv_val[2] = {nullptr, nullptr};         /* [nseq][P] BowVector values */
-    int32_t* bv_cnt[2] = {nullptr, nullptr};        /* [nseq] */
-    tb_bow_db* db = nullptr;                        /* the keyframe database (tb_vo_bow_db_enable), owned */
-    /* relocalisation (tb_vo_reloc_enable): the keyframe store, owned, and the query's outputs a caller does not take */
-    tb_kf_store* store = nullptr;
-    double *rl_scores = nullptr, *rl_top_score = nullptr;   /* [nseq][capacity], [nseq][max_candidates] */
-    int32_t *rl_top_slot = nullptr, *rl_top_kf = nullptr;   /* [nseq][max_candidates] */
-    /* recovery (tb_vo_recover_enable): the flags and the selection of the last step, the per-sequence tracking keyframe, the
-     * masked candidates, and the rings of the keyframes' word / node ids, ring-aligned with the store */
-    bool rec_on = false;
-    tb_vo_recover rec;
-    uint8_t* rc_lost = nullptr;                                          /* [nseq] */
-    int32_t *rc_track = nullptr, *rc_kf = nullptr, *rc_kf_ids = nullptr; /* [nseq] */
-    int32_t *rc_best_rank = nullptr, *rc_best_kf = nullptr;              /* [nseq] */
-    float* rc_best_Tcw = nullptr;                                        /* [nseq][16] */
-    int32_t* rc_masked = nullptr;                                        /* [nseq][topk] */
-    int32_t *rc_word_ring = nullptr, *rc_node_ring = nullptr;            /* [nseq][capacity][P] */
-    /* ragged batches (tb_vo_reset_seq_dev / tb_vo_step_ragged_dev): the per-sequence frame counters live on the host in both
-     * modes; everything else is allocated by the first call that needs it (vo_ragged_init) */
-    bool ragged = false;                            /* the sequences no longer share one frame counter */
-    std::vector<int32_t> seq_frame, seq_kf_frame;   /* [nseq] last frame, frame of the keyframe (-1: none) */
-    std::vector<uint8_t> seq_reset;                 /* [nseq] the sequence has been reset at least once */
-    bool rg_ready = false;
-    tb_vo_frame_out rg_prev;                        /* the second set of per-frame outputs: a ragged step swaps the two */
-    uint8_t* rg_left = nullptr;                     /* [nseq][h][w] the keyframe block's left images, compacted */
-    float* rg_keys = nullptr;                       /* [nseq][P][2] its keys */
-    int32_t* rg_kcnt = nullptr;                     /* [nseq] */
-    int32_t* rg_dev = nullptr;                      /* [2][nseq] the step's mask and its keyframe index list */
-    enum { RG_RING = 8 };
-    int32_t* rg_pin = nullptr;                      /* [RG_RING][2][nseq] pinned staging; a slot is reused after its copy ran */
-    hipEvent_t rg_ev[RG_RING] = {};
-    unsigned rg_slot = 0;
-};
-
-static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
-
-void tb_vo_destroy(tb_vo* vo) {
-    if (!vo) return;
-    hipSetDevice(vo->ctx->device);
-    hipStreamSynchronize(vo->ctx->stream);
-    if (vo->ex) tb_extractor_destroy(vo->ex);
-    tb_bow_db_destroy(vo->db);
-    tb_kf_store_destroy(vo->store);
-    hipFree(vo->rl_scores); hipFree(vo->rl_top_score); hipFree(vo->rl_top_slot); hipFree(vo->rl_top_kf);
-    hipFree(vo->rc_lost); hipFree(vo->rc_track); hipFree(vo->rc_kf); hipFree(vo->rc_kf_ids); hipFree(vo->rc_best_rank);
-    hipFree(vo->rc_best_kf); hipFree(vo->rc_best_Tcw); hipFree(vo->rc_masked); hipFree(vo->rc_word_ring); hipFree(vo->rc_node_ring);
-    for (int k = 0; k < 2; k++) {
-        hipFree(vo->img[k]); hipFree(vo->keys[k]); hipFree(vo->kcnt[k]); hipFree(vo->mp[k]); hipFree(vo->valid[k]); hipFree(vo->Tcw[k]);
-    }
-    hipFree(vo->right); hipFree(vo->status); hipFree(vo->matches); hipFree(vo->mcounts); hipFree(vo->obs); hipFree(vo->obs_counts);
-    hipFree(vo->outlier); hipFree(vo->n_inliers); hipFree(vo->st_pts); hipFree(vo->st_status); hipFree(vo->depth);
-    hipFree(vo->orb); hipFree(vo->orb_desc); hipFree(vo->orb_cnt); hipFree(vo->mflags); hipFree(vo->win); hipFree(vo->kf_orb);
-    hipFree(vo->kf_desc); hipFree(vo->kf_cnt); hipFree(vo->kf_mp); hipFree(vo->kf_valid); hipFree(vo->kf_cell_start);
-    hipFree(vo->kf_cell_items);
-    hipFree(vo->cell_start); hipFree(vo->cell_items); hipFree(vo->taken); hipFree(vo->mp_desc); hipFree(vo->kf_mp_desc); hipFree(vo->kf_rec);
-    for (int k = 0; k < 2; k++) {
-        hipFree(vo->map_rec[k]); hipFree(vo->map_desc[k]); hipFree(vo->map_n[k]); hipFree(vo->map_blocks[k]);
-    }
-    hipFree(vo->bow_wt);
-    for (int k = 0; k < 2; k++) {
-        hipFree(vo->bow_word[k]); hipFree(vo->bow_node[k]); hipFree(vo->fv_keys[k]); hipFree(vo->fv_cnt[k]); hipFree(vo->bv_word[k]);
-        hipFree(vo->bv_val[k]); hipFree(vo->bv_cnt[k]);
-    }
-    {
-        const tb_vo_frame_out& q = vo->rg_prev;
-        hipFree(q.obs); hipFree(q.obs_counts); hipFree(q.outlier); hipFree(q.n_inliers); hipFree(q.orb); hipFree(q.orb_desc);
-        hipFree(q.orb_cnt); hipFree(q.matches); hipFree(q.mcounts); hipFree(q.mflags); hipFree(q.mp_desc); hipFree(q.bow_word);
-        hipFree(q.bow_node); hipFree(q.fv_keys); hipFree(q.fv_cnt); hipFree(q.bv_word); hipFree(q.bv_val); hipFree(q.bv_cnt);
-        hipFree(vo->rg_left); hipFree(vo->rg_keys); hipFree(vo->rg_kcnt); hipFree(vo->rg_dev);
-        if (vo->rg_pin) hipHostFree(vo->rg_pin);
-        for (hipEvent_t e : vo->rg_ev)
-            if (e) hipEventDestroy(e);
-    }
-    delete vo;
-}
-
-static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out, const tb_vo_bow* bow = nullptr,
-                     const tb_vocab* voc = nullptr) {
-    if (!ctx || !p || !out) return TB_EINVAL;
-    *out = nullptr;
-    if (nseq < 1 || p->width < 1 || p->height < 1 || p->nlevels < 2 || p->nlevels > TB_MAX_LEVELS || !(p->scale > 0.f && p->scale < 1.f) ||
-        p->target < 1 || p->keyframe_every < 1 || !(p->K[0] > 0.0) || !(p->K[1] > 0.0) || !std::isfinite(p->K[2]) ||
-        !std::isfinite(p->K[3]) || !(p->bf > 0.f) || !std::isfinite(p->bf))
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_create: bad parameters (nseq %d, %dx%d, %d levels, scale %g, target %d, keyframe_every %d)",
-                       nseq, p->width, p->height, p->nlevels, (double)p->scale, p->target, p->keyframe_every);
-    std::vector<float> sf(p->nlevels), tmp(p->nlevels);
-    tb_scale_factors(p->nlevels, p->scale, sf.data(), tmp.data(), tmp.data(), tmp.data());
-    std::unique_ptr<tb_vo, void (*)(tb_vo*)> vu(new tb_vo(), tb_vo_destroy);
-    tb_vo* vo = vu.get();
-    vo->ctx = ctx;
-    vo->p = *p;
-    vo->nseq = nseq;
-    vo->seq_frame.assign(nseq, -1); vo->seq_kf_frame.assign(nseq, -1); vo->seq_reset.assign(nseq, 0);
-    memset(&vo->tr, 0, sizeof vo->tr);
-    if (tr) vo->tr = *tr;
-    memset(&vo->bw, 0, sizeof vo->bw);
-    if (bow) { vo->bw = *bow; vo->voc = voc; }
-    int rc = tb_extractor_create(ctx, p->width, p->height, p->nlevels, sf.data(), nullptr, nullptr, nseq, p->target, &vo->ex);
-    if (rc) return rc;
-    vo->P = vo->ex->g.selCap;
-    vo->Mcap = vo->P;
-    if (bow && vo->P > 8192)
-        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_bow: %d keys per frame (the transform sorts at most 8192)", vo->P);
-    if (vo->tr.kind == TB_VO_PROJECTION_MAP) {
-        if ((size_t)vo->tr.map_keyframes * (size_t)vo->P > (size_t)INT32_MAX / 64)
-            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: map_keyframes %d x %d keys is too large", vo->tr.map_keyframes, vo->P);
-        vo->mapK = vo->tr.map_keyframes;
-        vo->map_cap = vo->Mcap = vo->mapK * vo->P;
-    }
-    memset(&vo->cam, 0, sizeof vo->cam);
-    vo->cam.fx = (float)p->K[0]; vo->cam.fy = (float)p->K[1]; vo->cam.cx = (float)p->K[2]; vo->cam.cy = (float)p->K[3];
-    vo->cam.width = p->width; vo->cam.height = p->height;
-    const size_t S = (size_t)nseq, P = (size_t)vo->P, img = (size_t)p->width * p->height;
-    for (int k = 0; k < 2; k++) {
-        TB_HIP(ctx, hipMalloc(&vo->img[k], S * img));
-        TB_HIP(ctx, hipMalloc(&vo->keys[k], S * P * 2 * sizeof(float)));
-        TB_HIP(ctx, hipMalloc(&vo->kcnt[k], S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->mp[k], S * P * 3 * sizeof(float)));
-        TB_HIP(ctx, hipMalloc(&vo->valid[k], S * P));
-        TB_HIP(ctx, hipMalloc(&vo->Tcw[k], S * 16 * sizeof(float)));
-    }
-    TB_HIP(ctx, hipMalloc(&vo->right, S * img));
-    TB_HIP(ctx, hipMalloc(&vo->status, S * P));
-    TB_HIP(ctx, hipMalloc(&vo->matches, S * (size_t)vo->Mcap * sizeof(tb_match)));
-    TB_HIP(ctx, hipMalloc(&vo->mcounts, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->obs, S * P * sizeof(tb_obs)));
-    TB_HIP(ctx, hipMalloc(&vo->obs_counts, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->outlier, S * P));
-    TB_HIP(ctx, hipMalloc(&vo->n_inliers, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->st_pts, S * P * 2 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&vo->st_status, S * P));
-    TB_HIP(ctx, hipMalloc(&vo->depth, S * P * sizeof(float)));
-    for (int k = 0; k < 2; k++) {
-        TB_HIP(ctx, hipMemsetAsync(vo->kcnt[k], 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->valid[k], 0, S * P, ctx->stream));
-    }
-    TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, S * sizeof(int32_t), ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, S * sizeof(int32_t), ctx->stream));
-    /* every scratch slot the step's operators use, at its largest size now: a step never grows one (growth synchronises) */
-    const size_t pitch = img;
-    void* d;
-    if ((rc = tb_scratch(ctx, TB_SLOT_OPFLOW_EQ, S * pitch, &d)) || (rc = tb_scratch(ctx, TB_SLOT_WORK, S * 8 * 8 * 256, &d)) ||
-        (rc = tb_scratch(ctx, TB_SLOT_LK, std::max(tbk_lk_work_bytes(p->width, p->height, 3, nseq), S * P * 3 * sizeof(double)), &d)) ||
-        (rc = tb_scratch(ctx, TB_SLOT_RANSAC, tbk_ransac_work_bytes(nseq, vo->P), &d)) || (rc = tb_scratch(ctx, TB_SLOT_RANSAC_FLAGS, S * sizeof(int32_t), &d)) ||
-        (rc = tb_scratch(ctx, TB_SLOT_STEREO_MATCHES, S * P * sizeof(tb_match), &d)) || (rc = tb_scratch(ctx, TB_SLOT_STEREO_COUNTS, S * sizeof(int32_t), &d)))
-        return rc;
-    if (vo->tr.kind != TB_VO_OPFLOW) {
-        tb_scale_factors(p->nlevels, p->scale, tmp.data(), nullptr, nullptr, vo->inv_sigma2);
-        TB_HIP(ctx, hipMalloc(&vo->orb, S * P * sizeof(tb_keypoint)));
-        TB_HIP(ctx, hipMalloc(&vo->orb_desc, S * P * 32));
-        TB_HIP(ctx, hipMalloc(&vo->orb_cnt, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->mflags, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->win, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->kf_orb, S * P * sizeof(tb_keypoint)));
-        TB_HIP(ctx, hipMalloc(&vo->kf_desc, S * P * 32));
-        TB_HIP(ctx, hipMalloc(&vo->kf_cnt, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->kf_mp, S * P * 3 * sizeof(float)));
-        TB_HIP(ctx, hipMalloc(&vo->kf_valid, S * P));
-        TB_HIP(ctx, hipMalloc(&vo->kf_cell_start, S * 4321 * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->kf_cell_items, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMemsetAsync(vo->orb_cnt, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, S * sizeof(int32_t), ctx->stream));
-        /* an all-zero table is an empty grid: a ragged step runs the matcher for sequences that have no keyframe yet */
-        TB_HIP(ctx, hipMemsetAsync(vo->kf_cell_start, 0, S * 4321 * sizeof(int32_t), ctx->stream));
-        /* the matcher's slots: searchByBF's best rows per side, searchByViolence's (WORK, shared with CLAHE) */
-        if (vo->tr.kind == TB_VO_BF) {
-            if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, S * P * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, S * P * 8, &d))) return rc;
-        } else if (vo_is_proj(vo)) {
-            /* the projection matchers' best rows: 6 words per map point */
-            if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * (size_t)vo->Mcap * 6 * sizeof(int32_t), &d))) return rc;
-        } else if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * P * 16, &d))) {
-            return rc;
-        }
-    }
-    if (bow) {
-        /* every output of the transform is a buffer of the loop, so tb_bow_transform_batch_dev takes no scratch; the matcher's
-         * best rows (WORK) were sized above */
-        TB_HIP(ctx, hipMalloc(&vo->bow_wt, S * P * sizeof(double)));
-        for (int k = 0; k < 2; k++) {
-            TB_HIP(ctx, hipMalloc(&vo->bow_word[k], S * P * sizeof(int32_t)));
-            TB_HIP(ctx, hipMalloc(&vo->bow_node[k], S * P * sizeof(int32_t)));
-            TB_HIP(ctx, hipMalloc(&vo->fv_keys[k], S * P * sizeof(uint64_t)));
-            TB_HIP(ctx, hipMalloc(&vo->fv_cnt[k], S * sizeof(int32_t)));
-            TB_HIP(ctx, hipMalloc(&vo->bv_word[k], S * P * sizeof(int32_t)));
-            TB_HIP(ctx, hipMalloc(&vo->bv_val[k], S * P * sizeof(double)));
-            TB_HIP(ctx, hipMalloc(&vo->bv_cnt[k], S * sizeof(int32_t)));
-            TB_HIP(ctx, hipMemsetAsync(vo->fv_cnt[k], 0, S * sizeof(int32_t), ctx->stream));
-            TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[k], 0, S * sizeof(int32_t), ctx->stream));
-        }
-    }
-    if (vo_is_proj(vo)) {
-        for (int l = 0; l < p->nlevels; l++) vo->sf[l] = sf[l];
-        TB_HIP(ctx, hipMalloc(&vo->cell_start, S * 4321 * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->cell_items, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&vo->taken, S * P));
-        TB_HIP(ctx, hipMalloc(&vo->mp_desc, S * P * 32));
-        TB_HIP(ctx, hipMalloc(&vo->kf_mp_desc, S * P * 32));
-        TB_HIP(ctx, hipMemsetAsync(vo->taken, 0, S * P, ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mp_desc, 0, S * P * 32, ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->kf_mp_desc, 0, S * P * 32, ctx->stream));
-        if (vo->tr.kind == TB_VO_PROJECTION) {
-            TB_HIP(ctx, hipMalloc(&vo->kf_rec, S * P * sizeof(tb_mappoint)));
-        } else {
-            const size_t C = (size_t)vo->map_cap;
-            for (int k = 0; k < 2; k++) {
-                TB_HIP(ctx, hipMalloc(&vo->map_rec[k], S * C * sizeof(tb_mappoint)));
-                TB_HIP(ctx, hipMalloc(&vo->map_desc[k], S * C * 32));
-                TB_HIP(ctx, hipMalloc(&vo->map_n[k], S * sizeof(int32_t)));
-                TB_HIP(ctx, hipMalloc(&vo->map_blocks[k], S * vo->mapK * sizeof(int32_t)));
-                TB_HIP(ctx, hipMemsetAsync(vo->map_n[k], 0, S * sizeof(int32_t), ctx->stream));
-                TB_HIP(ctx, hipMemsetAsync(vo->map_blocks[k], 0, S * vo->mapK * sizeof(int32_t), ctx->stream));
-            }
-        }
-    }
-    *out = vu.release();
-    return TB_OK;
-}
-
-int tb_vo_create(tb_ctx* ctx, const tb_vo_params* p, int nseq, tb_vo** out) {
-    TB_ENTER(ctx);
-    return vo_create(ctx, p, nullptr, nseq, out);
-}
-
-int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out) {
-    TB_ENTER(ctx);
-    if (!ctx || !p || !out) return TB_EINVAL;
-    *out = nullptr;
-    if (tr && tr->kind != TB_VO_OPFLOW) {
-        if (tr->kind == TB_VO_BOW) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: TB_VO_BOW needs a vocabulary, use tb_vo_create_bow");
-        if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE && tr->kind != TB_VO_PROJECTION && tr->kind != TB_VO_PROJECTION_MAP)
-            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
-        if (tr->kind == TB_VO_PROJECTION || tr->kind == TB_VO_PROJECTION_MAP) {
-            const bool map = tr->kind == TB_VO_PROJECTION_MAP;
-            if (tr->th_high < 0 || tr->histo_len < 1 || tr->histo_len > 1024 || !std::isfinite(tr->nratio) ||
-                (map && (tr->map_keyframes < 1 || !std::isfinite(tr->radio))))
-                return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByProjection arguments (nratio %g, th_high %d, histo_len %d, radio %g, map_keyframes %d)",
-                               (double)tr->nratio, tr->th_high, tr->histo_len, (double)tr->radio, tr->map_keyframes);
-        } else if (tr->kind == TB_VO_BF) {
-            if (!std::isfinite(tr->bf_ratio) || !std::isfinite(tr->bf_min_th))
-                return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByBF ratio / minTh must be finite");
-            /* matcher.cpp:177: only MinLevel == 0 && MaxLevel == F1->GetMaxLevel() (= nLevels) takes the whole-set branch */
-            if (tr->min_level != 0 || tr->max_level != p->nlevels)
-                return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_ex: searchByBF levels (%d, %d): only the whole-set branch (0, %d) exists",
-                               tr->min_level, tr->max_level, p->nlevels);
-        } else if (tr->histo_len < 1 || tr->histo_len > 1024 || !(tr->radius > 0.f) || !std::isfinite(tr->radius) ||
-                   tr->min_level > tr->max_level || !std::isfinite(tr->nratio)) {
-            return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: searchByViolence arguments (levels %d..%d, radius %g, histo_len %d)",
-                           tr->min_level, tr->max_level, (double)tr->radius, tr->histo_len);
-        }
-    }
-    return vo_create(ctx, p, tr && tr->kind != TB_VO_OPFLOW ? tr : nullptr, nseq, out);
-}
-
-int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_bow* bow, const tb_vocab* voc, int nseq, tb_vo** out) {
-    TB_ENTER(ctx);
-    if (out) *out = nullptr;
-    if (!p || !out || !bow) return TB_EINVAL;
-    if (bow->histo_len < 1 || bow->histo_len > 1024 || bow->levelsup < 0 || bow->th_low < 0 || !std::isfinite(bow->nratio)) {
-        if (!ctx) return TB_EINVAL;
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: searchByBow arguments (levelsup %d, th_low %d, nratio %g, histo_len %d)",
-                       bow->levelsup, bow->th_low, (double)bow->nratio, bow->histo_len);
-    }
-    if (!ctx) return TB_EINVAL;
-    if (!voc || voc->ctx != ctx) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: a vocabulary of this context is required");
-    if (voc->weighting < 0 || voc->weighting > 3 || voc->scoring < 0 || voc->scoring > 5)
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_bow: the vocabulary's weighting %d / scoring %d", voc->weighting, voc->scoring);
-    tb_vo_tracker tr;
-    memset(&tr, 0, sizeof tr);
-    tr.kind = TB_VO_BOW;
-    tr.th_low = bow->th_low; tr.nratio = bow->nratio; tr.histo_len = bow->histo_len; tr.check_orientation = bow->check_orientation;
-    return vo_create(ctx, p, &tr, nseq, out, bow, voc);
-}
-
-static int vo_recover_clear(tb_vo* vo);
-
-int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo || !Tcw0) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    /* frame 0 reads the "last frame": no keys, pose Tcw0 */
-    TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[vo->cur], Tcw0, (size_t)vo->nseq * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(vo->kcnt[vo->cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
-    if (vo->tr.kind != TB_VO_OPFLOW) {   /* no keyframe yet */
-        TB_HIP(ctx, hipMemsetAsync(vo->kf_cnt, 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
-        vo->kf_frame = -1;
-    }
-    if (vo->tr.kind == TB_VO_BOW) {
-        TB_HIP(ctx, hipMemsetAsync(vo->fv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->bv_cnt[1], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
-        int rc;
-        if (vo->db && (rc = tb_bow_db_clear(vo->db))) return rc;   /* a new run: no keyframes yet */
-        if (vo->store && (rc = tb_kf_store_clear(vo->store))) return rc;
-        if (vo->rec_on && (rc = vo_recover_clear(vo))) return rc;
-    }
-    if (vo->mapK) {   /* an empty map */
-        TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->map_blocks[vo->map_cur], 0, (size_t)vo->nseq * vo->mapK * sizeof(int32_t), ctx->stream));
-        vo->map_nblk = 0;
-    }
-    vo->next = 0;
-    vo->ragged = false;
-    std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
-    std::fill(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end(), -1);
-    std::fill(vo->seq_reset.begin(), vo->seq_reset.end(), 1);
-    return TB_OK;
-}
-
-/* the recovery state of a new run: nothing flagged, nothing adopted, no tracking keyframe */
-static int vo_recover_clear(tb_vo* vo) {
-    tb_ctx* ctx = vo->ctx;
-    const size_t S = (size_t)vo->nseq;
-    TB_HIP(ctx, hipMemsetAsync(vo->rc_lost, 0, S, ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(vo->rc_track, 0, S * sizeof(int32_t), ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(vo->rc_kf, 0xff, S * sizeof(int32_t), ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(vo->rc_kf_ids, 0xff, S * sizeof(int32_t), ctx->stream));
-    return TB_OK;
-}
-
-/* The recovery stage of frame t > 0 (include/tb_capi.h, tb_vo_recover): flag, query, mask, verify, adopt, switch the tracking
- * keyframe. Every launch is on the context's stream; which sequences adopt is decided on the device. */
-static int vo_recover_stage(tb_vo* vo, int b) {
-    tb_ctx* ctx = vo->ctx;
-    tb_kf_store* st = vo->store;
-    tb_bow_db* db = vo->db;
-    const tb_vo_recover& r = vo->rec;
-    const int S = vo->nseq, P = vo->P;
-    int rc;
-    if ((rc = tb_bow_db_query_dev(db, vo->bv_word[0], vo->bv_val[0], vo->bv_cnt[0], P, r.exclude_newest, r.topk, vo->rl_scores,
-                                  vo->rl_top_slot, vo->rl_top_kf, vo->rl_top_score, nullptr)))
-        return rc;
-    if ((rc = tbk_vo_recover_mask(ctx, S, r.topk, r.lost_inliers, vo->n_inliers, vo->rl_top_slot, vo->rc_lost, vo->rc_track, vo->rc_masked)))
-        return rc;
-    tb_reloc_params prm;
-    prm.map_point_only = vo->bw.map_point_only; prm.th_low = vo->bw.th_low; prm.nratio = vo->bw.nratio; prm.histo_len = vo->bw.histo_len;
-    prm.check_orientation = vo->bw.check_orientation; prm.min_inliers = r.min_inliers;
-    tb_reloc_out out = {};
-    out.best_rank = vo->rc_best_rank; out.best_kf = vo->rc_best_kf; out.best_Tcw = vo->rc_best_Tcw;
-    if ((rc = tb_relocalize_batch_dev(st, vo->p.K, vo->p.nlevels, vo->p.scale, vo->orb, vo->orb_desc, vo->orb_cnt, vo->fv_keys[0], vo->fv_cnt[0],
-                                      P, vo->rc_masked, r.topk, &prm, &out)))
-        return rc;
-    tb_vo_recover_args a;
-    a.topk = r.topk; a.pitch = P;
-    a.lost = vo->rc_lost; a.best_rank = vo->rc_best_rank; a.best_kf = vo->rc_best_kf; a.ix2 = st->ix2; a.best_Tcw = vo->rc_best_Tcw;
-    a.w_matches = st->matches; a.w_obs = st->obs; a.w_outlier = st->outlier; a.w_mcounts = st->mcounts; a.w_flags = st->flags;
-    a.w_ocounts = st->ocounts; a.w_ninl = st->ninl;
-    a.s_keys = st->keys; a.s_desc = st->desc; a.s_fv = (const unsigned long long*)st->fv; a.s_mp = st->mp; a.s_valid = st->valid;
-    a.s_counts = st->counts; a.s_fv_counts = st->fv_counts;
-    a.db_words = db->words; a.db_values = db->values; a.db_counts = db->counts;
-    a.word_ring = vo->rc_word_ring; a.node_ring = vo->rc_node_ring;
-    a.orb_counts = vo->orb_cnt;
-    a.Tcw = vo->Tcw[b]; a.mp = vo->mp[b]; a.valid = vo->valid[b]; a.obs = vo->obs; a.outlier = vo->outlier; a.matches = vo->matches;
-    a.obs_counts = vo->obs_counts; a.n_inliers = vo->n_inliers; a.mcounts = vo->mcounts; a.mflags = vo->mflags; a.recovered_kf = vo->rc_kf;
-    a.kf_orb = vo->kf_orb; a.kf_desc = vo->kf_desc; a.kf_fv = (unsigned long long*)vo->fv_keys[1]; a.kf_mp = vo->kf_mp;
-    a.kf_valid = vo->kf_valid; a.kf_cnt = vo->kf_cnt; a.kf_fv_cnt = vo->fv_cnt[1];
-    a.kf_bv_word = vo->bv_word[1]; a.kf_bv_val = vo->bv_val[1]; a.kf_bv_cnt = vo->bv_cnt[1];
-    a.kf_word = vo->bow_word[1]; a.kf_node = vo->bow_node[1]; a.kf_ids = vo->rc_kf_ids;
-    if ((rc = tbk_vo_recover_adopt(ctx, S, &a))) return rc;
-    return tbk_vo_recover_switch(ctx, S, &a);
-}
-
-/* A descriptor tracker's frame t after the left images are in img[b] (see include/tb_capi.h, tb_vo_tracker). */
-static int vo_step_desc(tb_vo* vo, int t, bool keyframe, const uint8_t* right, int stride, size_t pitch) {
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    const tb_vo_tracker& tr = vo->tr;
-    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
-    const size_t ip = (size_t)W * H, SP = (size_t)S * P;
-    const int a = vo->cur, b = a ^ 1;
-    int rc;
-    /* ORB operator() on every frame; the extractor's results do not outlive its next call, so they are copied out */
-    if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
-    if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
-    if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
-    if ((rc = tb_extractor_copy_results_dev(vo->ex, S, vo->orb, vo->orb_desc, vo->orb_cnt, P))) return rc;
-    if (tr.kind == TB_VO_BOW) {
-        /* :705 cur_frame_ptr->SetBow(vocabulary) on every frame: voc->transform(descriptors, mBowVec, mFeatVec, levelsup) */
-        if ((rc = tb_bow_transform_batch_dev(ctx, vo->voc, S, vo->orb_desc, vo->orb_cnt, P, vo->bw.levelsup, vo->bow_word[0], vo->bow_node[0],
-                                             vo->bow_wt, vo->fv_keys[0], vo->fv_cnt[0])))
-            return rc;
-        if ((rc = tb_bow_vector_batch_dev(ctx, vo->voc, S, vo->bow_word[0], vo->bow_wt, vo->orb_cnt, P, vo->bv_word[0], vo->bv_val[0],
-                                          vo->bv_cnt[0])))
-            return rc;
-    }
-    if (t == 0) {
-        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-    } else if (tr.kind == TB_VO_BOW) {
-        /* searchByBow(cur, key_frame, MapPointOnly): F1 = the current frame, F2 = the keyframe, whose map points are has_mp2 */
-        if ((rc = tb_search_by_bow_batch_dev(ctx, S, vo->orb, vo->orb_desc, P, vo->fv_keys[0], vo->fv_cnt[0], vo->kf_orb, vo->kf_desc, P,
-                                             vo->fv_keys[1], vo->fv_cnt[1], vo->kf_valid, vo->bw.map_point_only, tr.th_low, tr.nratio,
-                                             tr.histo_len, tr.check_orientation, vo->matches, P, vo->mcounts, vo->mflags)))
-            return rc;
-    } else if (tr.kind == TB_VO_BF) {
-        /* :712 searchByBF(cur, key_frame, 0, nLevels, ratio, minTh): the whole-set branch */
-        if ((rc = tb_search_by_bf_batch_dev(ctx, S, vo->orb_desc, vo->orb_cnt, vo->kf_desc, vo->kf_cnt, (size_t)P * 32, tr.bf_ratio,
-                                            tr.bf_min_th, vo->matches, P, vo->mcounts)))
-            return rc;
-    } else {
-        /* :713 searchByViolence(cur, key_frame, min_level, max_level, radius) over the keyframe's lookup grid */
-        if ((rc = tb_search_by_violence_batch_dev(ctx, S, vo->orb, vo->orb_desc, vo->orb_cnt, P, vo->kf_orb, vo->kf_desc, vo->kf_cnt, P,
-                                                  vo->kf_cell_start, vo->kf_cell_items, W, H, tr.min_level, tr.max_level, tr.radius,
-                                                  tr.th_low, tr.nratio, tr.histo_len, tr.check_orientation, vo->matches, P, vo->mcounts,
-                                                  vo->mflags)))
-            return rc;
-    }
-    /* the keys, the map points the matches carry over and the pose rows (match count 0 at frame 0: a fresh frame) */
-    if ((rc = tbk_vo_match_carry(ctx, S, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->kf_mp, vo->kf_valid, vo->kf_cnt, P,
-                                 vo->inv_sigma2, p.nlevels, vo->win, vo->keys[b], vo->kcnt[b], vo->mp[b], vo->valid[b], vo->obs,
-                                 vo->obs_counts, vo->outlier)))
-        return rc;
-    if (t > 0 &&
-        (rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
-        return rc;
-    if (vo->rec_on && t > 0 && (rc = vo_recover_stage(vo, b))) return rc;
-    if (keyframe) {
-        /* :774-785 extracts again on the same pyramid: the same keys, so SetKeys resizes m to m and keeps every carried map
-         * point -- nothing to do. Then :800 AddMapPointsByStereo and the new map points (:802-832), as the optical-flow loop. */
-        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
-        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
-                                                        vo->st_pts, vo->st_status, vo->depth)))
-            return rc;
-        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
-        /* key_frame = cur_frame_ptr (:836): a snapshot of fixed-size slabs; violence's lookup grid once per keyframe */
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_orb, vo->orb, SP * sizeof(tb_keypoint), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_desc, vo->orb_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_cnt, vo->orb_cnt, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp, vo->mp[b], SP * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_valid, vo->valid[b], SP, hipMemcpyDeviceToDevice, ctx->stream));
-        if (tr.kind == TB_VO_VIOLENCE &&
-            (rc = tb_frame_grid_batch_dev(ctx, S, vo->kf_orb, vo->kf_cnt, P, W, H, vo->kf_cell_start, vo->kf_cell_items)))
-            return rc;
-        if (tr.kind == TB_VO_BOW) {   /* the keyframe keeps the vectors SetBow gave it: they are not computed again */
-            TB_HIP(ctx, hipMemcpyAsync(vo->bow_word[1], vo->bow_word[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->bow_node[1], vo->bow_node[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->fv_keys[1], vo->fv_keys[0], SP * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->fv_cnt[1], vo->fv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->bv_word[1], vo->bv_word[0], SP * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->bv_val[1], vo->bv_val[0], SP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            TB_HIP(ctx, hipMemcpyAsync(vo->bv_cnt[1], vo->bv_cnt[0], (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            /* the keyframe database, when enabled: the snapshot's BowVector into the ring slot of this keyframe */
-            if (vo->db && (rc = tb_bow_db_add_dev(vo->db, vo->bv_word[1], vo->bv_val[1], vo->bv_cnt[1], P, t))) return rc;
-            /* the keyframe store, when enabled: the snapshot itself and the frame's optimised pose into the same ring slot */
-            if (vo->store && (rc = tb_kf_store_add_dev(vo->store, vo->kf_orb, vo->kf_desc, vo->kf_cnt, vo->fv_keys[1], vo->fv_cnt[1], vo->kf_mp,
-                                                       vo->kf_valid, P, vo->Tcw[b], t)))
-                return rc;
-            /* recovery, when enabled: the snapshot's word / node ids into the same ring slot (the store has just counted this
-             * add); this keyframe is what every sequence tracks against from now on */
-            if (vo->rec_on) {
-                if ((rc = tbk_vo_recover_ring_add(ctx, S, vo->bow_word[1], vo->bow_node[1], vo->kf_cnt, vo->store->cap, P,
-                                                  (int)((vo->store->nadded - 1) % vo->store->cap), vo->rc_word_ring, vo->rc_node_ring)))
-                    return rc;
-                TB_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)vo->rc_kf_ids, t, (size_t)S, ctx->stream));
-            }
-        }
-        vo->kf_frame = t;
-    }
-    return TB_OK;
-}
-
-/* A projection tracker's frame t after the left images are in img[b] (see include/tb_capi.h, tb_vo_tracker). */
-static int vo_step_proj(tb_vo* vo, int t, bool keyframe, const uint8_t* right, int stride, size_t pitch) {
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    const tb_vo_tracker& tr = vo->tr;
-    const bool map = tr.kind == TB_VO_PROJECTION_MAP;
-    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
-    const size_t ip = (size_t)W * H, SP = (size_t)S * P;
-    const int a = vo->cur, b = a ^ 1;
-    int rc;
-    /* test_projection.cpp:495-504: ORB operator(), SetKeys, AssignFeaturesToGrid on every frame */
-    if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
-    if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
-    if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
-    if ((rc = tb_extractor_copy_results_dev(vo->ex, S, vo->orb, vo->orb_desc, vo->orb_cnt, P))) return rc;
-    if ((rc = tb_frame_grid_batch_dev(ctx, S, vo->orb, vo->orb_cnt, P, W, H, vo->cell_start, vo->cell_items))) return rc;
-    if (t == 0) {
-        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mcounts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->mflags, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-    } else if (map) {
-        /* :516-517 searchByProjection(map_ptr, cur, radio) at the last frame's pose (:510) */
-        if ((rc = tb_search_by_projection_map_batch_dev(ctx, S, vo->Tcw[a], &vo->cam, W, H, vo->orb, vo->orb_desc, vo->taken, vo->orb_cnt, P,
-                                                        vo->cell_start, vo->cell_items, vo->map_rec[vo->map_cur], vo->map_desc[vo->map_cur],
-                                                        vo->map_n[vo->map_cur], vo->map_cap, vo->map_cap, vo->sf, p.nlevels, tr.nratio,
-                                                        tr.radio, tr.th_high, vo->matches, vo->Mcap, vo->mcounts, vo->mflags)))
-            return rc;
-    } else {
-        /* :512-513 searchByProjection(cur, key_frame) at the last frame's pose (:510) */
-        if ((rc = tb_search_by_projection_batch_dev(ctx, S, vo->Tcw[a], &vo->cam, W, H, vo->orb, vo->orb_desc, vo->taken, vo->orb_cnt, P,
-                                                    vo->cell_start, vo->cell_items, vo->kf_orb, vo->kf_rec, vo->kf_mp_desc, vo->kf_cnt, P,
-                                                    vo->sf, p.nlevels, tr.nratio, tr.th_high, tr.histo_len, tr.check_orientation,
-                                                    vo->matches, vo->Mcap, vo->mcounts, vo->mflags)))
-            return rc;
-    }
-    /* :520-530: the keys, the map points (and their descriptors) the matches carry over, the pose rows (no match at frame 0) */
-    if (map) {
-        rc = tbk_vo_proj_carry(ctx, S, 1, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->Mcap, nullptr, nullptr, vo->map_rec[vo->map_cur],
-                               vo->map_desc[vo->map_cur], vo->map_n[vo->map_cur], vo->map_cap, P, vo->inv_sigma2, p.nlevels, vo->win,
-                               vo->keys[b], vo->kcnt[b], vo->mp[b], vo->valid[b], vo->mp_desc, vo->obs, vo->obs_counts, vo->outlier);
-    } else {
-        rc = tbk_vo_proj_carry(ctx, S, 0, vo->orb, vo->orb_cnt, vo->matches, vo->mcounts, vo->Mcap, vo->kf_mp, vo->kf_valid, nullptr,
-                               vo->kf_mp_desc, vo->kf_cnt, P, P, vo->inv_sigma2, p.nlevels, vo->win, vo->keys[b], vo->kcnt[b], vo->mp[b],
-                               vo->valid[b], vo->mp_desc, vo->obs, vo->obs_counts, vo->outlier);
-    }
-    if (rc) return rc;
-    if (t > 0 &&
-        (rc = tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr)))
-        return rc;
-    if (keyframe) {
-        /* :577-634: the second ORB call returns the same keys (see vo_step_desc); stereo depths, the new map points */
-        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
-        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
-                                                        vo->st_pts, vo->st_status, vo->depth)))
-            return rc;
-        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
-        int slot = 0;
-        if (map) {
-            if (vo->map_nblk == vo->mapK) {   /* the oldest keyframe's points leave; the survivors move into the other set */
-                const int c = vo->map_cur, d = c ^ 1;
-                if ((rc = tbk_vo_map_evict(ctx, S, vo->map_rec[c], vo->map_desc[c], vo->map_n[c], vo->map_blocks[c], vo->mapK, vo->map_cap,
-                                           vo->map_rec[d], vo->map_desc[d], vo->map_n[d], vo->map_blocks[d])))
-                    return rc;
-                vo->map_cur = d;
-                vo->map_nblk = vo->mapK - 1;
-            }
-            slot = vo->map_nblk++;
-        }
-        const int c = vo->map_cur;
-        if ((rc = tbk_vo_kf_append(ctx, S, vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->orb_desc, vo->Tcw[b], P, vo->mp_desc,
-                                   map ? nullptr : vo->kf_rec, map ? vo->map_rec[c] : nullptr, map ? vo->map_desc[c] : nullptr,
-                                   map ? vo->map_n[c] : nullptr, map ? vo->map_blocks[c] : nullptr, map ? vo->mapK : 0, slot, vo->map_cap)))
-            return rc;
-        /* key_frame = cur_frame_ptr (:641) */
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_orb, vo->orb, SP * sizeof(tb_keypoint), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_desc, vo->orb_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_cnt, vo->orb_cnt, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp, vo->mp[b], SP * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_valid, vo->valid[b], SP, hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemcpyAsync(vo->kf_mp_desc, vo->mp_desc, SP * 32, hipMemcpyDeviceToDevice, ctx->stream));
-        vo->kf_frame = t;
-    }
-    return TB_OK;
-}
-
-/* The optical-flow tracker's frame t > 0 after the left images are in img[b]. */
-static int vo_track_opflow(tb_vo* vo) {
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
-    const size_t ip = (size_t)W * H;
-    const int a = vo->cur, b = a ^ 1;
-    int rc;
-    /* test_vo.cpp:716: searchByOPFlow(cur, last, pts, true, true) -- the tracked points land in this frame's key list */
-    if ((rc = tb_search_by_opflow_batch_dev(ctx, S, vo->img[b], vo->img[a], W, H, W, ip, &vo->cam, vo->keys[a], vo->kcnt[a], P, 1, 1,
-                                            vo->keys[b], vo->status, vo->matches, P, vo->mcounts)))
-        return rc;
-    if ((rc = tbk_vo_track(ctx, S, vo->kcnt[a], vo->status, vo->keys[b], vo->mp[a], vo->valid[a], P, vo->kcnt[b], vo->mp[b], vo->valid[b],
-                           vo->obs, vo->obs_counts, vo->outlier)))
-        return rc;
-    /* :761 LocalBA::PoseOptimization, started from the last frame's pose (:688) */
-    return tb_pose_opt_batch_dev(ctx, S, p.K, vo->Tcw[a], vo->obs, vo->obs_counts, P, vo->outlier, vo->Tcw[b], vo->n_inliers, nullptr);
-}
-
-/* Frame t of every sequence (the arguments are checked): what tb_vo_step_dev launches. */
-static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    const int S = vo->nseq, P = vo->P, W = p.width, H = p.height;
-    const size_t ip = (size_t)W * H;
-    const int a = vo->cur, b = a ^ 1;   /* a: last frame, b: this frame */
-    int rc;
-    if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
-    if (vo->tr.kind != TB_VO_OPFLOW) {
-        if ((rc = vo_is_proj(vo) ? vo_step_proj(vo, t, keyframe, right, stride, pitch) : vo_step_desc(vo, t, keyframe, right, stride, pitch)))
-            return rc;
-    } else if (t == 0) {
-        TB_HIP(ctx, hipMemcpyAsync(vo->Tcw[b], vo->Tcw[a], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->kcnt[b], 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->obs_counts, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(vo->n_inliers, 0, (size_t)S * sizeof(int32_t), ctx->stream));
-    } else if ((rc = vo_track_opflow(vo))) {
-        return rc;
-    }
-    if (keyframe && vo->tr.kind == TB_VO_OPFLOW) {
-        /* :774-785 ORB operator()(pyramid, sf, target, init_th, min_th) + SetKeys */
-        if ((rc = tbk_vo_copy_image(ctx, S, right, W, H, stride, pitch, vo->right))) return rc;
-        if ((rc = tb_extractor_set_images_dev(vo->ex, vo->img[b], S, W, ip))) return rc;
-        if ((rc = tb_extractor_build_pyramid(vo->ex, S))) return rc;
-        if ((rc = tb_extractor_orb(vo->ex, S, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
-        const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
-        tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
-        if ((rc = tbk_vo_kf_pack(ctx, S, kps, cnt, selCap, P, vo->keys[b], vo->kcnt[b], vo->valid[b]))) return rc;
-        /* :800 AddMapPointsByStereo(cur, right, d * fx, fx), then the new map points (:802-832) */
-        if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, S, vo->right, vo->img[b], W, H, W, ip, &vo->cam, vo->keys[b], vo->kcnt[b], P, p.bf,
-                                                        vo->st_pts, vo->st_status, vo->depth)))
-            return rc;
-        if ((rc = tbk_vo_kf_spawn(ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b]))) return rc;
-    }
-    vo->cur = b;
-    vo->next = t + 1;
-    for (int s = 0; s < S; s++) {
-        vo->seq_frame[s] = t;
-        if (keyframe) vo->seq_kf_frame[s] = t;
-    }
-    return TB_OK;
-}
-
-int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    if (vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev: the loop is in ragged mode (tb_vo_step_ragged_dev, or tb_vo_reset_dev)");
-    if (vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_dev before tb_vo_reset_dev");
-    const int t = vo->next;
-    const bool keyframe = t % p.keyframe_every == 0;
-    if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
-    if (keyframe && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
-    return vo_step_lock(vo, t, keyframe, left, right, stride, pitch);
-}
-
-/* ---- ragged batches: see include/tb_capi.h, tb_vo_step_ragged_dev */
-static const char* vo_ragged_unsupported(const tb_vo* vo) {
-    if (vo->tr.kind == TB_VO_PROJECTION_MAP) return "TB_VO_PROJECTION_MAP counts the map's blocks and evicts for the whole batch";
-    if (vo->db) return "the keyframe database's ring slot is counted for the whole batch";
-    return nullptr;
-}
-
-/* the per-frame outputs the loop owns, as a set */
-static tb_vo_frame_out vo_frame_out(const tb_vo* vo) {
-    tb_vo_frame_out o;
-    o.obs = vo->obs; o.obs_counts = vo->obs_counts; o.outlier = vo->outlier; o.n_inliers = vo->n_inliers;
-    if (vo->tr.kind != TB_VO_OPFLOW) {
-        o.orb = vo->orb; o.orb_desc = vo->orb_desc; o.orb_cnt = vo->orb_cnt; o.matches = vo->matches; o.mcounts = vo->mcounts;
-        o.mflags = vo->mflags; o.mp_desc = vo->mp_desc;
-    }
-    if (vo->tr.kind == TB_VO_BOW) {
-        o.bow_word = vo->bow_word[0]; o.bow_node = vo->bow_node[0]; o.fv_keys = vo->fv_keys[0]; o.fv_cnt = vo->fv_cnt[0];
-        o.bv_word = vo->bv_word[0]; o.bv_val = vo->bv_val[0]; o.bv_cnt = vo->bv_cnt[0];
-    }
-    return o;
-}
-
-/* The step writes the other set from now on; rg_prev keeps what the last step left. */
-static void vo_swap_frame_out(tb_vo* vo) {
-    const tb_vo_frame_out cur = vo_frame_out(vo), n = vo->rg_prev;
-    vo->obs = n.obs; vo->obs_counts = n.obs_counts; vo->outlier = n.outlier; vo->n_inliers = n.n_inliers;
-    if (vo->tr.kind != TB_VO_OPFLOW) {
-        vo->orb = n.orb; vo->orb_desc = n.orb_desc; vo->orb_cnt = n.orb_cnt; vo->matches = n.matches; vo->mcounts = n.mcounts;
-        vo->mflags = n.mflags; vo->mp_desc = n.mp_desc;
-    }
-    if (vo->tr.kind == TB_VO_BOW) {
-        vo->bow_word[0] = n.bow_word; vo->bow_node[0] = n.bow_node; vo->fv_keys[0] = n.fv_keys; vo->fv_cnt[0] = n.fv_cnt;
-        vo->bv_word[0] = n.bv_word; vo->bv_val[0] = n.bv_val; vo->bv_cnt[0] = n.bv_cnt;
-    }
-    vo->rg_prev = cur;
-}
-
-/* Everything ragged mode needs beyond the lock-step loop, allocated once (allocation synchronises; a step never grows it). */
-static int vo_ragged_init(tb_vo* vo) {
-    if (vo->rg_ready) return TB_OK;
-    tb_ctx* ctx = vo->ctx;
-    const size_t S = (size_t)vo->nseq, P = (size_t)vo->P, img = (size_t)vo->p.width * vo->p.height;
-    tb_vo_frame_out& q = vo->rg_prev;
-    TB_HIP(ctx, hipMalloc(&q.obs, S * P * sizeof(tb_obs)));
-    TB_HIP(ctx, hipMalloc(&q.obs_counts, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&q.outlier, S * P));
-    TB_HIP(ctx, hipMalloc(&q.n_inliers, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMemsetAsync(q.obs_counts, 0, S * sizeof(int32_t), ctx->stream));
-    TB_HIP(ctx, hipMemsetAsync(q.n_inliers, 0, S * sizeof(int32_t), ctx->stream));
-    if (vo->tr.kind != TB_VO_OPFLOW) {
-        TB_HIP(ctx, hipMalloc(&q.orb, S * P * sizeof(tb_keypoint)));
-        TB_HIP(ctx, hipMalloc(&q.orb_desc, S * P * 32));
-        TB_HIP(ctx, hipMalloc(&q.orb_cnt, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.matches, S * (size_t)vo->Mcap * sizeof(tb_match)));
-        TB_HIP(ctx, hipMalloc(&q.mcounts, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.mflags, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMemsetAsync(q.orb_cnt, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(q.mcounts, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(q.mflags, 0, S * sizeof(int32_t), ctx->stream));
-        if (vo->mp_desc) {
-            TB_HIP(ctx, hipMalloc(&q.mp_desc, S * P * 32));
-            TB_HIP(ctx, hipMemsetAsync(q.mp_desc, 0, S * P * 32, ctx->stream));
-        }
-    }
-    if (vo->tr.kind == TB_VO_BOW) {
-        TB_HIP(ctx, hipMalloc(&q.bow_word, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.bow_node, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.fv_keys, S * P * sizeof(uint64_t)));
-        TB_HIP(ctx, hipMalloc(&q.fv_cnt, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.bv_word, S * P * sizeof(int32_t)));
-        TB_HIP(ctx, hipMalloc(&q.bv_val, S * P * sizeof(double)));
-        TB_HIP(ctx, hipMalloc(&q.bv_cnt, S * sizeof(int32_t)));
-        TB_HIP(ctx, hipMemsetAsync(q.fv_cnt, 0, S * sizeof(int32_t), ctx->stream));
-        TB_HIP(ctx, hipMemsetAsync(q.bv_cnt, 0, S * sizeof(int32_t), ctx->stream));
-    }
-    TB_HIP(ctx, hipMalloc(&vo->rg_left, S * img));
-    TB_HIP(ctx, hipMalloc(&vo->rg_keys, S * P * 2 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&vo->rg_kcnt, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rg_dev, 2 * S * sizeof(int32_t)));
-    TB_HIP(ctx, hipHostMalloc((void**)&vo->rg_pin, (size_t)tb_vo::RG_RING * 2 * S * sizeof(int32_t), hipHostMallocDefault));
-    for (hipEvent_t& e : vo->rg_ev) TB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    vo->rg_ready = true;
-    return TB_OK;
-}
-
-/* The one host -> device copy of a ragged call: mask [nseq] and index list [nseq] from a pinned ring slot into rg_dev. The slot
- * is reused RG_RING calls later, after its event says the copy has run. Returns the slot's host pointer through *pin. */
-static int vo_ragged_stage(tb_vo* vo, int32_t** pin) {
-    tb_ctx* ctx = vo->ctx;
-    const int k = (int)(vo->rg_slot % tb_vo::RG_RING);
-    TB_HIP(ctx, hipEventSynchronize(vo->rg_ev[k]));
-    *pin = vo->rg_pin + (size_t)k * 2 * vo->nseq;
-    return TB_OK;
-}
-static int vo_ragged_upload(tb_vo* vo, const int32_t* pin) {
-    tb_ctx* ctx = vo->ctx;
-    const int k = (int)(vo->rg_slot++ % tb_vo::RG_RING);
-    TB_HIP(ctx, hipMemcpyAsync(vo->rg_dev, pin, (size_t)2 * vo->nseq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    TB_HIP(ctx, hipEventRecord(vo->rg_ev[k], ctx->stream));
-    return TB_OK;
-}
-
-int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo || !which || !Tcw0) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    if (const char* why = vo_ragged_unsupported(vo)) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_reset_seq_dev: %s", why);
-    int rc;
-    if ((rc = vo_ragged_init(vo))) return rc;
-    const int S = vo->nseq;
-    int32_t* pin;
-    if ((rc = vo_ragged_stage(vo, &pin))) return rc;
-    for (int s = 0; s < S; s++) { pin[s] = which[s] ? 1 : 0; pin[S + s] = 0; }
-    if ((rc = vo_ragged_upload(vo, pin))) return rc;
-    const bool desc = vo->tr.kind != TB_VO_OPFLOW, bow = vo->tr.kind == TB_VO_BOW;
-    if ((rc = tbk_vo_reset_seq(ctx, S, vo->rg_dev, Tcw0, vo->Tcw[vo->cur], vo->kcnt[vo->cur], desc ? vo->kf_cnt : nullptr,
-                               bow ? vo->fv_cnt[1] : nullptr, bow ? vo->bv_cnt[1] : nullptr,
-                               vo->tr.kind == TB_VO_VIOLENCE ? vo->kf_cell_start : nullptr, 4321)))
-        return rc;
-    for (int s = 0; s < S; s++)
-        if (which[s]) { vo->seq_frame[s] = -1; vo->seq_kf_frame[s] = -1; vo->seq_reset[s] = 1; }
-    vo->ragged = true;
-    vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
-    vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
-    return TB_OK;
-}
-
-/* The keyframe block of a ragged step on the compacted batch of the nk sequences h_idx / d_idx name (ascending). */
-static int vo_keyframe_ragged(tb_vo* vo, int nk, const int32_t* h_idx, const int32_t* d_idx, const uint8_t* right, int stride, size_t pitch) {
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    const int P = vo->P, W = p.width, H = p.height, b = vo->cur;
-    const size_t ip = (size_t)W * H;
-    int rc;
-    if ((rc = tbk_vo_copy_image(ctx, nk, right, W, H, stride, pitch, vo->right, d_idx))) return rc;
-    if ((rc = tbk_vo_copy_image(ctx, nk, vo->img[b], W, H, W, ip, vo->rg_left, d_idx))) return rc;
-    if (vo->tr.kind == TB_VO_OPFLOW) {
-        if ((rc = tb_extractor_set_images_dev(vo->ex, vo->rg_left, nk, W, ip))) return rc;
-        if ((rc = tb_extractor_build_pyramid(vo->ex, nk))) return rc;
-        if ((rc = tb_extractor_orb(vo->ex, nk, p.target, p.init_th, p.min_th, 0, nullptr, 0))) return rc;
-        const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
-        tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
-        if ((rc = tbk_vo_kf_pack(ctx, nk, kps, cnt, selCap, P, vo->keys[b], vo->kcnt[b], vo->valid[b], d_idx))) return rc;
-    }
-    if ((rc = tbk_vo_kf_gather(ctx, nk, d_idx, vo->keys[b], vo->kcnt[b], P, vo->rg_keys, vo->rg_kcnt))) return rc;
-    if ((rc = tb_add_map_points_by_stereo_batch_dev(ctx, nk, vo->right, vo->rg_left, W, H, W, ip, &vo->cam, vo->rg_keys, vo->rg_kcnt, P, p.bf,
-                                                    vo->st_pts, vo->st_status, vo->depth)))
-        return rc;
-    if ((rc = tbk_vo_kf_spawn(ctx, nk, vo->keys[b], vo->kcnt[b], vo->depth, vo->Tcw[b], p.K, P, vo->mp[b], vo->valid[b], d_idx))) return rc;
-    if (vo->tr.kind == TB_VO_OPFLOW) return TB_OK;
-    if (vo->tr.kind == TB_VO_PROJECTION &&
-        (rc = tbk_vo_kf_append(ctx, nk, vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->orb_desc, vo->Tcw[b], P, vo->mp_desc, vo->kf_rec,
-                               nullptr, nullptr, nullptr, nullptr, 0, 0, vo->map_cap, d_idx)))
-        return rc;
-    /* key_frame = cur_frame_ptr for these sequences only */
-    const tb_vo_frame_out cur = vo_frame_out(vo);
-    tb_vo_kf_out kf;
-    kf.orb = vo->kf_orb; kf.desc = vo->kf_desc; kf.cnt = vo->kf_cnt; kf.mp = vo->kf_mp; kf.valid = vo->kf_valid; kf.mp_desc = vo->kf_mp_desc;
-    if (vo->tr.kind == TB_VO_BOW) {
-        kf.bow_word = vo->bow_word[1]; kf.bow_node = vo->bow_node[1]; kf.fv_keys = vo->fv_keys[1]; kf.fv_cnt = vo->fv_cnt[1];
-        kf.bv_word = vo->bv_word[1]; kf.bv_val = vo->bv_val[1]; kf.bv_cnt = vo->bv_cnt[1];
-    }
-    if ((rc = tbk_vo_kf_snapshot(ctx, nk, d_idx, P, &cur, vo->mp[b], vo->valid[b], &kf))) return rc;
-    if (vo->tr.kind == TB_VO_VIOLENCE) {
-        /* the keyframe's lookup grid, one call per run of neighbouring sequences */
-        for (int j = 0; j < nk;) {
-            int e = j + 1;
-            while (e < nk && h_idx[e] == h_idx[e - 1] + 1) e++;
-            const size_t s0 = (size_t)h_idx[j];
-            if ((rc = tb_frame_grid_batch_dev(ctx, e - j, vo->kf_orb + s0 * P, vo->kf_cnt + s0, P, W, H, vo->kf_cell_start + s0 * 4321,
-                                              vo->kf_cell_items + s0 * P)))
-                return rc;
-            j = e;
-        }
-    }
-    return TB_OK;
-}
-
-int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch, const uint8_t* active,
-                          const uint8_t* force_keyframe) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    const tb_vo_params& p = vo->p;
-    if (const char* why = vo_ragged_unsupported(vo)) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_step_ragged_dev: %s", why);
-    if (!vo->ragged && vo->next < 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_ragged_dev before tb_vo_reset_dev / tb_vo_reset_seq_dev");
-    const int S = vo->nseq;
-    int nact = 0, nkf = 0, t0 = -1;
-    bool same_t = true;
-    for (int s = 0; s < S; s++) {
-        if (active && !active[s]) continue;
-        if (!vo->seq_reset[s]) return tb_fail(ctx, TB_ESTATE, "tb_vo_step_ragged_dev: sequence %d is active and was never reset", s);
-        const int t = vo->seq_frame[s] + 1;
-        if (nact++ == 0) t0 = t;
-        same_t = same_t && t == t0;
-        nkf += t % p.keyframe_every == 0 || (force_keyframe && force_keyframe[s]);
-    }
-    if (nact == 0) return TB_OK;   /* every sequence idles: nothing changes */
-    if (!left || stride < p.width || pitch < (size_t)stride * p.height)
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_step_ragged_dev: left images / geometry");
-    if (nkf && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_ragged_dev: %d sequences have a keyframe and need the right images", nkf);
-    int rc;
-    if (nact == S && same_t && (nkf == 0 || nkf == S)) {
-        /* every sequence at the same frame with the same decision: this is tb_vo_step_dev's step, launch for launch */
-        if ((rc = vo_step_lock(vo, t0, nkf == S, left, right, stride, pitch))) return rc;
-        if (vo->ragged) vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
-        return TB_OK;
-    }
-    if ((rc = vo_ragged_init(vo))) return rc;
-    /* the masks, known to the host, go up in one copy; nothing is decided on the device and nothing is read back */
-    int32_t* pin;
-    if ((rc = vo_ragged_stage(vo, &pin))) return rc;
-    nkf = 0;
-    for (int s = 0; s < S; s++) {
-        const bool act = !active || active[s];
-        const int t = vo->seq_frame[s] + 1;
-        pin[s] = act ? (t == 0 ? 2 : 1) : 0;
-        if (act && (t % p.keyframe_every == 0 || (force_keyframe && force_keyframe[s]))) pin[S + nkf++] = s;
-    }
-    for (int j = nkf; j < S; j++) pin[S + j] = 0;
-    if ((rc = vo_ragged_upload(vo, pin))) return rc;
-    const int P = vo->P, W = p.width, H = p.height;
-    const int a = vo->cur, b = a ^ 1;
-    if ((rc = tbk_vo_copy_image(ctx, S, left, W, H, stride, pitch, vo->img[b]))) return rc;
-    /* the tracking half over all sequences, as frame t > 0 of the lock-step loop, into the other set of per-frame outputs: a
-     * sequence without keys or keyframe gets no match, no row and keeps its pose; an idle one is restored below */
-    vo_swap_frame_out(vo);
-    if (vo->tr.kind == TB_VO_OPFLOW) rc = vo_track_opflow(vo);
-    else if (vo_is_proj(vo)) rc = vo_step_proj(vo, 1, false, nullptr, 0, 0);
-    else rc = vo_step_desc(vo, 1, false, nullptr, 0, 0);
-    if (rc) { vo_swap_frame_out(vo); return rc; }
-    tb_vo_hold_args h;
-    h.mask = vo->rg_dev; h.pitch = P; h.match_pitch = vo->Mcap; h.npx = (size_t)W * H;
-    h.img[0] = vo->img[a]; h.img[1] = vo->img[b]; h.keys[0] = vo->keys[a]; h.keys[1] = vo->keys[b]; h.mp[0] = vo->mp[a]; h.mp[1] = vo->mp[b];
-    h.valid[0] = vo->valid[a]; h.valid[1] = vo->valid[b]; h.kcnt[0] = vo->kcnt[a]; h.kcnt[1] = vo->kcnt[b];
-    h.Tcw[0] = vo->Tcw[a]; h.Tcw[1] = vo->Tcw[b];
-    h.prev = vo->rg_prev; h.cur = vo_frame_out(vo);
-    if ((rc = tbk_vo_hold(ctx, S, &h))) return rc;
-    vo->cur = b;
-    if (nkf && (rc = vo_keyframe_ragged(vo, nkf, pin + S, vo->rg_dev + S, right, stride, pitch))) return rc;
-    for (int s = 0; s < S; s++)
-        if (pin[s]) vo->seq_frame[s]++;
-    for (int j = 0; j < nkf; j++) vo->seq_kf_frame[pin[S + j]] = vo->seq_frame[pin[S + j]];
-    vo->ragged = true;
-    vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
-    vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
-    return TB_OK;
-}
-
-int tb_vo_frames(tb_vo* vo, int32_t* frames, int32_t* kf_frames) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    for (int s = 0; s < vo->nseq; s++) {
-        if (frames) frames[s] = vo->seq_frame[s];
-        if (kf_frames) kf_frames[s] = vo->seq_kf_frame[s];
-    }
-    return TB_OK;
-}
-
-int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const float** map_points, const uint8_t** mp_valid,
-                    const int32_t** key_counts, const tb_obs** obs, const int32_t** obs_counts, const int32_t** n_inliers,
-                    const uint8_t** outlier, int* key_pitch, int* frame) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    const int c = vo->cur;
-    if (Tcw) *Tcw = vo->Tcw[c];
-    if (keys_xy) *keys_xy = vo->keys[c];
-    if (map_points) *map_points = vo->mp[c];
-    if (mp_valid) *mp_valid = vo->valid[c];
-    if (key_counts) *key_counts = vo->kcnt[c];
-    if (obs) *obs = vo->obs;
-    if (obs_counts) *obs_counts = vo->obs_counts;
-    if (n_inliers) *n_inliers = vo->n_inliers;
-    if (outlier) *outlier = vo->outlier;
-    if (key_pitch) *key_pitch = vo->P;
-    if (frame) *frame = vo->next - 1 < -1 ? -1 : vo->next - 1;
-    return TB_OK;
-}
-
-int tb_vo_tracker_state_dev(tb_vo* vo, const tb_keypoint** orb, const uint8_t** orb_desc, const int32_t** orb_counts,
-                            const tb_match** matches, const int32_t** match_counts, const int32_t** flags, const tb_keypoint** kf_orb,
-                            const uint8_t** kf_desc, const float** kf_map_points, const uint8_t** kf_mp_valid,
-                            const int32_t** kf_counts, int* kf_frame) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (vo->tr.kind == TB_VO_OPFLOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_tracker_state_dev: the loop tracks by optical flow");
-    if (orb) *orb = vo->orb;
-    if (orb_desc) *orb_desc = vo->orb_desc;
-    if (orb_counts) *orb_counts = vo->orb_cnt;
-    if (matches) *matches = vo->matches;
-    if (match_counts) *match_counts = vo->mcounts;
-    if (flags) *flags = vo->mflags;
-    if (kf_orb) *kf_orb = vo->kf_orb;
-    if (kf_desc) *kf_desc = vo->kf_desc;
-    if (kf_map_points) *kf_map_points = vo->kf_mp;
-    if (kf_mp_valid) *kf_mp_valid = vo->kf_valid;
-    if (kf_counts) *kf_counts = vo->kf_cnt;
-    if (kf_frame) *kf_frame = vo->kf_frame;
-    return TB_OK;
-}
-
-int tb_vo_bow_state_dev(tb_vo* vo, const uint64_t** fv_keys, const int32_t** fv_counts, const int32_t** bv_words, const double** bv_values,
-                        const int32_t** bv_counts, const int32_t** word_ids, const int32_t** node_ids, const uint64_t** kf_fv_keys,
-                        const int32_t** kf_fv_counts, const int32_t** kf_bv_words, const double** kf_bv_values, const int32_t** kf_bv_counts,
-                        const int32_t** kf_word_ids, const int32_t** kf_node_ids) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (vo->tr.kind != TB_VO_BOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_state_dev: the loop does not track by searchByBow");
-    if (fv_keys) *fv_keys = vo->fv_keys[0];
-    if (fv_counts) *fv_counts = vo->fv_cnt[0];
-    if (bv_words) *bv_words = vo->bv_word[0];
-    if (bv_values) *bv_values = vo->bv_val[0];
-    if (bv_counts) *bv_counts = vo->bv_cnt[0];
-    if (word_ids) *word_ids = vo->bow_word[0];
-    if (node_ids) *node_ids = vo->bow_node[0];
-    if (kf_fv_keys) *kf_fv_keys = vo->fv_keys[1];
-    if (kf_fv_counts) *kf_fv_counts = vo->fv_cnt[1];
-    if (kf_bv_words) *kf_bv_words = vo->bv_word[1];
-    if (kf_bv_values) *kf_bv_values = vo->bv_val[1];
-    if (kf_bv_counts) *kf_bv_counts = vo->bv_cnt[1];
-    if (kf_word_ids) *kf_word_ids = vo->bow_word[1];
-    if (kf_node_ids) *kf_node_ids = vo->bow_node[1];
-    return TB_OK;
-}
-
-int tb_vo_bow_db_enable(tb_vo* vo, int capacity) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (vo->tr.kind != TB_VO_BOW) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable: the loop does not track by searchByBow");
-    if (vo->next > 0) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable after a step (frame %d)", vo->next - 1);
-    if (vo->db) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_enable: the database is enabled already");
-    return tb_bow_db_create(vo->ctx, vo->nseq, capacity, vo->P, vo->voc->scoring, &vo->db);
-}
-
-int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out) {
-    if (!vo || !out) return TB_EINVAL;
-    *out = nullptr;
-    if (!vo->db) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_bow_db_get: the keyframe database is not enabled");
-    *out = vo->db;
-    return TB_OK;
-}
-
-int tb_vo_reloc_enable(tb_vo* vo, int max_candidates) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    if (vo->tr.kind != TB_VO_BOW) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: the loop does not track by searchByBow");
-    if (!vo->db) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: the keyframe database is not enabled (tb_vo_bow_db_enable)");
-    if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable after a step (frame %d)", vo->next - 1);
-    if (vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_enable: relocalisation is enabled already");
-    int rc = tb_kf_store_create(ctx, vo->nseq, vo->db->cap, vo->P, max_candidates, &vo->store);
-    if (rc) return rc;
-    const size_t S = (size_t)vo->nseq;
-    TB_HIP(ctx, hipMalloc(&vo->rl_scores, S * vo->db->cap * sizeof(double)));
-    TB_HIP(ctx, hipMalloc(&vo->rl_top_score, S * max_candidates * sizeof(double)));
-    TB_HIP(ctx, hipMalloc(&vo->rl_top_slot, S * max_candidates * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rl_top_kf, S * max_candidates * sizeof(int32_t)));
-    return TB_OK;
-}
-
-int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
-                         double* top_score, int32_t* top_count, const tb_reloc_out* out) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_dev: relocalisation is not enabled (tb_vo_reloc_enable)");
-    if (vo->next < 1) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_dev before the first step");
-    if (topk < 1 || topk > vo->store->max_cand || exclude_newest < 0)
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_relocalize_dev: topk %d (1..%d), exclude_newest %d", topk, vo->store->max_cand, exclude_newest);
-    if (!scores) scores = vo->rl_scores;
-    if (!top_slot) top_slot = vo->rl_top_slot;
-    if (!top_kf) top_kf = vo->rl_top_kf;
-    if (!top_score) top_score = vo->rl_top_score;
-    int rc = tb_bow_db_query_dev(vo->db, vo->bv_word[0], vo->bv_val[0], vo->bv_cnt[0], vo->P, exclude_newest, topk, scores, top_slot, top_kf,
-                                 top_score, top_count);
-    if (rc) return rc;
-    tb_reloc_params prm;
-    prm.map_point_only = vo->bw.map_point_only; prm.th_low = vo->bw.th_low; prm.nratio = vo->bw.nratio; prm.histo_len = vo->bw.histo_len;
-    prm.check_orientation = vo->bw.check_orientation; prm.min_inliers = min_inliers;
-    return tb_relocalize_batch_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, vo->orb, vo->orb_desc, vo->orb_cnt, vo->fv_keys[0],
-                                   vo->fv_cnt[0], vo->P, top_slot, topk, &prm, out);
-}
-
-int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    tb_ctx* ctx = vo->ctx;
-    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
-    if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable after a step (frame %d)", vo->next - 1);
-    if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: recovery is enabled already");
-    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: null parameters");
-    if (prm->lost_inliers < 0 || prm->min_inliers < 0 || prm->exclude_newest < 0 || prm->topk < 1 || prm->topk > vo->store->max_cand)
-        return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: lost_inliers %d, topk %d (1..%d), exclude_newest %d, min_inliers %d",
-                       prm->lost_inliers, prm->topk, vo->store->max_cand, prm->exclude_newest, prm->min_inliers);
-    const size_t S = (size_t)vo->nseq, ring = S * vo->store->cap * vo->P;
-    TB_HIP(ctx, hipMalloc(&vo->rc_lost, S));
-    TB_HIP(ctx, hipMalloc(&vo->rc_track, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_kf, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_kf_ids, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_best_rank, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_best_kf, S * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_best_Tcw, S * 16 * sizeof(float)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_masked, S * prm->topk * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_word_ring, ring * sizeof(int32_t)));
-    TB_HIP(ctx, hipMalloc(&vo->rc_node_ring, ring * sizeof(int32_t)));
-    int rc = vo_recover_clear(vo);
-    if (rc) return rc;
-    vo->rec = *prm;
-    vo->rec_on = true;
-    return TB_OK;
-}
-
-int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** track_inliers, const int32_t** recovered_kf,
-                            const int32_t** kf_ids, const int32_t** kf_word_ring, const int32_t** kf_node_ring) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (!vo->rec_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_recover_state_dev: recovery is not enabled (tb_vo_recover_enable)");
-    if (lost) *lost = vo->rc_lost;
-    if (track_inliers) *track_inliers = vo->rc_track;
-    if (recovered_kf) *recovered_kf = vo->rc_kf;
-    if (kf_ids) *kf_ids = vo->rc_kf_ids;
-    if (kf_word_ring) *kf_word_ring = vo->rc_word_ring;
-    if (kf_node_ring) *kf_node_ring = vo->rc_node_ring;
-    return TB_OK;
-}
-
-int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out) {
-    if (!vo || !out) return TB_EINVAL;
-    *out = nullptr;
-    if (!vo->store) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_kf_store_get: relocalisation is not enabled");
-    *out = vo->store;
-    return TB_OK;
-}
-
-int tb_vo_mp_desc_dev(tb_vo* vo, const uint8_t** mp_desc, const uint8_t** kf_mp_desc) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (!vo_is_proj(vo)) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_mp_desc_dev: the loop's tracker carries no map-point descriptors");
-    if (mp_desc) *mp_desc = vo->mp_desc;
-    if (kf_mp_desc) *kf_mp_desc = vo->kf_mp_desc;
-    return TB_OK;
-}
-
-int tb_vo_map_state_dev(tb_vo* vo, const tb_mappoint** points, const uint8_t** desc, const int32_t** counts, const int32_t** block_counts,
-                        int* capacity, int* map_keyframes, int* blocks) {
-    TB_ENTER((vo ? vo->ctx : nullptr));
-    if (!vo) return TB_EINVAL;
-    if (!vo->mapK) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_map_state_dev: the loop has no map");
-    const int c = vo->map_cur;
-    if (points) *points = vo->map_rec[c];
-    if (desc) *desc = vo->map_desc[c];
-    if (counts) *counts = vo->map_n[c];
-    if (block_counts) *block_counts = vo->map_blocks[c];
-    if (capacity) *capacity = vo->map_cap;
-    if (map_keyframes) *map_keyframes = vo->mapK;
-    if (blocks) *blocks = vo->map_nblk;
     return TB_OK;
 }
 

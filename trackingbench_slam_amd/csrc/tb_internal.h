@@ -16,6 +16,7 @@
 #define TB_BORDER 16          /* EDGE_THRESHOLD - 3, ORBextractor.cpp:749 */
 #define TB_NODE_CAP_MAX 2048  /* quadtree list capacity that fits LDS (k_octree.hip) */
 #define TB_GRID_CELLS (120 * 36) /* Frame's key lookup grid, FRAME_GRID_COLS x FRAME_GRID_ROWS */
+#define TB_GRID_STARTS (TB_GRID_CELLS + 1) /* entries of a grid's cell_start table: cell c holds items [start[c], start[c + 1]) */
 
 /* tb_scratch slots. A slot keeps what a call put there until the next call that takes it, and an entry point that chains
  * others (stereo -> opflow -> LK -> RANSAC, the VO step) must not hand them a slot it still reads. Host forms stage in
@@ -73,6 +74,38 @@ int tb_scratch(tb_ctx* ctx, int slot, size_t bytes, void** out);
             return tb_fail((ctx), TB_EDEVICE, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), \
                            __FILE__, __LINE__);                                               \
     } while (0)
+
+/* the same for a call that reports through tb_fail itself */
+#define TB_TRY(call)            \
+    do {                        \
+        int rc_ = (call);       \
+        if (rc_) return rc_;    \
+    } while (0)
+
+/* The device buffers of one handle: every pointer tb_dev_alloc hands out is recorded here, and release() frees them all, so a
+ * handle has no free list to keep in step with its allocations and a group that failed half way is not lost track of. */
+struct tb_dev_owner {
+    std::vector<void*> ptrs;
+    void release() {
+        for (void* p : ptrs) hipFree(p);
+        ptrs.clear();
+    }
+};
+
+/* `count` elements of T into *out, owned by `own`; fill 0 or 0xff queues that byte fill on the context's stream, -1 leaves
+ * the buffer uninitialised. */
+template <class T>
+static int tb_dev_alloc(tb_ctx* ctx, tb_dev_owner& own, T** out, size_t count, int fill = -1) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, count * sizeof(T));
+    if (e == hipSuccess) {
+        own.ptrs.push_back(p);
+        *out = static_cast<T*>(p);
+        if (fill >= 0) e = hipMemsetAsync(p, fill, count * sizeof(T), ctx->stream);
+    }
+    if (e != hipSuccess) return tb_fail(ctx, TB_EDEVICE, "device buffer of %zu x %zu bytes: %s", count, sizeof(T), hipGetErrorString(e));
+    return TB_OK;
+}
 
 /* First statement of every entry point that takes a context or a plan: the HIP "current device" is per host thread and
  * the caller may hold contexts on several GPUs (or drive one context from several threads in turn), so every call binds
@@ -177,6 +210,52 @@ struct tb_extractor {
     /* fastgrid scratch */
     unsigned long long* d_gridBest = nullptr; size_t gridBestCap = 0;
     uint8_t* d_occ = nullptr; size_t occCap = 0;
+};
+
+/* The handles the VO loop (tb_vo.cpp) reads the fields of; their functions are tb_capi.cpp's. */
+struct tb_vocab {
+    tb_ctx* ctx = nullptr;
+    int nnodes = 0, k = 0, L = 0, weighting = 0, scoring = 0;
+    int32_t *d_child_start = nullptr, *d_child_items = nullptr, *d_word_id = nullptr;
+    uint8_t* d_desc = nullptr;
+    double* d_weight = nullptr;
+};
+
+/* the keyframe database: per sequence a ring of BowVectors */
+struct tb_bow_db {
+    tb_ctx* ctx = nullptr;
+    int nseq = 0, cap = 0, pitch = 0, scoring = 0;
+    long long nadded = 0;             /* adds since the last clear: the next one goes to slot nadded % cap */
+    tb_dev_owner own;
+    int32_t* words = nullptr;         /* [nseq][cap][pitch] */
+    double* values = nullptr;         /* [nseq][cap][pitch] */
+    int32_t* counts = nullptr;        /* [nseq][cap] */
+    int32_t* kf_ids = nullptr;        /* [nseq][cap], -1 = empty */
+};
+
+/* the keyframe store and the work buffers of candidate verification */
+struct tb_kf_store {
+    tb_ctx* ctx = nullptr;
+    int nseq = 0, cap = 0, pitch = 0, max_cand = 0;
+    long long nadded = 0;                 /* adds since the last clear: the next one goes to slot nadded % cap */
+    tb_dev_owner own;
+    /* the rings, frame index s * cap + slot */
+    tb_keypoint* keys = nullptr;          /* [nseq][cap][pitch] */
+    uint8_t* desc = nullptr;              /* [nseq][cap][pitch][32] */
+    uint64_t* fv = nullptr;               /* [nseq][cap][pitch] */
+    float* mp = nullptr;                  /* [nseq][cap][pitch][3] */
+    uint8_t* valid = nullptr;             /* [nseq][cap][pitch] */
+    float* Tcw = nullptr;                 /* [nseq][cap][16] */
+    int32_t *counts = nullptr, *fv_counts = nullptr, *kf_ids = nullptr;   /* [nseq][cap] */
+    /* verification work, pairs = nseq * max_cand */
+    int32_t *ix1 = nullptr, *ix2 = nullptr;                  /* [pairs] the matcher's frame indices */
+    int32_t* best = nullptr;                                 /* [pairs][pitch][4] searchByBow's best rows */
+    tb_match* matches = nullptr;                             /* [pairs][pitch] */
+    tb_obs* obs = nullptr;                                   /* [pairs][pitch] */
+    uint8_t* outlier = nullptr;                              /* [pairs][pitch] */
+    double* err = nullptr;                                   /* [pairs][pitch][3] the pose kernel's residuals */
+    float *seed = nullptr, *pose = nullptr;                  /* [pairs][16] */
+    int32_t *mcounts = nullptr, *flags = nullptr, *ocounts = nullptr, *ninl = nullptr, *ckf = nullptr;   /* [pairs] */
 };
 
 /* kernel launchers (k_*.hip) */
