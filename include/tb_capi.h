@@ -575,8 +575,8 @@ int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf,
  *             map points of entries [0, min(n, m)) and nulls [n, m); AddMapPointsByStereo(cur, right, bf, fx) (:800); every key
  *             j with depth > 0 gets a new map point R * norm * depth + t (R, t of Twc at the optimised pose; norm from
  *             u = (int)x, v = (int)y in double). Deviation: a depth that is not finite (zero disparity) creates no point.
- * Dropped: the viewer, imshow and the printing; SetBow (:705) runs only in a TB_VO_BOW loop, the one that reads its output. Local BA is not part of the loop (the
- * reference's map_ptr->AddKeyFrame is commented out, :839).
+ * Dropped: the viewer, imshow and the printing; SetBow (:705) runs only in a TB_VO_BOW loop, the one that reads its output. Local BA is not part of the loop unless
+ * enabled (tb_vo_window_ba_enable below; the reference's map_ptr->AddKeyFrame is commented out, :839).
  * State lives in the object (ping-pong key / map-point buffers, a copy of the last left image); after the first step a step
  * makes no host synchronisation and no host <-> device copy. Key capacity = the extractor's kp_capacity. The object uses its
  * context's stream and must be destroyed before its context. */
@@ -645,7 +645,9 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
  * Supported: TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, and TB_VO_BOW without a database. TB_EUNSUPPORTED from
  * tb_vo_reset_seq_dev and tb_vo_step_ragged_dev: TB_VO_PROJECTION_MAP (the map's block count and eviction are counted on the host
  * for the whole batch) and a TB_VO_BOW loop after tb_vo_bow_db_enable (database, store, recovery: the ring slot is the host's
- * count of adds for the whole batch). Making those two per-sequence is a later change. */
+ * count of adds for the whole batch). Making those two per-sequence is a later change.
+ * A TB_VO_OPFLOW loop after tb_vo_window_ba_enable is refused by both as well (TB_EUNSUPPORTED): the slot of the segment log a
+ * frame goes to is the host's count of frames since the keyframe, for the whole batch. */
 int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0);
 int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch, const uint8_t* active,
                           const uint8_t* force_keyframe);
@@ -820,6 +822,52 @@ typedef struct tb_vo_recover {
 int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm);
 int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** track_inliers, const int32_t** recovered_kf,
                             const int32_t** kf_ids, const int32_t** kf_word_ring, const int32_t** kf_node_ring);
+/* Window BA in a TB_VO_OPFLOW loop in lock-step (off unless enabled; a loop that does not enable it launches what it launched
+ * before): every keyframe segment is refined by tb_local_ba_batch_dev before the keyframe spawns its stereo points. The reference
+ * has no such step (its map_ptr->AddKeyFrame is commented out); the operators are this library's and the composition is restated
+ * on the CPU oracle in tests/vo_window_reference.py. Between two keyframes key i of every frame is the same physical point
+ * (k_vo_track keeps the index, lost points included), so the E + 1 = keyframe_every + 1 frames from one keyframe to the next are a
+ * BA window over the first keyframe's stereo points: with fixed = 1, E free keyframes (10 by default: the MFMA-tiled path's limit).
+ *   segment start  at the end of every keyframe step's keyframe block, frame 0 included: slot 0 of the log takes the keyframe's
+ *                  keys (after SetKeys) and pose, seg_pts the frame's map points (zeros where a key has none), and seg_spawned[i] = 1 where the keyframe made
+ *                  a stereo point at key i in this step (depth > 0 and finite); seg_ok[0] = seg_spawned. An entry that survived
+ *                  only through SetKeys' resize is valid but not spawned and never enters a window
+ *   log            every frame t > 0, after the tracking half, into slot j = t - (the keyframe's frame): the tracked keys, the
+ *                  optimised pose, and seg_ok[j][i] = seg_spawned[i] & valid[i] & !outlier[row(i)], row(i) = key i's rank among
+ *                  the frame's valid keys (the order of PoseOptimization's rows). Fewer than 3 rows held the pose: ok is 0
+ *   window         on a keyframe step t > 0, after the log and before the keyframe block: a point with at least min_obs ok slots
+ *                  gives one tb_ba_obs {kf = slot, pt = key index, u, v, inv_sigma2 = 1} per ok slot, grouped by ascending
+ *                  point and, within a point, by ascending slot; obs_counts and the number of such points go beside it
+ *   BA             tb_local_ba_batch_dev(nseq windows, nkf = E + 1, nfixed = fixed, npt = key_pitch, obs_pitch = (E + 1) *
+ *                  key_pitch, iters) on a COPY of seg_pose / seg_pts (ba_pose / ba_pts: the smoothed segment; the log keeps
+ *                  what the tracker measured). A window without observations is left as it is by the BA (no iteration)
+ *   adopt          where the window has at least min_points points, stats[7] != -1 and every entry of ba_pose[E] is finite:
+ *                  the frame's Tcw = ba_pose[E], adopted = 1; otherwise the pose keeps every bit and adopted = 0. The keyframe
+ *                  block then runs unchanged and spawns at that pose. The frame's carried map points are not touched
+ * The BA call synchronises the stream once (LM termination is data dependent): the one host synchronisation a keyframe step
+ * gains. Tracking steps stay free of host synchronisation and host <-> device copies. A sequence's log, window and adoption do
+ * not depend on the batch; the BA's bits are tb_local_ba_batch_dev's, which deals its Schur workgroups by the number of windows.
+ * tb_vo_window_ba_enable allocates every buffer and sizes the BA's workspace. TB_ESTATE: not an optical-flow loop, after the
+ * first step, or enabled already; TB_EINVAL: null params, iters outside 1..99, fixed outside 1..keyframe_every, min_obs < 2,
+ * min_points < 1; TB_EUNSUPPORTED: keyframe_every + 1 - fixed > 64 (the BA's limit on free keyframes; 128 frames in all).
+ * tb_vo_reset_dev clears the state. tb_vo_reset_seq_dev and tb_vo_step_ragged_dev are TB_EUNSUPPORTED on an enabled loop.
+ * tb_vo_window_state_dev: device views, each nullable (TB_ESTATE when not enabled), E + 1 = *nslots:
+ *   seg_keys [nseq][E + 1][key_pitch][2] float, seg_ok [nseq][E + 1][key_pitch] bytes, seg_pose [nseq][E + 1][16],
+ *   seg_pts [nseq][key_pitch][3], seg_spawned [nseq][key_pitch] bytes: the log of the running segment (slots 0..*slot are this
+ *   segment's, *slot = frames since its keyframe; later slots still hold the previous segment's);
+ *   obs [nseq][(E + 1) * key_pitch], obs_counts [nseq], n_points [nseq], stats [nseq][8] (tb_local_ba_batch_dev's), adopted
+ *   [nseq] bytes, ba_pose [nseq][E + 1][16] and ba_pts [nseq][key_pitch][3]: the last window and its refined segment. */
+typedef struct tb_vo_window_ba {
+    int iters;        /* LM iterations (10) */
+    int fixed;        /* leading frames of the window held fixed (1: the keyframe; 2 measured worse) */
+    int min_obs;      /* ok slots a point needs to enter the window (2) */
+    int min_points;   /* points a window needs for its pose to be adopted (3) */
+} tb_vo_window_ba;
+int tb_vo_window_ba_enable(tb_vo* vo, const tb_vo_window_ba* prm);
+int tb_vo_window_state_dev(tb_vo* vo, const float** seg_keys, const uint8_t** seg_ok, const float** seg_pose, const float** seg_pts,
+                           const uint8_t** seg_spawned, const tb_ba_obs** obs, const int32_t** obs_counts, const int32_t** n_points,
+                           const double** stats, const uint8_t** adopted, const float** ba_pose, const float** ba_pts, int* slot,
+                           int* nslots);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

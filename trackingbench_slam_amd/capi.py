@@ -52,6 +52,7 @@ EXPORTS = [
     "tb_kf_store_work_dev", "tb_relocalize_batch_dev", "tb_reloc_rows_dev", "tb_vo_reloc_enable", "tb_vo_relocalize_dev",
     "tb_vo_kf_store_get", "tb_vo_recover_enable", "tb_vo_recover_state_dev",
     "tb_vo_reset_seq_dev", "tb_vo_step_ragged_dev", "tb_vo_frames",
+    "tb_vo_window_ba_enable", "tb_vo_window_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -225,6 +226,11 @@ class VORecover(C.Structure):
     _fields_ = [("lost_inliers", C.c_int), ("topk", C.c_int), ("exclude_newest", C.c_int), ("min_inliers", C.c_int)]
 
 
+class VOWindowBA(C.Structure):
+    """tb_vo_window_ba of include/tb_capi.h"""
+    _fields_ = [("iters", C.c_int), ("fixed", C.c_int), ("min_obs", C.c_int), ("min_points", C.c_int)]
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
@@ -366,6 +372,23 @@ class VO:
         ptrs = [C.c_void_p() for _ in names]
         self.ctx.check(lib().tb_vo_recover_state_dev(self._h, *[C.byref(q) for q in ptrs]))
         return {k: q.value for k, q in zip(names, ptrs)}
+
+    def window_ba_enable(self, prm):
+        """tb_vo_window_ba_enable with a VOWindowBA (None: a null pointer): returns the status code (0 or a negative TB_E* code),
+        so the state and argument checks can be tested."""
+        return lib().tb_vo_window_ba_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def window_state_dev(self):
+        """tb_vo_window_state_dev: dict of device pointers (seg_keys, seg_ok, seg_pose, seg_pts, seg_spawned, obs, obs_counts,
+        n_points, stats, adopted, ba_pose, ba_pts) + slot, nslots; TB_ESTATE when the window BA is not enabled."""
+        names = ("seg_keys", "seg_ok", "seg_pose", "seg_pts", "seg_spawned", "obs", "obs_counts", "n_points", "stats", "adopted",
+                 "ba_pose", "ba_pts")
+        ptrs = [C.c_void_p() for _ in names]
+        slot, nslots = C.c_int(0), C.c_int(0)
+        self.ctx.check(lib().tb_vo_window_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(slot), C.byref(nslots)))
+        out = {k: q.value for k, q in zip(names, ptrs)}
+        out["slot"], out["nslots"] = slot.value, nslots.value
+        return out
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""

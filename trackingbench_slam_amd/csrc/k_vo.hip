@@ -4,6 +4,7 @@
  * float32 arithmetic, one operation per statement (the library builds with -ffp-contract=off), left to right; the CPU
  * composition in tests/vo_reference.py does the same operations in the same order. */
 #include "tb_internal.h"
+#include "tb_device.h"
 #include "tb_kfcopy.h"
 
 /* Byte copy of nimg images into a tight [nimg][h][w] layout (the loop keeps the last left image for the next LK step). With an
@@ -694,6 +695,175 @@ int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, co
     }
     tb_prof_begin(ctx, "k_vo_kf_snapshot");
     hipLaunchKernelGGL(k_vo_kf_snapshot, dim3(nkf, groups), dim3(256), 0, ctx->stream, d_idx, R);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+/* ---- window BA of the optical-flow loop (include/tb_capi.h, tb_vo_window_ba_enable): between two keyframes key i of every frame
+ * is the same physical point, so the frames of a segment are a BA window over the keyframe's stereo points. The segment log is
+ * [nseq][nslot] rows at the loop's key pitch, slot 0 = the keyframe, slot j = the frame j steps after it. Every ok / spawned row
+ * is written over the whole pitch (zeros past the key count), so the window builder walks the pitch without a count. */
+
+/* Segment start, at the end of a keyframe step's keyframe block: slot 0 takes the keyframe's keys (after SetKeys) and pose, the
+ * segment takes the frame's map points (zeros where a key has none: those entries of the frame are never written), and spawned[i] says that the keyframe made a new stereo point at key i in this step --
+ * k_vo_kf_spawn's own test on depth[i]. An entry that only survived SetKeys' resize is valid but not spawned. */
+__global__ void __launch_bounds__(256)
+k_vo_seg_start(const float* __restrict__ keys, const int32_t* __restrict__ key_counts, const float* __restrict__ depth,
+               const float* __restrict__ mp, const uint8_t* __restrict__ valid, const float* __restrict__ Tcw, int pitch, int nslot,
+               float* __restrict__ seg_keys,
+               uint8_t* __restrict__ seg_ok, float* __restrict__ seg_pose, float* __restrict__ seg_pts,
+               uint8_t* __restrict__ seg_spawned) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int m = min(max(key_counts[s], 0), pitch);
+    const size_t o = (size_t)s * pitch, o0 = (size_t)s * nslot * pitch;
+    for (int i = tid; i < pitch; i += 256) {
+        uint8_t sp = 0;
+        float X = 0.f, Y = 0.f, Z = 0.f;
+        if (i < m) {
+            const float d = depth[o + i];
+            sp = (d > 0.f && isfinite(d)) ? 1 : 0;
+            seg_keys[2 * (o0 + i)] = keys[2 * (o + i)]; seg_keys[2 * (o0 + i) + 1] = keys[2 * (o + i) + 1];
+            if (valid[o + i]) { X = mp[3 * (o + i)]; Y = mp[3 * (o + i) + 1]; Z = mp[3 * (o + i) + 2]; }
+        }
+        seg_pts[3 * (o + i)] = X; seg_pts[3 * (o + i) + 1] = Y; seg_pts[3 * (o + i) + 2] = Z;
+        seg_spawned[o + i] = sp;
+        seg_ok[o0 + i] = sp;
+    }
+    if (tid < 16) seg_pose[16 * (size_t)s * nslot + tid] = Tcw[16 * (size_t)s + tid];
+}
+
+/* Frame t > 0 after its tracking half, into slot j = t - (the keyframe's frame): the tracked key list, the optimised pose, and
+ * ok[i] = spawned[i] & valid[i] & !outlier[row(i)], where row(i) is key i's rank among the frame's valid keys -- the ballot /
+ * prefix compaction in key order by which k_vo_track emitted the rows PoseOptimization flagged. With fewer than 3 rows the pose
+ * was held and nothing is an inlier: ok is 0. valid chains from frame to frame, so a point lost once stays out. */
+__global__ void __launch_bounds__(256)
+k_vo_seg_log(const float* __restrict__ keys, const int32_t* __restrict__ key_counts, const uint8_t* __restrict__ valid,
+             const uint8_t* __restrict__ outlier, const int32_t* __restrict__ obs_counts, const float* __restrict__ Tcw,
+             const uint8_t* __restrict__ seg_spawned, int pitch, int nslot, int slot, float* __restrict__ seg_keys,
+             uint8_t* __restrict__ seg_ok, float* __restrict__ seg_pose) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(key_counts[s], 0), pitch);
+    const bool held = obs_counts[s] < 3;
+    const size_t o = (size_t)s * pitch, oj = ((size_t)s * nslot + slot) * pitch;
+    int base = 0;
+    for (int i0 = 0; i0 < pitch; i0 += 256) {
+        const int i = i0 + tid;
+        const bool v = i < n && valid[o + i];
+        const unsigned long long bm = __ballot(v);
+        if (lane == 0) wsum[wave] = __popcll(bm);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        const int row = off + __popcll(bm & ((1ull << lane) - 1));   /* row < n <= pitch */
+        if (i < n) { seg_keys[2 * (oj + i)] = keys[2 * (o + i)]; seg_keys[2 * (oj + i) + 1] = keys[2 * (o + i) + 1]; }
+        if (i < pitch) seg_ok[oj + i] = (v && !held && seg_spawned[o + i] && !outlier[o + row]) ? 1 : 0;
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid < 16) seg_pose[16 * ((size_t)s * nslot + slot) + tid] = Tcw[16 * (size_t)s + tid];
+}
+
+/* The window of a segment, one workgroup per sequence: point i contributes its ok slots when there are at least min_obs of
+ * them; an exclusive scan of those counts over the points (wave scans, the wave totals through LDS, a running base over the
+ * 256-point slabs) places them, so the observations come out grouped by ascending point and, within a point, by ascending slot:
+ * the order tb_local_ba_batch_dev requires. kf = the slot, pt = the key index, inv_sigma2 = 1 (octave 0, as the pose rows).
+ * A point has at most nslot observations, so the list fits obs_pitch = nslot * pitch. */
+__global__ void __launch_bounds__(256)
+k_vo_seg_window(const float* __restrict__ seg_keys, const uint8_t* __restrict__ seg_ok, int pitch, int nslot, int min_obs,
+                tb_ba_obs* __restrict__ obs, int32_t* __restrict__ obs_counts, int32_t* __restrict__ n_points) {
+    __shared__ int wsum[4], wpts[4];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o0 = (size_t)s * nslot * pitch;
+    tb_ba_obs* O = obs + o0;
+    int base = 0, npts = 0;
+    for (int i0 = 0; i0 < pitch; i0 += 256) {
+        const int i = i0 + tid;
+        int c = 0;
+        if (i < pitch)
+            for (int j = 0; j < nslot; j++) c += seg_ok[o0 + (size_t)j * pitch + i] ? 1 : 0;
+        if (c < min_obs) c = 0;
+        const int incl = tb_wave_incl_scan(c);
+        const unsigned long long bm = __ballot(c > 0);
+        if (lane == 63) wsum[wave] = incl;
+        if (lane == 0) wpts[wave] = __popcll(bm);
+        __syncthreads();
+        int at = base + incl - c;
+        for (int w = 0; w < wave; w++) at += wsum[w];
+        if (c > 0)
+            for (int j = 0; j < nslot; j++) {
+                const size_t e = o0 + (size_t)j * pitch + i;
+                if (!seg_ok[e]) continue;
+                tb_ba_obs r;
+                r.kf = j; r.pt = i; r.u = seg_keys[2 * e]; r.v = seg_keys[2 * e + 1]; r.inv_sigma2 = 1.0f;
+                O[at++] = r;   /* at < sum of the counts <= nslot * pitch */
+            }
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        npts += wpts[0] + wpts[1] + wpts[2] + wpts[3];
+        __syncthreads();
+    }
+    if (tid == 0) { obs_counts[s] = base; n_points[s] = npts; }
+}
+
+/* After the BA: the frame's pose, on the side the keyframe block reads, takes the refined pose of the window's last slot when
+ * the window had at least min_points points, the BA accepted its observations (stats[7] != -1) and every entry of that pose is
+ * finite. Otherwise the pose keeps every bit. One wavefront per sequence. */
+__global__ void __launch_bounds__(64)
+k_vo_seg_adopt(const float* __restrict__ win_pose, const int32_t* __restrict__ n_points, const double* __restrict__ stats, int nslot,
+               int min_points, float* __restrict__ Tcw, uint8_t* __restrict__ adopted) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const float v = lane < 16 ? win_pose[16 * ((size_t)s * nslot + nslot - 1) + lane] : 0.f;
+    const bool fin = __ballot(!isfinite(v)) == 0ull;
+    const bool ok = fin && n_points[s] >= min_points && stats[8 * (size_t)s + 7] != -1.0;
+    if (ok && lane < 16) Tcw[16 * (size_t)s + lane] = v;
+    if (lane == 0) adopted[s] = ok ? 1 : 0;
+}
+
+int tbk_vo_seg_start(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_mp,
+                     const uint8_t* d_valid, const float* d_Tcw, int pitch, int nslot, float* d_seg_keys, uint8_t* d_seg_ok, float* d_seg_pose, float* d_seg_pts,
+                     uint8_t* d_seg_spawned) {
+    if (nseq <= 0) return TB_OK;
+    if (pitch < 1 || nslot < 2) return TB_EINVAL;
+    tb_prof_begin(ctx, "k_vo_seg_start");
+    hipLaunchKernelGGL(k_vo_seg_start, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_depth, d_mp, d_valid, d_Tcw, pitch, nslot,
+                       d_seg_keys, d_seg_ok, d_seg_pose, d_seg_pts, d_seg_spawned);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_seg_log(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const uint8_t* d_valid, const uint8_t* d_outlier,
+                   const int32_t* d_obs_counts, const float* d_Tcw, const uint8_t* d_seg_spawned, int pitch, int nslot, int slot,
+                   float* d_seg_keys, uint8_t* d_seg_ok, float* d_seg_pose) {
+    if (nseq <= 0) return TB_OK;
+    if (pitch < 1 || slot < 1 || slot >= nslot) return TB_EINVAL;
+    tb_prof_begin(ctx, "k_vo_seg_log");
+    hipLaunchKernelGGL(k_vo_seg_log, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_valid, d_outlier, d_obs_counts, d_Tcw,
+                       d_seg_spawned, pitch, nslot, slot, d_seg_keys, d_seg_ok, d_seg_pose);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_seg_window(tb_ctx* ctx, int nseq, const float* d_seg_keys, const uint8_t* d_seg_ok, int pitch, int nslot, int min_obs,
+                      tb_ba_obs* d_obs, int32_t* d_obs_counts, int32_t* d_n_points) {
+    if (nseq <= 0) return TB_OK;
+    if (pitch < 1 || nslot < 2 || min_obs < 1) return TB_EINVAL;
+    tb_prof_begin(ctx, "k_vo_seg_window");
+    hipLaunchKernelGGL(k_vo_seg_window, dim3(nseq), dim3(256), 0, ctx->stream, d_seg_keys, d_seg_ok, pitch, nslot, min_obs, d_obs,
+                       d_obs_counts, d_n_points);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+int tbk_vo_seg_adopt(tb_ctx* ctx, int nseq, const float* d_win_pose, const int32_t* d_n_points, const double* d_stats, int nslot,
+                     int min_points, float* d_Tcw, uint8_t* d_adopted) {
+    if (nseq <= 0) return TB_OK;
+    tb_prof_begin(ctx, "k_vo_seg_adopt");
+    hipLaunchKernelGGL(k_vo_seg_adopt, dim3(nseq), dim3(64), 0, ctx->stream, d_win_pose, d_n_points, d_stats, nslot, min_points, d_Tcw,
+                       d_adopted);
     tb_prof_end(ctx);
     TB_HIP(ctx, hipGetLastError());
     return TB_OK;

@@ -434,5 +434,17 @@ int tbk_vo_kf_gather(tb_ctx* ctx, int nkf, const int32_t* d_idx, const float* d_
 int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, const tb_vo_frame_out* cur, const float* d_mp,
                        const uint8_t* d_valid, const tb_vo_kf_out* kf);
 
+/* window BA of the optical-flow loop (k_vo.hip): the segment log [nseq][nslot] at the loop's key pitch, the window, the adoption */
+int tbk_vo_seg_start(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_mp,
+                     const uint8_t* d_valid, const float* d_Tcw, int pitch, int nslot, float* d_seg_keys, uint8_t* d_seg_ok, float* d_seg_pose, float* d_seg_pts,
+                     uint8_t* d_seg_spawned);
+int tbk_vo_seg_log(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const uint8_t* d_valid, const uint8_t* d_outlier,
+                   const int32_t* d_obs_counts, const float* d_Tcw, const uint8_t* d_seg_spawned, int pitch, int nslot, int slot,
+                   float* d_seg_keys, uint8_t* d_seg_ok, float* d_seg_pose);
+int tbk_vo_seg_window(tb_ctx* ctx, int nseq, const float* d_seg_keys, const uint8_t* d_seg_ok, int pitch, int nslot, int min_obs,
+                      tb_ba_obs* d_obs, int32_t* d_obs_counts, int32_t* d_n_points);
+int tbk_vo_seg_adopt(tb_ctx* ctx, int nseq, const float* d_win_pose, const int32_t* d_n_points, const double* d_stats, int nslot,
+                     int min_points, float* d_Tcw, uint8_t* d_adopted);
+
 
 #endif

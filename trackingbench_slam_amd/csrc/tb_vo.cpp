@@ -94,6 +94,21 @@ struct tb_vo {
     int32_t* rg_pin = nullptr;                      /* [RG_RING][2][nseq] pinned staging; a slot is reused after its copy ran */
     hipEvent_t rg_ev[RG_RING] = {};
     unsigned rg_slot = 0;
+    /* window BA (tb_vo_window_ba_enable, TB_VO_OPFLOW): the segment log since the last keyframe -- nslot = keyframe_every + 1
+     * slots, slot 0 the keyframe -- the window built from it, and the copy of the segment the BA refines */
+    bool wb_on = false;
+    tb_vo_window_ba wb;
+    int wb_nslot = 0, wb_slot = 0;                  /* slots; the slot the last step wrote (host counter: frames since the keyframe) */
+    float* sg_keys = nullptr;                       /* [nseq][nslot][P][2] */
+    uint8_t* sg_ok = nullptr;                       /* [nseq][nslot][P] */
+    float* sg_pose = nullptr;                       /* [nseq][nslot][16] */
+    float* sg_pts = nullptr;                        /* [nseq][P][3] */
+    uint8_t* sg_spawned = nullptr;                  /* [nseq][P] */
+    tb_ba_obs* wb_obs = nullptr;                    /* [nseq][nslot * P] */
+    int32_t *wb_counts = nullptr, *wb_npts = nullptr;   /* [nseq] observations, contributing points */
+    double* wb_stats = nullptr;                     /* [nseq][8] */
+    float *wb_pose = nullptr, *wb_pts = nullptr;    /* [nseq][nslot][16], [nseq][P][3]: the last window, refined */
+    uint8_t* wb_adopted = nullptr;                  /* [nseq] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -318,6 +333,7 @@ int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_bow* bow, c
 }
 
 static int vo_recover_clear(tb_vo* vo);
+static int vo_window_clear(tb_vo* vo);
 
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     TB_ENTER((vo ? vo->ctx : nullptr));
@@ -342,6 +358,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         TB_HIP(ctx, hipMemsetAsync(vo->map_blocks[vo->map_cur], 0, (size_t)vo->nseq * vo->mapK * sizeof(int32_t), ctx->stream));
         vo->map_nblk = 0;
     }
+    if (vo->wb_on) TB_TRY(vo_window_clear(vo));
     vo->next = 0;
     vo->ragged = false;
     std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
@@ -359,6 +376,40 @@ static int vo_recover_clear(tb_vo* vo) {
     TB_HIP(ctx, hipMemsetAsync(vo->rc_kf, 0xff, S * sizeof(int32_t), ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(vo->rc_kf_ids, 0xff, S * sizeof(int32_t), ctx->stream));
     return TB_OK;
+}
+
+/* the window-BA state of a new run: an empty log, an empty window, nothing adopted */
+static int vo_window_clear(tb_vo* vo) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq, P = (size_t)vo->P, N = (size_t)vo->wb_nslot;
+    TB_HIP(ctx, hipMemsetAsync(vo->sg_keys, 0, S * N * P * 2 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->sg_ok, 0, S * N * P, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->sg_pose, 0, S * N * 16 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->sg_pts, 0, S * P * 3 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->sg_spawned, 0, S * P, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_obs, 0, S * N * P * sizeof(tb_ba_obs), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_counts, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_npts, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_stats, 0, S * 8 * sizeof(double), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_pose, 0, S * N * 16 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_pts, 0, S * P * 3 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->wb_adopted, 0, S, ctx->stream));
+    vo->wb_slot = 0;
+    return TB_OK;
+}
+
+/* The window BA of keyframe step t > 0 (include/tb_capi.h, tb_vo_window_ba), after the step's own slot was logged and before
+ * the keyframe block: build the window, refine a copy of the segment, adopt the last slot's pose into side b. The BA call
+ * synchronises the stream once -- the one host synchronisation the feature adds, on keyframe steps only. */
+static int vo_window_ba(tb_vo* vo, int b) {
+    tb_ctx* ctx = vo->ctx;
+    const int S = vo->nseq, P = vo->P, N = vo->wb_nslot;
+    TB_TRY(tbk_vo_seg_window(ctx, S, vo->sg_keys, vo->sg_ok, P, N, vo->wb.min_obs, vo->wb_obs, vo->wb_counts, vo->wb_npts));
+    TB_HIP(ctx, hipMemcpyAsync(vo->wb_pose, vo->sg_pose, (size_t)S * N * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    TB_HIP(ctx, hipMemcpyAsync(vo->wb_pts, vo->sg_pts, (size_t)S * P * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    TB_TRY(tb_local_ba_batch_dev(ctx, S, vo->p.K, N, vo->wb.fixed, vo->wb_pose, P, vo->wb_pts, vo->wb_obs, vo->wb_counts, N * P, vo->wb.iters,
+                                 vo->wb_stats));
+    return tbk_vo_seg_adopt(ctx, S, vo->wb_pose, vo->wb_npts, vo->wb_stats, N, vo->wb.min_points, vo->Tcw[b], vo->wb_adopted);
 }
 
 /* searchByBow's arguments as candidate verification takes them */
@@ -600,8 +651,23 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
     const int S = vo->nseq, b = vo->cur ^ 1;
     TB_TRY(tbk_vo_copy_image(vo->ctx, S, left, vo->p.width, vo->p.height, stride, pitch, vo->img[b]));
     TB_TRY(vo_track(vo, t));
+    if (vo->wb_on && t > 0) {   /* the frame's slot of the segment log */
+        const tb_vo_frame_out& o = vo->out[vo->oc];
+        const int slot = t - vo->kf_frame;
+        if (slot < 1 || slot >= vo->wb_nslot) return tb_fail(vo->ctx, TB_ESTATE, "window BA: frame %d is %d frames past its keyframe", t, slot);
+        TB_TRY(tbk_vo_seg_log(vo->ctx, S, vo->keys[b], vo->kcnt[b], vo->valid[b], o.outlier, o.obs_counts, vo->Tcw[b], vo->sg_spawned, vo->P,
+                              vo->wb_nslot, slot, vo->sg_keys, vo->sg_ok, vo->sg_pose));
+        vo->wb_slot = slot;
+        if (keyframe) TB_TRY(vo_window_ba(vo, b));
+    }
     if (keyframe) {
         TB_TRY(vo_keyframe(vo, t, b, S, nullptr, nullptr, right, stride, pitch));
+        if (vo->wb_on) {   /* the next segment starts here */
+            TB_TRY(tbk_vo_seg_start(vo->ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->Tcw[b], vo->P, vo->wb_nslot,
+                                    vo->sg_keys,
+                                    vo->sg_ok, vo->sg_pose, vo->sg_pts, vo->sg_spawned));
+            vo->wb_slot = 0;
+        }
         vo->kf_frame = t;
     }
     vo->cur = b;
@@ -631,6 +697,7 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
 static const char* vo_ragged_unsupported(const tb_vo* vo) {
     if (vo->tr.kind == TB_VO_PROJECTION_MAP) return "TB_VO_PROJECTION_MAP counts the map's blocks and evicts for the whole batch";
     if (vo->db) return "the keyframe database's ring slot is counted for the whole batch";
+    if (vo->wb_on) return "the window BA counts the segment's slots for the whole batch";
     return nullptr;
 }
 
@@ -935,6 +1002,71 @@ int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** tra
     if (kf_ids) *kf_ids = vo->rc_kf_ids;
     if (kf_word_ring) *kf_word_ring = vo->rc_word_ring;
     if (kf_node_ring) *kf_node_ring = vo->rc_node_ring;
+    return TB_OK;
+}
+
+int tb_vo_window_ba_enable(tb_vo* vo, const tb_vo_window_ba* prm) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    const int E = vo->p.keyframe_every;
+    if (vo->tr.kind != TB_VO_OPFLOW) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable: the loop does not track by optical flow");
+    if (vo->next > 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable after a step (frame %d)", vo->next - 1);
+    if (vo->wb_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable: the window BA is enabled already");
+    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_window_ba_enable: null parameters");
+    if (prm->iters < 1 || prm->iters > 99 || prm->fixed < 1 || prm->fixed > E || prm->min_obs < 2 || prm->min_points < 1)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_window_ba_enable: iters %d (1..99), fixed %d (1..%d), min_obs %d (>= 2), min_points %d (>= 1)",
+                       prm->iters, prm->fixed, E, prm->min_obs, prm->min_points);
+    /* the local BA's limits: 64 free keyframes, 128 in all */
+    if (E + 1 - prm->fixed > 64 || E + 1 > 128)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_window_ba_enable: a window of %d frames with %d fixed (the local BA takes 64 free, 128 in all)",
+                       E + 1, prm->fixed);
+    const size_t S = (size_t)vo->nseq, P = (size_t)vo->P, N = (size_t)E + 1;
+    if (N * P > (size_t)INT32_MAX / 64) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_window_ba_enable: %zu x %zu observations per window", N, P);
+    vo->wb_nslot = (int)N;
+    tb_dev_owner& own = vo->own;
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->sg_keys, S * N * P * 2));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->sg_ok, S * N * P));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->sg_pose, S * N * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->sg_pts, S * P * 3));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->sg_spawned, S * P));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_obs, S * N * P));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_counts, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_npts, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_stats, S * 8));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_pose, S * N * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_pts, S * P * 3));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->wb_adopted, S));
+    TB_TRY(vo_window_clear(vo));
+    /* the BA's workspace at its size now: a step never grows a scratch slot (growth synchronises) */
+    void* d;
+    TB_TRY(tb_scratch(ctx, TB_SLOT_WORK, tbk_local_ba_work_bytes(ctx, vo->nseq, (int)N, prm->fixed, vo->P, (int)(N * P)), &d));
+    vo->wb = *prm;
+    vo->wb_on = true;
+    return TB_OK;
+}
+
+int tb_vo_window_state_dev(tb_vo* vo, const float** seg_keys, const uint8_t** seg_ok, const float** seg_pose, const float** seg_pts,
+                           const uint8_t** seg_spawned, const tb_ba_obs** obs, const int32_t** obs_counts, const int32_t** n_points,
+                           const double** stats, const uint8_t** adopted, const float** ba_pose, const float** ba_pts, int* slot,
+                           int* nslots) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->wb_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_window_state_dev: the window BA is not enabled (tb_vo_window_ba_enable)");
+    if (seg_keys) *seg_keys = vo->sg_keys;
+    if (seg_ok) *seg_ok = vo->sg_ok;
+    if (seg_pose) *seg_pose = vo->sg_pose;
+    if (seg_pts) *seg_pts = vo->sg_pts;
+    if (seg_spawned) *seg_spawned = vo->sg_spawned;
+    if (obs) *obs = vo->wb_obs;
+    if (obs_counts) *obs_counts = vo->wb_counts;
+    if (n_points) *n_points = vo->wb_npts;
+    if (stats) *stats = vo->wb_stats;
+    if (adopted) *adopted = vo->wb_adopted;
+    if (ba_pose) *ba_pose = vo->wb_pose;
+    if (ba_pts) *ba_pts = vo->wb_pts;
+    if (slot) *slot = vo->wb_slot;
+    if (nslots) *nslots = vo->wb_nslot;
     return TB_OK;
 }
 

@@ -30,6 +30,11 @@ The batch need not move in lock-step: `reset(Tcw0, which=)` restarts some sequen
 advances only the active ones and gives the flagged ones a keyframe off the cadence, `frames()` tells where each one is. A sequence
 of such a ragged batch computes what it computes alone (every tracker but "projection_map", and "bow" without keyframe_db=).
 
+`window_ba=True` (or a dict, see WINDOW_BA_DEFAULTS; optical-flow tracker, lock-step only) refines every keyframe segment: the
+frames from one keyframe to the next are a local-BA window over the first keyframe's stereo points (key i is the same point in
+all of them), and the next keyframe spawns its points at the refined pose. `window()` shows the segment log, the window and the
+refined segment. The BA's termination test is the one host synchronisation a keyframe step gains; tracking steps gain none.
+
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
 """
@@ -66,6 +71,9 @@ TRACKER_DEFAULTS = {
 # 4 candidates are verified and the keyframe being tracked against is left out of them.
 RECOVER_DEFAULTS = dict(lost_inliers=30, topk=4, exclude_newest=1, min_inliers=50)
 # test_vo_1's searchByBow arguments (:207 setBowParam(30, ..., 5), :212 MapPointOnly false)
+# window_ba=True: 10 LM iterations, the keyframe held fixed (a second fixed frame is a noisy single-frame estimate and measured
+# worse), a point needs 2 inlier observations, a window needs 3 points for its pose to be adopted
+WINDOW_BA_DEFAULTS = dict(iters=10, fixed=1, min_obs=2, min_points=3)
 BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
 
@@ -101,9 +109,17 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
+        if window_ba:
+            if tracker != "opflow":
+                raise TypeError("window_ba= needs the optical-flow tracker: its key lists are the window's point tracks")
+            unknown = set(window_ba) - set(WINDOW_BA_DEFAULTS) if isinstance(window_ba, dict) else ()
+            if unknown:
+                raise TypeError("window_ba= takes no parameter %s" % ", ".join(sorted(unknown)))
+            window_ba = dict(WINDOW_BA_DEFAULTS, **(window_ba if isinstance(window_ba, dict) else {}))
+        self.window_ba = window_ba or None
         if keyframe_db and tracker != "bow":
             raise TypeError("keyframe_db= needs tracker 'bow': the database holds the keyframes' BowVectors")
         if relocalize and not keyframe_db:
@@ -140,6 +156,13 @@ class StereoVO:
         self.params, self.tracker = prm, tracker
         if tracker == "opflow":
             self.vo = capi.VO(self.ctx, prm, self.S)
+            if self.window_ba:                # None = off: no call is made
+                try:
+                    self.ctx.check(self.vo.window_ba_enable(capi.VOWindowBA(*[int(self.window_ba[k]) for k in (
+                        "iters", "fixed", "min_obs", "min_points")])))
+                except Exception:
+                    self.close()
+                    raise
         else:
             try:
                 trk = _tracker(tracker, nlevels, tracker_params)
@@ -209,6 +232,8 @@ class StereoVO:
         return m
 
     def _ragged_ok(self):
+        if getattr(self, "window_ba", None):
+            raise TypeError("ragged batches: window_ba= counts the segment's slots for the whole batch")
         if self.tracker == "projection_map" or self.db is not None:
             raise TypeError("ragged batches: tracker 'projection_map' and keyframe_db= count keyframes for the whole batch")
 
@@ -216,9 +241,10 @@ class StereoVO:
         """Tcw0: [S, 4, 4] initial poses (array or tensor); the next step is frame 0. which= (a bool sequence [S] or an index
         list) restarts only those sequences -- Tcw0 is then [S, 4, 4] or [len(which), 4, 4] in ascending sequence order -- and the
         others keep their state: the loop is in ragged mode from then on (step() drives it; reset() without which= leaves it)."""
-        T = torch.as_tensor(np.asarray(Tcw0, np.float32) if not torch.is_tensor(Tcw0) else Tcw0, dtype=torch.float32)
         if which is not None:
             self._ragged_ok()
+        T = torch.as_tensor(np.asarray(Tcw0, np.float32) if not torch.is_tensor(Tcw0) else Tcw0, dtype=torch.float32)
+        if which is not None:
             w = self._mask(which, "which")
             T = T.reshape(-1, 16).to(self.dev)
             if T.shape[0] != self.S:
@@ -243,6 +269,8 @@ class StereoVO:
 
     def step_rc(self, left, right=None, active=None, keyframe=None):
         """One frame; returns the library's status code (0 or a negative TB_E* code)."""
+        if getattr(self, "window_ba", None) and (active is not None or keyframe is not None):
+            self._ragged_ok()
         assert left.dtype == torch.uint8 and left.is_cuda and tuple(left.shape) == (self.S, self.height, self.width)
         left = left.contiguous()
         if right is not None:
@@ -477,6 +505,27 @@ class StereoVO:
         d = self.vo.recover_state_dev()
         sh = ((self.S, self.db.capacity, self.key_pitch), "<i4", torch.int32)
         return self._pget(d["kf_word_ring"], *sh), self._pget(d["kf_node_ring"], *sh)
+
+    # ---- window BA (window_ba=...)
+    def window(self):
+        """The window-BA state after the last step: dict(keys [S, E + 1, P, 2], ok [S, E + 1, P] uint8, poses [S, E + 1, 4, 4],
+        points [S, P, 3], spawned [S, P] uint8 -- the log of the running segment, slot 0 its keyframe, E = keyframe_every; slots
+        past `slots` still hold the previous segment's --, obs [S, (E + 1) P, 5] int32 (kf, pt as integers; u, v, inv_sigma2 as
+        float32 bits), obs_counts / n_points [S] int32, stats [S, 8] float64, adopted [S] uint8, refined_poses [S, E + 1, 4, 4]
+        and refined_points [S, P, 3] -- the last window and the segment as the BA left it --, slots = frames since the segment's
+        keyframe, nslots = E + 1). TB_ESTATE when off."""
+        if self.window_ba is None:
+            raise capi.TBError(capi.TB_ESTATE, "the window BA is off: StereoVO(..., window_ba=True)")
+        d = self.vo.window_state_dev()
+        S, P, N = self.S, self.key_pitch, d["nslots"]
+        f32, u8, i32 = ("<f4", torch.float32), ("|u1", torch.uint8), ("<i4", torch.int32)
+        return dict(keys=self._pget(d["seg_keys"], (S, N, P, 2), *f32), ok=self._pget(d["seg_ok"], (S, N, P), *u8),
+                    poses=self._pget(d["seg_pose"], (S, N, 4, 4), *f32), points=self._pget(d["seg_pts"], (S, P, 3), *f32),
+                    spawned=self._pget(d["seg_spawned"], (S, P), *u8), obs=self._pget(d["obs"], (S, N * P, 5), *i32),
+                    obs_counts=self._pget(d["obs_counts"], (S,), *i32), n_points=self._pget(d["n_points"], (S,), *i32),
+                    stats=self._pget(d["stats"], (S, 8), "<f8", torch.float64), adopted=self._pget(d["adopted"], (S,), *u8),
+                    refined_poses=self._pget(d["ba_pose"], (S, N, 4, 4), *f32), refined_points=self._pget(d["ba_pts"], (S, P, 3), *f32),
+                    slots=d["slot"], nslots=N)
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
