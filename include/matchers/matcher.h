@@ -1,7 +1,8 @@
 /* Header shim: the hot-path slice of TRACKING_BENCH::Matcher with the reference's signatures
- * (reference include/matchers/matcher.h:18-80,149-150) on the C ABI (tb_search_by_bf,
+ * (reference include/matchers/matcher.h:18-80,149-150) on the C ABI (tb_search_by_nn, tb_search_by_bf,
  * tb_search_by_violence, tb_search_by_bow, tb_search_by_projection, tb_search_by_projection_map, tb_search_by_opflow).
- * The NN(LSH) and direct-alignment matchers are out of scope (SURVEY.md sections 2 and 8f). */
+ * The direct-alignment matchers and the Map* overloads of searchByNN / searchByBF (which write rows of an empty cv::Mat in
+ * the reference) are out of scope (SURVEY.md sections 2 and 8f). */
 #ifndef TRACKING_BENCH_MATCHER_H
 #define TRACKING_BENCH_MATCHER_H
 #include <memory>
@@ -24,6 +25,20 @@ namespace TRACKING_BENCH
         int HISTO_LENGTH = 30;
         bool checkOrientation = true;
         float nRatio{};
+
+        // OpenCV nearest neighbour (reference :29-34, matcher.cpp:35-95): FlannBasedMatcher(LshIndexParams(20, 10, 2)) restated
+        // in include/tb_capi.h; only the whole-set branch is defined, as for searchByBF. The reference fixes the LSH parameters
+        // in its constructor (matcher.cpp:17-18) and leaves the key bits to rand(): here they are fields, and lsh_seed draws the bits.
+        int lsh_tables = 20;
+        int lsh_key_size = 10;
+        int lsh_multi_probe_level = 2;
+        unsigned long long lsh_seed = 0;
+        std::vector<cv::DMatch> searchByNN(
+                const std::shared_ptr<Frame>& F1,
+                const std::shared_ptr<Frame>& F2,
+                int MinLevel, int MaxLevel,
+                float ratio, float minTh,
+                bool MapPointOnly = false);
 
         // OpenCV BF (reference :39-44); only the whole-set branch is defined
         std::vector<cv::DMatch> searchByBF(

@@ -142,6 +142,60 @@ int tb_search_by_bf(tb_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, i
 int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, const int32_t* counts1,
                               const uint8_t* desc2, const int32_t* counts2, size_t set_pitch,
                               float ratio, float min_th, tb_match* out, int cap, int32_t* out_counts);
+
+/* Matcher::searchByNN(F1, F2, MinLevel, MaxLevel, ratio, minTh), matcher.cpp:35-95 -- the tracking line test_vo_1 runs
+ * (test/test_vo.cpp:213): cv::FlannBasedMatcher(new cv::flann::LshIndexParams(20, 10, 2)).match(d1, d2) (matcher.cpp:17-18)
+ * followed by searchByBF's distance filter (:76-85 = :209-218). No cross-check, and the neighbour is approximate: the nearest
+ * among the train descriptors that share an LSH bucket with the query. Neither OpenCV nor FLANN is part of the reference tree,
+ * so the matcher is restated here and is UNPINNED against genuine OpenCV.
+ *
+ * The rule. Inputs: d1 [n1][32] (query, F1), d2 [n2][32] (train, F2), tables T, key_size k, multi_probe_level L, and a bit
+ * table bits [T][k] of descriptor bit indices 0..255; bit b is bit b % 8 of byte b / 8 (what FLANN's size_t masks address on a
+ * little-endian host).
+ *   key_t(d)  = the k bits of d at bits[t][0..k). Their order inside the key does not matter: the probe set below is symmetric
+ *               under a permutation of the key's bits.
+ *   cand(q)   = { j < n2 : there is a t < T with popcount(key_t(d1[q]) ^ key_t(d2[j])) <= L }. This is FLANN's multi-probe walk
+ *               (every xor mask with at most L bits set, over every table) stated per pair: buckets, speed levels and the
+ *               visiting order cannot change it.
+ *   nn(q)     = the j in cand(q) with the smallest (Hamming(d1[q], d2[j]), j) (KNNUniqueResultSet orders by distance, then index).
+ * The raw list (tb_match_lsh) is, for q ascending with cand(q) not empty, (queryIdx q, trainIdx nn(q), imgIdx 0 as tb_match_bf
+ * writes it, distance = (float)Hamming). A query without a candidate gives no match (convertToDMatches keeps idx >= 0 only).
+ * tb_search_by_nn keeps the matches of the raw list with distance < fminf(ratio * min_d, minTh), min_d = the smallest distance
+ * of the raw list, in the float expressions of tb_search_by_bf. An empty raw list, n1 == 0 or n2 == 0 give count 0 (the
+ * reference would dereference min_element of an empty vector). Only the whole-set branch exists, as for searchByBF (:45-49;
+ * the other branch writes rows of an empty cv::Mat): the shim and the VO loop refuse (MinLevel, MaxLevel) != (0, nLevels) and
+ * MapPointOnly with TB_EUNSUPPORTED. The Map* overload (:103-157) writes rows of an empty Mat too and is not built.
+ *
+ * The bit table. FLANN draws it with rand(); here it is an explicit input, drawn by tb_lsh_draw_bits (a restatement of OpenCV
+ * 3's LshIndex::buildIndex / LshTable<unsigned char> from memory) from the splitmix64 stream of `seed` (synth.Stream): word i
+ * (i = 0, 1, ...) is mix(seed + (i + 1) * 0x9E3779B97F4A7C15). A pool starts empty. Before table t draws, a pool with fewer
+ * than k entries is thrown away and refilled: a[i] = i for i < 256, then for i = 255 down to 1 the next word w of the stream
+ * gives j = w % (i + 1) and a[i], a[j] are swapped (Fisher-Yates: 255 words per refill, the r-th refill reads words 255 r ..
+ * 255 r + 254). Table t takes the first k entries of the pool, in pool order, and they leave the pool. (20, 10) uses 200
+ * distinct bits of one pool; (30, 10) refills before table 25.
+ * Deviations: the reference rebuilds its index with fresh rand() bits in every match() call, here the bits are fixed per
+ * handle; and a caller may pass an explicit table (bits != NULL: seed is ignored) instead of a seed.
+ * Limits: T in 1..32, k in 1..32, L in 0..k, descriptor sets of at most 8192 rows (the key pitch limit): TB_EINVAL outside.
+ * An explicit table with a value above 255 or a value repeated inside one table is TB_EINVAL.
+ *
+ * tb_lsh_draw_bits needs no context and no GPU: out [tables][key_size]. tb_lsh_info: each output nullable, bits
+ * [tables][key_size]. tb_match_lsh / tb_search_by_nn: host pointers, staged onto the batched form (more than cap matches:
+ * TB_ECAPACITY with the full count in *count and out not written). tb_search_by_nn_batch_dev: device pointers laid out as
+ * tb_search_by_bf_batch_dev's (set_pitch / 32 rows per set at most, which must be <= 8192); both sides' keys are computed
+ * inside the call and nothing of a call survives it; no host synchronisation, no host <-> device copy. */
+typedef struct tb_lsh tb_lsh;
+int tb_lsh_draw_bits(int tables, int key_size, uint64_t seed, uint16_t* out);
+int tb_lsh_create(tb_ctx* ctx, int tables, int key_size, int multi_probe_level, uint64_t seed, const uint16_t* bits,
+                  tb_lsh** out);
+void tb_lsh_destroy(tb_lsh* lsh);
+int tb_lsh_info(const tb_lsh* lsh, int* tables, int* key_size, int* multi_probe_level, uint16_t* bits);
+int tb_match_lsh(tb_ctx* ctx, const tb_lsh* lsh, const uint8_t* d1, int n1, const uint8_t* d2, int n2, tb_match* out, int cap,
+                 int* count);
+int tb_search_by_nn(tb_ctx* ctx, const tb_lsh* lsh, const uint8_t* d1, int n1, const uint8_t* d2, int n2, float ratio,
+                    float min_th, tb_match* out, int cap, int* count);
+int tb_search_by_nn_batch_dev(tb_ctx* ctx, const tb_lsh* lsh, int npairs, const uint8_t* desc1, const int32_t* counts1,
+                              const uint8_t* desc2, const int32_t* counts2, size_t set_pitch, float ratio, float min_th,
+                              tb_match* out, int cap, int32_t* out_counts);
 /* Matcher::searchByViolence, matcher.cpp:299-395 (+ Frame grid, Frame.cpp:187-265). Host pointers: stages F2's lookup grid
  * and one pair for tb_search_by_violence_batch_dev, so histo_len <= 1024 (the reference uses 30). */
 int tb_search_by_violence(tb_ctx* ctx, const tb_keypoint* k1, const uint8_t* d1, int n1,
@@ -642,7 +696,7 @@ int tb_vo_state_dev(tb_vo* vo, const float** Tcw, const float** keys_xy, const f
  * index of its keyframe (-1: none). It works in lock-step mode too, where every entry equals tb_vo_state_dev's *frame /
  * tb_vo_tracker_state_dev's *kf_frame. In ragged mode those two report the largest per-sequence value.
  *
- * Supported: TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, and TB_VO_BOW without a database. TB_EUNSUPPORTED from
+ * Supported: TB_VO_OPFLOW, TB_VO_BF, TB_VO_NN, TB_VO_VIOLENCE, TB_VO_PROJECTION, and TB_VO_BOW without a database. TB_EUNSUPPORTED from
  * tb_vo_reset_seq_dev and tb_vo_step_ragged_dev: TB_VO_PROJECTION_MAP (the map's block count and eviction are counted on the host
  * for the whole batch) and a TB_VO_BOW loop after tb_vo_bow_db_enable (database, store, recovery: the ring slot is the host's
  * count of adds for the whole batch). Making those two per-sequence is a later change.
@@ -754,6 +808,26 @@ typedef struct tb_vo_bow {
     int th_low; float nratio; int histo_len; int check_orientation;   /* the Matcher's fields after :706: 50, 6, 30, 1 */
 } tb_vo_bow;
 int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* params, const tb_vo_bow* bow, const tb_vocab* voc, int nseq, tb_vo** out);
+/* The tracking line test_vo_1 itself runs, searchByNN (test/test_vo.cpp:213):
+ *   TB_VO_NN  searchByNN(cur_frame_ptr, key_frame, 0, 5, 10, 30) with the Matcher's LshIndexParams(20, 10, 2): ratio 10, min_th
+ *             30, (min_level, max_level) = (0, nlevels) -- only the whole-set branch exists, anything else is TB_EUNSUPPORTED --
+ *             tables 20, key_size 10, multi_probe_level 2, and the bit table of tb_lsh_create (bits, or drawn from seed when
+ *             bits is NULL; read during the call only). The table is fixed for the life of the loop.
+ * A frame is the descriptor frame above with the matcher line swapped for tb_search_by_nn_batch_dev, current frame (query)
+ * against the keyframe (train); each queryIdx occurs at most once, in ascending order. The matcher keeps no index between
+ * calls, so the ragged entry points serve the loop as they serve TB_VO_BF. tb_vo_tracker keeps its layout: the loop has its
+ * own creation entry and tb_vo_create_ex answers TB_VO_NN with TB_EINVAL. ratio / min_th not finite and LSH parameters outside
+ * tb_lsh_create's limits are TB_EINVAL; a key capacity above 8192 is TB_EUNSUPPORTED. tb_vo_state_dev and
+ * tb_vo_tracker_state_dev serve it; after the first step a step makes no host synchronisation and no host <-> device copy. */
+enum { TB_VO_NN = 6 };
+typedef struct tb_vo_lsh {
+    float ratio, min_th;            /* searchByNN ratio / minTh (:213: 10, 30) */
+    int min_level, max_level;       /* (:213: 0, 5) */
+    int tables, key_size, multi_probe_level;   /* matcher.cpp:18: 20, 10, 2 */
+    uint64_t seed;                  /* the bit table's seed when bits is NULL */
+    const uint16_t* bits;           /* nullable: an explicit [tables][key_size] table */
+} tb_vo_lsh;
+int tb_vo_create_lsh(tb_ctx* ctx, const tb_vo_params* params, const tb_vo_lsh* lsh, int nseq, tb_vo** out);
 /* Device views of SetBow's outputs after the last step (valid until the next step; every output nullable; TB_ESTATE for any other
  * tracker), for the current frame and, kf_*, for the keyframe as computed on its frame: fv_keys [nseq][key_pitch] uint64
  * (node << 32 | key) with fv_counts [nseq]; bv_words / bv_values [nseq][key_pitch] with bv_counts [nseq]; word_ids and node_ids

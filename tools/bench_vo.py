@@ -14,7 +14,8 @@ test_projection.cpp:512-517; the map tracker's step grows with its map, so its t
 keyframes the map holds (--map-keyframes, default 4; --steps 41 fills four at the default keyframe period). bow is the fourth
 line of test_vo.cpp (:711, searchByBow against the keyframe, SetBow on every frame) with a vocabulary trained by
 tb_vocab_train_dev on the ORB descriptors of the sequences' first frames (k = 10, one result set per --voc-levels entry;
---bow-set picks test_kitti's or test_vo_1's arguments). Prints one JSON line.
+--bow-set picks test_kitti's or test_vo_1's arguments). lsh is the line test_vo_1 itself runs (:213, searchByNN) with the
+reference's LshIndexParams(20, 10, 2) and the bit table of seed 0. Prints one JSON line.
 """
 import argparse
 import json
@@ -136,7 +137,7 @@ def main():
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--distinct", type=int, default=4, help="different synthetic sequences, repeated to fill a batch")
     ap.add_argument("--keyframe-every", type=int, default=10)
-    ap.add_argument("--tracker", choices=("opflow", "bf", "violence", "projection", "projection_map", "bow"), default="opflow")
+    ap.add_argument("--tracker", choices=("opflow", "bf", "violence", "projection", "projection_map", "bow", "lsh"), default="opflow")
     ap.add_argument("--voc-levels", default="5,6", help="bow: depths L of the trained vocabularies (k = 10)")
     ap.add_argument("--bow-set", choices=("test_kitti", "test_vo_1"), default="test_kitti", help="bow: searchByBow's arguments")
     ap.add_argument("--map-keyframes", type=int, default=4, help="projection_map: keyframes the map holds")

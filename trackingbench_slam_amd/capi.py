@@ -53,6 +53,8 @@ EXPORTS = [
     "tb_vo_kf_store_get", "tb_vo_recover_enable", "tb_vo_recover_state_dev",
     "tb_vo_reset_seq_dev", "tb_vo_step_ragged_dev", "tb_vo_frames",
     "tb_vo_window_ba_enable", "tb_vo_window_state_dev",
+    "tb_lsh_draw_bits", "tb_lsh_create", "tb_lsh_destroy", "tb_lsh_info", "tb_match_lsh", "tb_search_by_nn", "tb_search_by_nn_batch_dev",
+    "tb_vo_create_lsh",
 ]
 
 TB_VOC_MAX_L = 8
@@ -117,6 +119,8 @@ def lib():
         L.tb_bow_db_destroy.argtypes = [C.c_void_p]
         L.tb_kf_store_destroy.restype = None
         L.tb_kf_store_destroy.argtypes = [C.c_void_p]
+        L.tb_lsh_destroy.restype = None
+        L.tb_lsh_destroy.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -206,6 +210,7 @@ class VOParams(C.Structure):
 
 TB_VO_OPFLOW, TB_VO_BF, TB_VO_VIOLENCE, TB_VO_PROJECTION, TB_VO_PROJECTION_MAP = 0, 1, 2, 3, 4
 TB_VO_BOW = 5
+TB_VO_NN = 6
 
 
 class VOTracker(C.Structure):
@@ -221,6 +226,31 @@ class VOBow(C.Structure):
                 ("check_orientation", C.c_int)]
 
 
+class VOLsh(C.Structure):
+    """tb_vo_lsh of include/tb_capi.h"""
+    _fields_ = [("ratio", C.c_float), ("min_th", C.c_float), ("min_level", C.c_int), ("max_level", C.c_int), ("tables", C.c_int),
+                ("key_size", C.c_int), ("multi_probe_level", C.c_int), ("seed", C.c_uint64), ("bits", C.c_void_p)]
+
+
+def lsh_draw_bits(tables, key_size, seed):
+    """tb_lsh_draw_bits: the [tables, key_size] uint16 bit table of `seed` (no context, no GPU)."""
+    out = np.zeros((max(int(tables), 0), max(int(key_size), 0)), np.uint16)
+    rc = lib().tb_lsh_draw_bits(int(tables), int(key_size), C.c_uint64(int(seed) & (2 ** 64 - 1)), _p(out))
+    if rc != TB_OK:
+        raise TBError(rc, lib().tb_strerror(rc).decode())
+    return out
+
+
+def _lsh_bits(bits, tables, key_size):
+    """an explicit bit table as the contiguous uint16 [tables, key_size] array the library reads (None stays None)"""
+    if bits is None:
+        return None
+    b = np.asarray(bits)
+    if b.shape != (int(tables), int(key_size)) or b.min() < 0 or b.max() > 65535:
+        raise ValueError("bits: a [tables, key_size] table of bit indices")
+    return np.ascontiguousarray(b, np.uint16)
+
+
 class VORecover(C.Structure):
     """tb_vo_recover of include/tb_capi.h"""
     _fields_ = [("lost_inliers", C.c_int), ("topk", C.c_int), ("exclude_newest", C.c_int), ("min_inliers", C.c_int)]
@@ -234,13 +264,16 @@ class VOWindowBA(C.Structure):
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
-    bow (a VOBow) = tb_vo_create_bow with the vocabulary handle `vocab` of the same context, which the loop borrows."""
+    bow (a VOBow) = tb_vo_create_bow with the vocabulary handle `vocab` of the same context, which the loop borrows.
+    lsh (a VOLsh) = tb_vo_create_lsh."""
 
-    def __init__(self, ctx, params, nseq, tracker=None, use_ex=False, bow=None, vocab=None):
+    def __init__(self, ctx, params, nseq, tracker=None, use_ex=False, bow=None, vocab=None, lsh=None):
         self.ctx = ctx
         self.nseq = int(nseq)
         self._h = C.c_void_p()
-        if bow is not None:
+        if lsh is not None:
+            ctx.check(lib().tb_vo_create_lsh(ctx._h, C.byref(params), C.byref(lsh), self.nseq, C.byref(self._h)))
+        elif bow is not None:
             ctx.check(lib().tb_vo_create_bow(ctx._h, C.byref(params), C.byref(bow), vocab, self.nseq, C.byref(self._h)))
         elif tracker is None and not use_ex:
             ctx.check(lib().tb_vo_create(ctx._h, C.byref(params), self.nseq, C.byref(self._h)))
@@ -558,6 +591,33 @@ class Context:
                                          _p(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def lsh(self, tables=20, key_size=10, multi_probe_level=2, seed=0, bits=None):
+        """tb_lsh_create: the searchByNN matcher's handle (the reference's LshIndexParams(20, 10, 2) by default)."""
+        return Lsh(self, tables, key_size, multi_probe_level, seed, bits)
+
+    def match_lsh(self, lsh, d1, d2):
+        """tb_match_lsh: the raw list (FlannBasedMatcher.match)."""
+        d1, d2 = self._desc(d1), self._desc(d2)
+        out = np.zeros(max(len(d1), 1), MATCH)
+        n = C.c_int(0)
+        self.check(lib().tb_match_lsh(self._h, lsh._h, _p(d1), len(d1), _p(d2), len(d2), _p(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def search_by_nn(self, lsh, d1, d2, ratio, min_th, cap=None):
+        d1, d2 = self._desc(d1), self._desc(d2)
+        out = np.zeros(max(len(d1), 1) if cap is None else max(int(cap), 1), MATCH)
+        n = C.c_int(0)
+        self.check(lib().tb_search_by_nn(self._h, lsh._h, _p(d1), len(d1), _p(d2), len(d2), C.c_float(ratio), C.c_float(min_th), _p(out),
+                                         len(out) if cap is None else int(cap), C.byref(n)))
+        return out[:n.value].copy()
+
+    def search_by_nn_batch_dev(self, lsh, npairs, desc1_ptr, counts1_ptr, desc2_ptr, counts2_ptr, set_pitch, ratio, min_th, out_ptr, cap,
+                               out_counts_ptr):
+        """tb_search_by_nn_batch_dev on device pointers; returns the library's status code."""
+        return lib().tb_search_by_nn_batch_dev(self._h, lsh._h, int(npairs), C.c_void_p(desc1_ptr), C.c_void_p(counts1_ptr),
+                                               C.c_void_p(desc2_ptr), C.c_void_p(counts2_ptr), C.c_size_t(set_pitch), C.c_float(ratio),
+                                               C.c_float(min_th), C.c_void_p(out_ptr), int(cap), C.c_void_p(out_counts_ptr))
+
     def search_by_violence(self, k1, d1, k2, d2, img2_w, img2_h, min_level=0, max_level=1, radius=10.0, th_low=50,
                            nratio=0.0, histo_len=30, check_orientation=True):
         k1 = np.ascontiguousarray(k1, KEYPOINT); k2 = np.ascontiguousarray(k2, KEYPOINT)
@@ -865,6 +925,36 @@ def bow_score(scoring, a_words, a_values, b_words, b_values):
     if rc:
         raise TBError(rc, "tb_bow_score: %s" % lib().tb_strerror(rc).decode())
     return out.value
+
+
+class Lsh:
+    """tb_lsh: the parameters and the bit table of the searchByNN matcher on one context."""
+
+    def __init__(self, ctx, tables=20, key_size=10, multi_probe_level=2, seed=0, bits=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        b = _lsh_bits(bits, tables, key_size)
+        ctx.check(lib().tb_lsh_create(ctx._h, int(tables), int(key_size), int(multi_probe_level), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                      _p(b), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().tb_lsh_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(tables, key_size, multi_probe_level, bits [tables, key_size] uint16)"""
+        T, k, L = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.ctx.check(lib().tb_lsh_info(self._h, C.byref(T), C.byref(k), C.byref(L), None))
+        bits = np.zeros((T.value, k.value), np.uint16)
+        self.ctx.check(lib().tb_lsh_info(self._h, None, None, None, _p(bits)))
+        return T.value, k.value, L.value, bits
 
 
 class BowDatabase:

@@ -145,6 +145,110 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * Matcher::searchByNN (matcher.cpp:35-95): the LSH nearest neighbour of include/tb_capi.h, stated per pair -- train j is a
+ * candidate of query q iff some table's keys differ in at most L bits; the match is the candidate with the smallest
+ * (Hamming, j). At the reference's (20, 10, 2) two unrelated descriptors are candidates with probability 0.675, so a bucket walk
+ * would visit more entries than there are pairs: this is k_bf_nn's all-pairs tile loop with the predicate on top. The result is
+ * a minimum over candidates, so the predicate is evaluated only for a pair whose distance beats the lane's best so far (strictly:
+ * a block walks its train rows in ascending order, so the lower index wins a tie), which is rare after the first rows.
+ *
+ * One thread per query, LSH_T per block; the block walks the train chunks c0 = blockIdx.y * LSH_TC, step gridDim.y * LSH_TC, and
+ * the blocks of one query tile meet in an atomicMin on (distance << 32 | train). LDS (dynamic, 16-byte aligned pieces):
+ *   td  [LSH_TC][4] u64   the chunk's descriptors (read as a broadcast: every lane reads the same row)
+ *   tk  [LSH_TC][T] u32   the chunk's keys, computed by the block from td (broadcast reads)
+ *   qk  [T][LSH_T] u32    the block's query keys, table-major: lane-consecutive words, no bank conflict
+ *   sb  [T * k] u8        the bit table
+ * = 4 KB + (LSH_TC + LSH_T) * T * 4 + T * k bytes: 34.9 KB at (20, 10), 54 KB at (32, 32). */
+#define LSH_T 256
+#define LSH_TC 128
+
+__device__ __forceinline__ unsigned lsh_key(const unsigned long long w0, const unsigned long long w1, const unsigned long long w2,
+                                            const unsigned long long w3, const uint8_t* __restrict__ tb, int k) {
+    unsigned key = 0;
+    for (int b = 0; b < k; b++) {
+        const unsigned bit = tb[b];   /* bit (bit % 8) of byte (bit / 8) = bit (bit % 64) of little-endian word (bit / 64) */
+        const unsigned long long lo = (bit & 64) ? w1 : w0, hi = (bit & 64) ? w3 : w2;
+        const unsigned long long w = (bit & 128) ? hi : lo;
+        key |= (unsigned)((w >> (bit & 63)) & 1ull) << b;
+    }
+    return key;
+}
+
+__global__ void __launch_bounds__(LSH_T)
+k_lsh_nn(const uint8_t* __restrict__ query, const int32_t* __restrict__ queryCounts, const uint8_t* __restrict__ train,
+         const int32_t* __restrict__ trainCounts, size_t set_pitch, int max_n, const uint8_t* __restrict__ bits, int T, int k, int L,
+         unsigned long long* __restrict__ qbest) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lsh_smem[];
+    unsigned long long* td = lsh_smem;
+    unsigned* tk = reinterpret_cast<unsigned*>(td + LSH_TC * 4);
+    unsigned* qk = tk + LSH_TC * T;
+    uint8_t* sb = reinterpret_cast<uint8_t*>(qk + LSH_T * T);
+    const int p = blockIdx.z, tid = threadIdx.x;
+    const int nq = min(queryCounts[p], max_n), nt = min(trainCounts[p], max_n);
+    if ((int)(blockIdx.x * LSH_T) >= nq || (int)(blockIdx.y * LSH_TC) >= nt) return;   /* block-uniform */
+    for (int i = tid; i < T * k; i += LSH_T) sb[i] = bits[i];
+    const int r = blockIdx.x * LSH_T + tid;
+    const bool live = r < nq;
+    Desc256 d;
+    d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0;
+    if (live) {
+        const unsigned long long* rsrc = reinterpret_cast<const unsigned long long*>(query + (size_t)p * set_pitch) + (size_t)r * 4;
+        d.w[0] = rsrc[0]; d.w[1] = rsrc[1]; d.w[2] = rsrc[2]; d.w[3] = rsrc[3];
+    }
+    __syncthreads();
+    for (int t = 0; t < T; t++) qk[t * LSH_T + tid] = lsh_key(d.w[0], d.w[1], d.w[2], d.w[3], sb + t * k, k);
+    int best = live ? 0x7fffffff : -1, bi = 0;   /* a lane past the set never takes a row */
+    const unsigned long long* tsrc = reinterpret_cast<const unsigned long long*>(train + (size_t)p * set_pitch);
+    for (int c0 = blockIdx.y * LSH_TC; c0 < nt; c0 += gridDim.y * LSH_TC) {
+        const int cn = min(LSH_TC, nt - c0);
+        __syncthreads();   /* the last chunk's readers are done (and, the first time, qk and sb are written) */
+        for (int i = tid; i < cn * 4; i += LSH_T) td[i] = tsrc[(size_t)c0 * 4 + i];
+        __syncthreads();
+        for (int i = tid; i < cn * T; i += LSH_T) {
+            const int c = i / T, t = i - c * T;
+            tk[i] = lsh_key(td[4 * c], td[4 * c + 1], td[4 * c + 2], td[4 * c + 3], sb + t * k, k);
+        }
+        __syncthreads();
+        for (int c = 0; c < cn; c++) {
+            const int dist = bf_dist(d, td + 4 * c);
+            if (dist < best) {
+                bool cand = false;
+                for (int t = 0; t < T; t++) cand |= __popc(qk[t * LSH_T + tid] ^ tk[c * T + t]) <= L;
+                if (cand) { best = dist; bi = c0 + c; }
+            }
+        }
+    }
+    if (live && best != 0x7fffffff)
+        atomicMin(&qbest[(size_t)p * max_n + r], ((unsigned long long)best << 32) | (unsigned)bi);
+}
+
+size_t tbk_lsh_lds_bytes(int T, int k) { return (size_t)LSH_TC * 32 + (size_t)(LSH_TC + LSH_T) * T * 4 + (size_t)T * k; }
+
+/* the raw list (filter 0) or searchByNN's (filter 1) of npairs set pairs; d_qbest [npairs][max_n] */
+int tbk_lsh_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, const uint8_t* d2, const int32_t* c2, size_t set_pitch,
+                  int max_n, const uint8_t* d_bits, int T, int k, int L, int filter, float ratio, float min_th, tb_match* out, int cap,
+                  int32_t* out_counts, unsigned long long* d_qbest) {
+    if (npairs <= 0 || max_n <= 0) return TB_OK;
+    TB_HIP(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)npairs * max_n * sizeof(unsigned long long), ctx->stream));
+    /* train chunks side by side only while the query tiles alone leave compute units idle: every extra block of a query tile
+     * starts its minimum afresh and pays the predicate for its first rows again */
+    const int tiles = (max_n + LSH_T - 1) / LSH_T, chunks = (max_n + LSH_TC - 1) / LSH_TC;
+    int split = 1;
+    while (split < 4 && split * 2 <= chunks && (long long)tiles * npairs * split < 2ll * ctx->num_cu) split *= 2;
+    tb_prof_begin(ctx, "k_lsh_nn");
+    hipLaunchKernelGGL(k_lsh_nn, dim3(tiles, split, npairs), dim3(LSH_T), tbk_lsh_lds_bytes(T, k), ctx->stream, d1, c1, d2, c2, set_pitch,
+                       max_n, d_bits, T, k, L, d_qbest);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    tb_prof_begin(ctx, "k_bf_finalize");
+    hipLaunchKernelGGL(k_bf_finalize, dim3(npairs), dim3(BF_T), 0, ctx->stream, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
+                       out_counts);
+    tb_prof_end(ctx);
+    TB_HIP(ctx, hipGetLastError());
+    return TB_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------
  * SURVEY 8(f) row 1 -- Matcher::searchByProjection, both overloads (matcher.cpp:406-617): device helpers of
  * k_proj_search_batch, which projects one map point into F1 and derives its search window (matcher.cpp:431-458; the map
  * overload: Frame::IsInFrustum, Frame.cpp:370-412, and matcher.cpp:558-567). Float arithmetic: one rounding

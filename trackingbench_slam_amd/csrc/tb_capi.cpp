@@ -954,6 +954,137 @@ int tb_search_by_bf_batch_dev(tb_ctx* ctx, int npairs, const uint8_t* desc1, con
                         (unsigned long long*)tb, (unsigned long long*)qb);
 }
 
+/* ---- Matcher::searchByNN: the LSH matcher (see include/tb_capi.h) */
+#define TB_LSH_MAX_N 8192
+
+static bool lsh_params_ok(int tables, int key_size, int probe) {
+    return tables >= 1 && tables <= 32 && key_size >= 1 && key_size <= 32 && probe >= 0 && probe <= key_size;
+}
+
+int tb_lsh_draw_bits(int tables, int key_size, uint64_t seed, uint16_t* out) {
+    if (!out || tables < 1 || tables > 32 || key_size < 1 || key_size > 32) return TB_EINVAL;
+    uint16_t pool[256];
+    int have = 0, at = 0;   /* entries left in the pool, the first of them */
+    uint64_t word = 0;      /* words of the stream read so far */
+    for (int t = 0; t < tables; t++) {
+        if (have < key_size) {
+            for (int i = 0; i < 256; i++) pool[i] = (uint16_t)i;
+            for (int i = 255; i >= 1; i--) {
+                uint64_t z = seed + (++word) * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                z = z ^ (z >> 31);
+                const int j = (int)(z % (uint64_t)(i + 1));
+                std::swap(pool[i], pool[j]);
+            }
+            have = 256; at = 0;
+        }
+        for (int b = 0; b < key_size; b++) out[(size_t)t * key_size + b] = pool[at + b];
+        at += key_size; have -= key_size;
+    }
+    return TB_OK;
+}
+
+int tb_lsh_create(tb_ctx* ctx, int tables, int key_size, int multi_probe_level, uint64_t seed, const uint16_t* bits, tb_lsh** out) {
+    TB_ENTER(ctx);
+    if (out) *out = nullptr;
+    if (!ctx || !out) return TB_EINVAL;
+    if (!lsh_params_ok(tables, key_size, multi_probe_level))
+        return tb_fail(ctx, TB_EINVAL, "tb_lsh_create: tables %d (1..32), key_size %d (1..32), multi_probe_level %d (0..key_size)", tables,
+                       key_size, multi_probe_level);
+    std::unique_ptr<tb_lsh, void (*)(tb_lsh*)> h(new tb_lsh(), tb_lsh_destroy);
+    h->ctx = ctx; h->T = tables; h->k = key_size; h->L = multi_probe_level;
+    h->bits.resize((size_t)tables * key_size);
+    if (bits) {
+        for (int t = 0; t < tables; t++) {
+            bool seen[256] = {};
+            for (int b = 0; b < key_size; b++) {
+                const uint16_t v = bits[(size_t)t * key_size + b];
+                if (v > 255 || seen[v]) return tb_fail(ctx, TB_EINVAL, "tb_lsh_create: bit %d of table %d is %d (0..255, once per table)", b, t, (int)v);
+                seen[v] = true;
+            }
+        }
+        std::copy(bits, bits + h->bits.size(), h->bits.begin());
+    } else {
+        tb_lsh_draw_bits(tables, key_size, seed, h->bits.data());
+    }
+    std::vector<uint8_t> b8(h->bits.begin(), h->bits.end());
+    TB_HIP(ctx, hipMalloc((void**)&h->d_bits, b8.size()));
+    TB_HIP(ctx, hipMemcpy(h->d_bits, b8.data(), b8.size(), hipMemcpyHostToDevice));
+    *out = h.release();
+    return TB_OK;
+}
+
+void tb_lsh_destroy(tb_lsh* lsh) {
+    if (!lsh) return;
+    if (lsh->ctx) hipSetDevice(lsh->ctx->device);
+    hipFree(lsh->d_bits);
+    delete lsh;
+}
+
+int tb_lsh_info(const tb_lsh* lsh, int* tables, int* key_size, int* multi_probe_level, uint16_t* bits) {
+    if (!lsh) return TB_EINVAL;
+    if (tables) *tables = lsh->T;
+    if (key_size) *key_size = lsh->k;
+    if (multi_probe_level) *multi_probe_level = lsh->L;
+    if (bits) std::copy(lsh->bits.begin(), lsh->bits.end(), bits);
+    return TB_OK;
+}
+
+/* one pair staged for tbk_lsh_batch, as bf_host stages it for tbk_bf_batch */
+static int lsh_host(tb_ctx* ctx, const tb_lsh* lsh, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int filter, float ratio,
+                    float min_th, tb_match* out, int cap, int* count) {
+    if (!ctx || !lsh || lsh->ctx != ctx || !count || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2)) return TB_EINVAL;
+    *count = 0;
+    if (n1 > TB_LSH_MAX_N || n2 > TB_LSH_MAX_N) return tb_fail(ctx, TB_EINVAL, "searchByNN: sets of %d / %d descriptors (at most %d)", n1, n2, TB_LSH_MAX_N);
+    if (n1 == 0 || n2 == 0) return TB_OK;
+    const int max_n = std::max(n1, n2);
+    const size_t pitch = (size_t)max_n * 32;
+    size_t end = 0;
+    const size_t oD1 = stage_piece(end, pitch), oD2 = stage_piece(end, pitch), oQb = stage_piece(end, (size_t)max_n * 8),
+                 oOut = stage_piece(end, (size_t)n1 * sizeof(tb_match)), oCnt = stage_piece(end, 16);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt[4] = {n1, n2, 0, 0}; /* n1, n2, then the match count and a flag that stays 0 */
+    int32_t* dcnt = (int32_t*)(b + oCnt);
+    TB_UPLOAD(ctx, b + oD1, d1, (size_t)n1 * 32);
+    TB_UPLOAD(ctx, b + oD2, d2, (size_t)n2 * 32);
+    TB_UPLOAD(ctx, dcnt, cnt, sizeof cnt);
+    if ((rc = tbk_lsh_batch(ctx, 1, (const uint8_t*)(b + oD1), dcnt, (const uint8_t*)(b + oD2), dcnt + 1, pitch, max_n, lsh->d_bits, lsh->T,
+                            lsh->k, lsh->L, filter, ratio, min_th, (tb_match*)(b + oOut), n1, dcnt + 2, (unsigned long long*)(b + oQb))))
+        return rc;
+    return match_tail(ctx, (const tb_match*)(b + oOut), dcnt + 2, cap, out, count);
+}
+
+int tb_match_lsh(tb_ctx* ctx, const tb_lsh* lsh, const uint8_t* d1, int n1, const uint8_t* d2, int n2, tb_match* out, int cap, int* count) {
+    TB_ENTER(ctx);
+    return lsh_host(ctx, lsh, d1, n1, d2, n2, 0, 0.f, 0.f, out, cap, count);
+}
+
+int tb_search_by_nn(tb_ctx* ctx, const tb_lsh* lsh, const uint8_t* d1, int n1, const uint8_t* d2, int n2, float ratio, float min_th,
+                    tb_match* out, int cap, int* count) {
+    TB_ENTER(ctx);
+    return lsh_host(ctx, lsh, d1, n1, d2, n2, 1, ratio, min_th, out, cap, count);
+}
+
+int tb_search_by_nn_batch_dev(tb_ctx* ctx, const tb_lsh* lsh, int npairs, const uint8_t* desc1, const int32_t* counts1, const uint8_t* desc2,
+                              const int32_t* counts2, size_t set_pitch, float ratio, float min_th, tb_match* out, int cap,
+                              int32_t* out_counts) {
+    TB_ENTER(ctx);
+    if (!ctx || !lsh || lsh->ctx != ctx || npairs < 0 || !desc1 || !desc2 || !counts1 || !counts2 || !out || !out_counts || set_pitch < 32 ||
+        cap < 1)
+        return TB_EINVAL;
+    if (set_pitch / 32 > TB_LSH_MAX_N) return tb_fail(ctx, TB_EINVAL, "searchByNN: %zu descriptors per set (at most %d)", set_pitch / 32, TB_LSH_MAX_N);
+    if (npairs == 0) return TB_OK;
+    const int max_n = (int)(set_pitch / 32);
+    void* qb;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, (size_t)npairs * max_n * 8, &qb))) return rc;
+    return tbk_lsh_batch(ctx, npairs, desc1, counts1, desc2, counts2, set_pitch, max_n, lsh->d_bits, lsh->T, lsh->k, lsh->L, 1, ratio, min_th,
+                         out, cap, out_counts, (unsigned long long*)qb);
+}
+
 /* ---- DBoW2 transform (see include/tb_capi.h) */
 void tb_vocab_destroy(tb_vocab* v) {
     if (!v) return;

@@ -24,7 +24,7 @@
 enum {
     TB_SLOT_HOST = 0,           /* host forms: staged inputs and outputs */
     TB_SLOT_BF_TRAIN = 1,       /* tb_search_by_bf_batch_dev: best match per train descriptor */
-    TB_SLOT_BF_QUERY = 2,       /* tb_search_by_bf_batch_dev: best match per query descriptor */
+    TB_SLOT_BF_QUERY = 2,       /* tb_search_by_bf_batch_dev, tb_search_by_nn_batch_dev: best match per query descriptor */
     TB_SLOT_BOW_NODES = 3,      /* tb_bow_transform_batch_dev: node ids */
     TB_SLOT_STEREO_SIGMA = 3,   /*   shared: tb_stereo_tracks_to_obs_batch_dev's sigma table */
     TB_SLOT_BOW_WEIGHTS = 4,    /* tb_bow_transform_batch_dev: weights */
@@ -221,6 +221,14 @@ struct tb_vocab {
     double* d_weight = nullptr;
 };
 
+/* the LSH matcher's parameters and its bit table (searchByNN) */
+struct tb_lsh {
+    tb_ctx* ctx = nullptr;
+    int T = 0, k = 0, L = 0;
+    std::vector<uint16_t> bits;   /* [T][k] */
+    uint8_t* d_bits = nullptr;    /* [T][k] the same on the device */
+};
+
 /* the keyframe database: per sequence a ring of BowVectors */
 struct tb_bow_db {
     tb_ctx* ctx = nullptr;
@@ -270,6 +278,9 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
                  const int32_t* c2, size_t set_pitch, int max_n, int crosscheck, int filter, float ratio,
                  float min_th, tb_match* out, int cap, int32_t* out_counts, unsigned long long* d_tbest,
                  unsigned long long* d_qbest);
+int tbk_lsh_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, const uint8_t* d2, const int32_t* c2, size_t set_pitch,
+                  int max_n, const uint8_t* d_bits, int T, int k, int L, int filter, float ratio, float min_th, tb_match* out, int cap,
+                  int32_t* out_counts, unsigned long long* d_qbest);
 int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, const int32_t* d_n1, int pitch1,
                        const tb_keypoint* d_k2, const uint8_t* d_d2, const int32_t* d_n2, int pitch2, const int32_t* d_cellStart,
                        const int32_t* d_cellItems, int img2_w, int img2_h, int min_level, int max_level, float radius, int th_low,

@@ -66,6 +66,8 @@ struct tb_vo {
     const tb_vocab* voc = nullptr;
     double* bow_wt = nullptr;                       /* [nseq][P] word weights of the current frame */
     tb_bow_db* db = nullptr;                        /* the keyframe database (tb_vo_bow_db_enable), owned */
+    /* searchByNN (TB_VO_NN): the matcher's parameters and bit table, owned; ratio / minTh are tr.bf_ratio / tr.bf_min_th */
+    tb_lsh* lsh = nullptr;
     /* relocalisation (tb_vo_reloc_enable): the keyframe store, owned, and the query's outputs a caller does not take */
     tb_kf_store* store = nullptr;
     double *rl_scores = nullptr, *rl_top_score = nullptr;   /* [nseq][capacity], [nseq][max_candidates] */
@@ -120,6 +122,7 @@ void tb_vo_destroy(tb_vo* vo) {
     if (vo->ex) tb_extractor_destroy(vo->ex);
     tb_bow_db_destroy(vo->db);
     tb_kf_store_destroy(vo->store);
+    tb_lsh_destroy(vo->lsh);
     vo->own.release();
     if (vo->rg_pin) hipHostFree(vo->rg_pin);
     for (hipEvent_t e : vo->rg_ev)
@@ -158,7 +161,7 @@ static int vo_alloc_frame_out(tb_vo* vo, tb_vo_frame_out& o) {
 }
 
 static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr, int nseq, tb_vo** out, const tb_vo_bow* bow = nullptr,
-                     const tb_vocab* voc = nullptr) {
+                     const tb_vocab* voc = nullptr, const tb_vo_lsh* lsh = nullptr) {
     if (!ctx || !p || !out) return TB_EINVAL;
     *out = nullptr;
     if (nseq < 1 || p->width < 1 || p->height < 1 || p->nlevels < 2 || p->nlevels > TB_MAX_LEVELS || !(p->scale > 0.f && p->scale < 1.f) ||
@@ -184,6 +187,10 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
     vo->Mcap = vo->P;
     if (bow && vo->P > 8192)
         return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_bow: %d keys per frame (the transform sorts at most 8192)", vo->P);
+    if (lsh) {
+        if (vo->P > 8192) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_lsh: %d keys per frame (searchByNN takes sets of at most 8192)", vo->P);
+        TB_TRY(tb_lsh_create(ctx, lsh->tables, lsh->key_size, lsh->multi_probe_level, lsh->seed, lsh->bits, &vo->lsh));
+    }
     if (vo->tr.kind == TB_VO_PROJECTION_MAP) {
         if ((size_t)vo->tr.map_keyframes * (size_t)vo->P > (size_t)INT32_MAX / 64)
             return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: map_keyframes %d x %d keys is too large", vo->tr.map_keyframes, vo->P);
@@ -235,6 +242,8 @@ static int vo_create(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr
         /* the matcher's slots: searchByBF's best rows per side, searchByViolence's (WORK, shared with CLAHE) */
         if (vo->tr.kind == TB_VO_BF) {
             if ((rc = tb_scratch(ctx, TB_SLOT_BF_TRAIN, SP * 8, &d)) || (rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, SP * 8, &d))) return rc;
+        } else if (vo->tr.kind == TB_VO_NN) {
+            if ((rc = tb_scratch(ctx, TB_SLOT_BF_QUERY, SP * 8, &d))) return rc;   /* searchByNN's best row per query */
         } else if (vo_is_proj(vo)) {
             /* the projection matchers' best rows: 6 words per map point */
             if ((rc = tb_scratch(ctx, TB_SLOT_WORK, S * (size_t)vo->Mcap * 6 * sizeof(int32_t), &d))) return rc;
@@ -288,6 +297,7 @@ int tb_vo_create_ex(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_tracker* tr,
     *out = nullptr;
     if (tr && tr->kind != TB_VO_OPFLOW) {
         if (tr->kind == TB_VO_BOW) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: TB_VO_BOW needs a vocabulary, use tb_vo_create_bow");
+        if (tr->kind == TB_VO_NN) return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: TB_VO_NN needs the LSH parameters, use tb_vo_create_lsh");
         if (tr->kind != TB_VO_BF && tr->kind != TB_VO_VIOLENCE && tr->kind != TB_VO_PROJECTION && tr->kind != TB_VO_PROJECTION_MAP)
             return tb_fail(ctx, TB_EINVAL, "tb_vo_create_ex: unknown tracker kind %d", tr->kind);
         if (tr->kind == TB_VO_PROJECTION || tr->kind == TB_VO_PROJECTION_MAP) {
@@ -330,6 +340,27 @@ int tb_vo_create_bow(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_bow* bow, c
     tr.kind = TB_VO_BOW;
     tr.th_low = bow->th_low; tr.nratio = bow->nratio; tr.histo_len = bow->histo_len; tr.check_orientation = bow->check_orientation;
     return vo_create(ctx, p, &tr, nseq, out, bow, voc);
+}
+
+int tb_vo_create_lsh(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_lsh* lsh, int nseq, tb_vo** out) {
+    TB_ENTER(ctx);
+    if (out) *out = nullptr;
+    if (!ctx || !p || !out || !lsh) return TB_EINVAL;
+    if (!std::isfinite(lsh->ratio) || !std::isfinite(lsh->min_th))
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_lsh: searchByNN ratio / minTh must be finite");
+    if (lsh->tables < 1 || lsh->tables > 32 || lsh->key_size < 1 || lsh->key_size > 32 || lsh->multi_probe_level < 0 ||
+        lsh->multi_probe_level > lsh->key_size)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_create_lsh: tables %d (1..32), key_size %d (1..32), multi_probe_level %d (0..key_size)",
+                       lsh->tables, lsh->key_size, lsh->multi_probe_level);
+    /* matcher.cpp:45: only MinLevel == 0 && MaxLevel == F1->GetMaxLevel() (= nLevels) takes the whole-set branch */
+    if (lsh->min_level != 0 || lsh->max_level != p->nlevels)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_create_lsh: searchByNN levels (%d, %d): only the whole-set branch (0, %d) exists",
+                       lsh->min_level, lsh->max_level, p->nlevels);
+    tb_vo_tracker tr;
+    memset(&tr, 0, sizeof tr);
+    tr.kind = TB_VO_NN;
+    tr.bf_ratio = lsh->ratio; tr.bf_min_th = lsh->min_th; tr.min_level = lsh->min_level; tr.max_level = lsh->max_level;
+    return vo_create(ctx, p, &tr, nseq, out, nullptr, nullptr, lsh);
 }
 
 static int vo_recover_clear(tb_vo* vo);
@@ -522,6 +553,10 @@ static int vo_track(tb_vo* vo, int t) {
         /* :712 searchByBF(cur, key_frame, 0, nLevels, ratio, minTh): the whole-set branch */
         TB_TRY(tb_search_by_bf_batch_dev(ctx, S, o.orb_desc, o.orb_cnt, kf.desc, kf.cnt, (size_t)P * 32, tr.bf_ratio, tr.bf_min_th, o.matches,
                                          P, o.mcounts));
+    } else if (tr.kind == TB_VO_NN) {
+        /* test_vo_1 :213 searchByNN(cur, key_frame, 0, nLevels, ratio, minTh): the whole-set branch */
+        TB_TRY(tb_search_by_nn_batch_dev(ctx, vo->lsh, S, o.orb_desc, o.orb_cnt, kf.desc, kf.cnt, (size_t)P * 32, tr.bf_ratio, tr.bf_min_th,
+                                         o.matches, P, o.mcounts));
     } else if (tr.kind == TB_VO_VIOLENCE) {
         /* :713 searchByViolence(cur, key_frame, min_level, max_level, radius) over the keyframe's lookup grid */
         TB_TRY(tb_search_by_violence_batch_dev(ctx, S, o.orb, o.orb_desc, o.orb_cnt, P, kf.orb, kf.desc, kf.cnt, P, vo->kf_cell_start,

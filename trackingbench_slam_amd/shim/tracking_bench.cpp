@@ -395,6 +395,28 @@ namespace TRACKING_BENCH
         return out;
     }
 
+    std::vector<cv::DMatch> Matcher::searchByNN(const std::shared_ptr<Frame>& F1, const std::shared_ptr<Frame>& F2, int MinLevel,
+                                                int MaxLevel, float ratio, float minTh, bool MapPointOnly)
+    {
+        /* matcher.cpp:45-70: only the whole-set branch is well defined, as for searchByBF. The reference builds a fresh LSH
+         * index inside every match() call; here the call makes the handle that holds the parameters and the bit table */
+        if (!(MinLevel == 0 && MaxLevel == F1->GetMaxLevel() && !MapPointOnly))
+            throw std::invalid_argument("Matcher::searchByNN: level sub-range / MapPointOnly branch is undefined in the reference");
+        std::vector<uint8_t> d1, d2;
+        frame_desc(F1, d1);
+        frame_desc(F2, d2);
+        const int n1 = (int)(d1.size() / 32), n2 = (int)(d2.size() / 32);
+        std::vector<cv::DMatch> out((size_t)std::max(n1, 1));
+        int n = 0;
+        tb_lsh* h = nullptr;
+        check(tb_lsh_create(shim_ctx(), lsh_tables, lsh_key_size, lsh_multi_probe_level, lsh_seed, nullptr, &h), "Matcher::searchByNN");
+        std::unique_ptr<tb_lsh, void (*)(tb_lsh*)> own(h, tb_lsh_destroy);
+        check(tb_search_by_nn(shim_ctx(), h, d1.data(), n1, d2.data(), n2, ratio, minTh, reinterpret_cast<tb_match*>(out.data()), (int)out.size(), &n),
+              "Matcher::searchByNN");
+        out.resize(n);
+        return out;
+    }
+
     std::vector<cv::DMatch> Matcher::searchByViolence(const std::shared_ptr<Frame>& F1, const std::shared_ptr<Frame>& F2, int min_level,
                                                       int max_level, float search_r, bool MapPointOnly)
     {

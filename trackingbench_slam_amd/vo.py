@@ -9,6 +9,10 @@
 `tracker="bf"` or `"violence"` swaps the tracking line for the reference's descriptor trackers (test_vo.cpp:712-713): ORB on
 every frame, searchByBF / searchByViolence against the last keyframe, the keyframe's map points carried through the matches.
 
+`tracker="lsh"` runs the line test_vo_1 itself runs (test_vo.cpp:213), searchByNN: the LSH nearest neighbour of
+FlannBasedMatcher(LshIndexParams(20, 10, 2)) with searchByBF's filter, restated in include/tb_capi.h; `seed=` or `bits=` fix the
+descriptor bits that form the hash keys (the reference leaves them to rand()).
+
 `tracker="projection"` or `"projection_map"` runs the reference's projection loop (test/test_projection.cpp:512-517):
 searchByProjection of the keyframe's map points, or of a device-resident map the keyframes add their points to, into the
 current frame's lookup grid. The map holds the points of the last `map_keyframes` keyframes.
@@ -65,6 +69,8 @@ TRACKER_DEFAULTS = {
     "projection_map": dict(nratio=20.0, radio=0.6, th_high=50, histo_len=30, check_orientation=True, map_keyframes=4),
     # :706 setBowParam(50, 100, 30, true, 6); :711 searchByBow(cur, key_frame, true); Frame.cpp:269 levelsup 4
     "bow": dict(levelsup=4, map_point_only=True, th_low=50, nratio=6.0, histo_len=30, check_orientation=True),
+    # test_vo_1 :213 searchByNN(cur, key_frame, 0, 5, 10, 30); matcher.cpp:18 LshIndexParams(20, 10, 2); seed / bits: the bit table
+    "lsh": dict(ratio=10.0, min_th=30.0, min_level=0, max_level=None, tables=20, key_size=10, multi_probe_level=2, seed=0, bits=None),
 }
 # recover=True. ORB-SLAM-style figures, NOT the reference's (it has no relocalisation): tracking counts as lost below 30 inliers
 # (ORB-SLAM's local-map tracking asks for 30), a candidate is accepted from 50 inliers on (its relocalisation's figure), the best
@@ -79,7 +85,7 @@ BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
 def _tracker(kind, nlevels, params):
     if kind not in TRACKER_DEFAULTS:
-        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence', 'projection', 'projection_map', 'bow'" % (kind,))
+        raise ValueError("tracker %r: one of 'opflow', 'bf', 'violence', 'projection', 'projection_map', 'bow', 'lsh'" % (kind,))
     unknown = set(params) - set(TRACKER_DEFAULTS[kind])
     if unknown:
         raise TypeError("tracker %r takes no parameter %s" % (kind, ", ".join(sorted(unknown))))
@@ -87,6 +93,12 @@ def _tracker(kind, nlevels, params):
     if kind == "bow":
         return capi.VOBow(int(q["levelsup"]), int(bool(q["map_point_only"])), int(q["th_low"]), float(q["nratio"]), int(q["histo_len"]),
                           int(bool(q["check_orientation"])))
+    if kind == "lsh":
+        t = capi.VOLsh(float(q["ratio"]), float(q["min_th"]), int(q["min_level"]), int(nlevels if q["max_level"] is None else q["max_level"]),
+                       int(q["tables"]), int(q["key_size"]), int(q["multi_probe_level"]), int(q["seed"]) & (2 ** 64 - 1), None)
+        t._bits = capi._lsh_bits(q["bits"], t.tables, t.key_size)   # kept alive with the struct; read during the create call
+        t.bits = t._bits.ctypes.data if t._bits is not None else None
+        return t
     t = capi.VOTracker()
     if kind in ("projection", "projection_map"):
         t.kind = capi.TB_VO_PROJECTION if kind == "projection" else capi.TB_VO_PROJECTION_MAP
@@ -185,6 +197,8 @@ class StereoVO:
                             if recover:               # None = off: no call is made
                                 self.ctx.check(self.vo.recover_enable(capi.VORecover(*[int(recover[k]) for k in (
                                     "lost_inliers", "topk", "exclude_newest", "min_inliers")])))
+                elif tracker == "lsh":
+                    self.vo = capi.VO(self.ctx, prm, self.S, lsh=trk)
                 else:
                     self.vo = capi.VO(self.ctx, prm, self.S, trk)
             except Exception:
