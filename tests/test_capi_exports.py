@@ -68,7 +68,9 @@ def test_host_only_entry_points_match_oracle(libpath):
     for _ in range(50):
         a = rng.integers(0, 256, 32, dtype=np.uint8); b = rng.integers(0, 256, 32, dtype=np.uint8)
         assert capi.descriptor_distance(a, b) == oracle.descriptor_distance(a, b)
-    for sizes in ([0, 5, 9, 2, 7], [100, 5, 9], [100, 50, 9], [0, 0, 0], list(rng.integers(0, 50, 30))):
+    # the second row: ties (first index wins), a second / third bin at and just below a tenth of the first, lengths 1 and 1024
+    for sizes in ([0, 5, 9, 2, 7], [100, 5, 9], [100, 50, 9], [0, 0, 0], list(rng.integers(0, 50, 30)),
+                  [7, 7, 7], [0, 3, 3, 3], [10, 1, 1], [11, 1, 0], [10, 5, 0], [4], list(rng.integers(0, 50, 1024))):
         assert capi.three_maxima(sizes) == oracle.three_maxima(sizes)
 
 

@@ -278,3 +278,44 @@ def test_pose_from_stereo_tracks_finds_the_baseline(ctx):
         if n > 10:
             assert abs(T[0, 3] + KITTI_BF / fx) < 0.02 and np.abs(T[:3, :3] - np.eye(3)).max() < 5e-3
             assert n // 12 <= outl.sum() < n // 6
+
+
+def test_stereo_tracks_ordered_compaction_edges(ctx):
+    """tb_stereo_tracks_to_obs_batch_dev's ordered compaction at wave (64) and workgroup (256) boundaries: one batch whose frames
+    hold 0 .. 600 matches, every third of them without disparity (dropped); each frame == the oracle, rows in match order."""
+    import torch
+    from trackingbench_slam_amd.pipeline import KITTI_BF, KITTI_K
+    dev = torch.device("cuda", 0)
+    counts = (0, 1, 63, 64, 65, 255, 256, 257, 600)
+    F, cap = len(counts), 600
+    isig2 = oracle.scale_factors(8, 0.8)[3]
+    rng = np.random.default_rng(23)
+    KL = np.zeros((F, cap), capi.KEYPOINT); KR = np.zeros((F, cap), capi.KEYPOINT)
+    M = np.zeros((F, cap), capi.MATCH); MC = np.array(counts, np.int32)
+    for f, n in enumerate(counts):
+        KL[f, :n]["x"] = rng.uniform(100, 1100, n); KL[f, :n]["y"] = rng.uniform(40, 340, n)
+        KL[f, :n]["octave"] = rng.integers(0, 8, n)
+        perm = rng.permutation(n)                                 # match i: left key i <-> right key perm[i]
+        KR[f, perm] = KL[f, :n]
+        disp = rng.uniform(5.0, 60.0, n).astype(np.float32)
+        disp[np.arange(n) % 3 == 0] = 0.0                         # every third match: no disparity
+        KR["x"][f, perm] = KL["x"][f, :n] - disp
+        M[f, :n]["queryIdx"] = np.arange(n); M[f, :n]["trainIdx"] = perm; M[f, :n]["imgIdx"] = -1
+    t = lambda a, dt: torch.from_numpy(a.view(dt).reshape(F, cap, -1)).to(dev)
+    dKL, dKR, dM = t(KL, np.float32), t(KR, np.float32), t(M, np.int32)
+    dMC = torch.from_numpy(MC).to(dev)
+    obs = torch.full((F, cap, 6), -1.0, dtype=torch.float32, device=dev)
+    oc = torch.full((F,), -1, dtype=torch.int32, device=dev)
+    Kf = np.ascontiguousarray(KITTI_K, np.float32)
+    ctx.check(capi.lib().tb_stereo_tracks_to_obs_batch_dev(ctx._h, F, C.c_void_p(dKL.data_ptr()), C.c_void_p(dKR.data_ptr()), cap,
+                                                           C.c_void_p(dM.data_ptr()), C.c_void_p(dMC.data_ptr()), cap,
+                                                           Kf.ctypes.data_as(C.c_void_p), C.c_float(KITTI_BF),
+                                                           isig2.ctypes.data_as(C.c_void_p), 8, C.c_void_p(obs.data_ptr()), cap,
+                                                           C.c_void_p(oc.data_ptr())))
+    ctx.synchronize()
+    got_all, got_n = obs.cpu().numpy(), oc.cpu().numpy()
+    for f, n in enumerate(counts):
+        exp = oracle.stereo_tracks_to_obs(KL[f], KR[f], M[f, :n], KITTI_K, KITTI_BF, isig2)
+        assert int(got_n[f]) == len(exp) == n - (n + 2) // 3
+        assert np.array_equal(got_all[f, :len(exp)].reshape(-1).view(capi.OBS), exp)
+        assert (got_all[f, len(exp):] == -1.0).all()              # nothing written past the list

@@ -16,6 +16,15 @@
 #include "tb_internal.h"
 #include "tb_device.h"
 
+/* one profiled launch on the context's stream; the launcher returns the error of a launch that fails */
+#define TB_LAUNCH(ctx, name, kernel, grid, block, lds, ...)                       \
+    do {                                                                          \
+        tb_prof_begin(ctx, name);                                                 \
+        hipLaunchKernelGGL(kernel, grid, block, lds, (ctx)->stream, __VA_ARGS__); \
+        tb_prof_end(ctx);                                                         \
+        TB_HIP(ctx, hipGetLastError());                                           \
+    } while (0)
+
 #define BF_T 256
 #define BF_QC 512 /* queries staged per block */
 
@@ -68,13 +77,12 @@ k_bf_cross(const int32_t* __restrict__ trainCounts, int max_n, const unsigned lo
 __global__ void __launch_bounds__(BF_T)
 k_bf_finalize(const int32_t* __restrict__ queryCounts, int max_n, const unsigned long long* __restrict__ qbest, int filter,
               float ratio, float min_th, tb_match* __restrict__ out, int cap, int32_t* __restrict__ outCounts) {
-    __shared__ int flags[BF_T];
-    __shared__ int tmp[8];
-    __shared__ int s_min, running;
+    __shared__ int wsum[4];
+    __shared__ int s_min;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int nq = min(queryCounts[p], max_n);
     const unsigned long long* qb = qbest + (size_t)p * max_n;
-    if (tid == 0) { s_min = 0x7fffffff; running = 0; }
+    if (tid == 0) s_min = 0x7fffffff;
     __syncthreads();
     int mn = 0x7fffffff;
     for (int qi = tid; qi < nq; qi += BF_T) {
@@ -86,26 +94,19 @@ k_bf_finalize(const int32_t* __restrict__ queryCounts, int max_n, const unsigned
     float lim = 3.0e38f;
     if (filter) lim = fminf(TB_FMUL(ratio, (float)s_min), min_th);
     tb_match* o = out + (size_t)p * cap;
-    for (int base = 0; base < nq; base += BF_T) {
-        const int qi = base + tid;
+    int running = 0;
+    for (int q0 = 0; q0 < nq; q0 += BF_T) {
+        const int qi = q0 + tid;
         unsigned long long v = ~0ull;
         if (qi < nq) v = qb[qi];
         const float dist = (float)(int)(v >> 32);
-        const int f = (v != ~0ull && (!filter || dist < lim)) ? 1 : 0;
-        flags[tid] = f;
-        __syncthreads();
-        const int total = tb_block_excl_scan(flags, BF_T, tmp);
-        if (f) {
-            const int slot = running + flags[tid];
-            if (slot < cap) {
-                tb_match m;
-                m.queryIdx = qi; m.trainIdx = (int)(unsigned)v; m.imgIdx = 0; m.distance = dist;
-                o[slot] = m;
-            }
+        const bool f = v != ~0ull && (!filter || dist < lim);
+        const int slot = tb_block_ordered_slot(f, running, wsum);
+        if (f && slot < cap) {
+            tb_match m;
+            m.queryIdx = qi; m.trainIdx = (int)(unsigned)v; m.imgIdx = 0; m.distance = dist;
+            o[slot] = m;
         }
-        __syncthreads();
-        if (tid == 0) running += total;
-        __syncthreads();
     }
     if (tid == 0) outCounts[p] = running; /* may exceed cap: the host reports TB_ECAPACITY */
 }
@@ -120,27 +121,14 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
     if (crosscheck) {
         TB_HIP(ctx, hipMemsetAsync(d_tbest, 0xff, bytes, ctx->stream));
         /* rows = train (d2), cols = query (d1) */
-        tb_prof_begin(ctx, "k_bf_nn");
-        hipLaunchKernelGGL(k_bf_nn, grid, dim3(BF_T), 0, ctx->stream, d2, c2, d1, c1, set_pitch, max_n, d_tbest);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
-        tb_prof_begin(ctx, "k_bf_cross");
-        hipLaunchKernelGGL(k_bf_cross, dim3((max_n + BF_T - 1) / BF_T, npairs), dim3(BF_T), 0, ctx->stream, c2, max_n, d_tbest,
-                           d_qbest);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_LAUNCH(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d2, c2, d1, c1, set_pitch, max_n, d_tbest);
+        TB_LAUNCH(ctx, "k_bf_cross", k_bf_cross, dim3((max_n + BF_T - 1) / BF_T, npairs), dim3(BF_T), 0, c2, max_n, d_tbest, d_qbest);
     } else {
         /* rows = query, cols = train: qbest[q] = (dist, nearest train) directly */
-        tb_prof_begin(ctx, "k_bf_nn");
-        hipLaunchKernelGGL(k_bf_nn, grid, dim3(BF_T), 0, ctx->stream, d1, c1, d2, c2, set_pitch, max_n, d_qbest);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_LAUNCH(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d1, c1, d2, c2, set_pitch, max_n, d_qbest);
     }
-    tb_prof_begin(ctx, "k_bf_finalize");
-    hipLaunchKernelGGL(k_bf_finalize, dim3(npairs), dim3(BF_T), 0, ctx->stream, c1, max_n, d_qbest, filter, ratio, min_th, out,
-                       cap, out_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
+              out_counts);
     return TB_OK;
 }
 
@@ -235,16 +223,10 @@ int tbk_lsh_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1,
     const int tiles = (max_n + LSH_T - 1) / LSH_T, chunks = (max_n + LSH_TC - 1) / LSH_TC;
     int split = 1;
     while (split < 4 && split * 2 <= chunks && (long long)tiles * npairs * split < 2ll * ctx->num_cu) split *= 2;
-    tb_prof_begin(ctx, "k_lsh_nn");
-    hipLaunchKernelGGL(k_lsh_nn, dim3(tiles, split, npairs), dim3(LSH_T), tbk_lsh_lds_bytes(T, k), ctx->stream, d1, c1, d2, c2, set_pitch,
-                       max_n, d_bits, T, k, L, d_qbest);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    tb_prof_begin(ctx, "k_bf_finalize");
-    hipLaunchKernelGGL(k_bf_finalize, dim3(npairs), dim3(BF_T), 0, ctx->stream, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
-                       out_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_lsh_nn", k_lsh_nn, dim3(tiles, split, npairs), dim3(LSH_T), tbk_lsh_lds_bytes(T, k), d1, c1, d2, c2, set_pitch,
+              max_n, d_bits, T, k, L, d_qbest);
+    TB_LAUNCH(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
+              out_counts);
     return TB_OK;
 }
 
@@ -331,6 +313,95 @@ k_grid_build(const tb_keypoint* __restrict__ keys, const int32_t* __restrict__ c
     }
 }
 
+/* Frame::GetFeaturesInArea (Frame.cpp:202-255) as the matchers use it: every key of the lookup grid (cellStart / cellItems of
+ * ONE frame, keys = that frame's) inside the box |kp - (x, y)| < r whose octave passes the level test, in the reference's
+ * order (ix, iy, insertion); visit(j, kp) sees each one. */
+template <class Visit>
+__device__ __forceinline__ void grid_window_walk(const int32_t* __restrict__ cellStart, const int32_t* __restrict__ cellItems,
+                                                 const tb_keypoint* __restrict__ keys, float x, float y, float r, float widthInv,
+                                                 float heightInv, int minL, int maxL, Visit visit) {
+    const int GRID_ROWS = 36, GRID_COLS = 120;
+    const int nMinCellX = max(0, (int)floorf((x - r) * widthInv));
+    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf((x + r) * widthInv));
+    const int nMinCellY = max(0, (int)floorf((y - r) * heightInv));
+    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf((y + r) * heightInv));
+    if (!(nMinCellX < GRID_COLS && nMaxCellX >= 0 && nMinCellY < GRID_ROWS && nMaxCellY >= 0)) return;
+    const bool bCheckLevels = (minL > 0) || (maxL >= 0);
+    for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
+        for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
+            const int c = ix * GRID_ROWS + iy;
+            for (int s = cellStart[c]; s < cellStart[c + 1]; s++) {
+                const int j = cellItems[s];
+                const tb_keypoint kp = keys[j];
+                if (bCheckLevels) {
+                    if (kp.octave < minL) continue;
+                    if (maxL >= 0 && kp.octave > maxL) continue;
+                }
+                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;
+                visit(j, kp);
+            }
+        }
+}
+
+/* The end of searchByProjection, searchByViolence and searchByBow (matcher.cpp:483-530, :352-395, :671-717): acceptance,
+ * rotation histogram, ComputeThreeMaxima and the ordered match list of one pair, by one workgroup of 256. The reference's
+ * output order -- kept bins ascending, inside a bin the order of acceptance -- is a stable partition: one ordered compaction
+ * pass per kept bin (at most three). A matcher is a policy:
+ *   int n                  candidates, in the reference's emission order
+ *   bool accept(int i)     the matcher's thresholds on candidate i < n
+ *   float rotation(int i)  the rotation of an accepted candidate, operands subtracted; asked for only when the orientation is
+ *                          checked (searchByProjection's map overload never does, and has no F2 keys to read an angle from)
+ *   tb_match make(int i)   the match of an accepted candidate
+ * A bin outside the histogram (the reference asserts) sets *flag = 2 and drops the candidate. *out_count may exceed cap: the
+ * list is truncated, the count is not. */
+template <class Policy>
+__device__ __forceinline__ void match_accept_stage(const Policy& P, int histo_len, int check_orientation, tb_match* __restrict__ out,
+                                                   int cap, int32_t* out_count, int32_t* flag) {
+    __shared__ int hist[1024];
+    __shared__ int wsum[4];
+    __shared__ int keep[3];
+    const int tid = threadIdx.x;
+    const float factor = 1.0f / (float)histo_len;
+    auto accepted = [&](int i, int& bin) -> bool {
+        if (i >= P.n || !P.accept(i)) return false;
+        bin = 0;
+        if (check_orientation) {
+            float rot = P.rotation(i);
+            if (rot < 0.0f) rot += 360.0f;
+            bin = (int)roundf(rot * factor);
+            if (bin == histo_len) bin = 0;
+            if (bin < 0 || bin >= histo_len) { *flag = 2; return false; }
+        }
+        return true;
+    };
+    if (tid == 0) { keep[0] = check_orientation ? -1 : 0; keep[1] = keep[2] = -1; }
+    for (int b = tid; b < histo_len; b += 256) hist[b] = 0;
+    __syncthreads();
+    if (check_orientation) {
+        for (int i = tid; i < P.n; i += 256) { int bin; if (accepted(i, bin)) atomicAdd(&hist[bin], 1); }
+        __syncthreads();
+        if (tid == 0) {
+            int i1 = -1, i2 = -1, i3 = -1;
+            tbm::three_maxima(hist, histo_len, &i1, &i2, &i3);
+            tbm::kept_bins_ascending(i1, i2, i3, keep);
+        }
+        __syncthreads();
+    }
+    int run = 0;
+    for (int kb = 0; kb < 3; kb++) {
+        const int want = keep[kb];
+        if (want < 0) continue;
+        for (int e0 = 0; e0 < P.n; e0 += 256) {
+            const int i = e0 + tid;
+            int bin = 0;
+            const bool f = accepted(i, bin) && (!check_orientation || bin == want);
+            const int slot = tb_block_ordered_slot(f, run, wsum);
+            if (f && slot < cap) out[slot] = P.make(i);
+        }
+    }
+    if (tid == 0) *out_count = run;
+}
+
 struct ProjBatch {
     const float* Tcw;                /* [npairs][16] */
     tb_camera cam;
@@ -398,138 +469,60 @@ k_proj_search_batch(ProjBatch B) {
         }
     }
     if (search) {
-        const int GRID_ROWS = 36, GRID_COLS = 120;
-        const int nMinCellX = max(0, (int)floorf((x - r) * B.widthInv));
-        const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf((x + r) * B.widthInv));
-        const int nMinCellY = max(0, (int)floorf((y - r) * B.heightInv));
-        const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf((y + r) * B.heightInv));
-        if (nMinCellX < GRID_COLS && nMaxCellX >= 0 && nMinCellY < GRID_ROWS && nMaxCellY >= 0) {
-            const bool bCheckLevels = (minL > 0) || (maxL >= 0);
-            const int32_t* cs = B.cellStart + (size_t)p * (GRID_CELLS + 1);
-            const int32_t* ci = B.cellItems + (size_t)p * B.pitch1;
-            const tb_keypoint* k1 = B.k1 + (size_t)p * B.pitch1;
-            const uint8_t* d1 = B.d1 + (size_t)p * B.pitch1 * 32;
-            const uint8_t* tk = B.taken1 + (size_t)p * B.pitch1;
-            const unsigned long long* a = reinterpret_cast<const unsigned long long*>(B.mp2d) + ((size_t)p * B.pitch2 + i2) * 4;
-            Desc256 da;
-            da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
-            for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
-                for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
-                    const int c = ix * GRID_ROWS + iy;
-                    for (int s = cs[c]; s < cs[c + 1]; s++) {
-                        const int j = ci[s];
-                        const tb_keypoint kp = k1[j];
-                        if (bCheckLevels) {
-                            if (kp.octave < minL) continue;
-                            if (maxL >= 0 && kp.octave > maxL) continue;
-                        }
-                        if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;
-                        ncand++;
-                        if (tk[j]) continue;
-                        const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d1) + (size_t)j * 4);
-                        if (dist < bestDist) {
-                            bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp.octave; bestIdx = j;
-                        } else if (dist < bestDist2) {
-                            bestLevel2 = kp.octave; bestDist2 = dist;
-                        }
-                    }
-                }
-        }
+        const uint8_t* d1 = B.d1 + (size_t)p * B.pitch1 * 32;
+        const uint8_t* tk = B.taken1 + (size_t)p * B.pitch1;
+        const unsigned long long* a = reinterpret_cast<const unsigned long long*>(B.mp2d) + ((size_t)p * B.pitch2 + i2) * 4;
+        Desc256 da;
+        da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
+        grid_window_walk(B.cellStart + (size_t)p * (GRID_CELLS + 1), B.cellItems + (size_t)p * B.pitch1, B.k1 + (size_t)p * B.pitch1,
+                         x, y, r, B.widthInv, B.heightInv, minL, maxL, [&](int j, const tb_keypoint& kp) {
+            ncand++;
+            if (tk[j]) return;
+            const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d1) + (size_t)j * 4);
+            if (dist < bestDist) {
+                bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp.octave; bestIdx = j;
+            } else if (dist < bestDist2) {
+                bestLevel2 = kp.octave; bestDist2 = dist;
+            }
+        });
     }
     int32_t* o = B.best + ((size_t)p * B.max_n2 + i2) * 6;
     o[0] = bestDist; o[1] = bestDist2; o[2] = bestIdx; o[3] = bestLevel; o[4] = bestLevel2; o[5] = ncand;
 }
 
-/* acceptance, rotation histogram, ComputeThreeMaxima and the ordered match list (matcher.cpp:483-530): one
- * workgroup per pair. The reference's output order -- kept bins ascending, inside a bin the order of acceptance --
- * is a stable partition: one ordered compaction pass per kept bin (at most three). */
+/* searchByProjection's acceptance (matcher.cpp:483-530; the map overload: :596-617), one workgroup per pair */
+struct ProjAccept {
+    int n, th_high, map_mode;
+    float radio;
+    const int32_t* best;
+    const tb_keypoint *k1, *k2;
+    __device__ bool accept(int i2) const {
+        const int bd = best[6 * (size_t)i2], bi = best[6 * (size_t)i2 + 2];
+        if (best[6 * (size_t)i2 + 5] == 0 || bi < 0 || bd > th_high) return false;
+        return !(map_mode && best[6 * (size_t)i2 + 3] == best[6 * (size_t)i2 + 4] &&
+                 (float)bd > radio * (float)best[6 * (size_t)i2 + 1]); /* matcher.cpp:608-609 */
+    }
+    __device__ float rotation(int i2) const { return k2[i2].angle - k1[best[6 * (size_t)i2 + 2]].angle; }
+    __device__ tb_match make(int i2) const {
+        tb_match m;
+        m.queryIdx = best[6 * (size_t)i2 + 2]; m.trainIdx = i2; m.imgIdx = -1; m.distance = (float)best[6 * (size_t)i2];
+        return m;
+    }
+};
 __global__ void __launch_bounds__(256)
 k_proj_accept_batch(ProjBatch B) {
-    __shared__ int hist[1024];
-    __shared__ int sflag[256];
-    __shared__ int tmp[8];
-    __shared__ int keep[3];
-    __shared__ int srun;
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int n2 = min(B.n2[p], B.max_n2);
-    const int32_t* best = B.best + (size_t)p * B.max_n2 * 6;
-    const tb_keypoint* k1 = B.k1 + (size_t)p * B.pitch1;
-    const tb_keypoint* k2 = B.k2 + (size_t)p * B.pitch2;
-    tb_match* out = B.out + (size_t)p * B.cap;
-    const float factor = 1.0f / (float)B.histo_len;
-    auto accepted = [&](int i2, int& bin) -> bool {
-        if (i2 >= n2) return false;
-        const int bd = best[6 * (size_t)i2], bi = best[6 * (size_t)i2 + 2];
-        if (best[6 * (size_t)i2 + 5] == 0 || bi < 0 || bd > B.th_high) return false;
-        if (B.map_mode && best[6 * (size_t)i2 + 3] == best[6 * (size_t)i2 + 4] &&
-            (float)bd > B.radio * (float)best[6 * (size_t)i2 + 1]) return false; /* matcher.cpp:608-609 */
-        bin = 0;
-        if (B.check_orientation) {
-            float rot = k2[i2].angle - k1[bi].angle;
-            if (rot < 0.0f) rot += 360.0f;
-            bin = (int)roundf(rot * factor);
-            if (bin == B.histo_len) bin = 0;
-            if (bin < 0 || bin >= B.histo_len) { B.flags[p] = 2; return false; } /* the reference asserts */
-        }
-        return true;
-    };
-    if (tid == 0) { keep[0] = B.check_orientation ? -1 : 0; keep[1] = keep[2] = -1; srun = 0; }
-    for (int b = tid; b < B.histo_len; b += 256) hist[b] = 0;
-    __syncthreads();
-    if (B.check_orientation) {
-        for (int i2 = tid; i2 < n2; i2 += 256) { int bin; if (accepted(i2, bin)) atomicAdd(&hist[bin], 1); }
-        __syncthreads();
-        if (tid == 0) { /* Matcher::ComputeThreeMaxima, matcher.cpp:810-851 */
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < B.histo_len; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            /* kept bins in ascending order */
-            int a = i1, b = i2, c = i3, t;
-            if (a < 0) a = 1 << 30; if (b < 0) b = 1 << 30; if (c < 0) c = 1 << 30;
-            if (a > b) { t = a; a = b; b = t; } if (b > c) { t = b; b = c; c = t; } if (a > b) { t = a; a = b; b = t; }
-            keep[0] = a < (1 << 30) ? a : -1; keep[1] = b < (1 << 30) ? b : -1; keep[2] = c < (1 << 30) ? c : -1;
-        }
-        __syncthreads();
-    }
-    for (int kb = 0; kb < 3; kb++) {
-        const int want = keep[kb];
-        if (want < 0) continue;
-        for (int e0 = 0; e0 < n2; e0 += 256) {
-            const int i2 = e0 + tid;
-            int bin = 0;
-            const int f = (accepted(i2, bin) && (!B.check_orientation || bin == want)) ? 1 : 0;
-            sflag[tid] = f;
-            __syncthreads();
-            const int total = tb_block_excl_scan(sflag, 256, tmp);
-            const int slot = srun + sflag[tid];
-            if (f && slot < B.cap) {
-                tb_match m;
-                m.queryIdx = best[6 * (size_t)i2 + 2]; m.trainIdx = i2; m.imgIdx = -1; m.distance = (float)best[6 * (size_t)i2];
-                out[slot] = m;
-            }
-            __syncthreads();
-            if (tid == 0) srun += total;
-            __syncthreads();
-        }
-    }
-    if (tid == 0) B.out_counts[p] = srun; /* may exceed cap: the list is truncated, the count is not */
+    const int p = blockIdx.x;
+    const ProjAccept P = {min(B.n2[p], B.max_n2), B.th_high, B.map_mode, B.radio, B.best + (size_t)p * B.max_n2 * 6,
+                          B.k1 + (size_t)p * B.pitch1, B.k2 + (size_t)p * B.pitch2};
+    match_accept_stage(P, B.histo_len, B.check_orientation, B.out + (size_t)p * B.cap, B.cap, B.out_counts + p, B.flags + p);
 }
 
 int tbk_grid_build_batch(tb_ctx* ctx, int nframes, const tb_keypoint* d_keys, const int32_t* d_counts, int key_pitch, int img_w,
                          int img_h, int32_t* d_cellStart, int32_t* d_cellItems) {
     if (nframes <= 0) return TB_OK;
     const float heightInv = 120.f / (float)img_w, widthInv = 36.f / (float)img_h; /* swapped in the reference; kept */
-    tb_prof_begin(ctx, "k_grid_build");
-    hipLaunchKernelGGL(k_grid_build, dim3(nframes), dim3(256), 0, ctx->stream, d_keys, d_counts, key_pitch, widthInv, heightInv,
-                       d_cellStart, d_cellItems);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_grid_build", k_grid_build, dim3(nframes), dim3(256), 0, d_keys, d_counts, key_pitch, widthInv, heightInv,
+              d_cellStart, d_cellItems);
     return TB_OK;
 }
 
@@ -552,14 +545,8 @@ int tbk_projection_batch(tb_ctx* ctx, int npairs, const float* d_Tcw, const tb_c
     B.th_high = th_high; B.histo_len = histo_len; B.check_orientation = check_orientation;
     B.best = d_best; B.out = d_out; B.cap = cap; B.out_counts = d_out_counts; B.flags = d_flags;
     TB_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)npairs * sizeof(int32_t), ctx->stream));
-    tb_prof_begin(ctx, "k_proj_search");
-    hipLaunchKernelGGL(k_proj_search_batch, dim3((max_n2 + 255) / 256, npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    tb_prof_begin(ctx, "k_proj_accept");
-    hipLaunchKernelGGL(k_proj_accept_batch, dim3(npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_proj_search", k_proj_search_batch, dim3((max_n2 + 255) / 256, npairs), dim3(256), 0, B);
+    TB_LAUNCH(ctx, "k_proj_accept", k_proj_accept_batch, dim3(npairs), dim3(256), 0, B);
     return TB_OK;
 }
 
@@ -579,123 +566,49 @@ struct VioBatch {
 
 __global__ void __launch_bounds__(256)
 k_window_batch(VioBatch B) {
-    const int GRID_ROWS = 36, GRID_COLS = 120;
     const int p = blockIdx.y, i1 = blockIdx.x * blockDim.x + threadIdx.x;
     const int n1 = min(B.n1[p], B.pitch1);
     if (i1 >= n1) return;
     const tb_keypoint* k1 = B.k1 + (size_t)p * B.pitch1;
-    const tb_keypoint* k2 = B.k2 + (size_t)p * B.pitch2;
     const uint8_t* d2 = B.d2 + (size_t)p * B.pitch2 * 32;
-    const int32_t* cs = B.cellStart + (size_t)p * (GRID_CELLS + 1);
-    const int32_t* ci = B.cellItems + (size_t)p * B.pitch2;
     int bestDist = 0x7fffffff, bestDist2 = 0x7fffffff, bestIdx = -1, ncand = 0;
-    const float x = k1[i1].x, y = k1[i1].y, r = B.r;
-    const int nMinCellX = max(0, (int)floorf((x - r) * B.widthInv));
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf((x + r) * B.widthInv));
-    const int nMinCellY = max(0, (int)floorf((y - r) * B.heightInv));
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf((y + r) * B.heightInv));
-    if (nMinCellX < GRID_COLS && nMaxCellX >= 0 && nMinCellY < GRID_ROWS && nMaxCellY >= 0) {
-        const bool bCheckLevels = (B.min_level > 0) || (B.max_level >= 0);
-        const unsigned long long* a = reinterpret_cast<const unsigned long long*>(B.d1) + ((size_t)p * B.pitch1 + i1) * 4;
-        Desc256 da;
-        da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
-            for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
-                const int c = ix * GRID_ROWS + iy;
-                for (int s = cs[c]; s < cs[c + 1]; s++) {
-                    const int j = ci[s];
-                    const tb_keypoint kp = k2[j];
-                    if (bCheckLevels) {
-                        if (kp.octave < B.min_level) continue;
-                        if (B.max_level >= 0 && kp.octave > B.max_level) continue;
-                    }
-                    if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;
-                    ncand++;
-                    const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d2) + (size_t)j * 4);
-                    if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx = j; }
-                    else if (dist < bestDist2) bestDist2 = dist;
-                }
-            }
-    }
+    const unsigned long long* a = reinterpret_cast<const unsigned long long*>(B.d1) + ((size_t)p * B.pitch1 + i1) * 4;
+    Desc256 da;
+    da.w[0] = a[0]; da.w[1] = a[1]; da.w[2] = a[2]; da.w[3] = a[3];
+    grid_window_walk(B.cellStart + (size_t)p * (GRID_CELLS + 1), B.cellItems + (size_t)p * B.pitch2, B.k2 + (size_t)p * B.pitch2,
+                     k1[i1].x, k1[i1].y, B.r, B.widthInv, B.heightInv, B.min_level, B.max_level, [&](int j, const tb_keypoint&) {
+        ncand++;
+        const int dist = bf_dist(da, reinterpret_cast<const unsigned long long*>(d2) + (size_t)j * 4);
+        if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx = j; }
+        else if (dist < bestDist2) bestDist2 = dist;
+    });
     int32_t* o = B.best + ((size_t)p * B.pitch1 + i1) * 4;
     o[0] = bestDist; o[1] = bestDist2; o[2] = bestIdx; o[3] = ncand;
 }
 
+/* searchByViolence's acceptance (matcher.cpp:352-377), one workgroup per pair */
+struct VioAccept {
+    int n, th_low;
+    float nratio;
+    const int32_t* best;
+    const tb_keypoint *k1, *k2;
+    __device__ bool accept(int i1) const {
+        const int bd = best[4 * (size_t)i1], bd2 = best[4 * (size_t)i1 + 1];
+        return best[4 * (size_t)i1 + 3] != 0 && bd <= th_low && (float)bd < (float)bd2 * nratio;
+    }
+    __device__ float rotation(int i1) const { return k1[i1].angle - k2[best[4 * (size_t)i1 + 2]].angle; }
+    __device__ tb_match make(int i1) const {
+        tb_match m;
+        m.queryIdx = i1; m.trainIdx = best[4 * (size_t)i1 + 2]; m.imgIdx = -1; m.distance = (float)best[4 * (size_t)i1];
+        return m;
+    }
+};
 __global__ void __launch_bounds__(256)
 k_violence_accept_batch(VioBatch B) {
-    __shared__ int hist[1024];
-    __shared__ int sflag[256];
-    __shared__ int tmp[8];
-    __shared__ int keep[3];
-    __shared__ int srun;
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int n1 = min(B.n1[p], B.pitch1);
-    const int32_t* best = B.best + (size_t)p * B.pitch1 * 4;
-    const tb_keypoint* k1 = B.k1 + (size_t)p * B.pitch1;
-    const tb_keypoint* k2 = B.k2 + (size_t)p * B.pitch2;
-    tb_match* out = B.out + (size_t)p * B.cap;
-    const float factor = 1.f / (float)B.histo_len;
-    auto accepted = [&](int i1, int& bin) -> bool { /* matcher.cpp:352-377 */
-        if (i1 >= n1) return false;
-        const int bd = best[4 * (size_t)i1], bd2 = best[4 * (size_t)i1 + 1], bi = best[4 * (size_t)i1 + 2];
-        if (best[4 * (size_t)i1 + 3] == 0) return false;
-        if (!(bd <= B.th_low && (float)bd < (float)bd2 * B.nratio)) return false;
-        bin = 0;
-        if (B.check_orientation) {
-            float rot = k1[i1].angle - k2[bi].angle;
-            if (rot < 0) rot += 360.f;
-            bin = (int)roundf(rot * factor);
-            if (bin == B.histo_len) bin = 0;
-            if (bin < 0 || bin >= B.histo_len) { B.flags[p] = 2; return false; } /* the reference asserts */
-        }
-        return true;
-    };
-    if (tid == 0) { keep[0] = B.check_orientation ? -1 : 0; keep[1] = keep[2] = -1; srun = 0; }
-    for (int b = tid; b < B.histo_len; b += 256) hist[b] = 0;
-    __syncthreads();
-    if (B.check_orientation) {
-        for (int i1 = tid; i1 < n1; i1 += 256) { int bin; if (accepted(i1, bin)) atomicAdd(&hist[bin], 1); }
-        __syncthreads();
-        if (tid == 0) { /* Matcher::ComputeThreeMaxima, matcher.cpp:810-851 */
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < B.histo_len; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            int a = i1 < 0 ? (1 << 30) : i1, b = i2 < 0 ? (1 << 30) : i2, c = i3 < 0 ? (1 << 30) : i3, t;
-            if (a > b) { t = a; a = b; b = t; }
-            if (b > c) { t = b; b = c; c = t; }
-            if (a > b) { t = a; a = b; b = t; }
-            keep[0] = a < (1 << 30) ? a : -1; keep[1] = b < (1 << 30) ? b : -1; keep[2] = c < (1 << 30) ? c : -1;
-        }
-        __syncthreads();
-    }
-    for (int kb = 0; kb < 3; kb++) {
-        const int want = keep[kb];
-        if (want < 0) continue;
-        for (int e0 = 0; e0 < n1; e0 += 256) {
-            const int i1 = e0 + tid;
-            int bin = 0;
-            const int f = (accepted(i1, bin) && (!B.check_orientation || bin == want)) ? 1 : 0;
-            sflag[tid] = f;
-            __syncthreads();
-            const int total = tb_block_excl_scan(sflag, 256, tmp);
-            const int slot = srun + sflag[tid];
-            if (f && slot < B.cap) {
-                tb_match m;
-                m.queryIdx = i1; m.trainIdx = best[4 * (size_t)i1 + 2]; m.imgIdx = -1; m.distance = (float)best[4 * (size_t)i1];
-                out[slot] = m;
-            }
-            __syncthreads();
-            if (tid == 0) srun += total;
-            __syncthreads();
-        }
-    }
-    if (tid == 0) B.out_counts[p] = srun;
+    const int p = blockIdx.x;
+    const VioAccept P = {min(B.n1[p], B.pitch1), B.th_low, B.nratio, B.best + (size_t)p * B.pitch1 * 4, B.k1 + (size_t)p * B.pitch1,
+                         B.k2 + (size_t)p * B.pitch2};
+    match_accept_stage(P, B.histo_len, B.check_orientation, B.out + (size_t)p * B.cap, B.cap, B.out_counts + p, B.flags + p);
 }
 
 int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const uint8_t* d_d1, const int32_t* d_n1, int pitch1,
@@ -713,14 +626,8 @@ int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const u
     B.th_low = th_low; B.histo_len = histo_len; B.check_orientation = check_orientation;
     B.best = d_best; B.out = d_out; B.cap = cap; B.out_counts = d_out_counts; B.flags = d_flags;
     TB_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)npairs * sizeof(int32_t), ctx->stream));
-    tb_prof_begin(ctx, "k_window_batch");
-    hipLaunchKernelGGL(k_window_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    tb_prof_begin(ctx, "k_violence_accept");
-    hipLaunchKernelGGL(k_violence_accept_batch, dim3(npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_window_batch", k_window_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B);
+    TB_LAUNCH(ctx, "k_violence_accept", k_violence_accept_batch, dim3(npairs), dim3(256), 0, B);
     return TB_OK;
 }
 
@@ -739,7 +646,7 @@ k_stereo_obs(const tb_keypoint* __restrict__ kl, const tb_keypoint* __restrict__
              const int32_t* __restrict__ match_counts, int match_pitch, float fx, float fy, float cx, float cy, float bf,
              const float* __restrict__ inv_sigma2, int nlevels, tb_obs* __restrict__ obs, int obs_pitch, int32_t* __restrict__ obs_counts) {
     __shared__ int wsum[4];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x, tid = threadIdx.x;
     const int n = min(match_counts[f], match_pitch);
     const tb_keypoint* L = kl + (size_t)f * key_pitch;
     const tb_keypoint* Rk = kr + (size_t)f * key_pitch;
@@ -760,15 +667,8 @@ k_stereo_obs(const tb_keypoint* __restrict__ kl, const tb_keypoint* __restrict__
             ok = isfinite(depth) && b.octave >= 0 && b.octave < nlevels;
             o.inv_sigma2 = ok ? inv_sigma2[b.octave] : 0.f;
         }
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = tb_block_ordered_slot(ok, base, wsum);
         if (ok && at < obs_pitch) O[at] = o;
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid == 0) obs_counts[f] = min(base, obs_pitch);
 }
@@ -777,11 +677,8 @@ int tbk_stereo_obs(tb_ctx* ctx, int nframes, const tb_keypoint* d_kl, const tb_k
                    const int32_t* d_match_counts, int match_pitch, const float K[4], float bf, const float* d_inv_sigma2, int nlevels,
                    tb_obs* d_obs, int obs_pitch, int32_t* d_obs_counts) {
     if (nframes <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_stereo_obs");
-    hipLaunchKernelGGL(k_stereo_obs, dim3(nframes), dim3(256), 0, ctx->stream, d_kl, d_kr, key_pitch, d_matches, d_match_counts, match_pitch,
-                       K[0], K[1], K[2], K[3], bf, d_inv_sigma2, nlevels, d_obs, obs_pitch, d_obs_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_stereo_obs", k_stereo_obs, dim3(nframes), dim3(256), 0, d_kl, d_kr, key_pitch, d_matches, d_match_counts,
+              match_pitch, K[0], K[1], K[2], K[3], bf, d_inv_sigma2, nlevels, d_obs, obs_pitch, d_obs_counts);
     return TB_OK;
 }
 
@@ -833,8 +730,29 @@ k_bow_transform(BowVocab V, const uint8_t* __restrict__ desc, const int32_t* __r
 
 /* The frame's FeatureVector as a sorted key list: (node id << 32 | feature index) of the features whose word is not
  * stopped (w > 0, TemplatedVocabulary.h:1159), ascending -- the std::map's node order, each node's features in insertion
- * order. One workgroup per frame: keys into LDS (padding = all ones), bitonic sort, count of real keys. */
+ * order. One workgroup per frame: bow_sorted_keys, then the real keys out. */
 #define BOW_MAXN 8192
+#define BOW_T 1024 /* threads of k_bow_fv_sort and k_bow_vector */
+/* (id << 32 | index) of the entries i < n with weight > 0 into sk (padded with all ones to a power of two), sorted ascending;
+ * returns how many there are. The whole block of BOW_T calls it; wsum: one int per wave, read by every thread before it returns. */
+__device__ __forceinline__ int bow_sorted_keys(const int32_t* __restrict__ ids, const double* __restrict__ weights, int n,
+                                               unsigned long long* sk, int* wsum) {
+    const int tid = threadIdx.x;
+    int m = 1;
+    while (m < n) m <<= 1;
+    int mine = 0;
+    for (int i = tid; i < m; i += BOW_T) {
+        unsigned long long k = ~0ull;
+        if (i < n && weights[i] > 0) { k = ((unsigned long long)(unsigned)ids[i] << 32) | (unsigned)i; mine++; }
+        sk[i] = k;
+    }
+    mine = tb_wave_sum(mine);
+    if ((tid & 63) == 0) wsum[tid >> 6] = mine;
+    tb_block_bitonic_sort_u64(sk, m, BOW_T);
+    int total = 0;
+    for (int w = 0; w < BOW_T / 64; w++) total += wsum[w];
+    return total;
+}
 __global__ void __launch_bounds__(1024)
 k_bow_fv_sort(const int32_t* __restrict__ node_ids, const double* __restrict__ weights, const int32_t* __restrict__ counts,
               int desc_pitch, unsigned long long* __restrict__ keys_out, int32_t* __restrict__ fv_counts) {
@@ -842,31 +760,7 @@ k_bow_fv_sort(const int32_t* __restrict__ node_ids, const double* __restrict__ w
     __shared__ int wsum[16];
     const int f = blockIdx.x, tid = threadIdx.x;
     const int n = counts ? min(counts[f], desc_pitch) : desc_pitch;
-    int m = 1;
-    while (m < n) m <<= 1;
-    int mine = 0;
-    for (int i = tid; i < m; i += 1024) {
-        unsigned long long k = ~0ull;
-        if (i < n && weights[(size_t)f * desc_pitch + i] > 0) { k = ((unsigned long long)(unsigned)node_ids[(size_t)f * desc_pitch + i] << 32) | (unsigned)i; mine++; }
-        sk[i] = k;
-    }
-    mine = tb_wave_sum(mine);
-    if ((tid & 63) == 0) wsum[tid >> 6] = mine;
-    __syncthreads();
-    for (int k2 = 2; k2 <= m; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < m; i += 1024) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = sk[i], y = sk[l];
-                    const bool up = (i & k2) == 0;
-                    if ((x > y) == up) { sk[i] = y; sk[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    int total = 0;
-    for (int w = 0; w < 16; w++) total += wsum[w];
+    const int total = bow_sorted_keys(node_ids + (size_t)f * desc_pitch, weights + (size_t)f * desc_pitch, n, sk, wsum);
     for (int i = tid; i < total; i += 1024) keys_out[(size_t)f * desc_pitch + i] = sk[i];
     if (tid == 0) fv_counts[f] = total;
 }
@@ -874,7 +768,7 @@ k_bow_fv_sort(const int32_t* __restrict__ node_ids, const double* __restrict__ w
 /* The frame's BowVector (the other half of Frame::SetBow): TemplatedVocabulary::transform(features, v, fv, levelsup),
  * TemplatedVocabulary.h:1124-1188, and BowVector::normalize, BowVector.cpp:57-80, as a sorted list -- word ids ascending (the
  * std::map's order) and their values. One workgroup per frame:
- *   1. (word << 32 | feature) keys of the features whose word is not stopped into LDS, bitonic sort (as k_bow_fv_sort);
+ *   1. (word << 32 | feature) keys of the features whose word is not stopped, sorted in LDS (bow_sorted_keys);
  *   2. a word = a run of equal upper halves; the thread that owns the run's first entry adds the run's weights in list order =
  *      ascending feature index (TF, TF_IDF: addWeight) or keeps the first (IDF, BINARY: addIfNotExist); its slot in the output
  *      is the number of run heads before it;
@@ -892,31 +786,7 @@ k_bow_vector(const int32_t* __restrict__ word_ids, const double* __restrict__ we
     const int f = blockIdx.x, tid = threadIdx.x;
     const int n = counts ? min(max(counts[f], 0), desc_pitch) : desc_pitch;
     const size_t base = (size_t)f * desc_pitch;
-    int m = 1;
-    while (m < n) m <<= 1;
-    int mine = 0;
-    for (int i = tid; i < m; i += 1024) {
-        unsigned long long k = ~0ull;
-        if (i < n && weights[base + i] > 0) { k = ((unsigned long long)(unsigned)word_ids[base + i] << 32) | (unsigned)i; mine++; }
-        sk[i] = k;
-    }
-    mine = tb_wave_sum(mine);
-    if ((tid & 63) == 0) wsum[tid >> 6] = mine;
-    __syncthreads();
-    for (int k2 = 2; k2 <= m; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < m; i += 1024) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = sk[i], y = sk[l];
-                    const bool up = (i & k2) == 0;
-                    if ((x > y) == up) { sk[i] = y; sk[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    int total = 0;
-    for (int w = 0; w < 16; w++) total += wsum[w];
+    const int total = bow_sorted_keys(word_ids + base, weights + base, n, sk, wsum);
     __syncthreads();   /* wsum is reused below */
     /* run heads of this thread's contiguous chunk, their rank among all heads */
     const int per = (total + 1023) / 1024;
@@ -1016,89 +886,36 @@ k_bow_search_batch(BowBatch B) {
     }
     reinterpret_cast<int4*>(B.best)[(size_t)p * B.pitch1 + pos] = make_int4(bestDist1, bestDist2, bestIdx2, found);
 }
-/* acceptance (matcher.cpp:671-689), rotation histogram, ComputeThreeMaxima and the reference's output order (kept bins in
- * ascending order, emission order inside a bin: matcher.cpp:703-717) -- the structure of k_violence_accept_batch */
+/* searchByBow's acceptance (matcher.cpp:671-689; output order :703-717), one workgroup per pair */
+struct BowAccept {
+    int n, th_low;
+    float nratio;
+    const int32_t* best;
+    const unsigned long long* F1;
+    const tb_keypoint *k1, *k2;
+    __device__ bool accept(int pos) const {
+        const int bd = best[4 * (size_t)pos], bd2 = best[4 * (size_t)pos + 1];
+        return best[4 * (size_t)pos + 3] != 0 && best[4 * (size_t)pos + 2] >= 0 && bd < th_low && (float)bd < nratio * (float)bd2;
+    }
+    __device__ float rotation(int pos) const { return k1[(unsigned)F1[pos]].angle - k2[best[4 * (size_t)pos + 2]].angle; }
+    __device__ tb_match make(int pos) const {
+        tb_match m;
+        m.queryIdx = (int)(unsigned)F1[pos]; m.trainIdx = best[4 * (size_t)pos + 2]; m.imgIdx = -1; m.distance = (float)best[4 * (size_t)pos];
+        return m;
+    }
+};
 __global__ void __launch_bounds__(256)
 k_bow_accept_batch(BowBatch B) {
-    __shared__ int hist[1024];
-    __shared__ int sflag[256];
-    __shared__ int tmp[8];
-    __shared__ int keep[3];
-    __shared__ int srun;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int f1 = B.ix1 ? B.ix1[p] : p, f2 = B.ix2 ? B.ix2[p] : p;
+    if (tid == 0) B.flags[p] = 0;   /* ahead of the stage's first barrier, so of every flag it raises */
     if (f1 < 0 || f2 < 0) {   /* the whole workgroup: no barrier has been reached */
-        if (tid == 0) { B.out_counts[p] = 0; B.flags[p] = 0; }
+        if (tid == 0) B.out_counts[p] = 0;
         return;
     }
-    const int n1 = min(B.n1[f1], B.pitch1);
-    const int32_t* best = B.best + (size_t)p * B.pitch1 * 4;
-    const unsigned long long* F1 = B.fv1 + (size_t)f1 * B.pitch1;
-    const tb_keypoint* k1 = B.k1 + (size_t)f1 * B.pitch1;
-    const tb_keypoint* k2 = B.k2 + (size_t)f2 * B.pitch2;
-    tb_match* out = B.out + (size_t)p * B.cap;
-    const float factor = 1.f / (float)B.histo_len;
-    auto accepted = [&](int pos, int& bin) -> bool {
-        if (pos >= n1) return false;
-        const int bd = best[4 * (size_t)pos], bd2 = best[4 * (size_t)pos + 1], bi = best[4 * (size_t)pos + 2];
-        if (best[4 * (size_t)pos + 3] == 0 || bi < 0) return false;
-        if (!(bd < B.th_low && (float)bd < B.nratio * (float)bd2)) return false;
-        bin = 0;
-        if (B.check_orientation) {
-            float rot = k1[(unsigned)F1[pos]].angle - k2[bi].angle;
-            if (rot < 0) rot += 360.f;
-            bin = (int)roundf(rot * factor);
-            if (bin == B.histo_len) bin = 0;
-            if (bin < 0 || bin >= B.histo_len) { B.flags[p] = 2; return false; } /* the reference asserts */
-        }
-        return true;
-    };
-    if (tid == 0) { keep[0] = B.check_orientation ? -1 : 0; keep[1] = keep[2] = -1; srun = 0; B.flags[p] = 0; }
-    for (int b = tid; b < B.histo_len; b += 256) hist[b] = 0;
-    __syncthreads();
-    if (B.check_orientation) {
-        for (int pos = tid; pos < n1; pos += 256) { int bin; if (accepted(pos, bin)) atomicAdd(&hist[bin], 1); }
-        __syncthreads();
-        if (tid == 0) { /* Matcher::ComputeThreeMaxima, matcher.cpp:810-851 */
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < B.histo_len; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            int a = i1 < 0 ? (1 << 30) : i1, b = i2 < 0 ? (1 << 30) : i2, c = i3 < 0 ? (1 << 30) : i3, t;
-            if (a > b) { t = a; a = b; b = t; }
-            if (b > c) { t = b; b = c; c = t; }
-            if (a > b) { t = a; a = b; b = t; }
-            keep[0] = a < (1 << 30) ? a : -1; keep[1] = b < (1 << 30) ? b : -1; keep[2] = c < (1 << 30) ? c : -1;
-        }
-        __syncthreads();
-    }
-    for (int kb = 0; kb < 3; kb++) {
-        const int want = keep[kb];
-        if (want < 0) continue;
-        for (int e0 = 0; e0 < n1; e0 += 256) {
-            const int pos = e0 + tid;
-            int bin = 0;
-            const int f = (accepted(pos, bin) && (!B.check_orientation || bin == want)) ? 1 : 0;
-            sflag[tid] = f;
-            __syncthreads();
-            const int total = tb_block_excl_scan(sflag, 256, tmp);
-            const int slot = srun + sflag[tid];
-            if (f && slot < B.cap) {
-                tb_match m;
-                m.queryIdx = (int)(unsigned)F1[pos]; m.trainIdx = best[4 * (size_t)pos + 2]; m.imgIdx = -1; m.distance = (float)best[4 * (size_t)pos];
-                out[slot] = m;
-            }
-            __syncthreads();
-            if (tid == 0) srun += total;
-            __syncthreads();
-        }
-    }
-    if (tid == 0) B.out_counts[p] = srun;
+    const BowAccept P = {min(B.n1[f1], B.pitch1), B.th_low, B.nratio, B.best + (size_t)p * B.pitch1 * 4, B.fv1 + (size_t)f1 * B.pitch1,
+                         B.k1 + (size_t)f1 * B.pitch1, B.k2 + (size_t)f2 * B.pitch2};
+    match_accept_stage(P, B.histo_len, B.check_orientation, B.out + (size_t)p * B.cap, B.cap, B.out_counts + p, B.flags + p);
 }
 
 int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_start, const int32_t* d_child_items, const uint8_t* d_vdesc,
@@ -1107,21 +924,15 @@ int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_sta
                       unsigned long long* d_fv_keys, int32_t* d_fv_counts) {
     if (nframes <= 0 || desc_pitch <= 0) return TB_OK;
     BowVocab V = {nnodes, L, d_child_start, d_child_items, d_vdesc, d_word_id, d_weight};
-    tb_prof_begin(ctx, "k_bow_transform");
-    hipLaunchKernelGGL(k_bow_transform, dim3((desc_pitch + 255) / 256, nframes), dim3(256), 0, ctx->stream, V, d_desc, d_counts, desc_pitch,
-                       levelsup, d_word_ids, d_node_ids, d_weights);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_bow_transform", k_bow_transform, dim3((desc_pitch + 255) / 256, nframes), dim3(256), 0, V, d_desc, d_counts,
+              desc_pitch, levelsup, d_word_ids, d_node_ids, d_weights);
     if (d_fv_keys) {
         int m = 1;
         while (m < desc_pitch) m <<= 1;
         const size_t lds = (size_t)m * sizeof(unsigned long long);
         TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_fv_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        tb_prof_begin(ctx, "k_bow_fv_sort");
-        hipLaunchKernelGGL(k_bow_fv_sort, dim3(nframes), dim3(1024), lds, ctx->stream, d_node_ids, d_weights, d_counts, desc_pitch, d_fv_keys,
-                           d_fv_counts);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_LAUNCH(ctx, "k_bow_fv_sort", k_bow_fv_sort, dim3(nframes), dim3(1024), lds, d_node_ids, d_weights, d_counts, desc_pitch,
+                  d_fv_keys, d_fv_counts);
     }
     return TB_OK;
 }
@@ -1133,11 +944,8 @@ int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const do
     while (m < desc_pitch) m <<= 1;
     const size_t lds = (size_t)m * sizeof(unsigned long long);
     TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tb_prof_begin(ctx, "k_bow_vector");
-    hipLaunchKernelGGL(k_bow_vector, dim3(nframes), dim3(1024), lds, ctx->stream, d_word_ids, d_weights, d_counts, desc_pitch, weighting,
-                       scoring, d_bv_words, d_bv_values, d_bv_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_bow_vector", k_bow_vector, dim3(nframes), dim3(1024), lds, d_word_ids, d_weights, d_counts, desc_pitch, weighting,
+              scoring, d_bv_words, d_bv_values, d_bv_counts);
     return TB_OK;
 }
 
@@ -1153,12 +961,7 @@ int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const
     B.pitch1 = pitch1; B.pitch2 = pitch2; B.map_point_only = map_point_only; B.th_low = th_low; B.histo_len = histo_len;
     B.check_orientation = check_orientation; B.cap = cap; B.nratio = nratio; B.best = d_best; B.out = d_out; B.out_counts = d_out_counts;
     B.flags = d_flags;
-    tb_prof_begin(ctx, "k_bow_search_batch");
-    hipLaunchKernelGGL(k_bow_search_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    tb_prof_begin(ctx, "k_bow_accept_batch");
-    hipLaunchKernelGGL(k_bow_accept_batch, dim3(npairs), dim3(256), 0, ctx->stream, B);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
+    TB_LAUNCH(ctx, "k_bow_search_batch", k_bow_search_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B);
+    TB_LAUNCH(ctx, "k_bow_accept_batch", k_bow_accept_batch, dim3(npairs), dim3(256), 0, B);
     return TB_OK;
 }

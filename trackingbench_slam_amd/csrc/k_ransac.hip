@@ -240,25 +240,18 @@ k_ransac_f(const float* __restrict__ pts1, const float* __restrict__ pts2, uint8
     for (int i0 = 0; i0 < n; i0 += RS_T) {
         const int i = i0 + tid;
         const bool v = i < n && (mode == 1 || st[i] != 0);
-        const unsigned long long bm = __ballot(v);
-        if (lane == 0) S.wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = m;
-        for (int w = 0; w < wave; w++) off += S.wsum[w];
-        const int tot = S.wsum[0] + S.wsum[1] + S.wsum[2] + S.wsum[3];
+        const int k = tb_block_ordered_slot(v, m, S.wsum);
         if (v) {
-            const int k = off + __popcll(bm & ((1ull << lane) - 1));
             id[k] = i;
             p1[2 * k] = c1[2 * i]; p1[2 * k + 1] = c1[2 * i + 1];
             p2[2 * k] = c2[2 * i]; p2[2 * k + 1] = c2[2 * i + 1];
         }
-        m += tot;
-        __syncthreads();
     }
     __threadfence_block();
     if (m < 7) { if (tid == 0 && mode == 1) flags[pair] = 1; return; }   /* no mask comes back: flags stay (UB in the reference) */
     if (m == 7) {                            /* the 7-point solver alone, every point an inlier */
         if (mode == 1) {
+            __syncthreads();   /* thread 0 reads the points the others gathered (the paths below meet a barrier before they do) */
             if (tid == 0) {
                 const int nm = rs_run_7point(p1, p2, S.A, S.F);
                 S.found = nm > 0;

@@ -4,6 +4,7 @@
  *
  * A store array is [nseq][cap][pitch]: frame index s * cap + slot, so the matcher reads a stored keyframe in place. */
 #include "tb_internal.h"
+#include "tb_device.h"
 #include "tb_kfcopy.h"
 
 struct KfStoreArrays {
@@ -84,7 +85,7 @@ k_reloc_rows(const tb_keypoint* __restrict__ q_keys, const int32_t* __restrict__
              int32_t* __restrict__ rows_out) {
     extern __shared__ int win[];   /* [q_pitch] */
     __shared__ int wsum[4];
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, tid = threadIdx.x;
     const int s = ix1[c], f = ix2[c];
     if (f < 0 || s < 0) {
         if (tid == 0) { obs_counts[c] = 0; if (rows_out) rows_out[c] = 0; }
@@ -123,15 +124,8 @@ k_reloc_rows(const tb_keypoint* __restrict__ q_keys, const int32_t* __restrict__
                 r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];
             }
         }
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = tb_block_ordered_slot(ok, base, wsum);
         if (ok) O[at] = r; /* at < n <= q_pitch <= pitch */
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid == 0) { obs_counts[c] = base; if (rows_out) rows_out[c] = base; }
 }

@@ -1,6 +1,6 @@
 /* Device-resident stereo VO loop (test/test_vo.cpp test_kitti, :674-850): the glue between the batched operators.
  *
- * One workgroup of 256 per sequence; ordered compaction with __ballot prefix counts (as k_stereo_obs, k_match.hip).
+ * One workgroup of 256 per sequence; ordered compaction with tb_block_ordered_slot (tb_device.h).
  * float32 arithmetic, one operation per statement (the library builds with -ffp-contract=off), left to right; the CPU
  * composition in tests/vo_reference.py does the same operations in the same order. */
 #include "tb_internal.h"
@@ -34,7 +34,7 @@ k_vo_track(const int32_t* __restrict__ prev_counts, const uint8_t* __restrict__ 
            float* __restrict__ mp, uint8_t* __restrict__ valid, tb_obs* __restrict__ obs, int32_t* __restrict__ obs_counts,
            uint8_t* __restrict__ outlier) {
     __shared__ int wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(prev_counts[s], 0), pitch);
     const size_t o = (size_t)s * pitch;
     tb_obs* O = obs + o;
@@ -54,15 +54,8 @@ k_vo_track(const int32_t* __restrict__ prev_counts, const uint8_t* __restrict__ 
             r.X = X; r.Y = Y; r.Z = Z;
             r.inv_sigma2 = 1.0f;
         }
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = tb_block_ordered_slot(ok, base, wsum);
         if (ok) O[at] = r; /* at < n <= pitch */
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
 }
@@ -89,7 +82,7 @@ k_vo_match_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict_
                  int32_t* __restrict__ key_counts, float* __restrict__ mp, uint8_t* __restrict__ valid, tb_obs* __restrict__ obs,
                  int32_t* __restrict__ obs_counts, uint8_t* __restrict__ outlier) {
     __shared__ int wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(orb_counts[s], 0), pitch);
     const int nm = min(max(match_counts[s], 0), pitch);
     const int nk = min(max(kf_counts[s], 0), pitch);
@@ -127,15 +120,8 @@ k_vo_match_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict_
             r.X = X; r.Y = Y; r.Z = Z;
             r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];   /* the extractor's octaves are in [0, nlevels) */
         }
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = tb_block_ordered_slot(ok, base, wsum);
         if (ok) O[at] = r; /* at < n <= pitch */
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
 }
@@ -222,7 +208,7 @@ k_vo_proj_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__
                 float* __restrict__ keys, int32_t* __restrict__ key_counts, float* __restrict__ mp, uint8_t* __restrict__ valid,
                 uint8_t* __restrict__ mp_desc, tb_obs* __restrict__ obs, int32_t* __restrict__ obs_counts, uint8_t* __restrict__ outlier) {
     __shared__ int wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(orb_counts[s], 0), pitch);
     const int nm = min(max(match_counts[s], 0), match_pitch);   /* the matcher's count is not truncated, its list is */
     const int ns = min(max(src_counts[s], 0), src_pitch);
@@ -266,15 +252,8 @@ k_vo_proj_carry(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__
             r.X = X; r.Y = Y; r.Z = Z;
             r.inv_sigma2 = sig.v[min(max(kp.octave, 0), sig.n - 1)];
         }
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = tb_block_ordered_slot(ok, base, wsum);
         if (ok) O[at] = r; /* at < n <= pitch */
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid == 0) { key_counts[s] = n; obs_counts[s] = base; }
 }
@@ -295,7 +274,7 @@ k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__
                uint8_t* __restrict__ map_desc, int32_t* __restrict__ map_n, int32_t* __restrict__ map_blocks, int nblk, int slot,
                int map_pitch, const int32_t* __restrict__ idx) {
     __shared__ int wsum[4];
-    const int rw = blockIdx.x, s = idx ? idx[rw] : rw, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   /* depth row rw */
+    const int rw = blockIdx.x, s = idx ? idx[rw] : rw, tid = threadIdx.x;   /* depth row rw */
     const int m = min(max(key_counts[s], 0), pitch);
     const size_t o = (size_t)s * pitch, om = (size_t)s * map_pitch, od = (size_t)rw * pitch;
     const float* T = Tcw + 16 * s;
@@ -331,12 +310,7 @@ k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__
             if (rec) rec[o + j] = r;
         }
         if (!map_rec) continue;   /* uniform over the workgroup */
-        const unsigned long long bm = __ballot(ok);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int at = n0 + off + __popcll(bm & ((1ull << lane) - 1));
+        const int at = n0 + tb_block_ordered_slot(ok, base, wsum);
         if (ok && at < map_pitch) {
             const float e0 = r.pos[0] - t[0], e1 = r.pos[1] - t[1], e2 = r.pos[2] - t[2];
             float q = e0 * e0;
@@ -351,8 +325,6 @@ k_vo_kf_append(const int32_t* __restrict__ key_counts, const float* __restrict__
             unsigned long long* E = reinterpret_cast<unsigned long long*>(map_desc) + 4 * (om + at);
             E[0] = d0; E[1] = d1; E[2] = d2; E[3] = d3;
         }
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (map_rec && tid == 0) {
         map_n[s] = min(n0 + base, map_pitch);
@@ -743,7 +715,7 @@ k_vo_seg_log(const float* __restrict__ keys, const int32_t* __restrict__ key_cou
              const uint8_t* __restrict__ seg_spawned, int pitch, int nslot, int slot, float* __restrict__ seg_keys,
              uint8_t* __restrict__ seg_ok, float* __restrict__ seg_pose) {
     __shared__ int wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(key_counts[s], 0), pitch);
     const bool held = obs_counts[s] < 3;
     const size_t o = (size_t)s * pitch, oj = ((size_t)s * nslot + slot) * pitch;
@@ -751,16 +723,9 @@ k_vo_seg_log(const float* __restrict__ keys, const int32_t* __restrict__ key_cou
     for (int i0 = 0; i0 < pitch; i0 += 256) {
         const int i = i0 + tid;
         const bool v = i < n && valid[o + i];
-        const unsigned long long bm = __ballot(v);
-        if (lane == 0) wsum[wave] = __popcll(bm);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        const int row = off + __popcll(bm & ((1ull << lane) - 1));   /* row < n <= pitch */
+        const int row = tb_block_ordered_slot(v, base, wsum);   /* row < n <= pitch */
         if (i < n) { seg_keys[2 * (oj + i)] = keys[2 * (o + i)]; seg_keys[2 * (oj + i) + 1] = keys[2 * (o + i) + 1]; }
         if (i < pitch) seg_ok[oj + i] = (v && !held && seg_spawned[o + i] && !outlier[o + row]) ? 1 : 0;
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
     }
     if (tid < 16) seg_pose[16 * ((size_t)s * nslot + slot) + tid] = Tcw[16 * (size_t)s + tid];
 }

@@ -875,16 +875,7 @@ int tb_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 }
 
 void tb_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3) {
-    /* Matcher::ComputeThreeMaxima, matcher.cpp:810-851 (caller initialises the indices, :379) */
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < L; i++) {
-        const int s = sizes[i];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; *ind3 = *ind2; *ind2 = *ind1; *ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; *ind3 = *ind2; *ind2 = i; }
-        else if (s > max3) { max3 = s; *ind3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { *ind2 = -1; *ind3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) { *ind3 = -1; }
+    tbm::three_maxima(sizes, L, ind1, ind2, ind3);   /* the function the matchers' accept stage runs on the device */
 }
 
 /* the end of every single-frame matcher: one synchronisation for the device list's count and flag (cf = count, flag), the

@@ -90,4 +90,40 @@ __device__ inline int tb_block_excl_scan(int* arr, int n, int* tmp) {
     return total;
 }
 
+/* Ordered compaction, one 256-thread chunk: the slot of this thread's element = base + the number of threads with a lower
+ * index whose `ok` is set (__ballot prefix counts inside a wave, the wave totals through wsum); base advances by the block's
+ * count. EVERY thread of a 256-thread block must call it (two barriers), with the same base; wsum: int[4] in LDS. The second
+ * barrier only frees wsum for the next call: it does not order the caller's stores to the slots. */
+__device__ __forceinline__ int tb_block_ordered_slot(bool ok, int& base, int* wsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bm = __ballot(ok);
+    if (lane == 0) wsum[wave] = __popcll(bm);
+    __syncthreads();
+    int at = base;
+    for (int w = 0; w < wave; w++) at += wsum[w];
+    at += __popcll(bm & ((1ull << lane) - 1));
+    base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    return at;
+}
+
+/* Ascending bitonic sort of sk[0..m) in LDS by the whole block, any block size (T = blockDim.x; a caller that knows it passes
+ * the constant, which keeps the strided loops' trip counts out of registers); m a power of two. A barrier in front (the caller
+ * has just staged sk) and one after every step: it ends on a barrier. */
+__device__ __forceinline__ void tb_block_bitonic_sort_u64(unsigned long long* sk, int m, const int T = blockDim.x) {
+    __syncthreads();
+    for (int k2 = 2; k2 <= m; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < m; i += T) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long x = sk[i], y = sk[l];
+                    const bool up = (i & k2) == 0;
+                    if ((x > y) == up) { sk[i] = y; sk[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
 #endif

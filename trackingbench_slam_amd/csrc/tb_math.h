@@ -154,5 +154,30 @@ TB_HD float fast_atan2(float y, float x) {
     return a;
 }
 
+/* Matcher::ComputeThreeMaxima, matcher.cpp:810-851: the indices of the three largest bins, first index on ties; the second
+ * and third are dropped (-1) when they are below a tenth of the largest. The caller initialises the indices (:379).
+ * always_inline: the device caller's indices stay in registers. */
+TB_HD __attribute__((always_inline)) void three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3) {
+    int max1 = 0, max2 = 0, max3 = 0, i1 = *ind1, i2 = *ind2, i3 = *ind3;
+    for (int i = 0; i < L; i++) {
+        const int s = sizes[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+        else if (s > max3) { max3 = s; i3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    *ind1 = i1; *ind2 = i2; *ind3 = i3;
+}
+
+/* the kept bins in ascending order, -1 (dropped) last: the order in which the matchers emit their bins */
+TB_HD __attribute__((always_inline)) void kept_bins_ascending(int i1, int i2, int i3, int* keep) {
+    int a = i1 < 0 ? (1 << 30) : i1, b = i2 < 0 ? (1 << 30) : i2, c = i3 < 0 ? (1 << 30) : i3, t;
+    if (a > b) { t = a; a = b; b = t; }
+    if (b > c) { t = b; b = c; c = t; }
+    if (a > b) { t = a; a = b; b = t; }
+    keep[0] = a < (1 << 30) ? a : -1; keep[1] = b < (1 << 30) ? b : -1; keep[2] = c < (1 << 30) ? c : -1;
+}
+
 }  // namespace tbm
 #endif
