@@ -58,6 +58,10 @@ int tb_measure_copy_seconds(tb_ctx* ctx, const void* d_src, void* d_dst, size_t 
 /* Test hook: on != 0 sends every block of the cell-wise FAST kernel down its any-density path (no candidate lists; the
  * results are the same). A context setting, not an environment variable: nothing outside the caller changes which kernels run. */
 int tb_debug_force_dense_fast(tb_ctx* ctx, int on);
+/* Test hook: on != 0 makes the point passes of tb_local_ba / tb_local_ba_batch_dev walk the array-of-structs copy of the
+ * observations in every window, also where they would read the lane-interleaved stream (tb_ba_obs_stream_positions). The
+ * results are the same bit for bit. */
+int tb_debug_ba_plain_obs(tb_ctx* ctx, int on);
 int tb_profile_report(tb_ctx* ctx, char* buf, int cap);
 
 /* ---------------------------------------------------------------- a1/a2/a3: host-side scalar set-up
@@ -613,6 +617,12 @@ int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* pose
 int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf, int nfixed, float* poses, int npt,
                           float* pts, const tb_ba_obs* obs, const int32_t* obs_counts, int obs_pitch, int iters,
                           double* stats);
+/* Host-only: the layout of the observation stream the local BA's point passes read in windows of up to 8192 points, 10 free and
+ * 64 keyframes. pt_start: npt + 1 ints, the first observation of every point (CSR, observations grouped by point); pos
+ * [pt_start[npt]]: pos[pt_start[p] + j] = stream entry of point p's j-th observation. The 64 points [64 B, 64 B + 63] own the
+ * entries pt_start[64 B] .. pt_start[64 B + 64]; there all points' observation 0 come first, then all observation 1, ..., each
+ * run in point order and holding only the points that have that many. */
+int tb_ba_obs_stream_positions(const int32_t* pt_start, int npt, int32_t* pos);
 
 /* ---------------------------------------------------------------- device-resident stereo VO loop
  * The tracking loop of the reference's main program, test/test_vo.cpp test_kitti (:674-850), for nseq independent stereo

@@ -28,7 +28,7 @@ TB_OK, TB_EINVAL, TB_ENOMEM, TB_ECAPACITY, TB_EUNSUPPORTED, TB_EDEVICE, TB_ESTAT
 # every symbol include/tb_capi.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = [
     "tb_create", "tb_destroy", "tb_last_error", "tb_strerror", "tb_version", "tb_set_stream", "tb_synchronize",
-    "tb_profile_enable", "tb_profile_only", "tb_profile_report", "tb_debug_force_dense_fast", "tb_measure_copy_seconds", "tb_set_concurrency", "tb_pack_rows_dev",
+    "tb_profile_enable", "tb_profile_only", "tb_profile_report", "tb_debug_force_dense_fast", "tb_debug_ba_plain_obs", "tb_measure_copy_seconds", "tb_set_concurrency", "tb_pack_rows_dev",
     "tb_scale_factors", "tb_pyramid_sizes", "tb_orb_quotas",
     "tb_extractor_create", "tb_extractor_destroy", "tb_extractor_set_images_host", "tb_extractor_set_images_dev",
     "tb_extractor_set_levels_host", "tb_extractor_build_pyramid", "tb_extractor_get_level_host", "tb_extractor_orb",
@@ -39,7 +39,7 @@ EXPORTS = [
     "tb_search_by_violence", "tb_search_by_bow", "tb_search_by_projection", "tb_search_by_projection_map", "tb_frame_grid_batch_dev",
     "tb_search_by_projection_batch_dev", "tb_search_by_projection_map_batch_dev",
     "tb_search_by_violence_batch_dev", "tb_stereo_tracks_to_obs_batch_dev", "tb_vocab_create", "tb_vocab_destroy", "tb_bow_transform",
-    "tb_bow_transform_batch_dev", "tb_search_by_bow_batch_dev", "tb_pose_opt", "tb_pose_opt_batch_dev", "tb_local_ba", "tb_local_ba_batch_dev",
+    "tb_bow_transform_batch_dev", "tb_search_by_bow_batch_dev", "tb_pose_opt", "tb_pose_opt_batch_dev", "tb_local_ba", "tb_local_ba_batch_dev", "tb_ba_obs_stream_positions",
     "tb_clahe", "tb_clahe_dev", "tb_optical_flow_pyr_lk", "tb_optical_flow_pyr_lk_dev", "tb_optical_flow_pyr_lk_batch_dev", "tb_search_by_opflow", "tb_search_by_opflow_batch_dev",
     "tb_find_fundamental_ransac", "tb_reject_with_f", "tb_reject_with_f_batch_dev", "tb_add_map_points_by_stereo", "tb_add_map_points_by_stereo_batch_dev",
     "tb_batch_run", "tb_vo_create", "tb_vo_destroy", "tb_vo_reset_dev", "tb_vo_step_dev", "tb_vo_state_dev",
@@ -172,6 +172,16 @@ def three_maxima(sizes):
     i1, i2, i3 = C.c_int(-1), C.c_int(-1), C.c_int(-1)
     lib().tb_three_maxima(_p(sizes), len(sizes), C.byref(i1), C.byref(i2), C.byref(i3))
     return i1.value, i2.value, i3.value
+
+
+def ba_obs_stream_positions(pt_start):
+    """tb_ba_obs_stream_positions: where the local BA's observation stream keeps every observation (pt_start: CSR by point)"""
+    pt_start = np.ascontiguousarray(pt_start, np.int32)
+    pos = np.full(int(pt_start[-1]), -1, np.int32)
+    rc = lib().tb_ba_obs_stream_positions(_p(pt_start), len(pt_start) - 1, _p(pos))
+    if rc:
+        raise TBError(rc, "tb_ba_obs_stream_positions")
+    return pos
 
 
 class BatchParams(C.Structure):
@@ -495,6 +505,10 @@ class Context:
     def set_concurrency(self, peers):
         """tb_set_concurrency: `peers` contexts share this GPU at the same time (launch-shape hint)."""
         self.check(lib().tb_set_concurrency(self._h, int(peers)))
+
+    def ba_plain_obs(self, on=True):
+        """test hook (tb_debug_ba_plain_obs): the local BA's point passes walk the array-of-structs observations"""
+        self.check(lib().tb_debug_ba_plain_obs(self._h, int(on)))
 
     def force_dense_fast(self, on=True):
         """Test hook: every FAST block takes the any-density path (same results)."""

@@ -31,6 +31,7 @@
 #include "tb_internal.h"
 #include "tb_device.h"
 #include "tb_se3.h"
+#include "tb_math.h"
 
 #define BA_T 256
 #ifndef BA_KFCH
@@ -44,6 +45,9 @@
 #define BA_SORT_LDS 8192      /* points of a window whose pattern sort runs in LDS (k_ba_groups) */
 #ifndef BA_EMAX
 #define BA_EMAX 64            /* free-keyframe edges of a Schur group at most: one lane each */
+#endif
+#ifndef BA_UPD_BATCH
+#define BA_UPD_BATCH 4        /* slots per fetch of k_ba_update's second walk */
 #endif
 #ifndef BA_PCAP
 #define BA_PCAP 21            /* points of a Schur group at most (their 12-double records fill 252 of 256 staged doubles) */
@@ -80,6 +84,9 @@ struct BaDims {
     int renum;                   /* k_ba_rank renumbered the window's points in visibility-pattern order: every later kernel works on
                                     the renumbered copy of the observations, ranks are the identity */
     unsigned long long oPerm;    /* ints (renum): old index of the point that is now r */
+    int stream;                  /* renum, unless tb_debug_ba_plain_obs: the point passes read the lane-interleaved observation stream
+                                    (ba_stream_walk) that k_ba_prepare writes at oFreeKP -- a region only the windows it does not
+                                    serve use (k_ba_setup's free-edge records for k_ba_groups and the block-pair kernels) */
     int schurWaveLds;            /* doubles of LDS per Schur wavefront (host: ba_c_wave_lds(nfree)) */
     int wgReduce;                /* Schur workgroups add their four wavefronts' partial systems through LDS (small batches: many
                                     workgroups per window, and k_ba_solve -- one workgroup per window -- adds them all) */
@@ -372,11 +379,82 @@ __device__ __forceinline__ void ba_write_rec(double* q, const double* Hll, const
     if (!ok) st->sing = 1; /* benign race: every writer stores 1 */
     const double u00 = i00, u11 = i11, u22 = i22, u01 = -c10 * i00 * i11, u12 = -c21 * i11 * i22,
                  u02 = -(c20 * i00 + c21 * u01) * i22;
-    q[0] = ok ? u00 : 0.0; q[1] = ok ? u01 : 0.0; q[2] = ok ? u02 : 0.0;
-    q[3] = ok ? u11 : 0.0; q[4] = ok ? u12 : 0.0; q[5] = ok ? u22 : 0.0;
-    q[6] = bl[0]; q[7] = bl[1]; q[8] = bl[2]; /* the gradient itself: the back-substitution needs it, the Schur kernels form U^T bl (ba_rec_utb) */
-    q[9] = X[0]; q[10] = X[1]; q[11] = X[2];
+    /* six 16-byte stores: a record starts at a multiple of 96 bytes behind oHq, and ba_dims' take() keeps every offset and the
+     * window stride even, so with the 16-byte-aligned workspace the int4 tables already need every record is 16-byte aligned */
+    ba_d2* q2 = reinterpret_cast<ba_d2*>(q);
+    q2[0] = ba_d2{ok ? u00 : 0.0, ok ? u01 : 0.0};
+    q2[1] = ba_d2{ok ? u02 : 0.0, ok ? u11 : 0.0};
+    q2[2] = ba_d2{ok ? u12 : 0.0, ok ? u22 : 0.0};
+    q2[3] = ba_d2{bl[0], bl[1]}; /* the gradient itself: the back-substitution needs it, the Schur kernels form U^T bl (ba_rec_utb) */
+    q2[4] = ba_d2{bl[2], X[0]};
+    q2[5] = ba_d2{X[1], X[2]};
 }
+/* a point record as six 16-byte loads (alignment: see ba_write_rec) */
+__device__ __forceinline__ void ba_load_rec(const double* __restrict__ q, double* __restrict__ r) {
+    const ba_d2* q2 = reinterpret_cast<const ba_d2*>(q);
+#pragma unroll
+    for (int i = 0; i < 6; i++) { const ba_d2 v = q2[i]; r[2 * i] = v.x; r[2 * i + 1] = v.y; }
+}
+
+/* The observation stream of renumbered windows: 16-byte entries {kf, u, v, inv_sigma2}, the point implicit, sliced by
+ * wavefront of the point passes. The 64 consecutive ranks [64 B, 64 B + 63] -- one wavefront, p = 256 bx + tid -- own the
+ * entries ptStart[64 B] .. ptStart[64 B + 64]; inside that range all lanes' slot 0 come first, then all slot 1, ..., a slot
+ * holds only the lanes with more observations than that, in lane order, without padding (tbm::ba_stream_slot is the rule, ba_stream_slot_self its form for the calling lane,
+ * tb_ba_obs_stream_positions its host form). Slot j of a point is its j-th observation in the caller's order, so a walk
+ * visits a point's observations in the order of the array-of-structs copy and every per-point sum keeps its order -- but a
+ * wave-level load reads one contiguous run of up to 1 KB where 64 lanes walking their own 20-byte structs (lane stride ~88
+ * bytes) touched 45-64 cache lines. No LDS, no barrier: the point passes share their CUs with the extractor's workgroups.
+ * f(entry) runs for this lane's slots 0 .. deg - 1; the next slot's load is in flight meanwhile. Every lane of the
+ * wavefront must call (deg = 0 for the lanes past the last point). */
+struct BaStreamPos { int base, deg; int4 first; }; /* where a lane's walk starts: ba_stream_begin */
+template <class F>
+__device__ __forceinline__ void ba_stream_walk(const int4* __restrict__ S, const BaStreamPos& sp, F f) {
+    const int deg = sp.deg;
+    int base = sp.base;
+    unsigned long long m = __ballot(0 < deg);
+    int4 rn = sp.first;
+    for (int j = 0; m != 0; j++) { /* wave-uniform trip count: the block's largest degree */
+        const int4 r = rn;
+        const unsigned long long mn = __ballot(j + 1 < deg);
+        const int idx = tbm::ba_stream_slot_self(mn, &base);
+        if (j + 1 < deg) rn = S[idx];
+        if (j < deg) f(r);
+        m = mn;
+    }
+}
+/* the same walk for a light f: N slots' loads in flight together, then their N calls (one memory latency per N slots where the
+ * walk above has one per slot unless f covers it) */
+template <int N, class F>
+__device__ __forceinline__ void ba_stream_walk_batched(const int4* __restrict__ S, const BaStreamPos& sp, F f) {
+    const int deg = sp.deg;
+    int base = sp.base - __popcll(__ballot(0 < deg)); /* sp.base is slot 1's: back to slot 0 */
+    for (int j0 = 0; __ballot(j0 < deg) != 0; j0 += N) {
+        int4 r[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const unsigned long long m = __ballot(j0 + i < deg);
+            const int idx = tbm::ba_stream_slot_self(m, &base);
+            r[i] = make_int4(0, 0, 0, 0);
+            if (j0 + i < deg) r[i] = S[idx];
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++)
+            if (j0 + i < deg) f(r[i]);
+    }
+}
+/* Start of the walk of point p (any p >= 0; every lane of the wavefront calls): this lane's degree, its slot-0 entry -- the load
+ * is issued here, so a pass calls this before it waits for its state and poses -- and the first entry of slot 1. The tables are
+ * complete and in range for every window, also one that k_ba_setup rejects. */
+__device__ __forceinline__ BaStreamPos ba_stream_begin(const BaDims& d, const int* __restrict__ I, int p) {
+    BaStreamPos sp;
+    sp.base = I[d.oPtStart + min(p & ~63, d.npt)];
+    sp.deg = (p < d.npt) ? I[d.oPtStart + p + 1] - I[d.oPtStart + p] : 0;
+    sp.first = make_int4(0, 0, 0, 0);
+    const int idx = tbm::ba_stream_slot_self(__ballot(0 < sp.deg), &sp.base);
+    if (0 < sp.deg) sp.first = reinterpret_cast<const int4*>(I + d.oFreeKP)[idx];
+    return sp;
+}
+
 /* U^T bl of a point record (zero for a block that was not positive definite: U is zero then) */
 __device__ __forceinline__ void ba_rec_utb(const double* q, double* t) {
     t[0] = q[0] * q[6];
@@ -384,7 +462,9 @@ __device__ __forceinline__ void ba_rec_utb(const double* q, double* t) {
     t[2] = q[2] * q[6] + q[4] * q[7] + q[5] * q[8];
 }
 
-/* ---- A: point pass */
+/* ---- A: point pass (STREAM: the window's observations come from the stream, d.stream; a template parameter so that each
+ * form keeps its own register count) */
+template <bool STREAM>
 __device__ __forceinline__ void ba_points_pass(const BaDims& d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw,
                                                BaState* __restrict__ states, const int* __restrict__ errflag, int bx, int w) {
     __shared__ double red[4];
@@ -393,14 +473,17 @@ __device__ __forceinline__ void ba_points_pass(const BaDims& d, const tb_ba_obs*
      * CUs beside the extractor's workgroups, which leave ~10 KB of LDS free */
     extern __shared__ __attribute__((aligned(16))) double sRt[];
     const int tid = threadIdx.x;
+    double* D = dw + (size_t)w * d.wstride;
+    const int* I = iw + (size_t)w * d.istride;
+    const int p = bx * BA_T + tid;
+    BaStreamPos sp;
+    if (STREAM) sp = ba_stream_begin(d, I, p); /* in flight beside the flag, the state and the poses */
     if (errflag[w]) { /* k_ba_setup rejected the window's observations: nothing may index with them */
         if (bx == 0 && tid == 0) { states[w].status = 1; states[w].err = 1; }
         return;
     }
     const BaState st = states[w];
     if (st.status) return;
-    double* D = dw + (size_t)w * d.wstride;
-    const int* I = iw + (size_t)w * d.istride;
     /* lambda of this trial is final unless it is the first one (k_ba_reduce derives it from the keyframe pass; k_ba_hinv then
      * writes the point records from the stored blocks). After a rejected step (need_lin == 0: same state, new lambda) the pass
      * simply runs again -- the same blocks, records for the new lambda -- so the blocks themselves are only stored in the
@@ -412,33 +495,42 @@ __device__ __forceinline__ void ba_points_pass(const BaDims& d, const tb_ba_obs*
     for (int k = tid; k < d.nkf; k += BA_T) ba_pose_to_Rt(T + k * 7, sRt + k * 12);
     __syncthreads();
     const double delta = (double)sqrtf(5.991f);
-    const int p = bx * BA_T + tid;
+    const bool in = p < d.npt;
     double chi = 0, maxd = 0;
-    if (p < d.npt) {
-        double Hll[6] = {0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
-        const double X[3] = {P[3 * p], P[3 * p + 1], P[3 * p + 2]};
+    double Hll[6] = {0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0}, X[3] = {0, 0, 0};
+    if (in) { X[0] = P[3 * p]; X[1] = P[3 * p + 1]; X[2] = P[3 * p + 2]; }
+    auto edge = [&](int kf, float ou, float ov, float ow) {
+        BaLin L;
+        ba_linearize(sRt + kf * 12, X, ou, ov, ow, d.fx, d.fy, d.cx, d.cy, delta, L);
+        const double ww = L.ww, e0 = L.e0, e1 = L.e1;
+        const double* Jl = L.Jl;
+        chi += ba_huber_rho0(L.c2, delta);
+        for (int a = 0; a < 3; a++) bl[a] = fma(-ww, fma(Jl[a], e0, Jl[3 + a] * e1), bl[a]);
+        Hll[0] = fma(ww, fma(Jl[0], Jl[0], Jl[3] * Jl[3]), Hll[0]);
+        Hll[1] = fma(ww, fma(Jl[0], Jl[1], Jl[3] * Jl[4]), Hll[1]);
+        Hll[2] = fma(ww, fma(Jl[0], Jl[2], Jl[3] * Jl[5]), Hll[2]);
+        Hll[3] = fma(ww, fma(Jl[1], Jl[1], Jl[4] * Jl[4]), Hll[3]);
+        Hll[4] = fma(ww, fma(Jl[1], Jl[2], Jl[4] * Jl[5]), Hll[4]);
+        Hll[5] = fma(ww, fma(Jl[2], Jl[2], Jl[5] * Jl[5]), Hll[5]);
+    };
+    if (STREAM) {
+        ba_stream_walk(reinterpret_cast<const int4*>(I + d.oFreeKP), sp,
+                       [&](const int4& r) { edge(r.x, __int_as_float(r.y), __int_as_float(r.z), __int_as_float(r.w)); });
+    } else if (in) {
         const int eBeg = I[d.oPtStart + p], eEnd = I[d.oPtStart + p + 1];
         tb_ba_obs on = obs[min(eBeg, d.obs_pitch - 1)]; /* the next observation is in flight while this one is linearised */
         for (int e = eBeg; e < eEnd; e++) {
             const tb_ba_obs o = on;
             on = obs[min(e + 1, d.obs_pitch - 1)];
-            BaLin L;
-            ba_linearize(sRt + o.kf * 12, X, o.u, o.v, o.inv_sigma2, d.fx, d.fy, d.cx, d.cy, delta, L);
-            const double ww = L.ww, e0 = L.e0, e1 = L.e1;
-            const double* Jl = L.Jl;
-            chi += ba_huber_rho0(L.c2, delta);
-            for (int a = 0; a < 3; a++) bl[a] = fma(-ww, fma(Jl[a], e0, Jl[3 + a] * e1), bl[a]);
-            Hll[0] = fma(ww, fma(Jl[0], Jl[0], Jl[3] * Jl[3]), Hll[0]);
-            Hll[1] = fma(ww, fma(Jl[0], Jl[1], Jl[3] * Jl[4]), Hll[1]);
-            Hll[2] = fma(ww, fma(Jl[0], Jl[2], Jl[3] * Jl[5]), Hll[2]);
-            Hll[3] = fma(ww, fma(Jl[1], Jl[1], Jl[4] * Jl[4]), Hll[3]);
-            Hll[4] = fma(ww, fma(Jl[1], Jl[2], Jl[4] * Jl[5]), Hll[4]);
-            Hll[5] = fma(ww, fma(Jl[2], Jl[2], Jl[5] * Jl[5]), Hll[5]);
+            edge(o.kf, o.u, o.v, o.inv_sigma2);
         }
+    }
+    if (in) {
         if (!lam_known) {
             for (int a = 0; a < 6; a++) D[d.oHll + (size_t)p * 6 + a] = Hll[a];
             for (int a = 0; a < 3; a++) D[d.oBl + (size_t)p * 3 + a] = bl[a];
-        } else ba_write_rec(D + d.oHq + (size_t)I[d.oPtRank + p] * 12, Hll, bl, X, st.lambda, states + w); /* lambda of this trial is final; records sit in pattern order */
+        } else /* lambda of this trial is final; records sit in pattern order (renumbered windows: the point order) */
+            ba_write_rec(D + d.oHq + (size_t)(d.renum ? p : I[d.oPtRank + p]) * 12, Hll, bl, X, st.lambda, states + w);
         maxd = fmax(fabs(Hll[0]), fmax(fabs(Hll[3]), fabs(Hll[5])));
     }
     const double s = ba_block_sum1(chi, red);
@@ -561,10 +653,11 @@ __device__ __forceinline__ void ba_kf_pass(const BaDims& d, const tb_ba_obs* __r
 }
 
 /* ---- C: ordered reduction of the partials, lambda_0 */
+template <bool STREAM>
 __global__ void __launch_bounds__(BA_T)
 k_ba_points(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw, BaState* __restrict__ states,
             const int* __restrict__ errflag) {
-    ba_points_pass(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x, (int)blockIdx.y);
+    ba_points_pass<STREAM>(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x, (int)blockIdx.y);
 }
 __global__ void __launch_bounds__(BA_T)
 k_ba_kf(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw, const BaState* __restrict__ states,
@@ -577,13 +670,14 @@ k_ba_kf(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw,
  * 0 ..: their window-per-XCD order needs id mod 8), then the point pass's. Large batches keep two launches: the fused kernel
  * carries the keyframe pass's 32 KB of LDS in every workgroup, and the point pass's workgroups are meant to sit on CUs beside
  * the extractor's, which leave ~10 KB free (measured inside the pipeline: 17.6 against 16.6-17.0 ms per 512-frame step). */
+template <bool STREAM>
 __global__ void __launch_bounds__(BA_T)
 k_ba_lin(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw, BaState* __restrict__ states,
          const int* __restrict__ errflag, int nKfBlocks) {
     if ((int)blockIdx.x < nKfBlocks) ba_kf_pass(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x);
     else {
         const int b = (int)blockIdx.x - nKfBlocks;
-        ba_points_pass(d, obsAll, dw, iw, states, errflag, b % d.nblkP, b / d.nblkP);
+        ba_points_pass<STREAM>(d, obsAll, dw, iw, states, errflag, b % d.nblkP, b / d.nblkP);
     }
 }
 
@@ -649,7 +743,7 @@ k_ba_hinv(BaDims d, double* __restrict__ dw, const int* __restrict__ iw, BaState
     for (int i = 0; i < 6; i++) ph[i] = D[d.oHll + (size_t)p * 6 + i];
 #pragma unroll
     for (int i = 0; i < 3; i++) { pb[i] = D[d.oBl + (size_t)p * 3 + i]; X[i] = D[d.oP + ((size_t)st.cur * d.npt + p) * 3 + i]; }
-    ba_write_rec(D + d.oHq + (size_t)I[d.oPtRank + p] * 12, ph, pb, X, st.lambda, states + w);
+    ba_write_rec(D + d.oHq + (size_t)(d.renum ? p : I[d.oPtRank + p]) * 12, ph, pb, X, st.lambda, states + w);
 }
 
 /* ---- D: Schur complement S' (np x np, lower triangle) and reduced rhs, pattern-compact MFMA form (round 3).
@@ -862,6 +956,26 @@ k_ba_prepare(BaDims d, const tb_ba_obs* __restrict__ obsAll, const int32_t* __re
     }
     __threadfence_block();
     __syncthreads(); /* the copy is complete and visible to the workgroup; first[] is free */
+    if (d.stream) {
+        /* the same observations once more as the point passes' stream (ba_stream_walk): a wavefront per 64-rank block walks the
+         * block's slots exactly as the readers do and writes every slot's entries as one contiguous run. In a window that
+         * k_ba_setup rejects the copy has slots nobody wrote; they are copied as they are, no pass reads them, and every
+         * position lies inside the block's own range of ptStart. */
+        int4* S = reinterpret_cast<int4*>(I + d.oFreeKP);
+        for (int r0 = 64 * wave; r0 < d.npt; r0 += 64 * NW) {
+            const int r = r0 + lane, eBeg = (r < d.npt) ? start2[r] : 0, deg = (r < d.npt) ? start2[r + 1] - eBeg : 0;
+            int base = start2[r0];
+            for (int j = 0;; j++) {
+                const unsigned long long m = __ballot(j < deg);
+                if (m == 0) break;
+                const int idx = tbm::ba_stream_slot_self(m, &base);
+                if (j < deg) {
+                    const tb_ba_obs o = obs2[eBeg + j];
+                    S[idx] = make_int4(o.kf, __float_as_int(o.u), __float_as_int(o.v), __float_as_int(o.inv_sigma2));
+                }
+            }
+        }
+    }
     /* masks by rank (the sort is done with the old order), free-edge prefix by rank, points per pattern */
     for (int r = tid; r < d.npt; r += BA_RT) {
         const unsigned m = word[pa_[r]] & 0xffffu;
@@ -2223,7 +2337,8 @@ k_ba_solve_big(BaDims d, double* __restrict__ dw, BaState* __restrict__ states) 
     }
 }
 
-/* ---- F: point back-substitution and trial errors */
+/* ---- F: point back-substitution and trial errors (STREAM: as in the point pass) */
+template <bool STREAM>
 __global__ void __launch_bounds__(BA_T)
 k_ba_update(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw,
             const BaState* __restrict__ states) {
@@ -2234,67 +2349,94 @@ k_ba_update(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__
     double* const sRtc = sdyn + (size_t)d.nkf * 12;/* [nkf][12] linearisation state */
     double* const sx = sdyn + (size_t)d.nkf * 24;  /* [np] */
     const int w = blockIdx.y, tid = threadIdx.x;
-    const BaState st = states[w];
-    if (st.status) return;
-    const tb_ba_obs* obs = obsAll + (size_t)w * d.obs_pitch;
     double* D = dw + (size_t)w * d.wstride;
     const int* I = iw + (size_t)w * d.istride;
+    const int p = blockIdx.x * BA_T + tid;
+    BaStreamPos sp;
+    if (STREAM) sp = ba_stream_begin(d, I, p); /* in flight beside the state, the poses and the increments */
+    /* the point record of this trial: A^-1 = U U^T (all zero for a singular block: xl stays 0), the gradient bl, and X at the
+     * linearisation state -- the point pass (or k_ba_hinv) stored the very doubles of P there, so P is not read again */
+    const bool in = p < d.npt;
+    double q[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    /* renumbered windows (STREAM implies d.renum): the record sits at p, an address that is in range whatever the window's
+     * state, so its load goes out beside the state's. The other windows find it through oPtRank, which k_ba_groups does not
+     * write for a window that k_ba_setup rejected: there nothing is loaded before the status says the window runs. */
+    if (STREAM && in) ba_load_rec(D + d.oHq + (size_t)p * 12, q);
+    const BaState st = states[w];
+    if (st.status) return;
+    if (!STREAM && in) ba_load_rec(D + d.oHq + (size_t)(d.renum ? p : I[d.oPtRank + p]) * 12, q);
+    const tb_ba_obs* obs = obsAll + (size_t)w * d.obs_pitch;
     const double* Tn = D + d.oT + (size_t)(st.cur ^ 1) * d.nkf * 7;
     for (int k = tid; k < d.nkf; k += BA_T) ba_pose_to_Rt(D + d.oT + ((size_t)st.cur * d.nkf + k) * 7, sRtc + k * 12);
-    const double* P = D + d.oP + (size_t)st.cur * d.npt * 3;
     double* Pn = D + d.oP + (size_t)(st.cur ^ 1) * d.npt * 3;
     for (int k = tid; k < d.nkf; k += BA_T) ba_pose_to_Rt(Tn + k * 7, sRt + k * 12);
     for (int i = tid; i < d.np; i += BA_T) sx[i] = D[d.oXp + i];
     __syncthreads();
     const double delta = (double)sqrtf(5.991f);
-    const int p = blockIdx.x * BA_T + tid;
     double chi = 0, sc = 0;
-    if (p < d.npt) {
-        /* the point record of this trial: A^-1 = U U^T (all zero for a singular block: xl stays 0), the gradient bl, X */
-        const double* q = D + d.oHq + (size_t)I[d.oPtRank + p] * 12;
-        double r[3] = {q[6], q[7], q[8]};
-        const double bl[3] = {r[0], r[1], r[2]};
-        double xl[3] = {0, 0, 0};
-        const int eBeg = I[d.oPtStart + p], eEnd = I[d.oPtStart + p + 1];
+    double r[3] = {q[6], q[7], q[8]};
+    const double bl[3] = {r[0], r[1], r[2]};
+    const double Xc[3] = {q[9], q[10], q[11]};
+    double xl[3] = {0, 0, 0}, X[3] = {0, 0, 0};
+    /* r = bl - sum_k Hpl_k^T x_k with Hpl_k = ww Jp^T Jl rebuilt from the observation (a 144-byte block per edge
+     * would cost more to fetch than its ~150 flops): Hpl^T x = ww Jl^T (Jp x) */
+    auto back = [&](int kf, float ou, float ov, float ow) {
+        if (kf < d.nfixed) return;
+        BaLin L;
+        double Jp[12];
+        ba_linearize(sRtc + kf * 12, Xc, ou, ov, ow, d.fx, d.fy, d.cx, d.cy, delta, L);
+        ba_jac_pose_iz(L.pc, L.invz, d.fx, d.fy, Jp);
+        const double* xp = sx + 6 * (kf - d.nfixed);
+        double s0 = 0, s1 = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++) { s0 = fma(Jp[a], xp[a], s0); s1 = fma(Jp[6 + a], xp[a], s1); }
+#pragma unroll
+        for (int c = 0; c < 3; c++) r[c] = fma(-L.ww, fma(L.Jl[c], s0, L.Jl[3 + c] * s1), r[c]);
+    };
+    auto step = [&]() { /* xl = U (U^T r), the trial point, the point's share of the gain's scale */
         if (st.ok2) {
             const double u00 = q[0], u01 = q[1], u02 = q[2], u11 = q[3], u12 = q[4], u22 = q[5];
-            /* r = bl - sum_k Hpl_k^T x_k with Hpl_k = ww Jp^T Jl rebuilt from the observation (a 144-byte block per edge
-             * would cost more to fetch than its ~150 flops): Hpl^T x = ww Jl^T (Jp x) */
-            const double Xc[3] = {P[3 * p], P[3 * p + 1], P[3 * p + 2]};
-            tb_ba_obs on = obs[min(eBeg, d.obs_pitch - 1)]; /* next observation in flight while this one is processed */
-            for (int e = eBeg; e < eEnd; e++) {
-                const tb_ba_obs o = on;
-                on = obs[min(e + 1, d.obs_pitch - 1)];
-                if (o.kf < d.nfixed) continue;
-                BaLin L;
-                double Jp[12];
-                ba_linearize(sRtc + o.kf * 12, Xc, o.u, o.v, o.inv_sigma2, d.fx, d.fy, d.cx, d.cy, delta, L);
-                ba_jac_pose_iz(L.pc, L.invz, d.fx, d.fy, Jp);
-                const double* xp = sx + 6 * (o.kf - d.nfixed);
-                double s0 = 0, s1 = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) { s0 = fma(Jp[a], xp[a], s0); s1 = fma(Jp[6 + a], xp[a], s1); }
-#pragma unroll
-                for (int c = 0; c < 3; c++) r[c] = fma(-L.ww, fma(L.Jl[c], s0, L.Jl[3 + c] * s1), r[c]);
-            }
             const double t0 = u00 * r[0], t1 = u01 * r[0] + u11 * r[1], t2 = u02 * r[0] + u12 * r[1] + u22 * r[2]; /* U^T r */
             xl[0] = u00 * t0 + u01 * t1 + u02 * t2;
             xl[1] = u11 * t1 + u12 * t2;
             xl[2] = u22 * t2;
         }
-        double X[3];
         for (int a = 0; a < 3; a++) {
-            X[a] = P[3 * p + a] + xl[a];
+            X[a] = Xc[a] + xl[a];
             Pn[3 * p + a] = X[a];
             sc += xl[a] * (st.lambda * xl[a] + bl[a]);
         }
+    };
+    auto trial = [&](int kf, float ou, float ov, float ow) {
+        BaLin L; /* the same residual arithmetic as the point pass: rho compares like with like */
+        ba_residual(sRt + kf * 12, X, ou, ov, ow, d.fx, d.fy, d.cx, d.cy, delta, L);
+        chi += ba_huber_rho0(L.c2, delta);
+    };
+    if (STREAM) {
+        /* both walks read the block's entries from the stream: the second finds them in the cache the first filled, and its
+         * residuals are too short to cover a load each, so it fetches BA_UPD_BATCH slots at a time (the registers are there:
+         * the kernel's count is set by the back-substitution) */
+        const int4* S = reinterpret_cast<const int4*>(I + d.oFreeKP);
+        if (st.ok2)
+            ba_stream_walk(S, sp, [&](const int4& e) { back(e.x, __int_as_float(e.y), __int_as_float(e.z), __int_as_float(e.w)); });
+        if (in) step();
+        ba_stream_walk_batched<BA_UPD_BATCH>(S, sp, [&](const int4& e) { trial(e.x, __int_as_float(e.y), __int_as_float(e.z), __int_as_float(e.w)); });
+    } else if (in) {
+        const int eBeg = I[d.oPtStart + p], eEnd = I[d.oPtStart + p + 1];
+        if (st.ok2) {
+            tb_ba_obs on = obs[min(eBeg, d.obs_pitch - 1)]; /* next observation in flight while this one is processed */
+            for (int e = eBeg; e < eEnd; e++) {
+                const tb_ba_obs o = on;
+                on = obs[min(e + 1, d.obs_pitch - 1)];
+                back(o.kf, o.u, o.v, o.inv_sigma2);
+            }
+        }
+        step();
         tb_ba_obs on2 = obs[min(eBeg, d.obs_pitch - 1)];
         for (int e = eBeg; e < eEnd; e++) {
             const tb_ba_obs o = on2;
             on2 = obs[min(e + 1, d.obs_pitch - 1)];
-            BaLin L; /* the same residual arithmetic as the point pass: rho compares like with like */
-            ba_residual(sRt + o.kf * 12, X, o.u, o.v, o.inv_sigma2, d.fx, d.fy, d.cx, d.cy, delta, L);
-            chi += ba_huber_rho0(L.c2, delta);
+            trial(o.kf, o.u, o.v, o.inv_sigma2);
         }
     }
     const double s1 = ba_block_sum1(chi, red);
@@ -2412,6 +2554,7 @@ static void ba_dims(BaDims& d, int num_cu, int peers, int W, const double K[4], 
     }
     d.big = d.nfree > BA_SMALL_MAXF;
     d.renum = (!d.big && npt <= BA_SORT_LDS && nkf <= BA_PREP_MAXKF) ? 1 : 0;
+    d.stream = d.renum;
     d.schurWaveLds = d.big ? 0 : ba_c_wave_lds(d.nfree);
     d.npairs = d.nfree * (d.nfree + 1) / 2;
     d.maxItems = (unsigned long long)obs_pitch * (d.nfree + 1) / 2 + 1; /* sum_p E_p (E_p + 1) / 2 with E_p <= nfree */
@@ -2477,6 +2620,7 @@ int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixe
     if (iters > 99) return tb_fail(ctx, TB_EUNSUPPORTED, "local BA: more than 99 LM iterations (one still-running counter per trial, 1000 of them)");
     BaDims d;
     ba_dims(d, ctx->num_cu, ctx->peers, W, K, nkf, nfixed, npt, obs_pitch, iters);
+    if (ctx->dbg_ba_plain_obs) d.stream = 0; /* test hook: the array-of-structs walk for every window (part of the graph key) */
     if (tbk_local_ba_work_bytes(ctx, W, nkf, nfixed, npt, obs_pitch) > work_bytes) return tb_fail(ctx, TB_ENOMEM, "local BA workspace too small");
     char* base = (char*)d_work;
     double* dw = (double*)base;
@@ -2538,12 +2682,12 @@ int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixe
             const int nKfBlocks = ((W + 7) / 8) * 8 * std::min(BA_KFBLK, d.kfChunks) * d.nfree;
             if (W <= 32) {
                 tb_prof_begin(ctx, "k_ba_lin");
-                hipLaunchKernelGGL(k_ba_lin, dim3(nKfBlocks + d.nblkP * W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states,
+                hipLaunchKernelGGL(d.stream ? k_ba_lin<true> : k_ba_lin<false>, dim3(nKfBlocks + d.nblkP * W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states,
                                    errflag, nKfBlocks);
                 tb_prof_end(ctx);
             } else {
                 tb_prof_begin(ctx, "k_ba_points");
-                hipLaunchKernelGGL(k_ba_points, dim3(d.nblkP, W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states, errflag);
+                hipLaunchKernelGGL(d.stream ? k_ba_points<true> : k_ba_points<false>, dim3(d.nblkP, W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states, errflag);
                 tb_prof_end(ctx);
                 tb_prof_begin(ctx, "k_ba_kf");
                 hipLaunchKernelGGL(k_ba_kf, dim3(nKfBlocks), dim3(BA_T), 0, s, d, d_obs, dw, iw, states, errflag);
@@ -2580,7 +2724,7 @@ int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixe
             tb_prof_end(ctx);
         }
         tb_prof_begin(ctx, "k_ba_update");
-        hipLaunchKernelGGL(k_ba_update, dim3(d.nblkP, W), dim3(BA_T), ((size_t)d.nkf * 24 + d.np) * sizeof(double), s, d, d_obs, dw, iw, states);
+        hipLaunchKernelGGL(d.stream ? k_ba_update<true> : k_ba_update<false>, dim3(d.nblkP, W), dim3(BA_T), ((size_t)d.nkf * 24 + d.np) * sizeof(double), s, d, d_obs, dw, iw, states);
         tb_prof_end(ctx);
         tb_prof_begin(ctx, "k_ba_decide");
         hipLaunchKernelGGL(k_ba_decide, dim3(W), dim3(64), 0, s, d, dw, states, running + round % ring);

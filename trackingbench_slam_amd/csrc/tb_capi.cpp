@@ -195,6 +195,12 @@ int tb_debug_force_dense_fast(tb_ctx* ctx, int on) {
     return TB_OK;
 }
 
+int tb_debug_ba_plain_obs(tb_ctx* ctx, int on) {
+    if (!ctx) return TB_EINVAL;
+    ctx->dbg_ba_plain_obs = on ? 1 : 0;
+    return TB_OK;
+}
+
 void tb_destroy(tb_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
@@ -872,6 +878,24 @@ int tb_descriptor_distance(const uint8_t* a, const uint8_t* b) {
         dist += __builtin_popcountll(x ^ y);
     }
     return dist;
+}
+
+int tb_ba_obs_stream_positions(const int32_t* pt_start, int npt, int32_t* pos) {
+    if (npt < 0 || !pt_start || (!pos && pt_start[npt] > 0)) return TB_EINVAL;
+    for (int r0 = 0; r0 < npt; r0 += 64) { /* one 64-point block = one wavefront of the point passes, slot by slot as they walk it */
+        int base = pt_start[r0];
+        for (int j = 0;; j++) {
+            unsigned long long m = 0;
+            for (int l = 0; l < 64 && r0 + l < npt; l++)
+                if (pt_start[r0 + l + 1] - pt_start[r0 + l] > j) m |= 1ull << l;
+            if (m == 0) break;
+            int next = base;
+            for (int l = 0; l < 64; l++)
+                if ((m >> l) & 1) { next = base; pos[pt_start[r0 + l] + j] = tbm::ba_stream_slot(m, l, &next); }
+            base = next;
+        }
+    }
+    return TB_OK;
 }
 
 void tb_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3) {

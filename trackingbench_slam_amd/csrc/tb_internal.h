@@ -44,6 +44,7 @@ struct tb_ctx {
     std::vector<std::pair<std::string, hipGraphExec_t>> ba_graphs; /* captured local-BA calls of small batches (k_ba.hip) */
     int peers = 1;      /* tb_set_concurrency: contexts expected to keep this GPU busy at the same time */
     int dbg_fast_dense = 0; /* tb_debug_force_dense_fast: every FAST block takes the any-density path (test hook) */
+    int dbg_ba_plain_obs = 0; /* tb_debug_ba_plain_obs: the local-BA point passes walk the array-of-structs observations (test hook) */
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;

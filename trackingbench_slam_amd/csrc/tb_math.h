@@ -179,5 +179,25 @@ TB_HD __attribute__((always_inline)) void kept_bins_ascending(int i1, int i2, in
     keep[0] = a < (1 << 30) ? a : -1; keep[1] = b < (1 << 30) ? b : -1; keep[2] = c < (1 << 30) ? c : -1;
 }
 
+/* Local BA, the lane-interleaved observation stream of a 64-point block (k_ba.hip, ba_stream_walk): m = the lanes that have
+ * the slot being walked, *base = the slot's first entry. Returns the entry of `lane` -- its rank among the set lanes, meaningful
+ * when its own bit is set in m -- and moves *base to the next slot. ONE rule for the kernel that writes the stream, the passes
+ * that read it and tb_ba_obs_stream_positions. */
+TB_HD __attribute__((always_inline)) int ba_stream_slot(unsigned long long m, int lane, int* base) {
+    const int idx = *base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    *base += __builtin_popcountll(m);
+    return idx;
+}
+#if defined(__HIPCC__)
+/* the same for the CALLING lane of a wavefront: its rank among the set lanes is the mask's bit count below it (v_mbcnt: two
+ * instructions, no lane mask held in registers). tests/test_gpu_ba_obs_stream.py holds the two forms against each other
+ * through the kernels: k_ba_prepare writes with this one, tb_ba_obs_stream_positions says where with the other. */
+__device__ __forceinline__ int ba_stream_slot_self(unsigned long long m, int* base) {
+    const int idx = *base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    *base += __builtin_popcountll(m);
+    return idx;
+}
+#endif
+
 }  // namespace tbm
 #endif
