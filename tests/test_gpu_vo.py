@@ -1,5 +1,7 @@
 """GPU tests of the device-resident stereo VO loop (trackingbench_slam_amd.vo.StereoVO, tb_vo_* of the C ABI) against the CPU
 composition in tests/vo_reference.py, on synthetic KITTI-geometry sequences (1241 x 376) with exact ground truth."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -17,13 +19,19 @@ SEEDS = (0, 1, 2, 3)
 GT_BOUND = 0.25   # metres at frame 20; tests/test_vo_reference.py measures the composition against it
 
 
-@pytest.fixture(scope="module")
-def seqs():
+@functools.lru_cache(maxsize=None)
+def _sequences():
+    """The module's sequences, rendered once per session (tests/test_gpu_gauge.py runs their first frames from other start poses)."""
     out = [synth_seq.sequence(s, T) for s in SEEDS]
     L = np.stack([o[0] for o in out], 1)   # [T, S, H, W]
     R = np.stack([o[1] for o in out], 1)
     G = np.stack([o[2] for o in out], 1)   # [T, S, 4, 4]
     return L, R, G
+
+
+@pytest.fixture(scope="module")
+def seqs():
+    return _sequences()
 
 
 def _dev(a):

@@ -7,6 +7,8 @@ The segment log, the window and the adoption are compared by their bits. The ref
 on the GPU's own window at the project's BA bar (tools/fuzz_parity.py): 1e-6 relative, entries near zero at 1e-6 of
 the array's largest entry -- or, for a window the CPU solver itself resolves no closer, within twice the CPU solver's own movement
 when its input points change by one ulp."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -26,10 +28,20 @@ N = EVERY + 1
 PITCH = 715
 
 
+@functools.lru_cache(maxsize=None)
+def _sequence(seed):
+    """One slow synthetic drive, rendered once per session (tests/test_gpu_gauge.py runs one more seed from other start poses)."""
+    return synth_seq.sequence(seed, T, width=W, height=H, K=K, speed=0.1)
+
+
+def _sequences(seeds):
+    out = [_sequence(s) for s in seeds]
+    return tuple(np.stack([o[i] for o in out], 1) for i in range(3))   # L, R [T, S, H, W], G [T, S, 4, 4]
+
+
 @pytest.fixture(scope="module")
 def seqs():
-    out = [synth_seq.sequence(s, T, width=W, height=H, K=K, speed=0.1) for s in SEEDS]
-    return tuple(np.stack([o[i] for o in out], 1) for i in range(3))   # L, R [T, S, H, W], G [T, S, 4, 4]
+    return _sequences(SEEDS)
 
 
 def _vo(nseq=S, **kw):
@@ -82,12 +94,15 @@ def _ba_parity(gP, gX, poses, pts, obs, prm, where):
     return dg, ds, st
 
 
-def test_step_parity_two_windows(seqs):
-    """After every step the CPU step runs from the GPU's previous state, segment included."""
+def _window_step_parity(seqs, nframes=T, min_obs=518, min_points=132):
+    """After every step the CPU step runs from the GPU's previous state, segment included. seqs: (L, R, G) of any number of
+    sequences, G[0] the start poses; min_obs / min_points: the floors every window of these drives is known to clear.
+    Returns the number of windows closed."""
     L, R, G = seqs
+    S, T = L.shape[1], nframes
     P = vr.Params(W, H, K, target=TARGET, keyframe_every=EVERY)
     prm = vw.DEFAULTS
-    vo = _vo(window_ba=True)
+    vo = _vo(S, window_ba=True)
     try:
         assert vo.key_pitch == PITCH
         vo.reset(G[0])
@@ -128,7 +143,7 @@ def test_step_parity_two_windows(seqs):
                     no = len(win["obs"])
                     assert w["obs_counts"][s] == no and w["n_points"][s] == win["n_points"], where
                     assert np.array_equal(w["obs"][s, :no], _obs_rows(win["obs"])), where
-                    assert no >= 518 and win["n_points"] >= 132, where
+                    assert no >= min_obs and win["n_points"] >= min_points, where
                     # the refined segment against the CPU solver on the GPU's own window
                     poses = np.stack([pw["poses"][s, k] for k in range(EVERY)] + [w["poses"][s, EVERY]])
                     pts = pw["points"][s]                       # all PITCH rows: pt is the key index
@@ -161,9 +176,13 @@ def test_step_parity_two_windows(seqs):
                 # the next CPU step starts from the GPU's state, segment included
                 got[s]["seg"] = _seg_of(w, s, n, t - t % EVERY)
             prev, pw = got, w
-        assert nwin == 2 * S
     finally:
         vo.close()
+    return nwin
+
+
+def test_step_parity_two_windows(seqs):
+    assert _window_step_parity(seqs) == 2 * S
 
 
 def _run(vo, L, R, G, nframes):

@@ -13,6 +13,7 @@ import pytest
 from scipy.optimize import least_squares
 
 import oracle
+import gauge_cases as gc
 from trackingbench_slam_amd import synth
 
 K = (718.856, 718.856, 607.1928, 185.2157)
@@ -82,7 +83,21 @@ def _solve(fun, x0):
 
 @pytest.mark.parametrize("seed,nkf,npt,nfixed", [(101, 4, 60, 2), (102, 6, 120, 2), (103, 5, 90, 1)])
 def test_local_ba_optimum_matches_scipy(seed, nkf, npt, nfixed):
+    _local_ba_vs_scipy(seed, nkf, npt, nfixed, None)
+
+
+def test_local_ba_optimum_matches_scipy_gauged():
+    """The first window in the y180 world gauge (tests/gauge_cases.py): every keyframe in the y branch of the quaternion
+    extraction, in the oracle and in _as_solver_pose. The bounds are the ungauged test's."""
+    _local_ba_vs_scipy(101, 4, 60, 2, "y180")
+
+
+def _local_ba_vs_scipy(seed, nkf, npt, nfixed, gname):
     Pt, Pi, Xt, Xi, obs = synth.ba_problem(seed, nkf, npt, K, obs_per_pt=4, noise_px=0.3, pose_noise=0.01, pt_noise=0.02)
+    if gname is not None:
+        G = gc.get(gname)
+        Pt, Pi, Xi = gc.gauge_poses(Pt, G), gc.gauge_poses(Pi, G), gc.gauge_points(Xi, G)
+        assert all(gc.quat_branch(T) == gc.GAUGE_BRANCH[gname] for T in Pi)
     # a point seen by one keyframe has a free direction (its depth) and a residual that only vanishes in the limit: LM stops
     # a few 1e-7 of the cost short of it. Keep the points that two or more keyframes see, renumbered.
     cnt = np.bincount(obs["pt"], minlength=npt)
@@ -124,10 +139,30 @@ def test_local_ba_optimum_matches_scipy(seed, nkf, npt, nfixed):
     assert np.abs((X0 + x[6 * nfree:].reshape(-1, 3))[seen] - Xo[seen]).max() < 2e-5
 
 
+# one gauge per quaternion branch. The bounds below are absolute on a float32 pose: gen2's 100 m translation alone rounds by up to
+# 3.8e-6 there, so the "w" variant takes gen2's rotation with the small translation of the 180-degree gauges.
+SCIPY_GAUGES = {"w": gc.gauge(gc.GAUGES["gen2"][:3, :3], (3, -2, 5)), "x": gc.GAUGES["x180"], "y": gc.GAUGES["y180"], "z": gc.GAUGES["z180"]}
+
+
 @pytest.mark.parametrize("seed,n,outlier_frac", [(201, 120, 0.0), (202, 400, 0.0), (203, 300, 0.12)])
 def test_pose_opt_optimum_matches_scipy(seed, n, outlier_frac):
+    _pose_opt_vs_scipy(seed, n, outlier_frac, None)
+
+
+@pytest.mark.parametrize("branch,seed,n,outlier_frac", [("w", 201, 120, 0.0), ("x", 202, 400, 0.0), ("y", 203, 300, 0.12), ("z", 201, 120, 0.0)])
+def test_pose_opt_optimum_matches_scipy_gauged(branch, seed, n, outlier_frac):
+    """The same problems in a world gauge that puts the start pose AND the optimum in the named branch of the quaternion
+    extraction (the oracle's, and _as_solver_pose's). The bounds are the ungauged test's."""
+    _pose_opt_vs_scipy(seed, n, outlier_frac, branch)
+
+
+def _pose_opt_vs_scipy(seed, n, outlier_frac, branch):
     Tt, Ti, obs = synth.pose_problem(seed, n, K, noise_px=0.3, outlier_frac=outlier_frac)
+    if branch is not None:
+        Ti, obs = gc.gauge_pose_problem(Ti, obs, SCIPY_GAUGES[branch])
+        assert gc.quat_branch(Ti) == branch
     ninl, To, outl, st = oracle.pose_opt(K, Ti, obs)
+    assert branch is None or gc.quat_branch(To) == branch
     keep = outl == 0
     assert ninl == keep.sum() and (outlier_frac > 0) == (not keep.all())
     X = np.stack([obs["X"], obs["Y"], obs["Z"]], 1).astype(np.float64)[keep]
