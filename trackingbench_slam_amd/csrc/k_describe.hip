@@ -5,11 +5,13 @@
  * coordinate rescale + level-major concatenation (:969-976).
  *
  * The reference blurs whole levels (2 x 2.48 MB of HBM traffic per 720p frame) and then gathers 512
- * taps per keypoint.  Every tap lies within 19 px of the keypoint, and the 8U blur is an exact integer
+ * taps per keypoint.  Every rotated, rounded tap lies within 18 px of the keypoint (the pattern's largest norm is
+ * |(13, 13)| = 18.385, the rotation adds three float roundings, and cv_round of anything below 18.5 is at most 18:
+ * tests/test_describe_reach_cpu.py), and the 8U blur is an exact integer
  * function of the 7x7 neighbourhood (kernel 18,34,49,55,49,34,18; (acc + 2^15) >> 16), so the blurred
- * 39x39 patch can be rebuilt bit-exactly from the 45x45 source patch that the orientation disc (radius
- * 15) needs anyway.  One wavefront per keypoint:
- *   stage 45x45 source patch in LDS (reflect-101 at level borders) -> integer moments (wave reduce) ->
+ * 37x37 patch can be rebuilt bit-exactly from the 43x43 source patch, which also holds the orientation disc
+ * (radius 15).  One wavefront per keypoint:
+ *   stage 43x43 source patch in LDS (reflect-101 at level borders) -> integer moments (wave reduce) ->
  *   fastAtan2 -> separable blur in LDS (u16 intermediate is exact: 255*257 = 65535) -> 256 rotated tests,
  *   4 x 64-lane ballots = 32 descriptor bytes.
  * No blurred level is ever written to HBM.  Roofline: HBM/L2 gather of 2 KB per keypoint (SURVEY 8d
@@ -48,11 +50,15 @@ constexpr DsDisc ds_make_disc() {
 }
 __constant__ __attribute__((aligned(16))) DsDisc c_disc = ds_make_disc();
 
-#define DS_P 45      /* source patch edge */
-#define DS_PS 84     /* source patch row stride: 21 dwords (odd) -> one-row-per-lane accesses hit distinct banks; = the h-pass row (below) */
-#define DS_B 39      /* blurred patch edge */
-#define DS_HS 42     /* h-pass row stride in u16 (21 dwords, odd) */
+#define DS_P 43      /* source patch edge: origin (kx - 21, ky - 21) */
+#define DS_PS 52     /* source patch row stride: 13 dwords (odd) -> one-row-per-lane accesses hit distinct banks; 12 are used */
+#define DS_B 37      /* blurred patch edge: centre (18, 18) */
+#define DS_CS 46     /* h-pass COLUMN stride in u16 (23 dwords, odd): the sums are stored transposed, [column][row]; rows 43..45 are slack */
 #define DS_BS 40     /* blurred patch row stride */
+/* the patch buffer's three tenants: source rows (46: the staging rounds store up to three rows past the patch), h-pass columns, blurred rows
+ * (40: the v-pass pieces store up to three rows past the patch) */
+#define DS_BUF 3408
+static_assert(DS_BUF >= 46 * DS_PS && DS_BUF >= DS_B * DS_CS * 2 && DS_BUF >= 40 * DS_BS && DS_BUF % 16 == 0, "patch buffer tenants");
 
 typedef unsigned short ds_u16x2 __attribute__((ext_vector_type(2)));
 
@@ -72,47 +78,81 @@ __device__ __forceinline__ uint32_t ds_udot2(uint32_t a, uint32_t b, uint32_t c)
     return __builtin_amdgcn_udot2(__builtin_bit_cast(ds_u16x2, a), __builtin_bit_cast(ds_u16x2, b), c, false);
 }
 
-/* horizontal 7-tap pass of one patch row held in 13 dwords, patch column 0 at byte SH: 39 exact u16 sums
- * (18,34,49,55,49,34,18; at most 255 * 257 = 65535) as two v_dot4_u32_u8 each */
+/* offset r * DS_BS + c of a steered tap from the patch centre: (r, c) = (rn(x b + y a), rn(x a - y b)), un-contracted
+ * (ORBextractor.cpp:57-62). cv_round of a coordinate (|v| < 19) is one float add: v + 1.5 * 2^23 is rounded to nearest-even at unit
+ * spacing and the sum's bit pattern is 0x4B400000 + rn(v) -- the integer v_rndne_f32 + v_cvt_i32_f32 give, from the fast issue
+ * class; the low 24 bits go into the multiply-add as they are and the constants come off once */
+__device__ __forceinline__ int ds_tap(float x, float y, float a, float b) {
+    const float r = TB_FADD(TB_FMUL(x, b), TB_FMUL(y, a)), c = TB_FSUB(TB_FMUL(x, a), TB_FMUL(y, b));
+    constexpr uint32_t M = 0x4B400000u;
+    const uint32_t br = __builtin_bit_cast(uint32_t, TB_FADD(r, 12582912.0f)), bc = __builtin_bit_cast(uint32_t, TB_FADD(c, 12582912.0f));
+    return (int)((uint32_t)__mul24((int)br, DS_BS) + bc - ((M & 0xffffffu) * DS_BS + M));
+}
+
+/* horizontal 7-tap pass of one patch row held in 12 dwords, patch column 0 at byte SH: 37 exact u16 sums
+ * (18,34,49,55,49,34,18; at most 255 * 257 = 65535) as two v_dot4_u32_u8 each, stored down the row's place in every column
+ * (out[c * DS_CS]). The K1 products of a group of outputs are issued before their K2 accumulations: a dependent v_dot4 pair
+ * back to back costs a wait state. */
 template <int SH>
 __device__ __forceinline__ void ds_hrow(const uint32_t* w, unsigned short* out) {
     constexpr uint32_t K1 = 18u | (34u << 8) | (49u << 16) | (55u << 24), K2 = 49u | (34u << 8) | (18u << 16);
-    uint32_t a[DS_B + 1];
+    constexpr int GRP = 8;
 #pragma unroll
-    for (int c = 0; c < DS_B; c++)
-        a[c] = __builtin_amdgcn_udot4(ds_window(w, c + SH + 4), K2, __builtin_amdgcn_udot4(ds_window(w, c + SH), K1, 0u, false), false);
-    a[DS_B] = 0;
+    for (int c0 = 0; c0 < DS_B; c0 += GRP) {
+        uint32_t a[GRP];
 #pragma unroll
-    for (int c = 0; c < DS_B; c += 2) *reinterpret_cast<uint32_t*>(out + c) = a[c] | (a[c + 1] << 16);
+        for (int i = 0; i < GRP; i++)
+            if (c0 + i < DS_B) a[i] = __builtin_amdgcn_udot4(ds_window(w, c0 + i + SH), K1, 0u, false);
+#pragma unroll
+        for (int i = 0; i < GRP; i++)
+            if (c0 + i < DS_B) a[i] = __builtin_amdgcn_udot4(ds_window(w, c0 + i + SH + 4), K2, a[i], false);
+#pragma unroll
+        for (int i = 0; i < GRP; i++)
+            if (c0 + i < DS_B) out[(c0 + i) * DS_CS] = (unsigned short)a[i];
+    }
 }
 
-/* vertical 7-tap pass of N outputs of one column: h[i] = u16 sums of rows r0 + i (N + 6 of them), exact 32-bit
- * accumulation as three v_dot2_u32_u16 and one multiply-add, (acc + 2^15) >> 16 saturated (the kernel sums to 257) */
+/* vertical 7-tap pass of N outputs of one column whose first h-pass row is even: P[k] = the column's u16 sums of rows
+ * (r0 + 2k, r0 + 2k + 1) as they lie in LDS, ((N - 1) >> 1) + 4 of them. The kernel is symmetric, so both output parities are
+ * four v_dot2_u32_u16 on these even-aligned pairs (exact 32-bit accumulation), (acc + 2^15) >> 16 saturated (the kernel sums
+ * to 257):
+ *   j = 2m:     P[m].(18,34) + P[m+1].(49,55) + P[m+2].(49,34) + P[m+3].(18, 0)
+ *   j = 2m + 1: P[m].( 0,18) + P[m+1].(34,49) + P[m+2].(55,49) + P[m+3].(34,18) */
 template <int N>
-__device__ __forceinline__ void ds_vcol(const uint32_t* h, uint8_t* out) {
-    constexpr uint32_t KA = 18u | (34u << 16), KB = 49u | (55u << 16), KC = 49u | (34u << 16);
-    uint32_t pr[N + 5];
+__device__ __forceinline__ void ds_vcol(const uint32_t* P, uint8_t* out) {
+    constexpr uint32_t KE[4] = {18u | (34u << 16), 49u | (55u << 16), 49u | (34u << 16), 18u};
+    constexpr uint32_t KO[4] = {18u << 16, 34u | (49u << 16), 55u | (49u << 16), 34u | (18u << 16)};
+    constexpr int GRP = 8;     /* outputs whose four dependent dots are issued stage by stage: no wait state between them */
 #pragma unroll
-    for (int i = 0; i < N + 5; i++) pr[i] = h[i] | (h[i + 1] << 16);
+    for (int j0 = 0; j0 < N; j0 += GRP) {
+        uint32_t acc[GRP];
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        uint32_t acc = 18u * h[j + 6] + (1u << 15);
-        acc = ds_udot2(pr[j], KA, acc);
-        acc = ds_udot2(pr[j + 2], KB, acc);
-        acc = ds_udot2(pr[j + 4], KC, acc);
-        out[j * DS_BS] = (uint8_t)min(acc >> 16, 255u);   /* rows past the patch land in the spare row of bl[] */
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int i = 0; i < GRP; i++) {
+                const int j = j0 + i;
+                if (j < N) acc[i] = ds_udot2(P[(j >> 1) + k], (j & 1) ? KO[k] : KE[k], k ? acc[i] : (1u << 15));
+            }
+#pragma unroll
+        for (int i = 0; i < GRP; i++)
+            if (j0 + i < N) acc[i] = min(acc[i] >> 16, 255u);
+#pragma unroll
+        for (int i = 0; i < GRP; i++)
+            if (j0 + i < N) out[(j0 + i) * DS_BS] = (uint8_t)acc[i];   /* rows past the patch land in the spare rows of bl[] */
     }
 }
 
 /* Instruction budget per keypoint (one wavefront), the quantity this kernel is bound by (~1080 vector instructions in
- * round 1, blur passes 51 % of them on 45 / 39 of the 64 lanes):
- *   staging   interior keypoints copy 45 rows as 13 aligned dwords each (the sub-dword phase of the patch is
- *             kept as a column shift), border keypoints take the per-byte reflect-101 path;
+ * round 1, blur passes 51 % of them):
+ *   staging   interior keypoints copy the patch rows as 12 aligned dwords each through a buffer resource (32-bit offsets,
+ *             out-of-range rows read zero; the sub-dword phase of the patch is kept as a column shift), border keypoints
+ *             take the per-byte reflect-101 path;
  *   moments   one lane per disc row: eight 4-byte windows against the disc's weight table, 16 v_dot4_u32_u8;
- *   h-pass    one lane per patch ROW: 13 dword reads, 39 outputs of two v_dot4_u32_u8 each (4 multiply-adds per
- *             instruction on the packed bytes), fully unrolled;
- *   v-pass    the 39 x 39 outputs over ALL lanes: columns 0-31 as two half columns of 20 rows per lane, then columns
- *             32-38 as eight 5-row pieces; u16 inputs, three v_dot2_u32_u16 + one multiply-add per output;
+ *   h-pass    one lane per patch ROW: 12 dword reads, 37 outputs of two v_dot4_u32_u8 each (4 multiply-adds per
+ *             instruction on the packed bytes), fully unrolled, stored transposed;
+ *   v-pass    the 37 x 37 outputs over ALL lanes: columns 0-31 as two column segments of 19 rows per lane (row 18 twice),
+ *             then columns 32-36 as ten 4-row pieces on 50 lanes; the operands are dword reads of row pairs, four
+ *             v_dot2_u32_u16 per output and no pairing instruction;
  *   tests     4 x 64 rotated comparisons -> 4 ballots. */
 #define DS_KPB 4     /* keypoints (wavefronts) per workgroup */
 
@@ -122,12 +162,11 @@ __global__ void __launch_bounds__(64 * DS_KPB)
 k_describe(PlanGeom g, const uint8_t* __restrict__ slab, const uint32_t* __restrict__ sel,
            const int32_t* __restrict__ selCount, tb_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
            int32_t* __restrict__ counts, int nImages, int by_image, int slotGroups) {
-    /* ONE patch buffer per keypoint, three tenants in turn: the source patch (rows of 84 bytes, 52 used), the h-pass sums (u16, the
-     * same 84-byte rows: every lane has its whole source row in registers before it stores), the blurred patch (40-byte rows from
-     * offset 0: every lane has all its h-pass operands in registers before the first store). 3.8 KB per keypoint instead of 7.7:
-     * the kernel's occupancy is bound by LDS (20 -> 32 wavefronts per CU, now the register limit). */
-    static_assert(DS_PS == DS_HS * 2, "source rows and h-pass rows share their LDS");
-    __shared__ __attribute__((aligned(16))) uint8_t buf_[DS_KPB][DS_P * DS_PS + 16];
+    /* ONE patch buffer per keypoint, three tenants in turn: the source patch (rows of 52 bytes, 48 used), the h-pass sums (u16,
+     * transposed: columns of 92 bytes), the blurred patch (40-byte rows). All of a wavefront's loads of one tenant complete before
+     * its first store of the next (ds_wave_fence). 3.4 KB per keypoint instead of 7.7 as three arrays: the kernel's occupancy was
+     * bound by LDS (20 -> 32 wavefronts per CU, now the register limit). */
+    __shared__ __attribute__((aligned(16))) uint8_t buf_[DS_KPB][DS_BUF];
     __shared__ int mom[DS_KPB][2];
     __shared__ float rot[DS_KPB][4];
     /* A workgroup = DS_KPB wavefronts = DS_KPB consecutive slots of one image, one keypoint per wavefront with its own patch
@@ -177,25 +216,24 @@ k_describe(PlanGeom g, const uint8_t* __restrict__ slab, const uint32_t* __restr
         const uint8_t* img = tb_level_ptr(g, slab, b, level, &stride);
 
         /* 1. stage the source patch: patch column c lives at LDS column c + sh */
-        const int x0 = kx - 22, y0 = ky - 22;
-        const bool interior = x0 >= 0 && y0 >= 0 && kx + 22 < G.w && ky + 22 < G.h && ((stride & 3) == 0) &&
-                              ((reinterpret_cast<uintptr_t>(img) & 3) == 0) && ((x0 & ~3) + 52 <= stride);
+        const int x0 = kx - 21, y0 = ky - 21;
+        const bool interior = x0 >= 0 && y0 >= 0 && kx + 21 < G.w && ky + 21 < G.h && ((stride & 3) == 0) &&
+                              ((reinterpret_cast<uintptr_t>(img) & 3) == 0) && ((x0 & ~3) + 48 <= stride);
         sh = interior ? (x0 & 3) : 0;
         if (interior) {
-            const int rr = (lane * 5042) >> 16, dd = lane - rr * 13; /* lane / 13: 4 rows x 13 dwords per pass, lanes 52..63 idle */
-            const uint8_t* srcp = img + (size_t)y0 * stride + (x0 & ~3) + 4 * dd;
-            uint32_t v[12];
+            /* 9 rounds of 5 rows x 12 dwords. One buffer resource per keypoint, base = the patch's first aligned dword, bounded by
+             * the end of the 12th dword of patch row 42: rows 43..45 of the last round read zero without touching memory, and
+             * the offsets are 32 bits wide. Lanes 60..63 (row 5 of a round) repeat the first dwords of the next round's first row;
+             * every lane stores what it loaded (rows 43..45 go to the buffer's slack), so neither loads nor stores need a predicate. */
+            const int rr = (lane * 5462) >> 16, dd = lane - rr * 12;     /* lane / 12 */
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint8_t*>(img) + (size_t)y0 * stride + (x0 & ~3), 0, (DS_P - 1) * stride + 48, 0x00020000);
+            const int off = rr * stride + 4 * dd;
+            uint32_t v[9];
 #pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const int r = 4 * j + rr;
-                v[j] = 0;
-                if (rr < 4 && r < DS_P) v[j] = *reinterpret_cast<const uint32_t*>(srcp + (size_t)r * stride);
-            }
+            for (int j = 0; j < 9; j++) v[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, off + 5 * j * stride, 0, 0);
 #pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const int r = 4 * j + rr;
-                if (rr < 4 && r < DS_P) *reinterpret_cast<uint32_t*>(src + r * DS_PS + 4 * dd) = v[j];
-            }
+            for (int j = 0; j < 9; j++) *reinterpret_cast<uint32_t*>(src + (5 * j + rr) * DS_PS + 4 * dd) = v[j];
         } else {
             for (int e = lane; e < DS_P * DS_P; e += 64) {
                 const int r = e / DS_P, c = e - r * DS_P;
@@ -209,8 +247,8 @@ k_describe(PlanGeom g, const uint8_t* __restrict__ slab, const uint32_t* __restr
         int m10 = 0, m01 = 0;
         if (lane < 31) {
             const int v = lane - 15, av = v < 0 ? -v : v;
-            const int o = 7 + sh;                                  /* byte of u = -15 in the row (patch column 22 - 15) */
-            const uint32_t* rw = reinterpret_cast<const uint32_t*>(src + (22 + v) * DS_PS) + (o >> 2);
+            const int o = 6 + sh;                                  /* byte of u = -15 in the row (patch column 21 - 15) */
+            const uint32_t* rw = reinterpret_cast<const uint32_t*>(src + (21 + v) * DS_PS) + (o >> 2);
             const uint4* t1 = reinterpret_cast<const uint4*>(c_disc.w1[av]);
             const uint4* tu = reinterpret_cast<const uint4*>(c_disc.wu[av]);
             const uint4 a0 = t1[0], a1 = t1[1], u0 = tu[0], u1 = tu[1];
@@ -244,34 +282,43 @@ k_describe(PlanGeom g, const uint8_t* __restrict__ slab, const uint32_t* __restr
         rot[lane][0] = angle; rot[lane][1] = a; rot[lane][2] = bsin;
     }
 
-    if (active) {
-        /* 3a. horizontal 7-tap pass, one lane per patch row (exact integers, u16 result) */
-        if (lane < DS_P) {
-            const uint32_t* rw = reinterpret_cast<const uint32_t*>(src + lane * DS_PS);
-            uint32_t w[14];
+    /* the lane's four tests (x0, y0, x1, y1): in flight across the blur passes */
+    float4 pt[4];
 #pragma unroll
-            for (int j = 0; j < 13; j++) w[j] = rw[j];
-            w[13] = 0;
-            unsigned short* out = hp + lane * DS_HS;
-            /* the sub-dword phase of the patch: four code paths with compile-time byte offsets */
-            if (sh == 0) ds_hrow<0>(w, out); else if (sh == 1) ds_hrow<1>(w, out); else if (sh == 2) ds_hrow<2>(w, out); else ds_hrow<3>(w, out);
+    for (int j = 0; j < 4; j++) pt[j] = reinterpret_cast<const float4*>(c_patternf.v)[j * 64 + lane];
+    if (active) {
+        /* 3a. horizontal 7-tap pass, one lane per patch row (exact integers, u16 result); the sums overwrite other lanes' source
+         * rows, so every lane has its row in registers first */
+        {
+            const uint32_t* rw = reinterpret_cast<const uint32_t*>(src + min(lane, DS_P - 1) * DS_PS);
+            uint32_t w[12];
+#pragma unroll
+            for (int j = 0; j < 12; j++) w[j] = rw[j];
+            ds_wave_fence();
+            if (lane < DS_P) {
+                unsigned short* out = hp + lane;
+                /* the sub-dword phase of the patch: four code paths with compile-time byte offsets */
+                if (sh == 0) ds_hrow<0>(w, out); else if (sh == 1) ds_hrow<1>(w, out); else if (sh == 2) ds_hrow<2>(w, out); else ds_hrow<3>(w, out);
+            }
         }
         ds_wave_fence();
         /* 3b. vertical pass over all 64 lanes: all operands first (the outputs overwrite them) */
         {
-            /* columns 0..31: lane = (column, upper / lower half): rows [0, 20) and [20, 39) */
-            const int c = lane & 31, r0 = 20 * (lane >> 5);
-            /* columns 32..38: lane = (column, one of eight 5-row pieces) */
-            const int cc = lane & 7, q0 = 5 * (lane >> 3);
-            const int c2 = 32 + min(cc, 6);
-            uint32_t h[26], h2[11];
+            /* columns 0..31: lane = (column, upper / lower segment): rows [0, 19) and [18, 37), 25 h-pass rows = 13 pairs each
+             * (the 26th row is weighed with 0) */
+            const int c = lane & 31, r0 = 18 * (lane >> 5);
+            /* columns 32..36: lane = (column, one of ten 4-row pieces): 10 h-pass rows = 5 pairs; lanes 50..63 repeat lane 49 */
+            const int l2 = min(lane, 49), pc = (l2 * 205) >> 10, c2 = 32 + l2 - 5 * pc, q0 = 4 * pc;     /* l2 / 5 */
+            const uint32_t* p1 = reinterpret_cast<const uint32_t*>(hp + c * DS_CS + r0);
+            const uint32_t* p2 = reinterpret_cast<const uint32_t*>(hp + c2 * DS_CS + q0);
+            uint32_t P[13], P2[5];
 #pragma unroll
-            for (int i = 0; i < 26; i++) h[i] = hp[min(r0 + i, DS_P - 1) * DS_HS + c];
+            for (int i = 0; i < 13; i++) P[i] = p1[i];
 #pragma unroll
-            for (int i = 0; i < 11; i++) h2[i] = hp[min(q0 + i, DS_P - 1) * DS_HS + c2];
+            for (int i = 0; i < 5; i++) P2[i] = p2[i];
             ds_wave_fence();
-            ds_vcol<20>(h, bl + r0 * DS_BS + c);          /* the lower half's 20th output is row 39: the spare row */
-            ds_vcol<5>(h2, bl + q0 * DS_BS + c2);         /* lanes with cc == 7 repeat column 38 (same values); rows reach 39 at most */
+            ds_vcol<19>(P, bl + r0 * DS_BS + c);
+            ds_vcol<4>(P2, bl + q0 * DS_BS + c2);         /* the last piece's rows 37..39 are the spare rows */
         }
     }
     __syncthreads();
@@ -279,25 +326,20 @@ k_describe(PlanGeom g, const uint8_t* __restrict__ slab, const uint32_t* __restr
 
     /* 4. steered BRIEF, ORBextractor.cpp:52-84 */
     const float angle = rot[wave][0], a = rot[wave][1], bsin = rot[wave][2];
-    const uint8_t* center = bl + 19 * DS_BS + 19;
+    const uint8_t* center = bl + 18 * DS_BS + 18;
     const size_t out = (size_t)b * g.selCap + base + idx;
     unsigned long long* d64 = reinterpret_cast<unsigned long long*>(desc + out * 32);
-    const float4* pat = reinterpret_cast<const float4*>(c_patternf.v);
+    unsigned long long bits[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const float4 pt = pat[j * 64 + lane];
-        const float x0f = pt.x, y0f = pt.y, x1f = pt.z, y1f = pt.w;
-        const int r0 = tbm::cv_round(TB_FADD(TB_FMUL(x0f, bsin), TB_FMUL(y0f, a)));
-        const int c0 = tbm::cv_round(TB_FSUB(TB_FMUL(x0f, a), TB_FMUL(y0f, bsin)));
-        const int r1 = tbm::cv_round(TB_FADD(TB_FMUL(x1f, bsin), TB_FMUL(y1f, a)));
-        const int c1 = tbm::cv_round(TB_FSUB(TB_FMUL(x1f, a), TB_FMUL(y1f, bsin)));
-        const int t0 = center[r0 * DS_BS + c0], t1 = center[r1 * DS_BS + c1];
-        const unsigned long long bits = __ballot(t0 < t1);
-        if (lane == 0) d64[j] = bits;
+        const int t0 = center[ds_tap(pt[j].x, pt[j].y, a, bsin)], t1 = center[ds_tap(pt[j].z, pt[j].w, a, bsin)];
+        bits[j] = __ballot(t0 < t1);
     }
 
-    /* 5. keypoint record; coordinates scaled by sf[level] for level != 0 (ORBextractor.cpp:969-974) */
+    /* 5. descriptor and keypoint record; coordinates scaled by sf[level] for level != 0 (ORBextractor.cpp:969-974) */
     if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) d64[j] = bits[j];
         tb_keypoint kp;
         kp.x = (float)kx;
         kp.y = (float)ky;
