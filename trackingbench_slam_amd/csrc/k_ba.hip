@@ -2598,12 +2598,168 @@ static void ba_dims(BaDims& d, int num_cu, int peers, int W, const double K[4], 
     d.istride = io;
 }
 
-size_t tbk_local_ba_work_bytes(const tb_ctx* ctx, int W, int nkf, int nfixed, int npt, int obs_pitch) {
+/* ---- the host side. One call is planned once (BaPlan: shapes, workspace pointers, kernels, LDS sizes); the head and the
+ * trials are queued from the plan, directly or through a captured graph. */
+#define BA_RING 1000 /* still-running counters: one per trial (the host refuses calls that could run more) */
+
+struct BaPlan {
     BaDims d;
+    /* the caller's arrays */
+    float *poses, *pts;
+    const tb_ba_obs* obs_in;
+    const int32_t* counts;
+    void* work;
+    /* the workspace, in this order: per-window doubles and ints, the LM states, one still-running counter per trial (no
+     * memset node between the trials), one rejected-input flag per window (zeroed together with the counters before the
+     * set-up kernel) and, for renumbered windows, the observations with the points in pattern order, laid out as the
+     * caller's array */
+    double* dw;
+    int* iw;
+    BaState* states;
+    int *running, *errflag;
+    tb_ba_obs* obs2;
+    size_t work_bytes;
+    const tb_ba_obs* obs; /* what the passes walk: obs2 for renumbered windows, else the caller's array */
+    /* the template instances this shape runs, and the dynamic LDS of the kernels that size it by the window */
+    decltype(&k_ba_schur_c<1>) schur;
+    decltype(&k_ba_solve<16>) solve;
+    decltype(&k_ba_lin<true>) lin;
+    decltype(&k_ba_points<true>) points;
+    decltype(&k_ba_update<true>) update;
+    size_t prepare_lds, pass_lds, schur_lds, big_lds, update_lds;
+};
+
+static BaPlan ba_plan(const tb_ctx* ctx, int W, const double K[4], int nkf, int nfixed, int npt, int obs_pitch, int iters, float* d_poses,
+                      float* d_pts, const tb_ba_obs* d_obs, const int32_t* d_counts, void* d_work) {
+    BaPlan p;
+    BaDims& d = p.d;
+    ba_dims(d, ctx->num_cu, ctx->peers, W, K, nkf, nfixed, npt, obs_pitch, iters);
+    if (ctx->dbg_ba_plain_obs) d.stream = 0; /* test hook: the array-of-structs walk for every window (part of the graph key) */
+    p.poses = d_poses; p.pts = d_pts; p.obs_in = d_obs; p.counts = d_counts; p.work = d_work;
+    /* The layout, said once: the regions follow each other from d_work, and the total is what they add up to. An aligned
+     * region starts at the next multiple of its alignment in the caller's address space, so the total counts the whole
+     * alignment for it. */
+    uintptr_t at = (uintptr_t)d_work;
+    size_t total = 0;
+    auto take = [&](size_t bytes, size_t align) {
+        at = (at + align - 1) / align * align;
+        const uintptr_t r = at;
+        at += bytes;
+        total += bytes + (align > 1 ? align : 0);
+        return r;
+    };
+    p.dw = (double*)take((size_t)W * d.wstride * sizeof(double), 1);
+    p.iw = (int*)take((size_t)W * d.istride * sizeof(int), 1);
+    p.states = (BaState*)take((size_t)W * sizeof(BaState), 1);
+    p.running = (int*)take(BA_RING * sizeof(int), 1);
+    p.errflag = (int*)take((size_t)W * sizeof(int), 1);
+    p.obs2 = d.renum ? (tb_ba_obs*)take((size_t)W * obs_pitch * sizeof(tb_ba_obs), 64) : nullptr;
+    p.work_bytes = total + 96; /* callers size their buffers by this value: the 96 spare bytes it has always had stay */
+    p.obs = d.renum ? p.obs2 : d_obs;
+    const int R = (d.np + 15) >> 4;
+    p.schur = R == 1 ? k_ba_schur_c<1> : R == 2 ? k_ba_schur_c<2> : R == 3 ? k_ba_schur_c<3> : k_ba_schur_c<4>;
+    p.solve = d.np <= 16 ? k_ba_solve<16> : d.np <= 32 ? k_ba_solve<32> : d.np <= 48 ? k_ba_solve<48> : k_ba_solve<64>;
+    p.lin = d.stream ? k_ba_lin<true> : k_ba_lin<false>;
+    p.points = d.stream ? k_ba_points<true> : k_ba_points<false>;
+    p.update = d.stream ? k_ba_update<true> : k_ba_update<false>;
+    p.prepare_lds = (size_t)npt * 16 + 16;
+    p.pass_lds = (size_t)d.nkf * 12 * sizeof(double);
+    /* Schur kernel: four wavefronts' tiles (small batches reuse them for the 64 x 64 sum of the wavefronts' systems) */
+    p.schur_lds = std::max<size_t>(4 * (size_t)d.schurWaveLds, d.wgReduce ? 64 * 64 : 0) * sizeof(double);
+    p.big_lds = (size_t)(d.np + 1) * BA_PLD * sizeof(double);
+    p.update_lds = ((size_t)d.nkf * 24 + d.np) * sizeof(double);
+    return p;
+}
+
+size_t tbk_local_ba_work_bytes(const tb_ctx* ctx, int W, int nkf, int nfixed, int npt, int obs_pitch) {
     const double K[4] = {1, 1, 0, 0};
-    ba_dims(d, ctx->num_cu, ctx->peers, W, K, nkf, nfixed, npt, obs_pitch, 1);
-    return (size_t)W * (d.wstride * sizeof(double) + d.istride * sizeof(int) + sizeof(BaState) + sizeof(int)) + 4096 +
-           (d.renum ? (size_t)W * obs_pitch * sizeof(tb_ba_obs) + 64 : 0);
+    return ba_plan(ctx, W, K, nkf, nfixed, npt, obs_pitch, 1, nullptr, nullptr, nullptr, nullptr, nullptr).work_bytes;
+}
+
+/* once per call: LM state, CSR tables, pattern groups (block-pair lists for large windows) */
+static int ba_enqueue_head(tb_ctx* ctx, const BaPlan& p) {
+    const BaDims& d = p.d;
+    const int W = d.W;
+    /* a kernel, not hipMemsetAsync: as a memset NODE of a replayed graph the fill came back as stale pointer-sized
+     * values on one of three contexts replaying from their own host threads (ROCm 7.2), the windows then read a set
+     * rejected-input flag and returned their input */
+    TB_TRY(tb_launch(ctx, nullptr, k_ba_zero, dim3((BA_RING + W + 255) / 256), dim3(256), 0, p.running, BA_RING + W));
+    if (d.renum) TB_TRY(tb_launch(ctx, "k_ba_prepare", k_ba_prepare, dim3(W), dim3(BA_RT), p.prepare_lds, d, p.obs_in, p.counts, p.iw, p.obs2));
+    TB_TRY(tb_launch(ctx, "k_ba_setup", k_ba_setup, dim3(d.nkf + 2, W), dim3(BA_T), 0, d, p.poses, p.pts, p.obs_in, p.obs, p.counts, p.dw, p.iw,
+                     p.states, p.errflag));
+    if (d.renum) {
+        /* k_ba_prepare did it */
+    } else if (!d.big) {
+        TB_TRY(tb_launch(ctx, "k_ba_groups", k_ba_groups, dim3(W), dim3(BA_T), 0, d, p.iw, p.errflag));
+    } else {
+        /* block-pair item lists of the large-window Schur kernel: count, scan, fill -- one profile record over the three */
+        tb_prof_begin(ctx, "k_ba_pairs");
+        TB_TRY(tb_launch(ctx, nullptr, k_ba_pairs<false>, dim3(d.nfree, W), dim3(64), 0, d, p.obs, p.iw, p.errflag));
+        TB_TRY(tb_launch(ctx, nullptr, k_ba_pair_scan, dim3(W), dim3(BA_T), 0, d, p.iw, p.errflag));
+        TB_TRY(tb_launch(ctx, nullptr, k_ba_pairs<true>, dim3(d.nfree, W), dim3(64), 0, d, p.obs, p.iw, p.errflag));
+        tb_prof_end(ctx);
+    }
+    return TB_OK;
+}
+
+/* one LM trial of every window: eight launches */
+static int ba_enqueue_round(tb_ctx* ctx, const BaPlan& p, int round) {
+    const BaDims& d = p.d;
+    const int W = d.W;
+    const int nKfBlocks = ((W + 7) / 8) * 8 * std::min(BA_KFBLK, d.kfChunks) * d.nfree;
+    if (W <= 32) {
+        TB_TRY(tb_launch(ctx, "k_ba_lin", p.lin, dim3(nKfBlocks + d.nblkP * W), dim3(BA_T), p.pass_lds, d, p.obs, p.dw, p.iw, p.states, p.errflag,
+                         nKfBlocks));
+    } else {
+        TB_TRY(tb_launch(ctx, "k_ba_points", p.points, dim3(d.nblkP, W), dim3(BA_T), p.pass_lds, d, p.obs, p.dw, p.iw, p.states, p.errflag));
+        TB_TRY(tb_launch(ctx, "k_ba_kf", k_ba_kf, dim3(nKfBlocks), dim3(BA_T), 0, d, p.obs, p.dw, p.iw, p.states, p.errflag));
+    }
+    const bool reduce_in_solve = !d.big && round > 0;
+    if (!reduce_in_solve) TB_TRY(tb_launch(ctx, "k_ba_reduce", k_ba_reduce, dim3(W), dim3(BA_T), 0, d, p.dw, p.iw, p.states));
+    if (round == 0) /* the first trial's lambda comes out of k_ba_reduce; later ones are known to k_ba_points */
+        TB_TRY(tb_launch(ctx, "k_ba_hinv", k_ba_hinv, dim3(d.nblkP, W), dim3(BA_T), 0, d, p.dw, p.iw, p.states));
+    if (d.big) {
+        TB_TRY(tb_launch(ctx, "k_ba_schur_pairs", k_ba_schur_pairs, dim3((d.npairs + 3) / 4, W), dim3(BA_T), 0, d, p.dw, p.iw, p.states));
+        TB_TRY(tb_launch(ctx, "k_ba_solve_big", k_ba_solve_big, dim3(W), dim3(BA_ST), p.big_lds, d, p.dw, p.states));
+    } else {
+        TB_TRY(tb_launch(ctx, "k_ba_schur", p.schur, dim3(d.wgReduce ? d.Gbase * W + d.Gextra : (d.Vbase * W + d.Vextra + 3) / 4), dim3(BA_T),
+                         p.schur_lds, d, p.dw, p.iw, p.states));
+        TB_TRY(tb_launch(ctx, "k_ba_solve", p.solve, dim3(W), dim3(BA_SOLVE_T), 0, d, p.dw, p.iw, p.states, reduce_in_solve ? 1 : 0));
+    }
+    TB_TRY(tb_launch(ctx, "k_ba_update", p.update, dim3(d.nblkP, W), dim3(BA_T), p.update_lds, d, p.obs, p.dw, p.iw, p.states));
+    return tb_launch(ctx, "k_ba_decide", k_ba_decide, dim3(W), dim3(64), 0, d, p.dw, p.states, p.running + round % BA_RING);
+}
+
+/* The head and the first nfirst trials as one graph, from the context's cache or captured now. The kernels read their state
+ * from the workspace, so a graph per (shape, buffers, stream) is the same every time it is replayed. */
+static int ba_graph(tb_ctx* ctx, const BaPlan& p, int nfirst, hipGraphExec_t* exec) {
+    struct Key { BaDims d; const void *poses, *pts, *obs, *counts, *work; hipStream_t s; } key;
+    memset(&key, 0, sizeof key);
+    key.d = p.d; key.poses = p.poses; key.pts = p.pts; key.obs = p.obs_in; key.counts = p.counts; key.work = p.work; key.s = ctx->stream;
+    const std::string kb((const char*)&key, sizeof key);
+    for (auto& g : ctx->ba_graphs)
+        if (g.first == kb) { *exec = g.second; return TB_OK; }
+    /* one capture at a time in the process: the pipeline drives its BA partitions from one host thread each, and
+     * three threads capturing on three streams at once produced graphs that did not replay the call (wrong poses,
+     * no error) -- a capture is rare (once per shape and buffer set), so it simply takes a lock */
+    static std::mutex capture_lock;
+    std::lock_guard<std::mutex> guard(capture_lock);
+    hipGraph_t graph = nullptr;
+    TB_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    int rc = ba_enqueue_head(ctx, p);
+    for (int r = 0; r < nfirst && rc == TB_OK; r++) rc = ba_enqueue_round(ctx, p, r);
+    const hipError_t e = hipStreamEndCapture(ctx->stream, &graph); /* always ends the capture, also after a failed launch */
+    if (rc != TB_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+    TB_HIP(ctx, e);
+    const hipError_t e2 = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    TB_HIP(ctx, e2);
+    if (ctx->ba_graphs.size() >= 8) { /* a caller cycling through more buffer sets than this re-captures */
+        hipGraphExecDestroy(ctx->ba_graphs.front().second);
+        ctx->ba_graphs.erase(ctx->ba_graphs.begin());
+    }
+    ctx->ba_graphs.emplace_back(kb, *exec);
+    return TB_OK;
 }
 
 int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixed, float* d_poses, int npt, float* d_pts,
@@ -2618,178 +2774,44 @@ int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixe
     if (nfree > BA_SMALL_MAXF && (unsigned long long)obs_pitch * (nfree + 1) >= (1ull << 31))
         return tb_fail(ctx, TB_EUNSUPPORTED, "local BA: large window with more than 2^31 / (free keyframes + 1) observations");
     if (iters > 99) return tb_fail(ctx, TB_EUNSUPPORTED, "local BA: more than 99 LM iterations (one still-running counter per trial, 1000 of them)");
-    BaDims d;
-    ba_dims(d, ctx->num_cu, ctx->peers, W, K, nkf, nfixed, npt, obs_pitch, iters);
-    if (ctx->dbg_ba_plain_obs) d.stream = 0; /* test hook: the array-of-structs walk for every window (part of the graph key) */
-    if (tbk_local_ba_work_bytes(ctx, W, nkf, nfixed, npt, obs_pitch) > work_bytes) return tb_fail(ctx, TB_ENOMEM, "local BA workspace too small");
-    char* base = (char*)d_work;
-    double* dw = (double*)base;
-    int* iw = (int*)(base + (size_t)W * d.wstride * sizeof(double));
-    BaState* states = (BaState*)((char*)iw + (size_t)W * d.istride * sizeof(int));
-    int* running = (int*)((char*)states + (size_t)W * sizeof(BaState));
+    const BaPlan p = ba_plan(ctx, W, K, nkf, nfixed, npt, obs_pitch, iters, d_poses, d_pts, d_obs, d_counts, d_work);
+    const BaDims& d = p.d;
+    if (p.work_bytes > work_bytes) return tb_fail(ctx, TB_ENOMEM, "local BA workspace too small");
     hipStream_t s = ctx->stream;
-    /* Schur kernel: four wavefronts' tiles (small batches reuse them for the 64 x 64 sum of the wavefronts' systems) */
-    const size_t schur_lds = std::max<size_t>(4 * (size_t)d.schurWaveLds, d.wgReduce ? 64 * 64 : 0) * sizeof(double);
-    /* behind the states: one still-running counter per round (no memset node between the rounds), then one
-     * rejected-input flag per window; zeroed together before the setup kernel */
-    const int ring = 1000;
-    int* errflag = running + ring;
-    /* behind those (renum): the observations with the points renumbered in pattern order, the layout of the caller's array */
-    tb_ba_obs* obs2 = (tb_ba_obs*)(((uintptr_t)(errflag + W) + 63) & ~(uintptr_t)63);
-    const tb_ba_obs* d_obs_in = d_obs;
-    if (d.renum) d_obs = obs2;
-    const size_t big_lds = (size_t)(d.np + 1) * BA_PLD * sizeof(double);
-    const int R = (d.np + 15) >> 4;
-    typedef void (*schur_t)(BaDims, double*, const int*, BaState*);
-    const schur_t ks = R == 1 ? (schur_t)k_ba_schur_c<1> : R == 2 ? (schur_t)k_ba_schur_c<2> : R == 3 ? (schur_t)k_ba_schur_c<3> : (schur_t)k_ba_schur_c<4>;
-    if (!d.big) TB_HIP(ctx, hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_lds));
-    if (d.renum) TB_HIP(ctx, hipFuncSetAttribute((const void*)k_ba_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, npt * 16 + 16));
-    else TB_HIP(ctx, hipFuncSetAttribute((const void*)k_ba_solve_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)big_lds));
-    /* once per call: LM state, CSR tables, pattern groups (block-pair lists for large windows) */
-    auto enqueue_head = [&]() -> int {
-        /* a kernel, not hipMemsetAsync: as a memset NODE of a replayed graph the fill came back as stale pointer-sized
-         * values on one of three contexts replaying from their own host threads (ROCm 7.2), the windows then read a set
-         * rejected-input flag and returned their input */
-        hipLaunchKernelGGL(k_ba_zero, dim3((ring + W + 255) / 256), dim3(256), 0, s, running, ring + W);
-        if (d.renum) {
-            tb_prof_begin(ctx, "k_ba_prepare");
-            hipLaunchKernelGGL(k_ba_prepare, dim3(W), dim3(BA_RT), (size_t)npt * 16 + 16, s, d, d_obs_in, d_counts, iw, obs2);
-            tb_prof_end(ctx);
-        }
-        tb_prof_begin(ctx, "k_ba_setup");
-        hipLaunchKernelGGL(k_ba_setup, dim3(nkf + 2, W), dim3(BA_T), 0, s, d, d_poses, d_pts, d_obs_in, d_obs, d_counts, dw, iw, states, errflag);
-        tb_prof_end(ctx);
-        if (d.renum) {
-            /* k_ba_prepare did it */
-        } else if (!d.big) {
-            tb_prof_begin(ctx, "k_ba_groups");
-            hipLaunchKernelGGL(k_ba_groups, dim3(W), dim3(BA_T), 0, s, d, iw, errflag);
-            tb_prof_end(ctx);
-        } else {
-            /* block-pair item lists of the large-window Schur kernel: count, scan, fill */
-            tb_prof_begin(ctx, "k_ba_pairs");
-            hipLaunchKernelGGL(k_ba_pairs<false>, dim3(d.nfree, W), dim3(64), 0, s, d, d_obs, iw, errflag);
-            hipLaunchKernelGGL(k_ba_pair_scan, dim3(W), dim3(BA_T), 0, s, d, iw, errflag);
-            hipLaunchKernelGGL(k_ba_pairs<true>, dim3(d.nfree, W), dim3(64), 0, s, d, d_obs, iw, errflag);
-            tb_prof_end(ctx);
-        }
-        TB_HIP(ctx, hipGetLastError());
-        return TB_OK;
-    };
-    /* one LM trial of every window: eight launches */
-    auto enqueue_round = [&](int round) -> int {
-        {
-            const int nKfBlocks = ((W + 7) / 8) * 8 * std::min(BA_KFBLK, d.kfChunks) * d.nfree;
-            if (W <= 32) {
-                tb_prof_begin(ctx, "k_ba_lin");
-                hipLaunchKernelGGL(d.stream ? k_ba_lin<true> : k_ba_lin<false>, dim3(nKfBlocks + d.nblkP * W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states,
-                                   errflag, nKfBlocks);
-                tb_prof_end(ctx);
-            } else {
-                tb_prof_begin(ctx, "k_ba_points");
-                hipLaunchKernelGGL(d.stream ? k_ba_points<true> : k_ba_points<false>, dim3(d.nblkP, W), dim3(BA_T), (size_t)d.nkf * 12 * sizeof(double), s, d, d_obs, dw, iw, states, errflag);
-                tb_prof_end(ctx);
-                tb_prof_begin(ctx, "k_ba_kf");
-                hipLaunchKernelGGL(k_ba_kf, dim3(nKfBlocks), dim3(BA_T), 0, s, d, d_obs, dw, iw, states, errflag);
-                tb_prof_end(ctx);
-            }
-        }
-        const bool reduce_in_solve = !d.big && round > 0;
-        if (!reduce_in_solve) {
-            tb_prof_begin(ctx, "k_ba_reduce");
-            hipLaunchKernelGGL(k_ba_reduce, dim3(W), dim3(BA_T), 0, s, d, dw, iw, states);
-            tb_prof_end(ctx);
-        }
-        if (round == 0) { /* the first trial's lambda comes out of k_ba_reduce; later ones are known to k_ba_points */
-            tb_prof_begin(ctx, "k_ba_hinv");
-            hipLaunchKernelGGL(k_ba_hinv, dim3(d.nblkP, W), dim3(BA_T), 0, s, d, dw, iw, states);
-            tb_prof_end(ctx);
-        }
-        if (d.big) {
-            tb_prof_begin(ctx, "k_ba_schur_pairs");
-            hipLaunchKernelGGL(k_ba_schur_pairs, dim3((d.npairs + 3) / 4, W), dim3(BA_T), 0, s, d, dw, iw, states);
-            tb_prof_end(ctx);
-            tb_prof_begin(ctx, "k_ba_solve_big");
-            hipLaunchKernelGGL(k_ba_solve_big, dim3(W), dim3(BA_ST), big_lds, s, d, dw, states);
-            tb_prof_end(ctx);
-        } else {
-            tb_prof_begin(ctx, "k_ba_schur");
-            hipLaunchKernelGGL(ks, dim3(d.wgReduce ? d.Gbase * W + d.Gextra : (d.Vbase * W + d.Vextra + 3) / 4), dim3(BA_T), schur_lds, s, d, dw, iw, states);
-            tb_prof_end(ctx);
-            tb_prof_begin(ctx, "k_ba_solve");
-            if (d.np <= 16) hipLaunchKernelGGL(k_ba_solve<16>, dim3(W), dim3(BA_SOLVE_T), 0, s, d, dw, iw, states, reduce_in_solve ? 1 : 0);
-            else if (d.np <= 32) hipLaunchKernelGGL(k_ba_solve<32>, dim3(W), dim3(BA_SOLVE_T), 0, s, d, dw, iw, states, reduce_in_solve ? 1 : 0);
-            else if (d.np <= 48) hipLaunchKernelGGL(k_ba_solve<48>, dim3(W), dim3(BA_SOLVE_T), 0, s, d, dw, iw, states, reduce_in_solve ? 1 : 0);
-            else hipLaunchKernelGGL(k_ba_solve<64>, dim3(W), dim3(BA_SOLVE_T), 0, s, d, dw, iw, states, reduce_in_solve ? 1 : 0);
-            tb_prof_end(ctx);
-        }
-        tb_prof_begin(ctx, "k_ba_update");
-        hipLaunchKernelGGL(d.stream ? k_ba_update<true> : k_ba_update<false>, dim3(d.nblkP, W), dim3(BA_T), ((size_t)d.nkf * 24 + d.np) * sizeof(double), s, d, d_obs, dw, iw, states);
-        tb_prof_end(ctx);
-        tb_prof_begin(ctx, "k_ba_decide");
-        hipLaunchKernelGGL(k_ba_decide, dim3(W), dim3(64), 0, s, d, dw, states, running + round % ring);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
-        return TB_OK;
-    };
-    int host_running = 1, rounds = 0, rc = TB_OK;
-    const int max_rounds = std::min(iters * 10 + 1, 1000); /* ring size below */
+    /* before any capture begins: the limits of the kernels whose dynamic LDS grows with the window (tb_lds_limit only raises) */
+    if (!d.big) TB_TRY(tb_lds_limit(ctx, (const void*)p.schur, p.schur_lds));
+    if (d.renum) TB_TRY(tb_lds_limit(ctx, (const void*)k_ba_prepare, p.prepare_lds));
+    if (d.big) TB_TRY(tb_lds_limit(ctx, (const void*)k_ba_solve_big, p.big_lds));
+    const int max_rounds = std::min(iters * 10 + 1, BA_RING);
     int batch = iters; /* what every window needs at least; a speculative extra round (rounds 1-3) was seven empty launches on
                           every call to save one host round trip on the calls with a rejected step */
+    const int nfirst = std::min(batch, max_rounds);
     /* Small batches: the set-up and the first `iters` trials -- ~100 launches of a few microseconds each, which a host
      * thread cannot queue as fast as the GPU retires them -- are captured ONCE into a HIP graph per (shape, buffers) and
-     * replayed with one call (the kernels read their state from the workspace, so the graph is the same every time). Large
-     * batches launch directly: their kernels are long enough for the queue to stay ahead, and the
-     * per-kernel timing hooks need ordinary launches. */
-    const bool use_graph = W <= 32 && !ctx->prof && std::min(batch, max_rounds) > 0;
+     * replayed with one call. Large batches launch directly: their kernels are long enough for the queue to stay ahead
+     * (DESIGN.md section 4), and the per-kernel timing hooks need ordinary launches. */
+    const bool use_graph = W <= 32 && !ctx->prof && nfirst > 0;
+    int rounds = 0;
     if (use_graph) {
-        struct Key { BaDims d; const void *poses, *pts, *obs, *counts, *work; hipStream_t s; } key;
-        memset(&key, 0, sizeof key);
-        key.d = d; key.poses = d_poses; key.pts = d_pts; key.obs = d_obs_in; key.counts = d_counts; key.work = d_work; key.s = s;
-        const std::string kb((const char*)&key, sizeof key);
         hipGraphExec_t exec = nullptr;
-        for (auto& g : ctx->ba_graphs)
-            if (g.first == kb) exec = g.second;
-        const int nfirst = std::min(batch, max_rounds);
-        if (!exec) {
-            /* one capture at a time in the process: the pipeline drives its BA partitions from one host thread each, and
-             * three threads capturing on three streams at once produced graphs that did not replay the call (wrong poses,
-             * no error) -- a capture is rare (once per shape and buffer set), so it simply takes a lock */
-            static std::mutex capture_lock;
-            std::lock_guard<std::mutex> guard(capture_lock);
-            hipGraph_t graph = nullptr;
-            TB_HIP(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_head();
-            for (int r = 0; r < nfirst && rc == TB_OK; r++) rc = enqueue_round(r);
-            const hipError_t e = hipStreamEndCapture(s, &graph); /* always ends the capture, also after a failed launch */
-            if (rc != TB_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-            TB_HIP(ctx, e);
-            const hipError_t e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
-            TB_HIP(ctx, e2);
-            if (ctx->ba_graphs.size() >= 8) { /* a caller cycling through more buffer sets than this re-captures */
-                hipGraphExecDestroy(ctx->ba_graphs.front().second);
-                ctx->ba_graphs.erase(ctx->ba_graphs.begin());
-            }
-            ctx->ba_graphs.emplace_back(kb, exec);
-        }
+        TB_TRY(ba_graph(ctx, p, nfirst, &exec));
         TB_HIP(ctx, hipGraphLaunch(exec, s));
         rounds = nfirst;
-    } else if ((rc = enqueue_head()) != TB_OK) return rc;
+    } else {
+        TB_TRY(ba_enqueue_head(ctx, p));
+    }
+    /* no trial asked for (iters == 0): nothing was queued behind the head, no counter was written and none is read -- the
+     * write-back returns the input as the set-up stored it */
+    int host_running = nfirst > 0 ? 1 : 0;
     bool replayed = use_graph; /* the first batch of trials is already queued */
     while (host_running > 0 && (rounds < max_rounds || replayed)) {
         if (!replayed)
-            for (int r = 0; r < batch && rounds < max_rounds; r++, rounds++)
-                if ((rc = enqueue_round(rounds)) != TB_OK) return rc;
+            for (int r = 0; r < batch && rounds < max_rounds; r++, rounds++) TB_TRY(ba_enqueue_round(ctx, p, rounds));
         replayed = false;
         /* windows still running after the expected number of trials (rejected steps): one sync, then continue */
-        TB_HIP(ctx, hipMemcpyAsync(&host_running, running + (rounds - 1) % ring, sizeof(int), hipMemcpyDeviceToHost, s));
+        TB_HIP(ctx, hipMemcpyAsync(&host_running, p.running + (rounds - 1) % BA_RING, sizeof(int), hipMemcpyDeviceToHost, s));
         TB_HIP(ctx, hipStreamSynchronize(s));
         batch = 4;
     }
-    tb_prof_begin(ctx, "k_ba_finish");
-    hipLaunchKernelGGL(k_ba_finish, dim3(W), dim3(BA_T), 0, s, d, dw, iw, states, d_poses, d_pts, d_stats);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_ba_finish", k_ba_finish, dim3(W), dim3(BA_T), 0, d, p.dw, p.iw, p.states, d_poses, d_pts, d_stats);
 }

@@ -226,31 +226,19 @@ int tbk_bow_score(tb_ctx* ctx, int scoring, double log_eps, int na, const int32_
     per = std::max<long long>(per, ((long long)nj + 65534) / 65535);
     A.epb = (int)per;
     const size_t lds = (size_t)a_pitch * (sizeof(double) + sizeof(int32_t));
-    TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_score, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tb_prof_begin(ctx, "k_bow_score");
-    hipLaunchKernelGGL(k_bow_score, dim3(na, (nj + A.epb - 1) / A.epb), dim3(256), lds, ctx->stream, A);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    TB_TRY(tb_lds_limit(ctx, (const void*)k_bow_score, lds));
+    return tb_launch(ctx, "k_bow_score", k_bow_score, dim3(na, (nj + A.epb - 1) / A.epb), dim3(256), lds, A);
 }
 
 int tbk_bow_db_add(tb_ctx* ctx, int nseq, const int32_t* d_src_w, const double* d_src_v, const int32_t* d_src_c, int src_pitch, int cap,
                    int pitch, int slot, int32_t kf_id, int32_t* d_words, double* d_values, int32_t* d_counts, int32_t* d_kf_ids) {
-    tb_prof_begin(ctx, "k_bow_db_add");
-    hipLaunchKernelGGL(k_bow_db_add, dim3(nseq), dim3(256), 0, ctx->stream, d_src_w, d_src_v, d_src_c, src_pitch, cap, pitch, slot, kf_id,
-                       d_words, d_values, d_counts, d_kf_ids);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_bow_db_add", k_bow_db_add, dim3(nseq), dim3(256), 0, d_src_w, d_src_v, d_src_c, src_pitch, cap, pitch, slot,
+                     kf_id, d_words, d_values, d_counts, d_kf_ids);
 }
 
 int tbk_bow_db_rank(tb_ctx* ctx, int nseq, const double* d_scores, const int32_t* d_kf_ids, int cap, int nfilled, int newest, int exclude,
                     int ascending, int topk, int32_t* d_top_slot, int32_t* d_top_kf, double* d_top_score, int32_t* d_top_count) {
     const int nranked = nfilled - std::min(exclude, nfilled);
-    tb_prof_begin(ctx, "k_bow_db_rank");
-    hipLaunchKernelGGL(k_bow_db_rank, dim3(nseq), dim3(256), 0, ctx->stream, d_scores, d_kf_ids, cap, nfilled, newest, exclude, nranked,
-                       ascending, topk, d_top_slot, d_top_kf, d_top_score, d_top_count);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_bow_db_rank", k_bow_db_rank, dim3(nseq), dim3(256), 0, d_scores, d_kf_ids, cap, nfilled, newest, exclude,
+                     nranked, ascending, topk, d_top_slot, d_top_kf, d_top_score, d_top_count);
 }

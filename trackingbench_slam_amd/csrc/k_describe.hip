@@ -361,10 +361,6 @@ int tbk_describe(tb_extractor* ex, int n) {
     const int by_image = n >= 64 ? 1 : 0;
     const int slotGroups = (ex->g.selCap + DS_KPB - 1) / DS_KPB;
     const dim3 grid = by_image ? dim3((unsigned)slotGroups * 8u * (unsigned)((n + 7) / 8)) : dim3(slotGroups, n);
-    tb_prof_begin(ctx, "k_describe");
-    hipLaunchKernelGGL(k_describe, grid, dim3(64 * DS_KPB), 0, ctx->stream, ex->g, ex->d_slab, ex->d_sel, ex->d_selCount,
-                       ex->d_kps, ex->d_desc, ex->d_counts, n, by_image, slotGroups);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_describe", k_describe, grid, dim3(64 * DS_KPB), 0, ex->g, ex->d_slab, ex->d_sel, ex->d_selCount, ex->d_kps,
+                     ex->d_desc, ex->d_counts, n, by_image, slotGroups);
 }

@@ -795,12 +795,8 @@ int tbk_fast_cells(tb_extractor* ex, int n, int init_th, int min_th) {
     static_assert(FB_LDS_BYTES - FB_PAD_LDS <= 32 * 1024, "five blocks per CU");
     /* test hook (tb_debug_force_dense_fast): every block down the any-density path (same results, no lists) */
     const int force_dense = ctx->dbg_fast_dense;
-    tb_prof_begin(ctx, "k_fast_cells");
-    hipLaunchKernelGGL(k_fast_blocks, grid, dim3(FB_NT), FB_LDS_BYTES, ctx->stream, ex->g, ex->d_slab, ex->d_blocks, ex->nBlocksTotal,
-                       n, by_image, ex->d_cand, ex->d_candCount, init_th, min_th, force_dense);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_fast_cells", k_fast_blocks, grid, dim3(FB_NT), FB_LDS_BYTES, ex->g, ex->d_slab, ex->d_blocks, ex->nBlocksTotal,
+                     n, by_image, ex->d_cand, ex->d_candCount, init_th, min_th, force_dense);
 }
 
 /* ---- whole-image mode: 58x58 output tiles, scan region [3,w-3) x [3,h-3) */
@@ -826,16 +822,8 @@ int tbk_fast_image(tb_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, 
     TB_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), ctx->stream));
     if (w < 7 || h < 7) return TB_OK;
     dim3 grid((w - 6 + FT_OUT - 1) / FT_OUT, (h - 6 + FT_OUT - 1) / FT_OUT, 1);
-    tb_prof_begin(ctx, "k_fast_image");
-    if (arc == 9)
-        hipLaunchKernelGGL(k_fast_image<9>, grid, dim3(256), 0, ctx->stream, d_img, w, h, stride, (size_t)0, th, nms,
-                           d_out, cap, (size_t)0, d_count, 0);
-    else
-        hipLaunchKernelGGL(k_fast_image<10>, grid, dim3(256), 0, ctx->stream, d_img, w, h, stride, (size_t)0, th, nms,
-                           d_out, cap, (size_t)0, d_count, 0);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_fast_image", arc == 9 ? k_fast_image<9> : k_fast_image<10>, grid, dim3(256), 0, d_img, w, h, stride, 0, th, nms,
+                     d_out, cap, 0, d_count, 0);
 }
 
 /* ---- a11: FASTExtractor grid selection.
@@ -957,22 +945,12 @@ int tbk_fastgrid(tb_extractor* ex, int n, int target, float threshold, int n_occ
         int stride;
         if (l == 0 && g.img0) { base = g.img0; pitch = g.img0_pitch; stride = g.img0_stride; }
         else { base = ex->d_slab + L.off; pitch = g.slabBytes; stride = L.stride; }
-        tb_prof_begin(ctx, "k_fast_image");
-        hipLaunchKernelGGL(k_fast_image<10>, grid, dim3(256), 0, ctx->stream, base, L.w, L.h, stride, pitch, 20, 1,
-                           ex->d_cand + L.candOff, L.candCap, (size_t)g.candPerImage, ex->d_candCount + l, TB_MAX_LEVELS);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_TRY(tb_launch(ctx, "k_fast_image", k_fast_image<10>, grid, dim3(256), 0, base, L.w, L.h, stride, pitch, 20, 1,
+                         ex->d_cand + L.candOff, L.candCap, (size_t)g.candPerImage, ex->d_candCount + l, TB_MAX_LEVELS));
         dim3 bgrid((L.candCap + 255) / 256, n);
-        tb_prof_begin(ctx, "k_fastgrid_bid");
-        hipLaunchKernelGGL(k_fastgrid_bid, bgrid, dim3(256), 0, ctx->stream, g, ex->d_slab, ex->d_cand, ex->d_candCount, l,
-                           cell_size, grid_cols, ncell, n_occ > 0 ? ex->d_occ : nullptr, n_occ, ex->d_gridBest);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_TRY(tb_launch(ctx, "k_fastgrid_bid", k_fastgrid_bid, bgrid, dim3(256), 0, g, ex->d_slab, ex->d_cand, ex->d_candCount, l,
+                         cell_size, grid_cols, ncell, n_occ > 0 ? ex->d_occ : nullptr, n_occ, ex->d_gridBest));
     }
-    tb_prof_begin(ctx, "k_fastgrid_emit");
-    hipLaunchKernelGGL(k_fastgrid_emit, dim3(n), dim3(256), 0, ctx->stream, g, ex->d_gridBest, ncell, threshold, ex->d_kps,
-                       ex->d_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_fastgrid_emit", k_fastgrid_emit, dim3(n), dim3(256), 0, g, ex->d_gridBest, ncell, threshold, ex->d_kps,
+                     ex->d_counts);
 }

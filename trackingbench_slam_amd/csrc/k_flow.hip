@@ -273,22 +273,18 @@ int tbk_lk_track(tb_ctx* ctx, int npairs, const uint8_t* d_prev, const uint8_t* 
         uint8_t* a = p; p += bytes * npairs;
         uint8_t* b = p; p += bytes * npairs;
         dim3 grid((lw + 63) / 64, (lh + 3) / 4, npairs);
-        tb_prof_begin(ctx, "k_pyr_down");
-        hipLaunchKernelGGL(k_pyr_down, grid, dim3(256), 0, ctx->stream, L.prev[l - 1], L.w[l - 1], L.h[l - 1], L.stride[l - 1],
-                           L.pitch[l - 1], a, lw, lh, lw, bytes);
-        hipLaunchKernelGGL(k_pyr_down, grid, dim3(256), 0, ctx->stream, L.next[l - 1], L.w[l - 1], L.h[l - 1], L.stride[l - 1],
-                           L.pitch[l - 1], b, lw, lh, lw, bytes);
+        tb_prof_begin(ctx, "k_pyr_down"); /* one record over both images' launches */
+        TB_TRY(tb_launch(ctx, nullptr, k_pyr_down, grid, dim3(256), 0, L.prev[l - 1], L.w[l - 1], L.h[l - 1], L.stride[l - 1], L.pitch[l - 1],
+                         a, lw, lh, lw, bytes));
+        TB_TRY(tb_launch(ctx, nullptr, k_pyr_down, grid, dim3(256), 0, L.next[l - 1], L.w[l - 1], L.h[l - 1], L.stride[l - 1], L.pitch[l - 1],
+                         b, lw, lh, lw, bytes));
         tb_prof_end(ctx);
         L.prev[l] = a; L.next[l] = b; L.w[l] = lw; L.h[l] = lh; L.stride[l] = lw; L.pitch[l] = bytes;
         L.top = l;
     }
     if (top_level) *top_level = L.top;
-    if (n > 0 && npairs > 0) {
-        tb_prof_begin(ctx, "k_lk_track");
-        hipLaunchKernelGGL(k_lk_track, dim3(n, npairs), dim3(64), 0, ctx->stream, L, d_prev_pts, d_counts, n, d_next_pts, d_status, d_err);
-        tb_prof_end(ctx);
-    }
-    TB_HIP(ctx, hipGetLastError());
+    if (n > 0 && npairs > 0)
+        TB_TRY(tb_launch(ctx, "k_lk_track", k_lk_track, dim3(n, npairs), dim3(64), 0, L, d_prev_pts, d_counts, n, d_next_pts, d_status, d_err));
     return TB_OK;
 }
 
@@ -365,13 +361,12 @@ int tbk_clahe(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int str
     const int tw = ew / tiles_x, th = eh / tiles_y, area = tw * th;
     int clip = 0;
     if (clip_limit > 0.0) { clip = (int)(clip_limit * area / 256); if (clip < 1) clip = 1; }
-    tb_prof_begin(ctx, "k_clahe");
-    hipLaunchKernelGGL(k_clahe_lut, dim3(tiles_x, tiles_y, nimg), dim3(256), 0, ctx->stream, d_src, w, h, stride, spitch, tw, th, clip,
-                       (float)255 / (float)area, d_lut);
-    hipLaunchKernelGGL(k_clahe_apply, dim3((w + 63) / 64, (h + 3) / 4, nimg), dim3(256), 0, ctx->stream, d_src, w, h, stride, spitch,
-                       tiles_x, tiles_y, 1.0f / (float)tw, 1.0f / (float)th, d_lut, d_dst, dstride, dpitch);
+    tb_prof_begin(ctx, "k_clahe"); /* one record over the table and the interpolation */
+    TB_TRY(tb_launch(ctx, nullptr, k_clahe_lut, dim3(tiles_x, tiles_y, nimg), dim3(256), 0, d_src, w, h, stride, spitch, tw, th, clip,
+                     (float)255 / (float)area, d_lut));
+    TB_TRY(tb_launch(ctx, nullptr, k_clahe_apply, dim3((w + 63) / 64, (h + 3) / 4, nimg), dim3(256), 0, d_src, w, h, stride, spitch, tiles_x,
+                     tiles_y, 1.0f / (float)tw, 1.0f / (float)th, d_lut, d_dst, dstride, dpitch));
     tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
     return TB_OK;
 }
 
@@ -408,10 +403,6 @@ k_flow_accept(const float* __restrict__ cur, uint8_t* __restrict__ status, const
 
 int tbk_flow_accept(tb_ctx* ctx, int npairs, const float* d_cur, uint8_t* d_status, const int32_t* d_counts, int pts_pitch, int width,
                     int height, tb_match* d_out, int cap, int32_t* d_out_counts) {
-    tb_prof_begin(ctx, "k_flow_accept");
-    hipLaunchKernelGGL(k_flow_accept, dim3(npairs), dim3(64), 0, ctx->stream, d_cur, d_status, d_counts, pts_pitch, width, height, d_out,
-                       cap, d_out_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_flow_accept", k_flow_accept, dim3(npairs), dim3(64), 0, d_cur, d_status, d_counts, pts_pitch, width, height,
+                     d_out, cap, d_out_counts);
 }

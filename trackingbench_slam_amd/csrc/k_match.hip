@@ -16,15 +16,6 @@
 #include "tb_internal.h"
 #include "tb_device.h"
 
-/* one profiled launch on the context's stream; the launcher returns the error of a launch that fails */
-#define TB_LAUNCH(ctx, name, kernel, grid, block, lds, ...)                       \
-    do {                                                                          \
-        tb_prof_begin(ctx, name);                                                 \
-        hipLaunchKernelGGL(kernel, grid, block, lds, (ctx)->stream, __VA_ARGS__); \
-        tb_prof_end(ctx);                                                         \
-        TB_HIP(ctx, hipGetLastError());                                           \
-    } while (0)
-
 #define BF_T 256
 #define BF_QC 512 /* queries staged per block */
 
@@ -121,14 +112,15 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
     if (crosscheck) {
         TB_HIP(ctx, hipMemsetAsync(d_tbest, 0xff, bytes, ctx->stream));
         /* rows = train (d2), cols = query (d1) */
-        TB_LAUNCH(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d2, c2, d1, c1, set_pitch, max_n, d_tbest);
-        TB_LAUNCH(ctx, "k_bf_cross", k_bf_cross, dim3((max_n + BF_T - 1) / BF_T, npairs), dim3(BF_T), 0, c2, max_n, d_tbest, d_qbest);
+        TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d2, c2, d1, c1, set_pitch, max_n, d_tbest));
+        TB_TRY(tb_launch(ctx, "k_bf_cross", k_bf_cross, dim3((max_n + BF_T - 1) / BF_T, npairs), dim3(BF_T), 0, c2, max_n, d_tbest,
+                         d_qbest));
     } else {
         /* rows = query, cols = train: qbest[q] = (dist, nearest train) directly */
-        TB_LAUNCH(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d1, c1, d2, c2, set_pitch, max_n, d_qbest);
+        TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d1, c1, d2, c2, set_pitch, max_n, d_qbest));
     }
-    TB_LAUNCH(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
-              out_counts);
+    TB_TRY(tb_launch(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
+                     out_counts));
     return TB_OK;
 }
 
@@ -223,10 +215,10 @@ int tbk_lsh_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1,
     const int tiles = (max_n + LSH_T - 1) / LSH_T, chunks = (max_n + LSH_TC - 1) / LSH_TC;
     int split = 1;
     while (split < 4 && split * 2 <= chunks && (long long)tiles * npairs * split < 2ll * ctx->num_cu) split *= 2;
-    TB_LAUNCH(ctx, "k_lsh_nn", k_lsh_nn, dim3(tiles, split, npairs), dim3(LSH_T), tbk_lsh_lds_bytes(T, k), d1, c1, d2, c2, set_pitch,
-              max_n, d_bits, T, k, L, d_qbest);
-    TB_LAUNCH(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
-              out_counts);
+    TB_TRY(tb_launch(ctx, "k_lsh_nn", k_lsh_nn, dim3(tiles, split, npairs), dim3(LSH_T), tbk_lsh_lds_bytes(T, k), d1, c1, d2, c2, set_pitch,
+                     max_n, d_bits, T, k, L, d_qbest));
+    TB_TRY(tb_launch(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
+                     out_counts));
     return TB_OK;
 }
 
@@ -521,8 +513,8 @@ int tbk_grid_build_batch(tb_ctx* ctx, int nframes, const tb_keypoint* d_keys, co
                          int img_h, int32_t* d_cellStart, int32_t* d_cellItems) {
     if (nframes <= 0) return TB_OK;
     const float heightInv = 120.f / (float)img_w, widthInv = 36.f / (float)img_h; /* swapped in the reference; kept */
-    TB_LAUNCH(ctx, "k_grid_build", k_grid_build, dim3(nframes), dim3(256), 0, d_keys, d_counts, key_pitch, widthInv, heightInv,
-              d_cellStart, d_cellItems);
+    TB_TRY(tb_launch(ctx, "k_grid_build", k_grid_build, dim3(nframes), dim3(256), 0, d_keys, d_counts, key_pitch, widthInv, heightInv,
+                     d_cellStart, d_cellItems));
     return TB_OK;
 }
 
@@ -545,8 +537,8 @@ int tbk_projection_batch(tb_ctx* ctx, int npairs, const float* d_Tcw, const tb_c
     B.th_high = th_high; B.histo_len = histo_len; B.check_orientation = check_orientation;
     B.best = d_best; B.out = d_out; B.cap = cap; B.out_counts = d_out_counts; B.flags = d_flags;
     TB_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)npairs * sizeof(int32_t), ctx->stream));
-    TB_LAUNCH(ctx, "k_proj_search", k_proj_search_batch, dim3((max_n2 + 255) / 256, npairs), dim3(256), 0, B);
-    TB_LAUNCH(ctx, "k_proj_accept", k_proj_accept_batch, dim3(npairs), dim3(256), 0, B);
+    TB_TRY(tb_launch(ctx, "k_proj_search", k_proj_search_batch, dim3((max_n2 + 255) / 256, npairs), dim3(256), 0, B));
+    TB_TRY(tb_launch(ctx, "k_proj_accept", k_proj_accept_batch, dim3(npairs), dim3(256), 0, B));
     return TB_OK;
 }
 
@@ -626,8 +618,8 @@ int tbk_violence_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const u
     B.th_low = th_low; B.histo_len = histo_len; B.check_orientation = check_orientation;
     B.best = d_best; B.out = d_out; B.cap = cap; B.out_counts = d_out_counts; B.flags = d_flags;
     TB_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)npairs * sizeof(int32_t), ctx->stream));
-    TB_LAUNCH(ctx, "k_window_batch", k_window_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B);
-    TB_LAUNCH(ctx, "k_violence_accept", k_violence_accept_batch, dim3(npairs), dim3(256), 0, B);
+    TB_TRY(tb_launch(ctx, "k_window_batch", k_window_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B));
+    TB_TRY(tb_launch(ctx, "k_violence_accept", k_violence_accept_batch, dim3(npairs), dim3(256), 0, B));
     return TB_OK;
 }
 
@@ -677,8 +669,8 @@ int tbk_stereo_obs(tb_ctx* ctx, int nframes, const tb_keypoint* d_kl, const tb_k
                    const int32_t* d_match_counts, int match_pitch, const float K[4], float bf, const float* d_inv_sigma2, int nlevels,
                    tb_obs* d_obs, int obs_pitch, int32_t* d_obs_counts) {
     if (nframes <= 0) return TB_OK;
-    TB_LAUNCH(ctx, "k_stereo_obs", k_stereo_obs, dim3(nframes), dim3(256), 0, d_kl, d_kr, key_pitch, d_matches, d_match_counts,
-              match_pitch, K[0], K[1], K[2], K[3], bf, d_inv_sigma2, nlevels, d_obs, obs_pitch, d_obs_counts);
+    TB_TRY(tb_launch(ctx, "k_stereo_obs", k_stereo_obs, dim3(nframes), dim3(256), 0, d_kl, d_kr, key_pitch, d_matches, d_match_counts,
+                     match_pitch, K[0], K[1], K[2], K[3], bf, d_inv_sigma2, nlevels, d_obs, obs_pitch, d_obs_counts));
     return TB_OK;
 }
 
@@ -924,15 +916,15 @@ int tbk_bow_transform(tb_ctx* ctx, int nnodes, int L, const int32_t* d_child_sta
                       unsigned long long* d_fv_keys, int32_t* d_fv_counts) {
     if (nframes <= 0 || desc_pitch <= 0) return TB_OK;
     BowVocab V = {nnodes, L, d_child_start, d_child_items, d_vdesc, d_word_id, d_weight};
-    TB_LAUNCH(ctx, "k_bow_transform", k_bow_transform, dim3((desc_pitch + 255) / 256, nframes), dim3(256), 0, V, d_desc, d_counts,
-              desc_pitch, levelsup, d_word_ids, d_node_ids, d_weights);
+    TB_TRY(tb_launch(ctx, "k_bow_transform", k_bow_transform, dim3((desc_pitch + 255) / 256, nframes), dim3(256), 0, V, d_desc, d_counts,
+                     desc_pitch, levelsup, d_word_ids, d_node_ids, d_weights));
     if (d_fv_keys) {
         int m = 1;
         while (m < desc_pitch) m <<= 1;
         const size_t lds = (size_t)m * sizeof(unsigned long long);
-        TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_fv_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        TB_LAUNCH(ctx, "k_bow_fv_sort", k_bow_fv_sort, dim3(nframes), dim3(1024), lds, d_node_ids, d_weights, d_counts, desc_pitch,
-                  d_fv_keys, d_fv_counts);
+        TB_TRY(tb_lds_limit(ctx, (const void*)k_bow_fv_sort, lds));
+        TB_TRY(tb_launch(ctx, "k_bow_fv_sort", k_bow_fv_sort, dim3(nframes), dim3(1024), lds, d_node_ids, d_weights, d_counts, desc_pitch,
+                         d_fv_keys, d_fv_counts));
     }
     return TB_OK;
 }
@@ -943,9 +935,9 @@ int tbk_bow_vector(tb_ctx* ctx, int nframes, const int32_t* d_word_ids, const do
     int m = 1;
     while (m < desc_pitch) m <<= 1;
     const size_t lds = (size_t)m * sizeof(unsigned long long);
-    TB_HIP(ctx, hipFuncSetAttribute((const void*)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TB_LAUNCH(ctx, "k_bow_vector", k_bow_vector, dim3(nframes), dim3(1024), lds, d_word_ids, d_weights, d_counts, desc_pitch, weighting,
-              scoring, d_bv_words, d_bv_values, d_bv_counts);
+    TB_TRY(tb_lds_limit(ctx, (const void*)k_bow_vector, lds));
+    TB_TRY(tb_launch(ctx, "k_bow_vector", k_bow_vector, dim3(nframes), dim3(1024), lds, d_word_ids, d_weights, d_counts, desc_pitch,
+                     weighting, scoring, d_bv_words, d_bv_values, d_bv_counts));
     return TB_OK;
 }
 
@@ -961,7 +953,7 @@ int tbk_bow_search_batch(tb_ctx* ctx, int npairs, const tb_keypoint* d_k1, const
     B.pitch1 = pitch1; B.pitch2 = pitch2; B.map_point_only = map_point_only; B.th_low = th_low; B.histo_len = histo_len;
     B.check_orientation = check_orientation; B.cap = cap; B.nratio = nratio; B.best = d_best; B.out = d_out; B.out_counts = d_out_counts;
     B.flags = d_flags;
-    TB_LAUNCH(ctx, "k_bow_search_batch", k_bow_search_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B);
-    TB_LAUNCH(ctx, "k_bow_accept_batch", k_bow_accept_batch, dim3(npairs), dim3(256), 0, B);
+    TB_TRY(tb_launch(ctx, "k_bow_search_batch", k_bow_search_batch, dim3((pitch1 + 255) / 256, npairs), dim3(256), 0, B));
+    TB_TRY(tb_launch(ctx, "k_bow_accept_batch", k_bow_accept_batch, dim3(npairs), dim3(256), 0, B));
     return TB_OK;
 }

@@ -519,15 +519,9 @@ int tbk_octree(tb_extractor* ex, int n, int n_exit) {
          * not the node tables, set the time, and 1024 threads are worth the idle lanes in the scans */
         const kern_t kern = part == 1 ? (kern_t)k_octree<128, 32> : big ? (kern_t)k_octree<OT_TMAX, 12> : (kern_t)k_octree<256, 32>;
         const int threads = part == 1 ? 128 : big ? OT_TMAX : 256;
-        /* a function attribute belongs to the (function, device) pair: set per call on the context's device whenever the
-         * launch needs more than the default 64 KB (no process-wide "done" flag) */
-        if (lds > 64 * 1024)
-            TB_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-        tb_prof_begin(ctx, "k_octree");
-        hipLaunchKernelGGL(kern, dim3(l1 - l0, n), dim3(threads), lds, ctx->stream, g, ex->d_cand, ex->d_candCount, ex->d_knode,
-                           ex->d_exit, n_exit, ex->d_enode, ex->d_sel, ex->d_selCount, capMax, l0);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
+        TB_TRY(tb_lds_limit(ctx, (const void*)kern, lds));
+        TB_TRY(tb_launch(ctx, "k_octree", kern, dim3(l1 - l0, n), dim3(threads), lds, g, ex->d_cand, ex->d_candCount, ex->d_knode,
+                         ex->d_exit, n_exit, ex->d_enode, ex->d_sel, ex->d_selCount, capMax, l0));
     }
     return TB_OK;
 }

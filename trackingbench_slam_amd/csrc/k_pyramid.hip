@@ -169,21 +169,12 @@ int tbk_resize_level(tb_extractor* ex, int level, int n) {
         const int tilesX = (D.stride + 255) / 256, tilesY = (D.h + RS_ROWS - 1) / RS_ROWS;
         const int by_image = n >= 64 ? 1 : 0;
         const dim3 grid = by_image ? dim3((unsigned)(tilesX * tilesY) * 8u * (unsigned)((n + 7) / 8)) : dim3(tilesX, tilesY, n);
-        tb_prof_begin(ctx, "k_resize");
-        hipLaunchKernelGGL(k_resize_lds, grid, dim3(64), lds, ctx->stream, ex->g, ex->d_slab, ex->d_rx[level], ex->d_ry[level], level,
-                           rowBytes, n, by_image, tilesX, tilesY);
-        tb_prof_end(ctx);
-        TB_HIP(ctx, hipGetLastError());
-        return TB_OK;
+        return tb_launch(ctx, "k_resize", k_resize_lds, grid, dim3(64), lds, ex->g, ex->d_slab, ex->d_rx[level], ex->d_ry[level], level,
+                         rowBytes, n, by_image, tilesX, tilesY);
     }
     const int groups = (D.stride >> 2) * D.h;
     dim3 grid((groups + 255) / 256, n);
-    tb_prof_begin(ctx, "k_resize");
-    hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, ex->ctx->stream, ex->g, ex->d_slab, ex->d_rx[level],
-                       ex->d_ry[level], level);
-    tb_prof_end(ctx);
-    TB_HIP(ex->ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_resize", k_resize, grid, dim3(256), 0, ex->g, ex->d_slab, ex->d_rx[level], ex->d_ry[level], level);
 }
 
 /* ---- measurement helper ("confirm on the box with a device-to-device copy microbench"): 16 bytes per lane, four
@@ -206,9 +197,7 @@ int tbk_copy16(tb_ctx* ctx, const void* d_src, void* d_dst, size_t bytes) {
     const size_t n16 = bytes / 16;
     if (n16 == 0) return TB_OK;
     const unsigned blocks = (unsigned)((n16 + 1023) / 1024);
-    hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(256), 0, ctx->stream, (const tb_u4*)d_src, (tb_u4*)d_dst, n16);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, nullptr, k_copy16, dim3(blocks), dim3(256), 0, (const tb_u4*)d_src, (tb_u4*)d_dst, n16);
 }
 
 /* ---- exchange helper: the live rows of a [F][cap] record array, frame after frame, to the front of a packed
@@ -246,8 +235,6 @@ k_pack_rows(const uint8_t* __restrict__ src, int row_bytes, int cap, const int32
 
 int tbk_pack_rows(tb_ctx* ctx, const void* d_src, int row_bytes, int cap, const int32_t* d_counts, int nframes, void* d_dst, long long* d_total) {
     if (nframes <= 0) return TB_OK;
-    hipLaunchKernelGGL(k_pack_rows, dim3(nframes), dim3(256), 0, ctx->stream, (const uint8_t*)d_src, row_bytes, cap, d_counts, nframes,
-                       (uint8_t*)d_dst, d_total);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, nullptr, k_pack_rows, dim3(nframes), dim3(256), 0, (const uint8_t*)d_src, row_bytes, cap, d_counts, nframes,
+                     (uint8_t*)d_dst, d_total);
 }

@@ -437,13 +437,9 @@ int tbk_ransac_f(tb_ctx* ctx, int npairs, const float* d_pts1, const float* d_pt
                  int pts_pitch, int mode, double thresh, double conf, void* d_work, int32_t* d_flags, double* d_F, int32_t* d_iters) {
     if (npairs <= 0 || pts_pitch <= 0) return TB_OK;
     const size_t lds = sizeof(RsShared);
-    TB_HIP(ctx, hipFuncSetAttribute((const void*)k_ransac_f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tb_prof_begin(ctx, "k_ransac_f");
-    hipLaunchKernelGGL(k_ransac_f, dim3(npairs), dim3(RS_T), lds, ctx->stream, d_pts1, d_pts2, d_status, d_counts, pts_pitch, mode,
-                       thresh, conf, (float*)d_work, d_flags, d_F, d_iters);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    TB_TRY(tb_lds_limit(ctx, (const void*)k_ransac_f, lds));
+    return tb_launch(ctx, "k_ransac_f", k_ransac_f, dim3(npairs), dim3(RS_T), lds, d_pts1, d_pts2, d_status, d_counts, pts_pitch, mode,
+                     thresh, conf, (float*)d_work, d_flags, d_F, d_iters);
 }
 
 /* LocalBA::AddMapPointsByStereo, LocalBA.cpp:54-66: Depth[i] = bf / fabsf(pts[i].x - key[i].x) for the matched keys, -1 else */
@@ -462,10 +458,6 @@ k_stereo_depth(const float* __restrict__ cur, const float* __restrict__ keys, co
 int tbk_stereo_depth(tb_ctx* ctx, int npairs, const float* d_cur, const float* d_keys, const uint8_t* d_status, const int32_t* d_counts,
                      int pts_pitch, float bf, float* d_depth) {
     if (npairs <= 0 || pts_pitch <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_stereo_depth");
-    hipLaunchKernelGGL(k_stereo_depth, dim3((pts_pitch + 255) / 256, npairs), dim3(256), 0, ctx->stream, d_cur, d_keys, d_status, d_counts,
-                       pts_pitch, bf, d_depth);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_stereo_depth", k_stereo_depth, dim3((pts_pitch + 255) / 256, npairs), dim3(256), 0, d_cur, d_keys, d_status,
+                     d_counts, pts_pitch, bf, d_depth);
 }

@@ -333,22 +333,14 @@ int tbk_kf_store_add(tb_ctx* ctx, int nseq, const tb_keypoint* d_keys, const uin
                      int32_t* s_kf_ids) {
     KfStoreSrc A = {d_keys, d_desc, d_fv, d_mp, d_valid, d_Tcw, d_counts, d_fv_counts};
     KfStoreArrays D = {s_keys, s_desc, s_fv, s_mp, s_valid, s_Tcw, s_counts, s_fv_counts, s_kf_ids};
-    tb_prof_begin(ctx, "k_kf_store_add");
-    hipLaunchKernelGGL(k_kf_store_add, dim3(nseq, 4), dim3(256), 0, ctx->stream, A, src_pitch, cap, pitch, slot, kf_id, D);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_kf_store_add", k_kf_store_add, dim3(nseq, 4), dim3(256), 0, A, src_pitch, cap, pitch, slot, kf_id, D);
 }
 
 int tbk_reloc_pairs(tb_ctx* ctx, int nseq, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids, const float* d_kf_Tcw,
                     int32_t* d_ix1, int32_t* d_ix2, float* d_seed, int32_t* d_cand_kf) {
     const int npairs = nseq * ncand;
-    tb_prof_begin(ctx, "k_reloc_pairs");
-    hipLaunchKernelGGL(k_reloc_pairs, dim3((npairs + 255) / 256), dim3(256), 0, ctx->stream, npairs, ncand, cap, d_cand_slot, d_kf_ids,
-                       d_kf_Tcw, d_ix1, d_ix2, d_seed, d_cand_kf);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_reloc_pairs", k_reloc_pairs, dim3((npairs + 255) / 256), dim3(256), 0, npairs, ncand, cap, d_cand_slot,
+                     d_kf_ids, d_kf_Tcw, d_ix1, d_ix2, d_seed, d_cand_kf);
 }
 
 int tbk_reloc_rows(tb_ctx* ctx, int npairs, const tb_keypoint* d_q_keys, const int32_t* d_q_counts, int q_pitch, const int32_t* d_ix1,
@@ -358,33 +350,21 @@ int tbk_reloc_rows(tb_ctx* ctx, int npairs, const tb_keypoint* d_q_keys, const i
     tb_reloc_sigma sig;
     sig.n = std::min(std::max(nlevels, 1), TB_MAX_LEVELS);
     for (int l = 0; l < TB_MAX_LEVELS; l++) sig.v[l] = l < sig.n ? inv_sigma2[l] : 1.f;
-    tb_prof_begin(ctx, "k_reloc_rows");
-    hipLaunchKernelGGL(k_reloc_rows, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), ctx->stream, d_q_keys, d_q_counts, q_pitch,
-                       d_ix1, d_ix2, d_matches, d_match_counts, d_kf_mp, d_kf_valid, d_kf_counts, pitch, sig, d_obs, d_obs_counts, d_outlier,
-                       d_rows_out);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_reloc_rows", k_reloc_rows, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), d_q_keys, d_q_counts,
+                     q_pitch, d_ix1, d_ix2, d_matches, d_match_counts, d_kf_mp, d_kf_valid, d_kf_counts, pitch, sig, d_obs,
+                     d_obs_counts, d_outlier, d_rows_out);
 }
 
 int tbk_reloc_select(tb_ctx* ctx, int nseq, int ncand, int min_inliers, const int32_t* d_cand_kf, const int32_t* d_cand_inliers,
                      const float* d_cand_Tcw, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_Tcw) {
-    tb_prof_begin(ctx, "k_reloc_select");
-    hipLaunchKernelGGL(k_reloc_select, dim3((nseq + 255) / 256), dim3(256), 0, ctx->stream, nseq, ncand, min_inliers, d_cand_kf,
-                       d_cand_inliers, d_cand_Tcw, d_best_rank, d_best_kf, d_best_Tcw);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_reloc_select", k_reloc_select, dim3((nseq + 255) / 256), dim3(256), 0, nseq, ncand, min_inliers, d_cand_kf,
+                     d_cand_inliers, d_cand_Tcw, d_best_rank, d_best_kf, d_best_Tcw);
 }
 
 int tbk_vo_recover_mask(tb_ctx* ctx, int nseq, int topk, int lost_inliers, const int32_t* d_n_inliers, const int32_t* d_top_slot,
                         uint8_t* d_lost, int32_t* d_track_inliers, int32_t* d_masked) {
-    tb_prof_begin(ctx, "k_vo_recover_mask");
-    hipLaunchKernelGGL(k_vo_recover_mask, dim3((nseq * topk + 255) / 256), dim3(256), 0, ctx->stream, nseq, topk, lost_inliers, d_n_inliers,
-                       d_top_slot, d_lost, d_track_inliers, d_masked);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_recover_mask", k_vo_recover_mask, dim3((nseq * topk + 255) / 256), dim3(256), 0, nseq, topk, lost_inliers,
+                     d_n_inliers, d_top_slot, d_lost, d_track_inliers, d_masked);
 }
 
 int tbk_vo_recover_adopt(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
@@ -393,12 +373,8 @@ int tbk_vo_recover_adopt(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
                        a->s_counts, a->best_kf, a->best_Tcw};
     VoRecoverState D = {a->Tcw, a->mp, a->valid, a->obs, a->outlier, a->matches, a->obs_counts, a->n_inliers, a->mcounts, a->mflags,
                         a->recovered_kf};
-    tb_prof_begin(ctx, "k_vo_recover_adopt");
-    hipLaunchKernelGGL(k_vo_recover_adopt, dim3(nseq), dim3(256), (size_t)a->pitch * sizeof(int), ctx->stream, W, A, a->orb_counts, a->pitch,
-                       D);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_recover_adopt", k_vo_recover_adopt, dim3(nseq), dim3(256), (size_t)a->pitch * sizeof(int), W, A,
+                     a->orb_counts, a->pitch, D);
 }
 
 int tbk_vo_recover_switch(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
@@ -407,19 +383,11 @@ int tbk_vo_recover_switch(tb_ctx* ctx, int nseq, const tb_vo_recover_args* a) {
                         a->db_counts, a->word_ring, a->node_ring, a->best_kf};
     VoRecoverSnap D = {a->kf_orb, a->kf_desc, a->kf_fv, a->kf_mp, a->kf_valid, a->kf_cnt, a->kf_fv_cnt, a->kf_bv_word, a->kf_bv_val,
                        a->kf_bv_cnt, a->kf_word, a->kf_node, a->kf_ids};
-    tb_prof_begin(ctx, "k_vo_recover_switch");
-    hipLaunchKernelGGL(k_vo_recover_switch, dim3(nseq, 6), dim3(256), 0, ctx->stream, W, A, a->pitch, D);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_recover_switch", k_vo_recover_switch, dim3(nseq, 6), dim3(256), 0, W, A, a->pitch, D);
 }
 
 int tbk_vo_recover_ring_add(tb_ctx* ctx, int nseq, const int32_t* d_word, const int32_t* d_node, const int32_t* d_counts, int cap, int pitch,
                             int slot, int32_t* d_word_ring, int32_t* d_node_ring) {
-    tb_prof_begin(ctx, "k_vo_recover_ring_add");
-    hipLaunchKernelGGL(k_vo_recover_ring_add, dim3(nseq, 2), dim3(256), 0, ctx->stream, d_word, d_node, d_counts, cap, pitch, slot,
-                       d_word_ring, d_node_ring);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_recover_ring_add", k_vo_recover_ring_add, dim3(nseq, 2), dim3(256), 0, d_word, d_node, d_counts, cap, pitch,
+                     slot, d_word_ring, d_node_ring);
 }

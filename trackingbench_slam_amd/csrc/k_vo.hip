@@ -510,45 +510,29 @@ int tbk_vo_copy_image(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h,
                       const int32_t* d_idx) {
     if (nimg <= 0) return TB_OK;
     const int bx = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 512);
-    tb_prof_begin(ctx, "k_vo_copy_image");
-    hipLaunchKernelGGL(k_vo_copy_image, dim3(bx, nimg), dim3(256), 0, ctx->stream, d_src, w, h, stride, pitch, d_idx, d_dst);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_copy_image", k_vo_copy_image, dim3(bx, nimg), dim3(256), 0, d_src, w, h, stride, pitch, d_idx, d_dst);
 }
 
 int tbk_vo_track(tb_ctx* ctx, int nseq, const int32_t* d_prev_counts, const uint8_t* d_status, const float* d_keys, const float* d_prev_mp,
                  const uint8_t* d_prev_valid, int pitch, int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, tb_obs* d_obs,
                  int32_t* d_obs_counts, uint8_t* d_outlier) {
     if (nseq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_track");
-    hipLaunchKernelGGL(k_vo_track, dim3(nseq), dim3(256), 0, ctx->stream, d_prev_counts, d_status, d_keys, d_prev_mp, d_prev_valid, pitch,
-                       d_key_counts, d_mp, d_valid, d_obs, d_obs_counts, d_outlier);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_track", k_vo_track, dim3(nseq), dim3(256), 0, d_prev_counts, d_status, d_keys, d_prev_mp, d_prev_valid,
+                     pitch, d_key_counts, d_mp, d_valid, d_obs, d_obs_counts, d_outlier);
 }
 
 int tbk_vo_kf_pack(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, float* d_keys,
                    int32_t* d_key_counts, uint8_t* d_valid, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_kf_pack");
-    hipLaunchKernelGGL(k_vo_kf_pack, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, orb_pitch, pitch, d_keys, d_key_counts,
-                       d_valid, d_idx);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_kf_pack", k_vo_kf_pack, dim3(nseq), dim3(256), 0, d_orb, d_orb_counts, orb_pitch, pitch, d_keys,
+                     d_key_counts, d_valid, d_idx);
 }
 
 int tbk_vo_kf_spawn(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const float* d_depth, const float* d_Tcw,
                     const double K[4], int pitch, float* d_mp, uint8_t* d_valid, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_kf_spawn");
-    hipLaunchKernelGGL(k_vo_kf_spawn, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_depth, d_Tcw, K[0], K[1], K[2], K[3],
-                       pitch, d_mp, d_valid, d_idx);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_kf_spawn", k_vo_kf_spawn, dim3(nseq), dim3(256), 0, d_keys, d_key_counts, d_depth, d_Tcw, K[0], K[1], K[2],
+                     K[3], pitch, d_mp, d_valid, d_idx);
 }
 
 int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
@@ -560,12 +544,9 @@ int tbk_vo_match_carry(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const in
     tb_vo_sigma sig = {};
     for (int l = 0; l < nlevels; l++) sig.v[l] = inv_sigma2[l];
     sig.n = nlevels;
-    tb_prof_begin(ctx, "k_vo_match_carry");
-    hipLaunchKernelGGL(k_vo_match_carry, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts, d_kf_mp,
-                       d_kf_valid, d_kf_counts, pitch, sig, d_win, d_keys, d_key_counts, d_mp, d_valid, d_obs, d_obs_counts, d_outlier);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_match_carry", k_vo_match_carry, dim3(nseq), dim3(256), 0, d_orb, d_orb_counts, d_matches, d_match_counts,
+                     d_kf_mp, d_kf_valid, d_kf_counts, pitch, sig, d_win, d_keys, d_key_counts, d_mp, d_valid, d_obs, d_obs_counts,
+                     d_outlier);
 }
 
 int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_orb, const int32_t* d_orb_counts, const tb_match* d_matches,
@@ -578,20 +559,10 @@ int tbk_vo_proj_carry(tb_ctx* ctx, int nseq, int map_mode, const tb_keypoint* d_
     tb_vo_sigma sig = {};
     for (int l = 0; l < nlevels; l++) sig.v[l] = inv_sigma2[l];
     sig.n = nlevels;
-    if (map_mode) {
-        tb_prof_begin(ctx, "k_vo_proj_carry_map");
-        hipLaunchKernelGGL(k_vo_proj_carry<true>, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts,
-                           match_pitch, d_src_mp, d_src_valid, d_src_rec, d_src_desc, d_src_counts, src_pitch, pitch, sig, d_win, d_keys,
-                           d_key_counts, d_mp, d_valid, d_mp_desc, d_obs, d_obs_counts, d_outlier);
-    } else {
-        tb_prof_begin(ctx, "k_vo_proj_carry_kf");
-        hipLaunchKernelGGL(k_vo_proj_carry<false>, dim3(nseq), dim3(256), 0, ctx->stream, d_orb, d_orb_counts, d_matches, d_match_counts,
-                           match_pitch, d_src_mp, d_src_valid, d_src_rec, d_src_desc, d_src_counts, src_pitch, pitch, sig, d_win, d_keys,
-                           d_key_counts, d_mp, d_valid, d_mp_desc, d_obs, d_obs_counts, d_outlier);
-    }
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, map_mode ? "k_vo_proj_carry_map" : "k_vo_proj_carry_kf", map_mode ? k_vo_proj_carry<true> : k_vo_proj_carry<false>,
+                     dim3(nseq), dim3(256), 0, d_orb, d_orb_counts, d_matches, d_match_counts, match_pitch, d_src_mp, d_src_valid, d_src_rec,
+                     d_src_desc, d_src_counts, src_pitch, pitch, sig, d_win, d_keys, d_key_counts, d_mp, d_valid, d_mp_desc, d_obs, d_obs_counts,
+                     d_outlier);
 }
 
 int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const float* d_depth, const float* d_mp, const uint8_t* d_valid,
@@ -600,12 +571,8 @@ int tbk_vo_kf_append(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const f
                      int map_pitch, const int32_t* d_idx) {
     if (nseq <= 0) return TB_OK;
     if (d_map_rec && (nblk < 1 || slot < 0 || slot >= nblk || map_pitch < 1)) return TB_EINVAL;
-    tb_prof_begin(ctx, "k_vo_kf_append");
-    hipLaunchKernelGGL(k_vo_kf_append, dim3(nseq), dim3(256), 0, ctx->stream, d_key_counts, d_depth, d_mp, d_valid, d_orb_desc, d_Tcw, pitch,
-                       d_mp_desc, d_rec, d_map_rec, d_map_desc, d_map_n, d_map_blocks, nblk, slot, map_pitch, d_idx);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_kf_append", k_vo_kf_append, dim3(nseq), dim3(256), 0, d_key_counts, d_depth, d_mp, d_valid, d_orb_desc,
+                     d_Tcw, pitch, d_mp_desc, d_rec, d_map_rec, d_map_desc, d_map_n, d_map_blocks, nblk, slot, map_pitch, d_idx);
 }
 
 int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const uint8_t* d_src_desc, const int32_t* d_src_n,
@@ -613,23 +580,15 @@ int tbk_vo_map_evict(tb_ctx* ctx, int nseq, const tb_mappoint* d_src_rec, const 
                      int32_t* d_dst_blocks) {
     if (nseq <= 0) return TB_OK;
     if (nblk < 1 || map_pitch < 1) return TB_EINVAL;
-    tb_prof_begin(ctx, "k_vo_map_evict");
-    hipLaunchKernelGGL(k_vo_map_evict, dim3(8, nseq), dim3(256), 0, ctx->stream, d_src_rec, d_src_desc, d_src_n, d_src_blocks, nblk, map_pitch,
-                       d_dst_rec, d_dst_desc, d_dst_n, d_dst_blocks);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_map_evict", k_vo_map_evict, dim3(8, nseq), dim3(256), 0, d_src_rec, d_src_desc, d_src_n, d_src_blocks, nblk,
+                     map_pitch, d_dst_rec, d_dst_desc, d_dst_n, d_dst_blocks);
 }
 
 int tbk_vo_reset_seq(tb_ctx* ctx, int nseq, const int32_t* d_mask, const float* d_Tcw0, float* d_Tcw, int32_t* d_key_counts,
                      int32_t* d_kf_counts, int32_t* d_kf_fv_counts, int32_t* d_kf_bv_counts, int32_t* d_cell_start, int ncell) {
     if (nseq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_reset_seq");
-    hipLaunchKernelGGL(k_vo_reset_seq, dim3(nseq), dim3(256), 0, ctx->stream, d_mask, d_Tcw0, d_Tcw, d_key_counts, d_kf_counts,
-                       d_kf_fv_counts, d_kf_bv_counts, d_cell_start, ncell);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_reset_seq", k_vo_reset_seq, dim3(nseq), dim3(256), 0, d_mask, d_Tcw0, d_Tcw, d_key_counts, d_kf_counts,
+                     d_kf_fv_counts, d_kf_bv_counts, d_cell_start, ncell);
 }
 
 int tbk_vo_hold(tb_ctx* ctx, int nseq, const tb_vo_hold_args* a) {
@@ -638,21 +597,14 @@ int tbk_vo_hold(tb_ctx* ctx, int nseq, const tb_vo_hold_args* a) {
     VoRows R;
     const int groups = vo_hold_rows(a, R);
     const VoHoldFix F = {a->Tcw[0], a->Tcw[1], a->cur.n_inliers, a->cur.mcounts, a->cur.mflags};
-    tb_prof_begin(ctx, "k_vo_hold");
-    hipLaunchKernelGGL(k_vo_hold, dim3(nseq, groups), dim3(256), 0, ctx->stream, a->mask, F, R);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_hold", k_vo_hold, dim3(nseq, groups), dim3(256), 0, a->mask, F, R);
 }
 
 int tbk_vo_kf_gather(tb_ctx* ctx, int nkf, const int32_t* d_idx, const float* d_keys, const int32_t* d_key_counts, int pitch,
                      float* d_out_keys, int32_t* d_out_counts) {
     if (nkf <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_kf_gather");
-    hipLaunchKernelGGL(k_vo_kf_gather, dim3(nkf), dim3(256), 0, ctx->stream, d_idx, d_keys, d_key_counts, pitch, d_out_keys, d_out_counts);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_kf_gather", k_vo_kf_gather, dim3(nkf), dim3(256), 0, d_idx, d_keys, d_key_counts, pitch, d_out_keys,
+                     d_out_counts);
 }
 
 int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, const tb_vo_frame_out* cur, const float* d_mp,
@@ -665,11 +617,7 @@ int tbk_vo_kf_snapshot(tb_ctx* ctx, int nkf, const int32_t* d_idx, int pitch, co
             TB_HIP(ctx, hipMemcpyAsync(R.r[i].dst, R.r[i].src, (size_t)nkf * R.r[i].stride * R.r[i].elem, hipMemcpyDeviceToDevice, ctx->stream));
         return TB_OK;
     }
-    tb_prof_begin(ctx, "k_vo_kf_snapshot");
-    hipLaunchKernelGGL(k_vo_kf_snapshot, dim3(nkf, groups), dim3(256), 0, ctx->stream, d_idx, R);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_kf_snapshot", k_vo_kf_snapshot, dim3(nkf, groups), dim3(256), 0, d_idx, R);
 }
 
 /* ---- window BA of the optical-flow loop (include/tb_capi.h, tb_vo_window_ba_enable): between two keyframes key i of every frame
@@ -790,12 +738,8 @@ int tbk_vo_seg_start(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* 
                      uint8_t* d_seg_spawned) {
     if (nseq <= 0) return TB_OK;
     if (pitch < 1 || nslot < 2) return TB_EINVAL;
-    tb_prof_begin(ctx, "k_vo_seg_start");
-    hipLaunchKernelGGL(k_vo_seg_start, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_depth, d_mp, d_valid, d_Tcw, pitch, nslot,
-                       d_seg_keys, d_seg_ok, d_seg_pose, d_seg_pts, d_seg_spawned);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_seg_start", k_vo_seg_start, dim3(nseq), dim3(256), 0, d_keys, d_key_counts, d_depth, d_mp, d_valid, d_Tcw,
+                     pitch, nslot, d_seg_keys, d_seg_ok, d_seg_pose, d_seg_pts, d_seg_spawned);
 }
 
 int tbk_vo_seg_log(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_key_counts, const uint8_t* d_valid, const uint8_t* d_outlier,
@@ -803,33 +747,21 @@ int tbk_vo_seg_log(tb_ctx* ctx, int nseq, const float* d_keys, const int32_t* d_
                    float* d_seg_keys, uint8_t* d_seg_ok, float* d_seg_pose) {
     if (nseq <= 0) return TB_OK;
     if (pitch < 1 || slot < 1 || slot >= nslot) return TB_EINVAL;
-    tb_prof_begin(ctx, "k_vo_seg_log");
-    hipLaunchKernelGGL(k_vo_seg_log, dim3(nseq), dim3(256), 0, ctx->stream, d_keys, d_key_counts, d_valid, d_outlier, d_obs_counts, d_Tcw,
-                       d_seg_spawned, pitch, nslot, slot, d_seg_keys, d_seg_ok, d_seg_pose);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_seg_log", k_vo_seg_log, dim3(nseq), dim3(256), 0, d_keys, d_key_counts, d_valid, d_outlier, d_obs_counts,
+                     d_Tcw, d_seg_spawned, pitch, nslot, slot, d_seg_keys, d_seg_ok, d_seg_pose);
 }
 
 int tbk_vo_seg_window(tb_ctx* ctx, int nseq, const float* d_seg_keys, const uint8_t* d_seg_ok, int pitch, int nslot, int min_obs,
                       tb_ba_obs* d_obs, int32_t* d_obs_counts, int32_t* d_n_points) {
     if (nseq <= 0) return TB_OK;
     if (pitch < 1 || nslot < 2 || min_obs < 1) return TB_EINVAL;
-    tb_prof_begin(ctx, "k_vo_seg_window");
-    hipLaunchKernelGGL(k_vo_seg_window, dim3(nseq), dim3(256), 0, ctx->stream, d_seg_keys, d_seg_ok, pitch, nslot, min_obs, d_obs,
-                       d_obs_counts, d_n_points);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_seg_window", k_vo_seg_window, dim3(nseq), dim3(256), 0, d_seg_keys, d_seg_ok, pitch, nslot, min_obs, d_obs,
+                     d_obs_counts, d_n_points);
 }
 
 int tbk_vo_seg_adopt(tb_ctx* ctx, int nseq, const float* d_win_pose, const int32_t* d_n_points, const double* d_stats, int nslot,
                      int min_points, float* d_Tcw, uint8_t* d_adopted) {
     if (nseq <= 0) return TB_OK;
-    tb_prof_begin(ctx, "k_vo_seg_adopt");
-    hipLaunchKernelGGL(k_vo_seg_adopt, dim3(nseq), dim3(64), 0, ctx->stream, d_win_pose, d_n_points, d_stats, nslot, min_points, d_Tcw,
-                       d_adopted);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_vo_seg_adopt", k_vo_seg_adopt, dim3(nseq), dim3(64), 0, d_win_pose, d_n_points, d_stats, nslot, min_points,
+                     d_Tcw, d_adopted);
 }

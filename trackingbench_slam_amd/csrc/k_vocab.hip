@@ -540,13 +540,7 @@ struct Work {   /* device allocations of one training run */
 inline unsigned blocks(size_t n) { return (unsigned)((n + VT - 1) / VT); }
 }  // namespace
 
-#define VLAUNCH(name, grid, block, ...)                                              \
-    do {                                                                             \
-        tb_prof_begin(ctx, #name);                                                   \
-        hipLaunchKernelGGL(name, grid, block, 0, ctx->stream, __VA_ARGS__);          \
-        tb_prof_end(ctx);                                                            \
-        TB_HIP(ctx, hipGetLastError());                                              \
-    } while (0)
+#define VLAUNCH(name, grid, block, ...) TB_TRY(tb_launch(ctx, #name, name, grid, block, 0, __VA_ARGS__))
 
 static int voc_scan(tb_ctx* ctx, int n, const int32_t* in, int32_t* out, int32_t* sums) {
     const int nt = (n + 1023) / 1024;

@@ -14,6 +14,7 @@
 #include <climits>
 #include <cmath>
 #include <memory>
+#include <mutex>
 
 /* ------------------------------------------------------------------ errors / context */
 int tb_fail(tb_ctx* ctx, int code, const char* fmt, ...) {
@@ -40,6 +41,26 @@ int tb_scratch(tb_ctx* ctx, int slot, size_t bytes, void** out) { /* only called
         ctx->scratch_cap[slot] = cap;
     }
     *out = ctx->scratch[slot];
+    return TB_OK;
+}
+
+/* The library's only write of a kernel's dynamic-LDS limit. The limit belongs to the (function, device) pair and is
+ * process-wide, while the size a call needs depends on its shapes: a call that wrote its own size would lower the limit
+ * under another context's launch on another host thread, or under a captured graph's later replays. So the limit only ever
+ * rises: the largest value set so far is kept per (kernel, device) and the runtime is called only for a larger one. The
+ * mutex guards the table; it does not close the window between one thread's set and another thread's launch -- that the
+ * value is never lowered does, every launch finds at least what its own call asked for. Requests within the 64 KB every
+ * kernel has by default need no call. */
+int tb_lds_limit(tb_ctx* ctx, const void* kernel, size_t bytes) {
+    if (bytes <= 64 * 1024) return TB_OK;
+    static std::mutex lock;
+    static std::map<std::pair<const void*, int>, size_t> limits;
+    std::lock_guard<std::mutex> guard(lock);
+    size_t& limit = limits[std::make_pair(kernel, ctx->device)];
+    if (bytes > limit) {
+        TB_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        limit = bytes;
+    }
     return TB_OK;
 }
 
@@ -687,12 +708,8 @@ int tb_extractor_copy_results_dev(tb_extractor* ex, int n, tb_keypoint* kps, uin
     if (!ex || n < 1 || n > ex->max_images || !kps || !desc || !counts || cap < 1) return TB_EINVAL;
     tb_ctx* ctx = ex->ctx;
     const int rows = std::min(cap, ex->g.selCap);
-    tb_prof_begin(ctx, "k_copy_results");
-    hipLaunchKernelGGL(k_copy_results, dim3((rows * 15 + 255) / 256, n), dim3(256), 0, ctx->stream, ex->d_kps, ex->d_desc,
-                       ex->d_counts, ex->g.selCap, kps, desc, counts, cap);
-    tb_prof_end(ctx);
-    TB_HIP(ctx, hipGetLastError());
-    return TB_OK;
+    return tb_launch(ctx, "k_copy_results", k_copy_results, dim3((rows * 15 + 255) / 256, n), dim3(256), 0, ex->d_kps, ex->d_desc,
+                     ex->d_counts, ex->g.selCap, kps, desc, counts, cap);
 }
 
 int tb_extractor_candidates_host(tb_extractor* ex, int index, int level, tb_corner* out, int cap, int* count) {

@@ -67,6 +67,7 @@ int tb_fail(tb_ctx* ctx, int code, const char* fmt, ...);
 void tb_prof_begin(tb_ctx* ctx, const char* name);
 void tb_prof_end(tb_ctx* ctx);
 int tb_scratch(tb_ctx* ctx, int slot, size_t bytes, void** out);
+int tb_lds_limit(tb_ctx* ctx, const void* kernel, size_t bytes); /* before a launch with `bytes` of dynamic LDS */
 
 #define TB_HIP(ctx, call)                                                                     \
     do {                                                                                      \
@@ -82,6 +83,19 @@ int tb_scratch(tb_ctx* ctx, int slot, size_t bytes, void** out);
         int rc_ = (call);       \
         if (rc_) return rc_;    \
     } while (0)
+
+/* Every kernel launch of the library: `kernel` on the context's stream, timed as one profile record `name`, and a launch
+ * the runtime refused reported through tb_fail. name == nullptr leaves the profile alone: a launch inside an explicit
+ * tb_prof_begin / tb_prof_end pair (one record over several launches) or one that is not timed at all. */
+template <class... P, class... A>
+static int tb_launch(tb_ctx* ctx, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
+    if (name) tb_prof_begin(ctx, name);
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+    if (name) tb_prof_end(ctx);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return tb_fail(ctx, TB_EDEVICE, "launch of %s: %s", name ? name : "a kernel", hipGetErrorString(e));
+    return TB_OK;
+}
 
 /* The device buffers of one handle: every pointer tb_dev_alloc hands out is recorded here, and release() frees them all, so a
  * handle has no free list to keep in step with its allocations and a group that failed half way is not lost track of. */
