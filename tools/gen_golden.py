@@ -6,6 +6,13 @@ built here (8c), so these vectors are produced by OUR oracle on the reference's 
 (data/left.png, data/right.png -> tests/golden/*.pgm) and on seeded synthetic inputs.  They pin
 oracle<->HIP agreement and guard the oracle against regressions; they do NOT pin agreement with
 genuine OpenCV / g2o ("parity unpinned").
+
+tests/golden/kitti00_disparity_1241x376.pgm.gz is not made here: it holds the decoded pixels of the reference's data/disparity.png
+(8-bit grey, 1241 x 376) behind the header "P5\n1241 376\n255\n", the layout of the two image fixtures, gzip-wrapped (the pixels
+hold no zero byte: git would show the plain file as text). Written once with PIL + numpy:
+gzip.GzipFile(filename="", mode="wb", fileobj=open(path, "wb"), compresslevel=9, mtime=0).write(
+    b"P5\n1241 376\n255\n" + numpy.asarray(PIL.Image.open(png)).tobytes()).
+tests/test_oracle_disparity.py asserts its pixel SHA-1.
 """
 import hashlib
 import os
