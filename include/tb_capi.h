@@ -520,6 +520,41 @@ int tb_pose_opt(tb_ctx* ctx, const double K[4], const float Tcw_in[16], const tb
 int tb_pose_opt_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const float* Tcw_in,
                           const tb_obs* obs, const int32_t* counts, int obs_pitch, uint8_t* outlier,
                           float* Tcw_out, int32_t* n_inliers, double* stats);
+/* LocalBA::LinearTriangle, LocalBA.cpp:24-43: two-view DLT with known poses, batched and device-resident, with the gates a map
+ * needs before it takes the point. Per point pair, in float64, one operation per statement, only + - * / sqrt
+ * (tests/triangulate_reference.py is the definition, statement for statement):
+ *   pixels     x = (u - cx) / fx, y = (v - cy) / fy. DEVIATION: the reference passes px_un -- pixels -- against a bare Tcw, and
+ *              its rows p * Tcw.row(2) - Tcw.row(0) describe a projection only in normalised coordinates
+ *   A          the four rows of LocalBA.cpp:31-35 on (x0, y0) / Tcw0 and (x1, y1) / Tcw1
+ *   solve      M = A^T A, 6 cyclic Jacobi sweeps in the pair order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) with the rotation of the
+ *              shim's LocalBA::LinearTriangle, a rotation skipped only where M[p][q] == 0, no convergence test (the reference
+ *              calls Eigen's JacobiSVD); the column of V at the smallest diagonal entry, the lowest index on a tie;
+ *              X = V[0..2] / V[3]
+ *   flags      the first failing gate decides:
+ *              0  not a candidate: beyond counts[p], or skip set
+ *              1  accepted: points = (float)X
+ *              2  V[3] == 0, or (float)X is not finite
+ *              3  the depth (row 2 of Tcw applied to X) is not above 0 in view 0 or in view 1
+ *              4  parallax: the cosine of the two pixel rays R^T (x, y, 1) in the world frame is not below cos_parallax_max
+ *              5  reprojection: squared pixel error * inv_sigma2 is above chi2_max in view 0 or in view 1
+ * Pair p: counts[p] point pairs (pitch apart; counts nullable = pitch each); xy0 / xy1 [npairs][pitch][2] pixels in view 0 /
+ * view 1; Tcw0 / Tcw1 [npairs][16]; K = fx, fy, cx, cy (host); inv_sigma2_0 / _1 [npairs][pitch] nullable (= 1); skip
+ * [npairs][pitch] nullable (non-zero: not a candidate). Out: points [npairs][pitch][3] float (WRITTEN ONLY WHERE ACCEPTED), flags
+ * [npairs][pitch] bytes, tally [npairs][6] int32 (how many entries of the row carry each code; code 0 counts the whole pitch).
+ * Device pointers, asynchronous on the context's stream; at most 65535 pairs per call.
+ * tb_linear_triangle: the host form, n point pairs of one pose pair on the batched entry (host pointers; points is zero where a
+ * pair was not accepted). The shim's LocalBA::LinearTriangle keeps its own host loop. */
+typedef struct tb_triangulate_params {
+    double cos_parallax_max;   /* 0.9998: reject when the rays' cosine is >= this */
+    double chi2_max;           /* 5.991: reject when either view's squared reprojection error * inv_sigma2 exceeds it */
+} tb_triangulate_params;
+int tb_linear_triangle_batch_dev(tb_ctx* ctx, int npairs, const float* xy0, const float* xy1, const int32_t* counts, int pitch,
+                                 const float* Tcw0, const float* Tcw1, const double K[4], const float* inv_sigma2_0,
+                                 const float* inv_sigma2_1, const uint8_t* skip, const tb_triangulate_params* prm, float* points,
+                                 uint8_t* flags, int32_t* tally);
+int tb_linear_triangle(tb_ctx* ctx, const float* xy0, const float* xy1, int n, const float Tcw0[16], const float Tcw1[16],
+                       const double K[4], const float* inv_sigma2_0, const float* inv_sigma2_1, const uint8_t* skip,
+                       const tb_triangulate_params* prm, float* points, uint8_t* flags, int32_t tally[6]);
 /* SURVEY 8(f) row 2, first part -- the optical-flow matcher.
  * tb_optical_flow_pyr_lk replaces the call cv::calcOpticalFlowPyrLK(prev, next, prev_pts, next_pts, status, err,
  * Size(win, win), max_level) of matcher.cpp:744 (default criteria: 30 iterations / eps 0.01, flags 0,
@@ -661,7 +696,7 @@ void tb_vo_destroy(tb_vo* vo);
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0);
 /* left / right: nseq device images each, row stride `stride` bytes, `pitch` bytes apart (read during the call's kernels; they
  * may be reused once the stream has passed them). right may be NULL on a step that is not a keyframe (TB_EINVAL on one that
- * is). TB_ESTATE before the first reset. Asynchronous on the context's stream. */
+ * is; a mono loop, tb_vo_mono_enable below, reads it at frame 0 only). TB_ESTATE before the first reset. Asynchronous on the context's stream. */
 int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int stride, size_t pitch);
 /* Device views of the state after the last step (valid until the next step; every output nullable):
  * Tcw [nseq][16]; keys_xy [nseq][key_pitch][2] float; map_points [nseq][key_pitch][3] float and mp_valid [nseq][key_pitch]
@@ -952,6 +987,40 @@ int tb_vo_window_state_dev(tb_vo* vo, const float** seg_keys, const uint8_t** se
                            const uint8_t** seg_spawned, const tb_ba_obs** obs, const int32_t** obs_counts, const int32_t** n_points,
                            const double** stats, const uint8_t** adopted, const float** ba_pose, const float** ba_pts, int* slot,
                            int* nslots);
+/* Monocular map growth in a TB_VO_OPFLOW loop in lock-step (off unless enabled; a loop that does not enable it launches what it
+ * launched before): after frame 0 the keyframes need no right image, and new map points come from triangulating the LK tracks.
+ * The reference has no such loop; its LocalBA::LinearTriangle is the operator (tb_linear_triangle_batch_dev above) and the
+ * composition is restated on the CPU oracle in tests/vo_mono_reference.py. Between two keyframes key i of every frame is the
+ * same physical point (k_vo_track keeps the index), so a key seen at the keyframe and now is a point pair with two known poses.
+ *   frame 0        unchanged: ORB, stereo depths, stereo points; it needs `right`, which fixes the scale. Then kf_keys = the key
+ *                  list as the keyframe left it, kf_Tcw = the frame's pose, alive[i] = 1
+ *   tracking       unchanged, plus alive[i] &= status[i] (LK's status of the step)
+ *   keyframe t > 0 `right` is not read and may be NULL. After the tracking half (alive updated as above):
+ *     triangulate  tb_linear_triangle_batch_dev(kf_keys, the frame's keys, the frame's key counts, kf_Tcw, the optimised Tcw,
+ *                  skip[i] = valid[i] || !alive[i], inv_sigma2 NULL) into tri_points / tri_flags / tri_tally; key i gets the map
+ *                  point tri_points[i] where tri_flags[i] == 1
+ *     merge        the new key list, by one workgroup per sequence (k_vo_kf_merge): first every key that has a map point, in
+ *                  index order, with its point (their number -> survivors[s]); then the frame's ORB keys in extractor order,
+ *                  without a map point, leaving out a key whose cell x cell pixel cell ((int)x / cell, (int)y / cell) holds a
+ *                  survivor (only survivors mark cells; a key outside the ceil(width / cell) x ceil(height / cell) grid marks
+ *                  and meets nothing), until the list holds key_pitch keys (their number -> added[s])
+ *     afterwards   kf_keys = the new list, kf_Tcw = Tcw, alive = 1. No stereo operator runs and no depth is made
+ * A mono loop makes no host synchronisation and no host <-> device copy after the first step.
+ * tb_vo_mono_enable: before the first tb_vo_reset_dev. TB_EUNSUPPORTED: any tracker but TB_VO_OPFLOW, or a loop with the window
+ * BA enabled (tb_vo_window_ba_enable on a mono loop is refused the same way); TB_ESTATE: after a reset, or enabled already;
+ * TB_EINVAL: null or non-finite parameters, cell <= 0, or a cell whose occupancy bitmap (one bit per cell, in LDS) is above 32 KB.
+ * tb_vo_reset_seq_dev and tb_vo_step_ragged_dev are TB_EUNSUPPORTED on a mono loop; tb_vo_reset_dev clears the state.
+ * tb_vo_mono_state_dev: device views, each nullable (TB_ESTATE when not enabled): kf_keys_xy [nseq][key_pitch][2], kf_Tcw
+ * [nseq][16], alive [nseq][key_pitch] bytes, tri_points [nseq][key_pitch][3] (meaningful where tri_flags is 1), tri_flags
+ * [nseq][key_pitch] bytes, tri_tally [nseq][6], survivors [nseq], added [nseq]: the tri_* and the two counts are the last mono
+ * keyframe's (zero before the first). */
+typedef struct tb_vo_mono {
+    double cos_parallax_max, chi2_max;   /* tb_triangulate_params (0.9998, 5.991) */
+    int cell;                            /* side of the merge's occupancy cells in pixels (8) */
+} tb_vo_mono;
+int tb_vo_mono_enable(tb_vo* vo, const tb_vo_mono* prm);
+int tb_vo_mono_state_dev(tb_vo* vo, const float** kf_keys_xy, const float** kf_Tcw, const uint8_t** alive, const float** tri_points,
+                         const uint8_t** tri_flags, const int32_t** tri_tally, const int32_t** survivors, const int32_t** added);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

@@ -55,6 +55,7 @@ EXPORTS = [
     "tb_vo_window_ba_enable", "tb_vo_window_state_dev",
     "tb_lsh_draw_bits", "tb_lsh_create", "tb_lsh_destroy", "tb_lsh_info", "tb_match_lsh", "tb_search_by_nn", "tb_search_by_nn_batch_dev",
     "tb_vo_create_lsh",
+    "tb_linear_triangle", "tb_linear_triangle_batch_dev", "tb_vo_mono_enable", "tb_vo_mono_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -271,6 +272,16 @@ class VOWindowBA(C.Structure):
     _fields_ = [("iters", C.c_int), ("fixed", C.c_int), ("min_obs", C.c_int), ("min_points", C.c_int)]
 
 
+class VOMono(C.Structure):
+    """tb_vo_mono of include/tb_capi.h"""
+    _fields_ = [("cos_parallax_max", C.c_double), ("chi2_max", C.c_double), ("cell", C.c_int)]
+
+
+class TriangulateParams(C.Structure):
+    """tb_triangulate_params of include/tb_capi.h"""
+    _fields_ = [("cos_parallax_max", C.c_double), ("chi2_max", C.c_double)]
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
@@ -432,6 +443,19 @@ class VO:
         out = {k: q.value for k, q in zip(names, ptrs)}
         out["slot"], out["nslots"] = slot.value, nslots.value
         return out
+
+    def mono_enable(self, prm):
+        """tb_vo_mono_enable with a VOMono (None: a null pointer): returns the status code (0 or a negative TB_E* code), so the
+        state and argument checks can be tested."""
+        return lib().tb_vo_mono_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def mono_state_dev(self):
+        """tb_vo_mono_state_dev: dict of device pointers (kf_keys_xy, kf_Tcw, alive, tri_points, tri_flags, tri_tally, survivors,
+        added); TB_ESTATE when the mono mode is not enabled."""
+        names = ("kf_keys_xy", "kf_Tcw", "alive", "tri_points", "tri_flags", "tri_tally", "survivors", "added")
+        ptrs = [C.c_void_p() for _ in names]
+        self.ctx.check(lib().tb_vo_mono_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        return {k: q.value for k, q in zip(names, ptrs)}
 
     def mp_desc_dev(self):
         """dict of device pointers of a projection tracker's map-point descriptors (mp_desc, kf_mp_desc)."""
@@ -916,6 +940,36 @@ class Context:
         n = C.c_int(0)
         self.check(lib().tb_pose_opt(self._h, _p(K), _p(Tcw), _p(obs), len(obs), _p(outl), _p(out), C.byref(n), _p(stats)))
         return n.value, out.reshape(4, 4), outl, stats
+
+    def linear_triangle(self, xy0, xy1, Tcw0, Tcw1, K, inv_sigma2_0=None, inv_sigma2_1=None, skip=None, cos_parallax_max=0.9998,
+                        chi2_max=5.991):
+        """tb_linear_triangle: n point pairs (xy0 / xy1 [n][2] pixels) of one pose pair -> (points [n][3] float32, zero where not
+        accepted; flags [n] uint8; tally [6] int32)"""
+        xy0 = np.ascontiguousarray(xy0, np.float32).reshape(-1, 2)
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        n = len(xy0)
+        assert len(xy1) == n
+        opt = [None if a is None else np.ascontiguousarray(a, t).reshape(n) for a, t in
+               ((inv_sigma2_0, np.float32), (inv_sigma2_1, np.float32), (skip, np.uint8))]
+        K = np.ascontiguousarray(K, np.float64)
+        T0 = np.ascontiguousarray(Tcw0, np.float32).reshape(16)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        prm = TriangulateParams(float(cos_parallax_max), float(chi2_max))
+        pts, flags, tally = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8), np.zeros(6, np.int32)
+        self.check(lib().tb_linear_triangle(self._h, _p(xy0), _p(xy1), n, _p(T0), _p(T1), _p(K), _p(opt[0]), _p(opt[1]), _p(opt[2]),
+                                            C.byref(prm), _p(pts), _p(flags), _p(tally)))
+        return pts, flags, tally
+
+    def linear_triangle_batch_dev(self, npairs, xy0_ptr, xy1_ptr, counts_ptr, pitch, Tcw0_ptr, Tcw1_ptr, K, inv_sigma2_0_ptr,
+                                  inv_sigma2_1_ptr, skip_ptr, points_ptr, flags_ptr, tally_ptr, cos_parallax_max=0.9998, chi2_max=5.991):
+        """tb_linear_triangle_batch_dev: device pointers (0 / None for the nullable ones), asynchronous on the context's stream.
+        Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        prm = TriangulateParams(float(cos_parallax_max), float(chi2_max))
+        v = lambda q: C.c_void_p(q or None)
+        return lib().tb_linear_triangle_batch_dev(self._h, int(npairs), v(xy0_ptr), v(xy1_ptr), v(counts_ptr), int(pitch), v(Tcw0_ptr),
+                                                  v(Tcw1_ptr), _p(K), v(inv_sigma2_0_ptr), v(inv_sigma2_1_ptr), v(skip_ptr),
+                                                  C.byref(prm), v(points_ptr), v(flags_ptr), v(tally_ptr))
 
     def local_ba(self, K, poses, nfixed, pts, obs, iters=10):
         K = np.ascontiguousarray(K, np.float64)

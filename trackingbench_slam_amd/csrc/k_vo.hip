@@ -765,3 +765,122 @@ int tbk_vo_seg_adopt(tb_ctx* ctx, int nseq, const float* d_win_pose, const int32
     return tb_launch(ctx, "k_vo_seg_adopt", k_vo_seg_adopt, dim3(nseq), dim3(64), 0, d_win_pose, d_n_points, d_stats, nslot, min_points,
                      d_Tcw, d_adopted);
 }
+
+/* ---- mono mode of the optical-flow loop (include/tb_capi.h, tb_vo_mono) */
+
+/* After a tracking half: a key stays a triangulation candidate while LK has held it in every frame since the keyframe
+ * (alive[i] &= status[i]); skip[i] = it has a map point already, or it was lost. */
+__global__ void __launch_bounds__(256)
+k_vo_mono_alive(const int32_t* __restrict__ key_counts, const uint8_t* __restrict__ status, const uint8_t* __restrict__ valid, int pitch,
+                uint8_t* __restrict__ alive, uint8_t* __restrict__ skip) {
+    const int s = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(max(key_counts[s], 0), pitch);
+    if (i >= n) return;
+    const size_t o = (size_t)s * pitch + i;
+    const uint8_t a = alive[o] && status[o] ? 1 : 0;
+    alive[o] = a;
+    skip[o] = valid[o] || !a ? 1 : 0;
+}
+
+/* The occupancy cell of a pixel, -1 outside the cw x ch grid (and for a coordinate no int holds) */
+__device__ __forceinline__ int vo_merge_cell(float x, float y, int cell, int cw, int ch) {
+    if (!(fabsf(x) < 1.0e9f) || !(fabsf(y) < 1.0e9f)) return -1;
+    const int cx = (int)x / cell, cy = (int)y / cell;
+    if (cx < 0 || cx >= cw || cy < 0 || cy >= ch) return -1;
+    return cy * cw + cx;
+}
+
+/* Mono keyframe: the new key list of sequence s, from side src of the ping-pong into side dst (never in place).
+ *   survivors  every key that has a map point -- valid[i], or triangulated in this step (tri_flags[i] == 1: its point is
+ *              tri_points[i]) -- in index order, with its point; each marks its cell in the LDS bitmap (cw * ch bits)
+ *   new keys   the ORB keys in extractor order, without a map point, except those whose cell holds a survivor, while the list
+ *              has room (pitch keys)
+ * kf_keys takes the new list and alive = 1: the next segment's keyframe. Both compactions are tb_block_ordered_slot's. */
+__global__ void __launch_bounds__(256)
+k_vo_kf_merge(const tb_keypoint* __restrict__ orb, const int32_t* __restrict__ orb_counts, int orb_pitch, int pitch, int cell, int cw, int ch,
+              const float* __restrict__ src_keys, const int32_t* __restrict__ src_counts, const float* __restrict__ src_mp,
+              const uint8_t* __restrict__ src_valid, const float* __restrict__ tri_points, const uint8_t* __restrict__ tri_flags,
+              float* __restrict__ keys, int32_t* __restrict__ key_counts, float* __restrict__ mp, uint8_t* __restrict__ valid,
+              float* __restrict__ kf_keys, uint8_t* __restrict__ alive, int32_t* __restrict__ survivors, int32_t* __restrict__ added) {
+    extern __shared__ unsigned int vo_bitmap[];
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int ncell = cw * ch, nword = (ncell + 31) >> 5;
+    const int n = min(max(src_counts[s], 0), pitch);
+    const int m = min(min(max(orb_counts[s], 0), orb_pitch), pitch);
+    const size_t o = (size_t)s * pitch;
+    const tb_keypoint* K = orb + (size_t)s * orb_pitch;
+    for (int w = tid; w < nword; w += 256) vo_bitmap[w] = 0u;
+    __syncthreads();
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        bool ok = false, tri = false;
+        if (i < n) {
+            tri = tri_flags[o + i] == 1;
+            ok = tri || src_valid[o + i];
+        }
+        const int at = tb_block_ordered_slot(ok, base, wsum);
+        if (ok) {   /* at <= i < pitch */
+            const float x = src_keys[2 * (o + i)], y = src_keys[2 * (o + i) + 1];
+            const float* X = tri ? tri_points + 3 * (o + i) : src_mp + 3 * (o + i);
+            keys[2 * (o + at)] = x; keys[2 * (o + at) + 1] = y;
+            kf_keys[2 * (o + at)] = x; kf_keys[2 * (o + at) + 1] = y;
+            mp[3 * (o + at)] = X[0]; mp[3 * (o + at) + 1] = X[1]; mp[3 * (o + at) + 2] = X[2];
+            valid[o + at] = 1;
+            const int c = vo_merge_cell(x, y, cell, cw, ch);
+            if (c >= 0 && c < ncell) atomicOr(&vo_bitmap[c >> 5], 1u << (c & 31));
+        }
+    }
+    const int nsurv = base;
+    __syncthreads();   /* the bitmap is complete */
+    for (int j0 = 0; j0 < m && base < pitch; j0 += 256) {   /* base is the same in every thread */
+        const int j = j0 + tid;
+        bool ok = false;
+        float x = 0.f, y = 0.f;
+        if (j < m) {
+            x = K[j].x; y = K[j].y;
+            const int c = vo_merge_cell(x, y, cell, cw, ch);
+            ok = !(c >= 0 && c < ncell && ((vo_bitmap[c >> 5] >> (c & 31)) & 1u));
+        }
+        const int at = tb_block_ordered_slot(ok, base, wsum);
+        if (ok && at < pitch) {
+            keys[2 * (o + at)] = x; keys[2 * (o + at) + 1] = y;
+            kf_keys[2 * (o + at)] = x; kf_keys[2 * (o + at) + 1] = y;
+            mp[3 * (o + at)] = 0.f; mp[3 * (o + at) + 1] = 0.f; mp[3 * (o + at) + 2] = 0.f;
+            valid[o + at] = 0;
+        }
+    }
+    const int total = min(base, pitch);
+    for (int k = tid; k < pitch; k += 256) {
+        alive[o + k] = 1;
+        if (k >= total) valid[o + k] = 0;
+    }
+    if (tid == 0) { key_counts[s] = total; survivors[s] = nsurv; added[s] = total - nsurv; }
+}
+
+size_t tbk_vo_merge_bitmap_bytes(int width, int height, int cell) {
+    const size_t cw = ((size_t)width + cell - 1) / cell, ch = ((size_t)height + cell - 1) / cell;
+    return (cw * ch + 31) / 32 * 4;
+}
+
+int tbk_vo_mono_alive(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const uint8_t* d_status, const uint8_t* d_valid, int pitch,
+                      uint8_t* d_alive, uint8_t* d_skip) {
+    if (nseq <= 0) return TB_OK;
+    return tb_launch(ctx, "k_vo_mono_alive", k_vo_mono_alive, dim3((pitch + 255) / 256, nseq), dim3(256), 0, d_key_counts, d_status, d_valid,
+                     pitch, d_alive, d_skip);
+}
+
+int tbk_vo_kf_merge(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, int width,
+                    int height, int cell, const float* d_src_keys, const int32_t* d_src_counts, const float* d_src_mp,
+                    const uint8_t* d_src_valid, const float* d_tri_points, const uint8_t* d_tri_flags, float* d_keys,
+                    int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, float* d_kf_keys, uint8_t* d_alive, int32_t* d_survivors,
+                    int32_t* d_added) {
+    if (nseq <= 0) return TB_OK;
+    if (cell < 1 || pitch < 1 || width < 1 || height < 1) return TB_EINVAL;
+    const size_t lds = tbk_vo_merge_bitmap_bytes(width, height, cell);
+    if (lds > TB_VO_MERGE_BITMAP_MAX) return tb_fail(ctx, TB_EINVAL, "k_vo_kf_merge: a bitmap of %zu bytes (cell %d)", lds, cell);
+    return tb_launch(ctx, "k_vo_kf_merge", k_vo_kf_merge, dim3(nseq), dim3(256), lds, d_orb, d_orb_counts, orb_pitch, pitch, cell,
+                     (width + cell - 1) / cell, (height + cell - 1) / cell, d_src_keys, d_src_counts, d_src_mp, d_src_valid, d_tri_points,
+                     d_tri_flags, d_keys, d_key_counts, d_mp, d_valid, d_kf_keys, d_alive, d_survivors, d_added);
+}

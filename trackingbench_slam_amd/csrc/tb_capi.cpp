@@ -1952,6 +1952,60 @@ int tb_pose_opt(tb_ctx* ctx, const double K[4], const float Tcw_in[16], const tb
     return TB_OK;
 }
 
+/* ------------------------------------------------------------------ linear triangulation */
+static bool triangulate_params_ok(const tb_triangulate_params* prm) {
+    return prm && std::isfinite(prm->cos_parallax_max) && std::isfinite(prm->chi2_max);
+}
+
+int tb_linear_triangle_batch_dev(tb_ctx* ctx, int npairs, const float* xy0, const float* xy1, const int32_t* counts, int pitch,
+                                 const float* Tcw0, const float* Tcw1, const double K[4], const float* inv_sigma2_0,
+                                 const float* inv_sigma2_1, const uint8_t* skip, const tb_triangulate_params* prm, float* points,
+                                 uint8_t* flags, int32_t* tally) {
+    TB_ENTER(ctx);
+    if (!ctx || npairs < 0 || pitch < 1 || !xy0 || !xy1 || !Tcw0 || !Tcw1 || !K || !points || !flags || !tally) return TB_EINVAL;
+    if (!triangulate_params_ok(prm) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_linear_triangle_batch_dev: parameters / K must be finite, fx and fy positive");
+    if (npairs > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_linear_triangle_batch_dev: %d pairs (at most 65535 per call)", npairs);
+    return tbk_linear_triangle(ctx, npairs, xy0, xy1, counts, pitch, Tcw0, Tcw1, K, inv_sigma2_0, inv_sigma2_1, skip,
+                               prm->cos_parallax_max, prm->chi2_max, points, flags, tally);
+}
+
+int tb_linear_triangle(tb_ctx* ctx, const float* xy0, const float* xy1, int n, const float Tcw0[16], const float Tcw1[16],
+                       const double K[4], const float* inv_sigma2_0, const float* inv_sigma2_1, const uint8_t* skip,
+                       const tb_triangulate_params* prm, float* points, uint8_t* flags, int32_t tally[6]) {
+    TB_ENTER(ctx);
+    if (!ctx || n < 0 || !Tcw0 || !Tcw1 || !K || !prm || !tally || (n && (!xy0 || !xy1 || !points || !flags))) return TB_EINVAL;
+    const size_t pitch = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oA = stage_piece(end, pitch * 8), oB = stage_piece(end, pitch * 8), oT0 = stage_piece(end, 64), oT1 = stage_piece(end, 64),
+                 oS0 = stage_piece(end, pitch * 4), oS1 = stage_piece(end, pitch * 4), oSkip = stage_piece(end, pitch),
+                 oPts = stage_piece(end, pitch * 12), oFlags = stage_piece(end, pitch), oTally = stage_piece(end, 24), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt = n;
+    TB_UPLOAD(ctx, b + oA, xy0, (size_t)n * 8);
+    TB_UPLOAD(ctx, b + oB, xy1, (size_t)n * 8);
+    TB_UPLOAD(ctx, b + oT0, Tcw0, 64);
+    TB_UPLOAD(ctx, b + oT1, Tcw1, 64);
+    TB_UPLOAD(ctx, b + oCnt, &cnt, 4);
+    if (inv_sigma2_0) TB_UPLOAD(ctx, b + oS0, inv_sigma2_0, (size_t)n * 4);
+    if (inv_sigma2_1) TB_UPLOAD(ctx, b + oS1, inv_sigma2_1, (size_t)n * 4);
+    if (skip) TB_UPLOAD(ctx, b + oSkip, skip, (size_t)n);
+    TB_HIP(ctx, hipMemsetAsync(b + oPts, 0, pitch * 12, ctx->stream));   /* the operator writes accepted points only */
+    if ((rc = tb_linear_triangle_batch_dev(ctx, 1, (const float*)(b + oA), (const float*)(b + oB), (const int32_t*)(b + oCnt), (int)pitch,
+                                           (const float*)(b + oT0), (const float*)(b + oT1), K, inv_sigma2_0 ? (const float*)(b + oS0) : nullptr,
+                                           inv_sigma2_1 ? (const float*)(b + oS1) : nullptr, skip ? (const uint8_t*)(b + oSkip) : nullptr, prm,
+                                           (float*)(b + oPts), (uint8_t*)(b + oFlags), (int32_t*)(b + oTally))))
+        return rc;
+    TB_DOWNLOAD(ctx, points, b + oPts, (size_t)n * 12);
+    TB_DOWNLOAD(ctx, flags, b + oFlags, (size_t)n);
+    TB_DOWNLOAD(ctx, tally, b + oTally, 24);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n == 0) tally[0] = 0;   /* the staged row of one entry is beyond the count */
+    return TB_OK;
+}
+
 int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf, int nfixed, float* poses, int npt, float* pts,
                           const tb_ba_obs* obs, const int32_t* obs_counts, int obs_pitch, int iters, double* stats) {
     TB_ENTER(ctx);

@@ -472,5 +472,22 @@ int tbk_vo_seg_window(tb_ctx* ctx, int nseq, const float* d_seg_keys, const uint
 int tbk_vo_seg_adopt(tb_ctx* ctx, int nseq, const float* d_win_pose, const int32_t* d_n_points, const double* d_stats, int nslot,
                      int min_points, float* d_Tcw, uint8_t* d_adopted);
 
+/* linear triangulation (k_triangulate.hip); zeroes d_tally first */
+int tbk_linear_triangle(tb_ctx* ctx, int npairs, const float* d_xy0, const float* d_xy1, const int32_t* d_counts, int pitch,
+                        const float* d_Tcw0, const float* d_Tcw1, const double K[4], const float* d_inv_sigma2_0,
+                        const float* d_inv_sigma2_1, const uint8_t* d_skip, double cos_parallax_max, double chi2_max, float* d_points,
+                        uint8_t* d_flags, int32_t* d_tally);
+/* mono mode of the optical-flow loop (k_vo.hip): the alive / skip masks after a tracking half, and the keyframe's merge from
+ * one side of the ping-pong (src) into the other (dst) */
+#define TB_VO_MERGE_BITMAP_MAX 32768 /* bytes of LDS the merge's occupancy bitmap may take */
+size_t tbk_vo_merge_bitmap_bytes(int width, int height, int cell);
+int tbk_vo_mono_alive(tb_ctx* ctx, int nseq, const int32_t* d_key_counts, const uint8_t* d_status, const uint8_t* d_valid, int pitch,
+                      uint8_t* d_alive, uint8_t* d_skip);
+int tbk_vo_kf_merge(tb_ctx* ctx, int nseq, const tb_keypoint* d_orb, const int32_t* d_orb_counts, int orb_pitch, int pitch, int width,
+                    int height, int cell, const float* d_src_keys, const int32_t* d_src_counts, const float* d_src_mp,
+                    const uint8_t* d_src_valid, const float* d_tri_points, const uint8_t* d_tri_flags, float* d_keys,
+                    int32_t* d_key_counts, float* d_mp, uint8_t* d_valid, float* d_kf_keys, uint8_t* d_alive, int32_t* d_survivors,
+                    int32_t* d_added);
+
 
 #endif

@@ -111,6 +111,15 @@ struct tb_vo {
     double* wb_stats = nullptr;                     /* [nseq][8] */
     float *wb_pose = nullptr, *wb_pts = nullptr;    /* [nseq][nslot][16], [nseq][P][3]: the last window, refined */
     uint8_t* wb_adopted = nullptr;                  /* [nseq] */
+    /* mono mode (tb_vo_mono_enable, TB_VO_OPFLOW): the keyframe's key list and pose, which keys LK has held since, and the last
+     * mono keyframe's triangulation and merge counts */
+    bool mono_on = false;
+    tb_vo_mono mono;
+    float *mn_kf_keys = nullptr, *mn_kf_Tcw = nullptr;   /* [nseq][P][2], [nseq][16] */
+    uint8_t *mn_alive = nullptr, *mn_skip = nullptr;     /* [nseq][P] */
+    float* mn_tri_points = nullptr;                      /* [nseq][P][3] */
+    uint8_t* mn_tri_flags = nullptr;                     /* [nseq][P] */
+    int32_t *mn_tri_tally = nullptr, *mn_survivors = nullptr, *mn_added = nullptr;   /* [nseq][6], [nseq], [nseq] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -365,6 +374,8 @@ int tb_vo_create_lsh(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_lsh* lsh, i
 
 static int vo_recover_clear(tb_vo* vo);
 static int vo_window_clear(tb_vo* vo);
+static int vo_mono_clear(tb_vo* vo);
+static int vo_extract(tb_vo* vo, const uint8_t* images, int n);
 
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     TB_ENTER((vo ? vo->ctx : nullptr));
@@ -390,6 +401,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         vo->map_nblk = 0;
     }
     if (vo->wb_on) TB_TRY(vo_window_clear(vo));
+    if (vo->mono_on) TB_TRY(vo_mono_clear(vo));
     vo->next = 0;
     vo->ragged = false;
     std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
@@ -426,6 +438,55 @@ static int vo_window_clear(tb_vo* vo) {
     TB_HIP(ctx, hipMemsetAsync(vo->wb_pts, 0, S * P * 3 * sizeof(float), ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(vo->wb_adopted, 0, S, ctx->stream));
     vo->wb_slot = 0;
+    return TB_OK;
+}
+
+/* the mono state of a new run: no keyframe yet, nothing triangulated */
+static int vo_mono_clear(tb_vo* vo) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq, SP = S * vo->P;
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_kf_keys, 0, SP * 2 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_kf_Tcw, 0, S * 16 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_alive, 0, SP, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_skip, 1, SP, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_tri_points, 0, SP * 3 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_tri_flags, 0, SP, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_tri_tally, 0, S * 6 * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_survivors, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_added, 0, S * sizeof(int32_t), ctx->stream));
+    return TB_OK;
+}
+
+/* Mono mode, the end of frame 0's stereo keyframe block: the key list and pose the next segment triangulates against. */
+static int vo_mono_start(tb_vo* vo, int b) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq, SP = S * vo->P;
+    TB_HIP(ctx, hipMemcpyAsync(vo->mn_kf_keys, vo->keys[b], SP * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    TB_HIP(ctx, hipMemcpyAsync(vo->mn_kf_Tcw, vo->Tcw[b], S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mn_alive, 1, SP, ctx->stream));
+    return TB_OK;
+}
+
+/* Mono mode, the keyframe block of frame t > 0 (include/tb_capi.h, tb_vo_mono): triangulate the segment's tracks at the
+ * optimised pose, then merge the keys that have a map point with the frame's ORB keys. The merge reads side b and writes side
+ * a, which nothing needs any more; the two sides of the key list, its counts and its map points then change places, so side b
+ * is the frame's again. */
+static int vo_mono_keyframe(tb_vo* vo, int b) {
+    tb_ctx* ctx = vo->ctx;
+    const tb_vo_params& p = vo->p;
+    const int S = vo->nseq, P = vo->P, a = b ^ 1;
+    const tb_triangulate_params tp = {vo->mono.cos_parallax_max, vo->mono.chi2_max};
+    TB_TRY(tb_linear_triangle_batch_dev(ctx, S, vo->mn_kf_keys, vo->keys[b], vo->kcnt[b], P, vo->mn_kf_Tcw, vo->Tcw[b], p.K, nullptr, nullptr,
+                                        vo->mn_skip, &tp, vo->mn_tri_points, vo->mn_tri_flags, vo->mn_tri_tally));
+    TB_TRY(vo_extract(vo, vo->img[b], S));
+    const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
+    tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
+    TB_TRY(tbk_vo_kf_merge(ctx, S, kps, cnt, selCap, P, p.width, p.height, vo->mono.cell, vo->keys[b], vo->kcnt[b], vo->mp[b], vo->valid[b],
+                           vo->mn_tri_points, vo->mn_tri_flags, vo->keys[a], vo->kcnt[a], vo->mp[a], vo->valid[a], vo->mn_kf_keys,
+                           vo->mn_alive, vo->mn_survivors, vo->mn_added));
+    std::swap(vo->keys[a], vo->keys[b]); std::swap(vo->kcnt[a], vo->kcnt[b]);
+    std::swap(vo->mp[a], vo->mp[b]); std::swap(vo->valid[a], vo->valid[b]);
+    TB_HIP(ctx, hipMemcpyAsync(vo->mn_kf_Tcw, vo->Tcw[b], (size_t)S * 16 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     return TB_OK;
 }
 
@@ -695,16 +756,21 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
         vo->wb_slot = slot;
         if (keyframe) TB_TRY(vo_window_ba(vo, b));
     }
-    if (keyframe) {
+    if (vo->mono_on && t > 0)   /* which keys LK still holds, and which of them have no map point yet */
+        TB_TRY(tbk_vo_mono_alive(vo->ctx, S, vo->kcnt[b], vo->status, vo->valid[b], vo->P, vo->mn_alive, vo->mn_skip));
+    if (keyframe && vo->mono_on && t > 0) {
+        TB_TRY(vo_mono_keyframe(vo, b));
+    } else if (keyframe) {
         TB_TRY(vo_keyframe(vo, t, b, S, nullptr, nullptr, right, stride, pitch));
+        if (vo->mono_on) TB_TRY(vo_mono_start(vo, b));
         if (vo->wb_on) {   /* the next segment starts here */
             TB_TRY(tbk_vo_seg_start(vo->ctx, S, vo->keys[b], vo->kcnt[b], vo->depth, vo->mp[b], vo->valid[b], vo->Tcw[b], vo->P, vo->wb_nslot,
                                     vo->sg_keys,
                                     vo->sg_ok, vo->sg_pose, vo->sg_pts, vo->sg_spawned));
             vo->wb_slot = 0;
         }
-        vo->kf_frame = t;
     }
+    if (keyframe) vo->kf_frame = t;
     vo->cur = b;
     vo->next = t + 1;
     for (int s = 0; s < S; s++) {
@@ -724,7 +790,8 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
     const int t = vo->next;
     const bool keyframe = t % p.keyframe_every == 0;
     if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
-    if (keyframe && !right) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
+    if (keyframe && !right && !(vo->mono_on && t > 0))
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
     return vo_step_lock(vo, t, keyframe, left, right, stride, pitch);
 }
 
@@ -733,6 +800,7 @@ static const char* vo_ragged_unsupported(const tb_vo* vo) {
     if (vo->tr.kind == TB_VO_PROJECTION_MAP) return "TB_VO_PROJECTION_MAP counts the map's blocks and evicts for the whole batch";
     if (vo->db) return "the keyframe database's ring slot is counted for the whole batch";
     if (vo->wb_on) return "the window BA counts the segment's slots for the whole batch";
+    if (vo->mono_on) return "the mono mode keeps one keyframe segment for the whole batch";
     return nullptr;
 }
 
@@ -1046,6 +1114,7 @@ int tb_vo_window_ba_enable(tb_vo* vo, const tb_vo_window_ba* prm) {
     tb_ctx* ctx = vo->ctx;
     const int E = vo->p.keyframe_every;
     if (vo->tr.kind != TB_VO_OPFLOW) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable: the loop does not track by optical flow");
+    if (vo->mono_on) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_window_ba_enable: the loop is in mono mode (its keyframes spawn no stereo points)");
     if (vo->next > 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable after a step (frame %d)", vo->next - 1);
     if (vo->wb_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_window_ba_enable: the window BA is enabled already");
     if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_window_ba_enable: null parameters");
@@ -1102,6 +1171,56 @@ int tb_vo_window_state_dev(tb_vo* vo, const float** seg_keys, const uint8_t** se
     if (ba_pts) *ba_pts = vo->wb_pts;
     if (slot) *slot = vo->wb_slot;
     if (nslots) *nslots = vo->wb_nslot;
+    return TB_OK;
+}
+
+int tb_vo_mono_enable(tb_vo* vo, const tb_vo_mono* prm) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (vo->tr.kind != TB_VO_OPFLOW)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_mono_enable: the loop does not track by optical flow (a later change)");
+    if (vo->wb_on) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_mono_enable: the window BA is enabled (a later change)");
+    if (vo->next >= 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_mono_enable after a reset");
+    if (vo->mono_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_mono_enable: the mono mode is enabled already");
+    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_mono_enable: null parameters");
+    if (!std::isfinite(prm->cos_parallax_max) || !std::isfinite(prm->chi2_max) || prm->cell <= 0)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_mono_enable: cos_parallax_max %g, chi2_max %g, cell %d (> 0)", prm->cos_parallax_max,
+                       prm->chi2_max, prm->cell);
+    const size_t bitmap = tbk_vo_merge_bitmap_bytes(vo->p.width, vo->p.height, prm->cell);
+    if (bitmap > TB_VO_MERGE_BITMAP_MAX)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_mono_enable: cell %d on %d x %d needs an occupancy bitmap of %zu bytes (at most %d)", prm->cell,
+                       vo->p.width, vo->p.height, bitmap, TB_VO_MERGE_BITMAP_MAX);
+    const size_t S = (size_t)vo->nseq, SP = S * vo->P;
+    tb_dev_owner& own = vo->own;
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_kf_keys, SP * 2));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_kf_Tcw, S * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_alive, SP));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_skip, SP));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_tri_points, SP * 3));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_tri_flags, SP));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_tri_tally, S * 6));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_survivors, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mn_added, S));
+    vo->mono = *prm;
+    TB_TRY(vo_mono_clear(vo));
+    vo->mono_on = true;
+    return TB_OK;
+}
+
+int tb_vo_mono_state_dev(tb_vo* vo, const float** kf_keys_xy, const float** kf_Tcw, const uint8_t** alive, const float** tri_points,
+                         const uint8_t** tri_flags, const int32_t** tri_tally, const int32_t** survivors, const int32_t** added) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->mono_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_mono_state_dev: the mono mode is not enabled (tb_vo_mono_enable)");
+    if (kf_keys_xy) *kf_keys_xy = vo->mn_kf_keys;
+    if (kf_Tcw) *kf_Tcw = vo->mn_kf_Tcw;
+    if (alive) *alive = vo->mn_alive;
+    if (tri_points) *tri_points = vo->mn_tri_points;
+    if (tri_flags) *tri_flags = vo->mn_tri_flags;
+    if (tri_tally) *tri_tally = vo->mn_tri_tally;
+    if (survivors) *survivors = vo->mn_survivors;
+    if (added) *added = vo->mn_added;
     return TB_OK;
 }
 

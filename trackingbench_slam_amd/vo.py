@@ -39,6 +39,12 @@ frames from one keyframe to the next are a local-BA window over the first keyfra
 all of them), and the next keyframe spawns its points at the refined pose. `window()` shows the segment log, the window and the
 refined segment. The BA's termination test is the one host synchronisation a keyframe step gains; tracking steps gain none.
 
+`mono=True` (or a dict, see MONO_DEFAULTS; optical-flow tracker, lock-step only, not with window_ba=) grows the map from one
+camera: frame 0 is the stereo keyframe that fixes the scale, and every later keyframe takes `right=None`, triangulates the keys
+LK has held since the last keyframe from the two known poses (LocalBA::LinearTriangle on the device, gated on depth, parallax
+and reprojection error) and merges the keys that have a map point with the frame's ORB keys. `mono()` shows the keyframe's key
+list, the triangulation's flags and the merge's counts.
+
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
 synchronisation and no host <-> device copy. torch supplies the frames and the stream. There is no CPU fallback.
 """
@@ -80,6 +86,9 @@ RECOVER_DEFAULTS = dict(lost_inliers=30, topk=4, exclude_newest=1, min_inliers=5
 # window_ba=True: 10 LM iterations, the keyframe held fixed (a second fixed frame is a noisy single-frame estimate and measured
 # worse), a point needs 2 inlier observations, a window needs 3 points for its pose to be adopted
 WINDOW_BA_DEFAULTS = dict(iters=10, fixed=1, min_obs=2, min_points=3)
+# mono=True: ORB-SLAM's triangulation gates (a ray cosine below 0.9998, the 95 % chi-square bound of 2 degrees of freedom) and
+# an 8-pixel occupancy cell for the keyframe's merge
+MONO_DEFAULTS = dict(cos_parallax_max=0.9998, chi2_max=5.991, cell=8)
 BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
 
@@ -121,9 +130,15 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
+        if mono:
+            unknown = set(mono) - set(MONO_DEFAULTS) if isinstance(mono, dict) else ()
+            if unknown:
+                raise TypeError("mono= takes no parameter %s" % ", ".join(sorted(unknown)))
+            mono = dict(MONO_DEFAULTS, **(mono if isinstance(mono, dict) else {}))
+        self.mono_params = mono or None
         if window_ba:
             if tracker != "opflow":
                 raise TypeError("window_ba= needs the optical-flow tracker: its key lists are the window's point tracks")
@@ -205,6 +220,13 @@ class StereoVO:
                 self.vo = None
                 self.close()
                 raise
+        if self.mono_params:                  # None = off: no call is made. The library refuses what the mode does not cover
+            try:
+                self.ctx.check(self.vo.mono_enable(capi.VOMono(float(self.mono_params["cos_parallax_max"]),
+                                                               float(self.mono_params["chi2_max"]), int(self.mono_params["cell"]))))
+            except Exception:
+                self.close()
+                raise
         self._Tcw0 = None
         self._ragged = False
         self.frame = -1
@@ -248,6 +270,8 @@ class StereoVO:
     def _ragged_ok(self):
         if getattr(self, "window_ba", None):
             raise TypeError("ragged batches: window_ba= counts the segment's slots for the whole batch")
+        if getattr(self, "mono_params", None):
+            raise TypeError("ragged batches: mono= keeps one keyframe segment for the whole batch")
         if self.tracker == "projection_map" or self.db is not None:
             raise TypeError("ragged batches: tracker 'projection_map' and keyframe_db= count keyframes for the whole batch")
 
@@ -540,6 +564,22 @@ class StereoVO:
                     stats=self._pget(d["stats"], (S, 8), "<f8", torch.float64), adopted=self._pget(d["adopted"], (S,), *u8),
                     refined_poses=self._pget(d["ba_pose"], (S, N, 4, 4), *f32), refined_points=self._pget(d["ba_pts"], (S, P, 3), *f32),
                     slots=d["slot"], nslots=N)
+
+    # ---- mono mode (mono=...)
+    def mono(self):
+        """The mono state after the last step: dict(kf_keys [S, P, 2] and kf_Tcw [S, 4, 4] -- the key list and pose of the keyframe
+        the running segment triangulates against --, alive [S, P] uint8 -- LK has held the key since --, tri_points [S, P, 3],
+        tri_flags [S, P] uint8 (tb_linear_triangle_batch_dev's codes), tri_tally [S, 6] int32, survivors / added [S] int32 -- the
+        last mono keyframe's triangulation, before the merge renumbered the keys, and the merge's counts). TB_ESTATE when off."""
+        if self.mono_params is None:
+            raise capi.TBError(capi.TB_ESTATE, "the mono mode is off: StereoVO(..., mono=True)")
+        d = self.vo.mono_state_dev()
+        S, P = self.S, self.key_pitch
+        f32, u8, i32 = ("<f4", torch.float32), ("|u1", torch.uint8), ("<i4", torch.int32)
+        return dict(kf_keys=self._pget(d["kf_keys_xy"], (S, P, 2), *f32), kf_Tcw=self._pget(d["kf_Tcw"], (S, 4, 4), *f32),
+                    alive=self._pget(d["alive"], (S, P), *u8), tri_points=self._pget(d["tri_points"], (S, P, 3), *f32),
+                    tri_flags=self._pget(d["tri_flags"], (S, P), *u8), tri_tally=self._pget(d["tri_tally"], (S, 6), *i32),
+                    survivors=self._pget(d["survivors"], (S,), *i32), added=self._pget(d["added"], (S,), *i32))
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
