@@ -659,6 +659,33 @@ int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf,
  * run in point order and holding only the points that have that many. */
 int tb_ba_obs_stream_positions(const int32_t* pt_start, int npt, int32_t* pos);
 
+/* SE(3) pose-graph optimisation -- extension, NO reference counterpart: the solver between PoseOptimization (one pose) and the
+ * local BA (poses and points), restated in numpy in tests/pose_graph_reference.py.
+ * A graph has nnodes poses Tcw (nnodes x 16 row-major, in/out, the first nfixed held) and edges (tb_pg_edge: a, b, Z ~ T_b T_a^-1,
+ * w_rot, w_trans). With E = Z^-1 T_b T_a^-1 the residual is r = Log(E) ordered (omega, upsilon) like every solver's update vector
+ * here (T <- exp(delta) T, SE3Quat::exp), chi2 = sum r' diag(w_rot I3, w_trans I3) r, no robust kernel; the Jacobians are the
+ * exact ones, J_b = Jl^-1(r) Ad(Z^-1), J_a = -Jl^-1(r) Ad(E). Everything is FP64; poses enter through the quaternion extraction of
+ * PoseOptimization and the local BA. Levenberg-Marquardt by g2o's rule as the local BA restates it: lambda0 = 1e-5 max diag H; a
+ * trial is accepted when rho > 0 and its chi2 is finite, then lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)); otherwise lambda *= nu,
+ * nu *= 2; at most 10 trials per iteration; stop at 10 rejections, at rho == 0, or after `iters` iterations.
+ * Limits: 1 <= nfixed < nnodes (TB_EINVAL otherwise), nnodes <= 64, at most 256 edges and 99 iterations (TB_EUNSUPPORTED beyond).
+ * Any connected edge set works: repeated pairs, edges listed as (b, a), several edges into one node. stats (nullable, 8
+ * doubles): iterations, initial chi2, final chi2, final lambda, trials (rejected ones included).
+ * A graph keeps EVERY BYTE of its poses when it has no edge, when no trial was accepted (iters == 0 among them; chi2 is still
+ * reported) or when it is malformed -- an index outside [0, nnodes), a == b, a count above the pitch, a non-finite Z or weight, a
+ * zero quaternion, a negative weight; fixed nodes always keep theirs. tb_pose_graph returns TB_EINVAL for a malformed graph. */
+int tb_pose_graph(tb_ctx* ctx, int nnodes, int nfixed, float* poses, const tb_pg_edge* edges, int nedges, int iters, double* stats);
+/* Batched device form: ngraphs graphs of one shape; graph g uses poses + g*nnodes*16, edges + g*edge_pitch (edge_counts[g] of
+ * them, edge_pitch <= 256), stats + 8g (nullable; stats[7] = -1 flags a malformed graph). Device pointers. One workgroup per
+ * graph runs the whole LM loop on the device: the call is asynchronous on the context's stream and makes no host synchronisation
+ * and no host <-> device copy (the work buffers are the context's and only grow; a call that grows them waits for the stream
+ * first). No floating-point atomics: a graph gives the same bits alone, inside any batch, and from run to run. */
+int tb_pose_graph_batch_dev(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, float* poses, const tb_pg_edge* edges,
+                            const int32_t* edge_counts, int edge_pitch, int iters, double* stats);
+/* Grows the context's work buffer to what tb_pose_graph_batch_dev needs for this shape, once and ahead of time: a later call of
+ * that shape or a smaller one then neither allocates nor waits for the stream. Same argument checks. */
+int tb_pose_graph_plan(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int edge_pitch);
+
 /* ---------------------------------------------------------------- device-resident stereo VO loop
  * The tracking loop of the reference's main program, test/test_vo.cpp test_kitti (:674-850), for nseq independent stereo
  * sequences in lock-step: one tb_vo_step_dev = frame t of every sequence, chained on the context's stream from the batched
@@ -900,8 +927,8 @@ int tb_vo_bow_db_get(tb_vo* vo, tb_bow_db** out);
  * tb_vo_bow fields. It changes neither the loop's pose nor its carried points nor its keyframe, and makes no host synchronisation
  * and no host <-> device copy. scores [nseq][capacity], top_slot / top_kf / top_score [nseq][topk] and top_count [nseq] are the
  * query's outputs (each nullable: the loop has buffers of its own); topk in 1..max_candidates. TB_ESTATE: not enabled, or before
- * the first step. Loop correction and ORB-SLAM's second stage (searchByProjection with the recovered pose) are not part of it;
- * adopting the pose after a loss is tb_vo_recover_enable's. tb_vo_kf_store_get lends the store (TB_ESTATE when not enabled). */
+ * the first step. ORB-SLAM's second stage (searchByProjection with the recovered pose) is not part of it; adopting the pose after
+ * a loss is tb_vo_recover_enable's, correcting the trajectory on a revisit tb_vo_loop_enable's. tb_vo_kf_store_get lends the store (TB_ESTATE when not enabled). */
 int tb_vo_reloc_enable(tb_vo* vo, int max_candidates);
 int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
                          double* top_score, int32_t* top_count, const tb_reloc_out* out);
@@ -926,7 +953,8 @@ int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
  * keyframe of every sequence (kf_ids[s] = t) and goes into the database, the store and the rings. The stage is on the context's
  * stream: no host synchronisation, no host <-> device copy; which sequences adopt is decided by device predicates alone.
  * tb_vo_tracker_state_dev's *kf_frame stays the last keyframe step. tb_vo_reset_dev clears the state (flags 0, ids -1).
- * tb_vo_recover_enable allocates every buffer. TB_ESTATE: relocalisation not enabled, after the first step, or enabled already;
+ * tb_vo_recover_enable allocates every buffer. TB_ESTATE: relocalisation not enabled, after the first step, enabled already, or
+ * loop correction enabled (tb_vo_loop_enable);
  * TB_EINVAL: null params, lost_inliers < 0, min_inliers < 0, exclude_newest < 0, topk outside 1..max_candidates.
  * tb_vo_recover_state_dev: device views, each nullable (TB_ESTATE when not enabled): lost [nseq] and track_inliers [nseq] of the
  * last step (the tracker's own count, before any adoption), recovered_kf [nseq] (the adopted keyframe's kf_id, or -1), kf_ids
@@ -941,6 +969,45 @@ typedef struct tb_vo_recover {
 int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm);
 int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** track_inliers, const int32_t** recovered_kf,
                             const int32_t** kf_ids, const int32_t** kf_word_ring, const int32_t** kf_node_ring);
+/* Loop correction in a TB_VO_BOW loop with relocalisation, lock-step (off unless enabled; a loop that does not enable it launches
+ * what it launched before): a verified revisit is spread back over the stored keyframes by tb_pose_graph_batch_dev. The reference
+ * has no such step; the composition is this library's, restated on the CPU oracle in tests/vo_loop_reference.py. At a keyframe
+ * step t > 0, after the tracking step's pose optimisation and before the keyframe block, all on the context's stream with no host
+ * synchronisation and no host <-> device copy:
+ *   query   tb_bow_db_query_dev(topk, exclude_newest) and tb_relocalize_batch_dev with the loop's tb_vo_bow fields and
+ *           min_inliers, into the loop's own buffers, as tb_vo_relocalize_dev
+ *   graph   k_vo_loop_graph: capacity + 1 nodes per sequence -- the live ring slots in ascending kf_id, then the current frame;
+ *           the unused nodes hold the identity and no edge names them. Node 0, the oldest, is fixed. Odometry edges join
+ *           consecutive nodes, Z = T_next T_prev^-1 from the stored poses and the current pose; one loop edge joins the winning
+ *           keyframe's node to the current node, Z = best_Tcw T_j^-1; weights w_rot, w_trans. best_rank < 0, or fewer than 2
+ *           keyframes held: edge count 0
+ *   solve   tb_pose_graph_batch_dev's kernel on the nseq graphs, nfixed = 1, iters
+ *   adopt   k_vo_loop_adopt, where a loop edge was built and the solver did not flag the graph: every stored keyframe's Tcw
+ *           becomes its node's pose and its valid map points move rigidly with it, X' = T_new^-1 T_old X in FP64 stored as float32;
+ *           the keyframe snapshot (kf_map_points) and the frame's carried map points, copies of the newest keyframe's points, move
+ *           by the newest keyframe's correction; the current Tcw becomes the last node's pose. obs, outlier, n_inliers and the
+ *           match list stay: they describe the tracking step. Every other sequence keeps every byte
+ * then the keyframe block as before: the frame spawns its stereo points at the corrected pose and goes into the database and the
+ * store with it. tb_vo_loop_enable allocates every buffer and plans the solver's work buffer (tb_pose_graph_plan), so no step
+ * grows it. TB_ESTATE: relocalisation not enabled (any other tracker, no database, no store), after the first step, a ragged
+ * loop, enabled already, or recovery enabled (tb_vo_recover_enable on a loop with correction is TB_ESTATE too: combining the two is
+ * a later change); TB_EINVAL: null params, a store capacity above 63 (nodes = keyframes + the frame <= 64), topk outside
+ * 1..max_candidates, exclude_newest < 0, min_inliers < 0, iters outside 0..99, a negative or non-finite weight.
+ * tb_vo_loop_state_dev: device views of the last keyframe step t > 0, each nullable (TB_ESTATE when not enabled): closed [nseq],
+ * loop_kf [nseq] (the keyframe's kf_id, -1 when nothing closed), loop_inliers [nseq], nnodes [nseq] (live keyframes + 1), node_kf
+ * [nseq][capacity + 1] (kf_id per node, the frame index for the current frame, -1 unused), before / after [nseq][capacity + 1][16],
+ * edges [nseq][capacity + 1] with edge_counts [nseq], stats [nseq][8] (tb_pose_graph_batch_dev's). tb_vo_reset_dev clears them. */
+typedef struct tb_vo_loop {
+    int topk;             /* candidates per sequence, 1..max_candidates of tb_vo_reloc_enable */
+    int exclude_newest;   /* as tb_bow_db_query_dev */
+    int min_inliers;      /* as tb_reloc_params: a loop closes when the best candidate keeps at least this many */
+    int iters;            /* LM iterations of the pose graph */
+    double w_rot, w_trans; /* the edges' information, diag(w_rot I3, w_trans I3) */
+} tb_vo_loop;
+int tb_vo_loop_enable(tb_vo* vo, const tb_vo_loop* prm);
+int tb_vo_loop_state_dev(tb_vo* vo, const uint8_t** closed, const int32_t** loop_kf, const int32_t** loop_inliers, const int32_t** nnodes,
+                         const int32_t** node_kf, const float** before, const float** after, const tb_pg_edge** edges,
+                         const int32_t** edge_counts, const double** stats);
 /* Window BA in a TB_VO_OPFLOW loop in lock-step (off unless enabled; a loop that does not enable it launches what it launched
  * before): every keyframe segment is refined by tb_local_ba_batch_dev before the keyframe spawns its stereo points. The reference
  * has no such step (its map_ptr->AddKeyFrame is commented out); the operators are this library's and the composition is restated

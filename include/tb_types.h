@@ -89,6 +89,16 @@ typedef struct tb_ba_obs {
     float inv_sigma2;
 } tb_ba_obs;
 
+/* One pose-graph edge: the measured motion Z ~ T_b T_a^-1 between nodes a and b as a unit quaternion (x, y, z, w) and a
+ * translation, in FP64 -- an edge built from two stored poses has a residual of rounding size, which a float32 Z would not give --
+ * and the weights of its information matrix diag(w_rot I3, w_trans I3). 80 bytes. */
+typedef struct tb_pg_edge {
+    int32_t a, b;
+    double q[4];
+    double t[3];
+    double w_rot, w_trans;
+} tb_pg_edge;
+
 /* Error codes (0 = ok). */
 enum {
     TB_OK = 0,

@@ -19,6 +19,7 @@ MATCH = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), (
 CORNER = np.dtype([("x", "<i4"), ("y", "<i4"), ("score", "<i4")])
 OBS = np.dtype([("u", "<f4"), ("v", "<f4"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("inv_sigma2", "<f4")])
 BA_OBS = np.dtype([("kf", "<i4"), ("pt", "<i4"), ("u", "<f4"), ("v", "<f4"), ("inv_sigma2", "<f4")])
+PG_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("w_rot", "<f8"), ("w_trans", "<f8")])
 CAMERA = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("width", "<i4"), ("height", "<i4"),
                    ("has_distortion", "<i4"), ("d", "<f4", (5,))])
 MAPPOINT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"), ("bad", "<i4")])
@@ -56,6 +57,7 @@ EXPORTS = [
     "tb_lsh_draw_bits", "tb_lsh_create", "tb_lsh_destroy", "tb_lsh_info", "tb_match_lsh", "tb_search_by_nn", "tb_search_by_nn_batch_dev",
     "tb_vo_create_lsh",
     "tb_linear_triangle", "tb_linear_triangle_batch_dev", "tb_vo_mono_enable", "tb_vo_mono_state_dev",
+    "tb_pose_graph", "tb_pose_graph_batch_dev", "tb_pose_graph_plan", "tb_vo_loop_enable", "tb_vo_loop_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -267,6 +269,12 @@ class VORecover(C.Structure):
     _fields_ = [("lost_inliers", C.c_int), ("topk", C.c_int), ("exclude_newest", C.c_int), ("min_inliers", C.c_int)]
 
 
+class VOLoop(C.Structure):
+    """tb_vo_loop of include/tb_capi.h"""
+    _fields_ = [("topk", C.c_int), ("exclude_newest", C.c_int), ("min_inliers", C.c_int), ("iters", C.c_int), ("w_rot", C.c_double),
+                ("w_trans", C.c_double)]
+
+
 class VOWindowBA(C.Structure):
     """tb_vo_window_ba of include/tb_capi.h"""
     _fields_ = [("iters", C.c_int), ("fixed", C.c_int), ("min_obs", C.c_int), ("min_points", C.c_int)]
@@ -425,6 +433,19 @@ class VO:
         names = ("lost", "track_inliers", "recovered_kf", "kf_ids", "kf_word_ring", "kf_node_ring")
         ptrs = [C.c_void_p() for _ in names]
         self.ctx.check(lib().tb_vo_recover_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        return {k: q.value for k, q in zip(names, ptrs)}
+
+    def loop_enable(self, prm):
+        """tb_vo_loop_enable with a VOLoop (None: a null pointer): returns the status code (0 or a negative TB_E* code), so the
+        state and argument checks can be tested."""
+        return lib().tb_vo_loop_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def loop_state_dev(self):
+        """tb_vo_loop_state_dev: dict of device pointers (closed, loop_kf, loop_inliers, nnodes, node_kf, before, after, edges,
+        edge_counts, stats); TB_ESTATE when loop correction is not enabled."""
+        names = ("closed", "loop_kf", "loop_inliers", "nnodes", "node_kf", "before", "after", "edges", "edge_counts", "stats")
+        ptrs = [C.c_void_p() for _ in names]
+        self.ctx.check(lib().tb_vo_loop_state_dev(self._h, *[C.byref(q) for q in ptrs]))
         return {k: q.value for k, q in zip(names, ptrs)}
 
     def window_ba_enable(self, prm):
@@ -980,6 +1001,65 @@ class Context:
         self.check(lib().tb_local_ba(self._h, _p(K), len(poses), int(nfixed), _p(poses), len(pts), _p(pts), _p(obs), len(obs),
                                      int(iters), _p(stats)))
         return int(stats[0]), poses.reshape(-1, 4, 4), pts, stats
+
+    def pose_graph(self, poses, nfixed, edges, iters=10):
+        """tb_pose_graph: one graph from host arrays. poses [nnodes, 4, 4] float32 Tcw, the first nfixed held; edges a PG_EDGE array
+        (pose_graph_edges builds one). Returns (iterations, poses, stats [8]); a malformed graph raises."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16).copy()
+        edges = np.ascontiguousarray(edges, PG_EDGE).reshape(-1)
+        stats = np.zeros(8, np.float64)
+        self.check(lib().tb_pose_graph(self._h, len(poses), int(nfixed), _p(poses), _p(edges) if len(edges) else None, len(edges),
+                                       int(iters), _p(stats)))
+        return int(stats[0]), poses.reshape(-1, 4, 4), stats
+
+    def pose_graph_plan(self, ngraphs, nnodes, nfixed, edge_pitch):
+        """tb_pose_graph_plan: size the work buffer for this shape ahead of time. Returns the status code."""
+        return lib().tb_pose_graph_plan(self._h, int(ngraphs), int(nnodes), int(nfixed), int(edge_pitch))
+
+    def pose_graph_dev(self, ngraphs, nnodes, nfixed, poses_ptr, edges_ptr, counts_ptr, edge_pitch, iters, stats_ptr=0):
+        """tb_pose_graph_batch_dev: device pointers (stats nullable), asynchronous on the context's stream. Returns the status code."""
+        return lib().tb_pose_graph_batch_dev(self._h, int(ngraphs), int(nnodes), int(nfixed), C.c_void_p(poses_ptr), C.c_void_p(edges_ptr),
+                                             C.c_void_p(counts_ptr), int(edge_pitch), int(iters), C.c_void_p(stats_ptr or None))
+
+
+def pose_graph_edges(pairs, Z, w_rot=1.0, w_trans=1.0):
+    """PG_EDGE records of the edges (a, b) in `pairs` with the measured motions Z [n, 4, 4] ~ T_b T_a^-1 (float64 rotation matrices,
+    turned into unit quaternions in float64 by the library's own rule) and the weights (scalars or [n])"""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    Z = np.asarray(Z, np.float64).reshape(-1, 4, 4)
+    assert len(Z) == len(pairs)
+    e = np.zeros(len(pairs), PG_EDGE)
+    e["a"], e["b"] = pairs[:, 0], pairs[:, 1]
+    e["w_rot"], e["w_trans"] = w_rot, w_trans
+    for i, T in enumerate(Z):
+        R = T[:3, :3]
+        # the library's own extraction (po_quat_from_R of csrc/tb_se3.h, Eigen's Quaternion(Matrix3)): trace > 0, else the largest
+        # diagonal entry, ties to the lower index; then w >= 0 and unit norm, as the kernel normalises what it reads
+        q = np.zeros(4)
+        t = R[0, 0] + R[1, 1] + R[2, 2]
+        if t > 0:
+            t = np.sqrt(t + 1.0)
+            q[3] = 0.5 * t
+            t = 0.5 / t
+            q[0], q[1], q[2] = (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t
+        else:
+            k = 0
+            if R[1, 1] > R[0, 0]:
+                k = 1
+            if R[2, 2] > R[k, k]:
+                k = 2
+            j, l = (k + 1) % 3, (k + 2) % 3
+            t = np.sqrt(R[k, k] - R[j, j] - R[l, l] + 1.0)
+            q[k] = 0.5 * t
+            t = 0.5 / t
+            q[3] = (R[l, j] - R[j, l]) * t
+            q[j] = (R[j, k] + R[k, j]) * t
+            q[l] = (R[l, k] + R[k, l]) * t
+        if q[3] < 0:
+            q = -q
+        e["q"][i] = q / np.sqrt((q * q).sum())
+        e["t"][i] = T[:3, 3]
+    return e
 
 
 def bow_score(scoring, a_words, a_values, b_words, b_values):

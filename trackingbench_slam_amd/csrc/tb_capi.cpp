@@ -2055,6 +2055,55 @@ int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* pose
     return TB_OK;
 }
 
+int tb_pose_graph_plan(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int edge_pitch) {
+    TB_ENTER(ctx);
+    if (!ctx || ngraphs < 0 || nfixed < 1 || nfixed >= nnodes || edge_pitch < 1) return TB_EINVAL;
+    if (nnodes > 64 || edge_pitch > 256)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph: %d nodes, %d edges (at most 64, 256)", nnodes, edge_pitch);
+    void* dwork;
+    return ngraphs ? tb_scratch(ctx, TB_SLOT_WORK, tbk_pose_graph_work_bytes(ngraphs, nnodes, nfixed, edge_pitch), &dwork) : TB_OK;
+}
+
+int tb_pose_graph_batch_dev(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, float* poses, const tb_pg_edge* edges,
+                            const int32_t* edge_counts, int edge_pitch, int iters, double* stats) {
+    TB_ENTER(ctx);
+    if (!ctx || !poses || !edges || !edge_counts || ngraphs < 0 || nfixed < 1 || nfixed >= nnodes || edge_pitch < 1 || iters < 0)
+        return TB_EINVAL;
+    if (nnodes > 64 || edge_pitch > 256 || iters > 99)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph: %d nodes, %d edges, %d iterations (at most 64, 256, 99)", nnodes, edge_pitch, iters);
+    if (ngraphs == 0) return TB_OK;
+    void* dwork;
+    TB_TRY(tb_scratch(ctx, TB_SLOT_WORK, tbk_pose_graph_work_bytes(ngraphs, nnodes, nfixed, edge_pitch), &dwork));
+    return tbk_pose_graph_batch(ctx, ngraphs, nnodes, nfixed, poses, edges, edge_counts, edge_pitch, iters, stats, dwork);
+}
+
+int tb_pose_graph(tb_ctx* ctx, int nnodes, int nfixed, float* poses, const tb_pg_edge* edges, int nedges, int iters, double* stats) {
+    TB_ENTER(ctx);
+    if (!ctx || !poses || (!edges && nedges > 0) || nedges < 0 || nfixed < 1 || nfixed >= nnodes || iters < 0) return TB_EINVAL;
+    if (nnodes > 64 || nedges > 256 || iters > 99)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph: %d nodes, %d edges, %d iterations (at most 64, 256, 99)", nnodes, nedges, iters);
+    const int pitch = std::max(nedges, 1);
+    size_t end = 0;
+    const size_t oPoses = stage_piece(end, (size_t)nnodes * 64), oEdges = stage_piece(end, (size_t)pitch * sizeof(tb_pg_edge)),
+                 oStats = stage_piece(end, 64), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_UPLOAD(ctx, b + oPoses, poses, (size_t)nnodes * 64);
+    TB_UPLOAD(ctx, b + oEdges, edges, (size_t)nedges * sizeof(tb_pg_edge));
+    TB_UPLOAD(ctx, b + oCnt, &nedges, 4);
+    if ((rc = tb_pose_graph_batch_dev(ctx, 1, nnodes, nfixed, (float*)(b + oPoses), (const tb_pg_edge*)(b + oEdges), (const int32_t*)(b + oCnt),
+                                      pitch, iters, (double*)(b + oStats))))
+        return rc;
+    double st[8];
+    TB_DOWNLOAD(ctx, poses, b + oPoses, (size_t)nnodes * 64);
+    TB_DOWNLOAD(ctx, st, b + oStats, 64);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) memcpy(stats, st, 64);
+    if (st[7] < 0) return tb_fail(ctx, TB_EINVAL, "pose_graph: edges rejected by the device-side check");
+    return TB_OK;
+}
+
 int tb_clahe_dev(tb_ctx* ctx, const uint8_t* src, int width, int height, int stride, double clip_limit, int tiles_x, int tiles_y,
                  uint8_t* dst, int dst_stride) {
     TB_ENTER(ctx);

@@ -388,6 +388,21 @@ int tbk_local_ba_batch(tb_ctx* ctx, int W, const double K[4], int nkf, int nfixe
                        const tb_ba_obs* d_obs, const int32_t* d_counts, int obs_pitch, int iters, double* d_stats, void* d_work,
                        size_t work_bytes);
 size_t tbk_local_ba_work_bytes(const tb_ctx* ctx, int W, int nkf, int nfixed, int npt, int obs_pitch);
+/* pose-graph optimisation (k_pgo.hip): one workgroup per graph runs the whole LM loop; d_work: tbk_pose_graph_work_bytes */
+size_t tbk_pose_graph_work_bytes(int ngraphs, int nnodes, int nfixed, int edge_pitch);
+int tbk_pose_graph_batch(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, float* d_poses, const tb_pg_edge* d_edges,
+                         const int32_t* d_counts, int edge_pitch, int iters, double* d_stats, void* d_work);
+/* loop correction in the VO loop (k_pgo.hip): the graph of the stored keyframes (ring slots (oldest + i) % cap, i < nlive) and the
+ * current frame, cap + 1 nodes and edge pitch cap + 1 per sequence; and the adoption of the solver's poses */
+int tbk_vo_loop_graph(tb_ctx* ctx, int nseq, int cap, int nlive, int oldest, int frame, int topk, double w_rot, double w_trans,
+                      const float* s_Tcw, const int32_t* s_kf_ids, const float* cur_Tcw, const int32_t* best_rank, const int32_t* best_kf,
+                      const float* best_Tcw, float* before, float* after, int32_t* node_kf, int32_t* nnodes, tb_pg_edge* edges,
+                      int32_t* ecount);
+int tbk_vo_loop_adopt(tb_ctx* ctx, int nseq, int cap, int nlive, int oldest, int topk, int pitch, const float* before, const float* after,
+                      const int32_t* ecount, const double* stats, const int32_t* best_rank, const int32_t* best_kf,
+                      const int32_t* cand_inliers, float* s_Tcw, float* s_mp, const uint8_t* s_valid, const int32_t* s_counts, float* kf_mp,
+                      const uint8_t* kf_valid, const int32_t* kf_cnt, float* mp, const uint8_t* valid, const int32_t* key_counts, float* Tcw,
+                      uint8_t* closed, int32_t* loop_kf, int32_t* loop_inliers);
 int tbk_clahe(tb_ctx* ctx, int nimg, const uint8_t* d_src, int w, int h, int stride, size_t spitch, double clip_limit, int tiles_x,
               int tiles_y, uint8_t* d_dst, int dstride, size_t dpitch, uint8_t* d_lut);
 int tbk_flow_accept(tb_ctx* ctx, int npairs, const float* d_cur, uint8_t* d_status, const int32_t* d_counts, int pts_pitch, int width,

@@ -108,6 +108,115 @@ __device__ inline PoSE3 po_exp_mul(const double* u, const PoSE3& T) {
     po_normalize(r);
     return r;
 }
+/* A * B, normalised like po_exp_mul's product */
+__device__ inline PoSE3 po_mul(const PoSE3& A, const PoSE3& B) {
+    PoSE3 r;
+    r.qw = A.qw * B.qw - A.qx * B.qx - A.qy * B.qy - A.qz * B.qz;
+    r.qx = A.qw * B.qx + A.qx * B.qw + A.qy * B.qz - A.qz * B.qy;
+    r.qy = A.qw * B.qy + A.qy * B.qw + A.qz * B.qx - A.qx * B.qz;
+    r.qz = A.qw * B.qz + A.qz * B.qw + A.qx * B.qy - A.qy * B.qx;
+    const double bt[3] = {B.tx, B.ty, B.tz};
+    double rt[3];
+    po_rot(A, bt, rt);
+    r.tx = A.tx + rt[0]; r.ty = A.ty + rt[1]; r.tz = A.tz + rt[2];
+    po_normalize(r);
+    return r;
+}
+__device__ inline PoSE3 po_inverse(const PoSE3& T) {
+    PoSE3 r;
+    r.qx = -T.qx; r.qy = -T.qy; r.qz = -T.qz; r.qw = T.qw;
+    const double t[3] = {T.tx, T.ty, T.tz};
+    double rt[3];
+    po_rot(r, t, rt);
+    r.tx = -rt[0]; r.ty = -rt[1]; r.tz = -rt[2];
+    return r;
+}
+/* Below PO_SMALL_ANGLE the coefficients of Log and of the inverse left Jacobian that cancel take three terms of their series
+ * (error below 2e-11 relative at the switch); tests/pose_graph_reference.py switches at the same angle. */
+#define PO_SMALL_ANGLE 0.1
+/* k of V^-1 = Jl^-1 of SO(3) = I - Omega / 2 + k Omega^2 */
+__device__ inline double po_so3_inv_coeff(double theta) {
+    if (theta < PO_SMALL_ANGLE) {
+        const double t2 = theta * theta;
+        return 1.0 / 12 + t2 / 720 + t2 * t2 / 30240;
+    }
+    const double h = 0.5 * theta;
+    return (1.0 - h * cos(h) / sin(h)) / (theta * theta);
+}
+/* o = (I - Omega / 2 + k Omega^2) v, Omega = [om]x */
+__device__ inline void po_so3_inv_apply(const double* om, double k, const double* v, double* o) {
+    const double c[3] = {om[1] * v[2] - om[2] * v[1], om[2] * v[0] - om[0] * v[2], om[0] * v[1] - om[1] * v[0]};
+    const double cc[3] = {om[1] * c[2] - om[2] * c[1], om[2] * c[0] - om[0] * c[2], om[0] * c[1] - om[1] * c[0]};
+    for (int i = 0; i < 3; i++) o[i] = v[i] - 0.5 * c[i] + k * cc[i];
+}
+/* r = (omega, upsilon) with SE3Quat::exp(r) = T, the angle in [0, pi]; T normalised (qw >= 0) */
+__device__ inline void po_log(const PoSE3& T, double* r) {
+    const double n = sqrt(T.qx * T.qx + T.qy * T.qy + T.qz * T.qz);
+    const double theta = 2.0 * atan2(n, T.qw);
+    const double s = theta < 0.00001 ? 2.0 / T.qw : theta / n;
+    r[0] = T.qx * s; r[1] = T.qy * s; r[2] = T.qz * s;
+    const double t[3] = {T.tx, T.ty, T.tz};
+    po_so3_inv_apply(r, po_so3_inv_coeff(theta), t, r + 3);
+}
+/* Ad(T) = [[R, 0], [[t]x R, R]] for the (omega, upsilon) ordering, row-major 6x6 */
+__device__ inline void po_adjoint(const PoSE3& T, double* A) {
+    double R[9];
+    po_to_R(T, R);
+    const double tx[9] = {0, -T.tz, T.ty, T.tz, 0, -T.tx, -T.ty, T.tx, 0};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            A[i * 6 + j] = R[i * 3 + j];
+            A[i * 6 + 3 + j] = 0.0;
+            A[(3 + i) * 6 + 3 + j] = R[i * 3 + j];
+            A[(3 + i) * 6 + j] = tx[i * 3] * R[j] + tx[i * 3 + 1] * R[3 + j] + tx[i * 3 + 2] * R[6 + j];
+        }
+}
+__device__ inline void po_mul3(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+}
+/* inverse left Jacobian of SE(3) at r = (omega, upsilon), row-major 6x6: [[Ji, 0], [-Ji Q Ji, Ji]], Ji = Jl^-1 of SO(3) and
+ * Q = Up / 2 + c1 (Om Up + Up Om + Om Up Om) + c2 (Om Om Up + Up Om Om - 3 Om Up Om) + c3 (Om Up Om Om + Om Om Up Om) */
+__device__ inline void po_jl_inv(const double* r, double* J) {
+    const double theta = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    double c1, c2, c3;
+    if (theta < PO_SMALL_ANGLE) {
+        const double t2 = theta * theta;
+        c1 = 1.0 / 6 - t2 / 120 + t2 * t2 / 5040;
+        c2 = 1.0 / 24 - t2 / 720 + t2 * t2 / 40320;
+        c3 = 1.0 / 120 - t2 / 2520 + t2 * t2 / 120960;
+    } else {
+        const double s = sin(theta), c = cos(theta), t2 = theta * theta;
+        c1 = (theta - s) / (t2 * theta);
+        c2 = (t2 + 2 * c - 2) / (2 * t2 * t2);
+        c3 = (2 * theta - 3 * s + theta * c) / (2 * t2 * t2 * theta);
+    }
+    const double Om[9] = {0, -r[2], r[1], r[2], 0, -r[0], -r[1], r[0], 0};
+    const double Up[9] = {0, -r[5], r[4], r[5], 0, -r[3], -r[4], r[3], 0};
+    double OU[9], UO[9], OUO[9], OOU[9], UOO[9], OUOO[9], OOUO[9], Om2[9], Ji[9], Q[9], T1[9], T2[9];
+    po_mul3(Om, Up, OU);
+    po_mul3(Up, Om, UO);
+    po_mul3(OU, Om, OUO);
+    po_mul3(Om, OU, OOU);
+    po_mul3(UO, Om, UOO);
+    po_mul3(OUO, Om, OUOO);
+    po_mul3(Om, OUO, OOUO);
+    po_mul3(Om, Om, Om2);
+    const double k = po_so3_inv_coeff(theta);
+    for (int i = 0; i < 9; i++) {
+        Q[i] = 0.5 * Up[i] + c1 * (OU[i] + UO[i] + OUO[i]) + c2 * (OOU[i] + UOO[i] - 3 * OUO[i]) + c3 * (OUOO[i] + OOUO[i]);
+        Ji[i] = ((i % 4 == 0) ? 1.0 : 0.0) - 0.5 * Om[i] + k * Om2[i];
+    }
+    po_mul3(Ji, Q, T1);
+    po_mul3(T1, Ji, T2);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            J[i * 6 + j] = Ji[i * 3 + j];
+            J[i * 6 + 3 + j] = 0.0;
+            J[(3 + i) * 6 + j] = -T2[i * 3 + j];
+            J[(3 + i) * 6 + 3 + j] = Ji[i * 3 + j];
+        }
+}
 /* un-pivoted Cholesky solve of the 6x6 system; false if not positive definite */
 __device__ inline bool po_chol6(const double* H, double lambda, const double* b, double* x) {
     double A[36];

@@ -82,6 +82,18 @@ struct tb_vo {
     float* rc_best_Tcw = nullptr;                                        /* [nseq][16] */
     int32_t* rc_masked = nullptr;                                        /* [nseq][topk] */
     int32_t *rc_word_ring = nullptr, *rc_node_ring = nullptr;            /* [nseq][capacity][P] */
+    /* loop correction (tb_vo_loop_enable): per sequence a graph of cap + 1 nodes -- the stored keyframes, then the current frame
+     * -- at edge pitch cap + 1, the solver's statistics and what the last keyframe step t > 0 closed */
+    bool lp_on = false;
+    tb_vo_loop lp;
+    uint8_t* lp_closed = nullptr;                                        /* [nseq] */
+    int32_t *lp_kf = nullptr, *lp_inl = nullptr, *lp_nnodes = nullptr, *lp_ecount = nullptr;   /* [nseq] */
+    int32_t *lp_best_rank = nullptr, *lp_best_kf = nullptr;              /* [nseq] */
+    float* lp_best_Tcw = nullptr;                                        /* [nseq][16] */
+    int32_t* lp_node_kf = nullptr;                                       /* [nseq][cap + 1] */
+    float *lp_before = nullptr, *lp_after = nullptr;                     /* [nseq][cap + 1][16] */
+    tb_pg_edge* lp_edges = nullptr;                                      /* [nseq][cap + 1] */
+    double* lp_stats = nullptr;                                          /* [nseq][8] */
     /* ragged batches (tb_vo_reset_seq_dev / tb_vo_step_ragged_dev): the per-sequence frame counters live on the host in both
      * modes; everything else is allocated by the first call that needs it (vo_ragged_init) */
     bool ragged = false;                            /* the sequences no longer share one frame counter */
@@ -373,6 +385,7 @@ int tb_vo_create_lsh(tb_ctx* ctx, const tb_vo_params* p, const tb_vo_lsh* lsh, i
 }
 
 static int vo_recover_clear(tb_vo* vo);
+static int vo_loop_clear(tb_vo* vo);
 static int vo_window_clear(tb_vo* vo);
 static int vo_mono_clear(tb_vo* vo);
 static int vo_extract(tb_vo* vo, const uint8_t* images, int n);
@@ -394,6 +407,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
         if (vo->db) TB_TRY(tb_bow_db_clear(vo->db));   /* a new run: no keyframes yet */
         if (vo->store) TB_TRY(tb_kf_store_clear(vo->store));
         if (vo->rec_on) TB_TRY(vo_recover_clear(vo));
+        if (vo->lp_on) TB_TRY(vo_loop_clear(vo));
     }
     if (vo->mapK) {   /* an empty map */
         TB_HIP(ctx, hipMemsetAsync(vo->map_n[vo->map_cur], 0, (size_t)vo->nseq * sizeof(int32_t), ctx->stream));
@@ -418,6 +432,23 @@ static int vo_recover_clear(tb_vo* vo) {
     TB_HIP(ctx, hipMemsetAsync(vo->rc_track, 0, S * sizeof(int32_t), ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(vo->rc_kf, 0xff, S * sizeof(int32_t), ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(vo->rc_kf_ids, 0xff, S * sizeof(int32_t), ctx->stream));
+    return TB_OK;
+}
+
+/* the loop-correction state of a new run: nothing closed, no graph */
+static int vo_loop_clear(tb_vo* vo) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq, nn = (size_t)vo->store->cap + 1;
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_closed, 0, S, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_kf, 0xff, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_inl, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_nnodes, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_ecount, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_node_kf, 0xff, S * nn * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_before, 0, S * nn * 16 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_after, 0, S * nn * 16 * sizeof(float), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_edges, 0, S * nn * sizeof(tb_pg_edge), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->lp_stats, 0, S * 8 * sizeof(double), ctx->stream));
     return TB_OK;
 }
 
@@ -548,6 +579,32 @@ static int vo_recover_stage(tb_vo* vo, int b) {
     a.kf_word = kf.bow_word; a.kf_node = kf.bow_node; a.kf_ids = vo->rc_kf_ids;
     TB_TRY(tbk_vo_recover_adopt(ctx, S, &a));
     return tbk_vo_recover_switch(ctx, S, &a);
+}
+
+/* The loop-correction stage of a keyframe step t > 0 (include/tb_capi.h, tb_vo_loop), between the tracking step's pose and the
+ * keyframe block: query, verify, build the graph, solve, adopt. Every launch is on the context's stream; the ring is counted for
+ * the whole batch, so which slots are live is host arithmetic, and which sequences adopt is decided on the device. */
+static int vo_loop_stage(tb_vo* vo, int b, int t) {
+    tb_ctx* ctx = vo->ctx;
+    tb_kf_store* st = vo->store;
+    const tb_vo_loop& l = vo->lp;
+    const tb_vo_frame_out& o = vo->out[vo->oc];
+    const int S = vo->nseq, P = vo->P, cap = st->cap, nn = cap + 1;
+    const int nlive = (int)std::min<long long>(st->nadded, cap), oldest = st->nadded >= cap ? (int)(st->nadded % cap) : 0;
+    TB_TRY(tb_bow_db_query_dev(vo->db, o.bv_word, o.bv_val, o.bv_cnt, P, l.exclude_newest, l.topk, vo->rl_scores, vo->rl_top_slot,
+                               vo->rl_top_kf, vo->rl_top_score, nullptr));
+    const tb_reloc_params prm = vo_reloc_params(vo, l.min_inliers);
+    tb_reloc_out out = {};
+    out.best_rank = vo->lp_best_rank; out.best_kf = vo->lp_best_kf; out.best_Tcw = vo->lp_best_Tcw;
+    TB_TRY(tb_relocalize_batch_dev(st, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_desc, o.orb_cnt, o.fv_keys, o.fv_cnt, P,
+                                   vo->rl_top_slot, l.topk, &prm, &out));
+    TB_TRY(tbk_vo_loop_graph(ctx, S, cap, nlive, oldest, t, l.topk, l.w_rot, l.w_trans, st->Tcw, st->kf_ids, vo->Tcw[b], vo->lp_best_rank,
+                             vo->lp_best_kf, vo->lp_best_Tcw, vo->lp_before, vo->lp_after, vo->lp_node_kf, vo->lp_nnodes, vo->lp_edges,
+                             vo->lp_ecount));
+    TB_TRY(tb_pose_graph_batch_dev(ctx, S, nn, 1, vo->lp_after, vo->lp_edges, vo->lp_ecount, nn, l.iters, vo->lp_stats));
+    return tbk_vo_loop_adopt(ctx, S, cap, nlive, oldest, l.topk, P, vo->lp_before, vo->lp_after, vo->lp_ecount, vo->lp_stats, vo->lp_best_rank,
+                             vo->lp_best_kf, st->ninl, st->Tcw, st->mp, st->valid, st->counts, vo->kf.mp, vo->kf.valid, vo->kf.cnt, vo->mp[b],
+                             vo->valid[b], vo->kcnt[b], vo->Tcw[b], vo->lp_closed, vo->lp_kf, vo->lp_inl);
 }
 
 /* ORB operator() on n images. The extractor's results do not outlive its next call, so a descriptor tracker copies them into
@@ -747,6 +804,7 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
     const int S = vo->nseq, b = vo->cur ^ 1;
     TB_TRY(tbk_vo_copy_image(vo->ctx, S, left, vo->p.width, vo->p.height, stride, pitch, vo->img[b]));
     TB_TRY(vo_track(vo, t));
+    if (vo->lp_on && keyframe && t > 0) TB_TRY(vo_loop_stage(vo, b, t));
     if (vo->wb_on && t > 0) {   /* the frame's slot of the segment log */
         const tb_vo_frame_out& o = vo->out[vo->oc];
         const int slot = t - vo->kf_frame;
@@ -1073,6 +1131,7 @@ int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm) {
     if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
     if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable after a step (frame %d)", vo->next - 1);
     if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: recovery is enabled already");
+    if (vo->lp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: loop correction is enabled; the two are not combined yet");
     if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: null parameters");
     if (prm->lost_inliers < 0 || prm->min_inliers < 0 || prm->exclude_newest < 0 || prm->topk < 1 || prm->topk > vo->store->max_cand)
         return tb_fail(ctx, TB_EINVAL, "tb_vo_recover_enable: lost_inliers %d, topk %d (1..%d), exclude_newest %d, min_inliers %d",
@@ -1105,6 +1164,61 @@ int tb_vo_recover_state_dev(tb_vo* vo, const uint8_t** lost, const int32_t** tra
     if (kf_ids) *kf_ids = vo->rc_kf_ids;
     if (kf_word_ring) *kf_word_ring = vo->rc_word_ring;
     if (kf_node_ring) *kf_node_ring = vo->rc_node_ring;
+    return TB_OK;
+}
+
+int tb_vo_loop_enable(tb_vo* vo, const tb_vo_loop* prm) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->next > 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable after a step, or on a ragged loop");
+    if (vo->lp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: loop correction is enabled already");
+    if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: recovery is enabled; the two are not combined yet");
+    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_loop_enable: null parameters");
+    if (vo->store->cap > 63)
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_loop_enable: store capacity %d: the graph holds the keyframes and the frame, 64 nodes", vo->store->cap);
+    if (prm->topk < 1 || prm->topk > vo->store->max_cand || prm->exclude_newest < 0 || prm->min_inliers < 0 || prm->iters < 0 ||
+        prm->iters > 99 || !(prm->w_rot >= 0) || !(prm->w_trans >= 0) || !std::isfinite(prm->w_rot) || !std::isfinite(prm->w_trans))
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_loop_enable: topk %d (1..%d), exclude_newest %d, min_inliers %d, iters %d (0..99), weights %g %g",
+                       prm->topk, vo->store->max_cand, prm->exclude_newest, prm->min_inliers, prm->iters, prm->w_rot, prm->w_trans);
+    const size_t S = (size_t)vo->nseq, nn = (size_t)vo->store->cap + 1;
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_closed, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_kf, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_inl, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_nnodes, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_ecount, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_best_rank, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_best_kf, S));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_best_Tcw, S * 16));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_node_kf, S * nn));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_before, S * nn * 16));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_after, S * nn * 16));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_edges, S * nn));
+    TB_TRY(tb_dev_alloc(ctx, vo->own, &vo->lp_stats, S * 8));
+    /* the solver's work buffer is planned here, so that no step grows it (growing waits for the stream) */
+    TB_TRY(tb_pose_graph_plan(ctx, vo->nseq, (int)nn, 1, (int)nn));
+    vo->lp = *prm;
+    vo->lp_on = true;
+    return vo_loop_clear(vo);
+}
+
+int tb_vo_loop_state_dev(tb_vo* vo, const uint8_t** closed, const int32_t** loop_kf, const int32_t** loop_inliers, const int32_t** nnodes,
+                         const int32_t** node_kf, const float** before, const float** after, const tb_pg_edge** edges,
+                         const int32_t** edge_counts, const double** stats) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->lp_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_loop_state_dev: loop correction is not enabled (tb_vo_loop_enable)");
+    if (closed) *closed = vo->lp_closed;
+    if (loop_kf) *loop_kf = vo->lp_kf;
+    if (loop_inliers) *loop_inliers = vo->lp_inl;
+    if (nnodes) *nnodes = vo->lp_nnodes;
+    if (node_kf) *node_kf = vo->lp_node_kf;
+    if (before) *before = vo->lp_before;
+    if (after) *after = vo->lp_after;
+    if (edges) *edges = vo->lp_edges;
+    if (edge_counts) *edge_counts = vo->lp_ecount;
+    if (stats) *stats = vo->lp_stats;
     return TB_OK;
 }
 

@@ -29,6 +29,10 @@ keyframe, PoseOptimization seeded with its pose, the candidate with the most inl
 `recover=True` (or a dict, see RECOVER_DEFAULTS; with relocalize=M) makes the loop use it: a sequence whose tracking step keeps
 fewer than lost_inliers inliers is relocalised inside the step, adopts the winner's pose, matches and map points, and tracks
 against the winning keyframe from then on. Which sequences do is decided on the device; the others are untouched.
+`loop_close=True` (or a dict, see LOOP_DEFAULTS; with relocalize=M, keyframe_db <= 63, lock-step, not with recover=) corrects the
+trajectory on a revisit: at a keyframe step whose best verified candidate reaches min_inliers, a pose graph of the stored
+keyframes and the current frame is optimised on the device (tb_pose_graph_batch_dev), the stored keyframes take their corrected
+poses, their map points move rigidly with them, and the frame spawns and is stored at the corrected pose. `loop()` shows it.
 
 The batch need not move in lock-step: `reset(Tcw0, which=)` restarts some sequences in their slots, `step(..., active=, keyframe=)`
 advances only the active ones and gives the flagged ones a keyframe off the cadence, `frames()` tells where each one is. A sequence
@@ -82,6 +86,8 @@ TRACKER_DEFAULTS = {
 # (ORB-SLAM's local-map tracking asks for 30), a candidate is accepted from 50 inliers on (its relocalisation's figure), the best
 # 4 candidates are verified and the keyframe being tracked against is left out of them.
 RECOVER_DEFAULTS = dict(lost_inliers=30, topk=4, exclude_newest=1, min_inliers=50)
+# loop_close=True. The weights 1 and 1 are the identity information ORB-SLAM's essential graph uses; the reference has no figure
+LOOP_DEFAULTS = dict(topk=4, exclude_newest=1, min_inliers=50, iters=10, w_rot=1.0, w_trans=1.0)
 # test_vo_1's searchByBow arguments (:207 setBowParam(30, ..., 5), :212 MapPointOnly false)
 # window_ba=True: 10 LM iterations, the keyframe held fixed (a second fixed frame is a noisy single-frame estimate and measured
 # worse), a point needs 2 inlier observations, a window needs 3 points for its pose to be adopted
@@ -130,7 +136,7 @@ def _tracker(kind, nlevels, params):
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, loop_close=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
         if mono:
@@ -159,6 +165,16 @@ class StereoVO:
                 raise TypeError("recover= takes no parameter %s" % ", ".join(sorted(unknown)))
             recover = dict(RECOVER_DEFAULTS, **(recover if isinstance(recover, dict) else {}))
         self.recover = recover or None
+        if loop_close and not relocalize:
+            raise TypeError("loop_close= needs relocalize=M: the loop edge is the verified candidate's pose")
+        if loop_close and recover:
+            raise TypeError("loop_close= and recover= are not combined yet")
+        if loop_close:
+            unknown = set(loop_close) - set(LOOP_DEFAULTS) if isinstance(loop_close, dict) else ()
+            if unknown:
+                raise TypeError("loop_close= takes no parameter %s" % ", ".join(sorted(unknown)))
+            loop_close = dict(LOOP_DEFAULTS, **(loop_close if isinstance(loop_close, dict) else {}))
+        self.loop_close = loop_close or None
         if tracker == "bow" and vocab is None:
             raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
         if tracker != "bow" and vocab is not None:
@@ -212,6 +228,10 @@ class StereoVO:
                             if recover:               # None = off: no call is made
                                 self.ctx.check(self.vo.recover_enable(capi.VORecover(*[int(recover[k]) for k in (
                                     "lost_inliers", "topk", "exclude_newest", "min_inliers")])))
+                            if loop_close:            # None = off: no call is made
+                                lc = loop_close
+                                self.ctx.check(self.vo.loop_enable(capi.VOLoop(int(lc["topk"]), int(lc["exclude_newest"]), int(lc["min_inliers"]),
+                                                                               int(lc["iters"]), float(lc["w_rot"]), float(lc["w_trans"]))))
                 elif tracker == "lsh":
                     self.vo = capi.VO(self.ctx, prm, self.S, lsh=trk)
                 else:
@@ -535,6 +555,24 @@ class StereoVO:
         i32 = ((self.S,), "<i4", torch.int32)
         return dict(lost=self._pget(d["lost"], (self.S,), "|u1", torch.uint8), track_inliers=self._pget(d["track_inliers"], *i32),
                     recovered_kf=self._pget(d["recovered_kf"], *i32), kf_ids=self._pget(d["kf_ids"], *i32))
+
+    def loop(self):
+        """The loop-correction state of the last keyframe step t > 0 (loop_close=...): dict(closed [S] uint8, loop_kf [S] int32 = the
+        kf_id of the keyframe the loop closed with or -1, loop_inliers [S], nnodes [S] = live keyframes + 1, node_kf [S, N + 1] (the
+        frame index for the current frame, -1 unused), before / after [S, N + 1, 4, 4], edges [S, N + 1, 80] uint8 (capi.PG_EDGE
+        records), edge_counts [S], stats [S, 8] float64). TB_ESTATE when off."""
+        if self.loop_close is None:
+            raise capi.TBError(capi.TB_ESTATE, "loop correction is off: StereoVO(..., keyframe_db=N, relocalize=M, loop_close=True)")
+        d = self.vo.loop_state_dev()
+        S, nn = self.S, self.db.capacity + 1
+        i32 = ((S,), "<i4", torch.int32)
+        return dict(closed=self._pget(d["closed"], (S,), "|u1", torch.uint8), loop_kf=self._pget(d["loop_kf"], *i32),
+                    loop_inliers=self._pget(d["loop_inliers"], *i32), nnodes=self._pget(d["nnodes"], *i32),
+                    node_kf=self._pget(d["node_kf"], (S, nn), "<i4", torch.int32),
+                    before=self._pget(d["before"], (S, nn, 4, 4), "<f4", torch.float32),
+                    after=self._pget(d["after"], (S, nn, 4, 4), "<f4", torch.float32),
+                    edges=self._pget(d["edges"], (S, nn, capi.PG_EDGE.itemsize), "|u1", torch.uint8),
+                    edge_counts=self._pget(d["edge_counts"], *i32), stats=self._pget(d["stats"], (S, 8), "<f8", torch.float64))
 
     def recovery_rings(self):
         """(word ids, node ids) [S, N, P] int32 of the stored keyframes, slot-aligned with keyframe_store()"""
