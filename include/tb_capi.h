@@ -443,6 +443,30 @@ int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, flo
                             int q_pitch, const int32_t* cand_slot, int ncand, const tb_reloc_params* params, const tb_reloc_out* out);
 int tb_reloc_rows_dev(tb_kf_store* st, int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts, int q_pitch,
                       const int32_t* cand_slot, int ncand, const int32_t* match_counts, int32_t* cand_rows);
+/* PnP in front of the pose stage (off unless enabled: a store that does not call it launches exactly what it launched before, and
+ * tb_relocalize_batch_dev's signature, tb_reloc_params and tb_reloc_out do not change). The pose stage above trusts the stored
+ * keyframe's pose as its seed; from a few metres away, or on a match list that is mostly wrong, PoseOptimization keeps nothing
+ * although the good rows are there. With tb_kf_store_pnp_enable(params (null: 256, 5.991, 0), min_consensus, expand) these stages
+ * run between rows and pose, per pair (tests/reloc_pnp_reference.py restates the composition on the CPU):
+ *   pnp      tb_pnp_ransac_batch_dev's kernel on the pair's rows with the stored Tcw as the prior
+ *   gather   consensus >= min_consensus (ORB-SLAM's minInliers is 10): the pair takes the PnP path -- its rows become the
+ *            consensus rows, in key order, and the pose stage is seeded with the PnP pose. Otherwise the pair runs as without
+ *            PnP, all rows and the stored seed, and its outputs are the same bytes
+ *   pose     as above, on the gathered rows
+ *   expand   (expand = 1) for a pair on the PnP path: every original row that is an inlier of the optimised pose (the RANSAC's
+ *            rule, on the float32 pose) in key order, and the pose stage once more, seeded with the optimised pose; its pose, inlier
+ *            count, rows and flags replace the first stage's
+ * cand_rows is the number of rows the pair's last pose stage ran on; tb_kf_store_work_dev's rows / row_counts / outlier are
+ * those rows. Selection is unchanged. Every buffer is allocated at enable, the second rows buffer only with expand: a
+ * verification still allocates nothing. TB_ESTATE: enabled already; TB_EINVAL: hypotheses outside 1..1024, chi2_max, min_consensus
+ * < 3, expand not 0 or 1.
+ * tb_kf_store_pnp_state_dev lends device views of the last call's per-pair PnP outputs (each nullable): the rows before the gather
+ * [pairs][pitch] with row_counts [pairs], consensus [pairs], winner [pairs][2], the PnP pose Tcw [pairs][16], took [pairs] bytes
+ * (1: the pair took the PnP path), flags [pairs]. TB_ESTATE when not enabled. */
+struct tb_pnp_params;   /* below, with tb_pnp_ransac_batch_dev */
+int tb_kf_store_pnp_enable(tb_kf_store* st, const struct tb_pnp_params* params, int min_consensus, int expand);
+int tb_kf_store_pnp_state_dev(tb_kf_store* st, const tb_obs** rows, const int32_t** row_counts, const int32_t** consensus,
+                              const int32_t** winner, const float** Tcw, const uint8_t** took, const int32_t** flags);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -555,6 +579,44 @@ int tb_linear_triangle_batch_dev(tb_ctx* ctx, int npairs, const float* xy0, cons
 int tb_linear_triangle(tb_ctx* ctx, const float* xy0, const float* xy1, int n, const float Tcw0[16], const float Tcw1[16],
                        const double K[4], const float* inv_sigma2_0, const float* inv_sigma2_1, const uint8_t* skip,
                        const tb_triangulate_params* prm, float* points, uint8_t* flags, int32_t tally[6]);
+/* A pose from 3D-2D rows without a prior: P3P hypotheses in a RANSAC, batched and device-resident. The reference has no PnP;
+ * ORB-SLAM puts one in front of PoseOptimization when it relocalises, which is what this is for (DESIGN.md 9l has the
+ * derivation; tests/pnp_reference.py is the definition, statement for statement, and the kernel matches it bit for bit).
+ * Problem p reads counts[p] rows tb_obs (u, v, X, Y, Z, inv_sigma2) at obs + p * obs_pitch, as tb_pose_opt_batch_dev does; a
+ * count is clamped to [0, obs_pitch]. K = fx, fy, cx, cy (host).
+ *   sampling  counter based: draw k of hypothesis h is mix(seed + (8 h + k + 1) * 0x9E3779B97F4A7C15) (splitmix64's output
+ *             function; output 8 h + k of synth.Stream(seed)); its high 32 bits times n, shifted right by 32, is a row. Draws
+ *             k = 0, 1, ... are taken until three distinct rows are found or 8 are used up; a hypothesis that runs out is void.
+ *             The sample depends on (seed, h, n) only, never on p: a problem gives the same bits alone and inside any batch
+ *   solver    P3P in float64 with + - * / sqrt and comparisons only and fixed loop counts: the unit bearings and the squared
+ *             side lengths give two homogeneous quadrics in the depths, a real root of the cubic det(D1 + g D2) = 0 (80
+ *             bisections inside the Cauchy bound, 2 Newton steps) a pair of planes, each plane a quadratic: at most 4 depth
+ *             triples, solutions 0, 1 from the first plane and 2, 3 from the second; R = Y X^-1 from the two edge vectors and
+ *             their cross product, t = L1 y1 - R x1. Coincident or collinear samples, non-finite rows and depths that are not
+ *             all positive give no solution, never a NaN pose
+ *   score     every solution against all n rows in float64: a row is an inlier iff its camera depth is > 0 and
+ *             ((u - u^)^2 + (v - v^)^2) * inv_sigma2 <= chi2_max. The winner has the most inliers, ties to the lower hypothesis,
+ *             then the lower solution. Tcw_prior [nproblems][16] (nullable) is scored as hypothesis -1 and wins ties. Counts are
+ *             integer sums; there is no floating-point atomic anywhere
+ *   void      n < 3, or no prior and no hypothesis with a solution: consensus 0, winner (-2, 0), Tcw_out = the prior or the
+ *             identity, an all-zero mask, flags bit 0 set
+ * Out (device, each nullable): Tcw_out [nproblems][16] float (the float32 rounding of the winning float64 pose; a winning prior
+ * is returned as given), consensus [nproblems], inlier [nproblems][obs_pitch] bytes (zero beyond the count), winner
+ * [nproblems][2] (hypothesis, solution; (-1, 0) the prior), flags [nproblems]. Asynchronous on the context's stream, no host
+ * synchronisation, no host <-> device copy, no work buffer: one launch whose state is registers and LDS. At most 65535 problems
+ * per call (TB_EUNSUPPORTED). TB_EINVAL: null obs / counts / K / params, obs_pitch < 1, hypotheses outside 1..1024, chi2_max
+ * negative or not finite, fx or fy not positive.
+ * tb_pnp_ransac: the host form, one problem of n rows on the batched entry (host pointers; Tcw_prior nullable; inlier [n]). */
+typedef struct tb_pnp_params {
+    int hypotheses;      /* 1..1024; 256 */
+    double chi2_max;     /* 5.991, PoseOptimization's chi2Mono */
+    uint64_t seed;
+} tb_pnp_params;
+int tb_pnp_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_obs* obs, const int32_t* counts, int obs_pitch,
+                            const tb_pnp_params* params, const float* Tcw_prior, float* Tcw_out, int32_t* consensus, uint8_t* inlier,
+                            int32_t* winner, int32_t* flags);
+int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, const tb_pnp_params* params, const float* Tcw_prior,
+                  float Tcw_out[16], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags);
 /* SURVEY 8(f) row 2, first part -- the optical-flow matcher.
  * tb_optical_flow_pyr_lk replaces the call cv::calcOpticalFlowPyrLK(prev, next, prev_pts, next_pts, status, err,
  * Size(win, win), max_level) of matcher.cpp:744 (default criteria: 30 iterations / eps 0.01, flags 0,
@@ -933,6 +995,11 @@ int tb_vo_reloc_enable(tb_vo* vo, int max_candidates);
 int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
                          double* top_score, int32_t* top_count, const tb_reloc_out* out);
 int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
+/* tb_kf_store_pnp_enable on the loop's store: tb_vo_relocalize_dev then runs the PnP verification (tb_kf_store_pnp_state_dev on
+ * tb_vo_kf_store_get's store lends its per-pair outputs) and stays a query that changes no state tensor. TB_ESTATE: relocalisation
+ * not enabled, after the first step, enabled already, or together with tb_vo_recover_enable / tb_vo_loop_enable in either order:
+ * their adoption kernels read the verification's rows by key, and have to be read against gathered rows first. */
+int tb_vo_reloc_pnp_enable(tb_vo* vo, const tb_pnp_params* params, int min_consensus, int expand);
 /* Recovery in a TB_VO_BOW loop with relocalisation (off unless enabled; a loop that does not enable it launches what it launched
  * before): a sequence that loses track adopts the relocalisation pose and tracks against the keyframe that gave it. The reference
  * has no such step; every operator is the reference's -- searchByBow (matcher.cpp:619-721), PoseOptimization and its rows

@@ -1,0 +1,190 @@
+"""GPU tests of tb_pnp_ransac_batch_dev / tb_pnp_ransac against the definition in tests/pnp_reference.py on the constructed
+problems of tests/pnp_cases.py. Winner, consensus, inlier mask and flags exact, the pose bit for bit the float32 rounding of the
+reference's float64 pose; every case's closest chi2 to chi2_max under its winner is checked to lie farther than 1e-9 relative, so
+that the exactness means something. Pitch 320 = one LDS chunk (256 rows) and a quarter."""
+import numpy as np
+import pytest
+import torch
+
+from trackingbench_slam_amd import capi
+
+import pnp_cases as pc
+import pnp_reference as pr
+
+pytestmark = pytest.mark.gpu
+
+PITCH = 320
+SEED = 5
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(0)
+    yield c
+    c.close()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _run(ctx, obs, counts, priors=None, hypotheses=256, chi2_max=pr.CHI2_MAX, seed=SEED):
+    """the batched entry on obs [P][pitch] -> dict of host arrays; outputs pre-filled so that an unwritten entry shows"""
+    P, pitch = obs.shape
+    d_obs, d_cnt = torch.from_numpy(obs.view(np.float32).reshape(P, pitch, 6).copy()).cuda(), _dev(np.asarray(counts, np.int32))
+    d_pr = None if priors is None else _dev(np.asarray(priors, np.float32).reshape(P, 16))
+    T = torch.full((P, 16), -7.0, dtype=torch.float32, device="cuda")
+    cons = torch.full((P,), -9, dtype=torch.int32, device="cuda")
+    inl = torch.full((P, pitch), 99, dtype=torch.uint8, device="cuda")
+    win = torch.full((P, 2), -9, dtype=torch.int32, device="cuda")
+    flags = torch.full((P,), -9, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.check(ctx.pnp_ransac_dev(P, pc.K, d_obs.data_ptr(), d_cnt.data_ptr(), pitch, 0 if d_pr is None else d_pr.data_ptr(), T.data_ptr(),
+                                 cons.data_ptr(), inl.data_ptr(), win.data_ptr(), flags.data_ptr(), hypotheses=hypotheses,
+                                 chi2_max=chi2_max, seed=seed))
+    ctx.synchronize()
+    return dict(Tcw=T.cpu().numpy().reshape(P, 4, 4), consensus=cons.cpu().numpy(), inlier=inl.cpu().numpy(), winner=win.cpu().numpy(),
+                flags=flags.cpu().numpy())
+
+
+def _check(got, refs, chi2_max=pr.CHI2_MAX):
+    for p, r in enumerate(refs):
+        tag = "problem %d" % p
+        assert tuple(got["winner"][p]) == r["winner"], tag
+        assert got["consensus"][p] == r["consensus"] and got["flags"][p] == r["flags"], tag
+        assert np.array_equal(got["inlier"][p], r["inlier"]), tag
+        assert np.array_equal(got["Tcw"][p].view(np.uint32), r["Tcw32"].view(np.uint32)), tag
+        assert pr.margin(r, chi2_max) > 1e-9, tag
+
+
+def _stack(problems):
+    return np.stack([p[0] for p in problems])
+
+
+@pytest.fixture(scope="module")
+def batch_a():
+    """row counts around every boundary, then the row contents; (obs [P][PITCH], counts, names)"""
+    items = []
+    for i, n in enumerate((2, 3, 4, 64, 65, pc.CHUNK - 1, pc.CHUNK, pc.CHUNK + 1, PITCH)):
+        items.append(("n%d" % n, pc.problem(100 + i, n, PITCH)[0], n))
+    items.insert(5, ("empty", pc.problem(99, 50, PITCH)[0], 0))                      # a zero count in the middle of the batch
+    items.append(("above", pc.problem(120, PITCH, PITCH)[0], PITCH + 80))            # a count above the pitch is clamped
+    items.append(("negative", pc.problem(121, 40, PITCH)[0], -3))
+    items.append(("outliers", pc.problem(122, 200, PITCH, outliers=1.0)[0], 200))
+    items.append(("coplanar", pc.problem(123, 200, PITCH, kind="coplanar")[0], 200))
+    items.append(("behind", pc.problem(124, 200, PITCH, kind="behind")[0], 200))
+    nan = pc.problem(125, 200, PITCH, outliers=0.3)[0]
+    nan["u"][7] = np.nan
+    nan["X"][11] = np.inf
+    nan["inv_sigma2"][13] = np.nan
+    items.append(("nan", nan, 200))
+    items.append(("octaves", pc.problem(126, 200, PITCH, octaves=True)[0], 200))
+    same = pc.problem(127, 1, PITCH)[0]
+    same[:40] = same[0]
+    items.append(("coincident", same, 40))                                           # forty copies of one row: every sample coincident
+    obs = np.stack([it[1] for it in items])
+    counts = np.array([it[2] for it in items], np.int32)
+    return obs, counts, [it[0] for it in items]
+
+
+@pytest.fixture(scope="module")
+def ref_a(batch_a):
+    obs, counts, _ = batch_a
+    return pr.ransac_batch(pc.K, obs, counts, 256, pr.CHI2_MAX, SEED)
+
+
+def test_batch_matches_the_definition(ctx, batch_a, ref_a):
+    obs, counts, names = batch_a
+    got = _run(ctx, obs, counts)
+    _check(got, ref_a)
+    by = dict(zip(names, range(len(names))))
+    for void in ("n2", "empty", "negative", "coincident"):
+        p = by[void]
+        assert got["flags"][p] == 1 and tuple(got["winner"][p]) == (-2, 0) and got["consensus"][p] == 0 and not got["inlier"][p].any()
+        assert np.array_equal(got["Tcw"][p], np.eye(4, dtype=np.float32))
+    for p, n in enumerate(counts):   # nothing is marked beyond a count
+        assert not got["inlier"][p, max(min(int(n), PITCH), 0):].any()
+    for found in ("n64", "n65", "n%d" % (pc.CHUNK - 1), "n%d" % pc.CHUNK, "n%d" % (pc.CHUNK + 1), "n%d" % PITCH, "above", "coplanar", "octaves", "nan"):
+        p = by[found]
+        n = min(int(counts[p]), PITCH)
+        assert got["consensus"][p] >= 0.25 * n, found      # at least half of the good rows (half of all rows are good): the pose was found
+    assert got["consensus"][by["outliers"]] < 12
+    assert not got["inlier"][by["nan"]][[7, 11, 13]].any()
+
+
+@pytest.mark.parametrize("hyp", [1, 100, 300])
+def test_hypothesis_counts(ctx, hyp):
+    """one hypothesis, a count that is no multiple of 64, a thread's second hypothesis"""
+    items = [pc.problem(200 + i, n, PITCH) for i, n in enumerate((100, pc.CHUNK + 1, PITCH))]
+    obs, counts = _stack(items), np.array([100, pc.CHUNK + 1, PITCH], np.int32)
+    ref = pr.ransac_batch(pc.K, obs, counts, hyp, pr.CHI2_MAX, SEED + hyp)
+    got = _run(ctx, obs, counts, hypotheses=hyp, seed=SEED + hyp)
+    _check(got, ref)
+
+
+def test_a_threads_second_hypothesis_wins(ctx):
+    """120 rows with 18 good ones: at seed 307 the reference's first all-good sample is hypothesis 276, thread 20's second"""
+    obs = pc.problem(203, 120, PITCH, outliers=0.85)[0][None]
+    ref = pr.ransac_batch(pc.K, obs, [120], 300, pr.CHI2_MAX, 307)
+    assert ref[0]["winner"] == (276, 2) and ref[0]["consensus"] == 18
+    _check(_run(ctx, obs, [120], hypotheses=300, seed=307), ref)
+
+
+def test_a_prior_wins_a_tie_and_loses_to_a_better_pose(ctx):
+    obs, _, T = pc.problem(300, 100, PITCH, outliers=0.0, noise=0.0)       # every row exact: the prior and the best hypothesis tie at 100
+    noisy = pc.problem(301, 100, PITCH)[0]
+    two = pc.problem(302, 2, PITCH)[0]
+    stack = np.stack([obs, obs, noisy, two])
+    counts = np.array([100, 100, 100, 2], np.int32)
+    far = pc.moved(T, 0.2, 3.0).astype(np.float64)
+    priors = np.stack([T, far, far, far]).astype(np.float32)
+    ref = pr.ransac_batch(pc.K, stack, counts, 256, pr.CHI2_MAX, SEED, priors)
+    got = _run(ctx, stack, counts, priors)
+    _check(got, ref)
+    assert tuple(got["winner"][0]) == (-1, 0) and got["consensus"][0] == 100
+    assert np.array_equal(got["Tcw"][0].view(np.uint32), priors[0].view(np.uint32))
+    assert got["winner"][1, 0] >= 0 and got["consensus"][1] == 100 and got["winner"][2, 0] >= 0
+    assert tuple(got["winner"][3]) == (-2, 0) and got["flags"][3] == 1 and np.array_equal(got["Tcw"][3].view(np.uint32), priors[3].view(np.uint32))
+
+
+def test_a_problem_alone_and_inside_a_batch_and_twice(ctx, batch_a, ref_a):
+    obs, counts, names = batch_a
+    p = names.index("n%d" % (pc.CHUNK + 1))
+    alone = _run(ctx, obs[p:p + 1], counts[p:p + 1])
+    five = np.stack([obs[0], obs[3], obs[8], obs[p], obs[1]])
+    inside = _run(ctx, five, np.array([counts[0], counts[3], counts[8], counts[p], counts[1]], np.int32))
+    again = _run(ctx, obs[p:p + 1], counts[p:p + 1])
+    for k in alone:
+        assert alone[k][0].tobytes() == inside[k][3].tobytes() == again[k][0].tobytes(), k
+    _check(alone, [ref_a[p]])
+
+
+def test_host_form_equals_the_batched_one(ctx, batch_a, ref_a):
+    obs, counts, names = batch_a
+    for name in ("n2", "n65", "n%d" % (pc.CHUNK + 1), "octaves"):
+        p = names.index(name)
+        n = int(counts[p])
+        h = ctx.pnp_ransac(pc.K, obs[p, :n], seed=SEED)
+        r = ref_a[p]
+        assert h["winner"] == r["winner"] and h["consensus"] == r["consensus"] and h["flags"] == r["flags"], name
+        assert np.array_equal(h["inlier"], r["inlier"][:n]) and np.array_equal(h["Tcw"].view(np.uint32), r["Tcw32"].view(np.uint32)), name
+    assert ctx.pnp_ransac(pc.K, obs[0, :0])["flags"] == 1
+
+
+def test_nullable_outputs_and_argument_checks(ctx, batch_a):
+    obs, counts, _ = batch_a
+    d_obs, d_cnt = torch.from_numpy(obs.view(np.float32).reshape(len(obs), PITCH, 6).copy()).cuda(), _dev(counts)
+    o, c = d_obs.data_ptr(), d_cnt.data_ptr()
+    assert ctx.pnp_ransac_dev(len(obs), pc.K, o, c, PITCH) == capi.TB_OK       # every output null
+    ctx.synchronize()
+    assert ctx.pnp_ransac_dev(1, pc.K, 0, c, PITCH) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, 0, PITCH) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, c, 0) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(-1, pc.K, o, c, PITCH) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, c, PITCH, hypotheses=0) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, c, PITCH, hypotheses=1025) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, c, PITCH, chi2_max=float("nan")) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, pc.K, o, c, PITCH, chi2_max=-1.0) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(1, (0.0, 360.0, 320.0, 120.0), o, c, PITCH) == capi.TB_EINVAL
+    assert ctx.pnp_ransac_dev(65536, pc.K, o, c, PITCH) == capi.TB_EUNSUPPORTED
+    assert ctx.pnp_ransac_dev(0, pc.K, o, c, PITCH) == capi.TB_OK

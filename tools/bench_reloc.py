@@ -14,7 +14,10 @@ tb_search_by_bow_batch_dev + tb_pose_opt_batch_dev calls on gathered copies of t
 rows between the two calls are the ones the batched call made, which the yardstick is not charged for). Its match counts and
 inlier counts must equal the batched call's.
 
-    python tools/bench_reloc.py [--frames 32] [--keys 2000] [--sizes 16 64 256] [--ring 16] [--topk 4] [--reps 10] [--out FILE]"""
+--pnp enables tb_kf_store_pnp_enable (256 hypotheses, min_consensus 10, expand 1) on the store: the line then carries the PnP
+kernels in its split and how many pairs took the PnP path, and no yardstick (the separate calls have no PnP to compare with).
+
+    python tools/bench_reloc.py [--frames 32] [--keys 2000] [--sizes 16 64 256] [--ring 16] [--topk 4] [--reps 10] [--pnp] [--out FILE]"""
 import argparse
 import concurrent.futures
 import ctypes as C
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--topk", type=int, default=4)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--pnp", action="store_true", help="P3P-RANSAC in front of the pose stage (tb_kf_store_pnp_enable)")
     ap.add_argument("--out", default=None, help="also write the lines to this JSON file (a list)")
     args = ap.parse_args()
 
@@ -109,6 +113,8 @@ def main():
         entry = (np.arange(S)[:, None] * 7 + np.arange(N)[None, :]) % F          # frame of ring entry (s, j)
         query = (np.arange(S) * 13 + 5) % F
         st = capi.KeyframeStore(ctx, S, N, P, topk)
+        if args.pnp:
+            ctx.check(st.pnp_enable())
         for j in range(N):
             idx = torch.from_numpy(entry[:, j]).to(dev)
             a = [t[idx].contiguous() for t in (kps_i, desc, counts, fv, fvc, mp_d, valid_d, poses_d)]
@@ -135,6 +141,25 @@ def main():
         ctx.synchronize()
         prof = ctx.profile_report()
         ctx.profile_enable(False)
+        if args.pnp:
+            pn = st.pnp_state(dev, topk)
+            inl = out["cand_inliers"].cpu().numpy()
+            line = {"metric": "candidate verification with PnP wall time (tb_relocalize_batch_dev after tb_kf_store_pnp_enable)",
+                    "value": round(ms, 4), "unit": "ms", "higher_is_better": False, "n_gpus": 1,
+                    "data": "%d synth_seq frames, %d keys/frame, cycled through the rings" % (F, args.keys),
+                    "config": {"S": S, "N": N, "topk": topk, "pitch": P, "reps": args.reps, "vocabulary": "synth k=10 L=5, levelsup 4",
+                               "pnp": {"hypotheses": 256, "chi2_max": 5.991, "seed": 0, "min_consensus": 10, "expand": 1}},
+                    "pairs": S * topk, "pairs_per_s": round(S * topk / (ms * 1e-3), 1),
+                    "mean_rows_before_pnp": round(float(pn["row_counts"].float().mean().item()), 1),
+                    "mean_consensus": round(float(pn["consensus"].float().mean().item()), 1),
+                    "pairs_on_the_pnp_path": int(pn["took"].sum().item()),
+                    "mean_rows_per_pair": round(float(out["cand_rows"].float().mean().item()), 1),
+                    "pairs_with_50_inliers": int((inl >= 50).sum()), "sequences_relocalised": int((out["best_rank"] >= 0).sum().item()),
+                    "kernels_ms_per_call": {k: round(v[1] / args.reps, 4) for k, v in sorted(prof.items())}}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            st.close()
+            continue
         work = {k: v.clone() for k, v in st.work(dev, topk).items()}
         torch.cuda.synchronize()
         # the yardstick: rank by rank on gathered copies

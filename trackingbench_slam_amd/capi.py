@@ -58,6 +58,7 @@ EXPORTS = [
     "tb_vo_create_lsh",
     "tb_linear_triangle", "tb_linear_triangle_batch_dev", "tb_vo_mono_enable", "tb_vo_mono_state_dev",
     "tb_pose_graph", "tb_pose_graph_batch_dev", "tb_pose_graph_plan", "tb_vo_loop_enable", "tb_vo_loop_state_dev",
+    "tb_pnp_ransac", "tb_pnp_ransac_batch_dev", "tb_kf_store_pnp_enable", "tb_kf_store_pnp_state_dev", "tb_vo_reloc_pnp_enable",
 ]
 
 TB_VOC_MAX_L = 8
@@ -290,6 +291,11 @@ class TriangulateParams(C.Structure):
     _fields_ = [("cos_parallax_max", C.c_double), ("chi2_max", C.c_double)]
 
 
+class PnpParams(C.Structure):
+    """tb_pnp_params of include/tb_capi.h"""
+    _fields_ = [("hypotheses", C.c_int), ("chi2_max", C.c_double), ("seed", C.c_uint64)]
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
@@ -421,6 +427,11 @@ class VO:
                                         p(q["top_kf"]), p(q["top_score"]), p(q["top_count"]), C.byref(ro))
         q.update(out)
         return rc, q
+
+    def reloc_pnp_enable(self, hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, expand=1):
+        """tb_vo_reloc_pnp_enable: returns the status code (0 or a negative TB_E* code), so the state checks can be tested."""
+        prm = PnpParams(int(hypotheses), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return lib().tb_vo_reloc_pnp_enable(self._h, C.byref(prm), int(min_consensus), int(expand))
 
     def recover_enable(self, prm):
         """tb_vo_recover_enable with a VORecover (None: a null pointer): returns the status code (0 or a negative TB_E* code), so
@@ -992,6 +1003,29 @@ class Context:
                                                   v(Tcw1_ptr), _p(K), v(inv_sigma2_0_ptr), v(inv_sigma2_1_ptr), v(skip_ptr),
                                                   C.byref(prm), v(points_ptr), v(flags_ptr), v(tally_ptr))
 
+    def pnp_ransac(self, K, obs, hypotheses=256, chi2_max=5.991, seed=0, prior=None):
+        """tb_pnp_ransac: a pose from the rows of one problem (an OBS array) without a prior, or with `prior` (4 x 4) as hypothesis
+        -1. Returns a dict: Tcw [4, 4] float32, consensus, inlier uint8 [n], winner (hypothesis, solution), flags."""
+        K = np.ascontiguousarray(K, np.float64)
+        obs = np.ascontiguousarray(obs, OBS).reshape(-1)
+        pr = None if prior is None else np.ascontiguousarray(prior, np.float32).reshape(16)
+        prm = PnpParams(int(hypotheses), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        T, inl, win = np.zeros(16, np.float32), np.zeros(len(obs), np.uint8), np.zeros(2, np.int32)
+        cons, flags = C.c_int(0), C.c_int(0)
+        self.check(lib().tb_pnp_ransac(self._h, _p(K), _p(obs) if len(obs) else None, len(obs), C.byref(prm), _p(pr), _p(T), C.byref(cons),
+                                       _p(inl) if len(obs) else None, _p(win), C.byref(flags)))
+        return dict(Tcw=T.reshape(4, 4), consensus=cons.value, inlier=inl, winner=(int(win[0]), int(win[1])), flags=flags.value)
+
+    def pnp_ransac_dev(self, nproblems, K, obs_ptr, counts_ptr, obs_pitch, prior_ptr=0, Tcw_ptr=0, consensus_ptr=0, inlier_ptr=0,
+                       winner_ptr=0, flags_ptr=0, hypotheses=256, chi2_max=5.991, seed=0):
+        """tb_pnp_ransac_batch_dev: device pointers (0 / None for the nullable ones), asynchronous on the context's stream.
+        Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        prm = PnpParams(int(hypotheses), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        v = lambda q: C.c_void_p(q or None)
+        return lib().tb_pnp_ransac_batch_dev(self._h, int(nproblems), _p(K), v(obs_ptr), v(counts_ptr), int(obs_pitch), C.byref(prm),
+                                             v(prior_ptr), v(Tcw_ptr), v(consensus_ptr), v(inlier_ptr), v(winner_ptr), v(flags_ptr))
+
     def local_ba(self, K, poses, nfixed, pts, obs, iters=10):
         K = np.ascontiguousarray(K, np.float64)
         poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16).copy()
@@ -1295,6 +1329,25 @@ class KeyframeStore:
         n, P = self.nseq * int(ncand), pitch.value
         spec = (("matches", (n, P, 4), "<i4", torch.int32), ("match_counts", (n,), "<i4", torch.int32), ("rows", (n, P, 6), "<f4", torch.float32),
                 ("row_counts", (n,), "<i4", torch.int32), ("outlier", (n, P), "|u1", torch.uint8))
+        return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
+
+    def pnp_enable(self, hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, expand=1):
+        """tb_kf_store_pnp_enable: P3P-RANSAC in front of the pose stage. Returns the status code (0 or a negative TB_E* code), so the
+        state and argument checks can be tested."""
+        prm = PnpParams(int(hypotheses), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return lib().tb_kf_store_pnp_enable(self._h, C.byref(prm), int(min_consensus), int(expand))
+
+    def pnp_state(self, device, ncand):
+        """tb_kf_store_pnp_state_dev: torch VIEWS (not copies) of the last call's per-pair PnP outputs for S x ncand pairs: rows
+        [pairs, P, 6] float32 (before the gather), row_counts [pairs], consensus [pairs], winner [pairs, 2], Tcw [pairs, 4, 4]
+        float32 (the PnP pose), took [pairs] uint8, flags [pairs]."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(7)]
+        self.ctx.check(lib().tb_kf_store_pnp_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        n, P = self.nseq * int(ncand), self.pitch
+        spec = (("rows", (n, P, 6), "<f4", torch.float32), ("row_counts", (n,), "<i4", torch.int32), ("consensus", (n,), "<i4", torch.int32),
+                ("winner", (n, 2), "<i4", torch.int32), ("Tcw", (n, 4, 4), "<f4", torch.float32), ("took", (n,), "|u1", torch.uint8),
+                ("flags", (n,), "<i4", torch.int32))
         return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
 
     def relocalize_rc(self, K, nlevels, scale, q_keys, q_desc, q_counts, q_fv_keys, q_fv_counts, cand_slot, map_point_only=True, th_low=50,

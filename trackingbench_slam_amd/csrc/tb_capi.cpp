@@ -1546,6 +1546,54 @@ int tb_kf_store_work_dev(tb_kf_store* st, tb_match** matches, int32_t** match_co
     return TB_OK;
 }
 
+int tb_kf_store_pnp_enable(tb_kf_store* st, const tb_pnp_params* prm, int min_consensus, int expand) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    if (st->pnp_on) return tb_fail(ctx, TB_ESTATE, "tb_kf_store_pnp_enable: enabled already");
+    static const tb_pnp_params dflt = {256, 5.991, 0};
+    const tb_pnp_params P = prm ? *prm : dflt;
+    if (P.hypotheses < 1 || P.hypotheses > 1024 || !(P.chi2_max >= 0.0) || !std::isfinite(P.chi2_max) || min_consensus < 3 ||
+        (expand != 0 && expand != 1))
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_pnp_enable: hypotheses %d (1..1024), chi2_max finite and not negative, min_consensus %d (>= 3), expand %d (0, 1)",
+                       P.hypotheses, min_consensus, expand);
+    const size_t pairs = (size_t)st->nseq * st->max_cand, pp = pairs * st->pitch;
+    tb_dev_owner& own = st->own;
+    TB_TRY(tb_dev_alloc(ctx, own, &st->rows0, pp));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->pmask, pp));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->took, pairs, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->ppose, pairs * 16, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->seed2, pairs * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->cnt0, pairs, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->pcons, pairs, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->pwin, pairs * 2, 0));
+    TB_TRY(tb_dev_alloc(ctx, own, &st->pflags, pairs, 0));
+    if (expand) {
+        TB_TRY(tb_dev_alloc(ctx, own, &st->rows2, pp));
+        TB_TRY(tb_dev_alloc(ctx, own, &st->outlier2, pp));
+        TB_TRY(tb_dev_alloc(ctx, own, &st->pose2, pairs * 16));
+        TB_TRY(tb_dev_alloc(ctx, own, &st->cnt2, pairs));
+        TB_TRY(tb_dev_alloc(ctx, own, &st->ninl2, pairs));
+    }
+    st->pnp = P; st->pnp_min = min_consensus; st->pnp_expand = expand;
+    st->pnp_on = true;
+    return TB_OK;
+}
+
+int tb_kf_store_pnp_state_dev(tb_kf_store* st, const tb_obs** rows, const int32_t** row_counts, const int32_t** consensus,
+                              const int32_t** winner, const float** Tcw, const uint8_t** took, const int32_t** flags) {
+    if (!st) return TB_EINVAL;
+    if (!st->pnp_on) return tb_fail(st->ctx, TB_ESTATE, "tb_kf_store_pnp_state_dev: PnP verification is not enabled");
+    if (rows) *rows = st->rows0;
+    if (row_counts) *row_counts = st->cnt0;
+    if (consensus) *consensus = st->pcons;
+    if (winner) *winner = st->pwin;
+    if (Tcw) *Tcw = st->ppose;
+    if (took) *took = st->took;
+    if (flags) *flags = st->pflags;
+    return TB_OK;
+}
+
 /* the checks both verification entry points share, and invLevelSigma2 */
 static int reloc_check(tb_kf_store* st, const char* who, int nlevels, float scale, const void* q_keys, const void* q_counts, int q_pitch,
                        const void* cand_slot, int ncand, float* inv_sigma2) {
@@ -1598,10 +1646,29 @@ int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, flo
                                    prm->nratio, prm->histo_len, prm->check_orientation, st->matches, st->pitch, mcounts, flags, st->best,
                                    st->ix1, st->ix2)))
         return rc;
-    if ((rc = tbk_reloc_rows(ctx, pairs, q_keys, q_counts, q_pitch, st->ix1, st->ix2, st->matches, mcounts, st->mp, st->valid, st->counts,
-                             st->pitch, inv_sigma2, nlevels, st->obs, st->ocounts, st->outlier, o.cand_rows)))
-        return rc;
-    if ((rc = tbk_pose_batch(ctx, pairs, K, st->seed, st->obs, st->ocounts, st->pitch, st->outlier, pose, ninl, nullptr, st->err))) return rc;
+    if (!st->pnp_on) {
+        if ((rc = tbk_reloc_rows(ctx, pairs, q_keys, q_counts, q_pitch, st->ix1, st->ix2, st->matches, mcounts, st->mp, st->valid, st->counts,
+                                 st->pitch, inv_sigma2, nlevels, st->obs, st->ocounts, st->outlier, o.cand_rows)))
+            return rc;
+        if ((rc = tbk_pose_batch(ctx, pairs, K, st->seed, st->obs, st->ocounts, st->pitch, st->outlier, pose, ninl, nullptr, st->err))) return rc;
+    } else {
+        /* rows -> P3P-RANSAC with the stored pose as the prior -> the consensus rows and the PnP pose into the pose stage, or every
+         * row and the stored seed where the consensus is short -> (expand) the optimised pose's inliers among all rows, once more */
+        TB_TRY(tbk_reloc_rows(ctx, pairs, q_keys, q_counts, q_pitch, st->ix1, st->ix2, st->matches, mcounts, st->mp, st->valid, st->counts,
+                              st->pitch, inv_sigma2, nlevels, st->rows0, st->cnt0, st->outlier, nullptr));
+        TB_TRY(tbk_pnp_batch(ctx, pairs, K, st->rows0, st->cnt0, st->pitch, st->pnp.hypotheses, st->pnp.chi2_max, st->pnp.seed, st->seed,
+                             st->ppose, st->pcons, st->pmask, st->pwin, st->pflags));
+        TB_TRY(tbk_pnp_gather(ctx, pairs, 0, K, st->pnp.chi2_max, st->pnp_min, st->rows0, st->cnt0, st->pitch, st->pmask, st->pcons, st->ppose,
+                              st->seed, st->took, st->obs, st->ocounts, st->outlier, st->seed2, o.cand_rows));
+        TB_TRY(tbk_pose_batch(ctx, pairs, K, st->seed2, st->obs, st->ocounts, st->pitch, st->outlier, pose, ninl, nullptr, st->err));
+        if (st->pnp_expand) {
+            TB_TRY(tbk_pnp_gather(ctx, pairs, 1, K, st->pnp.chi2_max, st->pnp_min, st->rows0, st->cnt0, st->pitch, nullptr, nullptr, pose,
+                                  nullptr, st->took, st->rows2, st->cnt2, st->outlier2, nullptr, o.cand_rows));
+            TB_TRY(tbk_pose_batch(ctx, pairs, K, pose, st->rows2, st->cnt2, st->pitch, st->outlier2, st->pose2, st->ninl2, nullptr, st->err));
+            TB_TRY(tbk_pnp_adopt(ctx, pairs, st->took, st->pitch, st->rows2, st->cnt2, st->outlier2, st->pose2, st->ninl2, st->obs, st->ocounts,
+                                 st->outlier, pose, ninl));
+        }
+    }
     if (mcounts != st->mcounts)   /* tb_kf_store_work_dev lends the last call's counts */
         TB_HIP(ctx, hipMemcpyAsync(st->mcounts, mcounts, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     if (!o.best_rank && !o.best_kf && !o.best_Tcw) return TB_OK;
@@ -2003,6 +2070,52 @@ int tb_linear_triangle(tb_ctx* ctx, const float* xy0, const float* xy1, int n, c
     TB_DOWNLOAD(ctx, tally, b + oTally, 24);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n == 0) tally[0] = 0;   /* the staged row of one entry is beyond the count */
+    return TB_OK;
+}
+
+int tb_pnp_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_obs* obs, const int32_t* counts, int obs_pitch,
+                            const tb_pnp_params* prm, const float* Tcw_prior, float* Tcw_out, int32_t* consensus, uint8_t* inlier,
+                            int32_t* winner, int32_t* flags) {
+    TB_ENTER(ctx);
+    if (!ctx || nproblems < 0 || obs_pitch < 1 || !K || !obs || !counts || !prm) return TB_EINVAL;
+    if (prm->hypotheses < 1 || prm->hypotheses > 1024 || !(prm->chi2_max >= 0.0) || !std::isfinite(prm->chi2_max) || !(K[0] > 0.0) ||
+        !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_pnp_ransac_batch_dev: hypotheses 1..1024, chi2_max finite and not negative, K finite, fx and fy positive");
+    if (nproblems > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_pnp_ransac_batch_dev: %d problems (at most 65535 per call)", nproblems);
+    return tbk_pnp_batch(ctx, nproblems, K, obs, counts, obs_pitch, prm->hypotheses, prm->chi2_max, prm->seed, Tcw_prior, Tcw_out,
+                         consensus, inlier, winner, flags);
+}
+
+int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, const tb_pnp_params* prm, const float* Tcw_prior,
+                  float Tcw_out[16], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags) {
+    TB_ENTER(ctx);
+    if (!ctx || n < 0 || !K || !prm || (n && !obs)) return TB_EINVAL;
+    const size_t pitch = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oObs = stage_piece(end, pitch * sizeof(tb_obs)), oPrior = stage_piece(end, 64), oT = stage_piece(end, 64),
+                 oInl = stage_piece(end, pitch), oRes = stage_piece(end, 16), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt = n;
+    TB_UPLOAD(ctx, b + oObs, obs, (size_t)n * sizeof(tb_obs));
+    TB_UPLOAD(ctx, b + oCnt, &cnt, 4);
+    if (Tcw_prior) TB_UPLOAD(ctx, b + oPrior, Tcw_prior, 64);
+    int32_t* res = (int32_t*)(b + oRes);   /* consensus, winner[2], flags */
+    if ((rc = tb_pnp_ransac_batch_dev(ctx, 1, K, (const tb_obs*)(b + oObs), (const int32_t*)(b + oCnt), (int)pitch, prm,
+                                      Tcw_prior ? (const float*)(b + oPrior) : nullptr, (float*)(b + oT), res, (uint8_t*)(b + oInl),
+                                      res + 1, res + 3)))
+        return rc;
+    int32_t h[4];
+    float T[16];
+    TB_DOWNLOAD(ctx, T, b + oT, 64);
+    TB_DOWNLOAD(ctx, h, res, 16);
+    if (inlier) TB_DOWNLOAD(ctx, inlier, b + oInl, (size_t)n);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (Tcw_out) memcpy(Tcw_out, T, 64);
+    if (consensus) *consensus = h[0];
+    if (winner) { winner[0] = h[1]; winner[1] = h[2]; }
+    if (flags) *flags = h[3];
     return TB_OK;
 }
 

@@ -279,6 +279,15 @@ struct tb_kf_store {
     double* err = nullptr;                                   /* [pairs][pitch][3] the pose kernel's residuals */
     float *seed = nullptr, *pose = nullptr;                  /* [pairs][16] */
     int32_t *mcounts = nullptr, *flags = nullptr, *ocounts = nullptr, *ninl = nullptr, *ckf = nullptr;   /* [pairs] */
+    /* PnP in front of the pose stage (tb_kf_store_pnp_enable): off unless enabled, its buffers allocated at enable */
+    bool pnp_on = false;
+    tb_pnp_params pnp = {};
+    int pnp_min = 0, pnp_expand = 0;
+    tb_obs *rows0 = nullptr, *rows2 = nullptr;               /* [pairs][pitch] the rows stage's rows; the expanded rows */
+    uint8_t *pmask = nullptr, *outlier2 = nullptr;           /* [pairs][pitch] */
+    uint8_t* took = nullptr;                                 /* [pairs] the pair took the PnP path */
+    float *ppose = nullptr, *seed2 = nullptr, *pose2 = nullptr;   /* [pairs][16] the PnP pose, the pose stage's seed, the second stage's pose */
+    int32_t *cnt0 = nullptr, *cnt2 = nullptr, *pcons = nullptr, *pwin = nullptr, *pflags = nullptr, *ninl2 = nullptr;   /* [pairs], pwin [pairs][2] */
 };
 
 /* kernel launchers (k_*.hip) */
@@ -492,6 +501,19 @@ int tbk_linear_triangle(tb_ctx* ctx, int npairs, const float* d_xy0, const float
                         const float* d_Tcw0, const float* d_Tcw1, const double K[4], const float* d_inv_sigma2_0,
                         const float* d_inv_sigma2_1, const uint8_t* d_skip, double cos_parallax_max, double chi2_max, float* d_points,
                         uint8_t* d_flags, int32_t* d_tally);
+/* P3P-RANSAC (k_pnp.hip): one workgroup per problem, no work buffer; every output nullable */
+int tbk_pnp_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_obs* d_obs, const int32_t* d_counts, int obs_pitch, int hypotheses,
+                  double chi2_max, unsigned long long seed, const float* d_Tcw_prior, float* d_Tcw_out, int32_t* d_consensus,
+                  uint8_t* d_inlier, int32_t* d_winner, int32_t* d_flags);
+/* PnP inside candidate verification (k_pnp.hip): the ordered gather of a pair's rows (stage 0: after the RANSAC, pose_a = the PnP
+ * pose, pose_b = the stored seed; stage 1: expand, pose_a = the optimised pose) and the adoption of the second pose stage */
+int tbk_pnp_gather(tb_ctx* ctx, int npairs, int stage, const double K[4], double chi2_max, int min_consensus, const tb_obs* d_rows0,
+                   const int32_t* d_cnt0, int pitch, const uint8_t* d_mask, const int32_t* d_consensus, const float* d_pose_a,
+                   const float* d_pose_b, uint8_t* d_took, tb_obs* d_rows, int32_t* d_cnt, uint8_t* d_outlier, float* d_seed,
+                   int32_t* d_rows_out);
+int tbk_pnp_adopt(tb_ctx* ctx, int npairs, const uint8_t* d_took, int pitch, const tb_obs* d_rows2, const int32_t* d_cnt2,
+                  const uint8_t* d_outlier2, const float* d_pose2, const int32_t* d_ninl2, tb_obs* d_rows, int32_t* d_cnt, uint8_t* d_outlier,
+                  float* d_pose, int32_t* d_ninl);
 /* mono mode of the optical-flow loop (k_vo.hip): the alive / skip masks after a tracking half, and the keyframe's merge from
  * one side of the ping-pong (src) into the other (dst) */
 #define TB_VO_MERGE_BITMAP_MAX 32768 /* bytes of LDS the merge's occupancy bitmap may take */

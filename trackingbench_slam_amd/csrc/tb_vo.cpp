@@ -552,6 +552,7 @@ static int vo_recover_stage(tb_vo* vo, int b) {
     const tb_vo_recover& r = vo->rec;
     const tb_vo_frame_out& o = vo->out[vo->oc];
     const tb_vo_kf_out& kf = vo->kf;
+    if (st->pnp_on) return tb_fail(ctx, TB_ESTATE, "recovery on a store with PnP verification (enabled on the lent store): not combined yet");
     const int S = vo->nseq, P = vo->P;
     TB_TRY(tb_bow_db_query_dev(db, o.bv_word, o.bv_val, o.bv_cnt, P, r.exclude_newest, r.topk, vo->rl_scores, vo->rl_top_slot, vo->rl_top_kf,
                                vo->rl_top_score, nullptr));
@@ -590,6 +591,7 @@ static int vo_loop_stage(tb_vo* vo, int b, int t) {
     const tb_vo_loop& l = vo->lp;
     const tb_vo_frame_out& o = vo->out[vo->oc];
     const int S = vo->nseq, P = vo->P, cap = st->cap, nn = cap + 1;
+    if (st->pnp_on) return tb_fail(ctx, TB_ESTATE, "loop correction on a store with PnP verification (enabled on the lent store): not combined yet");
     const int nlive = (int)std::min<long long>(st->nadded, cap), oldest = st->nadded >= cap ? (int)(st->nadded % cap) : 0;
     TB_TRY(tb_bow_db_query_dev(vo->db, o.bv_word, o.bv_val, o.bv_cnt, P, l.exclude_newest, l.topk, vo->rl_scores, vo->rl_top_slot,
                                vo->rl_top_kf, vo->rl_top_score, nullptr));
@@ -1124,11 +1126,24 @@ int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inlier
                                    top_slot, topk, &prm, out);
 }
 
+int tb_vo_reloc_pnp_enable(tb_vo* vo, const tb_pnp_params* prm, int min_consensus, int expand) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_pnp_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_pnp_enable after a step (frame %d)", vo->next - 1);
+    if (vo->rec_on || vo->lp_on)
+        return tb_fail(ctx, TB_ESTATE, "tb_vo_reloc_pnp_enable: recovery or loop correction is enabled; their adoption reads the verification's rows, "
+                                       "which PnP compacts: not combined yet");
+    return tb_kf_store_pnp_enable(vo->store, prm, min_consensus, expand);   /* TB_ESTATE when enabled already */
+}
+
 int tb_vo_recover_enable(tb_vo* vo, const tb_vo_recover* prm) {
     TB_ENTER((vo ? vo->ctx : nullptr));
     if (!vo) return TB_EINVAL;
     tb_ctx* ctx = vo->ctx;
     if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->store->pnp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: PnP verification is enabled; the two are not combined yet");
     if (vo->next > 0) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable after a step (frame %d)", vo->next - 1);
     if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: recovery is enabled already");
     if (vo->lp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_recover_enable: loop correction is enabled; the two are not combined yet");
@@ -1172,6 +1187,7 @@ int tb_vo_loop_enable(tb_vo* vo, const tb_vo_loop* prm) {
     if (!vo) return TB_EINVAL;
     tb_ctx* ctx = vo->ctx;
     if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->store->pnp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: PnP verification is enabled; the two are not combined yet");
     if (vo->next > 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable after a step, or on a ragged loop");
     if (vo->lp_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: loop correction is enabled already");
     if (vo->rec_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_enable: recovery is enabled; the two are not combined yet");

@@ -26,6 +26,9 @@ synth.Vocabulary (uploaded and owned by the loop), a callable `f(context) -> han
 `relocalize=M` (with keyframe_db=N) also keeps those keyframes themselves -- keys, descriptors, FeatureVector, map points, pose --
 in a device-resident store, and `relocalize()` verifies the best M candidates on the device: searchByBow against each stored
 keyframe, PoseOptimization seeded with its pose, the candidate with the most inliers. It is a query: the loop's state stays.
+`pnp=True` (or a dict, see PNP_DEFAULTS; with relocalize=M, not with recover= or loop_close=) puts a P3P-RANSAC in front of that
+pose stage, so that a candidate seen from metres away or through a mostly wrong match list is still verified: the consensus rows
+and the PnP pose go on to PoseOptimization, and `relocalize()` returns the PnP fields as well.
 `recover=True` (or a dict, see RECOVER_DEFAULTS; with relocalize=M) makes the loop use it: a sequence whose tracking step keeps
 fewer than lost_inliers inliers is relocalised inside the step, adopts the winner's pose, matches and map points, and tracks
 against the winning keyframe from then on. Which sequences do is decided on the device; the others are untouched.
@@ -134,9 +137,13 @@ def _tracker(kind, nlevels, params):
     return t
 
 
+# pnp=True. 256 hypotheses and chi2Mono are this library's defaults, 10 is ORB-SLAM's minInliers for its PnP solver
+PNP_DEFAULTS = dict(hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, expand=1)
+
+
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, loop_close=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, loop_close=None, pnp=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
         if mono:
@@ -175,6 +182,14 @@ class StereoVO:
                 raise TypeError("loop_close= takes no parameter %s" % ", ".join(sorted(unknown)))
             loop_close = dict(LOOP_DEFAULTS, **(loop_close if isinstance(loop_close, dict) else {}))
         self.loop_close = loop_close or None
+        if pnp and not relocalize:
+            raise TypeError("pnp= needs relocalize=M: it runs in front of the verification's pose stage")
+        if pnp:
+            unknown = set(pnp) - set(PNP_DEFAULTS) if isinstance(pnp, dict) else ()
+            if unknown:
+                raise TypeError("pnp= takes no parameter %s" % ", ".join(sorted(unknown)))
+            pnp = dict(PNP_DEFAULTS, **(pnp if isinstance(pnp, dict) else {}))
+        self.pnp = pnp or None
         if tracker == "bow" and vocab is None:
             raise ValueError("tracker 'bow' needs vocab=: a synth.Vocabulary, a callable f(context) -> handle, or a handle of context=")
         if tracker != "bow" and vocab is not None:
@@ -225,6 +240,8 @@ class StereoVO:
                         if relocalize:                # 0 = off: no call is made
                             self.ctx.check(self.vo.reloc_enable(relocalize))
                             self.store = self.vo.kf_store()
+                            if pnp:                   # None = off: no call is made. With recover= / loop_close= the library refuses
+                                self.ctx.check(self.vo.reloc_pnp_enable(**pnp))
                             if recover:               # None = off: no call is made
                                 self.ctx.check(self.vo.recover_enable(capi.VORecover(*[int(recover[k]) for k in (
                                     "lost_inliers", "topk", "exclude_newest", "min_inliers")])))
@@ -535,10 +552,17 @@ class StereoVO:
         through its map points, PoseOptimization seeded with its pose. Device tensors: query_keyframes' dict plus cand_kf /
         cand_matches / cand_rows / cand_inliers / cand_flags [S, topk] int32, cand_Tcw [S, topk, 4, 4], best_rank / best_kf [S]
         (-1: no candidate reached min_inliers -- ORB-SLAM's figure is 50; the reference has no such step) and best_Tcw [S, 4, 4]
-        (the identity when -1). A query: the loop's pose, points and keyframe stay. No host synchronisation."""
+        (the identity when -1). A query: the loop's pose, points and keyframe stay. No host synchronisation.
+        With pnp=: also pnp_rows [S, topk] int32 (the rows before the gather), pnp_consensus [S, topk], pnp_winner [S, topk, 2],
+        pnp_Tcw [S, topk, 4, 4], pnp_took [S, topk] uint8 (1: the pair went on with its consensus rows and the PnP pose) -- copies."""
         self._need_store()
         with torch.cuda.stream(self.stream):
             rc, out = self.vo.relocalize_dev(topk, exclude_newest, min_inliers, self.db.capacity, self.dev)
+            if rc == 0 and self.pnp:
+                st = self.store.pnp_state(self.dev, topk)
+                for k, name in (("row_counts", "pnp_rows"), ("consensus", "pnp_consensus"), ("winner", "pnp_winner"), ("Tcw", "pnp_Tcw"),
+                                ("took", "pnp_took")):
+                    out[name] = st[k].clone().reshape((self.S, int(topk)) + tuple(st[k].shape[1:]))
         self.ctx.check(rc)
         torch.cuda.current_stream(self.dev).wait_stream(self.stream)
         for t in out.values():
