@@ -16,7 +16,7 @@ SKIP_REASON = "oracle/_ref/ref_dbow2 is absent (built by build() only where the 
 
 
 class RefDbow2Error(AssertionError):
-    pass
+    returncode = None      # the driver's exit status where that is what failed
 
 
 def available():
@@ -46,8 +46,10 @@ def _run(case, mode, text, voc=None):
         except subprocess.TimeoutExpired:
             raise RefDbow2Error("case %s: ref_dbow2 %s did not finish in %d s" % (case, mode, TIMEOUT_S))
         if p.returncode != 0:
-            raise RefDbow2Error("case %s: ref_dbow2 %s exited with %d: %s" % (case, mode, p.returncode,
-                                                                            p.stderr.decode(errors="replace").strip()[-400:]))
+            e = RefDbow2Error("case %s: ref_dbow2 %s exited with %d: %s" % (case, mode, p.returncode,
+                                                                         p.stderr.decode(errors="replace").strip()[-400:]))
+            e.returncode = p.returncode
+            raise e
         lines = open(fout).read().splitlines()
     if not lines or lines[-1] != "end":
         raise RefDbow2Error("case %s: ref_dbow2 %s wrote an incomplete file" % (case, mode))
@@ -137,6 +139,56 @@ def create(docs, k, L, weighting, scoring, seeds, case="create"):
     out = {}
     _tree(rows, out)
     out["seeded"] = np.array([int(x) for x in [r for r in rows if r[0] == "seeded"][0][1:]], np.int64)   # calls, entries
+    return out
+
+
+_HAS_SCORE = None
+SCORE_SKIP_REASON = ("oracle/_ref/ref_dbow2 is absent, or answers the score command with its usage code: it was built from a driver "
+                     "older than the command and cannot be rebuilt here (build() rebuilds it only where the reference's DBoW2 "
+                     "sources exist; otherwise delete the stale oracle/_ref/)")
+
+
+def score_available():
+    """Is there a driver, and does it know the score command? build() leaves an existing oracle/_ref/ as it is where the reference
+    is absent, so the program there may be older than the command. It is asked once, with no vector and no pair. Exactly one answer
+    means "older than the command": exit status 2, the usage code a driver gives for a command it does not know. Anything else
+    that is not a clean answer -- a signal, a timeout, another exit status, an incomplete file -- is a failure of the driver and
+    is raised, here and on every later call, naming the case score/probe."""
+    global _HAS_SCORE
+    if _HAS_SCORE is None:
+        if not available():
+            _HAS_SCORE = False
+        else:
+            try:
+                rows = _run("score/probe", "score", "0\n" + "0\n" * 6)
+                if rows != []:
+                    raise RefDbow2Error("case score/probe: ref_dbow2 score answered the empty question with %d lines" % len(rows))
+                _HAS_SCORE = True
+            except RefDbow2Error as e:
+                _HAS_SCORE = False if e.returncode == 2 else e
+    if isinstance(_HAS_SCORE, RefDbow2Error):
+        raise _HAS_SCORE
+    return _HAS_SCORE
+
+
+def score(vectors, pairs, case="score"):
+    """The genuine TemplatedVocabulary::score(v1, v2), each code through a vocabulary constructed with it. vectors: a list of
+    (words, float64 values), entered with addWeight as given (no normalisation); pairs: per scoring code 0..5 a list of (i, j),
+    v1 = vectors[i], v2 = vectors[j]. -> bits0 .. bits5: per code a uint64 array, one result per pair in the order given."""
+    assert len(pairs) == 6
+    parts = ["%d" % len(vectors)]
+    for w, v in vectors:
+        v = np.ascontiguousarray(v, np.float64)
+        assert len(w) == len(v)
+        parts.append("%d %s\n%s" % (len(w), " ".join(str(int(x)) for x in w), " ".join(map(str, v.view(np.uint64).tolist()))))
+    for pl in pairs:
+        parts.append("%d %s" % (len(pl), " ".join("%d %d" % (i, j) for i, j in pl)))
+    rows = _run(case, "score", "\n".join(parts) + "\n")
+    out = {}
+    for code, pl in enumerate(pairs):
+        got = [r for r in rows if r[0] == "score" and int(r[1]) == code]
+        assert [(int(r[2]), int(r[3])) for r in got] == [(int(i), int(j)) for i, j in pl], "case %s: pairs of code %d" % (case, code)
+        out["bits%d" % code] = np.array([int(r[4]) for r in got], np.uint64)
     return out
 
 

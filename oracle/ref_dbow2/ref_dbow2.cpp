@@ -6,8 +6,12 @@
 //   ref_dbow2 transform VOC.txt IN OUT  loadFromTextFile, the per-feature transform and the two containers
 //   ref_dbow2 create    IN OUT          create(docs, k, L, weighting, scoring) with the seeds of every k-means node supplied
 //   ref_dbow2 seed      IN OUT          initiateClustersKMpp with rand() fed from a list
+//   ref_dbow2 score     IN OUT          TemplatedVocabulary::score(v1, v2) on BowVectors given entry by entry, under each of the six
+//                                       scoring codes, each through a vocabulary constructed with that code (createScoringObject)
 //
-// IN is a stream of whitespace-separated integers, OUT a text file of tagged lines (doubles as raw bit patterns).
+// IN is a stream of whitespace-separated integers, OUT a text file of tagged lines (doubles as raw bit patterns). score's IN:
+// the number of vectors, per vector `count, count words, count values as unsigned 64-bit patterns` (entered with addWeight as
+// given, never normalised here), then for each code 0..5 `npairs, npairs x (i j)`; its OUT: `score code i j bits` per pair.
 // Exit codes: 0 ok, 2 usage / malformed input, 3 rand() called with no draw left, 4 a k-means node with no supplied seeds.
 #include <cinttypes>
 #include <cstdint>
@@ -46,6 +50,15 @@ static long long rd() {
         std::exit(2);
     }
     return v;
+}
+
+static uint64_t rd_u64() {   // a double's bit pattern: the sign bit may be set, which %lld cannot take
+    unsigned long long v;
+    if (std::fscanf(g_in, "%llu", &v) != 1) {
+        std::fprintf(stderr, "ref_dbow2: input ended early\n");
+        std::exit(2);
+    }
+    return (uint64_t)v;
 }
 
 static cv::Mat rd_desc() {
@@ -230,6 +243,37 @@ static int mode_seed(FILE* o) {
     return 0;
 }
 
+static int mode_score(FILE* o) {
+    int nv = (int)rd();
+    if (nv < 0) return 2;
+    std::vector<DBoW2::BowVector> vs(nv);
+    for (int v = 0; v < nv; ++v) {
+        int n = (int)rd();
+        if (n < 0) return 2;
+        std::vector<long long> words(n);
+        for (int i = 0; i < n; ++i) {
+            words[i] = rd();
+            if (words[i] < 0 || words[i] > 0xFFFFFFFFLL) return 2;
+        }
+        for (int i = 0; i < n; ++i) {
+            uint64_t u = rd_u64();
+            double d;
+            std::memcpy(&d, &u, 8);
+            vs[v].addWeight((DBoW2::WordId)words[i], d);
+        }
+    }
+    for (int code = 0; code < 6; ++code) {
+        Voc voc(10, 5, DBoW2::TF_IDF, (DBoW2::ScoringType)code);   // the scoring object is the one createScoringObject chooses
+        int np = (int)rd();
+        for (int p = 0; p < np; ++p) {
+            int i = (int)rd(), j = (int)rd();
+            if (i < 0 || i >= nv || j < 0 || j >= nv) return 2;
+            std::fprintf(o, "score %d %d %d %" PRIu64 "\n", code, i, j, bits(voc.score(vs[i], vs[j])));
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 4) return 2;
     std::string mode = argv[1];
@@ -243,6 +287,7 @@ int main(int argc, char** argv) {
     else if (tr) rc = mode_transform(argv[2], o);
     else if (mode == "create") rc = mode_create(o);
     else if (mode == "seed") rc = mode_seed(o);
+    else if (mode == "score") rc = mode_score(o);
     if (rc == 0) std::fprintf(o, "end\n");
     std::fclose(o);
     return rc;

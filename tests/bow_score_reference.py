@@ -7,7 +7,14 @@ A vector is a pair (words ascending int array, values float64 array): the std::m
 cursors, one term per common word added into one accumulator in word order, std::map::lower_bound to skip, a closing formula.
 Python floats are IEEE doubles and every operator is one rounding, math.sqrt is correctly rounded, so codes 0, 1, 2, 4, 5 are
 exact restatements. KL's math.log is the C library's, which a device library's log need not equal bit for bit; kl_bound gives
-the derived tolerance. It is not yet compared with genuine DBoW2: the committed driver under oracle/ has no score command.
+the derived tolerance.
+
+Pinned to genuine DBoW2: tests/test_ref_dbow2_score.py holds score() and the host form tb_bow_score equal to the reference's own
+TemplatedVocabulary::score (oracle/ref_dbow2.py's score command, recorded in tests/golden/ref_dbow2_score_v1.npz) on the cases of
+tests/ref_dbow2_score_cases.py: bit for bit under codes 0, 1, 2, 4, 5 and, on the machine that recorded the fixture, under KL too
+(both sides call the same C library's log); tests/test_gpu_ref_dbow2_score.py holds the device to the same recorded results,
+KL within kl_bound. Not pinned, because the vendored DBoW2 has no database class: the Ring's rule (which slots are ranked, better
+first, ties to the lower kf_id) is the project's own.
 
 Scoring codes (include/tb_types.h): 0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 3 KL, 4 BHATTACHARYYA, 5 DOT_PRODUCT."""
 import bisect
@@ -31,9 +38,22 @@ def _log(x):
     return math.log(x)
 
 
-def score_detail(scoring, a_words, a_values, b_words, b_values):
+# Every branch of the six scoring functions and both sides of every guard, as (scoring, name): what score_detail's `branches`
+# argument can count. common / v1 behind / v2 behind are the three arms of the walk; "* ends first" how the walk's loop ended.
+_WALK = ("common", "v1 behind", "v2 behind", "v1 ends first", "v2 ends first", "both end")
+BRANCHES = {(s, b) for s in range(6) for b in _WALK}
+BRANCHES |= {(L2_NORM, "sum = 1"), (L2_NORM, "sum > 1"), (L2_NORM, "sum < 1"),
+             (CHI_SQUARE, "vi + wi != 0"), (CHI_SQUARE, "vi + wi == 0"),
+             (KL, "common added"), (KL, "common vi == 0"), (KL, "common wi == 0"),
+             (KL, ":204 vi != 0"), (KL, ":204 vi == 0"), (KL, "tail added"), (KL, "tail zero"), (KL, "no tail"),
+             (BHATTACHARYYA, "product >= 0"), (BHATTACHARYYA, "product < 0")}
+
+
+def score_detail(scoring, a_words, a_values, b_words, b_values, branches=None):
     """-> (score, A, n, M). v1 = a, v2 = b. For KL: A = sum of |vi| * (|log argument's log| + |LOG_EPS|) over the added terms,
-    n = the number of added terms, M = max |partial sum| (kl_bound's inputs); 0 for the other scorings."""
+    n = the number of added terms, M = max |partial sum| (kl_bound's inputs); 0 for the other scorings. branches: an optional
+    set that receives the members of BRANCHES this call took (test-side coverage; no result depends on it)."""
+    took = (lambda name: None) if branches is None else (lambda name: branches.add((scoring, name)))
     aw = [int(w) for w in a_words]; av = [float(v) for v in a_values]
     bw = [int(w) for w in b_words]; bv = [float(v) for v in b_values]
     assert len(aw) == len(av) and len(bw) == len(bv)
@@ -54,36 +74,48 @@ def score_detail(scoring, a_words, a_values, b_words, b_values):
     while i < na and j < nb:
         vi, wi = av[i], bv[j]
         if aw[i] == bw[j]:
+            took("common")
             if scoring == L1_NORM:
                 score += abs(vi - wi) - abs(vi) - abs(wi)              # :41
             elif scoring in (L2_NORM, DOT_PRODUCT):
                 score += vi * wi                                       # :91, :290
             elif scoring == CHI_SQUARE:
+                took("vi + wi != 0" if vi + wi != 0.0 else "vi + wi == 0")
                 if vi + wi != 0.0:
                     score += vi * wi / (vi + wi)                       # :148
             elif scoring == KL:
+                took("common added" if vi != 0 and wi != 0 else "common vi == 0" if not vi != 0 else "common wi == 0")
                 if vi != 0 and wi != 0:
                     kl_add(vi, vi / wi, False)                         # :195
             else:
                 p = vi * wi
+                took("product >= 0" if p >= 0 else "product < 0")
                 score += math.sqrt(p) if p >= 0 else math.nan          # :245
             i += 1; j += 1
         elif aw[i] < bw[j]:
+            took("v1 behind")
             if scoring == KL:
+                took(":204 vi != 0" if vi != 0 else ":204 vi == 0")
                 kl_add(vi, vi, True)                                   # :204, then ++v1_it
                 i += 1
             else:
                 i = bisect.bisect_left(aw, bw[j], i)                   # v1.lower_bound(v2_it->first)
         else:
+            took("v2 behind")
             j = bisect.bisect_left(bw, aw[i], j)                       # v2.lower_bound(v1_it->first)
+    took("both end" if i >= na and j >= nb else "v1 ends first" if i >= na else "v2 ends first")
     if scoring == L1_NORM:
         score = -score / 2.0                                           # :65
     elif scoring == L2_NORM:
+        took("sum = 1" if score == 1 else "sum > 1" if score > 1 else "sum < 1")
         score = 1.0 if score >= 1 else 1.0 - math.sqrt(1.0 - score)    # :114-117
     elif scoring == CHI_SQUARE:
         score = 2. * score                                             # :167
     elif scoring == KL:
+        if i >= na:
+            took("no tail")
         while i < na:                                                  # :216-218
+            took("tail added" if av[i] != 0 else "tail zero")
             if av[i] != 0:
                 kl_add(av[i], av[i], True)
             i += 1

@@ -219,6 +219,8 @@ def all_cases():
         for w, s in WS_ALL:
             c[("transform", transform_name(t, w, s))] = (w, s) in WS_RECORDED
         c[("transform", transform_name(t, 0, 0, "b"))] = True
+        for w, s in WS_RECORDED[1:]:      # the second feature set under the other recorded pairs: the score cases' vectors (live only)
+            c[("transform", transform_name(t, w, s, "b"))] = False
     for n in CREATE:
         c[("create", n)] = n not in CREATE_LIVE_ONLY
     for n in SEED:

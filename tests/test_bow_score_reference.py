@@ -4,36 +4,16 @@ through oracle.bow_transform / oracle.bow_containers (both pinned to the referen
 hand-built edge cases, and the recorded genuine-DBoW2 BowVectors of tests/golden/ref_dbow2_v1.npz. Codes 0, 1, 2, 4, 5 compare as
 64-bit patterns, KL within the derived bound (bow_score_reference.kl_bound). The same vectors feed tests/test_gpu_bow_score.py."""
 import ctypes as C
-import functools
 import math
 
 import numpy as np
 import pytest
 
 import bow_score_reference as br
+from bow_score_inputs import HAND, NFRAMES, SHAPES, _v, vectors
 import oracle
 import ref_dbow2_cases as cases
 from trackingbench_slam_amd import capi, synth
-
-SHAPES = [(4, 3, 300), (10, 3, 500), (10, 5, 2000)]      # (k, L, keys per frame)
-NFRAMES = 4
-
-
-@functools.lru_cache(maxsize=None)
-def _transformed(k, L, n):
-    voc = synth.vocabulary(1, k, L, stop_frac=0.05)
-    return [oracle.bow_transform(voc, synth.descriptors_near_words(10 + f, voc, n), 4) for f in range(NFRAMES)]
-
-
-@functools.lru_cache(maxsize=None)
-def vectors(k, L, n, scoring):
-    """the BowVectors (words, values) of NFRAMES frames under TF_IDF and the given scoring's normalisation"""
-    out = []
-    for wid, wt, nid in _transformed(k, L, n):
-        bv, _ = oracle.bow_containers(wid, wt, nid, weighting=0, scoring=scoring)
-        out.append((np.array(list(bv), np.int32), np.array(list(bv.values()), np.float64)))
-    return out
-
 
 def check(scoring, a, b, what):
     exp = br.score_detail(scoring, a[0], a[1], b[0], b[1])
@@ -65,22 +45,6 @@ def test_kl_is_not_symmetric_and_lower_is_more_similar():
     ab = capi.bow_score(br.KL, *vs[0], *vs[1]); ba = capi.bow_score(br.KL, *vs[1], *vs[0])
     assert ab != ba and ab > 0 and ba > 0
     assert capi.bow_score(br.KL, *vs[0], *vs[0]) < ab
-
-
-def _v(words, values):
-    return np.array(words, np.int32), np.array(values, np.float64)
-
-
-HAND = {
-    "disjoint": (_v([1, 3, 5], [0.5, 0.25, 0.25]), _v([0, 2, 4, 6], [0.25, 0.25, 0.25, 0.25])),
-    "a empty": (_v([], []), _v([0, 2], [0.5, 0.5])),
-    "b empty": (_v([0, 2], [0.5, 0.5]), _v([], [])),
-    "both empty": (_v([], []), _v([], [])),
-    "chi zero sum": (_v([1, 2, 7], [0.375, 0.5, 0.125]), _v([1, 2, 7], [0.25, -0.5, 0.75])),
-    "l2 sum above 1": (_v([0, 1, 2], [0.75, 0.75, 0.5]), _v([0, 1, 2], [0.75, 0.75, 0.5])),
-    "kl tail": (_v([1, 4, 9, 12, 15], [0.125, 0.25, 0.125, 0.25, 0.25]), _v([0, 4, 8, 9], [0.25, 0.25, 0.25, 0.25])),
-    "one word": (_v([3], [1.0]), _v([3], [1.0])),
-}
 
 
 @pytest.mark.parametrize("name", sorted(HAND))

@@ -11,7 +11,7 @@ import torch
 
 import bow_score_reference as br
 import oracle
-from test_bow_score_reference import HAND, vectors
+from bow_score_inputs import HAND, pack, random_vector as _random_vector, vectors
 from trackingbench_slam_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -24,19 +24,6 @@ def ctx():
     c = capi.Context(0)
     yield c
     c.close()
-
-
-def pack(vs, pitch, seed=5):
-    """[n][pitch] lists with garbage beyond the counts (what lies there is not read)"""
-    rng = np.random.default_rng(seed)
-    n = len(vs)
-    w = rng.integers(0, 1000, (n, pitch)).astype(np.int32)
-    v = rng.uniform(0.1, 3.0, (n, pitch))
-    for f, (ws, xs) in enumerate(vs):
-        assert len(ws) <= pitch
-        w[f, :len(ws)] = ws
-        v[f, :len(ws)] = xs
-    return [torch.from_numpy(x).cuda() for x in (w, v, np.array([len(x[0]) for x in vs], np.int32))]
 
 
 def dev_scores(ctx, scoring, A, B, pa, pb, mode):
@@ -74,12 +61,6 @@ def test_frames_in_both_modes(ctx, shape, scoring):
         j = (i + 1) % len(vs)
         alone = dev_scores(ctx, scoring, [vs[i]], [vs[j]], pitch, pitch, capi.TB_SCORE_PAIRWISE)
         assert pw[i].view(np.uint64) == ap[i, j].view(np.uint64) == alone[0].view(np.uint64), (shape, scoring, i)
-
-
-def _random_vector(rng, n, nwords):
-    w = np.sort(rng.choice(nwords, n, replace=False)).astype(np.int32)
-    v = rng.uniform(1e-3, 1.0, n)
-    return w, v / v.sum()
 
 
 @pytest.mark.parametrize("scoring", range(6))
