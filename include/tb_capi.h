@@ -617,6 +617,74 @@ int tb_pnp_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const
                             int32_t* winner, int32_t* flags);
 int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, const tb_pnp_params* params, const float* Tcw_prior,
                   float Tcw_out[16], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags);
+/* A relative pose and first points from 2D-2D rows alone: 8-point hypotheses in a RANSAC, a least-squares refit, the four
+ * decompositions of E told apart by triangulation; batched and device-resident. The reference has no such step (its
+ * LinearTriangle is handed poses); this is ORB-SLAM's Initializer on its fundamental-matrix branch (DESIGN.md 9m has the
+ * derivation and the deviations; tests/two_view_reference.py is the definition, statement for statement, and the kernel
+ * matches it bit for bit). Inputs as tb_linear_triangle_batch_dev's: problem p reads xy0 / xy1 [nproblems][pitch][2] float
+ * pixels of view 0 / view 1, counts [nproblems] (nullable = pitch each; clamped to [0, pitch]), skip [nproblems][pitch] bytes
+ * (nullable), inv_sigma2_0 / _1 [nproblems][pitch] (nullable = 1), K = fx, fy, cx, cy (host), Tcw0 [nproblems][16] (nullable =
+ * the identity). float64 with + - * / sqrt and comparisons only, fixed loop counts.
+ *   rows       the candidates are the rows below the count whose skip byte is 0, in index order, n of them; n < 8 is void
+ *   sampling   counter based: draw k of hypothesis h is mix(seed + (16 h + k + 1) * 0x9E3779B97F4A7C15) (splitmix64's output
+ *              function); its high 32 bits times n, shifted right by 32, is a candidate. Draws are taken until eight distinct
+ *              candidates are found or 16 are used up; a hypothesis that runs out is void. The sample depends on (seed, h, n)
+ *              only, never on p: a problem gives the same bits alone and inside any batch
+ *   solver     x = (u - cx) / fx, y = (v - cy) / fy; the 8 x 9 epipolar system in tb_find_fundamental_ransac's row layout
+ *              (x1' E x0 = 0, E row-major), Gauss-Jordan with partial pivoting (the unused row with the largest entry, the
+ *              lowest row on a tie) and the relative pivot test 1e-12 * scale. Exactly one free column gives the null vector,
+ *              which is E; any other count, or a non-finite entry, makes the hypothesis void, never a NaN
+ *   score      F = K^-T E K^-1; a row is in the consensus iff both squared point-to-epipolar-line distances in pixels, each times
+ *              its view's inv_sigma2, are <= chi2_epi (a NaN is not). The winner has the most rows, ties to the lower
+ *              hypothesis. Counts are integer sums; there is no floating-point atomic anywhere
+ *   refit      (refit != 0) the 9 x 9 normal matrix of the consensus rows, summed in a fixed order (candidate c in slot c mod 256,
+ *              a slot in index order, the slots by the butterfly t ^ 1, 2, ..., 128); 5 cyclic Jacobi sweeps in the pair order
+ *              (0,1) (0,2) ... (7,8) with the triangulation's rotation; the eigenvector at the smallest diagonal entry is the new
+ *              E, and the consensus is counted once more against it. No Hartley normalisation (it changed nothing measurable)
+ *   decompose  6 Jacobi sweeps on E' E give V and the squared singular values; u_i = E v_i / s_i for the two largest,
+ *              u3 = u1 x u2, v3 = v1 x v2 (both determinants +1). Candidates 0..3: (U W V', +u3), (U W V', -u3), (U W' V', +u3),
+ *              (U W' V', -u3)
+ *   cheirality every candidate triangulates every consensus row with tb_linear_triangle_batch_dev's statements and the gates
+ *              of `tri`, view 0 at the identity, view 1 at [R | t], |t| = 1, in float64. good[c] counts the flags 1 and 4, tri[c]
+ *              the flags 1
+ *   decision   c* = the largest good, ties to the lower candidate. status: 0 ok; 1 void (n < 8, or no hypothesis with a solution);
+ *              2 good[c*] < min_points or (double) good[c*] < min_good_ratio * (double) consensus; 3 another candidate has
+ *              (double) good[c] > ambiguity_ratio * (double) good[c*]; 4 tri[c*] < min_points. The first failing test decides.
+ *              min_good_ratio 0.9, ambiguity_ratio 0.7 and min_points 50 are ORB-SLAM's ReconstructF figures
+ * Out (device, each nullable): Tcw1 [nproblems][16] float = [R | baseline t] composed onto Tcw0 (the float32 rounding of the
+ * float64 product; status != 0: Tcw0 as given, or the identity); points [nproblems][pitch][3] float, world frame, WRITTEN ONLY
+ * WHERE point_flags IS 1 AND status IS 0 (the float32 point of view 0's frame times baseline, taken through Tcw0^-1; a failed
+ * problem leaves points untouched); point_flags [nproblems][pitch] bytes (the triangulation's codes under c*, 0 for a row that is
+ * not in the consensus); inlier [nproblems][pitch] bytes (the consensus mask); consensus [nproblems]; winner [nproblems][2]
+ * (hypothesis, candidate; (-1, -1) when void); good / tri [nproblems][4]; status [nproblems]. A void problem reports zeros.
+ * Asynchronous on the context's stream, no host synchronisation, no host <-> device copy, no work buffer: one launch of one
+ * 256-thread workgroup per problem whose state is registers and LDS, the candidate rows staged once in dynamic LDS (29 bytes per row
+ * of the pitch). TB_EUNSUPPORTED: more than
+ * 65535 problems, pitch above TB_TWO_VIEW_MAX_PITCH. TB_EINVAL: null xy0 / xy1 / K / params, pitch < 1, hypotheses outside
+ * 1..1024, chi2_epi or tri.chi2_max negative or not finite, tri.cos_parallax_max not finite, min_good_ratio or ambiguity_ratio
+ * outside (0, 1], min_points < 0, baseline not positive and finite, fx or fy not positive, K not finite.
+ * tb_two_view: the host form, one problem of n rows on the batched entry (host pointers; points is zero where nothing was
+ * written; good / tri [4], winner [2]). */
+#define TB_TWO_VIEW_MAX_PITCH 4096
+typedef struct tb_two_view_params {
+    int hypotheses;             /* 1..1024; 256 */
+    double chi2_epi;            /* 3.841 */
+    int refit;                  /* 1 */
+    tb_triangulate_params tri;  /* 0.9998, 5.991 */
+    double min_good_ratio;      /* 0.9 */
+    double ambiguity_ratio;     /* 0.7 */
+    int min_points;             /* 50 */
+    double baseline;            /* 1.0: the length given to the translation */
+    uint64_t seed;
+} tb_two_view_params;
+int tb_two_view_batch_dev(tb_ctx* ctx, int nproblems, const float* xy0, const float* xy1, const int32_t* counts, int pitch,
+                          const uint8_t* skip, const float* inv_sigma2_0, const float* inv_sigma2_1, const double K[4],
+                          const float* Tcw0, const tb_two_view_params* params, float* Tcw1, float* points, uint8_t* point_flags,
+                          uint8_t* inlier, int32_t* consensus, int32_t* winner, int32_t* good, int32_t* tri, int32_t* status);
+int tb_two_view(tb_ctx* ctx, const float* xy0, const float* xy1, int n, const uint8_t* skip, const float* inv_sigma2_0,
+                const float* inv_sigma2_1, const double K[4], const float Tcw0[16], const tb_two_view_params* params, float Tcw1[16],
+                float* points, uint8_t* point_flags, uint8_t* inlier, int* consensus, int32_t winner[2], int32_t good[4],
+                int32_t tri[4], int* status);
 /* SURVEY 8(f) row 2, first part -- the optical-flow matcher.
  * tb_optical_flow_pyr_lk replaces the call cv::calcOpticalFlowPyrLK(prev, next, prev_pts, next_pts, status, err,
  * Size(win, win), max_level) of matcher.cpp:744 (default criteria: 30 iterations / eps 0.01, flags 0,
@@ -1155,6 +1223,34 @@ typedef struct tb_vo_mono {
 int tb_vo_mono_enable(tb_vo* vo, const tb_vo_mono* prm);
 int tb_vo_mono_state_dev(tb_vo* vo, const float** kf_keys_xy, const float** kf_Tcw, const uint8_t** alive, const float** tri_points,
                          const uint8_t** tri_flags, const int32_t** tri_tally, const int32_t** survivors, const int32_t** added);
+/* The mono loop starting without a right image (off unless enabled: a mono loop that does not call it launches exactly what it
+ * launched before): tb_two_view_batch_dev gives the first pose and points, `two_view.baseline` sets the scale. The composition is
+ * restated on the CPU in tests/vo_mono_init_reference.py. Per sequence, initialised[s] starts at 0:
+ *   frame 0        `right` is not read and may be NULL at every step. ORB only: keys = the ORB list, no key has a map point, Tcw =
+ *                  the reset pose; kf_keys = keys, kf_Tcw = Tcw, alive = 1
+ *   tracking       LK and alive &= status as in the mono mode. While initialised[s] == 0 no key has a map point, the pose stage
+ *                  gets no rows and holds the pose: Tcw stays the reset pose bit for bit. An initialised sequence is the mono mode's
+ *   keyframe t > 0 initialised[s] == 0: the sequence takes no part in the triangulation (its tri_flags are 0). The two-view operator
+ *                  runs on (kf_keys, keys, the key count, skip = !alive, Tcw0 = kf_Tcw); attempts[s] += 1. Status 0 with at least
+ *                  min_tracks alive keys: Tcw = Tcw1, key i takes points[i] where point_flags[i] == 1 (through tri_points /
+ *                  tri_flags, which the merge reads), initialised[s] = 1, init_frame[s] = t. Otherwise nothing is adopted. Either
+ *                  way the mono mode's merge follows -- with no survivor it yields a fresh ORB list, the re-seed -- and kf_keys,
+ *                  kf_Tcw, alive are set as in the mono mode. initialised[s] == 1: the mono mode's keyframe, the same bytes
+ * Which sequences initialise is decided on the device (k_vo_init_adopt); a step makes no host round trip.
+ * tb_vo_mono_init_enable: after tb_vo_mono_enable and before the first tb_vo_reset_dev. TB_ESTATE: the mono mode is not enabled,
+ * after a reset, or enabled already; TB_EINVAL: null parameters, min_tracks < 0, or two-view parameters tb_two_view_batch_dev
+ * refuses; TB_EUNSUPPORTED: a key pitch above TB_TWO_VIEW_MAX_PITCH. tb_vo_reset_dev clears the state.
+ * tb_vo_mono_init_state_dev: device views, each nullable (TB_ESTATE when not enabled): initialised [nseq] bytes, init_frame [nseq]
+ * (-1: not yet), attempts [nseq], and the sequence's last attempt: status, consensus [nseq], winner [nseq][2], good / tri
+ * [nseq][4], Tcw1 [nseq][16] (zero before the first). */
+typedef struct tb_vo_mono_init {
+    tb_two_view_params two_view;
+    int min_tracks;              /* 100: fewer alive keys at the keyframe and nothing is adopted */
+} tb_vo_mono_init;
+int tb_vo_mono_init_enable(tb_vo* vo, const tb_vo_mono_init* prm);
+int tb_vo_mono_init_state_dev(tb_vo* vo, const uint8_t** initialised, const int32_t** init_frame, const int32_t** attempts,
+                              const int32_t** status, const int32_t** consensus, const int32_t** winner, const int32_t** good,
+                              const int32_t** tri, const float** Tcw1);
 /* Device views of the descriptors the projection trackers carry with the map points (TB_ESTATE for any other tracker):
  * mp_desc [nseq][key_pitch][32] next to tb_vo_state_dev's map_points, kf_mp_desc next to kf_map_points; entry j is read only
  * where its map point is valid. */

@@ -1,0 +1,98 @@
+"""Constructed 2D-2D problems for the two-view tests (tests/test_two_view_reference.py, tests/test_gpu_two_view.py): KITTI
+intrinsics at 1241 x 376, points on a ground plane 1.65 m below the camera and on two walls 7 m to either side, 4-60 m ahead,
+seen from the identity and from a second camera; Gaussian pixel noise in both views and planted outliers (view 1's pixel replaced
+by a uniformly random one). Every draw comes from synth.Stream(seed), so a seed names a problem."""
+import numpy as np
+
+from trackingbench_slam_amd.synth import Stream
+
+K = (718.856, 718.856, 607.1928, 185.2157)
+W, H = 1241, 376
+ROWS = 520
+
+
+def rot_y(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+
+
+def rot_x(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+
+
+def motion(kind, d=0.0):
+    """(R, t) of view 1, X1 = R X0 + t: "forward" d metres along the optical axis with a slight yaw and pitch, "sideways" d metres
+    to the right, "rotation" by d radians about the vertical axis on the spot, "none" """
+    if kind == "forward":
+        R = rot_y(0.01) @ rot_x(-0.004)
+        return R, -R @ np.array([0.03 * d, -0.01 * d, d])
+    if kind == "sideways":
+        return np.eye(3), -np.array([d, 0.0, 0.0])
+    if kind == "rotation":
+        return rot_y(d), np.zeros(3)
+    return np.eye(3), np.zeros(3)
+
+
+def _normal(st, shape):
+    n = int(np.prod(shape))
+    u1 = 1.0 - st.uniform(n)
+    u2 = st.uniform(n)
+    return (np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)).reshape(shape)
+
+
+def project(R, t, X):
+    pc = X @ R.T + t
+    return np.stack([pc[:, 0] / pc[:, 2] * K[0] + K[2], pc[:, 1] / pc[:, 2] * K[1] + K[3]], -1), pc[:, 2]
+
+
+def scene(st, m):
+    """m points: half on the ground, a quarter on each wall"""
+    z = st.uniform(m, 4.0, 60.0)
+    which = st.randint(m, 0, 4)
+    xg = st.uniform(m, -1.0, 1.0)
+    yw = st.uniform(m, -3.0, 1.65)
+    x = np.where(which < 2, xg * np.minimum(6.5, 0.8 * z), np.where(which == 2, -7.0, 7.0))
+    y = np.where(which < 2, 1.65, yw)
+    return np.stack([x, y, z], -1)
+
+
+def problem(seed, n=ROWS, kind="forward", d=2.5, noise=0.1, outliers=0.0, pitch=None):
+    """(xy0, xy1 float32 [pitch][2], good bool [pitch], R, t): n rows visible in both views, round(n * outliers) of them, in
+    random places, planted outliers; rows beyond n are zero"""
+    st = Stream(seed)
+    R, t = motion(kind, d)
+    X = scene(st, 6 * n)
+    p0, z0 = project(np.eye(3), np.zeros(3), X)
+    p1, z1 = project(R, t, X)
+    vis = (z0 > 1.0) & (z1 > 1.0)
+    for p in (p0, p1):
+        vis &= (p[:, 0] >= 8) & (p[:, 0] < W - 8) & (p[:, 1] >= 8) & (p[:, 1] < H - 8)
+    keep = np.nonzero(vis)[0][:n]
+    assert len(keep) == n, "the scene gives %d visible points" % len(keep)
+    p0 = p0[keep] + noise * _normal(st, (n, 2))
+    p1 = p1[keep] + noise * _normal(st, (n, 2))
+    nbad = int(round(n * outliers))
+    good = np.ones(n, bool)
+    good[np.argsort(st.uniform(n), kind="stable")[:nbad]] = False
+    bad = np.stack([st.uniform(n, 0, W), st.uniform(n, 0, H)], -1)
+    p1 = np.where(good[:, None], p1, bad)
+    pitch = n if pitch is None else pitch
+    xy0 = np.zeros((pitch, 2), np.float32)
+    xy1 = np.zeros((pitch, 2), np.float32)
+    g = np.zeros(pitch, bool)
+    xy0[:n], xy1[:n], g[:n] = p0, p1, good
+    return xy0, xy1, g, R, t
+
+
+def pose_error(R, t, Rt, tt):
+    """(Frobenius norm of R - Rt, cosine between t and tt)"""
+    return float(np.linalg.norm(np.asarray(R) - Rt)), float(np.dot(t, tt) / (np.linalg.norm(t) * np.linalg.norm(tt)))
+
+
+def tcw0():
+    """a view-0 pose away from the identity, rounded to float32"""
+    T = np.eye(4)
+    T[:3, :3] = rot_y(0.3) @ rot_x(-0.1)
+    T[:3, 3] = (1.5, -0.4, 2.0)
+    return T.astype(np.float32)

@@ -59,6 +59,7 @@ EXPORTS = [
     "tb_linear_triangle", "tb_linear_triangle_batch_dev", "tb_vo_mono_enable", "tb_vo_mono_state_dev",
     "tb_pose_graph", "tb_pose_graph_batch_dev", "tb_pose_graph_plan", "tb_vo_loop_enable", "tb_vo_loop_state_dev",
     "tb_pnp_ransac", "tb_pnp_ransac_batch_dev", "tb_kf_store_pnp_enable", "tb_kf_store_pnp_state_dev", "tb_vo_reloc_pnp_enable",
+    "tb_two_view", "tb_two_view_batch_dev", "tb_vo_mono_init_enable", "tb_vo_mono_init_state_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -296,6 +297,28 @@ class PnpParams(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("chi2_max", C.c_double), ("seed", C.c_uint64)]
 
 
+class TwoViewParams(C.Structure):
+    """tb_two_view_params of include/tb_capi.h"""
+    _fields_ = [("hypotheses", C.c_int), ("chi2_epi", C.c_double), ("refit", C.c_int), ("tri", TriangulateParams),
+                ("min_good_ratio", C.c_double), ("ambiguity_ratio", C.c_double), ("min_points", C.c_int), ("baseline", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+TB_TWO_VIEW_MAX_PITCH = 4096
+
+
+class VOMonoInit(C.Structure):
+    """tb_vo_mono_init of include/tb_capi.h"""
+    _fields_ = [("two_view", TwoViewParams), ("min_tracks", C.c_int)]
+
+
+def two_view_params(hypotheses=256, chi2_epi=3.841, refit=1, cos_parallax_max=0.9998, chi2_max=5.991, min_good_ratio=0.9,
+                    ambiguity_ratio=0.7, min_points=50, baseline=1.0, seed=0):
+    """a TwoViewParams with the defaults of include/tb_capi.h"""
+    return TwoViewParams(int(hypotheses), float(chi2_epi), int(refit), TriangulateParams(float(cos_parallax_max), float(chi2_max)),
+                         float(min_good_ratio), float(ambiguity_ratio), int(min_points), float(baseline), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
 class VO:
     """tb_vo: the device-resident stereo VO loop (test_kitti) for nseq sequences on one context. Device pointers in and out.
     tracker None = tb_vo_create (optical flow) unless use_ex; otherwise tb_vo_create_ex with the VOTracker (or NULL).
@@ -480,6 +503,18 @@ class VO:
         """tb_vo_mono_enable with a VOMono (None: a null pointer): returns the status code (0 or a negative TB_E* code), so the
         state and argument checks can be tested."""
         return lib().tb_vo_mono_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def mono_init_enable(self, prm):
+        """tb_vo_mono_init_enable with a VOMonoInit (None: a null pointer): returns the status code"""
+        return lib().tb_vo_mono_init_enable(self._h, C.byref(prm) if prm is not None else None)
+
+    def mono_init_state_dev(self):
+        """tb_vo_mono_init_state_dev: dict of device pointers (initialised, init_frame, attempts, status, consensus, winner, good,
+        tri, Tcw1); TB_ESTATE when not enabled."""
+        names = ("initialised", "init_frame", "attempts", "status", "consensus", "winner", "good", "tri", "Tcw1")
+        ptrs = [C.c_void_p() for _ in names]
+        self.ctx.check(lib().tb_vo_mono_init_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        return {k: q.value for k, q in zip(names, ptrs)}
 
     def mono_state_dev(self):
         """tb_vo_mono_state_dev: dict of device pointers (kf_keys_xy, kf_Tcw, alive, tri_points, tri_flags, tri_tally, survivors,
@@ -1025,6 +1060,42 @@ class Context:
         v = lambda q: C.c_void_p(q or None)
         return lib().tb_pnp_ransac_batch_dev(self._h, int(nproblems), _p(K), v(obs_ptr), v(counts_ptr), int(obs_pitch), C.byref(prm),
                                              v(prior_ptr), v(Tcw_ptr), v(consensus_ptr), v(inlier_ptr), v(winner_ptr), v(flags_ptr))
+
+    def two_view(self, xy0, xy1, K, skip=None, inv_sigma2_0=None, inv_sigma2_1=None, Tcw0=None, **params):
+        """tb_two_view: a relative pose and first points from the n point pairs (xy0 / xy1 [n][2] pixels) of one problem; params as
+        two_view_params. Returns a dict: status, Tcw1 [4, 4] float32, points [n][3] float32 (zero where nothing was written),
+        point_flags / inlier uint8 [n], consensus, winner (hypothesis, candidate), good / tri int32 [4]."""
+        xy0 = np.ascontiguousarray(xy0, np.float32).reshape(-1, 2)
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        n = len(xy0)
+        assert len(xy1) == n
+        opt = [None if a is None else np.ascontiguousarray(a, t).reshape(n) for a, t in
+               ((skip, np.uint8), (inv_sigma2_0, np.float32), (inv_sigma2_1, np.float32))]
+        K = np.ascontiguousarray(K, np.float64)
+        T0 = None if Tcw0 is None else np.ascontiguousarray(Tcw0, np.float32).reshape(16)
+        prm = two_view_params(**params)
+        T1, pts = np.zeros(16, np.float32), np.zeros((n, 3), np.float32)
+        pf, inl = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        win, good, tri = np.zeros(2, np.int32), np.zeros(4, np.int32), np.zeros(4, np.int32)
+        cons, status = C.c_int(0), C.c_int(0)
+        q = lambda a: _p(a) if n else None
+        self.check(lib().tb_two_view(self._h, q(xy0), q(xy1), n, _p(opt[0]), _p(opt[1]), _p(opt[2]), _p(K), _p(T0), C.byref(prm), _p(T1),
+                                     q(pts), q(pf), q(inl), C.byref(cons), _p(win), _p(good), _p(tri), C.byref(status)))
+        return dict(status=status.value, Tcw1=T1.reshape(4, 4), points=pts, point_flags=pf, inlier=inl, consensus=cons.value,
+                    winner=(int(win[0]), int(win[1])), good=good, tri=tri)
+
+    def two_view_dev(self, nproblems, xy0_ptr, xy1_ptr, counts_ptr, pitch, K, skip_ptr=0, inv_sigma2_0_ptr=0, inv_sigma2_1_ptr=0,
+                     Tcw0_ptr=0, Tcw1_ptr=0, points_ptr=0, point_flags_ptr=0, inlier_ptr=0, consensus_ptr=0, winner_ptr=0, good_ptr=0,
+                     tri_ptr=0, status_ptr=0, params=None, **kw):
+        """tb_two_view_batch_dev: device pointers (0 / None for the nullable ones), asynchronous on the context's stream; params a
+        TwoViewParams, or two_view_params' keywords. Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        prm = two_view_params(**kw) if params is None else params
+        v = lambda q: C.c_void_p(q or None)
+        return lib().tb_two_view_batch_dev(self._h, int(nproblems), v(xy0_ptr), v(xy1_ptr), v(counts_ptr), int(pitch), v(skip_ptr),
+                                           v(inv_sigma2_0_ptr), v(inv_sigma2_1_ptr), _p(K), v(Tcw0_ptr), C.byref(prm), v(Tcw1_ptr),
+                                           v(points_ptr), v(point_flags_ptr), v(inlier_ptr), v(consensus_ptr), v(winner_ptr), v(good_ptr),
+                                           v(tri_ptr), v(status_ptr))
 
     def local_ba(self, K, poses, nfixed, pts, obs, iters=10):
         K = np.ascontiguousarray(K, np.float64)

@@ -1,89 +1,17 @@
 /* Two-view linear triangulation with known poses (LocalBA::LinearTriangle, LocalBA.cpp:24-43), batched, with the acceptance
  * gates of include/tb_capi.h (tb_linear_triangle_batch_dev).
  *
- * One lane per point pair, everything in registers: the 4 x 4 matrices are C arrays whose every index is a compile-time constant
- * after unrolling (TRI_ROT's p, q are template arguments), so they are promoted to registers and the kernel has no scratch and
- * no LDS. A pair's poses and K are wave-uniform. float64, one operation per statement, only + - * / sqrt, in the order
- * tests/triangulate_reference.py writes down (the library builds with -ffp-contract=off). The Jacobi iteration runs a fixed
- * number of sweeps without a convergence test: the lanes of a wave stay converged and the result does not depend on a threshold. */
+ * One lane per point pair (the per-point code is tb_triangulate.h's tri_point, which k_two_view.hip shares), everything in
+ * registers: the 4 x 4 matrices are C arrays whose every index is a compile-time constant after unrolling (tri_rotate's P, Q are
+ * template arguments), so they are promoted to registers and the kernel has no scratch and no LDS. A pair's poses and K are
+ * wave-uniform. float64, one operation per statement, only + - * / sqrt, in the order tests/triangulate_reference.py writes down
+ * (the library builds with -ffp-contract=off). The Jacobi iteration runs a fixed number of sweeps without a convergence test: the
+ * lanes of a wave stay converged and the result does not depend on a threshold. */
 #include "tb_internal.h"
 #include "tb_device.h"
+#include "tb_triangulate.h"
 
 #define TRI_T 256
-#define TRI_SWEEPS 6
-
-/* one Jacobi rotation on the pair (P, Q), the shim's formulas; skipped only where M[P][Q] == 0 */
-template <int P, int Q>
-__device__ __forceinline__ void tri_rotate(double (&M)[4][4], double (&V)[4][4]) {
-    if (M[P][Q] == 0.0) return;
-    const double num = M[Q][Q] - M[P][P];
-    const double den = 2.0 * M[P][Q];
-    const double th = num / den;
-    double r = th * th;
-    r = r + 1.0;
-    r = sqrt(r);
-    r = fabs(th) + r;
-    const double t = (th >= 0.0 ? 1.0 : -1.0) / r;
-    double c = t * t;
-    c = c + 1.0;
-    c = sqrt(c);
-    c = 1.0 / c;
-    const double s = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double a = M[k][P], b = M[k][Q];
-        const double ca = c * a, sb = s * b, sa = s * a, cb = c * b;
-        M[k][P] = ca - sb;
-        M[k][Q] = sa + cb;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double a = M[P][k], b = M[Q][k];
-        const double ca = c * a, sb = s * b, sa = s * a, cb = c * b;
-        M[P][k] = ca - sb;
-        M[Q][k] = sa + cb;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double a = V[k][P], b = V[k][Q];
-        const double ca = c * a, sb = s * b, sa = s * a, cb = c * b;
-        V[k][P] = ca - sb;
-        V[k][Q] = sa + cb;
-    }
-}
-
-/* row r of T applied to (X, 1) */
-__device__ __forceinline__ double tri_row(const double (&T)[16], int r, double X, double Y, double Z) {
-    double a = T[r * 4 + 0] * X;
-    const double b = T[r * 4 + 1] * Y;
-    a = a + b;
-    const double c = T[r * 4 + 2] * Z;
-    a = a + c;
-    return a + T[r * 4 + 3];
-}
-
-__device__ __forceinline__ double tri_dot(double ax, double ay, double az, double bx, double by, double bz) {
-    double d = ax * bx;
-    const double e = ay * by;
-    d = d + e;
-    const double f = az * bz;
-    return d + f;
-}
-
-/* squared pixel error of X in the view T, times inv_sigma2 */
-__device__ __forceinline__ double tri_chi2(const double (&T)[16], double X, double Y, double Z, double z, double u, double v, double fx,
-                                           double fy, double cx, double cy, double inv_sigma2) {
-    double pu = tri_row(T, 0, X, Y, Z) / z;
-    pu = fx * pu;
-    pu = pu + cx;
-    double pv = tri_row(T, 1, X, Y, Z) / z;
-    pv = fy * pv;
-    pv = pv + cy;
-    const double du = pu - u, dv = pv - v;
-    const double e0 = du * du, e1 = dv * dv;
-    const double e = e0 + e1;
-    return e * inv_sigma2;
-}
 
 __global__ void __launch_bounds__(TRI_T)
 k_linear_triangle(const float* __restrict__ xy0, const float* __restrict__ xy1, const int32_t* __restrict__ counts, int pitch,
@@ -102,76 +30,9 @@ k_linear_triangle(const float* __restrict__ xy0, const float* __restrict__ xy1, 
         for (int k = 0; k < 16; k++) { T0[k] = (double)Tcw0[16 * p + k]; T1[k] = (double)Tcw1[16 * p + k]; }
         const double u0 = (double)xy0[2 * o], v0 = (double)xy0[2 * o + 1], u1 = (double)xy1[2 * o], v1 = (double)xy1[2 * o + 1];
         const double s0 = inv_sigma2_0 ? (double)inv_sigma2_0[o] : 1.0, s1 = inv_sigma2_1 ? (double)inv_sigma2_1[o] : 1.0;
-        double x0 = u0 - cx, y0 = v0 - cy, x1 = u1 - cx, y1 = v1 - cy;
-        x0 = x0 / fx; y0 = y0 / fy; x1 = x1 / fx; y1 = y1 / fy;
-        double A[4][4], M[4][4], V[4][4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const double a0 = x0 * T0[8 + c], a1 = y0 * T0[8 + c], a2 = x1 * T1[8 + c], a3 = y1 * T1[8 + c];
-            A[0][c] = a0 - T0[c];
-            A[1][c] = a1 - T0[4 + c];
-            A[2][c] = a2 - T1[c];
-            A[3][c] = a3 - T1[4 + c];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int c = r; c < 4; c++) {
-                double m = A[0][r] * A[0][c];
-                const double m1 = A[1][r] * A[1][c];
-                m = m + m1;
-                const double m2 = A[2][r] * A[2][c];
-                m = m + m2;
-                const double m3 = A[3][r] * A[3][c];
-                m = m + m3;
-                M[r][c] = m;
-                M[c][r] = m;
-                V[r][c] = r == c ? 1.0 : 0.0;
-                V[c][r] = r == c ? 1.0 : 0.0;
-            }
-        for (int sweep = 0; sweep < TRI_SWEEPS; sweep++) {
-            tri_rotate<0, 1>(M, V);
-            tri_rotate<0, 2>(M, V);
-            tri_rotate<0, 3>(M, V);
-            tri_rotate<1, 2>(M, V);
-            tri_rotate<1, 3>(M, V);
-            tri_rotate<2, 3>(M, V);
-        }
-        /* the column at the smallest diagonal entry, the lowest index on a tie */
-        double best = M[0][0], h0 = V[0][0], h1 = V[1][0], h2 = V[2][0], h3 = V[3][0];
-#pragma unroll
-        for (int k = 1; k < 4; k++)
-            if (M[k][k] < best) { best = M[k][k]; h0 = V[0][k]; h1 = V[1][k]; h2 = V[2][k]; h3 = V[3][k]; }
-        const double X = h0 / h3, Y = h1 / h3, Z = h2 / h3;
-        const float Xf = (float)X, Yf = (float)Y, Zf = (float)Z;
-        const double z0 = tri_row(T0, 2, X, Y, Z), z1 = tri_row(T1, 2, X, Y, Z);
-        /* the pixels' rays in the world frame: R^T (x, y, 1) */
-        double r0[3], r1[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            double a = T0[k] * x0;
-            const double b = T0[4 + k] * y0;
-            a = a + b;
-            r0[k] = a + T0[8 + k];
-            double c = T1[k] * x1;
-            const double d = T1[4 + k] * y1;
-            c = c + d;
-            r1[k] = c + T1[8 + k];
-        }
-        const double n0 = sqrt(tri_dot(r0[0], r0[1], r0[2], r0[0], r0[1], r0[2]));
-        const double n1 = sqrt(tri_dot(r1[0], r1[1], r1[2], r1[0], r1[1], r1[2]));
-        const double nn = n0 * n1;
-        const double cosv = tri_dot(r0[0], r0[1], r0[2], r1[0], r1[1], r1[2]) / nn;
-        const double c0 = tri_chi2(T0, X, Y, Z, z0, u0, v0, fx, fy, cx, cy, s0);
-        const double c1 = tri_chi2(T1, X, Y, Z, z1, u1, v1, fx, fy, cx, cy, s1);
-        if (h3 == 0.0 || !isfinite(Xf) || !isfinite(Yf) || !isfinite(Zf)) flag = 2;
-        else if (!(z0 > 0.0) || !(z1 > 0.0)) flag = 3;
-        else if (!(cosv < cos_parallax_max)) flag = 4;
-        else if (c0 > chi2_max || c1 > chi2_max) flag = 5;
-        else {
-            flag = 1;
-            points[3 * o] = Xf; points[3 * o + 1] = Yf; points[3 * o + 2] = Zf;
-        }
+        float Xf, Yf, Zf;
+        flag = tri_point(T0, T1, u0, v0, u1, v1, s0, s1, fx, fy, cx, cy, cos_parallax_max, chi2_max, Xf, Yf, Zf);
+        if (flag == 1) { points[3 * o] = Xf; points[3 * o + 1] = Yf; points[3 * o + 2] = Zf; }
     }
     if (in_row) flags[o] = (uint8_t)flag;
     /* one atomic per wavefront and code; integer sums do not depend on the order */

@@ -782,6 +782,83 @@ k_vo_mono_alive(const int32_t* __restrict__ key_counts, const uint8_t* __restric
     skip[o] = valid[o] || !a ? 1 : 0;
 }
 
+/* ---- the mono loop without a right image (include/tb_capi.h, tb_vo_mono_init) */
+
+/* Before a keyframe's triangulation: a sequence that is not initialised leaves the triangulation and is a two-view problem over
+ * the keys LK still holds; an initialised one is no two-view problem and keeps the triangulation's skip bytes. */
+__global__ void __launch_bounds__(256)
+k_vo_init_prep(const uint8_t* __restrict__ initialised, const uint8_t* __restrict__ alive, int pitch, uint8_t* __restrict__ tri_skip,
+               uint8_t* __restrict__ tv_skip) {
+    const int s = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pitch) return;
+    const size_t o = (size_t)s * pitch + i;
+    const bool ini = initialised[s] != 0;
+    tv_skip[o] = ini || !alive[o] ? 1 : 0;
+    if (!ini) tri_skip[o] = 1;
+}
+
+/* After the two-view call, one workgroup per sequence that is not initialised: the attempt's results (w_res, in planes: status, consensus,
+ * winner[2], good[4], tri[4]; w_Tcw1) are kept; with status 0 and at least min_tracks alive keys the sequence takes the pose and,
+ * through the triangulation's outputs the merge reads, the points. An initialised sequence keeps every byte. */
+__global__ void __launch_bounds__(256)
+k_vo_init_adopt(int t, int min_tracks, const int32_t* __restrict__ key_counts, const uint8_t* __restrict__ alive, int pitch,
+                const int32_t* __restrict__ w_res, const float* __restrict__ w_Tcw1, const float* __restrict__ points,
+                const uint8_t* __restrict__ pflags, uint8_t* __restrict__ initialised, int32_t* __restrict__ init_frame,
+                int32_t* __restrict__ attempts, int32_t* __restrict__ res, float* __restrict__ Tcw1, float* __restrict__ Tcw,
+                float* __restrict__ tri_points, uint8_t* __restrict__ tri_flags) {
+    __shared__ int wsum[4];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    if (initialised[s]) return;   /* block-uniform; written below only behind the barrier */
+    const int n = min(max(key_counts[s], 0), pitch);
+    const size_t o = (size_t)s * pitch;
+    int cnt = 0;
+    for (int i = tid; i < n; i += 256) cnt += alive[o + i] ? 1 : 0;
+    cnt = tb_wave_sum(cnt);
+    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
+    __syncthreads();
+    const int tracks = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const size_t S = gridDim.x;   /* planes: status [S], consensus [S], winner [S][2], good [S][4], tri [S][4] */
+    const bool ok = w_res[s] == 0 && tracks >= min_tracks;
+    if (tid < 12) {
+        const size_t at = tid == 0 ? (size_t)s : tid == 1 ? S + s : tid < 4 ? 2 * S + 2 * (size_t)s + (tid - 2)
+                        : tid < 8 ? 4 * S + 4 * (size_t)s + (tid - 4) : 8 * S + 4 * (size_t)s + (tid - 8);
+        res[at] = w_res[at];
+    }
+    if (tid < 16) {
+        const float v = w_Tcw1[16 * s + tid];
+        Tcw1[16 * s + tid] = v;
+        if (ok) Tcw[16 * s + tid] = v;
+    }
+    if (ok)
+        for (int i = tid; i < n; i += 256)
+            if (pflags[o + i] == 1) {
+                tri_points[3 * (o + i)] = points[3 * (o + i)];
+                tri_points[3 * (o + i) + 1] = points[3 * (o + i) + 1];
+                tri_points[3 * (o + i) + 2] = points[3 * (o + i) + 2];
+                tri_flags[o + i] = 1;
+            }
+    if (tid == 0) {
+        attempts[s] += 1;
+        if (ok) { initialised[s] = 1; init_frame[s] = t; }
+    }
+}
+
+int tbk_vo_init_prep(tb_ctx* ctx, int nseq, const uint8_t* d_initialised, const uint8_t* d_alive, int pitch, uint8_t* d_tri_skip,
+                     uint8_t* d_tv_skip) {
+    if (nseq <= 0) return TB_OK;
+    return tb_launch(ctx, "k_vo_init_prep", k_vo_init_prep, dim3((pitch + 255) / 256, nseq), dim3(256), 0, d_initialised, d_alive, pitch,
+                     d_tri_skip, d_tv_skip);
+}
+
+int tbk_vo_init_adopt(tb_ctx* ctx, int nseq, int t, int min_tracks, const int32_t* d_key_counts, const uint8_t* d_alive, int pitch,
+                      const int32_t* d_w_res, const float* d_w_Tcw1, const float* d_points, const uint8_t* d_pflags,
+                      uint8_t* d_initialised, int32_t* d_init_frame, int32_t* d_attempts, int32_t* d_res, float* d_Tcw1, float* d_Tcw,
+                      float* d_tri_points, uint8_t* d_tri_flags) {
+    if (nseq <= 0) return TB_OK;
+    return tb_launch(ctx, "k_vo_init_adopt", k_vo_init_adopt, dim3(nseq), dim3(256), 0, t, min_tracks, d_key_counts, d_alive, pitch, d_w_res,
+                     d_w_Tcw1, d_points, d_pflags, d_initialised, d_init_frame, d_attempts, d_res, d_Tcw1, d_Tcw, d_tri_points, d_tri_flags);
+}
+
 /* The occupancy cell of a pixel, -1 outside the cw x ch grid (and for a coordinate no int holds) */
 __device__ __forceinline__ int vo_merge_cell(float x, float y, int cell, int cw, int ch) {
     if (!(fabsf(x) < 1.0e9f) || !(fabsf(y) < 1.0e9f)) return -1;

@@ -2119,6 +2119,72 @@ int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, cons
     return TB_OK;
 }
 
+/* ------------------------------------------------------------------ two-view initialisation */
+int tb_two_view_batch_dev(tb_ctx* ctx, int nproblems, const float* xy0, const float* xy1, const int32_t* counts, int pitch,
+                          const uint8_t* skip, const float* inv_sigma2_0, const float* inv_sigma2_1, const double K[4],
+                          const float* Tcw0, const tb_two_view_params* prm, float* Tcw1, float* points, uint8_t* point_flags,
+                          uint8_t* inlier, int32_t* consensus, int32_t* winner, int32_t* good, int32_t* tri, int32_t* status) {
+    TB_ENTER(ctx);
+    if (!ctx || nproblems < 0 || pitch < 1 || !K || !xy0 || !xy1 || !prm) return TB_EINVAL;
+    if (!tb_two_view_params_ok(prm) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) ||
+        !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_two_view_batch_dev: hypotheses 1..1024, thresholds finite and not negative, ratios in (0, 1], "
+                                       "min_points >= 0, baseline positive and finite, K finite, fx and fy positive");
+    if (nproblems > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_two_view_batch_dev: %d problems (at most 65535 per call)", nproblems);
+    if (pitch > TB_TWO_VIEW_MAX_PITCH)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_two_view_batch_dev: pitch %d (at most %d rows are staged)", pitch, TB_TWO_VIEW_MAX_PITCH);
+    return tbk_two_view(ctx, nproblems, xy0, xy1, counts, skip, inv_sigma2_0, inv_sigma2_1, pitch, K, Tcw0, prm, Tcw1, points, point_flags,
+                        inlier, consensus, winner, good, tri, status);
+}
+
+int tb_two_view(tb_ctx* ctx, const float* xy0, const float* xy1, int n, const uint8_t* skip, const float* inv_sigma2_0,
+                const float* inv_sigma2_1, const double K[4], const float Tcw0[16], const tb_two_view_params* prm, float Tcw1[16],
+                float* points, uint8_t* point_flags, uint8_t* inlier, int* consensus, int32_t winner[2], int32_t good[4],
+                int32_t tri[4], int* status) {
+    TB_ENTER(ctx);
+    if (!ctx || n < 0 || !K || !prm || (n && (!xy0 || !xy1))) return TB_EINVAL;
+    const size_t pitch = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oA = stage_piece(end, pitch * 8), oB = stage_piece(end, pitch * 8), oT0 = stage_piece(end, 64), oT1 = stage_piece(end, 64),
+                 oS0 = stage_piece(end, pitch * 4), oS1 = stage_piece(end, pitch * 4), oSkip = stage_piece(end, pitch),
+                 oPts = stage_piece(end, pitch * 12), oFlags = stage_piece(end, pitch), oInl = stage_piece(end, pitch),
+                 oRes = stage_piece(end, 48), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt = n;
+    TB_UPLOAD(ctx, b + oA, xy0, (size_t)n * 8);
+    TB_UPLOAD(ctx, b + oB, xy1, (size_t)n * 8);
+    TB_UPLOAD(ctx, b + oCnt, &cnt, 4);
+    if (Tcw0) TB_UPLOAD(ctx, b + oT0, Tcw0, 64);
+    if (inv_sigma2_0) TB_UPLOAD(ctx, b + oS0, inv_sigma2_0, (size_t)n * 4);
+    if (inv_sigma2_1) TB_UPLOAD(ctx, b + oS1, inv_sigma2_1, (size_t)n * 4);
+    if (skip) TB_UPLOAD(ctx, b + oSkip, skip, (size_t)n);
+    TB_HIP(ctx, hipMemsetAsync(b + oPts, 0, pitch * 12, ctx->stream));   /* the operator writes accepted points only */
+    int32_t* res = (int32_t*)(b + oRes);   /* consensus, winner[2], good[4], tri[4], status */
+    if ((rc = tb_two_view_batch_dev(ctx, 1, (const float*)(b + oA), (const float*)(b + oB), (const int32_t*)(b + oCnt), (int)pitch,
+                                    skip ? (const uint8_t*)(b + oSkip) : nullptr, inv_sigma2_0 ? (const float*)(b + oS0) : nullptr,
+                                    inv_sigma2_1 ? (const float*)(b + oS1) : nullptr, K, Tcw0 ? (const float*)(b + oT0) : nullptr, prm,
+                                    (float*)(b + oT1), (float*)(b + oPts), (uint8_t*)(b + oFlags), (uint8_t*)(b + oInl), res, res + 1, res + 3,
+                                    res + 7, res + 11)))
+        return rc;
+    int32_t h[12];
+    float T[16];
+    TB_DOWNLOAD(ctx, T, b + oT1, 64);
+    TB_DOWNLOAD(ctx, h, res, 48);
+    if (points) TB_DOWNLOAD(ctx, points, b + oPts, (size_t)n * 12);
+    if (point_flags) TB_DOWNLOAD(ctx, point_flags, b + oFlags, (size_t)n);
+    if (inlier) TB_DOWNLOAD(ctx, inlier, b + oInl, (size_t)n);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (Tcw1) memcpy(Tcw1, T, 64);
+    if (consensus) *consensus = h[0];
+    if (winner) { winner[0] = h[1]; winner[1] = h[2]; }
+    if (good) memcpy(good, h + 3, 16);
+    if (tri) memcpy(tri, h + 7, 16);
+    if (status) *status = h[11];
+    return TB_OK;
+}
+
 int tb_local_ba_batch_dev(tb_ctx* ctx, int nwindows, const double K[4], int nkf, int nfixed, float* poses, int npt, float* pts,
                           const tb_ba_obs* obs, const int32_t* obs_counts, int obs_pitch, int iters, double* stats) {
     TB_ENTER(ctx);

@@ -2,6 +2,7 @@
 #ifndef TB_INTERNAL_H
 #define TB_INTERNAL_H
 
+#include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -505,6 +506,27 @@ int tbk_linear_triangle(tb_ctx* ctx, int npairs, const float* d_xy0, const float
 int tbk_pnp_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_obs* d_obs, const int32_t* d_counts, int obs_pitch, int hypotheses,
                   double chi2_max, unsigned long long seed, const float* d_Tcw_prior, float* d_Tcw_out, int32_t* d_consensus,
                   uint8_t* d_inlier, int32_t* d_winner, int32_t* d_flags);
+/* two-view initialisation (k_two_view.hip): one workgroup per problem, no work buffer; every output nullable; pitch <= 2048 */
+int tbk_two_view(tb_ctx* ctx, int nproblems, const float* d_xy0, const float* d_xy1, const int32_t* d_counts, const uint8_t* d_skip,
+                 const float* d_inv_sigma2_0, const float* d_inv_sigma2_1, int pitch, const double K[4], const float* d_Tcw0,
+                 const tb_two_view_params* prm, float* d_Tcw1, float* d_points, uint8_t* d_point_flags, uint8_t* d_inlier,
+                 int32_t* d_consensus, int32_t* d_winner, int32_t* d_good, int32_t* d_tri, int32_t* d_status);
+/* tb_two_view_batch_dev's parameter rules, for the entry points that store a parameter set */
+static inline bool tb_two_view_params_ok(const tb_two_view_params* prm) {
+    const bool ratios = prm->min_good_ratio > 0.0 && prm->min_good_ratio <= 1.0 && prm->ambiguity_ratio > 0.0 && prm->ambiguity_ratio <= 1.0;
+    return prm->hypotheses >= 1 && prm->hypotheses <= 1024 && prm->chi2_epi >= 0.0 && std::isfinite(prm->chi2_epi) &&
+           prm->tri.chi2_max >= 0.0 && std::isfinite(prm->tri.chi2_max) && std::isfinite(prm->tri.cos_parallax_max) && ratios &&
+           prm->min_points >= 0 && prm->baseline > 0.0 && std::isfinite(prm->baseline);
+}
+/* the mono loop without a right image (k_vo.hip): before the keyframe's triangulation, a sequence that is not initialised leaves
+ * it (tri_skip = 1) and becomes a two-view problem (tv_skip = !alive), an initialised one the other way round; after the
+ * two-view call, the sequences that initialise adopt pose and points, and every attempt's results are kept */
+int tbk_vo_init_prep(tb_ctx* ctx, int nseq, const uint8_t* d_initialised, const uint8_t* d_alive, int pitch, uint8_t* d_tri_skip,
+                     uint8_t* d_tv_skip);
+int tbk_vo_init_adopt(tb_ctx* ctx, int nseq, int t, int min_tracks, const int32_t* d_key_counts, const uint8_t* d_alive, int pitch,
+                      const int32_t* d_w_res, const float* d_w_Tcw1, const float* d_points, const uint8_t* d_pflags,
+                      uint8_t* d_initialised, int32_t* d_init_frame, int32_t* d_attempts, int32_t* d_res, float* d_Tcw1, float* d_Tcw,
+                      float* d_tri_points, uint8_t* d_tri_flags);
 /* PnP inside candidate verification (k_pnp.hip): the ordered gather of a pair's rows (stage 0: after the RANSAC, pose_a = the PnP
  * pose, pose_b = the stored seed; stage 1: expand, pose_a = the optimised pose) and the adoption of the second pose stage */
 int tbk_pnp_gather(tb_ctx* ctx, int npairs, int stage, const double K[4], double chi2_max, int min_consensus, const tb_obs* d_rows0,

@@ -132,6 +132,14 @@ struct tb_vo {
     float* mn_tri_points = nullptr;                      /* [nseq][P][3] */
     uint8_t* mn_tri_flags = nullptr;                     /* [nseq][P] */
     int32_t *mn_tri_tally = nullptr, *mn_survivors = nullptr, *mn_added = nullptr;   /* [nseq][6], [nseq], [nseq] */
+    /* the mono loop without a right image (tb_vo_mono_init_enable): which sequences are initialised, the two-view call's
+     * outputs of the step (w_: the planes status, consensus, winner[2], good[4], tri[4], 12 ints a sequence) and every sequence's last attempt */
+    bool mi_on = false;
+    tb_vo_mono_init mi;
+    uint8_t *mi_initialised = nullptr, *mi_skip = nullptr, *mi_pflags = nullptr;   /* [nseq], [nseq][P], [nseq][P] */
+    int32_t *mi_init_frame = nullptr, *mi_attempts = nullptr;                     /* [nseq] */
+    int32_t *mi_w_res = nullptr, *mi_res = nullptr;                               /* [nseq][12] */
+    float *mi_w_Tcw1 = nullptr, *mi_Tcw1 = nullptr, *mi_points = nullptr;         /* [nseq][16], [nseq][16], [nseq][P][3] */
 };
 
 static bool vo_is_proj(const tb_vo* vo) { return vo->tr.kind == TB_VO_PROJECTION || vo->tr.kind == TB_VO_PROJECTION_MAP; }
@@ -388,6 +396,7 @@ static int vo_recover_clear(tb_vo* vo);
 static int vo_loop_clear(tb_vo* vo);
 static int vo_window_clear(tb_vo* vo);
 static int vo_mono_clear(tb_vo* vo);
+static int vo_mono_init_clear(tb_vo* vo);
 static int vo_extract(tb_vo* vo, const uint8_t* images, int n);
 
 int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
@@ -416,6 +425,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     }
     if (vo->wb_on) TB_TRY(vo_window_clear(vo));
     if (vo->mono_on) TB_TRY(vo_mono_clear(vo));
+    if (vo->mi_on) TB_TRY(vo_mono_init_clear(vo));
     vo->next = 0;
     vo->ragged = false;
     std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
@@ -488,6 +498,18 @@ static int vo_mono_clear(tb_vo* vo) {
     return TB_OK;
 }
 
+/* the state of a new run without a right image: nothing initialised, no attempt yet */
+static int vo_mono_init_clear(tb_vo* vo) {
+    tb_ctx* ctx = vo->ctx;
+    const size_t S = (size_t)vo->nseq;
+    TB_HIP(ctx, hipMemsetAsync(vo->mi_initialised, 0, S, ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mi_init_frame, 0xff, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mi_attempts, 0, S * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mi_res, 0, S * 12 * sizeof(int32_t), ctx->stream));
+    TB_HIP(ctx, hipMemsetAsync(vo->mi_Tcw1, 0, S * 16 * sizeof(float), ctx->stream));
+    return TB_OK;
+}
+
 /* Mono mode, the end of frame 0's stereo keyframe block: the key list and pose the next segment triangulates against. */
 static int vo_mono_start(tb_vo* vo, int b) {
     tb_ctx* ctx = vo->ctx;
@@ -502,13 +524,23 @@ static int vo_mono_start(tb_vo* vo, int b) {
  * optimised pose, then merge the keys that have a map point with the frame's ORB keys. The merge reads side b and writes side
  * a, which nothing needs any more; the two sides of the key list, its counts and its map points then change places, so side b
  * is the frame's again. */
-static int vo_mono_keyframe(tb_vo* vo, int b) {
+static int vo_mono_keyframe(tb_vo* vo, int b, int t) {
     tb_ctx* ctx = vo->ctx;
     const tb_vo_params& p = vo->p;
     const int S = vo->nseq, P = vo->P, a = b ^ 1;
     const tb_triangulate_params tp = {vo->mono.cos_parallax_max, vo->mono.chi2_max};
+    if (vo->mi_on) TB_TRY(tbk_vo_init_prep(ctx, S, vo->mi_initialised, vo->mn_alive, P, vo->mn_skip, vo->mi_skip));
     TB_TRY(tb_linear_triangle_batch_dev(ctx, S, vo->mn_kf_keys, vo->keys[b], vo->kcnt[b], P, vo->mn_kf_Tcw, vo->Tcw[b], p.K, nullptr, nullptr,
                                         vo->mn_skip, &tp, vo->mn_tri_points, vo->mn_tri_flags, vo->mn_tri_tally));
+    if (vo->mi_on) {   /* the sequences that are not initialised yet: a pose and first points from the segment's tracks alone */
+        int32_t* w = vo->mi_w_res;   /* planes: status [S], consensus [S], winner [S][2], good [S][4], tri [S][4] */
+        TB_TRY(tbk_two_view(ctx, S, vo->mn_kf_keys, vo->keys[b], vo->kcnt[b], vo->mi_skip, nullptr, nullptr, P, p.K, vo->mn_kf_Tcw,
+                            &vo->mi.two_view, vo->mi_w_Tcw1, vo->mi_points, vo->mi_pflags, nullptr, w + (size_t)S, w + 2 * (size_t)S,
+                            w + 4 * (size_t)S, w + 8 * (size_t)S, w));
+        TB_TRY(tbk_vo_init_adopt(ctx, S, t, vo->mi.min_tracks, vo->kcnt[b], vo->mn_alive, P, w, vo->mi_w_Tcw1, vo->mi_points, vo->mi_pflags,
+                                 vo->mi_initialised, vo->mi_init_frame, vo->mi_attempts, vo->mi_res, vo->mi_Tcw1, vo->Tcw[b],
+                                 vo->mn_tri_points, vo->mn_tri_flags));
+    }
     TB_TRY(vo_extract(vo, vo->img[b], S));
     const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
     tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
@@ -819,7 +851,13 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
     if (vo->mono_on && t > 0)   /* which keys LK still holds, and which of them have no map point yet */
         TB_TRY(tbk_vo_mono_alive(vo->ctx, S, vo->kcnt[b], vo->status, vo->valid[b], vo->P, vo->mn_alive, vo->mn_skip));
     if (keyframe && vo->mono_on && t > 0) {
-        TB_TRY(vo_mono_keyframe(vo, b));
+        TB_TRY(vo_mono_keyframe(vo, b, t));
+    } else if (keyframe && vo->mi_on) {   /* frame 0 without a right image: ORB only, no key has a map point */
+        TB_TRY(vo_extract(vo, vo->img[b], S));
+        const tb_keypoint* kps = nullptr; const int32_t* cnt = nullptr; int selCap = 0;
+        tb_extractor_results_dev(vo->ex, &kps, nullptr, &cnt, &selCap);
+        TB_TRY(tbk_vo_kf_pack(vo->ctx, S, kps, cnt, selCap, vo->P, vo->keys[b], vo->kcnt[b], vo->valid[b], nullptr));
+        TB_TRY(vo_mono_start(vo, b));
     } else if (keyframe) {
         TB_TRY(vo_keyframe(vo, t, b, S, nullptr, nullptr, right, stride, pitch));
         if (vo->mono_on) TB_TRY(vo_mono_start(vo, b));
@@ -850,7 +888,7 @@ int tb_vo_step_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, int str
     const int t = vo->next;
     const bool keyframe = t % p.keyframe_every == 0;
     if (!left || stride < p.width || pitch < (size_t)stride * p.height) return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: left images / geometry");
-    if (keyframe && !right && !(vo->mono_on && t > 0))
+    if (keyframe && !right && !(vo->mono_on && (t > 0 || vo->mi_on)))
         return tb_fail(ctx, TB_EINVAL, "tb_vo_step_dev: frame %d is a keyframe and needs the right images", t);
     return vo_step_lock(vo, t, keyframe, left, right, stride, pitch);
 }
@@ -1335,6 +1373,57 @@ int tb_vo_mono_enable(tb_vo* vo, const tb_vo_mono* prm) {
     vo->mono = *prm;
     TB_TRY(vo_mono_clear(vo));
     vo->mono_on = true;
+    return TB_OK;
+}
+
+int tb_vo_mono_init_enable(tb_vo* vo, const tb_vo_mono_init* prm) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->mono_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_mono_init_enable: the mono mode is not enabled (tb_vo_mono_enable first)");
+    if (vo->next >= 0 || vo->ragged) return tb_fail(ctx, TB_ESTATE, "tb_vo_mono_init_enable after a reset");
+    if (vo->mi_on) return tb_fail(ctx, TB_ESTATE, "tb_vo_mono_init_enable: enabled already");
+    if (!prm) return tb_fail(ctx, TB_EINVAL, "tb_vo_mono_init_enable: null parameters");
+    if (prm->min_tracks < 0 || !tb_two_view_params_ok(&prm->two_view))
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_mono_init_enable: min_tracks %d (>= 0), or two-view parameters tb_two_view_batch_dev refuses",
+                       prm->min_tracks);
+    if (vo->P > TB_TWO_VIEW_MAX_PITCH)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "tb_vo_mono_init_enable: key pitch %d (the two-view operator stages at most %d rows)", vo->P,
+                       TB_TWO_VIEW_MAX_PITCH);
+    const size_t S = (size_t)vo->nseq, SP = S * vo->P;
+    tb_dev_owner& own = vo->own;
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_initialised, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_skip, SP));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_pflags, SP));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_init_frame, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_attempts, S));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_w_res, S * 12));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_res, S * 12));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_w_Tcw1, S * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_Tcw1, S * 16));
+    TB_TRY(tb_dev_alloc(ctx, own, &vo->mi_points, SP * 3));
+    vo->mi = *prm;
+    TB_TRY(vo_mono_init_clear(vo));
+    vo->mi_on = true;
+    return TB_OK;
+}
+
+int tb_vo_mono_init_state_dev(tb_vo* vo, const uint8_t** initialised, const int32_t** init_frame, const int32_t** attempts,
+                              const int32_t** status, const int32_t** consensus, const int32_t** winner, const int32_t** good,
+                              const int32_t** tri, const float** Tcw1) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    if (!vo->mi_on) return tb_fail(vo->ctx, TB_ESTATE, "tb_vo_mono_init_state_dev: not enabled (tb_vo_mono_init_enable)");
+    const size_t S = (size_t)vo->nseq;
+    if (initialised) *initialised = vo->mi_initialised;
+    if (init_frame) *init_frame = vo->mi_init_frame;
+    if (attempts) *attempts = vo->mi_attempts;
+    if (status) *status = vo->mi_res;
+    if (consensus) *consensus = vo->mi_res + S;
+    if (winner) *winner = vo->mi_res + 2 * S;
+    if (good) *good = vo->mi_res + 4 * S;
+    if (tri) *tri = vo->mi_res + 8 * S;
+    if (Tcw1) *Tcw1 = vo->mi_Tcw1;
     return TB_OK;
 }
 

@@ -49,7 +49,10 @@ refined segment. The BA's termination test is the one host synchronisation a key
 `mono=True` (or a dict, see MONO_DEFAULTS; optical-flow tracker, lock-step only, not with window_ba=) grows the map from one
 camera: frame 0 is the stereo keyframe that fixes the scale, and every later keyframe takes `right=None`, triangulates the keys
 LK has held since the last keyframe from the two known poses (LocalBA::LinearTriangle on the device, gated on depth, parallax
-and reprojection error) and merges the keys that have a map point with the frame's ORB keys. `mono()` shows the keyframe's key
+and reprojection error) and merges the keys that have a map point with the frame's ORB keys. `init=True` (or a dict, see
+INIT_DEFAULTS; with mono=) starts such a loop without any right image: frame 0 runs ORB only, and the first keyframe whose LK
+tracks give the two-view operator (tb_two_view_batch_dev) a pose and at least 50 points initialises the sequence, at the scale
+`baseline=` sets; `mono_init()` shows which sequences are initialised and their last attempt. `mono()` shows the keyframe's key
 list, the triangulation's flags and the merge's counts.
 
 All state stays in HBM inside the library's tb_vo object (include/tb_capi.h); after the first step a step makes no host
@@ -98,6 +101,10 @@ WINDOW_BA_DEFAULTS = dict(iters=10, fixed=1, min_obs=2, min_points=3)
 # mono=True: ORB-SLAM's triangulation gates (a ray cosine below 0.9998, the 95 % chi-square bound of 2 degrees of freedom) and
 # an 8-pixel occupancy cell for the keyframe's merge
 MONO_DEFAULTS = dict(cos_parallax_max=0.9998, chi2_max=5.991, cell=8)
+# init=True (with mono=): the two-view operator's defaults (capi.two_view_params; baseline sets the scale) and the least number of
+# keys LK must still hold at the keyframe
+INIT_DEFAULTS = dict(hypotheses=256, chi2_epi=3.841, refit=1, cos_parallax_max=0.9998, chi2_max=5.991, min_good_ratio=0.9,
+                     ambiguity_ratio=0.7, min_points=50, baseline=1.0, seed=0, min_tracks=100)
 BOW_TEST_VO_1 = dict(th_low=30, nratio=5.0, map_point_only=False)
 
 
@@ -143,7 +150,7 @@ PNP_DEFAULTS = dict(hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, ex
 
 class StereoVO:
     def __init__(self, nseq, width=1241, height=376, K=KITTI_K, bf=KITTI_BF, nlevels=5, scale=0.8, target=2000, init_th=80.0,
-                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, loop_close=None, pnp=None, **tracker_params):
+                 min_th=30.0, keyframe_every=10, device=0, tracker="opflow", vocab=None, context=None, keyframe_db=0, relocalize=0, recover=None, window_ba=None, mono=None, loop_close=None, pnp=None, init=None, **tracker_params):
         if tracker == "opflow" and tracker_params:
             raise TypeError("the optical-flow tracker takes no parameters")
         if mono:
@@ -152,6 +159,14 @@ class StereoVO:
                 raise TypeError("mono= takes no parameter %s" % ", ".join(sorted(unknown)))
             mono = dict(MONO_DEFAULTS, **(mono if isinstance(mono, dict) else {}))
         self.mono_params = mono or None
+        if init:
+            unknown = set(init) - set(INIT_DEFAULTS) if isinstance(init, dict) else ()
+            if unknown:
+                raise TypeError("init= takes no parameter %s" % ", ".join(sorted(unknown)))
+            if not mono:
+                raise TypeError("init= starts the mono loop without a right image: it needs mono=")
+            init = dict(INIT_DEFAULTS, **(init if isinstance(init, dict) else {}))
+        self.init_params = init or None
         if window_ba:
             if tracker != "opflow":
                 raise TypeError("window_ba= needs the optical-flow tracker: its key lists are the window's point tracks")
@@ -261,6 +276,13 @@ class StereoVO:
             try:
                 self.ctx.check(self.vo.mono_enable(capi.VOMono(float(self.mono_params["cos_parallax_max"]),
                                                                float(self.mono_params["chi2_max"]), int(self.mono_params["cell"]))))
+            except Exception:
+                self.close()
+                raise
+        if self.init_params:
+            try:
+                tvp = {k: v for k, v in self.init_params.items() if k != "min_tracks"}
+                self.ctx.check(self.vo.mono_init_enable(capi.VOMonoInit(capi.two_view_params(**tvp), int(self.init_params["min_tracks"]))))
             except Exception:
                 self.close()
                 raise
@@ -642,6 +664,21 @@ class StereoVO:
                     alive=self._pget(d["alive"], (S, P), *u8), tri_points=self._pget(d["tri_points"], (S, P, 3), *f32),
                     tri_flags=self._pget(d["tri_flags"], (S, P), *u8), tri_tally=self._pget(d["tri_tally"], (S, 6), *i32),
                     survivors=self._pget(d["survivors"], (S,), *i32), added=self._pget(d["added"], (S,), *i32))
+
+    def mono_init(self):
+        """The state of the start without a right image after the last step: dict(initialised [S] uint8, init_frame [S] int32 (-1:
+        not yet), attempts [S], and every sequence's last attempt: status, consensus [S], winner [S, 2], good / tri [S, 4], Tcw1
+        [S, 4, 4]). TB_ESTATE when off."""
+        if self.init_params is None:
+            raise capi.TBError(capi.TB_ESTATE, "the start without a right image is off: StereoVO(..., mono=True, init=True)")
+        d = self.vo.mono_init_state_dev()
+        S = self.S
+        f32, u8, i32 = ("<f4", torch.float32), ("|u1", torch.uint8), ("<i4", torch.int32)
+        return dict(initialised=self._pget(d["initialised"], (S,), *u8), init_frame=self._pget(d["init_frame"], (S,), *i32),
+                    attempts=self._pget(d["attempts"], (S,), *i32), status=self._pget(d["status"], (S,), *i32),
+                    consensus=self._pget(d["consensus"], (S,), *i32), winner=self._pget(d["winner"], (S, 2), *i32),
+                    good=self._pget(d["good"], (S, 4), *i32), tri=self._pget(d["tri"], (S, 4), *i32),
+                    Tcw1=self._pget(d["Tcw1"], (S, 4, 4), *f32))
 
     def profile_enable(self, on=True, only=None):
         self.ctx.profile_enable(on, only)
