@@ -62,6 +62,10 @@ int tb_debug_force_dense_fast(tb_ctx* ctx, int on);
  * observations in every window, also where they would read the lane-interleaved stream (tb_ba_obs_stream_positions). The
  * results are the same bit for bit. */
 int tb_debug_ba_plain_obs(tb_ctx* ctx, int on);
+/* Test hook: on != 0 makes every searchByBF entry point (tb_search_by_bf, tb_match_bf, tb_search_by_bf_batch_dev, the VO loop's
+ * bf tracker) find its nearest neighbours with the scalar popcount kernel, also where the matrix-core kernel would run. The
+ * results are the same bit for bit. */
+int tb_debug_bf_scalar(tb_ctx* ctx, int on);
 int tb_profile_report(tb_ctx* ctx, char* buf, int cap);
 
 /* ---------------------------------------------------------------- a1/a2/a3: host-side scalar set-up

@@ -13,7 +13,7 @@ for h in tb_capi tb_vo; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -Wno-unused-value $extra -x hip -c $cs/$h.cpp -o $root/build/variants/${h}_$name.o
 done
 objs=""
-for o in k_pyramid k_fast k_octree k_describe k_match k_pose k_ba k_flow k_ransac k_vo k_vocab k_bow_score k_reloc; do
+for o in k_pyramid k_fast k_octree k_describe k_match k_pose k_ba k_flow k_ransac k_vo k_vocab k_bow_score k_reloc k_triangulate k_pgo k_pnp k_two_view; do
   if [ "$o" = "$stem" ]; then objs="$objs $root/build/variants/${stem}_$name.o"; else objs="$objs $cs/$o.o"; fi
 done
 objs="$objs $root/build/variants/tb_capi_$name.o $root/build/variants/tb_vo_$name.o"

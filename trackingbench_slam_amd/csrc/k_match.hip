@@ -10,8 +10,11 @@
  * a14 Matcher::searchByViolence (:299-395): per F1 key, best / second-best over the 120x36 lookup grid
  *     window of F2 (Frame.cpp:202-255), traversal order (ix, iy, insertion) preserved per thread.
  *
- * Bound: integer VALU (v_bcnt accumulate), not HBM: a 2000 x 2000 pair is 4e6 popcount-256 on 128 KB
- * of descriptors that sit in LDS / L2.
+ * Bound: not HBM -- a 2000 x 2000 pair is 4e6 Hamming-256 on 128 KB of descriptors that sit in LDS / L2. The
+ * nearest-neighbour pass runs on the i8 matrix cores (k_bf_nn_mfma: the distances as an integer matrix product, 32 256
+ * v_mfma_i32_32x32x32_i8 per 2000 x 2000 pair; beside them the vector ALU forms the keys, takes the minima and expands candidate bits to
+ * bytes -- DESIGN.md 4e has the budget and what was measured). The scalar kernel (k_bf_nn: v_xor + v_bcnt, integer VALU
+ * bound) serves sets narrower than a tile and index fields wider than 16 bits, and is the yardstick behind tb_debug_bf_scalar.
  */
 #include "tb_internal.h"
 #include "tb_device.h"
@@ -50,6 +53,203 @@ k_bf_nn(const uint8_t* __restrict__ rows, const int32_t* __restrict__ rowCounts,
         if (dist < best) { best = dist; bi = c; }
     }
     atomicMin(&rbest[(size_t)p * max_n + r], ((unsigned long long)best << 32) | (unsigned)(c0 + bi));
+}
+
+/* The same nearest neighbour as an i8 matrix product. A candidate's bits as bytes {0, 1} and a row's bits as bytes
+ * {+1 for a 0 bit, -1 for a 1 bit} give Hamming(row, cand) = popcount(row) + D, D = sum_k cand[k] * row[k]: popcount(row) is
+ * constant per row, so the argmin is D's and the popcount is added once at the end.
+ *
+ * v_mfma_i32_32x32x32_i8, candidates = A (tile rows), rows = B (tile columns): the 32x32 C/D map puts the column on lane & 31
+ * and the 16 results of a lane on tile rows (i & 3) + 8 (i >> 2) + 4 (lane >> 5), so a lane keeps the running minimum of ITS row
+ * over its 16 registers and only the two lane halves of a row meet, once, at the end. A and B hold the same (lane >> 5, byte)
+ * -> k assignment whatever it is, and a sum over k does not care about its order: k-step s takes 32-bit word s of the
+ * descriptor, lane half h its 16-bit half h, byte j its bit j -- on both sides.
+ *
+ * key = (D << 16) + candidate, compared as signed: the smallest distance, the first index on ties -- the rule of the
+ * (dist << 32 | index) atomicMin above. D is in [-256, 256] and the index field holds max_n <= 65535.
+ *
+ * A workgroup is 4 wavefronts x 64 rows: a wavefront keeps its rows' two B fragments (8 k-steps x 4 VGPRs each) in registers
+ * for the whole sweep, and every ds_read_b128 of a candidate fragment feeds two MFMAs. The workgroup expands the candidates
+ * from bits to bytes into LDS, BFM_CH at a time, as ex[k-step][candidate][32 bytes]: the 64 lanes of a fragment read are
+ * 1 KB of consecutive bytes. Candidates past nc are zero bytes in LDS and take a key that never wins.
+ *
+ * grid (row blocks, candidate splits, pairs): with plain != 0 (one split) a row's result is stored, all ones where the row has
+ * no candidate, and rbest needs no fill; otherwise the splits of a row meet in the atomicMin on a filled rbest. */
+#define BFM_T 256
+#define BFM_ROWS 256       /* rows per workgroup: 64 per wavefront */
+#define BFM_CH 128         /* candidates per LDS chunk: 8 k-steps x 128 x 32 B = 32 KB */
+#define BFM_MIN_N 32       /* below one tile of candidates the scalar kernel runs */
+#define BFM_MAX_N 65535    /* the key's index field */
+
+typedef int bfm_i4 __attribute__((ext_vector_type(4)));
+typedef int bfm_i16 __attribute__((ext_vector_type(16)));
+
+/* bits 4n .. 4n + 3 of w as four bytes {0, 1}: x + (x << 7) + (x << 14) + (x << 21) puts bit b of the nibble on bit 8b */
+__device__ __forceinline__ unsigned bfm_expand4(unsigned w, int n) { return __umul24((w >> (4 * n)) & 0xfu, 0x204081u) & 0x01010101u; }
+
+/* the smallest key of one tile's 16 results per lane; the tile's candidate base is not in it */
+__device__ __forceinline__ int bfm_tile_min(const bfm_i16& acc) {
+    int m = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 16; i++) m = min(m, (int)(((unsigned)acc[i] << 16) + (unsigned)((i & 3) + 8 * (i >> 2))));
+    return m;
+}
+/* the same for a tile that reaches past nc: base = index of the lane's first candidate */
+__device__ __forceinline__ int bfm_tile_min_edge(const bfm_i16& acc, int base, int nc) {
+    int m = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int off = (i & 3) + 8 * (i >> 2);
+        if (base + off < nc) m = min(m, (int)(((unsigned)acc[i] << 16) + (unsigned)off));
+    }
+    return m;
+}
+
+__global__ void __launch_bounds__(BFM_T, 2)   /* two wavefronts per SIMD: 256 registers, so the MFMAs take VGPR accumulators */
+k_bf_nn_mfma(const uint8_t* __restrict__ rows, const int32_t* __restrict__ rowCounts, const uint8_t* __restrict__ cols,
+             const int32_t* __restrict__ colCounts, size_t set_pitch, int max_n, unsigned long long* __restrict__ rbest, int plain) {
+    __shared__ __attribute__((aligned(16))) unsigned ex[8 * BFM_CH * 8];
+    const int p = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nr = min(rowCounts[p], max_n), nc = min(colCounts[p], max_n);
+    const int r0 = blockIdx.x * BFM_ROWS;
+    if (r0 >= nr) return;   /* block-uniform */
+    const int n = lane & 31, h = lane >> 5;
+    const int wr0 = r0 + wave * 64;
+    const bool wave_live = wr0 < nr;   /* a wavefront past the set still expands candidates */
+
+    /* the rows' +-1 fragments: lane (n, h) holds bits 32 s + 16 h .. + 15 of row g * 32 + n in b[g][s] */
+    bfm_i4 b[2][8];
+    int pop[2];
+#pragma unroll
+    for (int g = 0; g < 2; g++) {
+        const int r = wr0 + g * 32 + n;
+        unsigned w[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) w[s] = 0;
+        if (r < nr) {
+            const unsigned long long* rsrc = reinterpret_cast<const unsigned long long*>(rows + (size_t)p * set_pitch) + (size_t)r * 4;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const unsigned long long v = rsrc[j];
+                w[2 * j] = (unsigned)v; w[2 * j + 1] = (unsigned)(v >> 32);
+            }
+        }
+        int pc = 0;
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            pc += __popc(w[s]);
+            const unsigned hw = (w[s] >> (16 * h)) & 0xffffu;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const unsigned e = bfm_expand4(hw, j);
+                b[g][s][j] = (int)(((e << 8) - e) | 0x01010101u);   /* byte 1 -> 0xff, byte 0 -> 0x01 */
+            }
+        }
+        pop[g] = pc;
+    }
+
+    int best0 = 0x7fffffff, best1 = 0x7fffffff;
+    const unsigned long long* csrc = reinterpret_cast<const unsigned long long*>(cols + (size_t)p * set_pitch);
+    const int nchunks = (nc + BFM_CH - 1) / BFM_CH;
+    /* thread (ec, eq) expands words 4 eq .. 4 eq + 3 of candidate c0 + ec; the words of the next chunk are loaded a chunk ahead */
+    const int ec = tid & (BFM_CH - 1), eq = tid >> 7;
+    unsigned long long v0 = 0, v1 = 0;
+    if ((int)blockIdx.y < nchunks && (int)blockIdx.y * BFM_CH + ec < nc) {
+        const unsigned long long* src = csrc + (size_t)(blockIdx.y * BFM_CH + ec) * 4 + eq * 2;
+        v0 = src[0]; v1 = src[1];
+    }
+    for (int ch = blockIdx.y; ch < nchunks; ch += gridDim.y) {
+        const int c0 = ch * BFM_CH;
+        __syncthreads();   /* the last chunk's readers are done */
+        {
+            const int c = ec, q = eq;
+            const unsigned w4[4] = {(unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32)};
+            v0 = v1 = 0;
+            const int cnext = (ch + (int)gridDim.y) * BFM_CH + ec;   /* past nc after the last chunk */
+            if (cnext < nc) {
+                const unsigned long long* src = csrc + (size_t)cnext * 4 + eq * 2;
+                v0 = src[0]; v1 = src[1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                uint4* dst = reinterpret_cast<uint4*>(&ex[((4 * q + j) * BFM_CH + c) * 8]);
+                dst[0] = make_uint4(bfm_expand4(w4[j], 0), bfm_expand4(w4[j], 1), bfm_expand4(w4[j], 2), bfm_expand4(w4[j], 3));
+                dst[1] = make_uint4(bfm_expand4(w4[j], 4), bfm_expand4(w4[j], 5), bfm_expand4(w4[j], 6), bfm_expand4(w4[j], 7));
+            }
+        }
+        __syncthreads();
+        if (!wave_live) continue;   /* wavefront-uniform; the barriers above are met by every wavefront */
+        if (c0 + BFM_CH <= nc) {
+            /* a full chunk, unrolled: the keys and minimum of tile t - 1 (vector ALU, two registers of each accumulator per
+             * k-step) are issued under the MFMAs of tile t, which write the other pair of accumulators */
+            bfm_i16 acc[2][2];
+#pragma unroll
+            for (int t = 0; t <= BFM_CH / 32; t++) {
+                int m0 = 0x7fffffff, m1 = 0x7fffffff;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    if (t < BFM_CH / 32) {
+                        const bfm_i4 a = *reinterpret_cast<const bfm_i4*>(&ex[(s * BFM_CH + t * 32 + n) * 8 + h * 4]);
+                        if (s == 0) {
+#pragma unroll
+                            for (int i = 0; i < 16; i++) { acc[t & 1][0][i] = 0; acc[t & 1][1][i] = 0; }
+                        }
+                        acc[t & 1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[0][s], acc[t & 1][0], 0, 0, 0);
+                        acc[t & 1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[1][s], acc[t & 1][1], 0, 0, 0);
+                    }
+                    if (t > 0) {
+                        const bfm_i16 &p0 = acc[(t - 1) & 1][0], &p1 = acc[(t - 1) & 1][1];
+                        const int i = 2 * s, j = 2 * s + 1;
+                        const unsigned oi = (i & 3) + 8 * (i >> 2), oj = (j & 3) + 8 * (j >> 2);
+                        m0 = min(m0, min((int)(((unsigned)p0[i] << 16) + oi), (int)(((unsigned)p0[j] << 16) + oj)));
+                        m1 = min(m1, min((int)(((unsigned)p1[i] << 16) + oi), (int)(((unsigned)p1[j] << 16) + oj)));
+                    }
+                }
+                if (t > 0) {
+                    const int base = c0 + (t - 1) * 32 + 4 * h;
+                    best0 = min(best0, m0 + base);
+                    best1 = min(best1, m1 + base);
+                }
+            }
+            continue;
+        }
+        const int ntile = min(BFM_CH / 32, (nc - c0 + 31) >> 5);
+        for (int t = 0; t < ntile; t++) {
+            bfm_i16 acc0, acc1;
+#pragma unroll
+            for (int i = 0; i < 16; i++) { acc0[i] = 0; acc1[i] = 0; }
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                const bfm_i4 a = *reinterpret_cast<const bfm_i4*>(&ex[(s * BFM_CH + t * 32 + n) * 8 + h * 4]);
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[0][s], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[1][s], acc1, 0, 0, 0);
+            }
+            const int base = c0 + t * 32 + 4 * h;
+            if (c0 + t * 32 + 32 <= nc) {   /* wavefront-uniform */
+                best0 = min(best0, bfm_tile_min(acc0) + base);
+                best1 = min(best1, bfm_tile_min(acc1) + base);
+            } else {
+                const int m0 = bfm_tile_min_edge(acc0, base, nc), m1 = bfm_tile_min_edge(acc1, base, nc);
+                if (m0 != 0x7fffffff) best0 = min(best0, m0 + base);
+                if (m1 != 0x7fffffff) best1 = min(best1, m1 + base);
+            }
+        }
+    }
+
+    /* the two lane halves of a row saw different candidates */
+    best0 = min(best0, __shfl_xor(best0, 32));
+    best1 = min(best1, __shfl_xor(best1, 32));
+    if (h == 0) {
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            const int r = wr0 + g * 32 + n, k = g ? best1 : best0;
+            if (r >= nr) continue;
+            unsigned long long v = ~0ull;
+            if (k != 0x7fffffff) v = ((unsigned long long)(unsigned)((k >> 16) + pop[g]) << 32) | (unsigned)(k & 0xffff);
+            if (plain) rbest[(size_t)p * max_n + r] = v;
+            else if (k != 0x7fffffff) atomicMin(&rbest[(size_t)p * max_n + r], v);
+        }
+    }
 }
 
 /* cross-check: train t -> its nearest query q; qbest[q] = min(dist << 32 | t) */
@@ -107,18 +307,27 @@ int tbk_bf_batch(tb_ctx* ctx, int npairs, const uint8_t* d1, const int32_t* c1, 
                  int32_t* out_counts, unsigned long long* d_tbest, unsigned long long* d_qbest) {
     if (npairs <= 0 || max_n <= 0) return TB_OK;
     const size_t bytes = (size_t)npairs * max_n * sizeof(unsigned long long);
+    /* the matrix-core kernel unless the sets are narrower than a tile, the key's index field is too narrow, or the test hook
+     * (tb_debug_bf_scalar) asks for the scalar one. Candidate chunks side by side only while the row blocks alone leave
+     * compute units idle; with one split the kernel stores and its output needs no fill. */
+    const bool mfma = !ctx->dbg_bf_scalar && max_n >= BFM_MIN_N && max_n <= BFM_MAX_N;
+    const int tiles = (max_n + BFM_ROWS - 1) / BFM_ROWS, chunks = (max_n + BFM_CH - 1) / BFM_CH;
+    int split = 1;
+    while (split * 2 <= chunks && (long long)tiles * npairs * split < 2ll * ctx->num_cu) split *= 2;
+    const int plain = mfma && split == 1;
+    const dim3 grid((max_n + BF_T - 1) / BF_T, (max_n + BF_QC - 1) / BF_QC, npairs), mgrid(tiles, split, npairs);
+    /* rows = train (d2), cols = query (d1) with the cross-check; else rows = query, cols = train: qbest[q] = (dist, nearest
+     * train) directly */
+    const uint8_t *rows = crosscheck ? d2 : d1, *cols = crosscheck ? d1 : d2;
+    const int32_t *rc = crosscheck ? c2 : c1, *cc = crosscheck ? c1 : c2;
+    unsigned long long* rbest = crosscheck ? d_tbest : d_qbest;
     TB_HIP(ctx, hipMemsetAsync(d_qbest, 0xff, bytes, ctx->stream));
-    dim3 grid((max_n + BF_T - 1) / BF_T, (max_n + BF_QC - 1) / BF_QC, npairs);
-    if (crosscheck) {
-        TB_HIP(ctx, hipMemsetAsync(d_tbest, 0xff, bytes, ctx->stream));
-        /* rows = train (d2), cols = query (d1) */
-        TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d2, c2, d1, c1, set_pitch, max_n, d_tbest));
+    if (crosscheck && !plain) TB_HIP(ctx, hipMemsetAsync(d_tbest, 0xff, bytes, ctx->stream));
+    if (mfma) TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn_mfma, mgrid, dim3(BFM_T), 0, rows, rc, cols, cc, set_pitch, max_n, rbest, plain));
+    else TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, rows, rc, cols, cc, set_pitch, max_n, rbest));
+    if (crosscheck)
         TB_TRY(tb_launch(ctx, "k_bf_cross", k_bf_cross, dim3((max_n + BF_T - 1) / BF_T, npairs), dim3(BF_T), 0, c2, max_n, d_tbest,
                          d_qbest));
-    } else {
-        /* rows = query, cols = train: qbest[q] = (dist, nearest train) directly */
-        TB_TRY(tb_launch(ctx, "k_bf_nn", k_bf_nn, grid, dim3(BF_T), 0, d1, c1, d2, c2, set_pitch, max_n, d_qbest));
-    }
     TB_TRY(tb_launch(ctx, "k_bf_finalize", k_bf_finalize, dim3(npairs), dim3(BF_T), 0, c1, max_n, d_qbest, filter, ratio, min_th, out, cap,
                      out_counts));
     return TB_OK;

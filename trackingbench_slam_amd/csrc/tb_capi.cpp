@@ -222,6 +222,12 @@ int tb_debug_ba_plain_obs(tb_ctx* ctx, int on) {
     return TB_OK;
 }
 
+int tb_debug_bf_scalar(tb_ctx* ctx, int on) {
+    if (!ctx) return TB_EINVAL;
+    ctx->dbg_bf_scalar = on ? 1 : 0;
+    return TB_OK;
+}
+
 void tb_destroy(tb_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);

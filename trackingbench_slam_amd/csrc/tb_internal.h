@@ -46,6 +46,7 @@ struct tb_ctx {
     int peers = 1;      /* tb_set_concurrency: contexts expected to keep this GPU busy at the same time */
     int dbg_fast_dense = 0; /* tb_debug_force_dense_fast: every FAST block takes the any-density path (test hook) */
     int dbg_ba_plain_obs = 0; /* tb_debug_ba_plain_obs: the local-BA point passes walk the array-of-structs observations (test hook) */
+    int dbg_bf_scalar = 0; /* tb_debug_bf_scalar: searchByBF's nearest neighbours by the scalar kernel everywhere (test hook) */
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
