@@ -1,6 +1,7 @@
 /* Micro-benchmark: issue rate of the vector instructions the hot loops are made of (gfx950, per SIMD, 16 independent chains, four
  * wavefronts per SIMD). Result (profiles/r02n_ubench_int_ops.json): plain 32-bit integer / logic / shift instructions run at about
  * 1.7x the rate of packed 16-bit, 24-bit multiply-add, dot-product and 64-bit ones -- an "instruction" is not a unit of cost.
+ * The multiplies (v_mul_lo_u32, v_mul_hi_u32, v_mul_u32_u24, v_mad_u64_u32, v_mad_i64_i32): profiles/int_ops_mul.json.
  *   hipcc -O3 --offload-arch=gfx950 tools/ubench/int_ops.hip -o tools/ubench/int_ops && tools/ubench/int_ops */
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -45,6 +46,9 @@ __global__ void __launch_bounds__(256) k(unsigned long long* out, unsigned a32, 
             if (MODE == 27) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(v[i]) : "v"(a32));
             if (MODE == 28) asm volatile("v_sad_u8 %0, %0, %1, %1" : "+v"(v[i]) : "v"(a32));
             if (MODE == 29) asm volatile("v_mov_b32_dpp %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(v[i]) : "v"(a32));
+            if (MODE == 30) asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(v[i]) : "v"(a32));
+            if (MODE == 31) asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, %0" : "+v"(w[i]) : "v"(a32) : "vcc");
+            if (MODE == 32) asm volatile("v_mad_i64_i32 %0, vcc, %1, %1, %0" : "+v"(w[i]) : "v"(a32) : "vcc");
         }
     }
     unsigned long long s = 0;
@@ -71,12 +75,12 @@ int main() {
     const int blocks = 256 * 4;
     unsigned long long* d_out;
     (void)hipMalloc(&d_out, (size_t)blocks * 256 * sizeof(unsigned long long));
-    const char* names[30] = {"v_add_u32", "v_lshl_add_u64", "v_pk_minimum3_f16", "v_mad_u32_u24", "v_bitop3_b32", "v_pk_min_i16", "v_alignbyte_b32", "v_perm_b32", "v_dot4_u32_u8", "v_dot2_u32_u16", "v_bcnt_u32_b32", "v_xor_b32", "v_mul_u32_u24", "v_lshl_or_b32", "v_min3_u32", "v_min_u32", "v_and_or_b32", "v_lshl_add_u32", "v_add3_u32", "v_lshrrev_b32", "v_bfe_u32", "v_med3_i32", "v_mul_f32", "v_fma_f32", "v_rndne_f32", "v_cvt_i32_f32", "v_cndmask_b32", "v_mul_lo_u32", "v_sad_u8", "v_mov_b32_dpp"};
-    float t[30] = {run<0>(d_out, blocks), run<1>(d_out, blocks), run<2>(d_out, blocks), run<3>(d_out, blocks), run<4>(d_out, blocks), run<5>(d_out, blocks), run<6>(d_out, blocks), run<7>(d_out, blocks), run<8>(d_out, blocks), run<9>(d_out, blocks), run<10>(d_out, blocks), run<11>(d_out, blocks), run<12>(d_out, blocks), run<13>(d_out, blocks), run<14>(d_out, blocks), run<15>(d_out, blocks), run<16>(d_out, blocks), run<17>(d_out, blocks), run<18>(d_out, blocks), run<19>(d_out, blocks), run<20>(d_out, blocks), run<21>(d_out, blocks), run<22>(d_out, blocks), run<23>(d_out, blocks), run<24>(d_out, blocks), run<25>(d_out, blocks), run<26>(d_out, blocks), run<27>(d_out, blocks), run<28>(d_out, blocks), run<29>(d_out, blocks)};
+    const char* names[33] = {"v_add_u32", "v_lshl_add_u64", "v_pk_minimum3_f16", "v_mad_u32_u24", "v_bitop3_b32", "v_pk_min_i16", "v_alignbyte_b32", "v_perm_b32", "v_dot4_u32_u8", "v_dot2_u32_u16", "v_bcnt_u32_b32", "v_xor_b32", "v_mul_u32_u24", "v_lshl_or_b32", "v_min3_u32", "v_min_u32", "v_and_or_b32", "v_lshl_add_u32", "v_add3_u32", "v_lshrrev_b32", "v_bfe_u32", "v_med3_i32", "v_mul_f32", "v_fma_f32", "v_rndne_f32", "v_cvt_i32_f32", "v_cndmask_b32", "v_mul_lo_u32", "v_sad_u8", "v_mov_b32_dpp", "v_mul_hi_u32", "v_mad_u64_u32", "v_mad_i64_i32"};
+    float t[33] = {run<0>(d_out, blocks), run<1>(d_out, blocks), run<2>(d_out, blocks), run<3>(d_out, blocks), run<4>(d_out, blocks), run<5>(d_out, blocks), run<6>(d_out, blocks), run<7>(d_out, blocks), run<8>(d_out, blocks), run<9>(d_out, blocks), run<10>(d_out, blocks), run<11>(d_out, blocks), run<12>(d_out, blocks), run<13>(d_out, blocks), run<14>(d_out, blocks), run<15>(d_out, blocks), run<16>(d_out, blocks), run<17>(d_out, blocks), run<18>(d_out, blocks), run<19>(d_out, blocks), run<20>(d_out, blocks), run<21>(d_out, blocks), run<22>(d_out, blocks), run<23>(d_out, blocks), run<24>(d_out, blocks), run<25>(d_out, blocks), run<26>(d_out, blocks), run<27>(d_out, blocks), run<28>(d_out, blocks), run<29>(d_out, blocks), run<30>(d_out, blocks), run<31>(d_out, blocks), run<32>(d_out, blocks)};
     printf("{");
-    for (int i = 0; i < 30; i++) {
+    for (int i = 0; i < 33; i++) {
         const double winst = (double)N_IT * N_CH * blocks * 4;                 /* wave-instructions */
-        printf("\"%s\": %.0f%s", names[i], winst / 1024.0 / (t[i] * 1e3), i < 29 ? ", " : "");
+        printf("\"%s\": %.0f%s", names[i], winst / 1024.0 / (t[i] * 1e3), i < 32 ? ", " : "");
     }
     printf("}\n");   /* wave-instructions per SIMD per microsecond */
     return 0;
