@@ -13,7 +13,7 @@
  * 20-byte observation and the state -- ~150 FP64 operations against what used to be a 144-byte Hpl block per edge
  * and pass through HBM.
  *   A point pass    (thread per point)   chi2, Hll, bl; the point's record once lambda is final  -- after an accepted step
- *   B keyframe pass (block per KF chunk) Hpp, bp as fixed-shape tree reductions                  -- "
+ *   B keyframe pass (block per free KF)  Hpp, bp as fixed-shape tree reductions                  -- "
  *   C reduce        chunk partials -> Hpp, bp, chi2, lambda_0
  *   C2 records      (thread per point)   A = Hll + lambda I = C C^T, U = C^-T (A^-1 = U U^T), bl, X -- when A could not
  *   D Schur         S' = sum_l Z_l Z_l^T, Z_l = Hpl_l U_l, on the FP64 matrix cores (v_mfma_f64_16x16x4): every
@@ -35,10 +35,30 @@
 
 #define BA_T 256
 #ifndef BA_KFCH
-#define BA_KFCH 512           /* edges per keyframe-pass chunk: two per thread (four: 134 VGPRs, three wavefronts per SIMD, 0.48 against 0.44 ms per 171-window call; one: 0.67) */
+#define BA_KFCH 512           /* edges per keyframe-pass chunk: the unit of a workgroup's share and of the oPartKF slots */
 #endif
 #ifndef BA_KFBLK
-#define BA_KFBLK 4            /* workgroups per keyframe in the keyframe pass */
+#define BA_KFBLK 1            /* workgroups per keyframe in the keyframe pass, each with a contiguous run of the keyframe's chunks: the
+                                 whole list (1) 0.316 ms per 171-window call alone and 14.12 ms per 512-frame step, halves (2) 0.390
+                                 and 14.51; the chunk-per-workgroup form this replaced 0.432 and 14.89 (profiles/ba_kf_pass_ab.json) */
+#endif
+#ifndef BA_KFE
+#define BA_KFE 2              /* edges per thread and round of the keyframe pass (a thread's edges come in list order either way: the
+                                 value changes the schedule, not a bit of the sums). 2: 128 VGPRs; 1: 106 VGPRs, 0.309 against
+                                 0.316 ms alone and the same step time (14.19 against 14.17 in the same alternation) */
+#endif
+#ifndef BA_LIN_FUSE_ALL
+#define BA_LIN_FUSE_ALL 0     /* 1: batches of more than 32 windows run the point and keyframe passes in one launch as well.
+                                 Measured again with the pass at 9.6 KB of LDS: 0.761 against 0.316 + 0.490 ms alone, but 14.5-15.2
+                                 against 14.0-14.1 ms per step: two launches stay */
+#endif
+#ifndef BA_KF_AHEAD
+#define BA_KF_AHEAD 1         /* keyframe pass: the next round's points and the one after's records load while a round computes
+                                 (0: load, gather, compute per round: 0.333 against 0.316 ms alone) */
+#endif
+#ifndef BA_KF_POSE_ONCE
+#define BA_KF_POSE_ONCE 1     /* keyframe pass: one wavefront converts the keyframe's pose, the others read R|t from LDS (0: every
+                                 thread converts, as before: 0.419 against 0.316 ms alone) */
 #endif
 #define BA_BIG_MAXF 64        /* free keyframes of a large window (6 bits of the free-edge key) */
 #define BA_SMALL_MAXF 10      /* free keyframes of a window on the MFMA path (visibility patterns are 10-bit masks) */
@@ -156,6 +176,11 @@ __device__ __forceinline__ void ba_pose_to_Rt(const double* T7, double* Rt) {
     s.qx = T7[0]; s.qy = T7[1]; s.qz = T7[2]; s.qw = T7[3]; s.tx = T7[4]; s.ty = T7[5]; s.tz = T7[6];
     po_to_R(s, Rt);
     Rt[9] = s.tx; Rt[10] = s.ty; Rt[11] = s.tz;
+}
+/* a value every lane of the wavefront holds alike, moved to scalar registers (two v_readfirstlane_b32) */
+__device__ __forceinline__ double ba_uniform(double v) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
 }
 /* d(projection)/d(pose increment), 2 x 6, rows at J[0..5] and J[6..11] (g2o EdgeSE3ProjectXYZ convention) */
 __device__ __forceinline__ void ba_jac_pose_iz(const double* pc, double invz, double fx, double fy, double* J) {
@@ -548,13 +573,19 @@ __device__ __forceinline__ void ba_points_pass(const BaDims& d, const tb_ba_obs*
  * time ([value][lane], row stride 65 doubles: conflict-free both ways), four lanes per value add 16 partials each in lane
  * order, one lane adds the four quarter sums, and threads 0..26 add the four wavefronts' sums: ~110 LDS / add slots per
  * wavefront, every sum of fixed shape. sh: BA_KFR_LDS doubles. */
-#define BA_KFG 14  /* values per transpose round: 32 KB of LDS per workgroup. 7 (17 KB, four rounds) measured 0.85 against 0.78 ms per 256 windows alone and the same step time inside the pipeline */
-#define BA_KFR_LDS (4 * (BA_KFG * 65 + 64) + 4 * 27)
+#ifndef BA_KFG
+#define BA_KFG 4   /* values per transpose round: 9.6 KB of LDS per workgroup, seven rounds. The pass reduces once per workgroup
+                      now, not once per 512 edges, and the workgroup fits beside the FAST kernel's resident blocks, which leave
+                      ~10 KB of a CU free. 14 (32 KB, two rounds): 0.294 against 0.316 ms per 171-window call alone, but 212
+                      against 199 us per launch inside the step and 14.20 against 14.09 ms per step */
+#endif
+#define BA_KFW_LDS (BA_KFG * 65 + 4 * BA_KFG)     /* doubles per wavefront: transpose tile + quarter sums */
+#define BA_KFR_LDS (4 * BA_KFW_LDS + 4 * 27)
 __device__ __forceinline__ double ba_block_sum27(const double (&v)[27], double* sh) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    double* T = sh + wave * (BA_KFG * 65 + 64);   /* this wavefront's transpose tile */
+    double* T = sh + wave * BA_KFW_LDS;           /* this wavefront's transpose tile */
     double* Qs = T + BA_KFG * 65;                 /* its 4 BA_KFG quarter sums */
-    double* red = sh + 4 * (BA_KFG * 65 + 64);    /* [4][27] wavefront sums */
+    double* red = sh + 4 * BA_KFW_LDS;            /* [4][27] wavefront sums */
 #pragma unroll
     for (int g = 0; g < (27 + BA_KFG - 1) / BA_KFG; g++) {
         const int nv = min(BA_KFG, 27 - BA_KFG * g);
@@ -583,7 +614,7 @@ __device__ __forceinline__ double ba_block_sum27(const double (&v)[27], double* 
 
 __device__ __forceinline__ void ba_kf_pass(const BaDims& d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw,
                                            const BaState* __restrict__ states, const int* __restrict__ errflag, int bid) {
-    __shared__ double red[BA_KFR_LDS];
+    __shared__ double red[BA_KFR_LDS + 12];
     /* 1-D grid, a window per XCD at a time: workgroup ids go round-robin over the eight XCDs, so ids r, r + 8, r + 16, ... of a
      * run of 8 x (workgroups per window) ids serve ONE window -- all keyframes of a window gather from the same point array
      * (each touches most of its cache lines), which then comes from HBM once, into one L2, instead of once per keyframe */
@@ -592,43 +623,72 @@ __device__ __forceinline__ void ba_kf_pass(const BaDims& d, const tb_ba_obs* __r
     const int w = run * 8 + (rr_ & 7), slot = rr_ >> 3;
     if (w >= d.W) return;
     if (errflag[w]) return; /* rejected input: the point pass flags the window, but runs BESIDE this pass now */
-    const int chunk0 = slot % nx, kfree = slot / nx, kf = d.nfixed + kfree;
+    const int share = slot % nx, kfree = slot / nx, kf = d.nfixed + kfree;
     const BaState st = states[w];
     if (st.status || !st.need_lin) return;
     double* D = dw + (size_t)w * d.wstride;
     const int* I = iw + (size_t)w * d.istride;
     const int beg = I[d.oKfStart + kf], end = I[d.oKfStart + kf + 1];
+    /* The workgroup's share: a contiguous run [c0, c1) of the keyframe's occupied chunks, a function of the keyframe's edge
+     * count alone (so a window sums the same way alone and in any batch). Its threads carry their 27 sums in registers over
+     * the whole run -- thread t takes edges t, t + 256, t + 512, ... of the run in list order -- and the workgroup reduces ONCE:
+     * with a reduction per 512-edge chunk (one chunk per workgroup at the bench's ~2100 edges per keyframe) close to half of a
+     * wavefront's instructions were the pose conversion, the tree and its barriers, not edges. k_ba_reduce's contract stays:
+     * it adds a keyframe's occupied chunk slots in index order; the run's total goes to its first slot, exact zeros to the rest. */
+    const int nch = (end - beg + BA_KFCH - 1) / BA_KFCH, cps = (nch + nx - 1) / nx;
+    const int c0 = share * cps, c1 = min(c0 + cps, nch);
+    if (c0 >= c1) return;
+    const int eb = beg + c0 * BA_KFCH, ee = min(beg + c1 * BA_KFCH, end); /* the share's edges */
+    /* the keyframe's R|t: the first wavefront converts the quaternion, the others read the 12 doubles -- and every wavefront
+     * holds them in scalar registers (they are uniform), which is what leaves room for the double buffer below */
     double Tk[12];
+#if BA_KF_POSE_ONCE
+    double* sRt = red + BA_KFR_LDS;
+    if (tid < 64) {
+        ba_pose_to_Rt(D + d.oT + ((size_t)st.cur * d.nkf + kf) * 7, Tk);
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 12; i++) sRt[i] = Tk[i];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 12; i++) Tk[i] = ba_uniform(sRt[i]);
+#else
     ba_pose_to_Rt(D + d.oT + ((size_t)st.cur * d.nkf + kf) * 7, Tk);
+#pragma unroll
+    for (int i = 0; i < 12; i++) Tk[i] = ba_uniform(Tk[i]);
+#endif
     const double* P = D + d.oP + (size_t)st.cur * d.npt * 3;
     const double delta = (double)sqrtf(5.991f);
-    /* BA_KFBLK blocks per keyframe walk its chunks; k_ba_reduce sums the occupied chunks in order */
-    for (int chunk = chunk0; chunk * BA_KFCH < end - beg; chunk += BA_KFBLK) {
-        double acc[27];
+    const int4* KR = reinterpret_cast<const int4*>(I + d.oKfRec);
+    const int nr = (ee - eb + BA_KFE * BA_T - 1) / (BA_KFE * BA_T);
+    /* the keyframe-ordered 16-byte records of a round's edges (written by the setup kernel: coalesced, no edge-id ->
+     * observation gather). Lanes past the share -- the tail round's, and the look-ahead past the last round -- read the
+     * share's last record, one cache line for all of them, and are marked: no branch in the loop, nothing out of bounds */
+    auto load_rec = [&](int r, int4 (&rec)[BA_KFE]) {
 #pragma unroll
-        for (int i = 0; i < 27; i++) acc[i] = 0;
-        /* two rounds of independent loads, each in flight together: the keyframe-ordered 16-byte records of the chunk's edges
-         * (written by the setup kernel: coalesced, no edge-id -> observation gather), then their points. A load-use-load
-         * chain per edge would be one memory latency per edge and round; the pass is bound by exactly these latencies, most
-         * of all inside the pipeline where the extractor's kernels load the memory system. */
-        int4 rr[BA_KFCH / BA_T];
-        double XX[BA_KFCH / BA_T][3];
-        const int4* KR = reinterpret_cast<const int4*>(I + d.oKfRec);
-#pragma unroll
-        for (int j = 0; j < BA_KFCH / BA_T; j++) {
-            const int idx = beg + chunk * BA_KFCH + j * BA_T + tid;
-            rr[j] = KR[min(idx, end - 1)];
-            if (idx >= end) rr[j].x = -1;
+        for (int j = 0; j < BA_KFE; j++) {
+            const int idx = eb + (r * BA_KFE + j) * BA_T + tid;
+            rec[j] = KR[min(idx, ee - 1)];
+            if (idx >= ee) rec[j].x = -1;
         }
+    };
+    auto gather = [&](const int4 (&rec)[BA_KFE], double (&X)[BA_KFE][3]) {
 #pragma unroll
-        for (int j = 0; j < BA_KFCH / BA_T; j++) {
-            const int p = min(max(rr[j].x, 0), d.npt - 1);
-            XX[j][0] = P[3 * p]; XX[j][1] = P[3 * p + 1]; XX[j][2] = P[3 * p + 2];
+        for (int j = 0; j < BA_KFE; j++) {
+            const int p = min(max(rec[j].x, 0), d.npt - 1);
+            X[j][0] = P[3 * p]; X[j][1] = P[3 * p + 1]; X[j][2] = P[3 * p + 2];
         }
+    };
+    double acc[27];
 #pragma unroll
-        for (int j = 0; j < BA_KFCH / BA_T; j++) {
-            if (rr[j].x < 0) continue;
-            const float ou = __int_as_float(rr[j].y), ov = __int_as_float(rr[j].z), ow = __int_as_float(rr[j].w);
+    for (int i = 0; i < 27; i++) acc[i] = 0;
+    auto edges = [&](const int4 (&rec)[BA_KFE], const double (&XX)[BA_KFE][3]) {
+#pragma unroll
+        for (int j = 0; j < BA_KFE; j++) {
+            if (rec[j].x < 0) continue;
+            const float ou = __int_as_float(rec[j].y), ov = __int_as_float(rec[j].z), ow = __int_as_float(rec[j].w);
             const double* X = XX[j];
             double Jp[12];
             BaLin L; /* residual and Huber weight exactly as the point pass computes them (same helper): cheaper than a
@@ -647,8 +707,43 @@ __device__ __forceinline__ void ba_kf_pass(const BaDims& d, const tb_ba_obs* __r
                 }
             }
         }
-        const double tot = ba_block_sum27(acc, red);
-        if (tid < 27) D[d.oPartKF + ((size_t)kfree * d.kfChunks + chunk) * 27 + tid] = tot;
+    };
+#if BA_KF_AHEAD
+    /* Register double buffer over the chain record -> point -> arithmetic: while round r's arithmetic runs, round r + 1's
+     * points (their records arrived during round r - 1) and round r + 2's records are in flight. A load-use-load chain per
+     * round was one memory latency per load step, paid by every workgroup; the pass is bound by exactly these latencies,
+     * most of all inside the pipeline where the extractor's kernels load the memory system. */
+    int4 ra[BA_KFE], rb[BA_KFE];
+    double Xa[BA_KFE][3];
+    load_rec(0, ra);
+    load_rec(1, rb);
+    gather(ra, Xa);
+    for (int r = 0; r < nr; r++) {
+        int4 rc[BA_KFE];
+        double Xb[BA_KFE][3];
+        gather(rb, Xb);
+        load_rec(r + 2, rc);
+        edges(ra, Xa);
+#pragma unroll
+        for (int j = 0; j < BA_KFE; j++) {
+            ra[j] = rb[j]; rb[j] = rc[j];
+            Xa[j][0] = Xb[j][0]; Xa[j][1] = Xb[j][1]; Xa[j][2] = Xb[j][2];
+        }
+    }
+#else
+    for (int r = 0; r < nr; r++) {
+        int4 ra[BA_KFE];
+        double Xa[BA_KFE][3];
+        load_rec(r, ra);
+        gather(ra, Xa);
+        edges(ra, Xa);
+    }
+#endif
+    const double tot = ba_block_sum27(acc, red);
+    if (tid < 27) {
+        double* out = D + d.oPartKF + ((size_t)kfree * d.kfChunks + c0) * 27 + tid;
+        out[0] = tot;
+        for (int ch = 1; ch < c1 - c0; ch++) out[ch * 27] = 0.0;
     }
 }
 
@@ -659,7 +754,8 @@ k_ba_points(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__
             const int* __restrict__ errflag) {
     ba_points_pass<STREAM>(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x, (int)blockIdx.y);
 }
-__global__ void __launch_bounds__(BA_T)
+/* four wavefronts per SIMD asked for: the double-buffered pass compiles to 130 registers without the bound, 128 (no spill) with it */
+__global__ void __launch_bounds__(BA_T, 4)
 k_ba_kf(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw, const BaState* __restrict__ states,
         const int* __restrict__ errflag) {
     ba_kf_pass(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x);
@@ -667,11 +763,12 @@ k_ba_kf(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw,
 /* ---- A + B in one launch, for small batches (the replayed graph): the point pass and the keyframe pass are independent of each
  * other (both read the state, each writes its own partials), so a batch that fills a fraction of the GPU runs them side by
  * side and saves a launch per trial (the 8-frame BA call 1.02 -> 0.97 ms). The keyframe pass's workgroups come first (ids
- * 0 ..: their window-per-XCD order needs id mod 8), then the point pass's. Large batches keep two launches: the fused kernel
- * carries the keyframe pass's 32 KB of LDS in every workgroup, and the point pass's workgroups are meant to sit on CUs beside
- * the extractor's, which leave ~10 KB free (measured inside the pipeline: 17.6 against 16.6-17.0 ms per 512-frame step). */
+ * 0 ..: their window-per-XCD order needs id mod 8), then the point pass's. Large batches keep two launches: measured inside the
+ * pipeline, the fused launch cost 17.6 against 16.6-17.0 ms per 512-frame step when the keyframe pass carried 32 KB of LDS into
+ * every workgroup, and still 14.5-15.2 against 14.0-14.1 now that it carries 9.6 KB (BA_LIN_FUSE_ALL) -- the point pass's
+ * workgroups then also take the keyframe pass's 128 registers. */
 template <bool STREAM>
-__global__ void __launch_bounds__(BA_T)
+__global__ void __launch_bounds__(BA_T, 4)
 k_ba_lin(BaDims d, const tb_ba_obs* __restrict__ obsAll, double* __restrict__ dw, const int* __restrict__ iw, BaState* __restrict__ states,
          const int* __restrict__ errflag, int nKfBlocks) {
     if ((int)blockIdx.x < nKfBlocks) ba_kf_pass(d, obsAll, dw, iw, states, errflag, (int)blockIdx.x);
@@ -2707,7 +2804,7 @@ static int ba_enqueue_round(tb_ctx* ctx, const BaPlan& p, int round) {
     const BaDims& d = p.d;
     const int W = d.W;
     const int nKfBlocks = ((W + 7) / 8) * 8 * std::min(BA_KFBLK, d.kfChunks) * d.nfree;
-    if (W <= 32) {
+    if (W <= 32 || BA_LIN_FUSE_ALL) {
         TB_TRY(tb_launch(ctx, "k_ba_lin", p.lin, dim3(nKfBlocks + d.nblkP * W), dim3(BA_T), p.pass_lds, d, p.obs, p.dw, p.iw, p.states, p.errflag,
                          nKfBlocks));
     } else {
