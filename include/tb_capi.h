@@ -471,6 +471,44 @@ struct tb_pnp_params;   /* below, with tb_pnp_ransac_batch_dev */
 int tb_kf_store_pnp_enable(tb_kf_store* st, const struct tb_pnp_params* params, int min_consensus, int expand);
 int tb_kf_store_pnp_state_dev(tb_kf_store* st, const tb_obs** rows, const int32_t** row_counts, const int32_t** consensus,
                               const int32_t** winner, const float** Tcw, const uint8_t** took, const int32_t** flags);
+/* A similarity transform between the query frame's own map and each candidate's stored map: a separate query after a
+ * tb_relocalize_batch_dev, whose match lists (tb_kf_store_work_dev's matches / match_counts per pair c = s * ncand + r) it reads.
+ * It changes no existing signature, struct or buffer: a store that never calls it launches what it launched before. The pose
+ * stage above measures the camera against the stored map, an SE(3) that cannot see scale; this one relates the two maps, which
+ * is what a loop closure on a drifted map needs (tests/reloc_sim3_reference.py restates rows and select on the CPU). The query
+ * frame brings its keys q_keys [nseq][q_pitch] with q_counts, its map points q_map_points [nseq][q_pitch][3] (world) with
+ * q_mp_valid [nseq][q_pitch] and its pose q_Tcw [nseq][16]; cand_slot [nseq][ncand] as tb_relocalize_batch_dev took it.
+ *   rows    one workgroup per pair, by the rows stage's rule: a match counts where the stored entry trainIdx AND the query key
+ *           queryIdx both have a valid map point, the last match in list order wins a key, rows in key order. X1 = q_Tcw[s]
+ *           applied to the query key's world point, X2 = the stored keyframe's Tcw applied to its stored world point, both in
+ *           float64 (((T0 X + T1 Y) + T2 Z) + T3) and stored as float32; inv_sigma2_1 / _2 = invLevelSigma2[octave] of the two
+ *           keys as tb_scale_factors(nlevels, scale) gives it. No candidate: no rows
+ *   sim3    tb_sim3_ransac_batch_dev's kernel on the nseq * ncand problems
+ *   select  per sequence the candidate with the largest consensus, ties to the lower rank (candidates that are absent never
+ *           win); best_rank[s] = its rank if its consensus >= min_consensus, else -1; best_kf[s] its kf_id or -1; best_S12 /
+ *           best_srt its transform, or the identity and scale 1 when -1
+ * tb_sim3_out (every pointer nullable, device): cand_rows / cand_consensus / cand_flags [nseq][ncand], cand_S12
+ * [nseq][ncand][16] float, cand_srt [nseq][ncand][8] double, best_rank / best_kf [nseq], best_S12 [nseq][16], best_srt [nseq][8].
+ * min_consensus is the caller's: ORB-SLAM's loop closing asks for 20, the reference has no figure. The rows, their masks and the
+ * per-pair outputs a caller does not take live in buffers the store allocates ON THE FIRST CALL, sized for nseq * max_candidates
+ * pairs: the first call may allocate, later ones do not. No host synchronisation and no host <-> device copy otherwise.
+ * TB_ESTATE: no verification has filled the match lists yet. TB_EINVAL: as tb_sim3_ransac_batch_dev, null inputs, ncand outside
+ * 1..max_candidates or not the last verification's, q_pitch < 1 or larger than the store's, nlevels outside 1..16, min_consensus < 0.
+ * tb_kf_store_sim3_state_dev lends device views of the last call's rows [pairs][pitch], row_counts [pairs] and masks
+ * [pairs][pitch] (each nullable). TB_ESTATE before the first tb_kf_store_sim3_dev. */
+struct tb_sim3_params;   /* below, with tb_sim3_ransac_batch_dev */
+typedef struct tb_sim3_out {
+    int32_t *cand_rows, *cand_consensus, *cand_flags;
+    float* cand_S12;
+    double* cand_srt;
+    int32_t *best_rank, *best_kf;
+    float* best_S12;
+    double* best_srt;
+} tb_sim3_out;
+int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts,
+                         const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch, const float* q_Tcw, const int32_t* cand_slot,
+                         int ncand, const struct tb_sim3_params* params, int min_consensus, const tb_sim3_out* out);
+int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const int32_t** row_counts, const uint8_t** inlier);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -621,6 +659,69 @@ int tb_pnp_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const
                             int32_t* winner, int32_t* flags);
 int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, const tb_pnp_params* params, const float* Tcw_prior,
                   float Tcw_out[16], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags);
+/* A similarity transform from 3D-3D rows: Horn's closed form (Horn 1987, unit quaternions) inside a RANSAC, with a least-squares
+ * refit; batched and device-resident. The reference has no such step; ORB-SLAM runs one (Sim3Solver) between the bag-of-words
+ * loop candidate and the pose-graph correction, which is what this is for (DESIGN.md 9n has the derivation;
+ * tests/sim3_reference.py is the definition, statement for statement, and the kernel matches it bit for bit).
+ * Problem p reads counts[p] rows tb_sim3_row (X1 Y1 Z1, X2 Y2 Z2, inv_sigma2_1, inv_sigma2_2: the same physical point in
+ * camera-1 and in camera-2 coordinates with the two keys' invLevelSigma2) at rows + p * pitch; a count is clamped to [0, pitch].
+ * K = fx, fy, cx, cy (host) serves both cameras. A row's observation in image i is the projection of its own point Xi, as in
+ * ORB-SLAM's solver: no pixel goes into the record. The transform sought is X1 = s R12 X2 + t12. float64 with + - * / sqrt fabs
+ * and comparisons only, one operation per statement, fixed loop counts.
+ *   sampling  tb_pnp_ransac_batch_dev's rule, unchanged: draw k of hypothesis h is mix(seed + (8 h + k + 1) * 0x9E3779B97F4A7C15)
+ *             (splitmix64's output function); its high 32 bits times n, shifted right by 32, is a row. Draws are taken until
+ *             three distinct rows are found or 8 are used up; a hypothesis that runs out is void. The sample depends on
+ *             (seed, h, n) only, never on p: a problem gives the same bits alone and inside any batch
+ *   solver    the sums S1, S2 of the m = 3 points of each set (a sum over a sample is ((0 + v0) + v1) + v2) and the centroids
+ *             O = S / m; the centred points Pr = X - O; M[i][j] = sum Pr2[i] Pr1[j]; Horn's symmetric 4 x 4
+ *             N = (M00+M11+M22, M12-M21, M20-M02, M01-M10; ., M00-M11-M22, M01+M10, M20+M02; ., ., M11-M00-M22, M12+M21;
+ *             ., ., ., M22-M00-M11); 5 cyclic Jacobi sweeps in the pair order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) with the
+ *             triangulation's rotation (tb_linear_triangle_batch_dev), no convergence test; the eigenvector v_k at the largest
+ *             diagonal entry lam_k, the lowest index on a tie, is corrected once to first order from its residual
+ *             r = N v_k - lam_k v_k against the N the sweeps started from: v_k + sum_(i != k) (v_i . r) / (lam_k - lam_i) v_i,
+ *             a term left out where its denominator is 0. Every product and partial sum of r is carried with its rounding
+ *             error (Dekker's product with the splitter 2^27 + 1, Knuth's sum: + - * only) and rounded once at the end, which
+ *             is what lets the result agree with LAPACK's to 1e-12 where two eigenvalues lie 1e-5 of the largest apart.
+ *             Negated where w < 0, it is the unit quaternion w x y z of R12;
+ *             R12 = (1-2(yy+zz), 2(xy-wz), 2(xz+wy); 2(xy+wz), 1-2(xx+zz), 2(yz-wx); 2(xz-wy), 2(yz+wx), 1-2(xx+yy));
+ *             P3 = R12 Pr2; s = sum(Pr1 . P3) / sum(P3 . P3), or exactly 1.0 with fixed_scale; t12 = O1 - s (R12 O2). The inverse
+ *             is R21 = R12', s21 = 1 / s, t21 = -(R12' t12) / s
+ *   void      a sample is void, never a NaN result, when it has a non-finite coordinate, a point whose own Z is not above 0, two
+ *             edge vectors a, b in either set with |a x b|^2 <= 1e-6 |a|^2 |b|^2 (coincident or collinear: the sine of the
+ *             angle is below 1e-3, where the two largest eigenvalues of N meet and the rotation about the line is free), or
+ *             an s that is not finite or not above 0 (or a t12, s21 or t21 that is not finite)
+ *   score     every hypothesis against all n rows: Q1 = (s R12) X2 + t12 and Q2 = (s21 R21) X1 + t21; a row is an inlier iff
+ *             the four depths Z1, Z2, Q1z, Q2z are above 0 and |proj(Q1) - proj(X1)|^2 * inv_sigma2_1 <= chi2_max and
+ *             |proj(Q2) - proj(X2)|^2 * inv_sigma2_2 <= chi2_max (proj(X) = (fx (X / Z) + cx, fy (Y / Z) + cy)). The winner has
+ *             the most inliers, ties to the lower hypothesis. Counts are integer sums; there is no floating-point atomic anywhere
+ *   refit     the solver's statements once more on all m consensus rows of the winner, centroids first, then the centred sums,
+ *             then the scale's two sums (no raw moments). A sum over the rows: row i belongs to thread i mod 256, a thread adds
+ *             its rows t, t + 256, ... in ascending order to 0.0, and the 256 partial sums meet in the butterfly
+ *             p[t] = p[t] + p[t ^ d], d = 1, 2, 4, ..., 128. The refitted transform is rescored; it replaces the hypothesis iff
+ *             it is not void and its consensus is not smaller: then the mask and the count are the refit's and winner[1] = 1.
+ *             Fewer than 3 consensus rows, or a void refit, keep the hypothesis and give winner[1] = 0
+ *   void problem   n < 3, or no hypothesis with a solution: consensus 0, winner (-2, 0), the identity and scale 1, an all-zero
+ *             mask, flags bit 0 set
+ * Out (device, each nullable): S12 [nproblems][16] float (the float32 rounding of [s R12 | t12; 0 0 0 1]); srt [nproblems][8]
+ * double (the unit quaternion w x y z, t12, s: the FP64 form tb_pg_edge uses, so that a Sim(3) graph can take it without a
+ * float32 detour); consensus [nproblems]; inlier [nproblems][pitch] bytes (zero beyond the count); winner [nproblems][2]
+ * (hypothesis, refitted); flags [nproblems]. Asynchronous on the context's stream, no host synchronisation, no host <-> device
+ * copy, no work buffer: one launch of one 256-thread workgroup per problem whose state is registers and LDS. At most 65535
+ * problems per call (TB_EUNSUPPORTED). TB_EINVAL: null rows / counts / K / params, pitch < 1, hypotheses outside 1..1024,
+ * fixed_scale not 0 or 1, chi2_max negative or not finite, fx or fy not positive.
+ * tb_sim3_ransac: the host form, one problem of n rows on the batched entry (host pointers; inlier [n]; S12 [16]; srt [8]). */
+typedef struct tb_sim3_params {
+    int hypotheses;      /* 1..1024; 256 */
+    int fixed_scale;     /* 0 | 1; a stereo map has a metric scale: 1 */
+    double chi2_max;     /* 9.210: chi-square, 2 degrees of freedom, 99 %, ORB-SLAM's Sim3Solver threshold. A default, not a
+                            measurement */
+    uint64_t seed;
+} tb_sim3_params;
+int tb_sim3_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_row* rows, const int32_t* counts, int pitch,
+                             const tb_sim3_params* params, float* S12, double* srt, int32_t* consensus, uint8_t* inlier, int32_t* winner,
+                             int32_t* flags);
+int tb_sim3_ransac(tb_ctx* ctx, const double K[4], const tb_sim3_row* rows, int n, const tb_sim3_params* params, float S12[16],
+                   double srt[8], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags);
 /* A relative pose and first points from 2D-2D rows alone: 8-point hypotheses in a RANSAC, a least-squares refit, the four
  * decompositions of E told apart by triangulation; batched and device-resident. The reference has no such step (its
  * LinearTriangle is handed poses); this is ORB-SLAM's Initializer on its fundamental-matrix branch (DESIGN.md 9m has the
@@ -1067,6 +1168,15 @@ int tb_vo_reloc_enable(tb_vo* vo, int max_candidates);
 int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inliers, double* scores, int32_t* top_slot, int32_t* top_kf,
                          double* top_score, int32_t* top_count, const tb_reloc_out* out);
 int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
+/* tb_vo_relocalize_sim3_dev is a query after tb_vo_relocalize_dev: tb_kf_store_sim3_dev with the loop's own current ORB keys, its
+ * carried map_points / mp_valid (tb_vo_state_dev's), its Tcw and the top_slot / topk of the last tb_vo_relocalize_dev. It changes
+ * no state tensor and makes no host synchronisation and no host <-> device copy (the store's first Sim(3) call may allocate); it
+ * works whether or not recovery, loop correction or the PnP verification are on, because it only reads. TB_ESTATE: relocalisation
+ * not enabled, before the first step, or no tb_vo_relocalize_dev since the last step. topk sizes the outputs ([nseq][topk]) and
+ * must be the topk of that tb_vo_relocalize_dev: anything else is TB_EINVAL and nothing is written. tb_vo_relocalize_dev keeps a
+ * device copy of a top_slot the caller took, so that buffer need not outlive the call. */
+struct tb_sim3_params;
+int tb_vo_relocalize_sim3_dev(tb_vo* vo, int topk, const struct tb_sim3_params* params, int min_consensus, const tb_sim3_out* out);
 /* tb_kf_store_pnp_enable on the loop's store: tb_vo_relocalize_dev then runs the PnP verification (tb_kf_store_pnp_state_dev on
  * tb_vo_kf_store_get's store lends its per-pair outputs) and stays a query that changes no state tensor. TB_ESTATE: relocalisation
  * not enabled, after the first step, enabled already, or together with tb_vo_recover_enable / tb_vo_loop_enable in either order:

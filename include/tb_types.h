@@ -46,6 +46,15 @@ typedef struct tb_obs {
     float inv_sigma2;
 } tb_obs;
 
+/* One 3D-3D row of the Sim(3) solver (tb_sim3_ransac_batch_dev), 32 bytes: the same physical point in camera-1 coordinates and
+ * in camera-2 coordinates, with the invLevelSigma2 of the two keys that observe it. No pixel is stored: a row's observation in
+ * image i is the projection of its own point Xi. */
+typedef struct tb_sim3_row {
+    float X1, Y1, Z1;
+    float X2, Y2, Z2;
+    float inv_sigma2_1, inv_sigma2_2;
+} tb_sim3_row;
+
 /* Pinhole camera as the projection matchers use it (reference PinholeCamera, CameraModel.cpp:63-93 and
  * CameraModel.h:33-39): focal lengths, principal point, image size for IsInFrame, and the radial-tangential
  * coefficients d[0..4] (k1 k2 p1 p2 k3) applied iff has_distortion. */

@@ -1,0 +1,206 @@
+"""GPU tests of tb_sim3_ransac_batch_dev / tb_sim3_ransac against the definition in tests/sim3_reference.py on the constructed
+problems of tests/sim3_cases.py. Winner, consensus, inlier mask and flags exact, srt bit for bit, S12 bit for bit the float32
+rounding of the reference's float64 matrix; every case's closest gated quantity to chi2_max, under its winning hypothesis and
+under its final transform, is checked to lie farther than 1e-9 relative, so that the exactness means something. Pitch 320 = one
+LDS chunk (256 rows) and a quarter."""
+import numpy as np
+import pytest
+import torch
+
+from trackingbench_slam_amd import capi
+
+import sim3_cases as sc
+import sim3_reference as sr
+
+pytestmark = pytest.mark.gpu
+
+PITCH = 320
+SEED = 5
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(0)
+    yield c
+    c.close()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _rows_dev(rows):
+    P, pitch = rows.shape
+    return torch.from_numpy(rows.view(np.float32).reshape(P, pitch, 8).copy()).cuda()
+
+
+def _run(ctx, rows, counts, hypotheses=256, fixed_scale=False, chi2_max=sr.CHI2_MAX, seed=SEED):
+    """the batched entry on rows [P][pitch] -> dict of host arrays; outputs pre-filled so that an unwritten entry shows"""
+    P, pitch = rows.shape
+    d_rows, d_cnt = _rows_dev(rows), _dev(np.asarray(counts, np.int32))
+    S = torch.full((P, 16), -7.0, dtype=torch.float32, device="cuda")
+    srt = torch.full((P, 8), -7.0, dtype=torch.float64, device="cuda")
+    cons = torch.full((P,), -9, dtype=torch.int32, device="cuda")
+    inl = torch.full((P, pitch), 99, dtype=torch.uint8, device="cuda")
+    win = torch.full((P, 2), -9, dtype=torch.int32, device="cuda")
+    flags = torch.full((P,), -9, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.check(ctx.sim3_ransac_dev(P, sc.K, d_rows.data_ptr(), d_cnt.data_ptr(), pitch, S.data_ptr(), srt.data_ptr(), cons.data_ptr(),
+                                  inl.data_ptr(), win.data_ptr(), flags.data_ptr(), hypotheses=hypotheses, fixed_scale=fixed_scale,
+                                  chi2_max=chi2_max, seed=seed))
+    ctx.synchronize()
+    return dict(S12=S.cpu().numpy().reshape(P, 4, 4), srt=srt.cpu().numpy(), consensus=cons.cpu().numpy(), inlier=inl.cpu().numpy(),
+                winner=win.cpu().numpy(), flags=flags.cpu().numpy())
+
+
+def _check(got, refs, chi2_max=sr.CHI2_MAX):
+    for p, r in enumerate(refs):
+        tag = "problem %d" % p
+        assert tuple(got["winner"][p]) == r["winner"], tag
+        assert got["consensus"][p] == r["consensus"] and got["flags"][p] == r["flags"], tag
+        assert np.array_equal(got["inlier"][p], r["inlier"]), tag
+        assert np.array_equal(got["srt"][p].view(np.uint64), r["srt"].view(np.uint64)), tag
+        assert np.array_equal(got["S12"][p].view(np.uint32), r["S1232"].view(np.uint32)), tag
+        assert sr.margin(r, chi2_max) > 1e-9, tag
+
+
+@pytest.fixture(scope="module")
+def batch_a():
+    """row counts around every boundary, then the row contents; (rows [P][PITCH], counts, names)"""
+    items = []
+    for i, n in enumerate((2, 3, 4, 64, 65, sc.CHUNK - 1, sc.CHUNK, sc.CHUNK + 1, PITCH)):
+        items.append(("n%d" % n, sc.problem(100 + i, n, PITCH)[0], n))
+    items.insert(5, ("empty", sc.problem(99, 50, PITCH)[0], 0))                      # a zero count in the middle of the batch
+    items.append(("above", sc.problem(120, PITCH, PITCH)[0], PITCH + 80))            # a count above the pitch is clamped
+    items.append(("negative", sc.problem(121, 40, PITCH)[0], -3))
+    items.append(("outliers", sc.problem(122, 200, PITCH, outliers=1.0)[0], 200))
+    items.append(("collinear", sc.problem(123, 200, PITCH, outliers=0.0, noise=0.0, kind="collinear")[0], 200))
+    same = sc.problem(127, 1, PITCH, outliers=0.0)[0]
+    same[:40] = same[0]
+    items.append(("coincident", same, 40))                                           # forty copies of one row: every sample coincident
+    nan = sc.problem(125, 200, PITCH, outliers=0.3)[0]
+    nan["X1"][7] = np.nan
+    nan["Z2"][11] = np.inf
+    nan["inv_sigma2_2"][13] = np.nan
+    nan["Y2"][17] = -np.inf
+    nan["Z1"][19] = -nan["Z1"][19]
+    items.append(("nan", nan, 200))
+    items.append(("octaves", sc.problem(126, 200, PITCH, octaves=True)[0], 200))
+    items.append(("clean", sc.problem(128, 300, PITCH, outliers=0.0, noise=0.0)[0], 300))
+    rows = np.stack([it[1] for it in items])
+    counts = np.array([it[2] for it in items], np.int32)
+    return rows, counts, [it[0] for it in items]
+
+
+@pytest.fixture(scope="module")
+def ref_a(batch_a):
+    rows, counts, _ = batch_a
+    return sr.ransac_batch(sc.K, rows, counts, hypotheses=256, seed=SEED)
+
+
+def test_batch_matches_the_definition(ctx, batch_a, ref_a):
+    rows, counts, names = batch_a
+    got = _run(ctx, rows, counts)
+    _check(got, ref_a)
+    by = dict(zip(names, range(len(names))))
+    for void in ("n2", "empty", "negative", "coincident", "collinear"):
+        p = by[void]
+        assert got["flags"][p] == 1 and tuple(got["winner"][p]) == (-2, 0) and got["consensus"][p] == 0 and not got["inlier"][p].any(), void
+        assert np.array_equal(got["S12"][p], np.eye(4, dtype=np.float32)) and np.array_equal(got["srt"][p], [1, 0, 0, 0, 0, 0, 0, 1]), void
+    for p, n in enumerate(counts):   # nothing is marked beyond a count
+        assert not got["inlier"][p, max(min(int(n), PITCH), 0):].any()
+    for found in ("n64", "n65", "n%d" % (sc.CHUNK - 1), "n%d" % sc.CHUNK, "n%d" % (sc.CHUNK + 1), "n%d" % PITCH, "above", "octaves", "nan"):
+        p = by[found]
+        n = min(int(counts[p]), PITCH)
+        assert got["consensus"][p] >= 0.25 * n, found      # at least half of the good rows: the transform was found
+        assert got["winner"][p, 0] >= 0 and abs(got["srt"][p, 7] / sc.S_TRUE - 1.0) < 0.01, found
+    assert got["consensus"][by["clean"]] == 300 and got["winner"][by["clean"], 1] == 1
+    assert got["consensus"][by["outliers"]] < 12
+    assert not got["inlier"][by["nan"]][[7, 11, 13, 17, 19]].any() and np.isfinite(got["srt"]).all() and np.isfinite(got["S12"]).all()
+    assert {int(w) for w in got["winner"][:, 1]} == {0, 1}     # refitted and not refitted both occur
+
+
+@pytest.mark.parametrize("hyp", [1, 256, 1024])
+@pytest.mark.parametrize("fixed", [False, True])
+def test_hypothesis_counts_and_fixed_scale(ctx, hyp, fixed):
+    """one hypothesis, one per thread, four per thread; the scale free and fixed (on rows whose true scale is 1)"""
+    T = sc.truth(s=1.0) if fixed else None
+    ns = (100, sc.CHUNK + 1, PITCH)
+    items = [sc.problem(200 + i, n, PITCH, outliers=0.0 if hyp == 1 else 0.5, T=T) for i, n in enumerate(ns)]
+    rows, counts = np.stack([it[0] for it in items]), np.array(ns, np.int32)
+    ref = sr.ransac_batch(sc.K, rows, counts, hypotheses=hyp, fixed_scale=fixed, seed=SEED + hyp)
+    got = _run(ctx, rows, counts, hypotheses=hyp, fixed_scale=fixed, seed=SEED + hyp)
+    _check(got, ref)
+    assert (got["flags"] == 0).all() and (got["consensus"] >= 0.4 * counts).all()
+    if fixed:
+        assert (got["srt"][:, 7] == 1.0).all()
+
+
+def test_a_threads_later_hypothesis_wins(ctx):
+    """120 rows with 18 good ones and 1024 hypotheses: the reference's winner is beyond the first 256, a thread's second or later"""
+    rows = sc.problem(203, 120, PITCH, outliers=0.85)[0][None]
+    seed = next(s for s in range(300, 340) if sr.ransac(sc.K, rows[0], 120, hypotheses=1024, seed=s)["winner"][0] >= 256)
+    ref = sr.ransac_batch(sc.K, rows, [120], hypotheses=1024, seed=seed)
+    assert ref[0]["consensus"] >= 15
+    _check(_run(ctx, rows, [120], hypotheses=1024, seed=seed), ref)
+
+
+def test_a_problem_alone_and_inside_a_batch_and_twice(ctx, batch_a, ref_a):
+    rows, counts, names = batch_a
+    p = names.index("n%d" % (sc.CHUNK + 1))
+    alone = _run(ctx, rows[p:p + 1], counts[p:p + 1])
+    five = np.stack([rows[0], rows[3], rows[8], rows[p], rows[1]])
+    inside = _run(ctx, five, np.array([counts[0], counts[3], counts[8], counts[p], counts[1]], np.int32))
+    again = _run(ctx, rows[p:p + 1], counts[p:p + 1])
+    for k in alone:
+        assert alone[k][0].tobytes() == inside[k][3].tobytes() == again[k][0].tobytes(), k
+    _check(alone, [ref_a[p]])
+
+
+def test_host_form_equals_the_batched_one(ctx, batch_a, ref_a):
+    rows, counts, names = batch_a
+    for name in ("n2", "n65", "n%d" % (sc.CHUNK + 1), "octaves"):
+        p = names.index(name)
+        n = int(counts[p])
+        h = ctx.sim3_ransac(rows[p, :n], sc.K, seed=SEED)
+        r = ref_a[p]
+        assert h["winner"] == r["winner"] and h["consensus"] == r["consensus"] and h["flags"] == r["flags"], name
+        assert np.array_equal(h["inlier"], r["inlier"][:n]) and np.array_equal(h["S12"].view(np.uint32), r["S1232"].view(np.uint32)), name
+        assert np.array_equal(h["srt"].view(np.uint64), r["srt"].view(np.uint64)), name
+    assert ctx.sim3_ransac(rows[0, :0], sc.K)["flags"] == 1
+    # the tuple form builds the same rows
+    p = names.index("octaves")
+    r = rows[p, :200]
+    t = ctx.sim3_ransac((np.stack([r["X1"], r["Y1"], r["Z1"]], -1), np.stack([r["X2"], r["Y2"], r["Z2"]], -1), r["inv_sigma2_1"],
+                         r["inv_sigma2_2"]), sc.K, seed=SEED)
+    assert t["winner"] == ref_a[p]["winner"] and np.array_equal(t["srt"].view(np.uint64), ref_a[p]["srt"].view(np.uint64))
+
+
+def test_nullable_outputs_and_argument_checks(ctx, batch_a):
+    rows, counts, _ = batch_a
+    d_rows, d_cnt = _rows_dev(rows), _dev(counts)
+    o, c = d_rows.data_ptr(), d_cnt.data_ptr()
+    assert ctx.sim3_ransac_dev(len(rows), sc.K, o, c, PITCH) == capi.TB_OK       # every output null
+    ctx.synchronize()
+    assert ctx.sim3_ransac_dev(1, sc.K, 0, c, PITCH) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, 0, PITCH) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, 0) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(-1, sc.K, o, c, PITCH) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, hypotheses=0) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, hypotheses=1025) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, fixed_scale=2) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, fixed_scale=-1) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, chi2_max=float("nan")) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, chi2_max=float("inf")) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, sc.K, o, c, PITCH, chi2_max=-1.0) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, (0.0, 718.0, 607.0, 185.0), o, c, PITCH) == capi.TB_EINVAL
+    assert ctx.sim3_ransac_dev(1, (718.0, -1.0, 607.0, 185.0), o, c, PITCH) == capi.TB_EINVAL
+    import ctypes as C
+    prm = capi.sim3_params()
+    L, h = capi.lib(), ctx._h
+    v = C.c_void_p
+    Kd = (C.c_double * 4)(*sc.K)
+    assert L.tb_sim3_ransac_batch_dev(h, 1, None, v(o), v(c), PITCH, C.byref(prm), None, None, None, None, None, None) == capi.TB_EINVAL   # null K
+    assert L.tb_sim3_ransac_batch_dev(h, 1, Kd, v(o), v(c), PITCH, None, None, None, None, None, None, None) == capi.TB_EINVAL             # null params
+    assert ctx.sim3_ransac_dev(65536, sc.K, o, c, PITCH) == capi.TB_EUNSUPPORTED
+    assert ctx.sim3_ransac_dev(0, sc.K, o, c, PITCH) == capi.TB_OK

@@ -18,6 +18,8 @@ KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 MATCH = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
 CORNER = np.dtype([("x", "<i4"), ("y", "<i4"), ("score", "<i4")])
 OBS = np.dtype([("u", "<f4"), ("v", "<f4"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("inv_sigma2", "<f4")])
+SIM3_ROW = np.dtype([("X1", "<f4"), ("Y1", "<f4"), ("Z1", "<f4"), ("X2", "<f4"), ("Y2", "<f4"), ("Z2", "<f4"), ("inv_sigma2_1", "<f4"),
+                     ("inv_sigma2_2", "<f4")])
 BA_OBS = np.dtype([("kf", "<i4"), ("pt", "<i4"), ("u", "<f4"), ("v", "<f4"), ("inv_sigma2", "<f4")])
 PG_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("w_rot", "<f8"), ("w_trans", "<f8")])
 CAMERA = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("width", "<i4"), ("height", "<i4"),
@@ -60,6 +62,7 @@ EXPORTS = [
     "tb_pose_graph", "tb_pose_graph_batch_dev", "tb_pose_graph_plan", "tb_vo_loop_enable", "tb_vo_loop_state_dev",
     "tb_pnp_ransac", "tb_pnp_ransac_batch_dev", "tb_kf_store_pnp_enable", "tb_kf_store_pnp_state_dev", "tb_vo_reloc_pnp_enable",
     "tb_two_view", "tb_two_view_batch_dev", "tb_vo_mono_init_enable", "tb_vo_mono_init_state_dev",
+    "tb_sim3_ransac", "tb_sim3_ransac_batch_dev", "tb_kf_store_sim3_dev", "tb_kf_store_sim3_state_dev", "tb_vo_relocalize_sim3_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -297,6 +300,35 @@ class PnpParams(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("chi2_max", C.c_double), ("seed", C.c_uint64)]
 
 
+class Sim3Params(C.Structure):
+    """tb_sim3_params of include/tb_capi.h"""
+    _fields_ = [("hypotheses", C.c_int), ("fixed_scale", C.c_int), ("chi2_max", C.c_double), ("seed", C.c_uint64)]
+
+
+def sim3_params(hypotheses=256, fixed_scale=False, chi2_max=9.210, seed=0):
+    """a Sim3Params with the defaults of include/tb_capi.h; fixed_scale is passed through as an int, so that the argument check
+    can be tested"""
+    return Sim3Params(int(hypotheses), int(fixed_scale), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class Sim3Out(C.Structure):
+    """tb_sim3_out of include/tb_capi.h: device pointers, each nullable"""
+    _fields_ = [(n, C.c_void_p) for n in ("cand_rows", "cand_consensus", "cand_flags", "cand_S12", "cand_srt", "best_rank", "best_kf",
+                                          "best_S12", "best_srt")]
+
+
+def sim3_out(S, ncand, device):
+    """(Sim3Out, dict of the torch tensors it points to): every output of a Sim(3) query of S sequences x ncand candidates"""
+    import torch
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=device)
+    t = dict(cand_rows=i32(S, ncand), cand_consensus=i32(S, ncand), cand_flags=i32(S, ncand),
+             cand_S12=torch.empty((S, ncand, 4, 4), dtype=torch.float32, device=device),
+             cand_srt=torch.empty((S, ncand, 8), dtype=torch.float64, device=device), best_rank=i32(S), best_kf=i32(S),
+             best_S12=torch.empty((S, 4, 4), dtype=torch.float32, device=device), best_srt=torch.empty((S, 8), dtype=torch.float64, device=device))
+    so = Sim3Out(**{k: (v.data_ptr() if v.numel() else None) for k, v in t.items()})
+    return so, t
+
+
 class TwoViewParams(C.Structure):
     """tb_two_view_params of include/tb_capi.h"""
     _fields_ = [("hypotheses", C.c_int), ("chi2_epi", C.c_double), ("refit", C.c_int), ("tri", TriangulateParams),
@@ -448,8 +480,20 @@ class VO:
         p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
         rc = lib().tb_vo_relocalize_dev(self._h, int(topk), int(exclude_newest), int(min_inliers), p(q["scores"]), p(q["top_slot"]),
                                         p(q["top_kf"]), p(q["top_score"]), p(q["top_count"]), C.byref(ro))
+        if rc == 0:
+            self._reloc_topk = int(topk)      # what relocalize_sim3_dev sizes its outputs by
         q.update(out)
         return rc, q
+
+    def relocalize_sim3_dev(self, device, min_consensus=20, topk=None, **params):
+        """tb_vo_relocalize_sim3_dev after relocalize_dev: (status code, dict of device tensors with tb_sim3_out's fields
+        [nseq, topk, ...]); params as sim3_params. topk None = the topk of this object's last relocalize_dev (1 when there was
+        none: the library then answers TB_ESTATE); the library refuses any other count than the verification's with TB_EINVAL
+        before it writes, so outputs sized here are never overrun."""
+        topk = getattr(self, "_reloc_topk", None) or 1 if topk is None else int(topk)
+        so, out = sim3_out(self.nseq, max(topk, 0), device)
+        prm = sim3_params(**params)
+        return lib().tb_vo_relocalize_sim3_dev(self._h, int(topk), C.byref(prm), int(min_consensus), C.byref(so)), out
 
     def reloc_pnp_enable(self, hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, expand=1):
         """tb_vo_reloc_pnp_enable: returns the status code (0 or a negative TB_E* code), so the state checks can be tested."""
@@ -1065,6 +1109,36 @@ class Context:
         return lib().tb_pnp_ransac_batch_dev(self._h, int(nproblems), _p(K), v(obs_ptr), v(counts_ptr), int(obs_pitch), C.byref(prm),
                                              v(prior_ptr), v(Tcw_ptr), v(consensus_ptr), v(inlier_ptr), v(winner_ptr), v(flags_ptr))
 
+    def sim3_ransac(self, rows, K, hypotheses=256, fixed_scale=False, chi2_max=9.210, seed=0):
+        """tb_sim3_ransac: the similarity transform X1 = s R12 X2 + t12 from the 3D-3D rows of one problem: a SIM3_ROW array, or the
+        tuple (X1 [n][3], X2 [n][3], inv_sigma2_1 [n], inv_sigma2_2 [n]). Returns a dict: S12 [4, 4] float32, srt [8] float64 (the
+        unit quaternion w x y z, t12, s), consensus, inlier uint8 [n], winner (hypothesis, refitted), flags."""
+        if isinstance(rows, tuple):
+            X1, X2 = (np.asarray(a, np.float32).reshape(-1, 3) for a in rows[:2])
+            r = np.zeros(len(X1), SIM3_ROW)
+            for k, (f1, f2) in enumerate((("X1", "X2"), ("Y1", "Y2"), ("Z1", "Z2"))):
+                r[f1], r[f2] = X1[:, k], X2[:, k]
+            r["inv_sigma2_1"], r["inv_sigma2_2"] = rows[2], rows[3]
+            rows = r
+        K = np.ascontiguousarray(K, np.float64)
+        rows = np.ascontiguousarray(rows, SIM3_ROW).reshape(-1)
+        prm = sim3_params(hypotheses, fixed_scale, chi2_max, seed)
+        S, srt, inl, win = np.zeros(16, np.float32), np.zeros(8, np.float64), np.zeros(len(rows), np.uint8), np.zeros(2, np.int32)
+        cons, flags = C.c_int(0), C.c_int(0)
+        self.check(lib().tb_sim3_ransac(self._h, _p(K), _p(rows) if len(rows) else None, len(rows), C.byref(prm), _p(S), _p(srt), C.byref(cons),
+                                        _p(inl) if len(rows) else None, _p(win), C.byref(flags)))
+        return dict(S12=S.reshape(4, 4), srt=srt, consensus=cons.value, inlier=inl, winner=(int(win[0]), int(win[1])), flags=flags.value)
+
+    def sim3_ransac_dev(self, nproblems, K, rows_ptr, counts_ptr, pitch, S12_ptr=0, srt_ptr=0, consensus_ptr=0, inlier_ptr=0, winner_ptr=0,
+                        flags_ptr=0, hypotheses=256, fixed_scale=False, chi2_max=9.210, seed=0):
+        """tb_sim3_ransac_batch_dev: device pointers (0 / None for the nullable ones), asynchronous on the context's stream.
+        Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        prm = sim3_params(hypotheses, fixed_scale, chi2_max, seed)
+        v = lambda q: C.c_void_p(q or None)
+        return lib().tb_sim3_ransac_batch_dev(self._h, int(nproblems), _p(K), v(rows_ptr), v(counts_ptr), int(pitch), C.byref(prm), v(S12_ptr),
+                                              v(srt_ptr), v(consensus_ptr), v(inlier_ptr), v(winner_ptr), v(flags_ptr))
+
     def two_view(self, xy0, xy1, K, skip=None, inv_sigma2_0=None, inv_sigma2_1=None, Tcw0=None, **params):
         """tb_two_view: a relative pose and first points from the n point pairs (xy0 / xy1 [n][2] pixels) of one problem; params as
         two_view_params. Returns a dict: status, Tcw1 [4, 4] float32, points [n][3] float32 (zero where nothing was written),
@@ -1423,6 +1497,38 @@ class KeyframeStore:
         spec = (("rows", (n, P, 6), "<f4", torch.float32), ("row_counts", (n,), "<i4", torch.int32), ("consensus", (n,), "<i4", torch.int32),
                 ("winner", (n, 2), "<i4", torch.int32), ("Tcw", (n, 4, 4), "<f4", torch.float32), ("took", (n,), "|u1", torch.uint8),
                 ("flags", (n,), "<i4", torch.int32))
+        return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
+
+    def sim3_rc(self, K, nlevels, scale, q_keys, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot, min_consensus=20, ncand=None,
+                q_pitch=None, **params):
+        """tb_kf_store_sim3_dev after a relocalize -> (status code, dict of output tensors). q_keys [S, Q, 7] int32 records,
+        q_counts [S], q_map_points [S, Q, 3] float32, q_mp_valid [S, Q] uint8, q_Tcw [S, 4, 4] float32, cand_slot [S, ncand] int32
+        (what the relocalize took); params as sim3_params."""
+        ts = (q_keys, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot)
+        assert all(t.is_contiguous() for t in ts)
+        ncand = int(cand_slot.shape[1] if ncand is None else ncand)
+        so, out = sim3_out(self.nseq, max(min(ncand, cand_slot.shape[1]), 0), q_keys.device)
+        prm = sim3_params(**params)
+        Kd = (C.c_double * 4)(*[float(k) for k in K])
+        p = [C.c_void_p(t.data_ptr()) for t in ts]
+        rc = lib().tb_kf_store_sim3_dev(self._h, Kd, int(nlevels), C.c_float(scale), p[0], p[1], p[2], p[3],
+                                        int(q_keys.shape[1] if q_pitch is None else q_pitch), p[4], p[5], ncand, C.byref(prm), int(min_consensus),
+                                        C.byref(so))
+        return rc, out
+
+    def sim3(self, *a, **kw):
+        rc, out = self.sim3_rc(*a, **kw)
+        self.ctx.check(rc)
+        return out
+
+    def sim3_state(self, device, ncand):
+        """tb_kf_store_sim3_state_dev: torch VIEWS (not copies) of the last Sim(3) query's work for S x ncand pairs: rows
+        [pairs, P, 8] float32 (SIM3_ROW records), row_counts [pairs], inlier [pairs, P] uint8."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self.ctx.check(lib().tb_kf_store_sim3_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        n, P = self.nseq * int(ncand), self.pitch
+        spec = (("rows", (n, P, 8), "<f4", torch.float32), ("row_counts", (n,), "<i4", torch.int32), ("inlier", (n, P), "|u1", torch.uint8))
         return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
 
     def relocalize_rc(self, K, nlevels, scale, q_keys, q_desc, q_counts, q_fv_keys, q_fv_counts, cand_slot, map_point_only=True, th_low=50,

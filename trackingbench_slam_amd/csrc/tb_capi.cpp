@@ -1677,8 +1677,63 @@ int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, flo
     }
     if (mcounts != st->mcounts)   /* tb_kf_store_work_dev lends the last call's counts */
         TB_HIP(ctx, hipMemcpyAsync(st->mcounts, mcounts, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    st->reloc_done = true;   /* the match lists are filled, pair-major at this ncand: tb_kf_store_sim3_dev may read them */
+    st->reloc_ncand = ncand;
     if (!o.best_rank && !o.best_kf && !o.best_Tcw) return TB_OK;
     return tbk_reloc_select(ctx, st->nseq, ncand, prm->min_inliers, ckf, ninl, pose, o.best_rank, o.best_kf, o.best_Tcw);
+}
+
+int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts,
+                         const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch, const float* q_Tcw, const int32_t* cand_slot,
+                         int ncand, const tb_sim3_params* prm, int min_consensus, const tb_sim3_out* out) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    if (!K || !q_map_points || !q_mp_valid || !q_Tcw || !prm || !tb_sim3_params_ok(prm) || min_consensus < 0 || !(K[0] > 0.0) || !(K[1] > 0.0) ||
+        !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_dev: null arguments, the Sim(3) parameters (hypotheses 1..1024, fixed_scale 0 or 1, chi2_max), "
+                                       "min_consensus %d or K", min_consensus);
+    float inv_sigma2[TB_MAX_LEVELS];
+    int rc;
+    if ((rc = reloc_check(st, "tb_kf_store_sim3_dev", nlevels, scale, q_keys, q_counts, q_pitch, cand_slot, ncand, inv_sigma2))) return rc;
+    if (!st->reloc_done) return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_dev: no verification (tb_relocalize_batch_dev) has filled the match lists");
+    if (ncand != st->reloc_ncand)
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_dev: ncand %d, but the match lists were filled for %d candidates a sequence", ncand, st->reloc_ncand);
+    if (!st->s3_ready) {   /* the first call allocates, later ones do not */
+        const size_t pairs = (size_t)st->nseq * st->max_cand, pp = pairs * st->pitch;
+        /* a buffer is allocated only while its pointer is null, so a call that failed half way is finished by the next one */
+        if (!st->s3_rows) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_rows, pp));
+        if (!st->s3_mask) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_mask, pp, 0));
+        if (!st->s3_cnt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_cnt, pairs, 0));
+        if (!st->s3_kf) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_kf, pairs));
+        if (!st->s3_cons) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_cons, pairs));
+        if (!st->s3_flags) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_flags, pairs));
+        if (!st->s3_S12) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_S12, pairs * 16));
+        if (!st->s3_srt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_srt, pairs * 8));
+        st->s3_ready = true;
+    }
+    static const tb_sim3_out none = {};
+    const tb_sim3_out& o = out ? *out : none;
+    const int pairs = st->nseq * ncand;
+    int32_t* cons = o.cand_consensus ? o.cand_consensus : st->s3_cons;
+    float* S12 = o.cand_S12 ? o.cand_S12 : st->s3_S12;
+    double* srt = o.cand_srt ? o.cand_srt : st->s3_srt;
+    TB_TRY(tbk_sim3_rows(ctx, pairs, ncand, st->cap, cand_slot, st->kf_ids, q_keys, q_counts, q_map_points, q_mp_valid, q_pitch, q_Tcw,
+                         st->matches, st->mcounts, st->keys, st->mp, st->valid, st->counts, st->Tcw, st->pitch, inv_sigma2, nlevels, st->s3_rows,
+                         st->s3_cnt, st->s3_kf, o.cand_rows));
+    TB_TRY(tbk_sim3_batch(ctx, pairs, K, st->s3_rows, st->s3_cnt, st->pitch, prm->hypotheses, prm->fixed_scale, prm->chi2_max, prm->seed, S12, srt,
+                          cons, st->s3_mask, nullptr, o.cand_flags ? o.cand_flags : st->s3_flags));
+    if (!o.best_rank && !o.best_kf && !o.best_S12 && !o.best_srt) return TB_OK;
+    return tbk_sim3_select(ctx, st->nseq, ncand, min_consensus, st->s3_kf, cons, S12, srt, o.best_rank, o.best_kf, o.best_S12, o.best_srt);
+}
+
+int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const int32_t** row_counts, const uint8_t** inlier) {
+    if (!st) return TB_EINVAL;
+    if (!st->s3_ready) return tb_fail(st->ctx, TB_ESTATE, "tb_kf_store_sim3_state_dev: before the first tb_kf_store_sim3_dev");
+    if (rows) *rows = st->s3_rows;
+    if (row_counts) *row_counts = st->s3_cnt;
+    if (inlier) *inlier = st->s3_mask;
+    return TB_OK;
 }
 
 int tb_bow_transform(tb_ctx* ctx, const tb_vocab* voc, const uint8_t* desc, int n, int levelsup, int32_t* word_ids, double* weights,
@@ -2119,6 +2174,54 @@ int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, cons
     if (inlier) TB_DOWNLOAD(ctx, inlier, b + oInl, (size_t)n);
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (Tcw_out) memcpy(Tcw_out, T, 64);
+    if (consensus) *consensus = h[0];
+    if (winner) { winner[0] = h[1]; winner[1] = h[2]; }
+    if (flags) *flags = h[3];
+    return TB_OK;
+}
+
+/* ------------------------------------------------------------------ Sim(3) from 3D-3D rows */
+int tb_sim3_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_row* rows, const int32_t* counts, int pitch,
+                             const tb_sim3_params* prm, float* S12, double* srt, int32_t* consensus, uint8_t* inlier, int32_t* winner,
+                             int32_t* flags) {
+    TB_ENTER(ctx);
+    if (!ctx || nproblems < 0 || pitch < 1 || !K || !rows || !counts || !prm) return TB_EINVAL;
+    if (!tb_sim3_params_ok(prm) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) ||
+        !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_sim3_ransac_batch_dev: hypotheses 1..1024, fixed_scale 0 or 1, chi2_max finite and not negative, K finite, fx and fy positive");
+    if (nproblems > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_sim3_ransac_batch_dev: %d problems (at most 65535 per call)", nproblems);
+    return tbk_sim3_batch(ctx, nproblems, K, rows, counts, pitch, prm->hypotheses, prm->fixed_scale, prm->chi2_max, prm->seed, S12, srt,
+                          consensus, inlier, winner, flags);
+}
+
+int tb_sim3_ransac(tb_ctx* ctx, const double K[4], const tb_sim3_row* rows, int n, const tb_sim3_params* prm, float S12[16], double srt[8],
+                   int* consensus, uint8_t* inlier, int32_t winner[2], int* flags) {
+    TB_ENTER(ctx);
+    if (!ctx || n < 0 || !K || !prm || (n && !rows)) return TB_EINVAL;
+    const size_t pitch = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oRows = stage_piece(end, pitch * sizeof(tb_sim3_row)), oS = stage_piece(end, 64), oQ = stage_piece(end, 64),
+                 oInl = stage_piece(end, pitch), oRes = stage_piece(end, 16), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt = n;
+    TB_UPLOAD(ctx, b + oRows, rows, (size_t)n * sizeof(tb_sim3_row));
+    TB_UPLOAD(ctx, b + oCnt, &cnt, 4);
+    int32_t* res = (int32_t*)(b + oRes);   /* consensus, winner[2], flags */
+    if ((rc = tb_sim3_ransac_batch_dev(ctx, 1, K, (const tb_sim3_row*)(b + oRows), (const int32_t*)(b + oCnt), (int)pitch, prm, (float*)(b + oS),
+                                       (double*)(b + oQ), res, (uint8_t*)(b + oInl), res + 1, res + 3)))
+        return rc;
+    int32_t h[4];
+    float S[16];
+    double q[8];
+    TB_DOWNLOAD(ctx, S, b + oS, 64);
+    TB_DOWNLOAD(ctx, q, b + oQ, 64);
+    TB_DOWNLOAD(ctx, h, res, 16);
+    if (inlier) TB_DOWNLOAD(ctx, inlier, b + oInl, (size_t)n);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (S12) memcpy(S12, S, 64);
+    if (srt) memcpy(srt, q, 64);
     if (consensus) *consensus = h[0];
     if (winner) { winner[0] = h[1]; winner[1] = h[2]; }
     if (flags) *flags = h[3];

@@ -290,6 +290,15 @@ struct tb_kf_store {
     uint8_t* took = nullptr;                                 /* [pairs] the pair took the PnP path */
     float *ppose = nullptr, *seed2 = nullptr, *pose2 = nullptr;   /* [pairs][16] the PnP pose, the pose stage's seed, the second stage's pose */
     int32_t *cnt0 = nullptr, *cnt2 = nullptr, *pcons = nullptr, *pwin = nullptr, *pflags = nullptr, *ninl2 = nullptr;   /* [pairs], pwin [pairs][2] */
+    /* the Sim(3) query (tb_kf_store_sim3_dev): reloc_done = a verification has filled the match lists; the buffers are allocated by
+     * the first query */
+    bool reloc_done = false, s3_ready = false;
+    int reloc_ncand = 0;                                     /* the last verification's candidates per sequence */
+    tb_sim3_row* s3_rows = nullptr;                          /* [pairs][pitch] */
+    uint8_t* s3_mask = nullptr;                              /* [pairs][pitch] */
+    int32_t *s3_cnt = nullptr, *s3_kf = nullptr, *s3_cons = nullptr, *s3_flags = nullptr;   /* [pairs] */
+    float* s3_S12 = nullptr;                                 /* [pairs][16] */
+    double* s3_srt = nullptr;                                /* [pairs][8] */
 };
 
 /* kernel launchers (k_*.hip) */
@@ -507,6 +516,24 @@ int tbk_linear_triangle(tb_ctx* ctx, int npairs, const float* d_xy0, const float
 int tbk_pnp_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_obs* d_obs, const int32_t* d_counts, int obs_pitch, int hypotheses,
                   double chi2_max, unsigned long long seed, const float* d_Tcw_prior, float* d_Tcw_out, int32_t* d_consensus,
                   uint8_t* d_inlier, int32_t* d_winner, int32_t* d_flags);
+/* Sim(3) RANSAC (k_sim3.hip): one workgroup per problem, no work buffer; every output nullable. The store's query around it: the
+ * 3D-3D rows of every pair through the verification's match lists (cand_kf -1 = no candidate), and the selection */
+int tbk_sim3_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_row* d_rows, const int32_t* d_counts, int pitch, int hypotheses,
+                   int fixed_scale, double chi2_max, unsigned long long seed, float* d_S12, double* d_srt, int32_t* d_consensus,
+                   uint8_t* d_inlier, int32_t* d_winner, int32_t* d_flags);
+int tbk_sim3_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids, const tb_keypoint* d_q_keys,
+                  const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch, const float* d_q_Tcw,
+                  const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys, const float* d_kf_mp,
+                  const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch, const float* inv_sigma2, int nlevels,
+                  tb_sim3_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf, int32_t* d_rows_out);
+int tbk_sim3_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_cand_kf, const int32_t* d_cand_consensus,
+                    const float* d_cand_S12, const double* d_cand_srt, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_S12,
+                    double* d_best_srt);
+/* tb_sim3_ransac_batch_dev's parameter rules, for the entry points around it */
+static inline bool tb_sim3_params_ok(const tb_sim3_params* prm) {
+    return prm->hypotheses >= 1 && prm->hypotheses <= 1024 && (prm->fixed_scale == 0 || prm->fixed_scale == 1) && prm->chi2_max >= 0.0 &&
+           std::isfinite(prm->chi2_max);
+}
 /* two-view initialisation (k_two_view.hip): one workgroup per problem, no work buffer; every output nullable; pitch <= 2048 */
 int tbk_two_view(tb_ctx* ctx, int nproblems, const float* d_xy0, const float* d_xy1, const int32_t* d_counts, const uint8_t* d_skip,
                  const float* d_inv_sigma2_0, const float* d_inv_sigma2_1, int pitch, const double K[4], const float* d_Tcw0,

@@ -71,7 +71,12 @@ struct tb_vo {
     /* relocalisation (tb_vo_reloc_enable): the keyframe store, owned, and the query's outputs a caller does not take */
     tb_kf_store* store = nullptr;
     double *rl_scores = nullptr, *rl_top_score = nullptr;   /* [nseq][capacity], [nseq][max_candidates] */
+    /* rl_top_slot is shared scratch: the recovery and loop stages of a step overwrite it before they read it, and
+     * tb_vo_relocalize_dev leaves the top_slot of its query in it (copied in when the caller took the output) for
+     * tb_vo_relocalize_sim3_dev, which is why every step clears s3_slot */
     int32_t *rl_top_slot = nullptr, *rl_top_kf = nullptr;   /* [nseq][max_candidates] */
+    const int32_t* s3_slot = nullptr;                       /* the top_slot of the tb_vo_relocalize_dev since the last step (null: none), */
+    int s3_topk = 0;                                        /* and its topk: what tb_vo_relocalize_sim3_dev runs on */
     /* recovery (tb_vo_recover_enable): the flags and the selection of the last step, the per-sequence tracking keyframe, the
      * masked candidates, and the rings of the keyframes' word / node ids, ring-aligned with the store */
     bool rec_on = false;
@@ -427,6 +432,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     if (vo->mono_on) TB_TRY(vo_mono_clear(vo));
     if (vo->mi_on) TB_TRY(vo_mono_init_clear(vo));
     vo->next = 0;
+    vo->s3_slot = nullptr;
     vo->ragged = false;
     std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
     std::fill(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end(), -1);
@@ -871,6 +877,7 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
     if (keyframe) vo->kf_frame = t;
     vo->cur = b;
     vo->next = t + 1;
+    vo->s3_slot = nullptr;   /* a Sim(3) query needs a tb_vo_relocalize_dev of this frame */
     for (int s = 0; s < S; s++) {
         vo->seq_frame[s] = t;
         if (keyframe) vo->seq_kf_frame[s] = t;
@@ -956,6 +963,7 @@ int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0) {
         if (which[s]) { vo->seq_frame[s] = -1; vo->seq_kf_frame[s] = -1; vo->seq_reset[s] = 1; }
     vo->ragged = true;
     vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
+    vo->s3_slot = nullptr;
     vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
     return TB_OK;
 }
@@ -1023,6 +1031,7 @@ int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, 
     for (int j = 0; j < nkf; j++) vo->seq_kf_frame[pin[S + j]] = vo->seq_frame[pin[S + j]];
     vo->ragged = true;
     vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
+    vo->s3_slot = nullptr;
     vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
     return TB_OK;
 }
@@ -1160,8 +1169,28 @@ int tb_vo_relocalize_dev(tb_vo* vo, int topk, int exclude_newest, int min_inlier
     TB_TRY(tb_bow_db_query_dev(vo->db, o.bv_word, o.bv_val, o.bv_cnt, vo->P, exclude_newest, topk, scores, top_slot, top_kf, top_score,
                                top_count));
     const tb_reloc_params prm = vo_reloc_params(vo, min_inliers);
-    return tb_relocalize_batch_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_desc, o.orb_cnt, o.fv_keys, o.fv_cnt, vo->P,
-                                   top_slot, topk, &prm, out);
+    TB_TRY(tb_relocalize_batch_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_desc, o.orb_cnt, o.fv_keys, o.fv_cnt, vo->P,
+                                   top_slot, topk, &prm, out));
+    if (top_slot != vo->rl_top_slot)   /* tb_vo_relocalize_sim3_dev reads the loop's own copy: the caller's buffer may be gone by then */
+        TB_HIP(ctx, hipMemcpyAsync(vo->rl_top_slot, top_slot, (size_t)vo->nseq * topk * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    vo->s3_slot = vo->rl_top_slot;
+    vo->s3_topk = topk;
+    return TB_OK;
+}
+
+int tb_vo_relocalize_sim3_dev(tb_vo* vo, int topk, const tb_sim3_params* prm, int min_consensus, const tb_sim3_out* out) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_sim3_dev: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (vo->next < 1) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_sim3_dev before the first step");
+    if (!vo->s3_slot) return tb_fail(ctx, TB_ESTATE, "tb_vo_relocalize_sim3_dev: no tb_vo_relocalize_dev since the last step");
+    if (topk != vo->s3_topk)   /* the outputs are [nseq][topk]: a caller that sized them for another count must not be written to */
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_relocalize_sim3_dev: topk %d, but the last tb_vo_relocalize_dev ran with %d", topk, vo->s3_topk);
+    const tb_vo_frame_out& o = vo->out[vo->oc];
+    const int c = vo->cur;
+    return tb_kf_store_sim3_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_cnt, vo->mp[c], vo->valid[c], vo->P, vo->Tcw[c],
+                                vo->s3_slot, vo->s3_topk, prm, min_consensus, out);
 }
 
 int tb_vo_reloc_pnp_enable(tb_vo* vo, const tb_pnp_params* prm, int min_consensus, int expand) {

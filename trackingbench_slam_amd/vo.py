@@ -591,6 +591,28 @@ class StereoVO:
             t.record_stream(self.stream)
         return out
 
+    def relocalize_sim3(self, fixed_scale=True, min_consensus=20, **params):
+        """After relocalize(topk, ...), on the same topk candidates: the similarity transform between the current frame's own map (its carried points, in its
+        camera) and each candidate's stored map (in the stored keyframe's camera), X_current = s R12 X_stored + t12, by Horn's
+        closed form in a RANSAC over the verification's matches. Device tensors: S12 [S, 4, 4] float32, srt [S, 8] float64 (the unit
+        quaternion w x y z, t12, s), consensus [S] (the winner's, 0 when none), best_rank / best_kf [S] (-1: no candidate reached
+        min_consensus -- ORB-SLAM's figure is 20) and the per-candidate cand_rows / cand_consensus / cand_flags [S, topk],
+        cand_S12 [S, topk, 4, 4], cand_srt [S, topk, 8]. fixed_scale=True suits a stereo map, whose scale is metric. A query: no
+        state tensor changes. No host synchronisation. params: hypotheses, chi2_max, seed."""
+        self._need_store()
+        with torch.cuda.stream(self.stream):
+            rc, out = self.vo.relocalize_sim3_dev(self.dev, min_consensus=min_consensus, fixed_scale=fixed_scale, **params)
+            if rc == 0:
+                pick = out["best_rank"].clamp(min=0).long().view(-1, 1)
+                cons = out["cand_consensus"].gather(1, pick).view(-1)
+                out["consensus"] = torch.where(out["best_rank"] >= 0, cons, torch.zeros_like(cons))
+                out["S12"], out["srt"] = out["best_S12"], out["best_srt"]
+        self.ctx.check(rc)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        return out
+
     def recovery(self):
         """The recovery state after the last step (recover=...): dict(lost [S] uint8 and track_inliers [S] int32 -- the tracker's own
         inlier count, before any adoption --, recovered_kf [S] int32 = the frame index of the keyframe the sequence adopted in
