@@ -877,7 +877,8 @@ int tb_add_map_points_by_stereo_batch_dev(tb_ctx* ctx, int npairs, const uint8_t
  * keyframe (repeated (kf, pt) pairs are rejected like out-of-range indices); at most 64 free keyframes (128 in all),
  * 2^25 points and 99 iterations per window (TB_EUNSUPPORTED beyond). Windows with up to 10 free keyframes run the
  * MFMA-tiled Schur path; 11..64 (reduced systems up to 384 x 384) the generic large-window kernels. stats (nullable, 8 doubles):
- * iterations, initial chi2, final chi2, final lambda. */
+ * iterations, initial chi2, final chi2, final lambda. tb_local_ba takes its observations in any order: it sorts a copy by
+ * (point, keyframe), so no bit of the result depends on the order; the batched form wants them grouped by ascending point. */
 int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* poses, int npt, float* pts,
                 const tb_ba_obs* obs, int nobs, int iters, double* stats);
 /* Batched device form: nwindows equally sized windows; window w uses poses + w*nkf*16, pts + w*npt*3,

@@ -149,7 +149,7 @@ BATCH_LOST = 7                                                                  
 FAR_BRANCH_BATCH = "y"                                                            # ... which under its gauge, y180, sits in "y"
 
 
-def problem(seed, n, frac):
+def problem(seed, n, frac, K=K):
     return synth.pose_problem(seed, n, K, noise_px=0.4, outlier_frac=frac)
 
 
@@ -217,7 +217,7 @@ BA_BATCH_GAUGES = ("x180", "y175", "z160", "gen2")
 
 
 @functools.lru_cache(maxsize=None)
-def ba_window(name):
+def ba_window(name, K=K):
     """(poses_init, pts_init, obs, nfixed, iters) of a named window, ungauged"""
     seed, nkf, npt, nfixed, per, pn, xn, iters = BA_WINDOWS[name]
     _, Pi, _, Xi, obs = synth.ba_problem(seed, nkf, npt, K, obs_per_pt=per, pose_noise=pn, pt_noise=xn)

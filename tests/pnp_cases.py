@@ -37,12 +37,12 @@ def moved(T, yaw, d):
     return (M @ T).astype(np.float32)
 
 
-def project(T, Xw):
+def project(T, Xw, K=K):
     pc = Xw @ T[:3, :3].T + T[:3, 3]
     return np.stack([pc[:, 0] / pc[:, 2] * K[0] + K[2], pc[:, 1] / pc[:, 2] * K[1] + K[3]], -1), pc[:, 2]
 
 
-def problem(seed, n, pitch=None, outliers=0.5, noise=0.5, T=None, kind="scene", octaves=False):
+def problem(seed, n, pitch=None, outliers=0.5, noise=0.5, T=None, kind="scene", octaves=False, K=K):
     """(obs OBS [pitch], good bool [pitch], Tcw float64): n rows, the first round(n * (1 - outliers)) in a random order true
     observations. kind: "scene" (depths 3-40 m), "coplanar" (world points on one plane), "behind" (every point behind the camera,
     its row the pinhole projection all the same)."""
@@ -58,7 +58,7 @@ def problem(seed, n, pitch=None, outliers=0.5, noise=0.5, T=None, kind="scene", 
         ray = np.stack([(uv[:, 0] - K[2]) / K[0], (uv[:, 1] - K[3]) / K[1], np.ones(n)], -1)
         pc = ray * (15.0 / (ray @ np.array([0.2, 0.1, 1.0])))[:, None]
     Xw = ((pc - T[:3, 3]) @ T[:3, :3]).astype(np.float32)
-    px, _ = project(T, Xw.astype(np.float64))
+    px, _ = project(T, Xw.astype(np.float64), K)
     px = px + rng.normal(0, noise, (n, 2)) if noise else px
     ngood = int(round(n * (1.0 - outliers)))
     good = np.zeros(n, bool)
@@ -74,7 +74,7 @@ def problem(seed, n, pitch=None, outliers=0.5, noise=0.5, T=None, kind="scene", 
     return obs, g, T
 
 
-def far_seed(seed):
+def far_seed(seed, K=K):
     """the issue's fixture: 200 rows, 60 of them good, 0.5 px noise; the stored seed 3 m / 0.2 rad from the truth"""
-    obs, good, T = problem(seed, 200, outliers=0.7)
+    obs, good, T = problem(seed, 200, outliers=0.7, K=K)
     return obs, good, T, moved(T, 0.2, 3.0)

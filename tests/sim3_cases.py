@@ -26,21 +26,21 @@ def truth(s=S_TRUE, angle=ANGLE_TRUE, dist=DIST_TRUE):
     return float(s), R, t
 
 
-def points(rng, n):
+def points(rng, n, K=K):
     """n points in camera-2 coordinates, inside the image, 5-40 m away -- and in front of camera 1 under truth()"""
     uv = np.stack([rng.uniform(0, W, n), rng.uniform(0, H, n)], -1)
     z = rng.uniform(5.0, 40.0, n)
     return np.stack([(uv[:, 0] - K[2]) / K[0] * z, (uv[:, 1] - K[3]) / K[1] * z, z], -1)
 
 
-def problem(seed, n, pitch=None, outliers=0.5, noise=0.0005, T=None, kind="scene", octaves=False):
+def problem(seed, n, pitch=None, outliers=0.5, noise=0.0005, T=None, kind="scene", octaves=False, K=K):
     """(rows ROW [pitch], good bool [pitch], (s, R, t)): n rows, round(n * (1 - outliers)) of them in a random order true
     correspondences with isotropic Gaussian noise of `noise` times the depth on every coordinate; the others pair two unrelated
     random points. kind: "scene", "collinear" (every point of set 2 on one line), "behind" (set 2 behind its camera)."""
     rng = np.random.default_rng(seed)
     pitch = n if pitch is None else pitch
     s, R, t = truth() if T is None else T
-    X2 = points(rng, n)
+    X2 = points(rng, n, K)
     if kind == "collinear":
         X2 = np.array([1.0, -0.5, 10.0]) + rng.uniform(0.0, 20.0, n)[:, None] * np.array([0.3, 0.1, 1.0])
     if kind == "behind":
@@ -52,7 +52,7 @@ def problem(seed, n, pitch=None, outliers=0.5, noise=0.0005, T=None, kind="scene
     ngood = int(round(n * (1.0 - outliers)))
     good = np.zeros(n, bool)
     good[rng.permutation(n)[:ngood]] = True
-    X1 = np.where(good[:, None], X1, points(rng, n))
+    X1 = np.where(good[:, None], X1, points(rng, n, K))
     w1 = w2 = None
     if octaves:
         w1 = (np.float32(1.2) ** (-2 * rng.integers(0, 8, n))).astype(np.float32)

@@ -28,7 +28,7 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _run(ctx, obs, counts, priors=None, hypotheses=256, chi2_max=pr.CHI2_MAX, seed=SEED):
+def _run(ctx, obs, counts, priors=None, hypotheses=256, chi2_max=pr.CHI2_MAX, seed=SEED, K=pc.K):
     """the batched entry on obs [P][pitch] -> dict of host arrays; outputs pre-filled so that an unwritten entry shows"""
     P, pitch = obs.shape
     d_obs, d_cnt = torch.from_numpy(obs.view(np.float32).reshape(P, pitch, 6).copy()).cuda(), _dev(np.asarray(counts, np.int32))
@@ -39,7 +39,7 @@ def _run(ctx, obs, counts, priors=None, hypotheses=256, chi2_max=pr.CHI2_MAX, se
     win = torch.full((P, 2), -9, dtype=torch.int32, device="cuda")
     flags = torch.full((P,), -9, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    ctx.check(ctx.pnp_ransac_dev(P, pc.K, d_obs.data_ptr(), d_cnt.data_ptr(), pitch, 0 if d_pr is None else d_pr.data_ptr(), T.data_ptr(),
+    ctx.check(ctx.pnp_ransac_dev(P, K, d_obs.data_ptr(), d_cnt.data_ptr(), pitch, 0 if d_pr is None else d_pr.data_ptr(), T.data_ptr(),
                                  cons.data_ptr(), inl.data_ptr(), win.data_ptr(), flags.data_ptr(), hypotheses=hypotheses,
                                  chi2_max=chi2_max, seed=seed))
     ctx.synchronize()

@@ -34,7 +34,7 @@ def _rows_dev(rows):
     return torch.from_numpy(rows.view(np.float32).reshape(P, pitch, 8).copy()).cuda()
 
 
-def _run(ctx, rows, counts, hypotheses=256, fixed_scale=False, chi2_max=sr.CHI2_MAX, seed=SEED):
+def _run(ctx, rows, counts, hypotheses=256, fixed_scale=False, chi2_max=sr.CHI2_MAX, seed=SEED, K=sc.K):
     """the batched entry on rows [P][pitch] -> dict of host arrays; outputs pre-filled so that an unwritten entry shows"""
     P, pitch = rows.shape
     d_rows, d_cnt = _rows_dev(rows), _dev(np.asarray(counts, np.int32))
@@ -45,7 +45,7 @@ def _run(ctx, rows, counts, hypotheses=256, fixed_scale=False, chi2_max=sr.CHI2_
     win = torch.full((P, 2), -9, dtype=torch.int32, device="cuda")
     flags = torch.full((P,), -9, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    ctx.check(ctx.sim3_ransac_dev(P, sc.K, d_rows.data_ptr(), d_cnt.data_ptr(), pitch, S.data_ptr(), srt.data_ptr(), cons.data_ptr(),
+    ctx.check(ctx.sim3_ransac_dev(P, K, d_rows.data_ptr(), d_cnt.data_ptr(), pitch, S.data_ptr(), srt.data_ptr(), cons.data_ptr(),
                                   inl.data_ptr(), win.data_ptr(), flags.data_ptr(), hypotheses=hypotheses, fixed_scale=fixed_scale,
                                   chi2_max=chi2_max, seed=seed))
     ctx.synchronize()

@@ -33,7 +33,7 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _run_batch(ctx, c, counts, s0, s1, skip, **prm):
+def _run_batch(ctx, c, counts, s0, s1, skip, K=tc.K, **prm):
     d = {k: _dev(c[k]) for k in ("xy0", "xy1", "Tcw0", "Tcw1")}
     opt = [None if a is None else _dev(a) for a in (counts, s0, s1, skip)]
     pts = torch.full((tc.NPAIRS, tc.PITCH, 3), -7.0, dtype=torch.float32, device="cuda")
@@ -41,7 +41,7 @@ def _run_batch(ctx, c, counts, s0, s1, skip, **prm):
     tally = torch.full((tc.NPAIRS, 6), -1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     q = lambda t: 0 if t is None else t.data_ptr()
-    rc = ctx.linear_triangle_batch_dev(tc.NPAIRS, q(d["xy0"]), q(d["xy1"]), q(opt[0]), tc.PITCH, q(d["Tcw0"]), q(d["Tcw1"]), tc.K,
+    rc = ctx.linear_triangle_batch_dev(tc.NPAIRS, q(d["xy0"]), q(d["xy1"]), q(opt[0]), tc.PITCH, q(d["Tcw0"]), q(d["Tcw1"]), K,
                                        q(opt[1]), q(opt[2]), q(opt[3]), q(pts), q(flags), q(tally), **prm)
     ctx.check(rc)
     ctx.synchronize()

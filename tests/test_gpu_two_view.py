@@ -32,7 +32,7 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def _run(ctx, xy0, xy1, counts=None, skip=None, w0=None, w1=None, Tcw0=None, **kw):
+def _run(ctx, xy0, xy1, counts=None, skip=None, w0=None, w1=None, Tcw0=None, K=tc.K, **kw):
     """the batched entry -> dict of host arrays; outputs pre-filled so that an unwritten entry shows"""
     P, pitch = xy0.shape[:2]
     d = [_dev(xy0, np.float32), _dev(xy1, np.float32), _dev(counts, np.int32), _dev(skip, np.uint8), _dev(w0, np.float32),
@@ -44,7 +44,7 @@ def _run(ctx, xy0, xy1, counts=None, skip=None, w0=None, w1=None, Tcw0=None, **k
     cons, status = full((P,), -9, torch.int32), full((P,), -9, torch.int32)
     win, good, tri = full((P, 2), -9, torch.int32), full((P, 4), -9, torch.int32), full((P, 4), -9, torch.int32)
     torch.cuda.synchronize()
-    ctx.check(ctx.two_view_dev(P, _ptr(d[0]), _ptr(d[1]), _ptr(d[2]), pitch, tc.K, _ptr(d[3]), _ptr(d[4]), _ptr(d[5]), _ptr(d[6]),
+    ctx.check(ctx.two_view_dev(P, _ptr(d[0]), _ptr(d[1]), _ptr(d[2]), pitch, K, _ptr(d[3]), _ptr(d[4]), _ptr(d[5]), _ptr(d[6]),
                                T.data_ptr(), pts.data_ptr(), pf.data_ptr(), inl.data_ptr(), cons.data_ptr(), win.data_ptr(),
                                good.data_ptr(), tri.data_ptr(), status.data_ptr(), **kw))
     ctx.synchronize()

@@ -53,11 +53,13 @@ def _same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def _step_parity(seqs, nframes, keyframe_every):
+def _step_parity(seqs, nframes, keyframe_every, K=None):
+    """K: the intrinsics the sequences were rendered with (None: the default of both sides, KITTI's)"""
     L, R, G = seqs
     S = L.shape[1]
-    P = vr.Params(keyframe_every=keyframe_every)
-    vo = StereoVO(S, keyframe_every=keyframe_every)
+    kw = {} if K is None else dict(K=K)
+    P = vr.Params(keyframe_every=keyframe_every, **kw)
+    vo = StereoVO(S, keyframe_every=keyframe_every, **kw)
     try:
         vo.reset(G[0])
         prev = [vr.initial_state(G[0, s]) for s in range(S)]

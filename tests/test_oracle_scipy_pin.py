@@ -13,7 +13,9 @@ import pytest
 from scipy.optimize import least_squares
 
 import oracle
+import ba_cases as bc
 import gauge_cases as gc
+from ba_cases import as_solver_pose as _as_solver_pose   # the solver's quaternion extraction, shared with robust_cost
 from trackingbench_slam_amd import synth
 
 K = (718.856, 718.856, 607.1928, 185.2157)
@@ -27,41 +29,6 @@ def _rodrigues(w):
     return np.eye(3) + np.sin(th) / th * Wx + (1 - np.cos(th)) / th ** 2 * (Wx @ Wx)
 
 
-def _as_solver_pose(T):
-    """The solvers take float32 4x4 poses, whose rotation blocks are orthonormal only to ~6e-8, and work on the unit
-    quaternion extracted from them (SE3Quat: oracle_pose.cpp:28-58,92-98). The same extraction here -- with the raw matrix the
-    cost function differs by ~3e-7 relative, more than the agreement asked for."""
-    R = T[:3, :3].astype(np.float64)
-    t = R[0, 0] + R[1, 1] + R[2, 2]
-    if t > 0:
-        t = np.sqrt(t + 1.0)
-        qw = 0.5 * t
-        t = 0.5 / t
-        q = np.array([(R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t, qw])
-    else:
-        i = 0
-        if R[1, 1] > R[0, 0]:
-            i = 1
-        if R[2, 2] > R[i, i]:
-            i = 2
-        j, k = (i + 1) % 3, (i + 2) % 3
-        t = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
-        c = np.zeros(3)
-        c[i] = 0.5 * t
-        t = 0.5 / t
-        qw = (R[k, j] - R[j, k]) * t
-        c[j] = (R[j, i] + R[i, j]) * t
-        c[k] = (R[k, i] + R[i, k]) * t
-        q = np.array([c[0], c[1], c[2], qw])
-    x, y, z, w = q / np.linalg.norm(q)
-    out = np.eye(4)
-    out[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                   [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                   [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
-    out[:3, 3] = T[:3, 3].astype(np.float64)
-    return out
-
-
 def _compose(xi, T0):
     """Tcw = [R(w) | t] * T0 -- any smooth chart works, the optimum is a point on SE(3)"""
     T = np.eye(4)
@@ -70,7 +37,7 @@ def _compose(xi, T0):
     return T @ T0
 
 
-def _reproj(T, X, uv, w):
+def _reproj(T, X, uv, w, K=K):
     pc = X @ T[:3, :3].T + T[:3, 3]
     proj = np.stack([K[0] * pc[:, 0] / pc[:, 2] + K[2], K[1] * pc[:, 1] / pc[:, 2] + K[3]], 1)
     return ((uv - proj) * np.sqrt(w)[:, None]).ravel()
@@ -92,8 +59,19 @@ def test_local_ba_optimum_matches_scipy_gauged():
     _local_ba_vs_scipy(101, 4, 60, 2, "y180")
 
 
-def _local_ba_vs_scipy(seed, nkf, npt, nfixed, gname):
+@pytest.mark.parametrize("seed,nkf,npt,nfixed", [(101, 4, 60, 2), (102, 6, 120, 2), (103, 5, 90, 1)])
+def test_local_ba_optimum_matches_scipy_weighted_aniso(seed, nkf, npt, nfixed):
+    """The same windows at fx != fy (ba_cases.K_ANISO) with octave weights 1.2^(-2o) drawn per observation: a weight on the
+    wrong edge, applied twice or missing from the right-hand side, or an fx where fy belongs, moves the optimum away from
+    scipy's. No outliers: the edge-wise Huber kernel has no scipy counterpart. The bounds are the unit-weight test's."""
+    _local_ba_vs_scipy(seed, nkf, npt, nfixed, None, K=bc.K_ANISO, weighted=True)
+
+
+def _local_ba_vs_scipy(seed, nkf, npt, nfixed, gname, K=K, weighted=False):
     Pt, Pi, Xt, Xi, obs = synth.ba_problem(seed, nkf, npt, K, obs_per_pt=4, noise_px=0.3, pose_noise=0.01, pt_noise=0.02)
+    if weighted:
+        obs["inv_sigma2"] = bc.octave_weights(np.random.default_rng(seed), len(obs))
+        assert len(np.unique(obs["inv_sigma2"])) == 8
     if gname is not None:
         G = gc.get(gname)
         Pt, Pi, Xi = gc.gauge_poses(Pt, G), gc.gauge_poses(Pi, G), gc.gauge_points(Xi, G)
@@ -124,7 +102,7 @@ def _local_ba_vs_scipy(seed, nkf, npt, nfixed, gname):
         r = np.empty(2 * len(obs))
         for k in range(nkf):
             m = kf == k
-            r[np.repeat(m, 2)] = _reproj(T[k], X[pt[m]], uv[m], w[m])
+            r[np.repeat(m, 2)] = _reproj(T[k], X[pt[m]], uv[m], w[m], K)
         return r
 
     x, cost = _solve(fun, np.zeros(6 * nfree + 3 * npt))

@@ -35,7 +35,7 @@ def _move(T, dx):
     return (M @ T.astype(np.float64)).astype(F32)
 
 
-def project(T, X):
+def project(T, X, K=K):
     T = T.astype(np.float64)
     Xc = X @ T[:3, :3].T + T[:3, 3]
     return np.stack([K[0] * Xc[:, 0] / Xc[:, 2] + K[2], K[1] * Xc[:, 1] / Xc[:, 2] + K[3]], -1), Xc[:, 2]
@@ -46,7 +46,7 @@ def _world(T, xc):
     return (xc - T[:3, 3]) @ T[:3, :3]
 
 
-def build(seed=11):
+def build(seed=11, K=K):
     """dict(xy0, xy1 [3][256][2] float32, counts, Tcw0, Tcw1 [3][4][4] float32, skip [3][256] uint8, X [3][256][3] float64 = the
     true points where there is one, slots = the gate cases' slots)"""
     rng = np.random.default_rng(seed)
@@ -63,7 +63,7 @@ def build(seed=11):
         xc[3, 2] = -8.0; xc[3, 0] = 1.0; xc[3, 1] = 0.5                 # behind the cameras
         xc[7] = [(u[7] - K[2]) / K[0] * 4000.0, (v[7] - K[3]) / K[1] * 4000.0, 4000.0]   # no parallax
         X[p] = _world(T0[p], xc)
-        a, _ = project(T0[p], X[p]); b, _ = project(T1[p], X[p])
+        a, _ = project(T0[p], X[p], K); b, _ = project(T1[p], X[p], K)
         xy0[p], xy1[p] = a.astype(F32), b.astype(F32)
         xy1[p, 5, 1] += F32(5.0)
         xy0[p, 9] = np.nan

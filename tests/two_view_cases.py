@@ -41,7 +41,7 @@ def _normal(st, shape):
     return (np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)).reshape(shape)
 
 
-def project(R, t, X):
+def project(R, t, X, K=K):
     pc = X @ R.T + t
     return np.stack([pc[:, 0] / pc[:, 2] * K[0] + K[2], pc[:, 1] / pc[:, 2] * K[1] + K[3]], -1), pc[:, 2]
 
@@ -57,14 +57,14 @@ def scene(st, m):
     return np.stack([x, y, z], -1)
 
 
-def problem(seed, n=ROWS, kind="forward", d=2.5, noise=0.1, outliers=0.0, pitch=None):
+def problem(seed, n=ROWS, kind="forward", d=2.5, noise=0.1, outliers=0.0, pitch=None, K=K):
     """(xy0, xy1 float32 [pitch][2], good bool [pitch], R, t): n rows visible in both views, round(n * outliers) of them, in
     random places, planted outliers; rows beyond n are zero"""
     st = Stream(seed)
     R, t = motion(kind, d)
     X = scene(st, 6 * n)
-    p0, z0 = project(np.eye(3), np.zeros(3), X)
-    p1, z1 = project(R, t, X)
+    p0, z0 = project(np.eye(3), np.zeros(3), X, K)
+    p1, z1 = project(R, t, X, K)
     vis = (z0 > 1.0) & (z1 > 1.0)
     for p in (p0, p1):
         vis &= (p[:, 0] >= 8) & (p[:, 0] < W - 8) & (p[:, 1] >= 8) & (p[:, 1] < H - 8)

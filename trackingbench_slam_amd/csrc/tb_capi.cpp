@@ -2316,9 +2316,11 @@ int tb_local_ba(tb_ctx* ctx, const double K[4], int nkf, int nfixed, float* pose
     for (int e = 0; e < nobs; e++)
         if (obs[e].kf < 0 || obs[e].kf >= nkf || obs[e].pt < 0 || obs[e].pt >= npt)
             return tb_fail(ctx, TB_EINVAL, "local_ba: observation %d out of range", e);
-    /* the kernels want observations grouped by point: stable sort keeps each point's edges in caller order */
+    /* the kernels want observations grouped by point; within a point by keyframe, so that the order of every sum, and with it
+     * every bit of the result, is independent of the caller's row order (a repeated (keyframe, point) pair is rejected below) */
     std::vector<tb_ba_obs> sorted(obs, obs + nobs);
-    std::stable_sort(sorted.begin(), sorted.end(), [](const tb_ba_obs& a, const tb_ba_obs& b) { return a.pt < b.pt; });
+    std::stable_sort(sorted.begin(), sorted.end(),
+                     [](const tb_ba_obs& a, const tb_ba_obs& b) { return a.pt != b.pt ? a.pt < b.pt : a.kf < b.kf; });
     size_t end = 0;
     const size_t oPoses = stage_piece(end, (size_t)nkf * 64), oPts = stage_piece(end, (size_t)npt * 12),
                  oObs = stage_piece(end, (size_t)nobs * sizeof(tb_ba_obs)), oStats = stage_piece(end, 64), oCnt = stage_piece(end, 4);
