@@ -508,6 +508,24 @@ typedef struct tb_sim3_out {
 int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts,
                          const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch, const float* q_Tcw, const int32_t* cand_slot,
                          int ncand, const struct tb_sim3_params* params, int min_consensus, const tb_sim3_out* out);
+/* The Sim(3) pose graph of the stored keyframes and a query frame, with the last tb_kf_store_sim3_dev's winner as the loop edge,
+ * optimised by tb_pose_graph_sim3_batch_dev: a read-only query, no ring and no work buffer of the store changes (DESIGN.md 9o;
+ * tests/sim3_graph_reference.py is the composition on the CPU). The store keeps its own device copy of that call's best_kf and
+ * best_srt (written by the same selection kernel), so the caller's buffers need not live on; a tb_kf_store_sim3_dev that asked for
+ * no best_* output selects nothing and leaves nothing to use.
+ * Per sequence, by the rules of the SE(3) loop graph (tb_vo_loop_enable): nodes are the live ring slots in ascending kf_id, then
+ * the query frame q_Tcw [nseq][16] (device); which slots are live is host arithmetic on the store's count. A node is the
+ * quaternion form of its float32 Tcw with s = 1; node 0 is fixed. Odometry edges Z = S_next S_prev^-1 join consecutive nodes; the
+ * loop edge has a = the node of best_kf, b = the frame's node and Z = best_srt copied byte for byte (the rows were X1 = q_Tcw Xw
+ * and X2 = Tcw_kf Xw', so S12 maps the keyframe's camera into the frame's). best_kf < 0 or fewer than 2 live keyframes: edge
+ * count 0, nodes after = before. A best_kf the ring no longer holds: a = -1, which the solver flags (stats[7] = -1).
+ * Then one launch of the solver on the nseq graphs: capacity + 1 nodes, edge pitch capacity + 1, nfixed 1. out (host struct)
+ * receives device pointers into the store's buffers; they and the solver's plan are made by the first call, later calls
+ * allocate nothing. Asynchronous on the context's stream, no host synchronisation, no host <-> device copy.
+ * TB_ESTATE: before a tb_kf_store_sim3_dev that selected a winner (tb_kf_store_clear forgets it). TB_EINVAL: null q_Tcw / out, iters
+ * outside 0..99, fixed_scale not 0 or 1, a negative or non-finite weight, a capacity above 63. */
+int tb_kf_store_sim3_graph_dev(tb_kf_store* st, const float* q_Tcw, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale,
+                               tb_sim3_graph_out* out);
 int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const int32_t** row_counts, const uint8_t** inlier);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
@@ -703,8 +721,8 @@ int tb_pnp_ransac(tb_ctx* ctx, const double K[4], const tb_obs* obs, int n, cons
  *   void problem   n < 3, or no hypothesis with a solution: consensus 0, winner (-2, 0), the identity and scale 1, an all-zero
  *             mask, flags bit 0 set
  * Out (device, each nullable): S12 [nproblems][16] float (the float32 rounding of [s R12 | t12; 0 0 0 1]); srt [nproblems][8]
- * double (the unit quaternion w x y z, t12, s: the FP64 form tb_pg_edge uses, so that a Sim(3) graph can take it without a
- * float32 detour); consensus [nproblems]; inlier [nproblems][pitch] bytes (zero beyond the count); winner [nproblems][2]
+ * double (the unit quaternion w x y z, t12, s: FP64, the layout of tb_pose_graph_sim3_batch_dev's nodes and edges, which take it
+ * without a float32 detour); consensus [nproblems]; inlier [nproblems][pitch] bytes (zero beyond the count); winner [nproblems][2]
  * (hypothesis, refitted); flags [nproblems]. Asynchronous on the context's stream, no host synchronisation, no host <-> device
  * copy, no work buffer: one launch of one 256-thread workgroup per problem whose state is registers and LDS. At most 65535
  * problems per call (TB_EUNSUPPORTED). TB_EINVAL: null rows / counts / K / params, pitch < 1, hypotheses outside 1..1024,
@@ -921,6 +939,32 @@ int tb_pose_graph_batch_dev(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, fl
 /* Grows the context's work buffer to what tb_pose_graph_batch_dev needs for this shape, once and ahead of time: a later call of
  * that shape or a smaller one then neither allocates nor waits for the stream. Same argument checks. */
 int tb_pose_graph_plan(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int edge_pitch);
+
+/* Sim(3) pose-graph optimisation -- extension, NO reference counterpart: the pose graph that can change scale, the consumer of the
+ * similarity tb_sim3_ransac_batch_dev measures; restated in numpy in tests/pose_graph_sim3_reference.py.
+ * A node is S = (s, R, t), X' = s R X + t, stored as 8 doubles in that solver's srt layout (the quaternion w x y z, t, s): nodes is
+ * nnodes x 8, in/out, the first nfixed held, so a device best_srt / cand_srt can be a node or an edge as it is. Edges are
+ * tb_pg_sim3_edge (a, b, Z ~ S_b S_a^-1, w_rot, w_trans, w_scale). With E = Z^-1 S_b S_a^-1 the residual is r = Log(E) ordered (omega,
+ * upsilon, sigma), chi2 = sum r' diag(w_rot I3, w_trans I3, w_scale) r, the update S <- Exp(delta) S, no robust kernel. Jacobians
+ * J_b = Jl^-1(r) Ad(Z^-1), J_a = -Jl^-1(r) Ad(E), Jl^-1 = sum_n B_n / n! ad(r)^n to the fixed order 22 (within 1e-9 of the exact ones for
+ * |omega| <= 2, |upsilon| <= 5, |sigma| <= 1; beyond that LM stays safe, a trial being accepted on the exact chi2). Everything is FP64;
+ * quaternions are normalised on entry (w >= 0). The LM rule, the limits, stats and the TB_EINVAL / TB_EUNSUPPORTED cases are
+ * tb_pose_graph's. fixed_scale (0 | 1, ORB-SLAM's bFixScale; anything else TB_EINVAL): a free node has the 6 unknowns (omega,
+ * upsilon) and its s keeps its bytes; the residual's seventh component still counts.
+ * A graph keeps EVERY BYTE of its nodes when it has no edge, when no trial was accepted or when it is malformed -- tb_pose_graph's
+ * list, and a node or edge with a non-finite entry, a zero quaternion or a scale that is not above 0, and a negative or
+ * non-finite w_scale; fixed nodes always keep theirs. tb_pose_graph_sim3 returns TB_EINVAL for a malformed graph. */
+int tb_pose_graph_sim3(tb_ctx* ctx, int nnodes, int nfixed, int fixed_scale, double* nodes, const tb_pg_sim3_edge* edges, int nedges,
+                       int iters, double* stats);
+/* Batched device form, as tb_pose_graph_batch_dev: graph g uses nodes + g*nnodes*8, edges + g*edge_pitch (edge_counts[g] of them),
+ * stats + 8g (nullable; stats[7] = -1 flags a malformed graph). One launch (k_pgo_sim3), one 256-thread workgroup per graph, the
+ * whole LM loop on the device: asynchronous on the context's stream, no host synchronisation, no host <-> device copy, no
+ * floating-point atomics -- a graph gives the same bits alone, inside any batch, and from run to run. */
+int tb_pose_graph_sim3_batch_dev(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int fixed_scale, double* nodes,
+                                 const tb_pg_sim3_edge* edges, const int32_t* edge_counts, int edge_pitch, int iters, double* stats);
+/* Grows the context's work buffer to what tb_pose_graph_sim3_batch_dev needs for this shape (about 1.8 MB a graph at 64 nodes and
+ * 256 edges; the same for either fixed_scale), once and ahead of time. Same argument checks. */
+int tb_pose_graph_sim3_plan(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int edge_pitch);
 
 /* ---------------------------------------------------------------- device-resident stereo VO loop
  * The tracking loop of the reference's main program, test/test_vo.cpp test_kitti (:674-850), for nseq independent stereo
@@ -1178,6 +1222,11 @@ int tb_vo_kf_store_get(tb_vo* vo, tb_kf_store** out);
  * device copy of a top_slot the caller took, so that buffer need not outlive the call. */
 struct tb_sim3_params;
 int tb_vo_relocalize_sim3_dev(tb_vo* vo, int topk, const struct tb_sim3_params* params, int min_consensus, const tb_sim3_out* out);
+/* tb_vo_loop_sim3_dev is a query after tb_vo_relocalize_sim3_dev: tb_kf_store_sim3_graph_dev with the loop's current pose as the
+ * query frame, whose node carries the frame index in node_kf. TB_ESTATE: relocalisation not enabled, or no
+ * tb_vo_relocalize_sim3_dev since the last step (every step and reset invalidates it). No state of the loop or the store changes:
+ * adopting the corrected nodes is left to a later change. */
+int tb_vo_loop_sim3_dev(tb_vo* vo, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale, tb_sim3_graph_out* out);
 /* tb_kf_store_pnp_enable on the loop's store: tb_vo_relocalize_dev then runs the PnP verification (tb_kf_store_pnp_state_dev on
  * tb_vo_kf_store_get's store lends its per-pair outputs) and stays a query that changes no state tensor. TB_ESTATE: relocalisation
  * not enabled, after the first step, enabled already, or together with tb_vo_recover_enable / tb_vo_loop_enable in either order:

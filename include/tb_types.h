@@ -108,6 +108,28 @@ typedef struct tb_pg_edge {
     double w_rot, w_trans;
 } tb_pg_edge;
 
+/* One Sim(3) pose-graph edge: the measured similarity Z ~ S_b S_a^-1 between nodes a and b in the FP64 srt layout of
+ * tb_sim3_ransac_batch_dev (the quaternion w x y z, then t, then s: X_b = s R X_a + t), and the weights of its information matrix
+ * diag(w_rot I3, w_trans I3, w_scale) over the residual (omega, upsilon, sigma). 96 bytes. */
+typedef struct tb_pg_sim3_edge {
+    int32_t a, b;
+    double srt[8];
+    double w_rot, w_trans, w_scale;
+} tb_pg_sim3_edge;
+
+/* What a Sim(3) graph query (tb_kf_store_sim3_graph_dev, tb_vo_loop_sim3_dev) hands back: device pointers into buffers the store
+ * owns, valid until its next graph query; nn = capacity + 1 nodes and edge slots a sequence. */
+typedef struct tb_sim3_graph_out {
+    int nn;
+    const int32_t* nnodes;        /* [nseq] live keyframes + 1 */
+    const int32_t* node_kf;       /* [nseq][nn] kf_id; the query frame's node: -2 (store) or the frame index (loop); -1 unused */
+    const double* before;         /* [nseq][nn][8] srt */
+    const double* after;          /* [nseq][nn][8] srt */
+    const tb_pg_sim3_edge* edges; /* [nseq][nn] */
+    const int32_t* edge_counts;   /* [nseq] */
+    const double* stats;          /* [nseq][8] tb_pose_graph_sim3_batch_dev's */
+} tb_sim3_graph_out;
+
 /* Error codes (0 = ok). */
 enum {
     TB_OK = 0,

@@ -22,6 +22,7 @@ SIM3_ROW = np.dtype([("X1", "<f4"), ("Y1", "<f4"), ("Z1", "<f4"), ("X2", "<f4"),
                      ("inv_sigma2_2", "<f4")])
 BA_OBS = np.dtype([("kf", "<i4"), ("pt", "<i4"), ("u", "<f4"), ("v", "<f4"), ("inv_sigma2", "<f4")])
 PG_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("w_rot", "<f8"), ("w_trans", "<f8")])
+PG_SIM3_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("srt", "<f8", (8,)), ("w_rot", "<f8"), ("w_trans", "<f8"), ("w_scale", "<f8")])
 CAMERA = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("width", "<i4"), ("height", "<i4"),
                    ("has_distortion", "<i4"), ("d", "<f4", (5,))])
 MAPPOINT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"), ("bad", "<i4")])
@@ -63,6 +64,7 @@ EXPORTS = [
     "tb_pnp_ransac", "tb_pnp_ransac_batch_dev", "tb_kf_store_pnp_enable", "tb_kf_store_pnp_state_dev", "tb_vo_reloc_pnp_enable",
     "tb_two_view", "tb_two_view_batch_dev", "tb_vo_mono_init_enable", "tb_vo_mono_init_state_dev",
     "tb_sim3_ransac", "tb_sim3_ransac_batch_dev", "tb_kf_store_sim3_dev", "tb_kf_store_sim3_state_dev", "tb_vo_relocalize_sim3_dev",
+    "tb_pose_graph_sim3", "tb_pose_graph_sim3_batch_dev", "tb_pose_graph_sim3_plan", "tb_kf_store_sim3_graph_dev", "tb_vo_loop_sim3_dev",
 ]
 
 TB_VOC_MAX_L = 8
@@ -329,6 +331,24 @@ def sim3_out(S, ncand, device):
     return so, t
 
 
+class Sim3GraphOut(C.Structure):
+    """tb_sim3_graph_out of include/tb_types.h: device pointers into the store's buffers"""
+    _fields_ = [("nn", C.c_int)] + [(n, C.c_void_p) for n in ("nnodes", "node_kf", "before", "after", "edges", "edge_counts", "stats")]
+
+
+def sim3_graph_tensors(go, S, device, copy):
+    """what a Sim3GraphOut points to, as torch VIEWS of the store's buffers or (copy) as copies made on the current stream:
+    dict(nnodes [S] int32, node_kf [S, nn] int32, before / after [S, nn, 8] float64 srt records, edges [S, nn, 96] uint8
+    (PG_SIM3_EDGE records), edge_counts [S], stats [S, 8] float64)"""
+    import torch
+    nn = go.nn
+    spec = dict(nnodes=((S,), "<i4", torch.int32), node_kf=((S, nn), "<i4", torch.int32), before=((S, nn, 8), "<f8", torch.float64),
+                after=((S, nn, 8), "<f8", torch.float64), edges=((S, nn, PG_SIM3_EDGE.itemsize), "|u1", torch.uint8),
+                edge_counts=((S,), "<i4", torch.int32), stats=((S, 8), "<f8", torch.float64))
+    out = {k: torch.as_tensor(_DevView(getattr(go, k), sh, ts), device=device).view(dt) for k, (sh, ts, dt) in spec.items()}
+    return {k: v.clone() for k, v in out.items()} if copy else out
+
+
 class TwoViewParams(C.Structure):
     """tb_two_view_params of include/tb_capi.h"""
     _fields_ = [("hypotheses", C.c_int), ("chi2_epi", C.c_double), ("refit", C.c_int), ("tri", TriangulateParams),
@@ -494,6 +514,15 @@ class VO:
         so, out = sim3_out(self.nseq, max(topk, 0), device)
         prm = sim3_params(**params)
         return lib().tb_vo_relocalize_sim3_dev(self._h, int(topk), C.byref(prm), int(min_consensus), C.byref(so)), out
+
+    def loop_sim3_dev(self, device, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
+        """tb_vo_loop_sim3_dev after relocalize_sim3_dev: (status code, sim3_graph_tensors' dict -- copies made on the current
+        stream, which the caller makes the loop's -- or None). fixed_scale is passed through as an int, so that the argument check
+        can be tested."""
+        go = Sim3GraphOut()
+        rc = lib().tb_vo_loop_sim3_dev(self._h, int(iters), int(fixed_scale), C.c_double(w_rot), C.c_double(w_trans), C.c_double(w_scale),
+                                       C.byref(go))
+        return rc, (sim3_graph_tensors(go, self.nseq, device, True) if rc == 0 else None)
 
     def reloc_pnp_enable(self, hypotheses=256, chi2_max=5.991, seed=0, min_consensus=10, expand=1):
         """tb_vo_reloc_pnp_enable: returns the status code (0 or a negative TB_E* code), so the state checks can be tested."""
@@ -1204,6 +1233,28 @@ class Context:
         return lib().tb_pose_graph_batch_dev(self._h, int(ngraphs), int(nnodes), int(nfixed), C.c_void_p(poses_ptr), C.c_void_p(edges_ptr),
                                              C.c_void_p(counts_ptr), int(edge_pitch), int(iters), C.c_void_p(stats_ptr or None))
 
+    def pose_graph_sim3(self, nodes, nfixed, edges, iters=10, fixed_scale=False):
+        """tb_pose_graph_sim3: one graph from host arrays. nodes [nnodes, 8] float64 srt records (the quaternion w x y z, t, s), the
+        first nfixed held; edges a PG_SIM3_EDGE array (pose_graph_sim3_edges builds one). Returns (nodes, stats [8]); a malformed
+        graph raises."""
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, 8).copy()
+        edges = np.ascontiguousarray(edges, PG_SIM3_EDGE).reshape(-1)
+        stats = np.zeros(8, np.float64)
+        self.check(lib().tb_pose_graph_sim3(self._h, len(nodes), int(nfixed), int(bool(fixed_scale)), _p(nodes),
+                                            _p(edges) if len(edges) else None, len(edges), int(iters), _p(stats)))
+        return nodes, stats
+
+    def pose_graph_sim3_plan(self, ngraphs, nnodes, nfixed, edge_pitch):
+        """tb_pose_graph_sim3_plan: size the work buffer for this shape ahead of time. Returns the status code."""
+        return lib().tb_pose_graph_sim3_plan(self._h, int(ngraphs), int(nnodes), int(nfixed), int(edge_pitch))
+
+    def pose_graph_sim3_dev(self, ngraphs, nnodes, nfixed, nodes_ptr, edges_ptr, counts_ptr, edge_pitch, iters, stats_ptr=0, fixed_scale=False):
+        """tb_pose_graph_sim3_batch_dev: device pointers (stats nullable), asynchronous on the context's stream. fixed_scale: a bool, or
+        an int handed through as it is. Returns the status code."""
+        return lib().tb_pose_graph_sim3_batch_dev(self._h, int(ngraphs), int(nnodes), int(nfixed), int(fixed_scale), C.c_void_p(nodes_ptr),
+                                                  C.c_void_p(edges_ptr), C.c_void_p(counts_ptr), int(edge_pitch), int(iters),
+                                                  C.c_void_p(stats_ptr or None))
+
 
 def pose_graph_edges(pairs, Z, w_rot=1.0, w_trans=1.0):
     """PG_EDGE records of the edges (a, b) in `pairs` with the measured motions Z [n, 4, 4] ~ T_b T_a^-1 (float64 rotation matrices,
@@ -1215,33 +1266,78 @@ def pose_graph_edges(pairs, Z, w_rot=1.0, w_trans=1.0):
     e["a"], e["b"] = pairs[:, 0], pairs[:, 1]
     e["w_rot"], e["w_trans"] = w_rot, w_trans
     for i, T in enumerate(Z):
-        R = T[:3, :3]
-        # the library's own extraction (po_quat_from_R of csrc/tb_se3.h, Eigen's Quaternion(Matrix3)): trace > 0, else the largest
-        # diagonal entry, ties to the lower index; then w >= 0 and unit norm, as the kernel normalises what it reads
-        q = np.zeros(4)
-        t = R[0, 0] + R[1, 1] + R[2, 2]
-        if t > 0:
-            t = np.sqrt(t + 1.0)
-            q[3] = 0.5 * t
-            t = 0.5 / t
-            q[0], q[1], q[2] = (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t
-        else:
-            k = 0
-            if R[1, 1] > R[0, 0]:
-                k = 1
-            if R[2, 2] > R[k, k]:
-                k = 2
-            j, l = (k + 1) % 3, (k + 2) % 3
-            t = np.sqrt(R[k, k] - R[j, j] - R[l, l] + 1.0)
-            q[k] = 0.5 * t
-            t = 0.5 / t
-            q[3] = (R[l, j] - R[j, l]) * t
-            q[j] = (R[j, k] + R[k, j]) * t
-            q[l] = (R[l, k] + R[k, l]) * t
-        if q[3] < 0:
-            q = -q
-        e["q"][i] = q / np.sqrt((q * q).sum())
+        e["q"][i] = _quat_xyzw_from_R(T[:3, :3])
         e["t"][i] = T[:3, 3]
+    return e
+
+
+def _quat_xyzw_from_R(R):
+    """the library's own extraction (po_quat_from_R of csrc/tb_se3.h, Eigen's Quaternion(Matrix3)): trace > 0, else the largest
+    diagonal entry, ties to the lower index; then w >= 0 and unit norm, as the kernels normalise what they read"""
+    q = np.zeros(4)
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0], q[1], q[2] = (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t
+    else:
+        k = 0
+        if R[1, 1] > R[0, 0]:
+            k = 1
+        if R[2, 2] > R[k, k]:
+            k = 2
+        j, l = (k + 1) % 3, (k + 2) % 3
+        t = np.sqrt(R[k, k] - R[j, j] - R[l, l] + 1.0)
+        q[k] = 0.5 * t
+        t = 0.5 / t
+        q[3] = (R[l, j] - R[j, l]) * t
+        q[j] = (R[j, k] + R[k, j]) * t
+        q[l] = (R[l, k] + R[k, l]) * t
+    if q[3] < 0:
+        q = -q
+    return q / np.sqrt((q * q).sum())
+
+
+def sim3_from_matrix(S):
+    """[n, 4, 4] (or [4, 4]) float64 matrices [[s R, t], [0, 1]] -> srt records [n, 8] (or [8]): the unit quaternion w x y z by the
+    kernels' rule (w >= 0), t, s = det(s R)^(1/3)"""
+    S = np.asarray(S, np.float64)
+    M = S.reshape(-1, 4, 4)
+    out = np.zeros((len(M), 8))
+    for i, A in enumerate(M):
+        s = np.cbrt(np.linalg.det(A[:3, :3]))
+        q = _quat_xyzw_from_R(A[:3, :3] / s)
+        out[i] = (q[3], q[0], q[1], q[2], A[0, 3], A[1, 3], A[2, 3], s)
+    return out.reshape(S.shape[:-2] + (8,))
+
+
+def sim3_to_matrix(srt):
+    """srt records [n, 8] (or [8]) -> float64 matrices [[s R, t], [0, 1]], the quaternion normalised as the kernels normalise it"""
+    srt = np.asarray(srt, np.float64)
+    V = srt.reshape(-1, 8)
+    out = np.zeros((len(V), 4, 4))
+    for i, v in enumerate(V):
+        w, x, y, z = v[:4] / np.sqrt((v[:4] ** 2).sum()) * (-1.0 if v[0] < 0 else 1.0)
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                      [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        out[i, :3, :3], out[i, :3, 3], out[i, 3, 3] = v[7] * R, v[4:7], 1.0
+    return out.reshape(srt.shape[:-1] + (4, 4))
+
+
+def pose_graph_sim3_edges(pairs, Z, w_rot=1.0, w_trans=1.0, w_scale=1.0):
+    """PG_SIM3_EDGE records of the edges (a, b) in `pairs` with the measured similarities Z ~ S_b S_a^-1, given as srt records
+    [n, 8] (copied as they are: a solver's best_srt stays byte for byte) or as matrices [n, 4, 4] [[s R, t], [0, 1]]
+    (sim3_from_matrix), and the weights (scalars or [n])"""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    Z = np.asarray(Z, np.float64)
+    Z = Z.reshape(-1, 8) if Z.shape[-1] == 8 else sim3_from_matrix(Z.reshape(-1, 4, 4))
+    assert len(Z) == len(pairs)
+    e = np.zeros(len(pairs), PG_SIM3_EDGE)
+    e["a"], e["b"] = pairs[:, 0], pairs[:, 1]
+    e["w_rot"], e["w_trans"], e["w_scale"] = w_rot, w_trans, w_scale
+    e["srt"] = Z
     return e
 
 
@@ -1518,6 +1614,24 @@ class KeyframeStore:
 
     def sim3(self, *a, **kw):
         rc, out = self.sim3_rc(*a, **kw)
+        self.ctx.check(rc)
+        return out
+
+    def sim3_graph_rc(self, q_Tcw, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
+        """tb_kf_store_sim3_graph_dev after a sim3 -> (status code, dict or None): the Sim(3) pose graph of the live keyframes and the
+        query frame q_Tcw [S, 4, 4] float32 with that query's winner as the loop edge, optimised on the device. The dict is
+        sim3_graph_tensors': nnodes, node_kf (the frame's node: -2), before, after, edges, edge_counts, stats -- torch VIEWS (not
+        copies) of the store's buffers, which the next graph query overwrites; the call is asynchronous on the context's stream,
+        so synchronise the context before reading them on another. A query: the store's rings and work do not change.
+        fixed_scale is passed through as an int, so that the argument check can be tested."""
+        assert q_Tcw is None or q_Tcw.is_contiguous()
+        go = Sim3GraphOut()
+        rc = lib().tb_kf_store_sim3_graph_dev(self._h, C.c_void_p(q_Tcw.data_ptr() if q_Tcw is not None else None), int(iters), int(fixed_scale),
+                                              C.c_double(w_rot), C.c_double(w_trans), C.c_double(w_scale), C.byref(go))
+        return rc, (sim3_graph_tensors(go, self.nseq, q_Tcw.device, False) if rc == 0 else None)
+
+    def sim3_graph(self, *a, **kw):
+        rc, out = self.sim3_graph_rc(*a, **kw)
         self.ctx.check(rc)
         return out
 

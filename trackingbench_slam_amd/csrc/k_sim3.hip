@@ -685,11 +685,13 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
 }
 
 /* Per sequence (one thread each): the candidate with the largest consensus, ties to the lower rank, candidates that are absent
- * left out; it is the answer when its consensus reaches min_consensus. best_rank -1: best_kf -1, the identity and scale 1. */
+ * left out; it is the answer when its consensus reaches min_consensus. best_rank -1: best_kf -1, the identity and scale 1.
+ * keep_kf / keep_srt (nullable): the store's own copy of best_kf / best_srt, which tb_kf_store_sim3_graph_dev reads. */
 __global__ void __launch_bounds__(256)
 k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_consensus,
               const float* __restrict__ cand_S12, const double* __restrict__ cand_srt, int32_t* __restrict__ best_rank,
-              int32_t* __restrict__ best_kf, float* __restrict__ best_S12, double* __restrict__ best_srt) {
+              int32_t* __restrict__ best_kf, float* __restrict__ best_S12, double* __restrict__ best_srt, int32_t* __restrict__ keep_kf,
+              double* __restrict__ keep_srt) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= nseq) return;
     int best = -1, most = -1;
@@ -707,6 +709,9 @@ k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict_
         for (int i = 0; i < 16; i++) best_S12[16 * (size_t)s + i] = best >= 0 ? cand_S12[16 * cb + i] : ((i & 3) == (i >> 2) ? 1.f : 0.f);
     if (best_srt)
         for (int i = 0; i < 8; i++) best_srt[8 * (size_t)s + i] = best >= 0 ? cand_srt[8 * cb + i] : ((i == 0 || i == 7) ? 1.0 : 0.0);
+    if (keep_kf) keep_kf[s] = best >= 0 ? cand_kf[cb] : -1;
+    if (keep_srt)
+        for (int i = 0; i < 8; i++) keep_srt[8 * (size_t)s + i] = best >= 0 ? cand_srt[8 * cb + i] : ((i == 0 || i == 7) ? 1.0 : 0.0);
 }
 
 int tbk_sim3_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_row* d_rows, const int32_t* d_counts, int pitch, int hypotheses,
@@ -733,7 +738,7 @@ int tbk_sim3_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_
 
 int tbk_sim3_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_cand_kf, const int32_t* d_cand_consensus,
                     const float* d_cand_S12, const double* d_cand_srt, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_S12,
-                    double* d_best_srt) {
+                    double* d_best_srt, int32_t* d_keep_kf, double* d_keep_srt) {
     return tb_launch(ctx, "k_sim3_select", k_sim3_select, dim3((nseq + 255) / 256), dim3(256), 0, nseq, ncand, min_consensus, d_cand_kf,
-                     d_cand_consensus, d_cand_S12, d_cand_srt, d_best_rank, d_best_kf, d_best_S12, d_best_srt);
+                     d_cand_consensus, d_cand_S12, d_cand_srt, d_best_rank, d_best_kf, d_best_S12, d_best_srt, d_keep_kf, d_keep_srt);
 }

@@ -1463,6 +1463,7 @@ int tb_kf_store_clear(tb_kf_store* st) {
     TB_HIP(ctx, hipMemsetAsync(st->fv_counts, 0, n * sizeof(int32_t), ctx->stream));
     TB_HIP(ctx, hipMemsetAsync(st->kf_ids, 0xff, n * sizeof(int32_t), ctx->stream));
     st->nadded = 0;
+    st->s3_best = false;   /* a winner of the ring that was: tb_kf_store_sim3_graph_dev needs a new Sim(3) query */
     return TB_OK;
 }
 
@@ -1710,6 +1711,8 @@ int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float 
         if (!st->s3_flags) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_flags, pairs));
         if (!st->s3_S12) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_S12, pairs * 16));
         if (!st->s3_srt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_srt, pairs * 8));
+        if (!st->s3_best_kf) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_best_kf, (size_t)st->nseq));
+        if (!st->s3_best_srt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->s3_best_srt, (size_t)st->nseq * 8));
         st->s3_ready = true;
     }
     static const tb_sim3_out none = {};
@@ -1723,8 +1726,54 @@ int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float 
                          st->s3_cnt, st->s3_kf, o.cand_rows));
     TB_TRY(tbk_sim3_batch(ctx, pairs, K, st->s3_rows, st->s3_cnt, st->pitch, prm->hypotheses, prm->fixed_scale, prm->chi2_max, prm->seed, S12, srt,
                           cons, st->s3_mask, nullptr, o.cand_flags ? o.cand_flags : st->s3_flags));
+    st->s3_best = false;   /* tb_kf_store_sim3_graph_dev needs the winner this call selects, if it selects one */
     if (!o.best_rank && !o.best_kf && !o.best_S12 && !o.best_srt) return TB_OK;
-    return tbk_sim3_select(ctx, st->nseq, ncand, min_consensus, st->s3_kf, cons, S12, srt, o.best_rank, o.best_kf, o.best_S12, o.best_srt);
+    TB_TRY(tbk_sim3_select(ctx, st->nseq, ncand, min_consensus, st->s3_kf, cons, S12, srt, o.best_rank, o.best_kf, o.best_S12, o.best_srt,
+                           st->s3_best_kf, st->s3_best_srt));
+    st->s3_best = true;
+    return TB_OK;
+}
+
+int tb_kf_store_sim3_graph_run(tb_kf_store* st, const char* who, const float* q_Tcw, int frame_id, int iters, int fixed_scale, double w_rot,
+                               double w_trans, double w_scale, tb_sim3_graph_out* out) {
+    tb_ctx* ctx = st->ctx;
+    const double w[3] = {w_rot, w_trans, w_scale};
+    bool wok = true;
+    for (double v : w) wok = wok && std::isfinite(v) && v >= 0.0;
+    if (!q_Tcw || !out || iters < 0 || iters > 99 || (fixed_scale != 0 && fixed_scale != 1) || !wok)
+        return tb_fail(ctx, TB_EINVAL, "%s: null arguments, iters %d (0..99), fixed_scale %d (0, 1) or a weight that is negative or not finite", who,
+                       iters, fixed_scale);
+    if (st->cap > 63) return tb_fail(ctx, TB_EINVAL, "%s: capacity %d, but a graph holds at most 64 nodes (capacity + 1)", who, st->cap);
+    if (!st->s3_best)
+        return tb_fail(ctx, TB_ESTATE, "%s: no tb_kf_store_sim3_dev has selected a winner (best_* outputs) since the store was made or cleared", who);
+    const int S = st->nseq, cap = st->cap, nn = cap + 1;
+    if (!st->g3_ready) {   /* the first call allocates and plans, later ones do not */
+        const size_t SN = (size_t)S * nn;
+        if (!st->g3_nnodes) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_nnodes, (size_t)S, 0));
+        if (!st->g3_ecount) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_ecount, (size_t)S, 0));
+        if (!st->g3_node_kf) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_node_kf, SN));
+        if (!st->g3_before) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_before, SN * 8));
+        if (!st->g3_after) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_after, SN * 8));
+        if (!st->g3_edges) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_edges, SN));
+        if (!st->g3_stats) TB_TRY(tb_dev_alloc(ctx, st->own, &st->g3_stats, (size_t)S * 8));
+        TB_TRY(tb_pose_graph_sim3_plan(ctx, S, nn, 1, nn));
+        st->g3_ready = true;
+    }
+    const int nlive = (int)std::min<long long>(st->nadded, cap), oldest = st->nadded >= cap ? (int)(st->nadded % cap) : 0;
+    TB_TRY(tbk_sim3_graph(ctx, S, cap, nlive, oldest, frame_id, w_rot, w_trans, w_scale, st->Tcw, st->kf_ids, q_Tcw, st->s3_best_kf,
+                          st->s3_best_srt, st->g3_before, st->g3_after, st->g3_node_kf, st->g3_nnodes, st->g3_edges, st->g3_ecount));
+    TB_TRY(tb_pose_graph_sim3_batch_dev(ctx, S, nn, 1, fixed_scale, st->g3_after, st->g3_edges, st->g3_ecount, nn, iters, st->g3_stats));
+    out->nn = nn;
+    out->nnodes = st->g3_nnodes; out->node_kf = st->g3_node_kf; out->before = st->g3_before; out->after = st->g3_after;
+    out->edges = st->g3_edges; out->edge_counts = st->g3_ecount; out->stats = st->g3_stats;
+    return TB_OK;
+}
+
+int tb_kf_store_sim3_graph_dev(tb_kf_store* st, const float* q_Tcw, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale,
+                               tb_sim3_graph_out* out) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    return tb_kf_store_sim3_graph_run(st, "tb_kf_store_sim3_graph_dev", q_Tcw, -2, iters, fixed_scale, w_rot, w_trans, w_scale, out);
 }
 
 int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const int32_t** row_counts, const uint8_t** inlier) {
@@ -2391,6 +2440,60 @@ int tb_pose_graph(tb_ctx* ctx, int nnodes, int nfixed, float* poses, const tb_pg
     TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) memcpy(stats, st, 64);
     if (st[7] < 0) return tb_fail(ctx, TB_EINVAL, "pose_graph: edges rejected by the device-side check");
+    return TB_OK;
+}
+
+int tb_pose_graph_sim3_plan(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int edge_pitch) {
+    TB_ENTER(ctx);
+    if (!ctx || ngraphs < 0 || nfixed < 1 || nfixed >= nnodes || edge_pitch < 1) return TB_EINVAL;
+    if (nnodes > 64 || edge_pitch > 256)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph_sim3: %d nodes, %d edges (at most 64, 256)", nnodes, edge_pitch);
+    void* dwork;
+    return ngraphs ? tb_scratch(ctx, TB_SLOT_WORK, tbk_pose_graph_sim3_work_bytes(ngraphs, nnodes, nfixed, edge_pitch), &dwork) : TB_OK;
+}
+
+int tb_pose_graph_sim3_batch_dev(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int fixed_scale, double* nodes,
+                                 const tb_pg_sim3_edge* edges, const int32_t* edge_counts, int edge_pitch, int iters, double* stats) {
+    TB_ENTER(ctx);
+    if (!ctx || !nodes || !edges || !edge_counts || ngraphs < 0 || nfixed < 1 || nfixed >= nnodes || edge_pitch < 1 || iters < 0 ||
+        (fixed_scale != 0 && fixed_scale != 1))
+        return TB_EINVAL;
+    if (nnodes > 64 || edge_pitch > 256 || iters > 99)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph_sim3: %d nodes, %d edges, %d iterations (at most 64, 256, 99)", nnodes, edge_pitch,
+                       iters);
+    if (ngraphs == 0) return TB_OK;
+    void* dwork;
+    TB_TRY(tb_scratch(ctx, TB_SLOT_WORK, tbk_pose_graph_sim3_work_bytes(ngraphs, nnodes, nfixed, edge_pitch), &dwork));
+    return tbk_pose_graph_sim3_batch(ctx, ngraphs, nnodes, nfixed, fixed_scale, nodes, edges, edge_counts, edge_pitch, iters, stats, dwork);
+}
+
+int tb_pose_graph_sim3(tb_ctx* ctx, int nnodes, int nfixed, int fixed_scale, double* nodes, const tb_pg_sim3_edge* edges, int nedges,
+                       int iters, double* stats) {
+    TB_ENTER(ctx);
+    if (!ctx || !nodes || (!edges && nedges > 0) || nedges < 0 || nfixed < 1 || nfixed >= nnodes || iters < 0 ||
+        (fixed_scale != 0 && fixed_scale != 1))
+        return TB_EINVAL;
+    if (nnodes > 64 || nedges > 256 || iters > 99)
+        return tb_fail(ctx, TB_EUNSUPPORTED, "pose_graph_sim3: %d nodes, %d edges, %d iterations (at most 64, 256, 99)", nnodes, nedges, iters);
+    const int pitch = std::max(nedges, 1);
+    size_t end = 0;
+    const size_t oNodes = stage_piece(end, (size_t)nnodes * 64), oEdges = stage_piece(end, (size_t)pitch * sizeof(tb_pg_sim3_edge)),
+                 oStats = stage_piece(end, 64), oCnt = stage_piece(end, 4);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    TB_UPLOAD(ctx, b + oNodes, nodes, (size_t)nnodes * 64);
+    TB_UPLOAD(ctx, b + oEdges, edges, (size_t)nedges * sizeof(tb_pg_sim3_edge));
+    TB_UPLOAD(ctx, b + oCnt, &nedges, 4);
+    if ((rc = tb_pose_graph_sim3_batch_dev(ctx, 1, nnodes, nfixed, fixed_scale, (double*)(b + oNodes), (const tb_pg_sim3_edge*)(b + oEdges),
+                                           (const int32_t*)(b + oCnt), pitch, iters, (double*)(b + oStats))))
+        return rc;
+    double st[8];
+    TB_DOWNLOAD(ctx, nodes, b + oNodes, (size_t)nnodes * 64);
+    TB_DOWNLOAD(ctx, st, b + oStats, 64);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) memcpy(stats, st, 64);
+    if (st[7] < 0) return tb_fail(ctx, TB_EINVAL, "pose_graph_sim3: nodes or edges rejected by the device-side check");
     return TB_OK;
 }
 

@@ -299,7 +299,22 @@ struct tb_kf_store {
     int32_t *s3_cnt = nullptr, *s3_kf = nullptr, *s3_cons = nullptr, *s3_flags = nullptr;   /* [pairs] */
     float* s3_S12 = nullptr;                                 /* [pairs][16] */
     double* s3_srt = nullptr;                                /* [pairs][8] */
+    /* the Sim(3) graph query (tb_kf_store_sim3_graph_dev): the store's own copy of the last Sim(3) query's best_kf / best_srt (the
+     * caller's are nullable and may be gone by then; s3_best: that query selected a winner into them), and the graph's buffers,
+     * allocated with the solver's plan by the first graph query; nn = cap + 1 */
+    bool s3_best = false, g3_ready = false;
+    int32_t* s3_best_kf = nullptr;                           /* [nseq] */
+    double* s3_best_srt = nullptr;                           /* [nseq][8] */
+    int32_t *g3_nnodes = nullptr, *g3_ecount = nullptr;      /* [nseq] */
+    int32_t* g3_node_kf = nullptr;                           /* [nseq][nn] */
+    double *g3_before = nullptr, *g3_after = nullptr;        /* [nseq][nn][8] */
+    tb_pg_sim3_edge* g3_edges = nullptr;                     /* [nseq][nn] */
+    double* g3_stats = nullptr;                              /* [nseq][8] */
 };
+
+/* tb_kf_store_sim3_graph_dev with the id the query frame's node is given (the public entry: -2; the VO loop: its frame index) */
+extern "C" int tb_kf_store_sim3_graph_run(tb_kf_store* st, const char* who, const float* q_Tcw, int frame_id, int iters, int fixed_scale, double w_rot,
+                               double w_trans, double w_scale, tb_sim3_graph_out* out);
 
 /* kernel launchers (k_*.hip) */
 int tbk_resize_level(tb_extractor* ex, int level, int n);
@@ -412,6 +427,16 @@ size_t tbk_local_ba_work_bytes(const tb_ctx* ctx, int W, int nkf, int nfixed, in
 size_t tbk_pose_graph_work_bytes(int ngraphs, int nnodes, int nfixed, int edge_pitch);
 int tbk_pose_graph_batch(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, float* d_poses, const tb_pg_edge* d_edges,
                          const int32_t* d_counts, int edge_pitch, int iters, double* d_stats, void* d_work);
+/* Sim(3) pose-graph optimisation (k_pgo_sim3.hip): as above on srt nodes [nnodes][8]; d_work: tbk_pose_graph_sim3_work_bytes */
+size_t tbk_pose_graph_sim3_work_bytes(int ngraphs, int nnodes, int nfixed, int edge_pitch);
+int tbk_pose_graph_sim3_batch(tb_ctx* ctx, int ngraphs, int nnodes, int nfixed, int fixed_scale, double* d_nodes,
+                              const tb_pg_sim3_edge* d_edges, const int32_t* d_counts, int edge_pitch, int iters, double* d_stats,
+                              void* d_work);
+/* the Sim(3) graph of a store's live keyframes and a query frame (k_pgo_sim3.hip): k_vo_loop_graph's rules on srt nodes, the loop
+ * edge the kept best_srt byte for byte */
+int tbk_sim3_graph(tb_ctx* ctx, int nseq, int cap, int nlive, int oldest, int frame_id, double w_rot, double w_trans, double w_scale,
+                   const float* s_Tcw, const int32_t* s_kf_ids, const float* q_Tcw, const int32_t* best_kf, const double* best_srt,
+                   double* before, double* after, int32_t* node_kf, int32_t* nnodes, tb_pg_sim3_edge* edges, int32_t* ecount);
 /* loop correction in the VO loop (k_pgo.hip): the graph of the stored keyframes (ring slots (oldest + i) % cap, i < nlive) and the
  * current frame, cap + 1 nodes and edge pitch cap + 1 per sequence; and the adoption of the solver's poses */
 int tbk_vo_loop_graph(tb_ctx* ctx, int nseq, int cap, int nlive, int oldest, int frame, int topk, double w_rot, double w_trans,
@@ -528,7 +553,7 @@ int tbk_sim3_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_
                   tb_sim3_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf, int32_t* d_rows_out);
 int tbk_sim3_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_cand_kf, const int32_t* d_cand_consensus,
                     const float* d_cand_S12, const double* d_cand_srt, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_S12,
-                    double* d_best_srt);
+                    double* d_best_srt, int32_t* d_keep_kf, double* d_keep_srt);
 /* tb_sim3_ransac_batch_dev's parameter rules, for the entry points around it */
 static inline bool tb_sim3_params_ok(const tb_sim3_params* prm) {
     return prm->hypotheses >= 1 && prm->hypotheses <= 1024 && (prm->fixed_scale == 0 || prm->fixed_scale == 1) && prm->chi2_max >= 0.0 &&

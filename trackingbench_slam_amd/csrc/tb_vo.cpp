@@ -77,6 +77,7 @@ struct tb_vo {
     int32_t *rl_top_slot = nullptr, *rl_top_kf = nullptr;   /* [nseq][max_candidates] */
     const int32_t* s3_slot = nullptr;                       /* the top_slot of the tb_vo_relocalize_dev since the last step (null: none), */
     int s3_topk = 0;                                        /* and its topk: what tb_vo_relocalize_sim3_dev runs on */
+    bool s3_done = false;                                   /* a tb_vo_relocalize_sim3_dev since the last step: tb_vo_loop_sim3_dev may run */
     /* recovery (tb_vo_recover_enable): the flags and the selection of the last step, the per-sequence tracking keyframe, the
      * masked candidates, and the rings of the keyframes' word / node ids, ring-aligned with the store */
     bool rec_on = false;
@@ -433,6 +434,7 @@ int tb_vo_reset_dev(tb_vo* vo, const float* Tcw0) {
     if (vo->mi_on) TB_TRY(vo_mono_init_clear(vo));
     vo->next = 0;
     vo->s3_slot = nullptr;
+    vo->s3_done = false;
     vo->ragged = false;
     std::fill(vo->seq_frame.begin(), vo->seq_frame.end(), -1);
     std::fill(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end(), -1);
@@ -878,6 +880,7 @@ static int vo_step_lock(tb_vo* vo, int t, bool keyframe, const uint8_t* left, co
     vo->cur = b;
     vo->next = t + 1;
     vo->s3_slot = nullptr;   /* a Sim(3) query needs a tb_vo_relocalize_dev of this frame */
+    vo->s3_done = false;
     for (int s = 0; s < S; s++) {
         vo->seq_frame[s] = t;
         if (keyframe) vo->seq_kf_frame[s] = t;
@@ -964,6 +967,7 @@ int tb_vo_reset_seq_dev(tb_vo* vo, const uint8_t* which, const float* Tcw0) {
     vo->ragged = true;
     vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
     vo->s3_slot = nullptr;
+    vo->s3_done = false;
     vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
     return TB_OK;
 }
@@ -1032,6 +1036,7 @@ int tb_vo_step_ragged_dev(tb_vo* vo, const uint8_t* left, const uint8_t* right, 
     vo->ragged = true;
     vo->next = 1 + *std::max_element(vo->seq_frame.begin(), vo->seq_frame.end());
     vo->s3_slot = nullptr;
+    vo->s3_done = false;
     vo->kf_frame = *std::max_element(vo->seq_kf_frame.begin(), vo->seq_kf_frame.end());
     return TB_OK;
 }
@@ -1189,8 +1194,21 @@ int tb_vo_relocalize_sim3_dev(tb_vo* vo, int topk, const tb_sim3_params* prm, in
         return tb_fail(ctx, TB_EINVAL, "tb_vo_relocalize_sim3_dev: topk %d, but the last tb_vo_relocalize_dev ran with %d", topk, vo->s3_topk);
     const tb_vo_frame_out& o = vo->out[vo->oc];
     const int c = vo->cur;
-    return tb_kf_store_sim3_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_cnt, vo->mp[c], vo->valid[c], vo->P, vo->Tcw[c],
-                                vo->s3_slot, vo->s3_topk, prm, min_consensus, out);
+    vo->s3_done = false;
+    TB_TRY(tb_kf_store_sim3_dev(vo->store, vo->p.K, vo->p.nlevels, vo->p.scale, o.orb, o.orb_cnt, vo->mp[c], vo->valid[c], vo->P, vo->Tcw[c],
+                                vo->s3_slot, vo->s3_topk, prm, min_consensus, out));
+    vo->s3_done = true;
+    return TB_OK;
+}
+
+int tb_vo_loop_sim3_dev(tb_vo* vo, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale, tb_sim3_graph_out* out) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_sim3_dev: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (!vo->s3_done) return tb_fail(ctx, TB_ESTATE, "tb_vo_loop_sim3_dev: no tb_vo_relocalize_sim3_dev since the last step");
+    return tb_kf_store_sim3_graph_run(vo->store, "tb_vo_loop_sim3_dev", vo->Tcw[vo->cur], vo->next - 1, iters, fixed_scale, w_rot, w_trans,
+                                      w_scale, out);
 }
 
 int tb_vo_reloc_pnp_enable(tb_vo* vo, const tb_pnp_params* prm, int min_consensus, int expand) {

@@ -613,6 +613,23 @@ class StereoVO:
             t.record_stream(self.stream)
         return out
 
+    def loop_sim3(self, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
+        """After relocalize_sim3(...): the Sim(3) pose graph of the stored keyframes and the current frame, the Sim(3) winner as the
+        loop edge (the node of best_kf -> the frame's node, Z = best_srt), optimised by the device solver. Device tensors, copies:
+        nnodes [S] = live keyframes + 1, node_kf [S, N + 1] (the frame index for the current frame, -1 unused), before / after
+        [S, N + 1, 8] float64 srt nodes (the quaternion w x y z, t, s), edges [S, N + 1, 96] uint8 (capi.PG_SIM3_EDGE records),
+        edge_counts [S] (0: no winner, or fewer than 2 stored keyframes), stats [S, 8] float64 (stats[7] = -1: the winner's
+        keyframe has left the ring). fixed_scale=True suits a stereo map. A query: no state tensor changes -- adopting the corrected
+        nodes is not done here. No host synchronisation."""
+        self._need_store()
+        with torch.cuda.stream(self.stream):
+            rc, out = self.vo.loop_sim3_dev(self.dev, iters, fixed_scale, w_rot, w_trans, w_scale)
+        self.ctx.check(rc)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        return out
+
     def recovery(self):
         """The recovery state after the last step (recover=...): dict(lost [S] uint8 and track_inliers [S] int32 -- the tracker's own
         inlier count, before any adoption --, recovered_kf [S] int32 = the frame index of the keyframe the sequence adopted in
