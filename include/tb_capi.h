@@ -527,6 +527,52 @@ int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float 
 int tb_kf_store_sim3_graph_dev(tb_kf_store* st, const float* q_Tcw, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale,
                                tb_sim3_graph_out* out);
 int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const int32_t** row_counts, const uint8_t** inlier);
+/* The Sim(3) query's candidates refined on pixels: tb_sim3_optimize_batch_dev on every candidate pair of the last
+ * tb_kf_store_sim3_dev (tests/reloc_sim3_opt_reference.py is the composition on the CPU). The caller passes the
+ * arguments of that Sim(3) query again -- K, the query frames' keys, map points and poses, cand_slot, ncand -- and nothing may have
+ * changed in between. Stages, each one launch:
+ *   rows    the pixel rows tb_sim3_obs_row by the Sim(3) query's own row rule (the same kernel, instantiated for the other row
+ *           type: same keys, same order), so row i of a pair is row i of the store's tb_sim3_row list and the RANSAC mask lines
+ *           up; (u1, v1) and (u2, v2) are the two keys' x, y, as tb_reloc_rows_dev takes them for its tb_obs rows
+ *   seeds   a pair with no candidate, or with a consensus below 3, is skipped: it runs as an empty problem from the identity;
+ *           every other pair's seed is its cand_srt
+ *   refine  tb_sim3_optimize_batch_dev's kernel on the nseq * ncand problems, the active rows the Sim(3) query's inlier masks,
+ *           fixed_scale and the other parameters the caller's (min_keep >= 1)
+ *   select  the four outputs of every candidate, and of the candidate the Sim(3) query selected (its rule and its min_consensus;
+ *           the selection is unchanged); a skipped pair is flagged stats[7] = 2 and has the identity, as has best_* where
+ *           nothing was selected. With use_for_graph = 1, where the selected candidate ran (stats[7] = 0) and its refined inliers
+ *           reach min_inliers (ORB-SLAM asks for 20), the store's own copy of best_srt takes the refined srt: that is the copy
+ *           tb_kf_store_sim3_graph_dev reads, so the next graph query has the refined transform as its loop edge. With
+ *           use_for_graph = 0 nothing of the store changes but this query's own buffers
+ * cand_srt [nseq][ncand][8] and cand_consensus [nseq][ncand]: what the Sim(3) query wrote; each is NULL where that query was not
+ * given that output, so that it is in the store's own buffer. tb_sim3_refine_out (every pointer nullable, device): cand_srt
+ * [nseq][ncand][8], cand_S12 [nseq][ncand][16], cand_inliers [nseq][ncand], cand_stats [nseq][ncand][8]; best_srt [nseq][8],
+ * best_S12 [nseq][16], best_inliers [nseq], best_stats [nseq][8]. Asynchronous, no host synchronisation; the first call may
+ * allocate the query's buffers, a store that never calls it launches and holds what it did before.
+ * TB_ESTATE: no tb_kf_store_sim3_dev since the store was made or cleared, or a tb_relocalize_batch_dev since that query (its
+ * match lists are no longer the ones the query's masks and seeds belong to); cand_srt or cand_consensus NULL although the Sim(3)
+ * query wrote it elsewhere; a best_* output or use_for_graph = 1 although the Sim(3) query selected nothing. TB_EINVAL: as
+ * tb_sim3_optimize_batch_dev and tb_kf_store_sim3_dev, min_keep < 1, min_inliers < 0, use_for_graph not 0 or 1.
+ * tb_kf_store_sim3_refine_state_dev lends device views of the last call's pixel rows [pairs][pitch], row_counts [pairs], the active
+ * masks it started from (the Sim(3) query's) and the final inlier masks [pairs][pitch] (each nullable). TB_ESTATE before the first
+ * tb_kf_store_sim3_refine_dev. */
+struct tb_sim3_opt_params;   /* below, with tb_sim3_optimize_batch_dev */
+typedef struct tb_sim3_refine_out {
+    double* cand_srt;
+    float* cand_S12;
+    int32_t* cand_inliers;
+    double* cand_stats;
+    double* best_srt;
+    float* best_S12;
+    int32_t* best_inliers;
+    double* best_stats;
+} tb_sim3_refine_out;
+int tb_kf_store_sim3_refine_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts,
+                                const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch, const float* q_Tcw, const int32_t* cand_slot,
+                                int ncand, const double* cand_srt, const int32_t* cand_consensus, const struct tb_sim3_opt_params* params,
+                                int min_inliers, int use_for_graph, const tb_sim3_refine_out* out);
+int tb_kf_store_sim3_refine_state_dev(tb_kf_store* st, const tb_sim3_obs_row** rows, const int32_t** row_counts, const uint8_t** active,
+                                      const uint8_t** inlier);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -740,6 +786,71 @@ int tb_sim3_ransac_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], cons
                              int32_t* flags);
 int tb_sim3_ransac(tb_ctx* ctx, const double K[4], const tb_sim3_row* rows, int n, const tb_sim3_params* params, float S12[16],
                    double srt[8], int* consensus, uint8_t* inlier, int32_t winner[2], int* flags);
+/* The non-linear refinement of a similarity on pixels: ORB-SLAM's Optimizer::OptimizeSim3, which LoopClosing runs on the
+ * Sim3Solver's winner before the transform becomes the pose graph's loop edge; batched and device-resident. The reference has no
+ * such step. tb_sim3_ransac_batch_dev never sees a pixel and fits in 3D, where every point counts the same although a stereo
+ * point's depth error grows with Z^2; this entry minimises the reprojection error in both images instead (DESIGN.md 9p has the
+ * derivation and what it buys; tests/sim3_opt_reference.py is the definition, statement for statement).
+ * Problem p reads counts[p] rows tb_sim3_obs_row (a tb_sim3_row's X1 Y1 Z1, X2 Y2 Z2, then the pixels u1 v1 and u2 v2 of the two
+ * keys that observe the point, then inv_sigma2_1, inv_sigma2_2) at rows + p * pitch; a count below 0 is clamped to 0, one above
+ * pitch to pitch. K = fx, fy, cx, cy (host) serves both cameras, proj(X) = (fx X / Z + cx, fy Y / Z + cy). The unknown is one
+ * S12 = (s, R12, t12), X1 = s R12 X2 + t12, read from srt_in + 8 p and written to srt_out + 8 p in tb_sim3_ransac_batch_dev's srt
+ * layout (FP64: the unit quaternion w x y z, t12, s; srt_out may be srt_in), and to S12 + 16 p as the float32 [s R12 | t12; 0 0 0 1].
+ *   cost      with Q1 = s R12 X2 + t12 and Q2 = S12^-1 X1 = R12' (X1 - t12) / s a row has ORB-SLAM's two edges
+ *             e12 = (u1, v1) - proj(Q1), chi2 c1 = inv_sigma2_1 |e12|^2, and e21 = (u2, v2) - proj(Q2), c2 = inv_sigma2_2 |e21|^2.
+ *             Each goes under g2o's Huber kernel with delta = sqrt(th2): rho(c) = c and rho' = 1 where sqrt(c) <= delta, otherwise
+ *             rho(c) = 2 sqrt(c) delta - th2 and rho' = delta / sqrt(c). The robust chi2 is the sum of rho over both edges of
+ *             the active rows. A transform that takes an active row's Q1z or Q2z to 0 or below has chi2 = +inf
+ *   update    S <- Exp(delta) S, delta = (omega, upsilon, sigma), with tb_pose_graph_sim3_batch_dev's Exp
+ *   Jacobians exact: dQ1 / ddelta = [-[Q1]x | I | Q1], dQ2 / ddelta = -(1 / s) R12' [-[X1]x | I | X1], each chained through
+ *             -P(Q), P(Q) = (fx / Z, 0, -fx X / Z^2; 0, fy / Z, -fy Y / Z^2). H = sum J' (w rho') J, g = -sum J' (w rho') e.
+ *             With fixed_scale = 1 the unknowns are the six (omega, upsilon), sigma = 0, and s keeps its bytes
+ *   sums      row i belongs to thread i mod 256; a thread adds its rows t, t + 256, ... in ascending order to 0.0 and the 256
+ *             partial sums meet in the butterfly p[t] = p[t] + p[t ^ d], d = 1, 2, 4, ..., 128 (tb_sim3_ransac_batch_dev's rule):
+ *             28 + 7 sums for a linearisation, 1 for a trial's chi2. No floating-point atomic anywhere
+ *   LM        one round of `iters` iterations is tb_pose_graph_batch_dev's rule, unchanged: lambda0 = 1e-5 max |diag H| at the
+ *             round's first iteration (g2o's initialisation); a trial solves (H + lambda I) x = g by an un-pivoted Cholesky (a
+ *             failed factorisation is a trial of chi2 DBL_MAX) and is judged on the exact robust chi2 of Exp(x) S:
+ *             rho = (chi2 - trial) / (x . (lambda x + g) + 1e-3); accepted on rho > 0 and a finite trial, then
+ *             lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)), nu = 2; otherwise lambda *= nu, nu *= 2; at most 10 trials an
+ *             iteration; the round stops after 10 rejections, at rho == 0 or after `iters`
+ *   procedure (ORB-SLAM's) 0. the seed's quaternion is normalised (w >= 0). The rows that start active are those of active_in
+ *             [nproblems][pitch] bytes (NULL: every row; tb_sim3_ransac_batch_dev's mask is the intended input) below the count;
+ *             of these a row with a non-finite field, with Z1 or Z2 not above 0, or with Q1z or Q2z not above 0 under the seed
+ *             is dropped (stats[5] counts them). 1. Fewer than min_keep rows active: the problem stops as in 3. Otherwise
+ *             iters_first LM iterations on the active rows, both edges of each. 2. A row is bad where either of its two edges'
+ *             plain chi2 exceeds th2 under the result; bad rows leave, both edges together; nBad is their count. 3. If fewer
+ *             than min_keep rows stay the problem stops: inliers 0, an all-zero mask, srt_out is srt_in byte for byte, S12 the
+ *             seed's, stats[7] = 1. 4. Otherwise a second round, lambda starting anew as in a second g2o optimize(): iters_bad
+ *             iterations if nBad > 0, else iters_clean. 5. The mask marks the rows still active whose two chi2 are both at most
+ *             th2 under the final transform; inliers is their count. A problem that accepted no trial returns srt_in byte for byte
+ *   malformed a seed with a non-finite entry, a zero quaternion (or one whose norm is not finite) or s not above 0:
+ *             stats[7] = -1, srt_out is srt_in byte for byte, S12 the identity, inliers 0, an all-zero mask, the other stats 0
+ * Out (device): srt_out [nproblems][8] double, S12 [nproblems][16] float, inliers [nproblems] and stats [nproblems][8] double are
+ * nullable; inlier_mask [nproblems][pitch] bytes is not: a thread keeps its rows' active flags there during the call (it may be
+ * the buffer active_in points to, which is then overwritten). stats = iterations run, initial robust chi2 (the starting rows
+ * under the seed), final robust chi2 (the rows left, under the final transform), trials, nBad, dropped rows, final lambda, flag
+ * (0, 1 = stopped below min_keep, -1 = malformed). Asynchronous on the context's stream, no host synchronisation, no host <->
+ * device copy, no work buffer: one launch (k_sim3_opt) of one 256-thread workgroup per problem; a problem gives the same bits
+ * alone, at any batch position and from run to run. At most 65535 problems per call (TB_EUNSUPPORTED). TB_EINVAL: null rows /
+ * counts / K / params / srt_in / inlier_mask, pitch < 1, K not finite, fx or fy not positive, fixed_scale not 0 or 1, th2 negative
+ * or not finite, an iteration count outside 0..99, min_keep < 0.
+ * tb_sim3_optimize: the host form, one problem of n rows on the batched entry (host pointers; active nullable [n]; srt_in and
+ * srt_out [8]; S12 [16]; inlier_mask [n] and stats [8] nullable). */
+typedef struct tb_sim3_opt_params {
+    double th2;          /* 10.0: ORB-SLAM's (LoopClosing passes 10). A default, not a measurement */
+    int iters_first;     /* 0..99; 5 */
+    int iters_bad;       /* 0..99; 10: the second round when the first left bad rows */
+    int iters_clean;     /* 0..99; 5: the second round otherwise */
+    int min_keep;        /* >= 0; 10 */
+    int fixed_scale;     /* 0 | 1; a stereo map has a metric scale: 1 */
+} tb_sim3_opt_params;
+int tb_sim3_optimize_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_obs_row* rows, const int32_t* counts, int pitch,
+                               const uint8_t* active_in, const double* srt_in, const tb_sim3_opt_params* params, double* srt_out,
+                               float* S12, int32_t* inliers, uint8_t* inlier_mask, double* stats);
+int tb_sim3_optimize(tb_ctx* ctx, const double K[4], const tb_sim3_obs_row* rows, int n, const uint8_t* active, const double srt_in[8],
+                     const tb_sim3_opt_params* params, double srt_out[8], float S12[16], int* inliers, uint8_t* inlier_mask,
+                     double stats[8]);
 /* A relative pose and first points from 2D-2D rows alone: 8-point hypotheses in a RANSAC, a least-squares refit, the four
  * decompositions of E told apart by triangulation; batched and device-resident. The reference has no such step (its
  * LinearTriangle is handed poses); this is ORB-SLAM's Initializer on its fundamental-matrix branch (DESIGN.md 9m has the
@@ -1227,6 +1338,17 @@ int tb_vo_relocalize_sim3_dev(tb_vo* vo, int topk, const struct tb_sim3_params* 
  * tb_vo_relocalize_sim3_dev since the last step (every step and reset invalidates it). No state of the loop or the store changes:
  * adopting the corrected nodes is left to a later change. */
 int tb_vo_loop_sim3_dev(tb_vo* vo, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale, tb_sim3_graph_out* out);
+/* tb_vo_refine_sim3_dev is a query after tb_vo_relocalize_sim3_dev: tb_kf_store_sim3_refine_dev with the same arguments that call
+ * made -- the loop's current ORB keys, its carried map points and pose, the candidates of the last tb_vo_relocalize_dev. cand_srt /
+ * cand_consensus: what tb_vo_relocalize_sim3_dev wrote (NULL for one it kept in the store). topk: that of the last
+ * tb_vo_relocalize_dev, which sizes every input and output; any other count is TB_EINVAL. TB_ESTATE: relocalisation not enabled, or
+ * no tb_vo_relocalize_sim3_dev since the last step (every step and reset invalidates it), or a tb_vo_relocalize_dev since that query
+ * (the match lists are no longer the ones its masks and seeds belong to). With use_for_graph = 0 no state of the
+ * loop or the store changes, and a loop that never calls it ends in the same bytes; with 1 the next tb_vo_loop_sim3_dev takes the
+ * refined transform as its loop edge. */
+struct tb_sim3_opt_params;
+int tb_vo_refine_sim3_dev(tb_vo* vo, int topk, const double* cand_srt, const int32_t* cand_consensus, const struct tb_sim3_opt_params* params,
+                          int min_inliers, int use_for_graph, const tb_sim3_refine_out* out);
 /* tb_kf_store_pnp_enable on the loop's store: tb_vo_relocalize_dev then runs the PnP verification (tb_kf_store_pnp_state_dev on
  * tb_vo_kf_store_get's store lends its per-pair outputs) and stays a query that changes no state tensor. TB_ESTATE: relocalisation
  * not enabled, after the first step, enabled already, or together with tb_vo_recover_enable / tb_vo_loop_enable in either order:

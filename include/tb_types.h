@@ -55,6 +55,17 @@ typedef struct tb_sim3_row {
     float inv_sigma2_1, inv_sigma2_2;
 } tb_sim3_row;
 
+/* One pixel row of the Sim(3) optimiser (tb_sim3_optimize_batch_dev), 48 bytes: a tb_sim3_row's two points, then the pixels
+ * (u1, v1) and (u2, v2) of the two keys that observe the point, then the two keys' invLevelSigma2. The first six fields and
+ * the two weights mean what they mean in tb_sim3_row. */
+typedef struct tb_sim3_obs_row {
+    float X1, Y1, Z1;
+    float X2, Y2, Z2;
+    float u1, v1;
+    float u2, v2;
+    float inv_sigma2_1, inv_sigma2_2;
+} tb_sim3_obs_row;
+
 /* Pinhole camera as the projection matchers use it (reference PinholeCamera, CameraModel.cpp:63-93 and
  * CameraModel.h:33-39): focal lengths, principal point, image size for IsInFrame, and the radial-tangential
  * coefficients d[0..4] (k1 k2 p1 p2 k3) applied iff has_distortion. */

@@ -20,6 +20,8 @@ CORNER = np.dtype([("x", "<i4"), ("y", "<i4"), ("score", "<i4")])
 OBS = np.dtype([("u", "<f4"), ("v", "<f4"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("inv_sigma2", "<f4")])
 SIM3_ROW = np.dtype([("X1", "<f4"), ("Y1", "<f4"), ("Z1", "<f4"), ("X2", "<f4"), ("Y2", "<f4"), ("Z2", "<f4"), ("inv_sigma2_1", "<f4"),
                      ("inv_sigma2_2", "<f4")])
+SIM3_OBS_ROW = np.dtype([("X1", "<f4"), ("Y1", "<f4"), ("Z1", "<f4"), ("X2", "<f4"), ("Y2", "<f4"), ("Z2", "<f4"), ("u1", "<f4"), ("v1", "<f4"),
+                         ("u2", "<f4"), ("v2", "<f4"), ("inv_sigma2_1", "<f4"), ("inv_sigma2_2", "<f4")])
 BA_OBS = np.dtype([("kf", "<i4"), ("pt", "<i4"), ("u", "<f4"), ("v", "<f4"), ("inv_sigma2", "<f4")])
 PG_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("w_rot", "<f8"), ("w_trans", "<f8")])
 PG_SIM3_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("srt", "<f8", (8,)), ("w_rot", "<f8"), ("w_trans", "<f8"), ("w_scale", "<f8")])
@@ -64,6 +66,8 @@ EXPORTS = [
     "tb_pnp_ransac", "tb_pnp_ransac_batch_dev", "tb_kf_store_pnp_enable", "tb_kf_store_pnp_state_dev", "tb_vo_reloc_pnp_enable",
     "tb_two_view", "tb_two_view_batch_dev", "tb_vo_mono_init_enable", "tb_vo_mono_init_state_dev",
     "tb_sim3_ransac", "tb_sim3_ransac_batch_dev", "tb_kf_store_sim3_dev", "tb_kf_store_sim3_state_dev", "tb_vo_relocalize_sim3_dev",
+    "tb_sim3_optimize", "tb_sim3_optimize_batch_dev", "tb_kf_store_sim3_refine_dev", "tb_kf_store_sim3_refine_state_dev",
+    "tb_vo_refine_sim3_dev",
     "tb_pose_graph_sim3", "tb_pose_graph_sim3_batch_dev", "tb_pose_graph_sim3_plan", "tb_kf_store_sim3_graph_dev", "tb_vo_loop_sim3_dev",
 ]
 
@@ -313,6 +317,36 @@ def sim3_params(hypotheses=256, fixed_scale=False, chi2_max=9.210, seed=0):
     return Sim3Params(int(hypotheses), int(fixed_scale), float(chi2_max), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
+class Sim3OptParams(C.Structure):
+    """tb_sim3_opt_params of include/tb_capi.h"""
+    _fields_ = [("th2", C.c_double), ("iters_first", C.c_int), ("iters_bad", C.c_int), ("iters_clean", C.c_int), ("min_keep", C.c_int),
+                ("fixed_scale", C.c_int)]
+
+
+def sim3_opt_params(th2=10.0, iters_first=5, iters_bad=10, iters_clean=5, min_keep=10, fixed_scale=False):
+    """a Sim3OptParams with the defaults of include/tb_capi.h; fixed_scale is passed through as an int, so that the argument check
+    can be tested"""
+    return Sim3OptParams(float(th2), int(iters_first), int(iters_bad), int(iters_clean), int(min_keep), int(fixed_scale))
+
+
+class Sim3RefineOut(C.Structure):
+    """tb_sim3_refine_out of include/tb_capi.h: device pointers, each nullable"""
+    _fields_ = [(n, C.c_void_p) for n in ("cand_srt", "cand_S12", "cand_inliers", "cand_stats", "best_srt", "best_S12", "best_inliers",
+                                          "best_stats")]
+
+
+def sim3_refine_out(S, ncand, device):
+    """(Sim3RefineOut, dict of the torch tensors it points to): every output of a Sim(3) refinement of S sequences x ncand candidates"""
+    import torch
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=device)
+    t = dict(cand_srt=f64(S, ncand, 8), cand_S12=torch.empty((S, ncand, 4, 4), dtype=torch.float32, device=device),
+             cand_inliers=torch.empty((S, ncand), dtype=torch.int32, device=device), cand_stats=f64(S, ncand, 8), best_srt=f64(S, 8),
+             best_S12=torch.empty((S, 4, 4), dtype=torch.float32, device=device), best_inliers=torch.empty((S,), dtype=torch.int32, device=device),
+             best_stats=f64(S, 8))
+    ro = Sim3RefineOut(**{k: (v.data_ptr() if v.numel() else None) for k, v in t.items()})
+    return ro, t
+
+
 class Sim3Out(C.Structure):
     """tb_sim3_out of include/tb_capi.h: device pointers, each nullable"""
     _fields_ = [(n, C.c_void_p) for n in ("cand_rows", "cand_consensus", "cand_flags", "cand_S12", "cand_srt", "best_rank", "best_kf",
@@ -514,6 +548,18 @@ class VO:
         so, out = sim3_out(self.nseq, max(topk, 0), device)
         prm = sim3_params(**params)
         return lib().tb_vo_relocalize_sim3_dev(self._h, int(topk), C.byref(prm), int(min_consensus), C.byref(so)), out
+
+    def refine_sim3_dev(self, device, sim3, min_inliers=20, use_for_graph=False, topk=None, **params):
+        """tb_vo_refine_sim3_dev after relocalize_sim3_dev: (status code, dict of device tensors with tb_sim3_refine_out's fields
+        [nseq, topk, ...]). sim3: the dict relocalize_sim3_dev returned (its cand_srt and cand_consensus seed the refinement);
+        params as sim3_opt_params. topk None = the topk of this object's last relocalize_dev; the library refuses any other count.
+        use_for_graph is passed through as an int, so that the argument check can be tested."""
+        topk = getattr(self, "_reloc_topk", 1) if topk is None else topk
+        ro, out = sim3_refine_out(self.nseq, max(int(topk), 0), device)
+        prm = sim3_opt_params(**params)
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        srt, cons = (sim3 or {}).get("cand_srt"), (sim3 or {}).get("cand_consensus")
+        return lib().tb_vo_refine_sim3_dev(self._h, int(topk), p(srt), p(cons), C.byref(prm), int(min_inliers), int(use_for_graph), C.byref(ro)), out
 
     def loop_sim3_dev(self, device, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
         """tb_vo_loop_sim3_dev after relocalize_sim3_dev: (status code, sim3_graph_tensors' dict -- copies made on the current
@@ -1168,6 +1214,35 @@ class Context:
         return lib().tb_sim3_ransac_batch_dev(self._h, int(nproblems), _p(K), v(rows_ptr), v(counts_ptr), int(pitch), C.byref(prm), v(S12_ptr),
                                               v(srt_ptr), v(consensus_ptr), v(inlier_ptr), v(winner_ptr), v(flags_ptr))
 
+    def sim3_optimize(self, rows, K, srt0, active=None, **params):
+        """tb_sim3_optimize: the similarity srt0 [8] (the unit quaternion w x y z, t12, s: sim3_ransac's srt) refined on the two-image
+        reprojection error of one problem's pixel rows (a SIM3_OBS_ROW array); active: the rows that start active (None: all;
+        sim3_ransac's inlier mask is the intended input); params as sim3_opt_params. Returns a dict: srt [8] float64, S12 [4, 4]
+        float32, inliers, inlier uint8 [n], stats [8] (iterations, initial and final robust chi2, trials, nBad, dropped rows,
+        final lambda, flag)."""
+        K = np.ascontiguousarray(K, np.float64)
+        rows = np.ascontiguousarray(rows, SIM3_OBS_ROW).reshape(-1)
+        n = len(rows)
+        srt0 = np.ascontiguousarray(srt0, np.float64).reshape(8)
+        act = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8).reshape(n)
+        prm = sim3_opt_params(**params)
+        srt, S, inl, st = np.zeros(8, np.float64), np.zeros(16, np.float32), np.zeros(n, np.uint8), np.zeros(8, np.float64)
+        cnt = C.c_int(0)
+        self.check(lib().tb_sim3_optimize(self._h, _p(K), _p(rows) if n else None, n, _p(act) if (act is not None and n) else None, _p(srt0),
+                                          C.byref(prm), _p(srt), _p(S), C.byref(cnt), _p(inl) if n else None, _p(st)))
+        return dict(srt=srt, S12=S.reshape(4, 4), inliers=cnt.value, inlier=inl, stats=st)
+
+    def sim3_optimize_dev(self, nproblems, K, rows_ptr, counts_ptr, pitch, srt_in_ptr, mask_ptr, active_ptr=0, srt_out_ptr=0, S12_ptr=0,
+                          inliers_ptr=0, stats_ptr=0, **params):
+        """tb_sim3_optimize_batch_dev: device pointers (0 / None for the nullable ones: active, srt_out, S12, inliers, stats),
+        asynchronous on the context's stream; params as sim3_opt_params. Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        prm = sim3_opt_params(**params)
+        v = lambda q: C.c_void_p(q or None)
+        return lib().tb_sim3_optimize_batch_dev(self._h, int(nproblems), _p(K), v(rows_ptr), v(counts_ptr), int(pitch), v(active_ptr),
+                                                v(srt_in_ptr), C.byref(prm), v(srt_out_ptr), v(S12_ptr), v(inliers_ptr), v(mask_ptr),
+                                                v(stats_ptr))
+
     def two_view(self, xy0, xy1, K, skip=None, inv_sigma2_0=None, inv_sigma2_1=None, Tcw0=None, **params):
         """tb_two_view: a relative pose and first points from the n point pairs (xy0 / xy1 [n][2] pixels) of one problem; params as
         two_view_params. Returns a dict: status, Tcw1 [4, 4] float32, points [n][3] float32 (zero where nothing was written),
@@ -1616,6 +1691,43 @@ class KeyframeStore:
         rc, out = self.sim3_rc(*a, **kw)
         self.ctx.check(rc)
         return out
+
+    def sim3_refine_rc(self, K, nlevels, scale, q_keys, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot, sim3, min_inliers=20,
+                       use_for_graph=False, ncand=None, q_pitch=None, **params):
+        """tb_kf_store_sim3_refine_dev after a sim3 -> (status code, dict of output tensors with tb_sim3_refine_out's fields). The
+        first nine arguments are those the sim3 call took; sim3 is the dict it returned (its cand_srt and cand_consensus seed the
+        refinement; None: the store's own buffers); params as sim3_opt_params. use_for_graph is passed through as an int, so that
+        the argument check can be tested."""
+        ts = (q_keys, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot)
+        assert all(t.is_contiguous() for t in ts)
+        ncand = int(cand_slot.shape[1] if ncand is None else ncand)
+        ro, out = sim3_refine_out(self.nseq, max(min(ncand, cand_slot.shape[1]), 0), q_keys.device)
+        prm = sim3_opt_params(**params)
+        Kd = (C.c_double * 4)(*[float(k) for k in K])
+        p = [C.c_void_p(t.data_ptr()) for t in ts]
+        v = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        srt, cons = (sim3 or {}).get("cand_srt"), (sim3 or {}).get("cand_consensus")
+        rc = lib().tb_kf_store_sim3_refine_dev(self._h, Kd, int(nlevels), C.c_float(scale), p[0], p[1], p[2], p[3],
+                                               int(q_keys.shape[1] if q_pitch is None else q_pitch), p[4], p[5], ncand, v(srt), v(cons),
+                                               C.byref(prm), int(min_inliers), int(use_for_graph), C.byref(ro))
+        return rc, out
+
+    def sim3_refine(self, *a, **kw):
+        rc, out = self.sim3_refine_rc(*a, **kw)
+        self.ctx.check(rc)
+        return out
+
+    def sim3_refine_state(self, device, ncand):
+        """tb_kf_store_sim3_refine_state_dev: torch VIEWS (not copies) of the last refinement's work for S x ncand pairs: rows
+        [pairs, P, 12] float32 (SIM3_OBS_ROW records), row_counts [pairs], active [pairs, P] uint8 (the Sim(3) query's masks, where the
+        refinement started), inlier [pairs, P] uint8."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self.ctx.check(lib().tb_kf_store_sim3_refine_state_dev(self._h, *[C.byref(q) for q in ptrs]))
+        n, P = self.nseq * int(ncand), self.pitch
+        spec = (("rows", (n, P, 12), "<f4", torch.float32), ("row_counts", (n,), "<i4", torch.int32), ("active", (n, P), "|u1", torch.uint8),
+                ("inlier", (n, P), "|u1", torch.uint8))
+        return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
 
     def sim3_graph_rc(self, q_Tcw, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
         """tb_kf_store_sim3_graph_dev after a sim3 -> (status code, dict or None): the Sim(3) pose graph of the live keyframes and the

@@ -606,7 +606,10 @@ k_sim3(double fx, double fy, double cx, double cy, const tb_sim3_row* __restrict
  * per query key); one row per key that has one, IN KEY ORDER. X1 = the query's Tcw applied to the query key's world point, X2 =
  * the stored keyframe's Tcw applied to its stored world point, both in float64 (one operation per statement) and stored as
  * float32; the weights are invLevelSigma2[octave] of the two keys. A slot of -1, one outside the ring or an empty one is no
- * candidate: no rows, cand_kf -1. */
+ * candidate: no rows, cand_kf -1.
+ * The kernel is a template over the row type: tb_sim3_row for the solver, tb_sim3_obs_row for the optimiser's query
+ * (tb_kf_store_sim3_refine_dev), which adds the two keys' x, y as (u1, v1), (u2, v2) the way k_reloc_rows takes them for its tb_obs
+ * rows. Same keys, same order: row i of a pair is the same match in both lists. */
 struct tb_sim3_sigma {
     float v[TB_MAX_LEVELS];
     int n;
@@ -620,13 +623,20 @@ __device__ __forceinline__ float s3_apply(const float* __restrict__ T, int r, fl
     return (float)a;
 }
 
+__device__ __forceinline__ void s3_set_pixels(tb_sim3_row&, const tb_keypoint&, const tb_keypoint&) {}
+__device__ __forceinline__ void s3_set_pixels(tb_sim3_obs_row& r, const tb_keypoint& k1, const tb_keypoint& k2) {
+    r.u1 = k1.x; r.v1 = k1.y;
+    r.u2 = k2.x; r.v2 = k2.y;
+}
+
+template <typename Row>
 __global__ void __launch_bounds__(256)
 k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int32_t* __restrict__ kf_ids, const tb_keypoint* __restrict__ q_keys,
             const int32_t* __restrict__ q_counts, const float* __restrict__ q_mp, const uint8_t* __restrict__ q_valid, int q_pitch,
             const float* __restrict__ q_Tcw, const tb_match* __restrict__ matches, const int32_t* __restrict__ match_counts,
             const tb_keypoint* __restrict__ kf_keys, const float* __restrict__ kf_mp, const uint8_t* __restrict__ kf_valid,
             const int32_t* __restrict__ kf_counts, const float* __restrict__ kf_Tcw, int pitch, tb_sim3_sigma sig,
-            tb_sim3_row* __restrict__ rows, int32_t* __restrict__ row_counts, int32_t* __restrict__ cand_kf, int32_t* __restrict__ rows_out) {
+            Row* __restrict__ rows, int32_t* __restrict__ row_counts, int32_t* __restrict__ cand_kf, int32_t* __restrict__ rows_out) {
     extern __shared__ int win[];   /* [q_pitch] */
     __shared__ int wsum[4];
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -652,7 +662,7 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
     const float* MP2 = kf_mp + 3 * (size_t)f * pitch;
     const uint8_t* V2 = kf_valid + (size_t)f * pitch;
     const float* T2 = kf_Tcw + 16 * (size_t)f;
-    tb_sim3_row* O = rows + (size_t)c * pitch;
+    Row* O = rows + (size_t)c * pitch;
     for (int i = tid; i < n; i += 256) win[i] = -1;
     __syncthreads();
     for (int k = tid; k < nm; k += 256) {
@@ -664,7 +674,7 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         bool ok = false;
-        tb_sim3_row r = {0, 0, 0, 0, 0, 0, 0, 0};
+        Row r = {};
         if (i < n) {
             const int k = win[i];
             ok = k >= 0;
@@ -676,6 +686,7 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
                 r.X2 = s3_apply(T2, 0, b0, b1, b2); r.Y2 = s3_apply(T2, 1, b0, b1, b2); r.Z2 = s3_apply(T2, 2, b0, b1, b2);
                 r.inv_sigma2_1 = sig.v[min(max(K1[i].octave, 0), sig.n - 1)];
                 r.inv_sigma2_2 = sig.v[min(max(K2[j].octave, 0), sig.n - 1)];
+                s3_set_pixels(r, K1[i], K2[j]);
             }
         }
         const int at = tb_block_ordered_slot(ok, base, wsum);
@@ -687,13 +698,8 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
 /* Per sequence (one thread each): the candidate with the largest consensus, ties to the lower rank, candidates that are absent
  * left out; it is the answer when its consensus reaches min_consensus. best_rank -1: best_kf -1, the identity and scale 1.
  * keep_kf / keep_srt (nullable): the store's own copy of best_kf / best_srt, which tb_kf_store_sim3_graph_dev reads. */
-__global__ void __launch_bounds__(256)
-k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_consensus,
-              const float* __restrict__ cand_S12, const double* __restrict__ cand_srt, int32_t* __restrict__ best_rank,
-              int32_t* __restrict__ best_kf, float* __restrict__ best_S12, double* __restrict__ best_srt, int32_t* __restrict__ keep_kf,
-              double* __restrict__ keep_srt) {
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= nseq) return;
+__device__ __forceinline__ int s3_select_rank(int ncand, int min_consensus, const int32_t* __restrict__ cand_kf,
+                                              const int32_t* __restrict__ cand_consensus, int s) {
     int best = -1, most = -1;
     for (int r = 0; r < ncand; r++) {
         const size_t c = (size_t)s * ncand + r;
@@ -702,6 +708,17 @@ k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict_
         if (ni > most) { most = ni; best = r; }
     }
     if (best >= 0 && most < min_consensus) best = -1;
+    return best;
+}
+
+__global__ void __launch_bounds__(256)
+k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_consensus,
+              const float* __restrict__ cand_S12, const double* __restrict__ cand_srt, int32_t* __restrict__ best_rank,
+              int32_t* __restrict__ best_kf, float* __restrict__ best_S12, double* __restrict__ best_srt, int32_t* __restrict__ keep_kf,
+              double* __restrict__ keep_srt) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nseq) return;
+    const int best = s3_select_rank(ncand, min_consensus, cand_kf, cand_consensus, s);
     const size_t cb = (size_t)s * ncand + (best >= 0 ? best : 0);
     if (best_rank) best_rank[s] = best;
     if (best_kf) best_kf[s] = best >= 0 ? cand_kf[cb] : -1;
@@ -722,18 +739,99 @@ int tbk_sim3_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_
                      fixed_scale, chi2_max, seed, d_S12, d_srt, d_consensus, d_inlier, d_winner, d_flags);
 }
 
+template <typename Row>
+static int s3_rows_launch(tb_ctx* ctx, const char* name, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids,
+                          const tb_keypoint* d_q_keys, const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch,
+                          const float* d_q_Tcw, const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys,
+                          const float* d_kf_mp, const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch,
+                          const float* inv_sigma2, int nlevels, Row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf, int32_t* d_rows_out) {
+    if (npairs <= 0) return TB_OK;
+    tb_sim3_sigma sig;
+    sig.n = nlevels;
+    for (int i = 0; i < TB_MAX_LEVELS; i++) sig.v[i] = i < nlevels ? inv_sigma2[i] : 0.f;
+    return tb_launch(ctx, name, k_sim3_rows<Row>, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), ncand, cap, d_cand_slot, d_kf_ids,
+                     d_q_keys, d_q_counts, d_q_mp, d_q_valid, q_pitch, d_q_Tcw, d_matches, d_match_counts, d_kf_keys, d_kf_mp, d_kf_valid,
+                     d_kf_counts, d_kf_Tcw, pitch, sig, d_rows, d_row_counts, d_cand_kf, d_rows_out);
+}
+
 int tbk_sim3_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids, const tb_keypoint* d_q_keys,
                   const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch, const float* d_q_Tcw,
                   const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys, const float* d_kf_mp,
                   const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch, const float* inv_sigma2, int nlevels,
                   tb_sim3_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf, int32_t* d_rows_out) {
+    return s3_rows_launch(ctx, "k_sim3_rows", npairs, ncand, cap, d_cand_slot, d_kf_ids, d_q_keys, d_q_counts, d_q_mp, d_q_valid, q_pitch, d_q_Tcw,
+                          d_matches, d_match_counts, d_kf_keys, d_kf_mp, d_kf_valid, d_kf_counts, d_kf_Tcw, pitch, inv_sigma2, nlevels, d_rows,
+                          d_row_counts, d_cand_kf, d_rows_out);
+}
+
+int tbk_sim3_obs_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids,
+                      const tb_keypoint* d_q_keys, const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch,
+                      const float* d_q_Tcw, const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys,
+                      const float* d_kf_mp, const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch,
+                      const float* inv_sigma2, int nlevels, tb_sim3_obs_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf) {
+    return s3_rows_launch(ctx, "k_sim3_rows_obs", npairs, ncand, cap, d_cand_slot, d_kf_ids, d_q_keys, d_q_counts, d_q_mp, d_q_valid, q_pitch,
+                          d_q_Tcw, d_matches, d_match_counts, d_kf_keys, d_kf_mp, d_kf_valid, d_kf_counts, d_kf_Tcw, pitch, inv_sigma2, nlevels,
+                          d_rows, d_row_counts, d_cand_kf, nullptr);
+}
+
+/* Per sequence (one 64-thread workgroup each), after the optimiser ran on every pair of tb_kf_store_sim3_refine_dev: a thread
+ * hands candidates r, r + 64, ... their four outputs to the caller (a skipped pair -- no candidate, or a consensus below 3 -- ran as an empty problem
+ * from the identity and is flagged stats[7] = 2 here); thread 0 finds the candidate the Sim(3) query selected, by its rule, copies
+ * its four outputs (rank -1: the identity, zeros, stats[7] = 2) and, with use_for_graph, gives the store's kept best_srt the
+ * refined srt where its inliers reach min_inliers. */
+__global__ void __launch_bounds__(64)
+k_sim3_refine_select(int ncand, int min_consensus, int min_inliers, int use_for_graph, const int32_t* __restrict__ cand_kf,
+                     const int32_t* __restrict__ cand_consensus, double* __restrict__ srt, float* __restrict__ S12, int32_t* __restrict__ inl,
+                     double* __restrict__ stats, double* __restrict__ o_srt, float* __restrict__ o_S12, int32_t* __restrict__ o_inl,
+                     double* __restrict__ o_stats, double* __restrict__ b_srt, float* __restrict__ b_S12, int32_t* __restrict__ b_inl,
+                     double* __restrict__ b_stats, double* __restrict__ keep_srt) {
+    const int s = blockIdx.x;
+    for (int r = threadIdx.x; r < ncand; r += 64) {
+        const size_t c = (size_t)s * ncand + r;
+        if (cand_kf[c] < 0 || cand_consensus[c] < 3) stats[8 * c + 7] = 2.0;
+        if (o_srt) for (int i = 0; i < 8; i++) o_srt[8 * c + i] = srt[8 * c + i];
+        if (o_S12) for (int i = 0; i < 16; i++) o_S12[16 * c + i] = S12[16 * c + i];
+        if (o_inl) o_inl[c] = inl[c];
+        if (o_stats) for (int i = 0; i < 8; i++) o_stats[8 * c + i] = stats[8 * c + i];
+    }
+    __syncthreads();   /* thread 0 reads flags other threads wrote */
+    if (threadIdx.x != 0 || min_consensus < 0) return;   /* min_consensus < 0: the Sim(3) query selected nothing */
+    const int best = s3_select_rank(ncand, min_consensus, cand_kf, cand_consensus, s);
+    const size_t cb = (size_t)s * ncand + (best >= 0 ? best : 0);
+    if (b_srt) for (int i = 0; i < 8; i++) b_srt[8 * (size_t)s + i] = best >= 0 ? srt[8 * cb + i] : ((i == 0 || i == 7) ? 1.0 : 0.0);
+    if (b_S12) for (int i = 0; i < 16; i++) b_S12[16 * (size_t)s + i] = best >= 0 ? S12[16 * cb + i] : ((i & 3) == (i >> 2) ? 1.f : 0.f);
+    if (b_inl) b_inl[s] = best >= 0 ? inl[cb] : 0;
+    if (b_stats) for (int i = 0; i < 8; i++) b_stats[8 * (size_t)s + i] = best >= 0 ? stats[8 * cb + i] : (i == 7 ? 2.0 : 0.0);
+    if (use_for_graph && best >= 0 && stats[8 * cb + 7] == 0.0 && inl[cb] >= min_inliers)
+        for (int i = 0; i < 8; i++) keep_srt[8 * (size_t)s + i] = srt[8 * cb + i];
+}
+
+/* Per pair (one thread each), before the optimiser: a pair without a candidate or with a consensus below 3 becomes an empty problem
+ * seeded with the identity; every other pair keeps its row count and takes its cand_srt as the seed */
+__global__ void __launch_bounds__(256)
+k_sim3_refine_prep(int npairs, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_consensus, const double* __restrict__ cand_srt,
+                   const int32_t* __restrict__ row_counts, int32_t* __restrict__ counts, double* __restrict__ seed) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= npairs) return;
+    const bool skip = cand_kf[c] < 0 || cand_consensus[c] < 3;
+    counts[c] = skip ? 0 : row_counts[c];
+    for (int i = 0; i < 8; i++) seed[8 * (size_t)c + i] = skip ? ((i == 0 || i == 7) ? 1.0 : 0.0) : cand_srt[8 * (size_t)c + i];
+}
+
+int tbk_sim3_refine_prep(tb_ctx* ctx, int npairs, const int32_t* d_cand_kf, const int32_t* d_cand_consensus, const double* d_cand_srt,
+                         const int32_t* d_row_counts, int32_t* d_counts, double* d_seed) {
     if (npairs <= 0) return TB_OK;
-    tb_sim3_sigma sig;
-    sig.n = nlevels;
-    for (int i = 0; i < TB_MAX_LEVELS; i++) sig.v[i] = i < nlevels ? inv_sigma2[i] : 0.f;
-    return tb_launch(ctx, "k_sim3_rows", k_sim3_rows, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), ncand, cap, d_cand_slot, d_kf_ids,
-                     d_q_keys, d_q_counts, d_q_mp, d_q_valid, q_pitch, d_q_Tcw, d_matches, d_match_counts, d_kf_keys, d_kf_mp, d_kf_valid,
-                     d_kf_counts, d_kf_Tcw, pitch, sig, d_rows, d_row_counts, d_cand_kf, d_rows_out);
+    return tb_launch(ctx, "k_sim3_refine_prep", k_sim3_refine_prep, dim3((npairs + 255) / 256), dim3(256), 0, npairs, d_cand_kf, d_cand_consensus,
+                     d_cand_srt, d_row_counts, d_counts, d_seed);
+}
+
+int tbk_sim3_refine_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, int min_inliers, int use_for_graph, const int32_t* d_cand_kf,
+                           const int32_t* d_cand_consensus, double* d_srt, float* d_S12, int32_t* d_inl, double* d_stats, double* o_srt,
+                           float* o_S12, int32_t* o_inl, double* o_stats, double* b_srt, float* b_S12, int32_t* b_inl, double* b_stats,
+                           double* d_keep_srt) {
+    return tb_launch(ctx, "k_sim3_refine_select", k_sim3_refine_select, dim3(nseq), dim3(64), 0, ncand, min_consensus, min_inliers, use_for_graph,
+                     d_cand_kf, d_cand_consensus, d_srt, d_S12, d_inl, d_stats, o_srt, o_S12, o_inl, o_stats, b_srt, b_S12, b_inl, b_stats,
+                     d_keep_srt);
 }
 
 int tbk_sim3_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_cand_kf, const int32_t* d_cand_consensus,

@@ -1464,6 +1464,7 @@ int tb_kf_store_clear(tb_kf_store* st) {
     TB_HIP(ctx, hipMemsetAsync(st->kf_ids, 0xff, n * sizeof(int32_t), ctx->stream));
     st->nadded = 0;
     st->s3_best = false;   /* a winner of the ring that was: tb_kf_store_sim3_graph_dev needs a new Sim(3) query */
+    st->s3_done = false;   /* and so does tb_kf_store_sim3_refine_dev */
     return TB_OK;
 }
 
@@ -1679,6 +1680,7 @@ int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, flo
     if (mcounts != st->mcounts)   /* tb_kf_store_work_dev lends the last call's counts */
         TB_HIP(ctx, hipMemcpyAsync(st->mcounts, mcounts, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     st->reloc_done = true;   /* the match lists are filled, pair-major at this ncand: tb_kf_store_sim3_dev may read them */
+    st->s3_done = false;     /* and they are no longer those the last Sim(3) query's masks and seeds belong to: no refinement on them */
     st->reloc_ncand = ncand;
     if (!o.best_rank && !o.best_kf && !o.best_Tcw) return TB_OK;
     return tbk_reloc_select(ctx, st->nseq, ncand, prm->min_inliers, ckf, ninl, pose, o.best_rank, o.best_kf, o.best_Tcw);
@@ -1727,10 +1729,80 @@ int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float 
     TB_TRY(tbk_sim3_batch(ctx, pairs, K, st->s3_rows, st->s3_cnt, st->pitch, prm->hypotheses, prm->fixed_scale, prm->chi2_max, prm->seed, S12, srt,
                           cons, st->s3_mask, nullptr, o.cand_flags ? o.cand_flags : st->s3_flags));
     st->s3_best = false;   /* tb_kf_store_sim3_graph_dev needs the winner this call selects, if it selects one */
+    st->s3_done = true;    /* tb_kf_store_sim3_refine_dev may run; it is told where cand_srt and cand_consensus went */
+    st->s3_own_srt = !o.cand_srt;
+    st->s3_own_cons = !o.cand_consensus;
+    st->s3_min_cons = -1;
     if (!o.best_rank && !o.best_kf && !o.best_S12 && !o.best_srt) return TB_OK;
     TB_TRY(tbk_sim3_select(ctx, st->nseq, ncand, min_consensus, st->s3_kf, cons, S12, srt, o.best_rank, o.best_kf, o.best_S12, o.best_srt,
                            st->s3_best_kf, st->s3_best_srt));
     st->s3_best = true;
+    st->s3_min_cons = min_consensus;
+    return TB_OK;
+}
+
+int tb_kf_store_sim3_refine_dev(tb_kf_store* st, const double K[4], int nlevels, float scale, const tb_keypoint* q_keys, const int32_t* q_counts,
+                                const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch, const float* q_Tcw, const int32_t* cand_slot,
+                                int ncand, const double* cand_srt, const int32_t* cand_consensus, const tb_sim3_opt_params* prm, int min_inliers,
+                                int use_for_graph, const tb_sim3_refine_out* out) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    if (!K || !q_map_points || !q_mp_valid || !q_Tcw || !prm || !tb_sim3_opt_params_ok(prm) || prm->min_keep < 1 || min_inliers < 0 ||
+        (use_for_graph != 0 && use_for_graph != 1) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) ||
+        !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_refine_dev: null arguments, the optimiser's parameters (th2, iteration counts 0..99, "
+                                       "min_keep >= 1, fixed_scale 0 or 1), min_inliers %d, use_for_graph %d (0, 1) or K", min_inliers, use_for_graph);
+    float inv_sigma2[TB_MAX_LEVELS];
+    int rc;
+    if ((rc = reloc_check(st, "tb_kf_store_sim3_refine_dev", nlevels, scale, q_keys, q_counts, q_pitch, cand_slot, ncand, inv_sigma2))) return rc;
+    if (!st->s3_ready || !st->s3_done || !st->reloc_done)
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_refine_dev: no tb_kf_store_sim3_dev since the store was made or cleared or the last verification");
+    if (ncand != st->reloc_ncand)
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_refine_dev: ncand %d, but the match lists were filled for %d candidates a sequence", ncand, st->reloc_ncand);
+    if ((!cand_srt && !st->s3_own_srt) || (!cand_consensus && !st->s3_own_cons))
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_refine_dev: the Sim(3) query wrote cand_srt / cand_consensus to the caller's buffer: pass it");
+    static const tb_sim3_refine_out none = {};
+    const tb_sim3_refine_out& o = out ? *out : none;
+    const bool wants_best = o.best_srt || o.best_S12 || o.best_inliers || o.best_stats || use_for_graph;
+    if (wants_best && !st->s3_best)
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_refine_dev: the Sim(3) query selected no candidate (it was given no best_* output)");
+    if (!st->o3_ready) {   /* the first call allocates, later ones do not */
+        const size_t pairs = (size_t)st->nseq * st->max_cand, pp = pairs * st->pitch;
+        if (!st->o3_rows) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_rows, pp));
+        if (!st->o3_mask) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_mask, pp, 0));
+        if (!st->o3_cnt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_cnt, pairs, 0));
+        if (!st->o3_kf) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_kf, pairs));
+        if (!st->o3_run) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_run, pairs, 0));
+        if (!st->o3_inl) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_inl, pairs));
+        if (!st->o3_seed) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_seed, pairs * 8));
+        if (!st->o3_srt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_srt, pairs * 8));
+        if (!st->o3_stats) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_stats, pairs * 8));
+        if (!st->o3_S12) TB_TRY(tb_dev_alloc(ctx, st->own, &st->o3_S12, pairs * 16));
+        st->o3_ready = true;
+    }
+    const int pairs = st->nseq * ncand;
+    const double* seeds = cand_srt ? cand_srt : st->s3_srt;
+    const int32_t* cons = cand_consensus ? cand_consensus : st->s3_cons;
+    TB_TRY(tbk_sim3_obs_rows(ctx, pairs, ncand, st->cap, cand_slot, st->kf_ids, q_keys, q_counts, q_map_points, q_mp_valid, q_pitch, q_Tcw,
+                             st->matches, st->mcounts, st->keys, st->mp, st->valid, st->counts, st->Tcw, st->pitch, inv_sigma2, nlevels, st->o3_rows,
+                             st->o3_cnt, st->o3_kf));
+    TB_TRY(tbk_sim3_refine_prep(ctx, pairs, st->o3_kf, cons, seeds, st->o3_cnt, st->o3_run, st->o3_seed));
+    TB_TRY(tbk_sim3_opt_batch(ctx, pairs, K, st->o3_rows, st->o3_run, st->pitch, st->s3_mask, st->o3_seed, prm, st->o3_srt, st->o3_S12, st->o3_inl,
+                              st->o3_mask, st->o3_stats));
+    return tbk_sim3_refine_select(ctx, st->nseq, ncand, st->s3_best ? st->s3_min_cons : -1, min_inliers, use_for_graph, st->o3_kf, cons, st->o3_srt,
+                                  st->o3_S12, st->o3_inl, st->o3_stats, o.cand_srt, o.cand_S12, o.cand_inliers, o.cand_stats, o.best_srt,
+                                  o.best_S12, o.best_inliers, o.best_stats, st->s3_best_srt);
+}
+
+int tb_kf_store_sim3_refine_state_dev(tb_kf_store* st, const tb_sim3_obs_row** rows, const int32_t** row_counts, const uint8_t** active,
+                                      const uint8_t** inlier) {
+    if (!st) return TB_EINVAL;
+    if (!st->o3_ready) return tb_fail(st->ctx, TB_ESTATE, "tb_kf_store_sim3_refine_state_dev: before the first tb_kf_store_sim3_refine_dev");
+    if (rows) *rows = st->o3_rows;
+    if (row_counts) *row_counts = st->o3_cnt;
+    if (active) *active = st->s3_mask;
+    if (inlier) *inlier = st->o3_mask;
     return TB_OK;
 }
 
@@ -2274,6 +2346,57 @@ int tb_sim3_ransac(tb_ctx* ctx, const double K[4], const tb_sim3_row* rows, int 
     if (consensus) *consensus = h[0];
     if (winner) { winner[0] = h[1]; winner[1] = h[2]; }
     if (flags) *flags = h[3];
+    return TB_OK;
+}
+
+/* ------------------------------------------------------------------ Sim(3) refinement on pixel rows */
+int tb_sim3_optimize_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_obs_row* rows, const int32_t* counts, int pitch,
+                               const uint8_t* active_in, const double* srt_in, const tb_sim3_opt_params* prm, double* srt_out, float* S12,
+                               int32_t* inliers, uint8_t* inlier_mask, double* stats) {
+    TB_ENTER(ctx);
+    if (!ctx || nproblems < 0 || pitch < 1 || !K || !rows || !counts || !prm || !srt_in || !inlier_mask) return TB_EINVAL;
+    if (!tb_sim3_opt_params_ok(prm) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) ||
+        !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_sim3_optimize_batch_dev: th2 finite and not negative, iteration counts 0..99, min_keep >= 0, fixed_scale 0 or 1, K finite, fx and fy positive");
+    if (nproblems > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_sim3_optimize_batch_dev: %d problems (at most 65535 per call)", nproblems);
+    return tbk_sim3_opt_batch(ctx, nproblems, K, rows, counts, pitch, active_in, srt_in, prm, srt_out, S12, inliers, inlier_mask, stats);
+}
+
+int tb_sim3_optimize(tb_ctx* ctx, const double K[4], const tb_sim3_obs_row* rows, int n, const uint8_t* active, const double srt_in[8],
+                     const tb_sim3_opt_params* prm, double srt_out[8], float S12[16], int* inliers, uint8_t* inlier_mask, double stats[8]) {
+    TB_ENTER(ctx);
+    if (!ctx || n < 0 || !K || !prm || !srt_in || (n && !rows)) return TB_EINVAL;
+    const size_t pitch = (size_t)std::max(n, 1);
+    size_t end = 0;
+    const size_t oRows = stage_piece(end, pitch * sizeof(tb_sim3_obs_row)), oIn = stage_piece(end, 64), oOut = stage_piece(end, 64),
+                 oS = stage_piece(end, 64), oStats = stage_piece(end, 64), oAct = stage_piece(end, pitch), oMask = stage_piece(end, pitch),
+                 oCnt = stage_piece(end, 8);
+    char* b;
+    int rc;
+    if ((rc = tb_scratch(ctx, TB_SLOT_HOST, end, (void**)&b))) return rc;
+    const int32_t cnt = n;
+    TB_UPLOAD(ctx, b + oRows, rows, (size_t)n * sizeof(tb_sim3_obs_row));
+    TB_UPLOAD(ctx, b + oIn, srt_in, 64);
+    TB_UPLOAD(ctx, b + oCnt, &cnt, 4);
+    if (active && n) TB_UPLOAD(ctx, b + oAct, active, (size_t)n);
+    int32_t* res = (int32_t*)(b + oCnt) + 1;   /* inliers */
+    if ((rc = tb_sim3_optimize_batch_dev(ctx, 1, K, (const tb_sim3_obs_row*)(b + oRows), (const int32_t*)(b + oCnt), (int)pitch,
+                                         active && n ? (const uint8_t*)(b + oAct) : nullptr, (const double*)(b + oIn), prm, (double*)(b + oOut),
+                                         (float*)(b + oS), res, (uint8_t*)(b + oMask), (double*)(b + oStats))))
+        return rc;
+    double q[8], st[8];
+    float S[16];
+    int32_t h;
+    TB_DOWNLOAD(ctx, q, b + oOut, 64);
+    TB_DOWNLOAD(ctx, S, b + oS, 64);
+    TB_DOWNLOAD(ctx, st, b + oStats, 64);
+    TB_DOWNLOAD(ctx, &h, res, 4);
+    if (inlier_mask && n) TB_DOWNLOAD(ctx, inlier_mask, b + oMask, (size_t)n);
+    TB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (srt_out) memcpy(srt_out, q, 64);
+    if (S12) memcpy(S12, S, 64);
+    if (stats) memcpy(stats, st, 64);
+    if (inliers) *inliers = h;
     return TB_OK;
 }
 

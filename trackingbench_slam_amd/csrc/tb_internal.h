@@ -299,6 +299,17 @@ struct tb_kf_store {
     int32_t *s3_cnt = nullptr, *s3_kf = nullptr, *s3_cons = nullptr, *s3_flags = nullptr;   /* [pairs] */
     float* s3_S12 = nullptr;                                 /* [pairs][16] */
     double* s3_srt = nullptr;                                /* [pairs][8] */
+    /* the Sim(3) refinement query (tb_kf_store_sim3_refine_dev), allocated by its first call: the pixel rows (row i of a pair is row i
+     * of s3_rows), their counts and keyframes as the row kernel writes them, the counts and seeds the optimiser runs on, its mask
+     * and its four outputs. s3_done: a tb_kf_store_sim3_dev ran since the store was made or cleared and since the last verification (whose match lists its
+     * masks and seeds belong to); s3_own_srt / s3_own_cons: it wrote cand_srt / cand_consensus into the store's own s3_srt / s3_cons; s3_min_cons: its min_consensus (-1: it selected nothing) */
+    bool s3_done = false, s3_own_srt = false, s3_own_cons = false, o3_ready = false;
+    int s3_min_cons = -1;
+    tb_sim3_obs_row* o3_rows = nullptr;                      /* [pairs][pitch] */
+    uint8_t* o3_mask = nullptr;                              /* [pairs][pitch] */
+    int32_t *o3_cnt = nullptr, *o3_kf = nullptr, *o3_run = nullptr, *o3_inl = nullptr;   /* [pairs] */
+    double *o3_seed = nullptr, *o3_srt = nullptr, *o3_stats = nullptr;                   /* [pairs][8] */
+    float* o3_S12 = nullptr;                                 /* [pairs][16] */
     /* the Sim(3) graph query (tb_kf_store_sim3_graph_dev): the store's own copy of the last Sim(3) query's best_kf / best_srt (the
      * caller's are nullable and may be gone by then; s3_best: that query selected a winner into them), and the graph's buffers,
      * allocated with the solver's plan by the first graph query; nn = cap + 1 */
@@ -551,9 +562,32 @@ int tbk_sim3_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_
                   const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys, const float* d_kf_mp,
                   const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch, const float* inv_sigma2, int nlevels,
                   tb_sim3_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf, int32_t* d_rows_out);
+/* the same rows with the two keys' pixels (tb_kf_store_sim3_refine_dev), and that query's kernels around the optimiser */
+int tbk_sim3_obs_rows(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids,
+                      const tb_keypoint* d_q_keys, const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch,
+                      const float* d_q_Tcw, const tb_match* d_matches, const int32_t* d_match_counts, const tb_keypoint* d_kf_keys,
+                      const float* d_kf_mp, const uint8_t* d_kf_valid, const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch,
+                      const float* inv_sigma2, int nlevels, tb_sim3_obs_row* d_rows, int32_t* d_row_counts, int32_t* d_cand_kf);
+int tbk_sim3_refine_prep(tb_ctx* ctx, int npairs, const int32_t* d_cand_kf, const int32_t* d_cand_consensus, const double* d_cand_srt,
+                         const int32_t* d_row_counts, int32_t* d_counts, double* d_seed);
+int tbk_sim3_refine_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, int min_inliers, int use_for_graph, const int32_t* d_cand_kf,
+                           const int32_t* d_cand_consensus, double* d_srt, float* d_S12, int32_t* d_inl, double* d_stats, double* o_srt,
+                           float* o_S12, int32_t* o_inl, double* o_stats, double* b_srt, float* b_S12, int32_t* b_inl, double* b_stats,
+                           double* d_keep_srt);
 int tbk_sim3_select(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_cand_kf, const int32_t* d_cand_consensus,
                     const float* d_cand_S12, const double* d_cand_srt, int32_t* d_best_rank, int32_t* d_best_kf, float* d_best_S12,
                     double* d_best_srt, int32_t* d_keep_kf, double* d_keep_srt);
+/* Sim(3) refinement on pixel rows (k_sim3_opt.hip): one workgroup per problem, no work buffer; d_active, d_srt_out, d_S12,
+ * d_inliers and d_stats nullable, d_mask not (it carries the rows' active flags during the call) */
+int tbk_sim3_opt_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_obs_row* d_rows, const int32_t* d_counts, int pitch,
+                       const uint8_t* d_active, const double* d_srt_in, const tb_sim3_opt_params* prm, double* d_srt_out, float* d_S12,
+                       int32_t* d_inliers, uint8_t* d_mask, double* d_stats);
+/* tb_sim3_optimize_batch_dev's parameter rules, for the entry points around it */
+static inline bool tb_sim3_opt_params_ok(const tb_sim3_opt_params* prm) {
+    auto it = [](int v) { return v >= 0 && v <= 99; };
+    return prm->th2 >= 0.0 && std::isfinite(prm->th2) && it(prm->iters_first) && it(prm->iters_bad) && it(prm->iters_clean) &&
+           prm->min_keep >= 0 && (prm->fixed_scale == 0 || prm->fixed_scale == 1);
+}
 /* tb_sim3_ransac_batch_dev's parameter rules, for the entry points around it */
 static inline bool tb_sim3_params_ok(const tb_sim3_params* prm) {
     return prm->hypotheses >= 1 && prm->hypotheses <= 1024 && (prm->fixed_scale == 0 || prm->fixed_scale == 1) && prm->chi2_max >= 0.0 &&

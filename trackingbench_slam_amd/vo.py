@@ -340,6 +340,7 @@ class StereoVO:
         others keep their state: the loop is in ragged mode from then on (step() drives it; reset() without which= leaves it)."""
         if which is not None:
             self._ragged_ok()
+        self._sim3 = None      # a Sim(3) query belongs to one frame
         T = torch.as_tensor(np.asarray(Tcw0, np.float32) if not torch.is_tensor(Tcw0) else Tcw0, dtype=torch.float32)
         if which is not None:
             w = self._mask(which, "which")
@@ -366,6 +367,7 @@ class StereoVO:
 
     def step_rc(self, left, right=None, active=None, keyframe=None):
         """One frame; returns the library's status code (0 or a negative TB_E* code)."""
+        self._sim3 = None      # a Sim(3) query belongs to one frame
         if getattr(self, "window_ba", None) and (active is not None or keyframe is not None):
             self._ragged_ok()
         assert left.dtype == torch.uint8 and left.is_cuda and tuple(left.shape) == (self.S, self.height, self.width)
@@ -578,6 +580,7 @@ class StereoVO:
         With pnp=: also pnp_rows [S, topk] int32 (the rows before the gather), pnp_consensus [S, topk], pnp_winner [S, topk, 2],
         pnp_Tcw [S, topk, 4, 4], pnp_took [S, topk] uint8 (1: the pair went on with its consensus rows and the PnP pose) -- copies."""
         self._need_store()
+        self._sim3 = None      # and to one verification: refine_sim3 needs a relocalize_sim3 after this call
         with torch.cuda.stream(self.stream):
             rc, out = self.vo.relocalize_dev(topk, exclude_newest, min_inliers, self.db.capacity, self.dev)
             if rc == 0 and self.pnp:
@@ -607,6 +610,28 @@ class StereoVO:
                 cons = out["cand_consensus"].gather(1, pick).view(-1)
                 out["consensus"] = torch.where(out["best_rank"] >= 0, cons, torch.zeros_like(cons))
                 out["S12"], out["srt"] = out["best_S12"], out["best_srt"]
+        self.ctx.check(rc)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        self._sim3 = out      # refine_sim3 seeds from its cand_srt / cand_consensus
+        return out
+
+    def refine_sim3(self, fixed_scale=True, min_inliers=20, use_for_graph=False, **params):
+        """After relocalize_sim3(...): ORB-SLAM's OptimizeSim3 on every candidate -- the similarity refined on the reprojection error
+        of the matched keys' pixels in both images, from the candidate's cand_srt and its RANSAC inliers. Device tensors: srt [S, 8]
+        float64, S12 [S, 4, 4] float32, inliers [S] and stats [S, 8] of the candidate relocalize_sim3 selected (the identity, 0 and
+        stats[7] = 2 when none), and cand_srt / cand_S12 / cand_inliers / cand_stats [S, topk, ...]. use_for_graph=True hands the
+        refined transform to the next loop_sim3() as its loop edge where the refined inliers reach min_inliers (ORB-SLAM asks for
+        20); otherwise no state changes. No host synchronisation. params: th2, iters_first, iters_bad, iters_clean, min_keep."""
+        self._need_store()
+        if getattr(self, "_sim3", None) is None:
+            raise capi.TBError(capi.TB_ESTATE, "refine_sim3 needs a relocalize_sim3 of this frame")
+        with torch.cuda.stream(self.stream):
+            rc, out = self.vo.refine_sim3_dev(self.dev, self._sim3, min_inliers=min_inliers, use_for_graph=bool(use_for_graph),
+                                              fixed_scale=fixed_scale, **params)
+            if rc == 0:
+                out["srt"], out["S12"], out["inliers"], out["stats"] = out["best_srt"], out["best_S12"], out["best_inliers"], out["best_stats"]
         self.ctx.check(rc)
         torch.cuda.current_stream(self.dev).wait_stream(self.stream)
         for t in out.values():
