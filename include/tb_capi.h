@@ -1548,6 +1548,85 @@ int tb_vo_mp_desc_dev(tb_vo* vo, const uint8_t** mp_desc, const uint8_t** kf_mp_
 int tb_vo_map_state_dev(tb_vo* vo, const tb_mappoint** points, const uint8_t** desc, const int32_t** counts,
                         const int32_t** block_counts, int* capacity, int* map_keyframes, int* blocks);
 
+/* ---- the depth filter: per sequence up to `pitch` seeds -- a pixel of a reference image with a Gaussian x Beta belief over the
+ * inverse range along its ray -- that every later frame with a known pose narrows by an epipolar search, until the seed is a map
+ * point. An operator next to the VO loop: it is fed poses and images and touches nothing of a loop. The definition, statement for
+ * statement, is tests/depth_filter_reference.py; the kernels (k_depth_filter.hip) are held to it: flag, n, win and score bit for
+ * bit, the float64 results at 1e-6 relative. The warp and the patch follow Matcher::FindMatchDirect (matcher.cpp:1518-1592), the
+ * alignment the commented-out body of Matcher::Align1D (matcher.cpp:1247-1364), the depth, tau and the update the published SVO /
+ * REMODE formulas; everything is float64 unless marked integer, one rounding per statement, sums left to right.
+ *
+ * A seed (tb_df_seed) starts with mu = 1 / depth_mean, z_range = 1 / depth_min, sigma2 = z_range^2 / 36, a = b = 10, state 1.
+ * The update of one active seed against a frame (image, Tcw), with T_cr = Tcw Tcw_ref^-1 = (R, t) and f the unit ray of (u, v):
+ *   1 range ends   d = 1 / mu, d_min = 1 / (mu + sqrt(sigma2)), d_max = 1 / max(mu - sqrt(sigma2), 1e-8); A and B are the
+ *                  normalised-plane projections of R f d_min + t and R f d_max + t. BEHIND: one of the three depths is <= 0.
+ *                  OUTSIDE: the point at d projects outside the image less a margin of 5 px. Both leave the seed unchanged.
+ *   2 affine warp  A_cur_ref at depth d, level 0, half size 5. WARP, unchanged: its determinant is outside (1/3, 3) -- the
+ *                  project's own rule: the search runs at level 0 only and the warp takes the scale.
+ *   3 patch        the warped 10 x 10 patch with border as uint8: floor of the bilinear sample, 0 outside; the inner 8 x 8 is the patch.
+ *   4 search       epi_len = the pixel distance of A and B; DEGENERATE, unchanged, below 1e-6. n = max(1, floor(epi_len / 0.7));
+ *                  n > max_steps is NO_MATCH. Samples i = 0..n run from B to A, uniform on the normalised plane; each is rounded
+ *                  to the integer pixel floor(p + 0.5); a sample on the previous sample's pixel is skipped, and so is a pixel
+ *                  closer than 4 to the border. The score is the zero-mean SSD as an exact integer, 64 (sum AA - 2 sum AB + sum BB) -
+ *                  (sum A - sum B)^2; the first minimum wins. No sample, or a best score >= 64 zmssd_max, is NO_MATCH.
+ *   5 alignment    Align1D from the winning pixel along the unit pixel direction of the line, on the bordered patch, at most
+ *                  align_iters iterations, with the mean-difference term, the "error increased" step back and the 0.03 px stop
+ *                  of the reference's body; its 64-pixel sums take the butterfly p[t] = p[t] + p[t ^ d], d = 1 .. 32, t = 8 y + x.
+ *                  Not converged is NO_MATCH.
+ *   6 depth        z from the least-squares intersection of R f and the current unit ray; |det A'A| < 1e-6 is DEGENERATE,
+ *                  unchanged -- the project's own rule: SVO counts a failed match there, which penalises the seeds near the
+ *                  epipole of a camera that moves forward. tau by SVO's computeTau with px_error_angle = 2 atan(px_noise /
+ *                  (2 sqrt(fx fy))) (acos arguments clamped to [-1, 1]); tau_inv = 0.5 (1 / max(1e-7, z - tau) - 1 / (z + tau)).
+ *   7 update       the Vogiatzis-Hernandez update with x = 1 / z, tau2 = tau_inv^2. A non-finite sqrt(sigma2 + tau2) is
+ *                  NONFINITE, unchanged. NO_MATCH is b += 1 and nothing else (but the count of updates).
+ *   8 convergence  CONVERGED when sqrt(sigma2) < z_range / conv_div: state becomes 2; the world point is Tcw_ref^-1 (f / mu).
+ *                  Converged and dropped seeds are not updated again.
+ * Every update leaves one tb_df_trace an entry (flag -1 for an entry that is not active).
+ * Keyframes: a sequence has a ring of ref_slots reference images with their poses. An add takes the slot after the newest one, sets
+ * every seed still bound to that slot to state 3 (dropped: its entry counts as free from then on), and appends one seed per
+ * offered key that is not skipped, in key order, into the entries that are free (state 0 or 3) in ascending entry order. Keys that
+ * do not fit are not added; their count is returned.
+ *
+ * tb_depth_filter_create: K = (fx, fy, cx, cy); images are width x height. TB_EINVAL: nseq < 1, pitch < 1, ref_slots outside 1..16,
+ * depth_min <= 0, depth_mean < depth_min, conv_div or px_noise not positive, max_steps < 1, zmssd_max < 0, align_iters outside 0..99,
+ * a focal length that is not positive; TB_EUNSUPPORTED: an image under 16 px in either dimension, more than 65535 sequences.
+ * Must be destroyed before its context. A filter that is never created changes nothing in any other call.
+ * `active` (add, update) and `which` (clear) are nullable HOST byte masks [nseq], as in tb_vo_step_ragged_dev: NULL = every sequence;
+ * an inactive sequence keeps every byte. images: device, sequence s at images + s * image_pitch, rows `stride` bytes apart; Tcw:
+ * device float [nseq][16], row-major world -> camera. A NULL image or pose, stride < width or image_pitch < stride * height is TB_EINVAL.
+ * tb_depth_filter_add_keyframe_dev: keys_xy device float [nseq][key_pitch][2] (level-0 pixels), counts device int32 [nseq] (clamped
+ * to 0..key_pitch), skip nullable device bytes [nseq][key_pitch] (non-zero: the key is not offered), not_added nullable device
+ * int32 [nseq] (written for the active sequences).
+ * tb_depth_filter_update_dev: one launch of k_df_update per run of consecutive active sequences -- one launch when all are active
+ * -- and nothing else: no host synchronisation, no copy.
+ * tb_depth_filter_points_dev: points device float [nseq][pitch][3] (zero where flags is 0), flags device bytes [nseq][pitch]: 1 where
+ * the entry is converged; release != 0 makes those entries free.
+ * tb_depth_filter_state_dev lends the device pointers (each output nullable): seeds / traces [nseq][pitch], slot_Tcw
+ * [nseq][ref_slots][16]; newest_slot: HOST int32 [nseq], filled with the slot of each sequence's last keyframe (-1: none yet). */
+typedef struct tb_depth_filter tb_depth_filter;
+typedef struct tb_depth_filter_params {
+    double depth_mean;   /* 15 */
+    double depth_min;    /* 2 */
+    double conv_div;     /* 200 */
+    double px_noise;     /* 1 */
+    int max_steps;       /* 1000 */
+    int zmssd_max;       /* 2000 */
+    int align_iters;     /* 10 */
+    int reserved;
+} tb_depth_filter_params;
+int tb_depth_filter_create(tb_ctx* ctx, int nseq, int pitch, int ref_slots, int width, int height, const double K[4],
+                           const tb_depth_filter_params* params, tb_depth_filter** out);
+void tb_depth_filter_destroy(tb_depth_filter* df);
+int tb_depth_filter_clear(tb_depth_filter* df, const uint8_t* which);
+int tb_depth_filter_add_keyframe_dev(tb_depth_filter* df, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw,
+                                     const float* keys_xy, const int32_t* counts, int key_pitch, const uint8_t* skip,
+                                     const uint8_t* active, int32_t* not_added);
+int tb_depth_filter_update_dev(tb_depth_filter* df, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw,
+                               const uint8_t* active);
+int tb_depth_filter_points_dev(tb_depth_filter* df, float* points, uint8_t* flags, int release);
+int tb_depth_filter_state_dev(tb_depth_filter* df, const tb_df_seed** seeds, const tb_df_trace** traces, const float** slot_Tcw,
+                              int32_t* newest_slot);
+
 /* ---- multi-GPU batch entry (SURVEY.md section 8(b) `tb_batch_run`, 8(e): frames are independent units through
  * extract -> left/right match, sharded as contiguous blocks of frames, one exchange step at the end).
  * The in-process counterpart of trackingbench_slam_amd/dist.py for a C++ host that holds one context per GPU:

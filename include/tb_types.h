@@ -141,6 +141,26 @@ typedef struct tb_sim3_graph_out {
     const double* stats;          /* [nseq][8] tb_pose_graph_sim3_batch_dev's */
 } tb_sim3_graph_out;
 
+/* One entry of a depth filter (tb_depth_filter_*, include/tb_capi.h): the reference pixel (u, v) at level 0 and the ring slot of
+ * its reference image; mu, sigma2: inverse range along the pixel's unit ray and its variance; a, b: the Beta counts of the inlier
+ * ratio; z_range = 1 / depth_min; state 0 free, 1 active, 2 converged, 3 dropped; updates: the updates that reached the match
+ * stage (success or NO_MATCH). 64 bytes. */
+typedef struct tb_df_seed {
+    double mu, sigma2, a, b, z_range;
+    float u, v;
+    int32_t slot, state, updates, reserved;
+} tb_df_seed;
+
+/* What the last update did with an entry: flag -1 idle (the entry was not active), 0 updated, 1 BEHIND, 2 OUTSIDE, 3 WARP,
+ * 4 DEGENERATE, 5 NO_MATCH, 6 CONVERGED (updated, and the state became 2), 7 NONFINITE; n: the sample count of the epipolar search
+ * (0 before step 4), win / score: the winning sample and its score (-1: none), (px, py): the aligned pixel, z: the range the two
+ * rays give, tau: its uncertainty (0 where the update did not get there). 56 bytes. */
+typedef struct tb_df_trace {
+    int64_t score;
+    double px, py, z, tau;
+    int32_t flag, n, win, reserved;
+} tb_df_trace;
+
 /* Error codes (0 = ok). */
 enum {
     TB_OK = 0,

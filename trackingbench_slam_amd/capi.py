@@ -28,6 +28,11 @@ PG_SIM3_EDGE = np.dtype([("a", "<i4"), ("b", "<i4"), ("srt", "<f8", (8,)), ("w_r
 CAMERA = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("width", "<i4"), ("height", "<i4"),
                    ("has_distortion", "<i4"), ("d", "<f4", (5,))])
 MAPPOINT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"), ("bad", "<i4")])
+# tb_df_seed / tb_df_trace of include/tb_types.h (the depth filter)
+DF_SEED = np.dtype([("mu", "<f8"), ("sigma2", "<f8"), ("a", "<f8"), ("b", "<f8"), ("z_range", "<f8"), ("u", "<f4"), ("v", "<f4"),
+                    ("slot", "<i4"), ("state", "<i4"), ("updates", "<i4"), ("reserved", "<i4")])
+DF_TRACE = np.dtype([("score", "<i8"), ("px", "<f8"), ("py", "<f8"), ("z", "<f8"), ("tau", "<f8"), ("flag", "<i4"), ("n", "<i4"),
+                     ("win", "<i4"), ("reserved", "<i4")])
 
 TB_OK, TB_EINVAL, TB_ENOMEM, TB_ECAPACITY, TB_EUNSUPPORTED, TB_EDEVICE, TB_ESTATE = 0, -1, -2, -3, -4, -5, -6
 
@@ -68,6 +73,8 @@ EXPORTS = [
     "tb_sim3_ransac", "tb_sim3_ransac_batch_dev", "tb_kf_store_sim3_dev", "tb_kf_store_sim3_state_dev", "tb_vo_relocalize_sim3_dev",
     "tb_sim3_optimize", "tb_sim3_optimize_batch_dev", "tb_kf_store_sim3_refine_dev", "tb_kf_store_sim3_refine_state_dev",
     "tb_vo_refine_sim3_dev",
+    "tb_depth_filter_create", "tb_depth_filter_destroy", "tb_depth_filter_clear", "tb_depth_filter_add_keyframe_dev",
+    "tb_depth_filter_update_dev", "tb_depth_filter_points_dev", "tb_depth_filter_state_dev",
     "tb_pose_graph_sim3", "tb_pose_graph_sim3_batch_dev", "tb_pose_graph_sim3_plan", "tb_kf_store_sim3_graph_dev", "tb_vo_loop_sim3_dev",
 ]
 
@@ -135,6 +142,9 @@ def lib():
         L.tb_kf_store_destroy.argtypes = [C.c_void_p]
         L.tb_lsh_destroy.restype = None
         L.tb_lsh_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "tb_depth_filter_destroy"):   # TB_HIP_LIB may name an older library (A/B runs)
+            L.tb_depth_filter_destroy.restype = None
+            L.tb_depth_filter_destroy.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -1539,6 +1549,76 @@ class BowDatabase:
                     kf_ids=((S, N), "<i4", torch.int32))
         out = {k: torch.as_tensor(_DevView(d[k], sh, ts), device=device).view(dt).clone() for k, (sh, ts, dt) in spec.items()}
         out["nadded"] = d["nadded"]
+        return out
+
+
+class DepthFilterParams(C.Structure):
+    """tb_depth_filter_params of include/tb_capi.h"""
+    _fields_ = [("depth_mean", C.c_double), ("depth_min", C.c_double), ("conv_div", C.c_double), ("px_noise", C.c_double),
+                ("max_steps", C.c_int), ("zmssd_max", C.c_int), ("align_iters", C.c_int), ("reserved", C.c_int)]
+
+
+def depth_filter_params(depth_mean=15.0, depth_min=2.0, conv_div=200.0, px_noise=1.0, max_steps=1000, zmssd_max=2000, align_iters=10):
+    return DepthFilterParams(float(depth_mean), float(depth_min), float(conv_div), float(px_noise), int(max_steps), int(zmssd_max),
+                             int(align_iters), 0)
+
+
+class DepthFilter:
+    """tb_depth_filter (include/tb_capi.h) on device pointers: per sequence `pitch` seeds and a ring of ref_slots reference images.
+    Every call is asynchronous on the context's stream; the methods return the library's status code. Masks are host bool [S]."""
+
+    def __init__(self, ctx, nseq, pitch, ref_slots, width, height, K, params=None):
+        self.ctx = ctx
+        self.nseq, self.pitch, self.ref_slots, self.width, self.height = int(nseq), int(pitch), int(ref_slots), int(width), int(height)
+        self.params = params if params is not None else depth_filter_params()
+        self._h = C.c_void_p()
+        ctx.check(lib().tb_depth_filter_create(ctx._h, self.nseq, self.pitch, self.ref_slots, self.width, self.height,
+                                               (C.c_double * 4)(*[float(k) for k in K]), C.byref(self.params), C.byref(self._h)))
+
+    def close(self):
+        if self._h and self.ctx._h:
+            lib().tb_depth_filter_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, m):
+        if m is None:
+            return None, None
+        a = np.ascontiguousarray(m, np.uint8)
+        assert a.shape == (self.nseq,)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def clear(self, which=None):
+        _keep, w = self._mask(which)
+        return lib().tb_depth_filter_clear(self._h, w)
+
+    def add_keyframe_dev(self, images_ptr, stride, image_pitch, Tcw_ptr, keys_ptr, counts_ptr, key_pitch, skip_ptr=0, active=None,
+                         not_added_ptr=0):
+        _keep, a = self._mask(active)
+        return lib().tb_depth_filter_add_keyframe_dev(self._h, C.c_void_p(images_ptr), int(stride), C.c_size_t(int(image_pitch)),
+                                                      C.c_void_p(Tcw_ptr), C.c_void_p(keys_ptr), C.c_void_p(counts_ptr), int(key_pitch),
+                                                      C.c_void_p(skip_ptr or None), a, C.c_void_p(not_added_ptr or None))
+
+    def update_dev(self, images_ptr, stride, image_pitch, Tcw_ptr, active=None):
+        _keep, a = self._mask(active)
+        return lib().tb_depth_filter_update_dev(self._h, C.c_void_p(images_ptr), int(stride), C.c_size_t(int(image_pitch)),
+                                                C.c_void_p(Tcw_ptr), a)
+
+    def points_dev(self, points_ptr, flags_ptr, release=False):
+        return lib().tb_depth_filter_points_dev(self._h, C.c_void_p(points_ptr), C.c_void_p(flags_ptr), int(bool(release)))
+
+    def state_dev(self):
+        """dict of device pointers (seeds, traces, slot_Tcw) + newest_slot, an int32 array [S] (-1: no keyframe yet)"""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        newest = np.zeros(self.nseq, np.int32)
+        self.ctx.check(lib().tb_depth_filter_state_dev(self._h, *[C.byref(q) for q in ptrs], _p(newest)))
+        out = {k: q.value for k, q in zip(("seeds", "traces", "slot_Tcw"), ptrs)}
+        out["newest_slot"] = newest
         return out
 
 

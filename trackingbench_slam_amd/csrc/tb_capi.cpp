@@ -13,6 +13,7 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <functional>
 #include <memory>
 #include <mutex>
 
@@ -2992,6 +2993,126 @@ int tb_batch_run(tb_ctx** ctxs, int ngpu, const tb_batch_params* p, int nframes,
     }
     release();
     return rc;
+}
+
+/* ---- the depth filter (see include/tb_capi.h; kernels in k_depth_filter.hip) */
+void tb_depth_filter_destroy(tb_depth_filter* df) {
+    if (!df) return;
+    if (df->ctx) { hipSetDevice(df->ctx->device); hipStreamSynchronize(df->ctx->stream); }
+    df->own.release();
+    delete df;
+}
+
+/* fn(s0, n) for every run of consecutive sequences the nullable host mask selects */
+static int df_for_runs(int nseq, const uint8_t* mask, const std::function<int(int, int)>& fn) {
+    for (int s = 0; s < nseq;) {
+        if (mask && !mask[s]) { s++; continue; }
+        int e = s + 1;
+        while (e < nseq && (!mask || mask[e])) e++;
+        TB_TRY(fn(s, e - s));
+        s = e;
+    }
+    return TB_OK;
+}
+
+int tb_depth_filter_clear(tb_depth_filter* df, const uint8_t* which) {
+    TB_ENTER((df ? df->ctx : nullptr));
+    if (!df) return TB_EINVAL;
+    tb_ctx* ctx = df->ctx;
+    return df_for_runs(df->nseq, which, [&](int s0, int n) -> int {
+        const size_t at = (size_t)s0 * df->pitch, cnt = (size_t)n * df->pitch;
+        TB_HIP(ctx, hipMemsetAsync(df->seeds + at, 0, cnt * sizeof(tb_df_seed), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(df->traces + at, 0, cnt * sizeof(tb_df_trace), ctx->stream));
+        TB_HIP(ctx, hipMemsetAsync(df->newest + s0, 0xff, (size_t)n * sizeof(int32_t), ctx->stream));
+        for (int s = s0; s < s0 + n; s++) df->h_newest[s] = -1;
+        return TB_OK;
+    });
+}
+
+int tb_depth_filter_create(tb_ctx* ctx, int nseq, int pitch, int ref_slots, int width, int height, const double K[4],
+                           const tb_depth_filter_params* prm, tb_depth_filter** out) {
+    TB_ENTER(ctx);
+    if (!ctx || !out) return TB_EINVAL;
+    *out = nullptr;
+    if (!K || !prm) return tb_fail(ctx, TB_EINVAL, "tb_depth_filter_create: null K / params");
+    if (nseq < 1 || pitch < 1 || ref_slots < 1 || ref_slots > 16 || width < 1 || height < 1)
+        return tb_fail(ctx, TB_EINVAL, "tb_depth_filter_create: %d sequences, pitch %d, %d reference slots (1..16), %d x %d", nseq, pitch,
+                       ref_slots, width, height);
+    if (!(prm->depth_min > 0.0) || !(prm->depth_mean >= prm->depth_min) || !std::isfinite(prm->depth_mean) || !(prm->conv_div > 0.0) ||
+        !std::isfinite(prm->conv_div) || !(prm->px_noise > 0.0) || !std::isfinite(prm->px_noise) || prm->max_steps < 1 ||
+        prm->zmssd_max < 0 || prm->align_iters < 0 || prm->align_iters > 99)
+        return tb_fail(ctx, TB_EINVAL, "tb_depth_filter_create: depth_mean %g, depth_min %g, conv_div %g, px_noise %g, max_steps %d, "
+                       "zmssd_max %d, align_iters %d (0..99)", prm->depth_mean, prm->depth_min, prm->conv_div, prm->px_noise, prm->max_steps,
+                       prm->zmssd_max, prm->align_iters);
+    if (!(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_depth_filter_create: K");
+    if (width < 16 || height < 16) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_depth_filter_create: a %d x %d image (16 x 16 at least)", width, height);
+    if (nseq > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_depth_filter_create: %d sequences (65535 at most)", nseq);
+    std::unique_ptr<tb_depth_filter, void (*)(tb_depth_filter*)> du(new tb_depth_filter(), tb_depth_filter_destroy);
+    tb_depth_filter* df = du.get();
+    df->ctx = ctx; df->nseq = nseq; df->pitch = pitch; df->ref_slots = ref_slots; df->width = width; df->height = height;
+    for (int i = 0; i < 4; i++) df->K[i] = K[i];
+    df->prm = *prm;
+    df->px_err = 2.0 * std::atan(prm->px_noise / (2.0 * std::sqrt(K[0] * K[1])));
+    df->h_newest.assign(nseq, -1);
+    const size_t n = (size_t)nseq * pitch;
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->seeds, n));
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->traces, n));
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->freelist, n, 0));
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->ring, (size_t)nseq * ref_slots * width * height, 0));
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->ring_Tcw, (size_t)nseq * ref_slots * 16, 0));
+    TB_TRY(tb_dev_alloc(ctx, df->own, &df->newest, (size_t)nseq));
+    TB_TRY(tb_depth_filter_clear(df, nullptr));
+    *out = du.release();
+    return TB_OK;
+}
+
+static int df_frame_args(tb_depth_filter* df, const char* who, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw) {
+    if (!images || !Tcw) return tb_fail(df->ctx, TB_EINVAL, "%s: null images / Tcw", who);
+    if (stride < df->width || image_pitch < (size_t)stride * df->height)
+        return tb_fail(df->ctx, TB_EINVAL, "%s: stride %d, image pitch %zu for %d x %d images", who, stride, image_pitch, df->width, df->height);
+    return TB_OK;
+}
+
+int tb_depth_filter_add_keyframe_dev(tb_depth_filter* df, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw,
+                                     const float* keys_xy, const int32_t* counts, int key_pitch, const uint8_t* skip,
+                                     const uint8_t* active, int32_t* not_added) {
+    TB_ENTER((df ? df->ctx : nullptr));
+    if (!df) return TB_EINVAL;
+    TB_TRY(df_frame_args(df, "tb_depth_filter_add_keyframe_dev", images, stride, image_pitch, Tcw));
+    if (!keys_xy || !counts || key_pitch < 1) return tb_fail(df->ctx, TB_EINVAL, "tb_depth_filter_add_keyframe_dev: keys / counts / key pitch %d", key_pitch);
+    return df_for_runs(df->nseq, active, [&](int s0, int n) -> int {
+        TB_TRY(tbk_df_add(df, s0, n, images, stride, image_pitch, Tcw, keys_xy, counts, key_pitch, skip, not_added));
+        for (int s = s0; s < s0 + n; s++) df->h_newest[s] = (df->h_newest[s] + 1) % df->ref_slots;
+        return TB_OK;
+    });
+}
+
+int tb_depth_filter_update_dev(tb_depth_filter* df, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw,
+                               const uint8_t* active) {
+    TB_ENTER((df ? df->ctx : nullptr));
+    if (!df) return TB_EINVAL;
+    TB_TRY(df_frame_args(df, "tb_depth_filter_update_dev", images, stride, image_pitch, Tcw));
+    return df_for_runs(df->nseq, active, [&](int s0, int n) -> int { return tbk_df_update(df, s0, n, images, stride, image_pitch, Tcw); });
+}
+
+int tb_depth_filter_points_dev(tb_depth_filter* df, float* points, uint8_t* flags, int release) {
+    TB_ENTER((df ? df->ctx : nullptr));
+    if (!df) return TB_EINVAL;
+    if (!points || !flags) return tb_fail(df->ctx, TB_EINVAL, "tb_depth_filter_points_dev: null points / flags");
+    return tbk_df_points(df, points, flags, release);
+}
+
+int tb_depth_filter_state_dev(tb_depth_filter* df, const tb_df_seed** seeds, const tb_df_trace** traces, const float** slot_Tcw,
+                              int32_t* newest_slot) {
+    TB_ENTER((df ? df->ctx : nullptr));
+    if (!df) return TB_EINVAL;
+    if (seeds) *seeds = df->seeds;
+    if (traces) *traces = df->traces;
+    if (slot_Tcw) *slot_Tcw = df->ring_Tcw;
+    if (newest_slot)
+        for (int s = 0; s < df->nseq; s++) newest_slot[s] = df->h_newest[s];
+    return TB_OK;
 }
 
 }  // extern "C"

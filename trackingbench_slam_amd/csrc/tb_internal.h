@@ -327,6 +327,28 @@ struct tb_kf_store {
 extern "C" int tb_kf_store_sim3_graph_run(tb_kf_store* st, const char* who, const float* q_Tcw, int frame_id, int iters, int fixed_scale, double w_rot,
                                double w_trans, double w_scale, tb_sim3_graph_out* out);
 
+/* the depth filter (k_depth_filter.hip): per sequence `pitch` entries, a ring of ref_slots reference images with their poses */
+struct tb_depth_filter {
+    tb_ctx* ctx = nullptr;
+    int nseq = 0, pitch = 0, ref_slots = 0, width = 0, height = 0;
+    double K[4] = {};
+    double px_err = 0.0;                  /* 2 atan(px_noise / (2 sqrt(fx fy))) */
+    tb_depth_filter_params prm = {};
+    tb_dev_owner own;
+    tb_df_seed* seeds = nullptr;          /* [nseq][pitch] */
+    tb_df_trace* traces = nullptr;        /* [nseq][pitch] */
+    uint8_t* ring = nullptr;              /* [nseq][ref_slots][height][width] */
+    float* ring_Tcw = nullptr;            /* [nseq][ref_slots][16] */
+    int32_t* newest = nullptr;            /* [nseq] the slot of the last keyframe, -1 before the first */
+    int32_t* freelist = nullptr;          /* [nseq][pitch] k_df_add's list of free entries */
+    std::vector<int32_t> h_newest;        /* the host's copy of newest: the same rule, no read back */
+};
+/* one launch over sequences [seq0, seq0 + nseq) */
+int tbk_df_update(tb_depth_filter* df, int seq0, int nseq, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw);
+int tbk_df_add(tb_depth_filter* df, int seq0, int nseq, const uint8_t* images, int stride, size_t image_pitch, const float* Tcw,
+               const float* keys_xy, const int32_t* counts, int key_pitch, const uint8_t* skip, int32_t* not_added);
+int tbk_df_points(tb_depth_filter* df, float* points, uint8_t* flags, int release);
+
 /* kernel launchers (k_*.hip) */
 int tbk_resize_level(tb_extractor* ex, int level, int n);
 int tbk_fast_cells(tb_extractor* ex, int n, int init_th, int min_th);
