@@ -544,6 +544,8 @@ int tb_kf_store_sim3_state_dev(tb_kf_store* st, const tb_sim3_row** rows, const 
  *           reach min_inliers (ORB-SLAM asks for 20), the store's own copy of best_srt takes the refined srt: that is the copy
  *           tb_kf_store_sim3_graph_dev reads, so the next graph query has the refined transform as its loop edge. With
  *           use_for_graph = 0 nothing of the store changes but this query's own buffers
+ * After a tb_kf_store_sim3_search_dev with use_for_refine = 1 (below) the rows stage reads that query's widened match lists in place
+ * of the verification's and every row starts active; nothing else differs.
  * cand_srt [nseq][ncand][8] and cand_consensus [nseq][ncand]: what the Sim(3) query wrote; each is NULL where that query was not
  * given that output, so that it is in the store's own buffer. tb_sim3_refine_out (every pointer nullable, device): cand_srt
  * [nseq][ncand][8], cand_S12 [nseq][ncand][16], cand_inliers [nseq][ncand], cand_stats [nseq][ncand][8]; best_srt [nseq][8],
@@ -573,6 +575,49 @@ int tb_kf_store_sim3_refine_dev(tb_kf_store* st, const double K[4], int nlevels,
                                 int min_inliers, int use_for_graph, const tb_sim3_refine_out* out);
 int tb_kf_store_sim3_refine_state_dev(tb_kf_store* st, const tb_sim3_obs_row** rows, const int32_t** row_counts, const uint8_t** active,
                                       const uint8_t** inlier);
+/* ORB-SLAM's SearchBySim3 between the Sim(3) query and its refinement: tb_search_by_sim3_batch_dev (below, with the rules) on every
+ * candidate pair of the last tb_kf_store_sim3_dev, so that OptimizeSim3 also sees the correspondences searchByBow let drop (one word of
+ * the vocabulary, TH_LOW, the ratio test, the rotation histogram) although the similarity already says where they are (DESIGN.md 9r;
+ * tests/reloc_sim3_search_reference.py is the composition on the CPU). Valid after a tb_kf_store_sim3_dev, with that query's arguments
+ * passed again as tb_kf_store_sim3_refine_dev takes them, plus the query frames' descriptors q_desc [nseq][q_pitch][32] and the
+ * image size. cand_srt / cand_consensus: what the Sim(3) query wrote (NULL where it kept them in the store); a caller may pass the
+ * REFINED cand_srt instead, to search again under the refined transform. Per pair c = s * ncand + r:
+ *   prep    the camera points of EVERY key of both sides, formed exactly as the row kernel forms X1 and X2 (the frame's Tcw applied to
+ *           the key's world point, float64, stored as float32). A key is `already matched` if it belongs to a row of the Sim(3)
+ *           query's list whose RANSAC mask is 1. A pair with no candidate or with a consensus below 3 (a flagged Sim(3) output has
+ *           consensus 0) is skipped: cand_stats flag 2, no pairs, no widened list
+ *   search  the operator with side 1 = the query frame, side 2 = the stored keyframe, read in place
+ *   merge   the widened match list: the RANSAC-inlier rows' matches (the verification's records, as they stand) united with the new
+ *           pairs, in ascending query key, one entry a key; a count goes with it
+ * tb_sim3_search_out (every pointer nullable, device): cand_new [nseq][ncand] the new pairs, cand_total [nseq][ncand] the widened
+ * list's length, cand_stats [nseq][ncand][8] the operator's; best_new [nseq] and best_total [nseq] for the candidate the Sim(3) query
+ * selected (0 where it selected none).
+ * With use_for_refine = 1 the next tb_kf_store_sim3_refine_dev builds its pixel rows from the widened lists, by the same row kernel,
+ * and starts with every one of those rows active: that is what ORB-SLAM hands OptimizeSim3. Its signature, its skip rule and its
+ * selection are unchanged, and tb_kf_store_sim3_refine_state_dev then shows the widened rows and an all-ones active mask;
+ * tb_kf_store_work_dev and tb_kf_store_sim3_state_dev keep showing the verification's and the RANSAC's own bytes. A new
+ * tb_relocalize_batch_dev, tb_kf_store_sim3_dev or tb_kf_store_clear drops the widened lists. With use_for_refine = 0 nothing of the
+ * store changes but this query's own buffers. Asynchronous, no host synchronisation; the first call may allocate the query's
+ * buffers, a store that never calls it launches and holds what it did before.
+ * TB_ESTATE: as tb_kf_store_sim3_refine_dev's (no Sim(3) query, a tb_relocalize_batch_dev since that query, cand_srt or
+ * cand_consensus NULL although the Sim(3) query wrote it elsewhere, a best_* output although nothing was selected). TB_EINVAL: as
+ * tb_search_by_sim3_batch_dev and tb_kf_store_sim3_dev, use_for_refine not 0 or 1.
+ * tb_kf_store_sim3_search_state_dev lends device views of the last call's match1 [pairs][q_pitch], match2 [pairs][pitch], the new
+ * pairs [pairs][pitch] with pair_counts [pairs] and the widened lists [pairs][pitch] with widened_counts [pairs] (each nullable);
+ * q_pitch: that call's. TB_ESTATE before the first tb_kf_store_sim3_search_dev. */
+typedef struct tb_sim3_search_out {
+    int32_t* cand_new;
+    int32_t* cand_total;
+    int32_t* cand_stats;
+    int32_t* best_new;
+    int32_t* best_total;
+} tb_sim3_search_out;
+int tb_kf_store_sim3_search_dev(tb_kf_store* st, const double K[4], int width, int height, int nlevels, float scale, const tb_keypoint* q_keys,
+                                const uint8_t* q_desc, const int32_t* q_counts, const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch,
+                                const float* q_Tcw, const int32_t* cand_slot, int ncand, const double* cand_srt, const int32_t* cand_consensus,
+                                float th, int th_high, int use_for_refine, const tb_sim3_search_out* out);
+int tb_kf_store_sim3_search_state_dev(tb_kf_store* st, const int32_t** match1, const int32_t** match2, const tb_match** pairs,
+                                      const int32_t** pair_counts, const tb_match** widened, const int32_t** widened_counts, int* q_pitch);
 /* Batched, device-resident Matcher::searchByBow(F1, F2, MapPointOnly) (matcher.cpp:619-721) on feature vectors in the
  * list form above, grouped by ascending node id (inside a node, list order is the visiting order): pair p matches frame p
  * of side 1 against frame p of side 2 (keys / descriptors [npairs][pitchX], fv keys [npairs][pitchX] with fv_countsX[p]
@@ -851,6 +896,50 @@ int tb_sim3_optimize_batch_dev(tb_ctx* ctx, int nproblems, const double K[4], co
 int tb_sim3_optimize(tb_ctx* ctx, const double K[4], const tb_sim3_obs_row* rows, int n, const uint8_t* active, const double srt_in[8],
                      const tb_sim3_opt_params* params, double srt_out[8], float S12[16], int* inliers, uint8_t* inlier_mask,
                      double stats[8]);
+/* Guided mutual matching under a similarity: ORB-SLAM's ORBmatcher::SearchBySim3, which LoopClosing runs between the Sim3Solver and
+ * OptimizeSim3 so that the refinement also sees the correspondences the bag-of-words matcher let drop; batched and device-resident.
+ * The reference has no such step; tests/sim3_search_reference.py is the definition, statement for statement, and the kernels give
+ * the same integers.
+ * Pair p has two sides. Side k reads countsk[p] keys (clamped to [0, pitchk]) at keysk + p * pitchk, their descriptors at descK +
+ * 32 p pitchk, the keys' points IN THE SIDE'S OWN CAMERA FRAME at pointsk + 3 p pitchk (float32), a validity byte a key (validk: the
+ * key has a point) and an `already matched` byte a key (matchedk). srt + 8 p is the similarity in tb_sim3_ransac_batch_dev's layout
+ * (FP64: the quaternion w x y z, taken as it is given, then t, then s): X1 = s R X2 + t. Shared by the batch: K = fx, fy, cx, cy
+ * (host), the image width x height, and the level table g[l], l < nlevels: the size of a level-l pixel in level-0 pixels, which is
+ * tb_scale_factors(nlevels, scale)'s inv_sf (float32; 1.25^l at this project's scale = 0.8) -- ORB-SLAM's mvScaleFactors. (sf, the
+ * shrink factor 0.8^l, cannot serve: under it 0.8 minD <= d <= 1.2 maxD below has no solution once sf[nlevels - 1] < 2 / 3.)
+ *   1 -> 2    for every key i of side 1 below the count with valid1[i] != 0 and matched1[i] == 0 (a point that is TRIED):
+ *             P = R' (X1c[i] - t) / s; skipped unless P.z > 0; u = fx (P.x / P.z) + cx, v likewise; skipped unless 0 <= u < width
+ *             and 0 <= v < height; maxD = |X1c[i]| g[octave_i], minD = maxD / g[nlevels - 1]; d = s |P| (the length in side 1's
+ *             units); skipped unless 0.8 minD <= d <= 1.2 maxD; the predicted level L is the smallest l with g[l] d >= maxD, or
+ *             nlevels - 1 if there is none (ORB-SLAM's ceil(log(maxD / d) / log(1.2)) clamped, written with comparisons against the
+ *             table); r = th g[L]. The point has then REACHED THE SEARCH: its candidates are all keys j of side 2 below the count
+ *             with |x_j - u| < r, |y_j - v| < r and octave L - 1 or L (a candidate need not have a point and may be matched
+ *             already: ORB-SLAM); the best has the smallest Hamming distance between the two KEYS' descriptors, a tie goes to the
+ *             lowest j (the minimum of distance << 32 | j: the visiting order decides nothing). match1[i] = j if that distance is
+ *             <= th_high, else -1
+ *   2 -> 1    the same with P = s (R X2c[j]) + t, d = |P| / s and the sides exchanged: match2[j]
+ *   agreement (i, j) is a new pair where match1[i] = j and match2[j] = i; new pairs are listed in ascending i
+ *   numbers   float64 from the float32 inputs, one rounding a statement, no contraction, only + - * / sqrt; a dot product adds its
+ *             terms left to right; |x| = sqrt((x0 x0 + x1 x1) + x2 x2). No atomic on any path that decides an output
+ * Two stated deviations from ORB-SLAM: the key's own descriptor stands for the map point's (a store holds no representative
+ * descriptor), and the range test and the level prediction compare lengths in one map's units (s |P|, |P| / s) where ORB-SLAM
+ * compares them raw; the two coincide at s = 1.
+ * Out (device, each nullable): match1 [npairs][pitch1] and match2 [npairs][pitch2] int32 (-1 beyond the count too); pairs
+ * [npairs][cap] tb_match (queryIdx = i, trainIdx = j, imgIdx = -1, distance = the Hamming distance) with pair_counts [npairs]: the
+ * list is truncated at cap, the count is not; stats [npairs][8] int32 = points tried 1 -> 2, points that reached the search 1 -> 2,
+ * the same two for 2 -> 1, accepted 1 -> 2, accepted 2 -> 1, new pairs, flag. A malformed problem -- a key below a count whose
+ * octave lies outside 0 .. nlevels - 1, or an s that is not finite or not above 0 -- is flagged: flag 1, every match -1, counts
+ * and the other stats 0. Asynchronous on the context's stream, no host synchronisation, no host <-> device copy; two launches
+ * (k_sim3_search: chunks of 256 source keys x 2 directions x pairs; k_sim3_search_agree: one workgroup a pair); a problem gives the
+ * same bits alone, in any batch, in any slot and from run to run. At most 65535 pairs per call (TB_EUNSUPPORTED). TB_EINVAL: null
+ * inputs, a pitch outside 1..8192, nlevels outside 1..16, th not positive, th_high outside 0..256, width or height not positive,
+ * scale not positive, K not finite, fx or fy not positive, cap < 0 (cap < 1 with pairs). ORB-SLAM: th = 7.5, th_high = 100. */
+int tb_search_by_sim3_batch_dev(tb_ctx* ctx, int npairs, const double K[4], int width, int height, int nlevels, float scale,
+                                const tb_keypoint* keys1, const uint8_t* desc1, const float* points1, const uint8_t* valid1,
+                                const uint8_t* matched1, const int32_t* counts1, int pitch1, const tb_keypoint* keys2, const uint8_t* desc2,
+                                const float* points2, const uint8_t* valid2, const uint8_t* matched2, const int32_t* counts2, int pitch2,
+                                const double* srt, float th, int th_high, int32_t* match1, int32_t* match2, tb_match* pairs, int cap,
+                                int32_t* pair_counts, int32_t* stats);
 /* A relative pose and first points from 2D-2D rows alone: 8-point hypotheses in a RANSAC, a least-squares refit, the four
  * decompositions of E told apart by triangulation; batched and device-resident. The reference has no such step (its
  * LinearTriangle is handed poses); this is ORB-SLAM's Initializer on its fundamental-matrix branch (DESIGN.md 9m has the
@@ -1349,6 +1438,13 @@ int tb_vo_loop_sim3_dev(tb_vo* vo, int iters, int fixed_scale, double w_rot, dou
 struct tb_sim3_opt_params;
 int tb_vo_refine_sim3_dev(tb_vo* vo, int topk, const double* cand_srt, const int32_t* cand_consensus, const struct tb_sim3_opt_params* params,
                           int min_inliers, int use_for_graph, const tb_sim3_refine_out* out);
+/* tb_vo_search_sim3_dev is a query after tb_vo_relocalize_sim3_dev: tb_kf_store_sim3_search_dev with the loop's current ORB keys and
+ * descriptors, its carried map points, its pose and its image size, on the candidates of the last tb_vo_relocalize_dev. cand_srt /
+ * cand_consensus, topk and TB_ESTATE as tb_vo_refine_sim3_dev's: every step and reset invalidates it, and so does a
+ * tb_vo_relocalize_dev after the Sim(3) query. It reads the loop and writes only the store's search buffers: a loop that never calls
+ * it ends in the same bytes. With use_for_refine = 1 the next tb_vo_refine_sim3_dev refines on the widened lists. */
+int tb_vo_search_sim3_dev(tb_vo* vo, int topk, const double* cand_srt, const int32_t* cand_consensus, float th, int th_high, int use_for_refine,
+                          const tb_sim3_search_out* out);
 /* tb_kf_store_pnp_enable on the loop's store: tb_vo_relocalize_dev then runs the PnP verification (tb_kf_store_pnp_state_dev on
  * tb_vo_kf_store_get's store lends its per-pair outputs) and stays a query that changes no state tensor. TB_ESTATE: relocalisation
  * not enabled, after the first step, enabled already, or together with tb_vo_recover_enable / tb_vo_loop_enable in either order:

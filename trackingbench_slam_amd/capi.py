@@ -73,6 +73,7 @@ EXPORTS = [
     "tb_sim3_ransac", "tb_sim3_ransac_batch_dev", "tb_kf_store_sim3_dev", "tb_kf_store_sim3_state_dev", "tb_vo_relocalize_sim3_dev",
     "tb_sim3_optimize", "tb_sim3_optimize_batch_dev", "tb_kf_store_sim3_refine_dev", "tb_kf_store_sim3_refine_state_dev",
     "tb_vo_refine_sim3_dev",
+    "tb_search_by_sim3_batch_dev", "tb_kf_store_sim3_search_dev", "tb_kf_store_sim3_search_state_dev", "tb_vo_search_sim3_dev",
     "tb_depth_filter_create", "tb_depth_filter_destroy", "tb_depth_filter_clear", "tb_depth_filter_add_keyframe_dev",
     "tb_depth_filter_update_dev", "tb_depth_filter_points_dev", "tb_depth_filter_state_dev",
     "tb_pose_graph_sim3", "tb_pose_graph_sim3_batch_dev", "tb_pose_graph_sim3_plan", "tb_kf_store_sim3_graph_dev", "tb_vo_loop_sim3_dev",
@@ -375,6 +376,23 @@ def sim3_out(S, ncand, device):
     return so, t
 
 
+class Sim3SearchOut(C.Structure):
+    """tb_sim3_search_out of include/tb_capi.h: device pointers, each nullable"""
+    _fields_ = [(n, C.c_void_p) for n in ("cand_new", "cand_total", "cand_stats", "best_new", "best_total")]
+
+
+def sim3_search_out(S, ncand, device, best=True):
+    """(Sim3SearchOut, dict of the torch tensors it points to): every output of a SearchBySim3 query of S sequences x ncand
+    candidates; best=False leaves out best_new / best_total (the Sim(3) query selected nothing)"""
+    import torch
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=device)
+    t = dict(cand_new=i32(S, ncand), cand_total=i32(S, ncand), cand_stats=i32(S, ncand, 8))
+    if best:
+        t.update(best_new=i32(S), best_total=i32(S))
+    so = Sim3SearchOut(**{k: (v.data_ptr() if v.numel() else None) for k, v in t.items()})
+    return so, t
+
+
 class Sim3GraphOut(C.Structure):
     """tb_sim3_graph_out of include/tb_types.h: device pointers into the store's buffers"""
     _fields_ = [("nn", C.c_int)] + [(n, C.c_void_p) for n in ("nnodes", "node_kf", "before", "after", "edges", "edge_counts", "stats")]
@@ -571,6 +589,17 @@ class VO:
         srt, cons = (sim3 or {}).get("cand_srt"), (sim3 or {}).get("cand_consensus")
         return lib().tb_vo_refine_sim3_dev(self._h, int(topk), p(srt), p(cons), C.byref(prm), int(min_inliers), int(use_for_graph), C.byref(ro)), out
 
+    def search_sim3_dev(self, device, sim3, th=7.5, th_high=100, use_for_refine=True, topk=None, best=True):
+        """tb_vo_search_sim3_dev after relocalize_sim3_dev: (status code, dict of device tensors with tb_sim3_search_out's fields
+        [nseq, topk, ...]). sim3: a dict with cand_srt and cand_consensus (relocalize_sim3_dev's, or one with a refined cand_srt);
+        topk None = the topk of this object's last relocalize_dev; the library refuses any other count. use_for_refine is passed
+        through as an int, so that the argument check can be tested."""
+        topk = getattr(self, "_reloc_topk", 1) if topk is None else topk
+        so, out = sim3_search_out(self.nseq, max(int(topk), 0), device, best)
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        srt, cons = (sim3 or {}).get("cand_srt"), (sim3 or {}).get("cand_consensus")
+        return lib().tb_vo_search_sim3_dev(self._h, int(topk), p(srt), p(cons), C.c_float(th), int(th_high), int(use_for_refine), C.byref(so)), out
+
     def loop_sim3_dev(self, device, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
         """tb_vo_loop_sim3_dev after relocalize_sim3_dev: (status code, sim3_graph_tensors' dict -- copies made on the current
         stream, which the caller makes the loop's -- or None). fixed_scale is passed through as an int, so that the argument check
@@ -674,6 +703,7 @@ class Context:
 
     def __init__(self, device=0, stream=None):
         self._h = C.c_void_p()
+        self.device = int(device)
         rc = lib().tb_create(int(device), C.byref(self._h))
         if rc:
             raise TBError(rc, "tb_create(device=%d): %s" % (device, lib().tb_strerror(rc).decode()))
@@ -1253,6 +1283,64 @@ class Context:
                                                 v(srt_in_ptr), C.byref(prm), v(srt_out_ptr), v(S12_ptr), v(inliers_ptr), v(mask_ptr),
                                                 v(stats_ptr))
 
+    def search_by_sim3_dev(self, npairs, K, width, height, nlevels, scale, side1, side2, srt_ptr, th=7.5, th_high=100, match1_ptr=0,
+                           match2_ptr=0, pairs_ptr=0, cap=0, pair_counts_ptr=0, stats_ptr=0):
+        """tb_search_by_sim3_batch_dev: side1 / side2 = (keys_ptr, desc_ptr, points_ptr, valid_ptr, matched_ptr, counts_ptr, pitch),
+        device pointers (0 / None for the nullable outputs), asynchronous on the context's stream. Returns the status code."""
+        K = np.ascontiguousarray(K, np.float64)
+        v = lambda q: C.c_void_p(q or None)
+        a = []
+        for sd in (side1, side2):
+            a += [v(q) for q in sd[:6]] + [int(sd[6])]
+        return lib().tb_search_by_sim3_batch_dev(self._h, int(npairs), _p(K), int(width), int(height), int(nlevels), C.c_float(scale), *a,
+                                                 v(srt_ptr), C.c_float(th), int(th_high), v(match1_ptr), v(match2_ptr), v(pairs_ptr),
+                                                 int(cap), v(pair_counts_ptr), v(stats_ptr))
+
+    def search_by_sim3(self, sides1, sides2, srt, K, width, height, nlevels, scale, th=7.5, th_high=100, cap=None):
+        """ORB-SLAM's SearchBySim3 on host arrays, one pair or several in one call. A side is a dict(keys = KEYPOINT records [n], desc
+        uint8 [n][32], points float32 [n][3] in the side's own camera frame, valid [n], matched [n] (optional)); sides1 / sides2 are one
+        such dict each and srt [8] (w x y z, t, s: X1 = s R X2 + t), or lists of them and srt [P][8]. Returns a dict (or a list of
+        dicts): match1 [n1] and match2 [n2] int32, pairs (MATCH records, ascending queryIdx, at most cap of them), pair_count (not
+        truncated), stats [8] int32 (tried, searched 1 -> 2; tried, searched 2 -> 1; accepted 1 -> 2, 2 -> 1; new pairs; flag)."""
+        import torch
+        one = isinstance(sides1, dict)
+        if one:
+            sides1, sides2 = [sides1], [sides2]
+        P = len(sides1)
+        srt = np.ascontiguousarray(srt, np.float64).reshape(P, 8)
+        dev = torch.device("cuda", self.device)
+        packed = []
+        for sides in (sides1, sides2):
+            pitch = max(1, max(len(s["keys"]) for s in sides))
+            keys, desc = np.zeros((P, pitch), KEYPOINT), np.zeros((P, pitch, 32), np.uint8)
+            pts, val, mat = np.zeros((P, pitch, 3), np.float32), np.zeros((P, pitch), np.uint8), np.zeros((P, pitch), np.uint8)
+            cnt = np.zeros(P, np.int32)
+            for p, s in enumerate(sides):
+                n = cnt[p] = len(s["keys"])
+                keys[p, :n], desc[p, :n] = s["keys"], np.asarray(s["desc"], np.uint8).reshape(n, 32)
+                pts[p, :n], val[p, :n] = np.asarray(s["points"], np.float32).reshape(n, 3), np.asarray(s["valid"]).reshape(n) != 0
+                if s.get("matched") is not None:
+                    mat[p, :n] = np.asarray(s["matched"]).reshape(n) != 0
+            t = [torch.from_numpy(a.view(np.uint8) if a.dtype == KEYPOINT else a).to(dev) for a in (keys, desc, pts, val, mat, cnt)]
+            packed.append((t, pitch))
+        (t1, p1), (t2, p2) = packed
+        cap = max(1, min(p1, p2) if cap is None else int(cap))
+        i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
+        m1, m2, pr, pc, st = i32(P, p1), i32(P, p2), i32(P, cap, 4), i32(P), i32(P, 8)
+        dsrt = torch.from_numpy(srt).to(dev)
+        torch.cuda.current_stream(dev).synchronize()   # the uploads ran on torch's stream, the call runs on the context's
+        self.check(self.search_by_sim3_dev(P, K, width, height, nlevels, scale, tuple(x.data_ptr() for x in t1) + (p1,),
+                                           tuple(x.data_ptr() for x in t2) + (p2,), dsrt.data_ptr(), th, th_high, m1.data_ptr(), m2.data_ptr(),
+                                           pr.data_ptr(), cap, pc.data_ptr(), st.data_ptr()))
+        self.synchronize()
+        m1, m2, pr, pc, st = (x.cpu().numpy() for x in (m1, m2, pr, pc, st))
+        out = []
+        for p in range(P):
+            n = min(int(pc[p]), cap)
+            out.append(dict(match1=m1[p, :len(sides1[p]["keys"])].copy(), match2=m2[p, :len(sides2[p]["keys"])].copy(),
+                            pairs=np.ascontiguousarray(pr[p, :n]).view(MATCH).reshape(n), pair_count=int(pc[p]), stats=st[p].copy()))
+        return out[0] if one else out
+
     def two_view(self, xy0, xy1, K, skip=None, inv_sigma2_0=None, inv_sigma2_1=None, Tcw0=None, **params):
         """tb_two_view: a relative pose and first points from the n point pairs (xy0 / xy1 [n][2] pixels) of one problem; params as
         two_view_params. Returns a dict: status, Tcw1 [4, 4] float32, points [n][3] float32 (zero where nothing was written),
@@ -1800,13 +1888,51 @@ class KeyframeStore:
     def sim3_refine_state(self, device, ncand):
         """tb_kf_store_sim3_refine_state_dev: torch VIEWS (not copies) of the last refinement's work for S x ncand pairs: rows
         [pairs, P, 12] float32 (SIM3_OBS_ROW records), row_counts [pairs], active [pairs, P] uint8 (the Sim(3) query's masks, where the
-        refinement started), inlier [pairs, P] uint8."""
+        refinement started; all ones after a sim3_search with use_for_refine), inlier [pairs, P] uint8."""
         import torch
         ptrs = [C.c_void_p() for _ in range(4)]
         self.ctx.check(lib().tb_kf_store_sim3_refine_state_dev(self._h, *[C.byref(q) for q in ptrs]))
         n, P = self.nseq * int(ncand), self.pitch
         spec = (("rows", (n, P, 12), "<f4", torch.float32), ("row_counts", (n,), "<i4", torch.int32), ("active", (n, P), "|u1", torch.uint8),
                 ("inlier", (n, P), "|u1", torch.uint8))
+        return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
+
+    def sim3_search_rc(self, K, width, height, nlevels, scale, q_keys, q_desc, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot, sim3,
+                       th=7.5, th_high=100, use_for_refine=True, ncand=None, q_pitch=None, best=True):
+        """tb_kf_store_sim3_search_dev after a sim3 -> (status code, dict of output tensors with tb_sim3_search_out's fields): ORB-SLAM's
+        SearchBySim3 on every candidate pair. The arguments are those the sim3 call took plus the query's descriptors q_desc [S, Q, 32]
+        and the image size; sim3 is the dict it returned (its cand_srt and cand_consensus; a refined cand_srt may stand in; None: the
+        store's own buffers). use_for_refine: the next sim3_refine runs on the widened lists; it is passed through as an int, so
+        that the argument check can be tested. best=False: no best_* outputs (for a sim3 that selected nothing)."""
+        ts = (q_keys, q_desc, q_counts, q_map_points, q_mp_valid, q_Tcw, cand_slot)
+        assert all(t.is_contiguous() for t in ts)
+        ncand = int(cand_slot.shape[1] if ncand is None else ncand)
+        so, out = sim3_search_out(self.nseq, max(min(ncand, cand_slot.shape[1]), 0), q_keys.device, best)
+        Kd = (C.c_double * 4)(*[float(k) for k in K])
+        p = [C.c_void_p(t.data_ptr()) for t in ts]
+        v = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        srt, cons = (sim3 or {}).get("cand_srt"), (sim3 or {}).get("cand_consensus")
+        rc = lib().tb_kf_store_sim3_search_dev(self._h, Kd, int(width), int(height), int(nlevels), C.c_float(scale), p[0], p[1], p[2], p[3], p[4],
+                                               int(q_keys.shape[1] if q_pitch is None else q_pitch), p[5], p[6], ncand, v(srt), v(cons),
+                                               C.c_float(th), int(th_high), int(use_for_refine), C.byref(so))
+        return rc, out
+
+    def sim3_search(self, *a, **kw):
+        rc, out = self.sim3_search_rc(*a, **kw)
+        self.ctx.check(rc)
+        return out
+
+    def sim3_search_state(self, device, ncand):
+        """tb_kf_store_sim3_search_state_dev: torch VIEWS (not copies) of the last search's work for S x ncand pairs: match1 [pairs, Q]
+        int32 (Q = that call's query pitch), match2 [pairs, P] int32, pairs [pairs, P, 4] int32 (MATCH records) with pair_counts
+        [pairs], widened [pairs, P, 4] int32 with widened_counts [pairs]."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(6)]
+        qp = C.c_int(0)
+        self.ctx.check(lib().tb_kf_store_sim3_search_state_dev(self._h, *[C.byref(q) for q in ptrs], C.byref(qp)))
+        n, P, Q = self.nseq * int(ncand), self.pitch, qp.value
+        spec = (("match1", (n, Q), "<i4", torch.int32), ("match2", (n, P), "<i4", torch.int32), ("pairs", (n, P, 4), "<i4", torch.int32),
+                ("pair_counts", (n,), "<i4", torch.int32), ("widened", (n, P, 4), "<i4", torch.int32), ("widened_counts", (n,), "<i4", torch.int32))
         return {k: torch.as_tensor(_DevView(q.value, sh, ts), device=device).view(dt) for q, (k, sh, ts, dt) in zip(ptrs, spec)}
 
     def sim3_graph_rc(self, q_Tcw, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):

@@ -629,6 +629,32 @@ __device__ __forceinline__ void s3_set_pixels(tb_sim3_obs_row& r, const tb_keypo
     r.u2 = k2.x; r.v2 = k2.y;
 }
 
+/* win[q] (LDS, one int per query key below n) = the index of the last match in list order that counts for key q, or -1: the row
+ * rule's selection, stated once for the row kernel and for the search query's prep. Every thread of the 256 calls it; it ends on a
+ * barrier. */
+__device__ __forceinline__ void s3_row_winners(int* win, int n, const tb_match* __restrict__ M, int nm, int nk, const uint8_t* __restrict__ V1,
+                                               const uint8_t* __restrict__ V2) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n; i += 256) win[i] = -1;
+    __syncthreads();
+    for (int k = tid; k < nm; k += 256) {
+        const int q = M[k].queryIdx, tr = M[k].trainIdx;
+        if (q >= 0 && q < n && tr >= 0 && tr < nk && V2[tr] && V1[q]) atomicMax(&win[q], k);
+    }
+    __syncthreads();
+}
+
+/* the frame s * cap + slot of pair c and its keyframe id, or -1, -1 where the slot is no candidate */
+__device__ __forceinline__ void s3_pair_frame(int c, int ncand, int cap, const int32_t* __restrict__ cand_slot, const int32_t* __restrict__ kf_ids,
+                                              int& f, int& kf) {
+    const int s = c / ncand, slot = cand_slot[c];
+    f = -1; kf = -1;
+    if (slot >= 0 && slot < cap) {
+        kf = kf_ids[(size_t)s * cap + slot];
+        if (kf >= 0) f = s * cap + slot; else kf = -1;
+    }
+}
+
 template <typename Row>
 __global__ void __launch_bounds__(256)
 k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int32_t* __restrict__ kf_ids, const tb_keypoint* __restrict__ q_keys,
@@ -640,12 +666,9 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
     extern __shared__ int win[];   /* [q_pitch] */
     __shared__ int wsum[4];
     const int c = blockIdx.x, tid = threadIdx.x;
-    const int s = c / ncand, slot = cand_slot[c];
-    int f = -1, kf = -1;
-    if (slot >= 0 && slot < cap) {
-        kf = kf_ids[(size_t)s * cap + slot];
-        if (kf >= 0) f = s * cap + slot; else kf = -1;
-    }
+    const int s = c / ncand;
+    int f, kf;
+    s3_pair_frame(c, ncand, cap, cand_slot, kf_ids, f, kf);
     if (f < 0) {
         if (tid == 0) { row_counts[c] = 0; cand_kf[c] = -1; if (rows_out) rows_out[c] = 0; }
         return;
@@ -663,13 +686,7 @@ k_sim3_rows(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int
     const uint8_t* V2 = kf_valid + (size_t)f * pitch;
     const float* T2 = kf_Tcw + 16 * (size_t)f;
     Row* O = rows + (size_t)c * pitch;
-    for (int i = tid; i < n; i += 256) win[i] = -1;
-    __syncthreads();
-    for (int k = tid; k < nm; k += 256) {
-        const int q = M[k].queryIdx, tr = M[k].trainIdx;
-        if (q >= 0 && q < n && tr >= 0 && tr < nk && V2[tr] && V1[q]) atomicMax(&win[q], k);
-    }
-    __syncthreads();
+    s3_row_winners(win, n, M, nm, nk, V1, V2);
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
@@ -729,6 +746,147 @@ k_sim3_select(int nseq, int ncand, int min_consensus, const int32_t* __restrict_
     if (keep_kf) keep_kf[s] = best >= 0 ? cand_kf[cb] : -1;
     if (keep_srt)
         for (int i = 0; i < 8; i++) keep_srt[8 * (size_t)s + i] = best >= 0 ? cand_srt[8 * cb + i] : ((i == 0 || i == 7) ? 1.0 : 0.0);
+}
+
+/* ---- the keyframe store's SearchBySim3 query (tb_kf_store_sim3_search_dev) around the operator of k_sim3_search.hip.
+ * k_sim3_search_prep, pair c = s * ncand + r (one workgroup each): the pair is skipped (skip[c] = 1) without a candidate or with a
+ * consensus below 3; otherwise the camera points of EVERY key of both sides, formed as k_sim3_rows forms X1 and X2, and the
+ * `already matched` bytes: the rows of the Sim(3) query's list are walked again by the row rule (row `at` of the list belongs to
+ * the at-th key with a winner), and where the RANSAC's mask of that row is 1 the query key and the stored key are matched and
+ * wink[i] keeps the index of the row's match in the verification's list, for the merge. The operator reads the query frame at
+ * fr1[c] = s and the stored keyframe at fr2[c] = s * cap + slot, in place. */
+__global__ void __launch_bounds__(256)
+k_sim3_search_prep(int ncand, int cap, const int32_t* __restrict__ cand_slot, const int32_t* __restrict__ kf_ids, const int32_t* __restrict__ q_counts,
+                   const float* __restrict__ q_mp, const uint8_t* __restrict__ q_valid, int q_pitch, const float* __restrict__ q_Tcw,
+                   const tb_match* __restrict__ matches, const int32_t* __restrict__ match_counts, const float* __restrict__ kf_mp,
+                   const uint8_t* __restrict__ kf_valid, const int32_t* __restrict__ kf_counts, const float* __restrict__ kf_Tcw, int pitch,
+                   const int32_t* __restrict__ cand_consensus, const uint8_t* __restrict__ inlier, float* __restrict__ pts1,
+                   float* __restrict__ pts2, uint8_t* __restrict__ m1, uint8_t* __restrict__ m2, int32_t* __restrict__ wink,
+                   int32_t* __restrict__ skip, int32_t* __restrict__ fr1, int32_t* __restrict__ fr2) {
+    extern __shared__ int win[];   /* [q_pitch] */
+    __shared__ int wsum[4];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int s = c / ncand;
+    int f, kf;
+    s3_pair_frame(c, ncand, cap, cand_slot, kf_ids, f, kf);
+    const bool skipped = f < 0 || cand_consensus[c] < 3;
+    if (tid == 0) { skip[c] = skipped ? 1 : 0; fr1[c] = s; fr2[c] = f < 0 ? 0 : f; }
+    uint8_t* M1 = m1 + (size_t)c * q_pitch;
+    uint8_t* M2 = m2 + (size_t)c * pitch;
+    int32_t* W = wink + (size_t)c * q_pitch;
+    for (int i = tid; i < q_pitch; i += 256) { M1[i] = 0; W[i] = -1; }
+    for (int j = tid; j < pitch; j += 256) M2[j] = 0;
+    if (skipped) return;
+    const int n = min(max(q_counts[s], 0), q_pitch);
+    const int nm = min(max(match_counts[c], 0), pitch);
+    const int nk = min(max(kf_counts[f], 0), pitch);
+    const float* MP1 = q_mp + 3 * (size_t)s * q_pitch;
+    const uint8_t* V1 = q_valid + (size_t)s * q_pitch;
+    const float* T1 = q_Tcw + 16 * (size_t)s;
+    const tb_match* M = matches + (size_t)c * pitch;
+    const float* MP2 = kf_mp + 3 * (size_t)f * pitch;
+    const uint8_t* V2 = kf_valid + (size_t)f * pitch;
+    const float* T2 = kf_Tcw + 16 * (size_t)f;
+    const uint8_t* I = inlier + (size_t)c * pitch;
+    float* P1 = pts1 + 3 * (size_t)c * q_pitch;
+    float* P2 = pts2 + 3 * (size_t)c * pitch;
+    for (int i = tid; i < n; i += 256) {
+        const float a0 = MP1[3 * i], a1 = MP1[3 * i + 1], a2 = MP1[3 * i + 2];
+        P1[3 * i] = s3_apply(T1, 0, a0, a1, a2); P1[3 * i + 1] = s3_apply(T1, 1, a0, a1, a2); P1[3 * i + 2] = s3_apply(T1, 2, a0, a1, a2);
+    }
+    for (int j = tid; j < nk; j += 256) {
+        const float b0 = MP2[3 * j], b1 = MP2[3 * j + 1], b2 = MP2[3 * j + 2];
+        P2[3 * j] = s3_apply(T2, 0, b0, b1, b2); P2[3 * j + 1] = s3_apply(T2, 1, b0, b1, b2); P2[3 * j + 2] = s3_apply(T2, 2, b0, b1, b2);
+    }
+    s3_row_winners(win, n, M, nm, nk, V1, V2);   /* its barriers also order the zeroes above before the ones below */
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const int k = i < n ? win[i] : -1;
+        const int at = tb_block_ordered_slot(k >= 0, base, wsum);
+        if (k >= 0 && I[at]) { M1[i] = 1; M2[M[k].trainIdx] = 1; W[i] = k; }
+    }
+}
+
+/* Pair c (one workgroup each), after the operator: the widened match list -- in ascending query key i the match of the RANSAC-inlier
+ * row of i (wink[i], copied from the verification's list as it stands) or the new pair of i (the operator's list is in ascending i
+ * and, at cap = pitch, never truncated: the n-th new key owns its n-th entry), one entry a key. A skipped pair has none. */
+__global__ void __launch_bounds__(256)
+k_sim3_search_merge(int ncand, const int32_t* __restrict__ q_counts, int q_pitch, int pitch, const tb_match* __restrict__ matches,
+                    const int32_t* __restrict__ wink, const int32_t* __restrict__ skip, const int32_t* __restrict__ match1,
+                    const int32_t* __restrict__ match2, const tb_match* __restrict__ pairs, tb_match* __restrict__ wide,
+                    int32_t* __restrict__ wide_counts) {
+    __shared__ int wsum[4];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int n = skip[c] ? 0 : min(max(q_counts[c / ncand], 0), q_pitch);
+    const tb_match* M = matches + (size_t)c * pitch;
+    const tb_match* P = pairs + (size_t)c * pitch;
+    const int32_t* W = wink + (size_t)c * q_pitch;
+    const int32_t* A = match1 + (size_t)c * q_pitch;
+    const int32_t* B = match2 + (size_t)c * pitch;
+    tb_match* O = wide + (size_t)c * pitch;
+    int fresh = 0, all = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        int k = -1;
+        bool isnew = false;
+        if (i < n) {
+            k = W[i];
+            if (k < 0) { const int j = A[i]; isnew = j >= 0 && j < pitch && B[j] == i; }
+        }
+        const int pn = tb_block_ordered_slot(isnew, fresh, wsum);
+        const int at = tb_block_ordered_slot(k >= 0 || isnew, all, wsum);
+        if (k >= 0) O[at] = M[k];            /* at <= i < q_pitch <= pitch */
+        else if (isnew) O[at] = P[pn];
+    }
+    if (tid == 0) wide_counts[c] = all;
+}
+
+/* Per sequence (one 64-thread workgroup each): the per-candidate counts to the caller, and those of the candidate the Sim(3) query
+ * selected, by its rule (rank -1, or min_consensus < 0 = it selected nothing: zeros) */
+__global__ void __launch_bounds__(64)
+k_sim3_search_select(int ncand, int min_consensus, const int32_t* __restrict__ cand_kf, const int32_t* __restrict__ cand_consensus,
+                     const int32_t* __restrict__ new_counts, const int32_t* __restrict__ wide_counts, const int32_t* __restrict__ stats,
+                     int32_t* __restrict__ o_new, int32_t* __restrict__ o_total, int32_t* __restrict__ o_stats, int32_t* __restrict__ b_new,
+                     int32_t* __restrict__ b_total) {
+    const int s = blockIdx.x;
+    for (int r = threadIdx.x; r < ncand; r += 64) {
+        const size_t c = (size_t)s * ncand + r;
+        if (o_new) o_new[c] = new_counts[c];
+        if (o_total) o_total[c] = wide_counts[c];
+        if (o_stats) for (int i = 0; i < 8; i++) o_stats[8 * c + i] = stats[8 * c + i];
+    }
+    if (threadIdx.x != 0 || (!b_new && !b_total)) return;
+    const int best = min_consensus < 0 ? -1 : s3_select_rank(ncand, min_consensus, cand_kf, cand_consensus, s);
+    const size_t cb = (size_t)s * ncand + (best >= 0 ? best : 0);
+    if (b_new) b_new[s] = best >= 0 ? new_counts[cb] : 0;
+    if (b_total) b_total[s] = best >= 0 ? wide_counts[cb] : 0;
+}
+
+int tbk_sim3_search_prep(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids,
+                         const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch, const float* d_q_Tcw,
+                         const tb_match* d_matches, const int32_t* d_match_counts, const float* d_kf_mp, const uint8_t* d_kf_valid,
+                         const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch, const int32_t* d_cand_consensus, const uint8_t* d_inlier,
+                         float* d_pts1, float* d_pts2, uint8_t* d_m1, uint8_t* d_m2, int32_t* d_wink, int32_t* d_skip, int32_t* d_fr1,
+                         int32_t* d_fr2) {
+    if (npairs <= 0) return TB_OK;
+    return tb_launch(ctx, "k_sim3_search_prep", k_sim3_search_prep, dim3(npairs), dim3(256), (size_t)q_pitch * sizeof(int), ncand, cap, d_cand_slot,
+                     d_kf_ids, d_q_counts, d_q_mp, d_q_valid, q_pitch, d_q_Tcw, d_matches, d_match_counts, d_kf_mp, d_kf_valid, d_kf_counts,
+                     d_kf_Tcw, pitch, d_cand_consensus, d_inlier, d_pts1, d_pts2, d_m1, d_m2, d_wink, d_skip, d_fr1, d_fr2);
+}
+
+int tbk_sim3_search_merge(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_q_counts, int q_pitch, int pitch,
+                          const tb_match* d_matches, const int32_t* d_wink, const int32_t* d_skip, const int32_t* d_match1,
+                          const int32_t* d_match2, const tb_match* d_pairs, const int32_t* d_new_counts, const int32_t* d_stats,
+                          const int32_t* d_cand_kf, const int32_t* d_cand_consensus, tb_match* d_wide, int32_t* d_wide_counts, int32_t* o_new,
+                          int32_t* o_total, int32_t* o_stats, int32_t* b_new, int32_t* b_total) {
+    const int npairs = nseq * ncand;
+    if (npairs <= 0) return TB_OK;
+    TB_TRY(tb_launch(ctx, "k_sim3_search_merge", k_sim3_search_merge, dim3(npairs), dim3(256), 0, ncand, d_q_counts, q_pitch, pitch, d_matches,
+                     d_wink, d_skip, d_match1, d_match2, d_pairs, d_wide, d_wide_counts));
+    if (!o_new && !o_total && !o_stats && !b_new && !b_total) return TB_OK;
+    return tb_launch(ctx, "k_sim3_search_select", k_sim3_search_select, dim3(nseq), dim3(64), 0, ncand, min_consensus, d_cand_kf, d_cand_consensus,
+                     d_new_counts, d_wide_counts, d_stats, o_new, o_total, o_stats, b_new, b_total);
 }
 
 int tbk_sim3_batch(tb_ctx* ctx, int nproblems, const double K[4], const tb_sim3_row* d_rows, const int32_t* d_counts, int pitch, int hypotheses,

@@ -1466,6 +1466,7 @@ int tb_kf_store_clear(tb_kf_store* st) {
     st->nadded = 0;
     st->s3_best = false;   /* a winner of the ring that was: tb_kf_store_sim3_graph_dev needs a new Sim(3) query */
     st->s3_done = false;   /* and so does tb_kf_store_sim3_refine_dev */
+    st->w3_use = false;    /* the widened lists of a search belong to the ring that was */
     return TB_OK;
 }
 
@@ -1682,6 +1683,7 @@ int tb_relocalize_batch_dev(tb_kf_store* st, const double K[4], int nlevels, flo
         TB_HIP(ctx, hipMemcpyAsync(st->mcounts, mcounts, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     st->reloc_done = true;   /* the match lists are filled, pair-major at this ncand: tb_kf_store_sim3_dev may read them */
     st->s3_done = false;     /* and they are no longer those the last Sim(3) query's masks and seeds belong to: no refinement on them */
+    st->w3_use = false;      /* nor on the widened lists a search made of them */
     st->reloc_ncand = ncand;
     if (!o.best_rank && !o.best_kf && !o.best_Tcw) return TB_OK;
     return tbk_reloc_select(ctx, st->nseq, ncand, prm->min_inliers, ckf, ninl, pose, o.best_rank, o.best_kf, o.best_Tcw);
@@ -1731,6 +1733,7 @@ int tb_kf_store_sim3_dev(tb_kf_store* st, const double K[4], int nlevels, float 
                           cons, st->s3_mask, nullptr, o.cand_flags ? o.cand_flags : st->s3_flags));
     st->s3_best = false;   /* tb_kf_store_sim3_graph_dev needs the winner this call selects, if it selects one */
     st->s3_done = true;    /* tb_kf_store_sim3_refine_dev may run; it is told where cand_srt and cand_consensus went */
+    st->w3_use = false;    /* on this query's masks, not on the widened lists an earlier search left */
     st->s3_own_srt = !o.cand_srt;
     st->s3_own_cons = !o.cand_consensus;
     st->s3_min_cons = -1;
@@ -1785,12 +1788,19 @@ int tb_kf_store_sim3_refine_dev(tb_kf_store* st, const double K[4], int nlevels,
     const int pairs = st->nseq * ncand;
     const double* seeds = cand_srt ? cand_srt : st->s3_srt;
     const int32_t* cons = cand_consensus ? cand_consensus : st->s3_cons;
+    /* after a search with use_for_refine: the widened lists through the same row kernel, every row active (ORB-SLAM hands
+     * OptimizeSim3 the RANSAC's inliers and SearchBySim3's pairs) */
+    const bool wide = st->w3_use;
+    if (wide && q_pitch != st->w3_qpitch)
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_refine_dev: query pitch %d, but the search whose lists it refines ran with %d", q_pitch,
+                       st->w3_qpitch);
     TB_TRY(tbk_sim3_obs_rows(ctx, pairs, ncand, st->cap, cand_slot, st->kf_ids, q_keys, q_counts, q_map_points, q_mp_valid, q_pitch, q_Tcw,
-                             st->matches, st->mcounts, st->keys, st->mp, st->valid, st->counts, st->Tcw, st->pitch, inv_sigma2, nlevels, st->o3_rows,
-                             st->o3_cnt, st->o3_kf));
+                             wide ? st->w3_wide : st->matches, wide ? st->w3_wcnt : st->mcounts, st->keys, st->mp, st->valid, st->counts, st->Tcw,
+                             st->pitch, inv_sigma2, nlevels, st->o3_rows, st->o3_cnt, st->o3_kf));
     TB_TRY(tbk_sim3_refine_prep(ctx, pairs, st->o3_kf, cons, seeds, st->o3_cnt, st->o3_run, st->o3_seed));
-    TB_TRY(tbk_sim3_opt_batch(ctx, pairs, K, st->o3_rows, st->o3_run, st->pitch, st->s3_mask, st->o3_seed, prm, st->o3_srt, st->o3_S12, st->o3_inl,
-                              st->o3_mask, st->o3_stats));
+    TB_TRY(tbk_sim3_opt_batch(ctx, pairs, K, st->o3_rows, st->o3_run, st->pitch, wide ? st->w3_ones : st->s3_mask, st->o3_seed, prm, st->o3_srt,
+                              st->o3_S12, st->o3_inl, st->o3_mask, st->o3_stats));
+    st->o3_wide = wide;
     return tbk_sim3_refine_select(ctx, st->nseq, ncand, st->s3_best ? st->s3_min_cons : -1, min_inliers, use_for_graph, st->o3_kf, cons, st->o3_srt,
                                   st->o3_S12, st->o3_inl, st->o3_stats, o.cand_srt, o.cand_S12, o.cand_inliers, o.cand_stats, o.best_srt,
                                   o.best_S12, o.best_inliers, o.best_stats, st->s3_best_srt);
@@ -1802,8 +1812,89 @@ int tb_kf_store_sim3_refine_state_dev(tb_kf_store* st, const tb_sim3_obs_row** r
     if (!st->o3_ready) return tb_fail(st->ctx, TB_ESTATE, "tb_kf_store_sim3_refine_state_dev: before the first tb_kf_store_sim3_refine_dev");
     if (rows) *rows = st->o3_rows;
     if (row_counts) *row_counts = st->o3_cnt;
-    if (active) *active = st->s3_mask;
+    if (active) *active = st->o3_wide ? st->w3_ones : st->s3_mask;
     if (inlier) *inlier = st->o3_mask;
+    return TB_OK;
+}
+
+int tb_kf_store_sim3_search_dev(tb_kf_store* st, const double K[4], int width, int height, int nlevels, float scale, const tb_keypoint* q_keys,
+                                const uint8_t* q_desc, const int32_t* q_counts, const float* q_map_points, const uint8_t* q_mp_valid, int q_pitch,
+                                const float* q_Tcw, const int32_t* cand_slot, int ncand, const double* cand_srt, const int32_t* cand_consensus,
+                                float th, int th_high, int use_for_refine, const tb_sim3_search_out* out) {
+    TB_ENTER((st ? st->ctx : nullptr));
+    if (!st) return TB_EINVAL;
+    tb_ctx* ctx = st->ctx;
+    if (!K || !q_desc || !q_map_points || !q_mp_valid || !q_Tcw || !(th > 0.f) || !std::isfinite(th) || th_high < 0 || th_high > 256 ||
+        width < 1 || height < 1 || !(scale > 0.f) || (use_for_refine != 0 && use_for_refine != 1) || !(K[0] > 0.0) || !(K[1] > 0.0) ||
+        !std::isfinite(K[0]) || !std::isfinite(K[1]) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_search_dev: null arguments, th (positive), th_high %d (0..256), image %d x %d, scale "
+                                       "(positive), use_for_refine %d (0, 1) or K", th_high, width, height, use_for_refine);
+    float inv_sigma2[TB_MAX_LEVELS];
+    int rc;
+    if ((rc = reloc_check(st, "tb_kf_store_sim3_search_dev", nlevels, scale, q_keys, q_counts, q_pitch, cand_slot, ncand, inv_sigma2))) return rc;
+    if (!st->s3_ready || !st->s3_done || !st->reloc_done)
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_search_dev: no tb_kf_store_sim3_dev since the store was made or cleared or the last verification");
+    if (ncand != st->reloc_ncand)
+        return tb_fail(ctx, TB_EINVAL, "tb_kf_store_sim3_search_dev: ncand %d, but the match lists were filled for %d candidates a sequence", ncand, st->reloc_ncand);
+    if ((!cand_srt && !st->s3_own_srt) || (!cand_consensus && !st->s3_own_cons))
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_search_dev: the Sim(3) query wrote cand_srt / cand_consensus to the caller's buffer: pass it");
+    static const tb_sim3_search_out none = {};
+    const tb_sim3_search_out& o = out ? *out : none;
+    if ((o.best_new || o.best_total) && !st->s3_best)
+        return tb_fail(ctx, TB_ESTATE, "tb_kf_store_sim3_search_dev: the Sim(3) query selected no candidate (it was given no best_* output)");
+    if (!st->w3_ready) {   /* the first call allocates, later ones do not */
+        const size_t pairs = (size_t)st->nseq * st->max_cand, pp = pairs * st->pitch;
+        if (!st->w3_pts1) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_pts1, pp * 3));
+        if (!st->w3_pts2) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_pts2, pp * 3));
+        if (!st->w3_m1) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_m1, pp));
+        if (!st->w3_m2) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_m2, pp));
+        if (!st->w3_ones) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_ones, pp, 1));
+        if (!st->w3_wink) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_wink, pp));
+        if (!st->w3_match1) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_match1, pp, 0xff));
+        if (!st->w3_match2) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_match2, pp, 0xff));
+        if (!st->w3_pairs) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_pairs, pp));
+        if (!st->w3_wide) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_wide, pp));
+        if (!st->w3_pcnt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_pcnt, pairs, 0));
+        if (!st->w3_wcnt) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_wcnt, pairs, 0));
+        if (!st->w3_skip) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_skip, pairs));
+        if (!st->w3_f1) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_f1, pairs));
+        if (!st->w3_f2) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_f2, pairs));
+        if (!st->w3_stats) TB_TRY(tb_dev_alloc(ctx, st->own, &st->w3_stats, pairs * 8));
+        st->w3_ready = true;
+    }
+    const int pairs = st->nseq * ncand;
+    const double* srt = cand_srt ? cand_srt : st->s3_srt;
+    const int32_t* cons = cand_consensus ? cand_consensus : st->s3_cons;
+    float sf[TB_MAX_LEVELS], px[TB_MAX_LEVELS];
+    TB_TRY(tb_scale_factors(nlevels, scale, sf, px, nullptr, nullptr));
+    st->w3_use = false;   /* the lists it referred to are overwritten from here on */
+    TB_TRY(tbk_sim3_search_prep(ctx, pairs, ncand, st->cap, cand_slot, st->kf_ids, q_counts, q_map_points, q_mp_valid, q_pitch, q_Tcw, st->matches,
+                                st->mcounts, st->mp, st->valid, st->counts, st->Tcw, st->pitch, cons, st->s3_mask, st->w3_pts1, st->w3_pts2,
+                                st->w3_m1, st->w3_m2, st->w3_wink, st->w3_skip, st->w3_f1, st->w3_f2));
+    /* side 1 = the query frame s, side 2 = the stored keyframe s * cap + slot, both read where they lie */
+    const tbk_sim3_search_side s1 = {q_keys, q_desc, q_mp_valid, q_counts, st->w3_f1, st->w3_pts1, st->w3_m1, q_pitch};
+    const tbk_sim3_search_side s2 = {st->keys, st->desc, st->valid, st->counts, st->w3_f2, st->w3_pts2, st->w3_m2, st->pitch};
+    TB_TRY(tbk_sim3_search_batch(ctx, pairs, K, width, height, nlevels, px, &s1, &s2, srt, st->w3_skip, th, th_high, st->w3_match1, st->w3_match2,
+                                 st->w3_pairs, st->pitch, st->w3_pcnt, st->w3_stats));
+    TB_TRY(tbk_sim3_search_merge(ctx, st->nseq, ncand, st->s3_best ? st->s3_min_cons : -1, q_counts, q_pitch, st->pitch, st->matches, st->w3_wink,
+                                 st->w3_skip, st->w3_match1, st->w3_match2, st->w3_pairs, st->w3_pcnt, st->w3_stats, st->s3_kf, cons, st->w3_wide,
+                                 st->w3_wcnt, o.cand_new, o.cand_total, o.cand_stats, o.best_new, o.best_total));
+    st->w3_qpitch = q_pitch;
+    st->w3_use = use_for_refine == 1;
+    return TB_OK;
+}
+
+int tb_kf_store_sim3_search_state_dev(tb_kf_store* st, const int32_t** match1, const int32_t** match2, const tb_match** pairs,
+                                      const int32_t** pair_counts, const tb_match** widened, const int32_t** widened_counts, int* q_pitch) {
+    if (!st) return TB_EINVAL;
+    if (!st->w3_ready) return tb_fail(st->ctx, TB_ESTATE, "tb_kf_store_sim3_search_state_dev: before the first tb_kf_store_sim3_search_dev");
+    if (match1) *match1 = st->w3_match1;
+    if (match2) *match2 = st->w3_match2;
+    if (pairs) *pairs = st->w3_pairs;
+    if (pair_counts) *pair_counts = st->w3_pcnt;
+    if (widened) *widened = st->w3_wide;
+    if (widened_counts) *widened_counts = st->w3_wcnt;
+    if (q_pitch) *q_pitch = st->w3_qpitch;
     return TB_OK;
 }
 
@@ -2399,6 +2490,39 @@ int tb_sim3_optimize(tb_ctx* ctx, const double K[4], const tb_sim3_obs_row* rows
     if (stats) memcpy(stats, st, 64);
     if (inliers) *inliers = h;
     return TB_OK;
+}
+
+/* ------------------------------------------------------------------ SearchBySim3 */
+int tb_search_by_sim3_batch_dev(tb_ctx* ctx, int npairs, const double K[4], int width, int height, int nlevels, float scale,
+                                const tb_keypoint* keys1, const uint8_t* desc1, const float* points1, const uint8_t* valid1,
+                                const uint8_t* matched1, const int32_t* counts1, int pitch1, const tb_keypoint* keys2, const uint8_t* desc2,
+                                const float* points2, const uint8_t* valid2, const uint8_t* matched2, const int32_t* counts2, int pitch2,
+                                const double* srt, float th, int th_high, int32_t* match1, int32_t* match2, tb_match* pairs, int cap,
+                                int32_t* pair_counts, int32_t* stats) {
+    TB_ENTER(ctx);
+    if (!ctx) return TB_EINVAL;
+    if (npairs < 0 || !K || !keys1 || !desc1 || !points1 || !valid1 || !matched1 || !counts1 || !keys2 || !desc2 || !points2 || !valid2 ||
+        !matched2 || !counts2 || !srt || pitch1 < 1 || pitch1 > 8192 || pitch2 < 1 || pitch2 > 8192 || nlevels < 1 || nlevels > TB_MAX_LEVELS ||
+        !(th > 0.f) || !std::isfinite(th) || th_high < 0 || th_high > 256 || width < 1 || height < 1 || cap < 0 || (pairs && cap < 1) ||
+        !(scale > 0.f) || !std::isfinite(scale) || !(K[0] > 0.0) || !(K[1] > 0.0) || !std::isfinite(K[0]) || !std::isfinite(K[1]) ||
+        !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return tb_fail(ctx, TB_EINVAL, "tb_search_by_sim3_batch_dev: null inputs, pitches %d, %d (1..8192), %d levels (1..%d), th (positive), "
+                                       "th_high %d (0..256), image %d x %d, cap %d, scale (positive) or K", pitch1, pitch2, nlevels, TB_MAX_LEVELS,
+                       th_high, width, height, cap);
+    if (npairs > 65535) return tb_fail(ctx, TB_EUNSUPPORTED, "tb_search_by_sim3_batch_dev: %d pairs (at most 65535 per call)", npairs);
+    if (npairs == 0) return TB_OK;
+    float sf[TB_MAX_LEVELS], px[TB_MAX_LEVELS];
+    TB_TRY(tb_scale_factors(nlevels, scale, sf, px, nullptr, nullptr));
+    if (!match1 || !match2) {   /* the agreement pass needs both directions' lists: the caller's, or work */
+        void* w;
+        TB_TRY(tb_scratch(ctx, TB_SLOT_WORK, (size_t)npairs * ((size_t)pitch1 + pitch2) * sizeof(int32_t), &w));
+        if (!match1) match1 = (int32_t*)w;
+        if (!match2) match2 = (int32_t*)w + (size_t)npairs * pitch1;
+    }
+    const tbk_sim3_search_side s1 = {keys1, desc1, valid1, counts1, nullptr, points1, matched1, pitch1};
+    const tbk_sim3_search_side s2 = {keys2, desc2, valid2, counts2, nullptr, points2, matched2, pitch2};
+    return tbk_sim3_search_batch(ctx, npairs, K, width, height, nlevels, px, &s1, &s2, srt, nullptr, th, th_high, match1, match2, pairs, cap,
+                                 pair_counts, stats);
 }
 
 /* ------------------------------------------------------------------ two-view initialisation */

@@ -310,6 +310,18 @@ struct tb_kf_store {
     int32_t *o3_cnt = nullptr, *o3_kf = nullptr, *o3_run = nullptr, *o3_inl = nullptr;   /* [pairs] */
     double *o3_seed = nullptr, *o3_srt = nullptr, *o3_stats = nullptr;                   /* [pairs][8] */
     float* o3_S12 = nullptr;                                 /* [pairs][16] */
+    /* the SearchBySim3 query (tb_kf_store_sim3_search_dev), allocated by its first call: the operator's inputs the prep forms, its
+     * outputs and the widened lists. w3_use: the last search asked for use_for_refine and no verification, Sim(3) query or clear came
+     * since: the next refinement builds its rows from w3_wide and starts with every row active (w3_ones, all 1, never written
+     * again); w3_qpitch: that search's query pitch, the row pitch of w3_match1. o3_wide: the last refinement did so */
+    bool w3_ready = false, w3_use = false, o3_wide = false;
+    int w3_qpitch = 0;
+    float *w3_pts1 = nullptr, *w3_pts2 = nullptr;            /* [pairs][pitch][3] */
+    uint8_t *w3_m1 = nullptr, *w3_m2 = nullptr, *w3_ones = nullptr;   /* [pairs][pitch] */
+    int32_t *w3_wink = nullptr, *w3_match1 = nullptr, *w3_match2 = nullptr;   /* [pairs][pitch] */
+    tb_match *w3_pairs = nullptr, *w3_wide = nullptr;        /* [pairs][pitch] */
+    int32_t *w3_pcnt = nullptr, *w3_wcnt = nullptr, *w3_skip = nullptr, *w3_f1 = nullptr, *w3_f2 = nullptr;   /* [pairs] */
+    int32_t* w3_stats = nullptr;                             /* [pairs][8] */
     /* the Sim(3) graph query (tb_kf_store_sim3_graph_dev): the store's own copy of the last Sim(3) query's best_kf / best_srt (the
      * caller's are nullable and may be gone by then; s3_best: that query selected a winner into them), and the graph's buffers,
      * allocated with the solver's plan by the first graph query; nn = cap + 1 */
@@ -615,6 +627,33 @@ static inline bool tb_sim3_params_ok(const tb_sim3_params* prm) {
     return prm->hypotheses >= 1 && prm->hypotheses <= 1024 && (prm->fixed_scale == 0 || prm->fixed_scale == 1) && prm->chi2_max >= 0.0 &&
            std::isfinite(prm->chi2_max);
 }
+/* SearchBySim3 (k_sim3_search.hip): guided mutual matching of the two sides of every pair under its similarity. A side's keys,
+ * descriptors, validity bytes and counts are read at frame[p] (nullptr: p) of their arrays, so a caller that keeps frames in a ring
+ * reads them where they lie; its camera points and `already matched` bytes are per pair. d_skip (nullable): a non-zero entry skips
+ * the pair (match -1, no pairs, stats flag 2). level_px[l]: the size of a level-l pixel in level-0 pixels (tb_scale_factors'
+ * inv_sf). d_match1 / d_match2 are work AND output and not nullable here; d_pairs, d_pair_counts and d_stats are nullable. */
+struct tbk_sim3_search_side {
+    const tb_keypoint* keys; const uint8_t* desc; const uint8_t* valid; const int32_t* counts; const int32_t* frame;
+    const float* points; const uint8_t* matched; int pitch;
+};
+int tbk_sim3_search_batch(tb_ctx* ctx, int npairs, const double K[4], int width, int height, int nlevels, const float* level_px,
+                          const tbk_sim3_search_side* s1, const tbk_sim3_search_side* s2, const double* d_srt, const int32_t* d_skip,
+                          float th, int th_high, int32_t* d_match1, int32_t* d_match2, tb_match* d_pairs, int cap, int32_t* d_pair_counts,
+                          int32_t* d_stats);
+/* the store's query around it (k_sim3.hip, beside the row kernel whose rule they walk): prep = skip flags, frame indices, the camera
+ * points of both sides and the `already matched` bytes from the Sim(3) query's masks; merge = the widened match lists, then the
+ * per-candidate counts to the caller and those of the selected candidate (min_consensus < 0: none was selected) */
+int tbk_sim3_search_prep(tb_ctx* ctx, int npairs, int ncand, int cap, const int32_t* d_cand_slot, const int32_t* d_kf_ids,
+                         const int32_t* d_q_counts, const float* d_q_mp, const uint8_t* d_q_valid, int q_pitch, const float* d_q_Tcw,
+                         const tb_match* d_matches, const int32_t* d_match_counts, const float* d_kf_mp, const uint8_t* d_kf_valid,
+                         const int32_t* d_kf_counts, const float* d_kf_Tcw, int pitch, const int32_t* d_cand_consensus, const uint8_t* d_inlier,
+                         float* d_pts1, float* d_pts2, uint8_t* d_m1, uint8_t* d_m2, int32_t* d_wink, int32_t* d_skip, int32_t* d_fr1,
+                         int32_t* d_fr2);
+int tbk_sim3_search_merge(tb_ctx* ctx, int nseq, int ncand, int min_consensus, const int32_t* d_q_counts, int q_pitch, int pitch,
+                          const tb_match* d_matches, const int32_t* d_wink, const int32_t* d_skip, const int32_t* d_match1,
+                          const int32_t* d_match2, const tb_match* d_pairs, const int32_t* d_new_counts, const int32_t* d_stats,
+                          const int32_t* d_cand_kf, const int32_t* d_cand_consensus, tb_match* d_wide, int32_t* d_wide_counts, int32_t* o_new,
+                          int32_t* o_total, int32_t* o_stats, int32_t* b_new, int32_t* b_total);
 /* two-view initialisation (k_two_view.hip): one workgroup per problem, no work buffer; every output nullable; pitch <= 2048 */
 int tbk_two_view(tb_ctx* ctx, int nproblems, const float* d_xy0, const float* d_xy1, const int32_t* d_counts, const uint8_t* d_skip,
                  const float* d_inv_sigma2_0, const float* d_inv_sigma2_1, int pitch, const double K[4], const float* d_Tcw0,

@@ -1216,6 +1216,22 @@ int tb_vo_refine_sim3_dev(tb_vo* vo, int topk, const double* cand_srt, const int
                                        vo->Tcw[c], vo->s3_slot, vo->s3_topk, cand_srt, cand_consensus, prm, min_inliers, use_for_graph, out);
 }
 
+int tb_vo_search_sim3_dev(tb_vo* vo, int topk, const double* cand_srt, const int32_t* cand_consensus, float th, int th_high, int use_for_refine,
+                          const tb_sim3_search_out* out) {
+    TB_ENTER((vo ? vo->ctx : nullptr));
+    if (!vo) return TB_EINVAL;
+    tb_ctx* ctx = vo->ctx;
+    if (!vo->store) return tb_fail(ctx, TB_ESTATE, "tb_vo_search_sim3_dev: relocalisation is not enabled (tb_vo_reloc_enable)");
+    if (!vo->s3_done || !vo->s3_slot) return tb_fail(ctx, TB_ESTATE, "tb_vo_search_sim3_dev: no tb_vo_relocalize_sim3_dev since the last step");
+    if (topk != vo->s3_topk)   /* the inputs and outputs are [nseq][topk]: a caller that sized them for another count must not be read or written past */
+        return tb_fail(ctx, TB_EINVAL, "tb_vo_search_sim3_dev: topk %d, but the last tb_vo_relocalize_dev ran with %d", topk, vo->s3_topk);
+    const tb_vo_frame_out& o = vo->out[vo->oc];
+    const int c = vo->cur;
+    return tb_kf_store_sim3_search_dev(vo->store, vo->p.K, vo->p.width, vo->p.height, vo->p.nlevels, vo->p.scale, o.orb, o.orb_desc, o.orb_cnt,
+                                       vo->mp[c], vo->valid[c], vo->P, vo->Tcw[c], vo->s3_slot, vo->s3_topk, cand_srt, cand_consensus, th, th_high,
+                                       use_for_refine, out);
+}
+
 int tb_vo_loop_sim3_dev(tb_vo* vo, int iters, int fixed_scale, double w_rot, double w_trans, double w_scale, tb_sim3_graph_out* out) {
     TB_ENTER((vo ? vo->ctx : nullptr));
     if (!vo) return TB_EINVAL;

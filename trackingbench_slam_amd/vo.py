@@ -638,6 +638,29 @@ class StereoVO:
             t.record_stream(self.stream)
         return out
 
+    def search_sim3(self, th=7.5, th_high=100, use_for_refine=True, srt=None):
+        """After relocalize_sim3(...): ORB-SLAM's SearchBySim3 on every candidate -- each frame's points are taken through the
+        candidate's similarity into the other frame, a scale-dependent window there is searched by Hamming distance (th: the window in
+        level pixels, th_high: the largest distance accepted) and the pairs on which both directions agree join the RANSAC's inliers.
+        Device tensors: new [S] and total [S] of the candidate relocalize_sim3 selected (0 when none), cand_new / cand_total [S, topk]
+        and cand_stats [S, topk, 8] int32 (tried, searched 1 -> 2; tried, searched 2 -> 1; accepted 1 -> 2, 2 -> 1; new pairs; flag,
+        2 = skipped). srt [S, topk, 8]: search under these transforms (a refine_sim3's cand_srt) in place of relocalize_sim3's.
+        use_for_refine=True: the next refine_sim3 runs on the widened lists, every row active; otherwise no state changes. A query of
+        the loop: it ends in the same bytes whether or not this is called. No host synchronisation."""
+        self._need_store()
+        if getattr(self, "_sim3", None) is None:
+            raise capi.TBError(capi.TB_ESTATE, "search_sim3 needs a relocalize_sim3 of this frame")
+        seeds = self._sim3 if srt is None else dict(self._sim3, cand_srt=srt.contiguous())
+        with torch.cuda.stream(self.stream):
+            rc, out = self.vo.search_sim3_dev(self.dev, seeds, th=th, th_high=th_high, use_for_refine=bool(use_for_refine))
+            if rc == 0:
+                out["new"], out["total"] = out["best_new"], out["best_total"]
+        self.ctx.check(rc)
+        torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(self.stream)
+        return out
+
     def loop_sim3(self, iters=10, fixed_scale=True, w_rot=1.0, w_trans=1.0, w_scale=1.0):
         """After relocalize_sim3(...): the Sim(3) pose graph of the stored keyframes and the current frame, the Sim(3) winner as the
         loop edge (the node of best_kf -> the frame's node, Z = best_srt), optimised by the device solver. Device tensors, copies:
